@@ -15,6 +15,10 @@ the engine's own RCCL communicator (kt_comm_*: what a Go host links), `--torch-c
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line.  Everything else it can measure or
+check (per-kernel times, roofline, fingerprints and rank agreement, --verify, CPU baseline, latency leg, the extra configs)
+runs only with --full.  --dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -94,6 +98,60 @@ def verify_against_oracle(full_snap, now, rec, throttle_rows, nthreads=None):
             if not np.array_equal(np.asarray(g), np.asarray(w)):
                 bad.append((name, int(t)))
     return bad
+
+
+EXTRA_LEG_MIN_SECONDS = 0.25  # each --full extra leg times at least this long
+DUMP_MAX_POD_ROWS = 2_000_000  # 4 float32 summary fields: at most 32 MB
+DUMP_MAX_THROTTLE_ROWS = 20_000  # at most ~17 MB at D = 16
+DUMP_SEED = 20260101
+
+
+def _dump_rows(n, cap):
+    """Every row when n <= cap, else a fixed seeded sample of `cap` rows (sorted): the same rows from run to run."""
+    import numpy as np
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, rec, summary):
+    """Writes what one step handed back to a caller as float32 / float64 .npy files under `out_dir`: the reconcile result of
+    every throttle row (`rec`, an engine.ReconcileResult) and the PreFilter summary word of every pod row (`summary`).
+    Counts and amounts become float64; bitmask words become [rows, 32] bit planes and the summary word its four fields
+    (verdict and three throttle counts, float32), so that a tolerance comparison cannot hide a flipped low bit.  More rows
+    than DUMP_MAX_*_ROWS are sampled (`pod_rows.npy` / `throttle_rows.npy` name the rows written).  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    bits = lambda a: ((a.astype(np.uint64)[:, None] >> np.arange(32, dtype=np.uint64)) & 1).astype(np.float32)
+    arrays = {}
+    n_thr = rec.used.n
+    t_rows = _dump_rows(n_thr, DUMP_MAX_THROTTLE_ROWS)
+    pick = (lambda a: a[:n_thr]) if t_rows is None else (lambda a: a[t_rows])
+    if t_rows is not None:
+        arrays["throttle_rows"] = t_rows.astype(np.float64)
+    for name, amt in (("used", rec.used), ("calc", rec.calc)):
+        arrays[name + "_v"] = pick(amt.v).astype(np.float64)
+        arrays[name + "_present"] = bits(pick(amt.present))
+        arrays[name + "_count"] = pick(amt.count).astype(np.float64)
+        arrays[name + "_has_count"] = pick(amt.has_count).astype(np.float32)
+    arrays["calc_updated"] = pick(rec.calc_updated).astype(np.float32)
+    arrays["thrl_flag"] = bits(pick(rec.thrl_flag))
+    arrays["thrl_has"] = bits(pick(rec.thrl_has))
+    arrays["thrl_pod"] = pick(rec.thrl_pod).astype(np.float32)
+    arrays["error"] = pick(rec.error).astype(np.float32)
+    summary = np.asarray(summary, dtype=np.uint64)
+    p_rows = _dump_rows(len(summary), DUMP_MAX_POD_ROWS)
+    if p_rows is not None:
+        arrays["pod_rows"] = p_rows.astype(np.float64)
+        summary = summary[p_rows]
+    for name, shift, mask in (("verdict", 0, 0x3), ("n_exceeds", 4, 0xFFFFF), ("n_active", 24, 0xFFFFF),
+                              ("n_insufficient", 44, 0xFFFFF)):  # KT_SUMMARY_* in include/kt_engine.h
+        arrays["summary_" + name] = ((summary >> np.uint64(shift)) & np.uint64(mask)).astype(np.float32)
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        total += a.nbytes
+    return total
 
 
 def extra_leg(index, min_seconds):
@@ -223,14 +281,21 @@ def main():
     ap.add_argument("--sweep", action="store_true",
                     help="one GPU: the step as ONE kt_sweep_launch — PreFilter sweep (against the stored status) and the reconcile scan "
                          "fused into one pass over the pod tables — instead of kt_reconcile_launch + kt_check_launch")
-    ap.add_argument("--min-seconds", type=float, default=0.25,
-                    help="the timed region runs at least this long: --steps is raised (to a multiple of itself) when K steps "
-                         "would take less; the line reports the steps actually timed and the steps requested")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="opt-in: the timed region runs at least this long: --steps is raised (to a multiple of itself) when K "
+                         "steps would take less; the line reports the steps actually timed and the steps requested.  The extra "
+                         "legs of --full run at least max(this, %g) s" % EXTRA_LEG_MIN_SECONDS)
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the extra legs (configs[3] and one configs[4] shard, timed after the headline leg on one GPU)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: fixed rows per GPU (default); strong: the config's total pod count divided over the GPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg also measure and check everything else: per-kernel times and roofline, result "
+                         "fingerprints and rank agreement, CPU baseline, latency leg, extra configs (--verify implies it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; float32 / float64, < 64 MB)")
     args = ap.parse_args()
+    args.full = args.full or args.verify
 
     import numpy as np
     import torch
@@ -364,8 +429,9 @@ def main():
         ev_chk = [torch.cuda.Event(), torch.cuda.Event()]
         step()  # the serial form once: its results are what the overlapped loop has to reproduce bit for bit
         fence()
-        _, ref_summary = eng.check_fetch(per_gpu, False)
-        ref_rec = eng.reconcile_fetch()
+        if args.full:
+            _, ref_summary = eng.check_fetch(per_gpu, False)
+            ref_rec = eng.reconcile_fetch()
         eng.check_atomic(rows=np.zeros(1, np.int64), want_status=False)  # a PreFilter call: switches the double buffer on
         fence()
         n_over = [0]
@@ -386,19 +452,20 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    # A timed region of a millisecond (20 steps of 0.05 ms) rests on one noisy box: the requested K is raised to the multiple
-    # of K that fills --min-seconds, from one untimed calibration pass of K steps (part of the warm-up).  Every rank
-    # takes the same count (MAX over ranks).
+    # --min-seconds S (opt-in): one untimed calibration pass of K steps (part of the warm-up) raises the requested K to the
+    # multiple of K that fills S seconds, so that a timed region of a millisecond (20 steps of 0.05 ms) does not rest on one
+    # noisy box.  Every rank takes the same count (MAX over ranks).  Without it, exactly --steps steps are timed.
     steps_requested = args.steps
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    t_cal = time.perf_counter() - t0
     mult = 1
-    if args.min_seconds > 0 and t_cal < args.min_seconds:
-        mult = int(min(10000, -(-(1.2 * args.min_seconds) // max(t_cal, 1e-6))))  # (20 % margin: the calibration pass is short)
-    if world > 1:
+    if args.min_seconds > 0:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        t_cal = time.perf_counter() - t0
+        if t_cal < args.min_seconds:
+            mult = int(min(10000, -(-(1.2 * args.min_seconds) // max(t_cal, 1e-6))))  # (20 % margin: the calibration pass is short)
+    if world > 1 and args.min_seconds > 0:
         tm = torch.tensor([mult], dtype=torch.int64, device="cuda")
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         mult = int(tm.item())
@@ -419,6 +486,45 @@ def main():
         dist.all_gather(all_t, te)
         rank_ms = [float(t.item()) * 1e3 / args.steps for t in all_t]
         elapsed = max(float(t.item()) for t in all_t)  # MAX over ranks
+    if args.dump_outputs and rank == 0:
+        _, sm_d = eng.check_fetch(per_gpu, False)
+        dump_outputs(args.dump_outputs, eng.reconcile_fetch(), sm_d)
+
+    decisions_per_step = float(P_total) * float(T)
+    ms_per_step = elapsed * 1e3 / args.steps
+    value = decisions_per_step * args.steps / elapsed
+    engine_version = E.version()
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "pod_throttle_decisions_per_sec", "value": value, "unit": "decisions/s", "n_gpus": world,
+            "steps": args.steps, "steps_requested": steps_requested, "timed_region_s": round(elapsed, 6),
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+            "config": {"workload": WORKLOADS[args.config] + (" — throttle count overridden (--throttles): not a BASELINE config" if args.throttles else "")
+                                   + (" — dimensions / labels overridden (--dims / --labels): not a BASELINE config" if args.dims or args.labels else ""),
+                       "pods_total": P_total, "pods_per_gpu": per_gpu,
+                       "throttles": T, "dims": D, "labels_per_pod": L, "namespaces": snap.n_ns,
+                       "step": "sweep(check all pods against the stored status + aggregate, one pass)+finalize(apply)" if args.sweep
+                               else "reconcile(aggregate+allreduce+finalize,apply)+check(all pods)",
+                       "streams": "check(i) on a second stream beside reconcile(i+1); check(i) after finalize(i)" if overlap else "one",
+                       "overlap_identical_to_serial": None, "results_sha1": None,
+                       "kernel_variant": args.variant, "parallelism": f"pods row-sharded x{world}, throttles replicated",
+                       "exchange": "kt_comm (RCCL, native)" if args.native_comm else ("torch.distributed (RCCL)" if world > 1 else "none"),
+                       "native_exchange_error": native_comm_error,
+                       "generate_s": round(t_gen, 2), "load_s": round(t_load, 2), "engine_version": engine_version},
+            "per_rank_ms_per_step": [round(x, 6) for x in rank_ms],
+        }
+    if not args.full:  # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(out))
+        if args.native_comm:
+            eng.comm_destroy()
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     if overlap:
         _, got_summary = eng.check_fetch(per_gpu, False)
         got_rec = eng.reconcile_fetch()
@@ -513,10 +619,6 @@ def main():
         dist.all_gather_object(gathered, {k: round(v, 6) for k, v in k_ms.items()} | {"exchange": None if exchange_ms is None else round(exchange_ms, 6)})
         per_rank_kernel_ms = gathered
 
-    decisions_per_step = float(P_total) * float(T)
-    ms_per_step = elapsed * 1e3 / args.steps
-    value = decisions_per_step * args.steps / elapsed
-
     # ---- roofline of the dominant kernel (per launch, this rank's shard)
     flags = snap.pod_flags[:per_gpu]
     need = S.POD_VALID | S.POD_SCHED_MATCH | S.POD_SCHEDULED
@@ -536,7 +638,6 @@ def main():
     # PMC traffic (FETCH_SIZE x2 + WRITE_SIZE per launch, tools/profile.sh + tools/pmc_summary.py) is only quoted when it
     # was measured on the SAME kernel sources as the library that just ran (kt_version() carries their hash)
     traffic = None
-    engine_version = E.version()
     pmc_path = os.path.join(ROOT, "profiles", "pmc_summary.json")
     pmc_kernels = {}
     pmc_source = None
@@ -697,41 +798,25 @@ def main():
                 if sw["after_pod_event_ms"] > 0 else 0.0}
 
     if rank == 0:
-        out = {
-            "metric": "pod_throttle_decisions_per_sec", "value": value, "unit": "decisions/s", "n_gpus": world,
-            "steps": args.steps, "steps_requested": steps_requested, "timed_region_s": round(elapsed, 6),
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-            "config": {"workload": WORKLOADS[args.config] + (" — throttle count overridden (--throttles): not a BASELINE config" if args.throttles else "")
-                                   + (" — dimensions / labels overridden (--dims / --labels): not a BASELINE config" if args.dims or args.labels else ""),
-                       "pods_total": P_total, "pods_per_gpu": per_gpu,
-                       "throttles": T, "dims": D, "labels_per_pod": L, "namespaces": snap.n_ns,
-                       "step": "sweep(check all pods against the stored status + aggregate, one pass)+finalize(apply)" if args.sweep
-                               else "reconcile(aggregate+allreduce+finalize,apply)+check(all pods)",
-                       "streams": "check(i) on a second stream beside reconcile(i+1); check(i) after finalize(i)" if overlap else "one",
-                       "overlap_identical_to_serial": overlap_identical, "results_sha1": results_sha1,
-                       "kernel_variant": args.variant, "parallelism": f"pods row-sharded x{world}, throttles replicated",
-                       "exchange": "kt_comm (RCCL, native)" if args.native_comm else ("torch.distributed (RCCL)" if world > 1 else "none"),
-                       "native_exchange_error": native_comm_error,
-                       "generate_s": round(t_gen, 2), "load_s": round(t_load, 2), "engine_version": engine_version},
-            "per_rank_ms_per_step": [round(x, 6) for x in rank_ms],
+        out["config"].update({"overlap_identical_to_serial": overlap_identical, "results_sha1": results_sha1})
+        out.update({
             "exchange_ms": None if exchange_ms is None else round(exchange_ms, 6),
             "per_rank_kernel_ms": per_rank_kernel_ms,
             "ranks_agree": agree, "per_rank_hashes": per_rank_hashes, "oracle_verify": oracle_verify,
             "index": index_stats, "partial_words": pending[0], "per_rank_index": per_rank_index,
             "roofline": roofline, "cpu_baseline": cpu_baseline, "latency": latency,
-        }
+        })
     if args.native_comm:
         eng.comm_destroy()
     eng.close()
     if rank == 0:
         # the other single-GPU BASELINE configurations, driver-observed instead of builder-claimed: after the headline leg
-        # (its engine is closed), on this GPU, each for at least --min-seconds
+        # (its engine is closed), on this GPU, each for at least max(--min-seconds, EXTRA_LEG_MIN_SECONDS)
         if world == 1 and not args.no_extra and args.config == 2 and not args.pods_per_gpu and not args.throttles and not args.dims and not args.labels and args.variant == "indexed":
             extra = {}
             for idx, key in ((3, "configs[3]"), (4, "configs[4] shard")):
                 try:
-                    extra[key] = extra_leg(idx, args.min_seconds)
+                    extra[key] = extra_leg(idx, max(args.min_seconds, EXTRA_LEG_MIN_SECONDS))
                 except Exception as ex:  # never lose the headline line over an extra leg
                     extra[key] = {"error": repr(ex)}
             out["extra_configs"] = extra

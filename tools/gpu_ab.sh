@@ -15,7 +15,7 @@ for cfg in $CFGS; do
     so=$REPO/tools/ab/libkt_engine_$base.so
     [ "$base" == "tree" ] && so=$REPO/kube_throttler_amd/csrc/libkt_engine.so
     name=${TAG}_$(echo "$lib" | tr -c 'A-Za-z0-9\n' '_')_cfg${cfg}
-    env $envs KT_ENGINE_LIB=$so timeout 400 python bench.py --config $cfg --steps $steps --warmup 10 --no-cpu-baseline --no-latency --no-extra $EXTRA > $OUT/$name.json 2> $OUT/$name.err
+    env $envs KT_ENGINE_LIB=$so timeout 400 python bench.py --full --config $cfg --steps $steps --warmup 10 --no-cpu-baseline --no-latency --no-extra $EXTRA > $OUT/$name.json 2> $OUT/$name.err
     rc=$?
     python - "$OUT/$name.json" "$lib" "$cfg" "$rc" <<'PY'
 import json, sys

@@ -18,13 +18,13 @@ PY
 }
 for cfg in 2 4 3 1; do
   name=${TAG}_bench_cfg${cfg}
-  timeout 300 python bench.py --config $cfg --steps 200 --warmup 10 --no-cpu-baseline --no-latency --verify > $OUT/$name.json 2> $OUT/$name.err
+  timeout 300 python bench.py --full --config $cfg --steps 200 --warmup 10 --no-cpu-baseline --no-latency --verify > $OUT/$name.json 2> $OUT/$name.err
   echo "bench cfg$cfg: exit $?"; show $OUT/$name.json "cfg$cfg"
 done
-timeout 300 python bench.py --config 2 --pods-per-gpu 4000000 --steps 50 --warmup 5 --no-cpu-baseline --no-latency --verify > $OUT/${TAG}_bench_cfg2_4M.json 2> $OUT/${TAG}_bench_cfg2_4M.err; show $OUT/${TAG}_bench_cfg2_4M.json "cfg2 4M pods"
+timeout 300 python bench.py --full --config 2 --pods-per-gpu 4000000 --steps 50 --warmup 5 --no-cpu-baseline --no-latency --verify > $OUT/${TAG}_bench_cfg2_4M.json 2> $OUT/${TAG}_bench_cfg2_4M.err; show $OUT/${TAG}_bench_cfg2_4M.json "cfg2 4M pods"
 cd /tmp && export TMPDIR=/tmp
 for cfg in 2 4; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_cfg$cfg -- python $REPO/bench.py --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-latency > /dev/null 2> $OUT/${TAG}_prof_cfg$cfg.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_cfg$cfg -- python $REPO/bench.py --full --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-latency > /dev/null 2> $OUT/${TAG}_prof_cfg$cfg.err
   f=$(find $OUT/prof_${TAG}_cfg$cfg -name '*kernel_stats.csv' | head -1)
   echo "kernel stats cfg$cfg:"; python - "$f" <<'PY'
 import csv, sys

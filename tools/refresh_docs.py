@@ -135,5 +135,5 @@ if os.path.exists(q):
             (r"`launch_gaps_ms` −?[0-9.]+", "`launch_gaps_ms` %s" % str(d["roofline"].get("launch_gaps_ms")).replace("-", "−")),
         ])
     else:
-        print("profiles/%s_quoted_bench_cfg2_driver.json was taken on other sources: run `python bench.py --steps 20 --warmup 5` again" % rnd)
+        print("profiles/%s_quoted_bench_cfg2_driver.json was taken on other sources: run `python bench.py --full --steps 20 --warmup 5` again" % rnd)
 print("documents follow profiles/%s_bench_*.json (src=%s)" % (rnd, src))

@@ -12,7 +12,7 @@ cd $REPO
 timeout 900 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_pytest_gpu.log 2>&1; echo "pytest -m gpu: exit $?"; tail -3 $OUT/${TAG}_pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1; echo "smoke: exit $?"; tail -1 $OUT/${TAG}_smoke.log
 for cfg in 2 3 1 4; do
-  timeout 400 python bench.py --config $cfg --steps 50 --warmup 5 > $OUT/${TAG}_bench_cfg${cfg}.json 2> $OUT/${TAG}_bench_cfg${cfg}.err
+  timeout 400 python bench.py --full --config $cfg --steps 50 --warmup 5 > $OUT/${TAG}_bench_cfg${cfg}.json 2> $OUT/${TAG}_bench_cfg${cfg}.err
   echo "bench cfg$cfg: exit $?"; python - <<PY
 import json
 try:
