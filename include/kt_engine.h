@@ -332,7 +332,7 @@ int64_t kt_counter(kt_engine* e, int32_t which);
 /* ---- More resource names than one engine has dimensions (KT_MAX_DIMS): PAGES.  The reference sums and compares any resource
  *      name (pkg/resourcelist/resourcelist.go:27-54, resource_amount.go:127-159).  The host builds the same cluster once per
  *      page of <= KT_MAX_DIMS names — every page engine holds every pod row and every throttle row, with the requests /
- *      thresholds of ITS names — and these two calls run a step on every page and combine the results.  The combination is
+ *      thresholds of ITS names — and these calls run a step on every page and combine the results.  The combination is
  *      exact: every step of CheckThrottledFor (throttle_types.go:128-153) is `count part OR exists a resource name ...`; the
  *      count part needs no name (every page computes it alike) and the name part of the cluster is the OR over the pages:
  *          exceeds <=> some page says exceeds; else active <=> some page says active; else insufficient <=> some page says so;
@@ -350,6 +350,25 @@ int32_t kt_paged_check(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
  * launched page's result has been drained, never with pending reconciles left behind. */
 int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now_s, int32_t now_ns, uint32_t flags, int32_t n,
                            const kt_status* page_out, uint8_t* replaced_any, uint8_t* error_any);
+/* kt_admit_launch over the pages: the queue pod_rows[0..n) (NULL: rows [0, n)) admitted IN ORDER, pod i checked against the
+ * reserved amounts of every page as the pods admitted before it left them, its verdict the combination above over every page,
+ * and on Success ResourceAmountOfPod(pod) added to every affected throttle in every page (each page its own names' amounts; the
+ * pod count in every page).  One kt_check of page 0 (which throttles affect which pod: the selector side is the same in every
+ * page) and ONE kernel (kt_admit_paged: one wave, the selector scan once per pod, the name part of the four steps evaluated
+ * against every page) on page 0's stream.  Synchronous: out_summary [n] and out_status [n][throttle rows] (both nullable)
+ * receive what PreFilter returned for pod i AT ITS TURN, combined over the pages; n_pages == 1 gives exactly
+ * kt_admit_launch + kt_check_fetch.  flags: KT_ADMIT_COMMIT keeps every page's resulting reserved amounts (kt_fetch_reserved
+ * per page); without it the call is a dry run.  Duplicate pods: as for kt_admit_launch, every admitted pod ADDS its amount, so
+ * a pod whose amount is already reserved, or that occurs twice in the queue, must not be in it.
+ * Refused: pages with different throttle-row counts or an engine named twice (KT_ERR_INVALID_ARGUMENT), pages on different
+ * devices or a page whose stored `used` is wider than int64 (KT_ERR_UNSUPPORTED), n x throttle_rows > 2^31
+ * (KT_ERR_OUT_OF_RANGE).  Every page is locked exclusively for the call, in address order.  Ordering: the streams of pages
+ * 1.. are synchronised before the launch (their uploads and earlier kernels have completed; their newest feed kernel is
+ * ordered on the device).  The call uses page 0's check slot (a pending kt_check_launch of page 0 is dropped, as with
+ * kt_affected_pods).  The state of all pages lives in LDS while the sum over the pages of throttle_rows x (8 x n_dims + 16)
+ * plus the list fits 160 KiB, beyond that in HBM on page 0. */
+int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
+                       uint64_t* out_summary, uint8_t* out_status);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

@@ -103,7 +103,7 @@ func (d *Dict) Dim(name string) (int, error) {
 		return i, nil
 	}
 	if len(d.dims) >= 16 {
-		return 0, fmt.Errorf("resource name %q is the 17th of this engine: run one engine per page of 16 names (kt_paged_check / kt_paged_reconcile)", name)
+		return 0, fmt.Errorf("resource name %q is the 17th of this engine: run one engine per page of 16 names (kt_paged_check / kt_paged_reconcile / kt_paged_admit: PagedAdmit)", name)
 	}
 	i := len(d.dims)
 	d.dims[name] = i

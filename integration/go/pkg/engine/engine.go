@@ -331,6 +331,31 @@ func (e *Engine) Admit(rows []int64, onEqual, commit bool) (summary []uint64, st
 	return summary, status[:len(rows)*T], nil
 }
 
+// PagedAdmit is Admit over the pages of a cluster with more than 16 resource names (kt_paged_admit): one engine per page of
+// <= 16 names, pages[0] first; verdicts and status rows are combined over the pages, and with commit every page keeps its
+// reserved amounts.  The same duplicate-pod rule as Admit: a pod already reserved, or twice in rows, must not be in the queue.
+func PagedAdmit(pages []*Engine, rows []int64, onEqual, commit bool) (summary []uint64, status []uint8, err error) {
+	if len(pages) == 0 {
+		return nil, nil, fmt.Errorf("PagedAdmit: no pages")
+	}
+	var flags C.uint32_t
+	if commit {
+		flags = C.KT_ADMIT_COMMIT
+	}
+	hs := make([]*C.kt_engine, len(pages))
+	for k, p := range pages {
+		hs[k] = p.h
+	}
+	T := pages[0].ThrottleRows()
+	summary = make([]uint64, len(rows)+1)
+	status = make([]uint8, len(rows)*T+1)
+	if rc := C.kt_paged_admit((**C.kt_engine)(unsafe.Pointer(&hs[0])), C.int32_t(len(pages)), C.int64_t(len(rows)), i64(rows), b2i(onEqual),
+		flags, (*C.uint64_t)(unsafe.Pointer(&summary[0])), u8(status)); rc != C.KT_OK {
+		return nil, nil, pages[0].err(rc)
+	}
+	return summary[:len(rows)], status[:len(rows)*T], nil
+}
+
 // ---- aggregation: [Cluster]ThrottleController.reconcile (throttle_controller.go:103-133, clusterthrottle_controller.go:106-136)
 
 // Status is the reconcile result of n throttle rows at the engine's scales.

@@ -449,6 +449,87 @@ int32_t kt_paged_check(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
   return KT_OK;
 }
 
+// kt_admit_launch over the pages: one kt_admit_paged launch on page 0's stream after one status-matrix check of page 0
+int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
+                       uint64_t* out_summary, uint8_t* out_status) {
+  if (!pages || n_pages < 1 || n < 0) return KT_ERR_INVALID_ARGUMENT;
+  for (int32_t k = 0; k < n_pages; ++k) {
+    if (!pages[k]) return KT_ERR_INVALID_ARGUMENT;
+    for (int32_t j = 0; j < k; ++j)
+      if (pages[j] == pages[k]) return pages[k]->fail(KT_ERR_INVALID_ARGUMENT, "paged admit: the engine of page %d is also page %d", k, j);
+  }
+  // every page exclusively, in address order: two paged calls over overlapping pages cannot deadlock
+  std::vector<kt_engine*> by_addr(pages, pages + n_pages);
+  std::sort(by_addr.begin(), by_addr.end(), std::less<kt_engine*>());
+  std::vector<std::unique_ptr<LaunchLock>> locks;
+  for (kt_engine* e : by_addr) locks.emplace_back(new LaunchLock(e, /*force_exclusive=*/true));
+  kt_engine* e0 = pages[0];
+  const int32_t T = e0->thr_rows_hi;
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if (e->thr_rows_hi != T) return e->fail(KT_ERR_INVALID_ARGUMENT, "page %d holds %d throttle rows, page 0 %d: every page holds every throttle", k, e->thr_rows_hi, T);
+    if (e->device != e0->device) return e->fail(KT_ERR_UNSUPPORTED, "paged admit: page %d is on device %d, page 0 on %d", k, e->device, e0->device);
+    if (e->wide)
+      return e->fail(KT_ERR_UNSUPPORTED, "paged admit: the stored `used` of page %d is wider than int64 (kt_admit_paged reads int64 tables)", k);
+    if (pod_rows) {
+      for (int64_t i = 0; i < n; ++i)
+        if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "page %d: pod row %lld", k, (long long)pod_rows[i]);
+    } else if (n > e->cfg.pod_capacity) {
+      return e->fail(KT_ERR_OUT_OF_RANGE, "page %d: n=%lld > pod_capacity", k, (long long)n);
+    }
+  }
+  if ((double)n * (double)T > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "paged admit: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  if (n == 0) return KT_OK;
+  KT_HIP(e0, hipSetDevice(e0->device));
+  hipStream_t s = pick_stream(e0, nullptr);
+  // Ordering: the kernel reads every page's tables on page 0's stream.  Uploads of host-side status / reserved rows (ensure_ready)
+  // and earlier launches of page k ran on page k's streams: they are SYNCHRONISED here (the call is synchronous anyway); the
+  // newest feed kernel of page k is ordered before the launch on the device (order_behind_ingest).
+  for (int32_t k = 1; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    int32_t rc = ensure_ready(e, e->own_stream);
+    if (rc != KT_OK) return rc;
+    KT_HIP(e, hipStreamSynchronize(e->own_stream));
+    if (e->last_stream && e->last_stream != e->own_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+    order_behind_ingest(e, s);
+  }
+  // (a) who affects whom, from page 0 (selectors, namespaces and responsibility are the same in every page)
+  int32_t rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  if (rc != KT_OK) return rc;
+  e0->check_ready = false;  // the call used page 0's check slot (as kt_affected_pods): a pending kt_check_launch is gone
+  // the descriptors' host copy lives until the stream synchronisation below (hipMemcpyAsync from pageable memory)
+  std::vector<kt::AdmitPage> desc((size_t)n_pages);
+  if (T > 0) {
+    // (b) the queue in order, one wave, every page's reserved amounts side by side
+    for (int32_t k = 0; k < n_pages; ++k) {
+      const kt_engine* e = pages[k];
+      desc[k] = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+    }
+    const bool commit = (flags & KT_ADMIT_COMMIT) != 0;
+    KT_HIP(e0, e0->d_admit.reserve(kt::admit_paged_state_bytes(T, desc.data(), n_pages) + 64));
+    KT_HIP(e0, e0->d_admit_pages.reserve(sizeof(kt::AdmitPage) * (size_t)n_pages));
+    static const bool force_global = getenv("KT_ADMIT_FORCE_GLOBAL") != nullptr;  // test hook: HBM-resident state
+    hipError_t herr = hipSuccess;
+    const bool launched = kt::launch_admit_paged(desc.data(), n_pages, (kt::AdmitPage*)e0->d_admit_pages.p, n, pod_rows ? e0->d_rows.p : nullptr,
+                                                 T, on_equal != 0, commit, e0->d_status.p, e0->d_summary.p, e0->d_admit.p, force_global, s, &herr);
+    if (herr != hipSuccess) return e0->fail(KT_ERR_DEVICE, "paged admit: copy of the page descriptors: %s", hipGetErrorString(herr));
+    if (!launched) return e0->fail(KT_ERR_UNSUPPORTED, "paged admit: %d throttle rows exceed the kernel's LDS list", T);
+    KT_HIP(e0, hipGetLastError());
+    if (commit)
+      for (int32_t k = 0; k < n_pages; ++k) {
+        kt_engine* e = pages[k];
+        e->reserved_dev_newer = true;
+        std::lock_guard<std::mutex> g(e->recs_mu);
+        e->recs_valid = false;
+      }
+  }
+  if (out_summary) KT_HIP(e0, hipMemcpyAsync(out_summary, e0->d_summary.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (out_status && T > 0) KT_HIP(e0, hipMemcpyAsync(out_status, e0->d_status.p, (size_t)n * (size_t)T, hipMemcpyDeviceToHost, s));
+  KT_HIP(e0, hipStreamSynchronize(s));  // (also: from here on `desc` is no longer read)
+  return KT_OK;
+}
+
 int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now_s, int32_t now_ns, uint32_t flags, int32_t n,
                            const kt_status* page_out, uint8_t* replaced_any, uint8_t* error_any) {
   if (!pages || n_pages < 1 || n < 0 || !page_out) return KT_ERR_INVALID_ARGUMENT;

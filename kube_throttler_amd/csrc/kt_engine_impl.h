@@ -306,6 +306,7 @@ struct kt_engine {
   // ---- reconcile state
   DevBuf<unsigned long long> d_partial;
   DevBuf<uint8_t> d_admit;  // HBM-resident state of kt_admit_sequential when it does not fit LDS
+  DevBuf<uint8_t> d_admit_pages;  // page descriptors of kt_paged_admit (on page 0)
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;

@@ -36,6 +36,18 @@ struct AdmitArgs {
   uint32_t off_rv, off_rc, off_rp, off_list, list_cap;
 };
 
+struct AdmitPagedArgs {
+  const AdmitPage* pages;  // [n_pages] in device memory (ThrTables is too large to pass by value per page)
+  int32_t n_pages;
+  const int64_t* rows;  // nullable: queue position -> pod table row (the same rows in every page)
+  int64_t n;
+  unsigned char* scratch;  // every page's state in HBM when it does not fit LDS (nullable)
+  uint8_t* status;    // [n][T] in/out: page 0's matrix in, the combined statuses out
+  uint64_t* summary;  // [n] out
+  int32_t T, on_equal, commit;
+  uint32_t off_list, list_cap;
+};
+
 // the sums of used + reserved (+ the pod) are formed in 128 bits: an all-reduced `used` may come close to int64's end
 __device__ __forceinline__ bool admit_cmp(__int128 a, int64_t b, bool eq) { return eq ? a >= (__int128)b : a > (__int128)b; }
 
@@ -68,30 +80,85 @@ struct AdmitState<false> {
   __device__ __forceinline__ void st_p(int i, uint32_t x) const { __hip_atomic_store(rp + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
 
-template <int DT, bool IN_LDS>
-__global__ __launch_bounds__(kWave) void kt_admit_sequential(const AdmitArgs a) {
-  KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
+// the state of one engine's T throttle rows at byte offsets of LDS or of the scratch buffer
+template <bool IN_LDS>
+__device__ __forceinline__ AdmitState<IN_LDS> admit_state_at(KT_LDS unsigned char* lds, unsigned char* scratch, uint32_t off_rv,
+                                                             uint32_t off_rc, uint32_t off_rp) {
   AdmitState<IN_LDS> st;
   if constexpr (IN_LDS) {
-    st.rv = (KT_LDS int64_t*)(lds + a.off_rv);    // [T][D] reserved requests
-    st.rc = (KT_LDS int64_t*)(lds + a.off_rc);    // [T]    reserved pod count
-    st.rp = (KT_LDS uint32_t*)(lds + a.off_rp);   // [T]    presence mask | has_count << 31
+    st.rv = (KT_LDS int64_t*)(lds + off_rv);    // [T][D] reserved requests
+    st.rc = (KT_LDS int64_t*)(lds + off_rc);    // [T]    reserved pod count
+    st.rp = (KT_LDS uint32_t*)(lds + off_rp);   // [T]    presence mask | has_count << 31
   } else {
-    st.rv = (int64_t*)(a.scratch + a.off_rv);
-    st.rc = (int64_t*)(a.scratch + a.off_rc);
-    st.rp = (uint32_t*)(a.scratch + a.off_rp);
+    st.rv = (int64_t*)(scratch + off_rv);
+    st.rc = (int64_t*)(scratch + off_rc);
+    st.rp = (uint32_t*)(scratch + off_rp);
   }
-  lds_u32wp list = (lds_u32wp)(lds + a.off_list);            // affected throttles of the current pod
-  const int T = a.T, D = a.D;
-  const uint32_t lane = threadIdx.x;
-  const ThrTables& tt = a.tt;
-  for (int t = (int)lane; t < T; t += kWave) {
+  return st;
+}
+// reserved tables (HBM) -> state, and back (commit)
+template <bool IN_LDS>
+__device__ __forceinline__ void admit_load_state(const AdmitState<IN_LDS>& st, const ThrTables& tt, int T, int D) {
+  for (int t = (int)threadIdx.x; t < T; t += kWave) {
     const uint32_t p = tt.reserved.present[t];
     for (int d = 0; d < D; ++d) st.st_v(t * D + d, ((p >> d) & 1u) ? tt.reserved.v[(size_t)t * D + d] : 0);
     const bool hc = tt.reserved.has_count[t] != 0;
     st.st_c(t, hc ? tt.reserved.count[t] : 0);
     st.st_p(t, p | (hc ? 0x80000000u : 0u));
   }
+}
+template <bool IN_LDS>
+__device__ __forceinline__ void admit_store_state(const AdmitState<IN_LDS>& st, const ThrTables& tt, int T, int D) {
+  for (int t = (int)threadIdx.x; t < T; t += kWave) {
+    const uint32_t w = st.ld_p(t);
+    for (int dd = 0; dd < D; ++dd) tt.reserved.v[(size_t)t * D + dd] = st.ld_v(t * D + dd);
+    tt.reserved.present[t] = w & 0x7FFFFFFFu;
+    tt.reserved.has_count[t] = (uint8_t)(w >> 31);
+    tt.reserved.count[t] = st.ld_c(t);
+  }
+}
+
+// (1) of a pod: the nonzero bytes of its status-matrix row -> the affected-throttle list (16 bytes per lane and chunk,
+// ballot/mbcnt append); returns the wave-uniform count, *err = the row holds an error byte
+__device__ __forceinline__ uint32_t admit_affected(const uint8_t* row, int T, lds_u32wp list, uint32_t list_cap, bool* err_out) {
+  const uint32_t lane = threadIdx.x;
+  uint32_t n_aff = 0;  // wave-uniform
+  bool err = false;
+  for (int c0 = 0; c0 < T; c0 += kWave * 16) {
+    const int b0 = c0 + (int)lane * 16;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (b0 < T) v = *(const u32x4*)(row + b0);  // the buffer has slack past the last row
+    uint32_t nzm = 0;                            // bit k: byte k is nonzero
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const uint32_t byte = (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
+      if (b0 + k < T && byte != 0) nzm |= 1u << k;
+      err |= (b0 + k < T) && byte == 255u;
+    }
+    while (__ballot(nzm != 0) != 0ull) {
+      const bool has = nzm != 0;
+      const uint32_t k = (uint32_t)__ffs((int)nzm) - 1u;
+      nzm &= nzm - 1u;
+      const uint64_t mk = __ballot(has);
+      const uint32_t pos = n_aff + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+      if (has && pos < list_cap) list[pos] = (uint32_t)b0 + k;
+      n_aff += (uint32_t)__popcll(mk);
+    }
+  }
+  *err_out = err;
+  return n_aff;
+}
+
+template <int DT, bool IN_LDS>
+__global__ __launch_bounds__(kWave) void kt_admit_sequential(const AdmitArgs a) {
+  KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
+  const AdmitState<IN_LDS> st = admit_state_at<IN_LDS>(lds, a.scratch, a.off_rv, a.off_rc, a.off_rp);
+  lds_u32wp list = (lds_u32wp)(lds + a.off_list);            // affected throttles of the current pod
+  const int T = a.T, D = a.D;
+  const uint32_t lane = threadIdx.x;
+  const ThrTables& tt = a.tt;
+  admit_load_state(st, tt, T, D);
   if (!IN_LDS) __threadfence();
   constexpr int MPW = kWave / DT;
   const uint32_t d = lane % DT, ml = lane / DT;
@@ -103,30 +170,8 @@ __global__ __launch_bounds__(kWave) void kt_admit_sequential(const AdmitArgs a) 
     const uint32_t present = fl >> kPresentShift;
     uint8_t* row = a.status + i * T;
     // ---- (1) affected throttles: nonzero bytes of the matrix row, 16 per lane and chunk
-    uint32_t n_aff = 0;  // wave-uniform
-    bool err = false;
-    for (int c0 = 0; c0 < T; c0 += kWave * 16) {
-      const int b0 = c0 + (int)lane * 16;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (b0 < T) v = *(const u32x4*)(row + b0);  // the buffer has slack past the last row
-      uint32_t nzm = 0;                            // bit k: byte k is nonzero
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const uint32_t byte = (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
-        if (b0 + k < T && byte != 0) nzm |= 1u << k;
-        err |= (b0 + k < T) && byte == 255u;
-      }
-      while (__ballot(nzm != 0) != 0ull) {
-        const bool has = nzm != 0;
-        const uint32_t k = (uint32_t)__ffs((int)nzm) - 1u;
-        nzm &= nzm - 1u;
-        const uint64_t mk = __ballot(has);
-        const uint32_t pos = n_aff + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-        if (has && pos < a.list_cap) list[pos] = (uint32_t)b0 + k;
-        n_aff += (uint32_t)__popcll(mk);
-      }
-    }
+    bool err;
+    const uint32_t n_aff = admit_affected(row, T, list, a.list_cap, &err);
     if (__ballot(err) != 0ull || !(fl & kPodValid) || n_aff > a.list_cap) {
       // error row (selector / namespace error, plugin.go:154-168), empty row, or a pod affected by more
       // throttles than the list holds: the pre-computed summary stands and nothing is reserved
@@ -189,15 +234,118 @@ __global__ __launch_bounds__(kWave) void kt_admit_sequential(const AdmitArgs a) 
       }
     }
   }
-  if (a.commit) {
-    for (int t = (int)lane; t < T; t += kWave) {
-      const uint32_t w = st.ld_p(t);
-      for (int dd = 0; dd < D; ++dd) tt.reserved.v[(size_t)t * D + dd] = st.ld_v(t * D + dd);
-      tt.reserved.present[t] = w & 0x7FFFFFFFu;
-      tt.reserved.has_count[t] = (uint8_t)(w >> 31);
-      tt.reserved.count[t] = st.ld_c(t);
+  if (a.commit) admit_store_state(st, tt, T, D);
+}
+
+// a page descriptor by value: read through the constant address space (nothing writes the descriptors while the kernel
+// runs), so the wave-uniform fields come in with scalar loads into SGPRs
+__device__ __forceinline__ AdmitPage admit_page(const AdmitPage* pages, int k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ((const __attribute__((address_space(4))) AdmitPage*)pages)[k];
+#else
+  return pages[k];
+#endif
+}
+
+// ---- the paged form (kt_paged_admit): one wave, the queue in order, every page's state side by side.  Page 0's status matrix
+// gives the affected list once per pod (selectors, namespaces and responsibility are the same in every page); the name part of
+// the four steps is evaluated against every page's tables and reserved state and OR-ed before the reduction (exceeds > active >
+// insufficient, as kt_paged_check combines), the count part once, on page 0; Success reserves on every page.
+template <int DT, bool IN_LDS>
+__global__ __launch_bounds__(kWave) void kt_admit_paged(const AdmitPagedArgs a) {
+  KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
+  lds_u32wp list = (lds_u32wp)(lds + a.off_list);
+  const int T = a.T, n_pages = a.n_pages;
+  const uint32_t lane = threadIdx.x;
+  for (int k = 0; k < n_pages; ++k) {
+    const AdmitPage pg = admit_page(a.pages, k);
+    admit_load_state(admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp), pg.tt, T, pg.D);
+  }
+  if (!IN_LDS) __threadfence();
+  constexpr int MPW = kWave / DT;
+  const uint32_t d = lane % DT, ml = lane / DT;
+  const bool eq = a.on_equal != 0;
+  for (int64_t i = 0; i < a.n; ++i) {
+    const int64_t p = a.rows ? a.rows[i] : i;
+    uint8_t* row = a.status + i * T;
+    bool err;
+    const uint32_t n_aff = admit_affected(row, T, list, a.list_cap, &err);
+    if (__ballot(err) != 0ull || !(admit_page(a.pages, 0).pod_flags[p] & kPodValid) || n_aff > a.list_cap) continue;  // page 0's summary stands
+    uint32_t n_exc = 0, n_act = 0, n_ins = 0;
+    for (uint32_t base = 0; base < n_aff; base += MPW) {
+      const uint32_t j = base + ml;
+      const bool vv = j < n_aff;
+      const uint32_t t = list[vv ? j : 0u];
+      uint32_t bits = 0;
+      for (int k = 0; k < n_pages; ++k) {
+        const AdmitPage pg = admit_page(a.pages, k);
+        const ThrTables& tt = pg.tt;
+        const int D = pg.D;
+        if (!vv) continue;
+        const AdmitState<IN_LDS> st = admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp);
+        const uint32_t tf = tt.flags[t];
+        const AmountTab& th = (tf & kThrCalcAtNonzero) ? tt.calc : tt.spec;
+        const bool eq3 = (tf & kThrCluster) ? eq : true;
+        if (k == 0 && d == 0) {  // resourceCounts.pod: the same in every page, evaluated on page 0
+          const bool th_hc = th.has_count[t] != 0;
+          const int64_t th_c = th.count[t];
+          const bool u_hc = tt.used.has_count[t] != 0, r_hc = (st.ld_p(t) >> 31) != 0;
+          const int64_t u_c = u_hc ? tt.used.count[t] : 0, r_c = st.ld_c(t);
+          if (th_hc && 1 > th_c) bits |= 1u;
+          if ((tf & kThrThrottledPod) || (th_hc && (u_hc || r_hc) && admit_cmp((__int128)u_c + r_c, th_c, eq3))) bits |= 2u;
+          if (th_hc && admit_cmp((__int128)u_c + 1 + r_c, th_c, eq)) bits |= 4u;
+        }
+        if ((int)d >= D) continue;  // name part: dimension d of every page
+        const int64_t v = pg.req[p * pg.DS + d];
+        if (v == 0) continue;  // steps 1-4 of a name the pod does not request
+        const uint32_t th_p = th.present[t], u_p = tt.used.present[t], r_pw = st.ld_p(t);
+        if ((th_p >> d) & 1u) {
+          const int64_t tv = th.v[(size_t)t * D + d];
+          const int64_t uv = ((u_p >> d) & 1u) ? tt.used.v[(size_t)t * D + d] : 0;
+          const int64_t rvd = st.ld_v(t * D + d);
+          if (v > tv) bits |= 1u;                                                               // step 1
+          if ((((u_p | r_pw) >> d) & 1u) && admit_cmp((__int128)uv + rvd, tv, eq3)) bits |= 2u;  // step 3
+          if (admit_cmp((__int128)uv + v + rvd, tv, eq)) bits |= 4u;                             // step 4
+        }
+        if (((tt.thrl_flag[t] & tt.thrl_has[t]) >> d) & 1u) bits |= 2u;                         // step 2
+      }
+#pragma unroll
+      for (int o = DT / 2; o >= 1; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, o);
+      const uint32_t stc = (bits & 1u) ? 4u : (bits & 2u) ? 2u : (bits & 4u) ? 3u : 1u;
+      const bool lead = vv && d == 0;
+      if (lead) row[t] = (uint8_t)stc;
+      n_exc += (uint32_t)__popcll(__ballot(lead && stc == 4u));
+      n_act += (uint32_t)__popcll(__ballot(lead && stc == 2u));
+      n_ins += (uint32_t)__popcll(__ballot(lead && stc == 3u));
+    }
+    if (lane == 0) a.summary[i] = pack_summary(n_exc, n_act, n_ins, false);
+    if ((n_exc | n_act | n_ins) != 0) continue;
+    // Success: Reserve on every page (its own names' amounts; the count and has_count in every page)
+    for (int k = 0; k < n_pages; ++k) {
+      const AdmitPage pg = admit_page(a.pages, k);
+      const int D = pg.D;
+      const AdmitState<IN_LDS> st = admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp);
+      const uint32_t present = pg.pod_flags[p] >> kPresentShift;
+      const bool d_in = (int)d < D;
+      const int64_t v = d_in ? pg.req[p * pg.DS + d] : 0;
+      for (uint32_t base = 0; base < n_aff; base += MPW) {
+        const uint32_t j = base + ml;
+        if (j < n_aff) {
+          const uint32_t t = list[j];
+          if (d_in && ((present >> d) & 1u)) st.st_v(t * D + d, st.ld_v(t * D + d) + v);
+          if (d == 0) {
+            st.st_c(t, st.ld_c(t) + 1);
+            st.st_p(t, st.ld_p(t) | present | 0x80000000u);
+          }
+        }
+      }
     }
   }
+  if (a.commit)
+    for (int k = 0; k < n_pages; ++k) {
+      const AdmitPage pg = admit_page(a.pages, k);
+      admit_store_state(admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp), pg.tt, T, pg.D);
+    }
 }
 
 // LDS: state + list when the state fits, else the list alone
@@ -229,6 +377,48 @@ bool launch_admit(const PodTable& pods, int64_t n, const int64_t* rows_dev, cons
 #define KT_ADMIT_CASE(DT_)                                                                                        \
   {                                                                                                              \
     auto kfn = in_lds ? kt_admit_sequential<DT_, true> : kt_admit_sequential<DT_, false>;                        \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
+    hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a);                                              \
+  }
+  if (DT == 4) KT_ADMIT_CASE(4) else if (DT == 8) KT_ADMIT_CASE(8) else KT_ADMIT_CASE(16)
+#undef KT_ADMIT_CASE
+  return true;
+}
+
+size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages) {
+  size_t b = 0;
+  for (int k = 0; k < n_pages; ++k) b += admit_state_bytes(T, pages[k].D);
+  return b;
+}
+
+bool launch_admit_paged(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, int64_t n, const int64_t* rows_dev, int T,
+                        bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global,
+                        hipStream_t s, hipError_t* hip_err) {
+  *hip_err = hipSuccess;
+  const size_t list_bytes = ((size_t)T * 4 + 15) / 16 * 16;
+  const bool in_lds = !force_global && admit_paged_state_bytes(T, pages, n_pages) + list_bytes <= (size_t)kMaxLds;
+  if (!in_lds && (!scratch || list_bytes > (size_t)kMaxLds)) return false;
+  uint32_t o = 0;
+  auto take = [&](size_t bytes) { uint32_t r = o; o += (uint32_t)((bytes + 15) & ~(size_t)15); return r; };
+  int maxD = 1;
+  for (int k = 0; k < n_pages; ++k) {  // offsets inside LDS or inside the scratch buffer, page after page
+    pages[k].off_rv = take((size_t)T * pages[k].D * 8);
+    pages[k].off_rc = take((size_t)T * 8);
+    pages[k].off_rp = take((size_t)T * 4);
+    maxD = pages[k].D > maxD ? pages[k].D : maxD;
+  }
+  if (!in_lds) o = 0;
+  AdmitPagedArgs a{};
+  a.pages = pages_dev, a.n_pages = n_pages, a.rows = rows_dev, a.n = n, a.scratch = (unsigned char*)scratch;
+  a.status = status, a.summary = summary, a.T = T, a.on_equal = on_equal ? 1 : 0, a.commit = commit ? 1 : 0;
+  a.list_cap = (uint32_t)T;
+  a.off_list = take((size_t)a.list_cap * 4);
+  const size_t lds_bytes = o;
+  if ((*hip_err = hipMemcpyAsync(pages_dev, pages, sizeof(AdmitPage) * (size_t)n_pages, hipMemcpyHostToDevice, s)) != hipSuccess) return false;
+  const int DT = dt_bucket(maxD);
+#define KT_ADMIT_CASE(DT_)                                                                                        \
+  {                                                                                                              \
+    auto kfn = in_lds ? kt_admit_paged<DT_, true> : kt_admit_paged<DT_, false>;                                  \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
     hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a);                                              \
   }

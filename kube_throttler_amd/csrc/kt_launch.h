@@ -88,6 +88,22 @@ bool launch_admit(const PodTable& pods, int64_t n, const int64_t* rows_dev, cons
                   bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global,
                   hipStream_t s);
 
+// the multi-page form (kt_paged_admit): one descriptor per page, the offsets are filled in by the launcher, which also
+// copies the descriptors to pages_dev (n_pages entries of device memory).  The state of all pages lives in LDS while
+// admit_paged_state_bytes + the list fit, else in `scratch` (admit_paged_state_bytes bytes).  false: the list does not fit
+// LDS, or (*hip_err != hipSuccess) the copy of the descriptors failed
+struct AdmitPage {
+  const uint32_t* pod_flags;  // the page's pod flags (presence bits of ITS names)
+  const int64_t* req;         // [pods][DS]
+  ThrTables tt;
+  int32_t D, DS;
+  uint32_t off_rv, off_rc, off_rp;
+};
+size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages);
+bool launch_admit_paged(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, int64_t n, const int64_t* rows_dev, int T,
+                        bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global,
+                        hipStream_t s, hipError_t* hip_err);
+
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations
 inline int lt_bucket(int L) { return L <= 8 ? 8 : 16; }

@@ -40,6 +40,7 @@ EXPORTS = [
     "kt_check", "kt_upsert_namespace", "kt_upsert_pod", "kt_upsert_throttle", "kt_comm_unique_id", "kt_comm_init",
     "kt_comm_allreduce_partial", "kt_comm_destroy", "kt_reconcile_rows_launch", "kt_set_exchange_world", "kt_counter", "kt_reconcile_fetch_used_hi",
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
+    "kt_paged_admit",
 ]
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
@@ -73,6 +74,22 @@ def paged_check(engines, n, rows=None, on_equal=False):
     rc = lib().kt_paged_check(hs, len(engines), n, rows_a.ctypes.data, int(on_equal), summary.ctypes.data, status.ctypes.data)
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_check: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return status[:n, :T], summary[:n]
+
+
+def paged_admit(engines, rows, on_equal=False, commit=False):
+    """kt_paged_admit: the queue ``rows`` admitted in order over the page engines (PreFilter, and Reserve on Success, with
+    every page's names) -> (status matrix [n][T] at each pod's turn, summary words [n]), combined over the pages."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    T = engines[0].throttle_rows()
+    rows_a = np.ascontiguousarray(rows, dtype=np.int64)
+    n = len(rows_a)
+    status = np.zeros((max(n, 1), max(T, 1)), np.uint8)
+    summary = np.zeros(max(n, 1), np.uint64)
+    rc = lib().kt_paged_admit(hs, len(engines), n, rows_a.ctypes.data if n else None, int(on_equal),
+                              ADMIT_COMMIT if commit else 0, summary.ctypes.data, status.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_admit: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return status[:n, :T], summary[:n]
 
 
@@ -164,6 +181,8 @@ def lib():
         L.kt_paged_check.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.kt_paged_reconcile.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_int32,
                                          C.POINTER(KtStatus), C.c_void_p, C.c_void_p]
+        L.kt_paged_admit.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p,
+                                     C.c_void_p]
         L.kt_counter.argtypes = [C.c_void_p, C.c_int32]
         L.kt_reconcile_fetch_used_hi.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
         L.kt_counter.restype = C.c_int64

@@ -316,11 +316,24 @@ struct RowTable {  // key -> dense row with a free list
   }
 };
 
+// more than KT_MAX_DIMS resource names: one engine per PAGE of KT_MAX_DIMS names (kt_paged_*); a name's values live at
+// v[page * KT_MAX_DIMS + dimension], its presence bit in present[page]
+constexpr int kMaxPages = 16;
 struct DenseAmount {
-  int64_t v[KT_MAX_DIMS] = {0};
-  uint32_t present = 0;
+  int64_t v[KT_MAX_DIMS * kMaxPages] = {0};
+  uint32_t present[kMaxPages] = {0};
   int64_t count = 0;
   uint8_t has_count = 0;
+};
+// the count part of a throttle row's applied status (what a page created after a ReconcileAll has to be seeded with)
+struct CountPart {
+  bool set = false;
+  int64_t used_count = 0, calc_count = 0;
+  uint8_t used_has = 0, calc_has = 0, calc_at_nonzero = 0, thrl_pod = 0;
+  uint64_t msgs_fp = 0;
+};
+struct DimRef {
+  int page, dim, scale;
 };
 
 }  // namespace
@@ -330,9 +343,14 @@ struct KubeThrottler::Impl {
   // goroutines (plugin.go:148-257): every public method takes this lock (recursive: the methods call each other)
   std::recursive_mutex mu;
   PluginArgs args;
-  kt_engine* e = nullptr;
+  kt_engine* e = nullptr;  // page 0
+  std::vector<kt_engine*> pages;  // pages[0] == e; page k is created the first time a name does not fit pages 0..k-1
+  kt_config cfg{};
   int D = KT_MAX_DIMS;
-  std::map<std::string, std::pair<int, int>> dims;  // resource name -> (dimension, scale)
+  std::map<std::string, DimRef> dims;  // resource name -> (page, dimension, scale)
+  std::map<std::string, Namespace> ns_objs;  // Namespace objects seen (a page created later replays them)
+  std::vector<CountPart> count_part;         // per throttle row
+  std::vector<uint64_t> spec_fp;             // per throttle row: fingerprint of its override messages
   // resource name -> Format of the first non-zero quantity seen under that name: what a `used` sum inherits through
   // Quantity.Add when every pod writes the resource in one suffix family (the reference's result otherwise depends on
   // the lister's pod order)
@@ -359,68 +377,107 @@ struct KubeThrottler::Impl {
   }
   static std::string thr_key(const Throttle& t) { return (t.cluster ? "C:" : "T:") + t.Key(); }
 
-  bool dim_of(const std::string& name, int* dim, int* scale, std::string* err) {
+  // a name's (page, dimension, scale); a name that fits no existing page opens the next one (add_page)
+  bool dim_of(const std::string& name, DimRef* out, std::string* err) {
     auto it = dims.find(name);
     if (it == dims.end()) {
-      if ((int)dims.size() >= D) {
-        if (err) *err = "more than " + std::to_string(D) + " distinct resource names";
+      const int page = (int)(dims.size() / (size_t)D);
+      if (page >= kMaxPages) {
+        if (err) *err = "more than " + std::to_string(D * kMaxPages) + " distinct resource names";
         return false;
       }
+      if (page >= (int)pages.size() && !add_page(err)) return false;
       int sc = name == "cpu" ? -3 : 0;
       auto s = args.resourceScales.find(name);
       if (s != args.resourceScales.end()) sc = s->second;
-      it = dims.emplace(name, std::make_pair((int)dims.size(), sc)).first;
+      it = dims.emplace(name, DimRef{page, (int)(dims.size() % (size_t)D), sc}).first;
     }
-    *dim = it->second.first;
-    *scale = it->second.second;
+    *out = it->second;
     return true;
   }
-  bool fill_row(const ResourceList& rl, int64_t* v, uint32_t* present, std::string* err) {
+  bool register_names(const ResourceList& rl, std::string* err) {
+    DimRef r;
+    for (auto& kv : rl)
+      if (!dim_of(kv.first, &r, err)) return false;
+    return true;
+  }
+  bool register_names(const ResourceAmount& a, std::string* err) { return register_names(a.requests, err); }
+  // page `page`'s values of a resource list (every name is parsed and checked, the other pages' names are skipped)
+  bool fill_row(const ResourceList& rl, int page, int64_t* v, uint32_t* present, std::string* err) {
     for (auto& kv : rl) {
       Quantity q;
-      int dim, scale;
-      if (!ParseQuantity(kv.second, &q, err) || !dim_of(kv.first, &dim, &scale, err)) return false;
+      DimRef r;
+      if (!ParseQuantity(kv.second, &q, err) || !dim_of(kv.first, &r, err)) return false;
       int64_t x;
-      if (!ScaledValue(q, scale, &x)) {
-        if (err) *err = "quantity " + kv.second + " of " + kv.first + " is not representable at scale 1e" + std::to_string(scale);
+      if (!ScaledValue(q, r.scale, &x)) {
+        if (err) *err = "quantity " + kv.second + " of " + kv.first + " is not representable at scale 1e" + std::to_string(r.scale);
         return false;
       }
-      v[dim] = x;
-      *present |= 1u << dim;
       if (q.nano != 0) dim_format.emplace(kv.first, q.format);
+      if (r.page != page) continue;
+      v[r.dim] = x;
+      *present |= 1u << r.dim;
     }
     return true;
   }
-  bool fill_amount(const ResourceAmount& a, DenseAmount* d, std::string* err) {
+  bool fill_amount(const ResourceAmount& a, int page, DenseAmount* d, std::string* err) {
     *d = DenseAmount();
     d->has_count = a.hasCounts;
     d->count = a.hasCounts ? a.pod : 0;
-    return fill_row(a.requests, d->v, &d->present, err);
+    return fill_row(a.requests, page, d->v, &d->present[0], err);
   }
   std::string engine_error(int32_t rc) { return "kt: " + std::to_string(rc) + ": " + kt_last_error(e); }
+  std::string engine_error(int32_t rc, kt_engine* pe) { return "kt: " + std::to_string(rc) + ": " + kt_last_error(pe); }
 
-  bool push_reserved(int32_t row, std::string* err) {
+  // page = -1: every page
+  bool push_reserved(int32_t row, std::string* err, int only_page = -1) {
     DenseAmount tot;
     auto it = reserved.find(row);
     if (it != reserved.end())
       for (auto& kv : it->second) {  // podResourceAmountMap.totalResoruceAmount (reserved_resource_amounts.go:148-156)
         tot.has_count = 1;
         tot.count += 1;
-        tot.present |= kv.second.present;
-        for (int d = 0; d < D; ++d) tot.v[d] += kv.second.v[d];
+        for (size_t k = 0; k < pages.size(); ++k) tot.present[k] |= kv.second.present[k];
+        for (size_t d = 0; d < (size_t)D * pages.size(); ++d) tot.v[d] += kv.second.v[d];
       }
-    kt_amounts am{tot.v, &tot.present, &tot.count, &tot.has_count};
-    int32_t rc = kt_set_reserved(e, 1, &row, &am);
-    if (rc != KT_OK) {
-      if (err) *err = engine_error(rc);
-      return false;
+    for (size_t k = 0; k < pages.size(); ++k) {
+      if (only_page >= 0 && (int)k != only_page) continue;
+      kt_amounts am{tot.v + k * (size_t)D, &tot.present[k], &tot.count, &tot.has_count};
+      int32_t rc = kt_set_reserved(pages[k], 1, &row, &am);
+      if (rc != KT_OK) {
+        if (err) *err = engine_error(rc, pages[k]);
+        return false;
+      }
     }
     return true;
   }
+  // ResourceAmountOfPod of pod rows as the engines hold them (every page its own names)
+  int32_t fetch_pod_amounts(int64_t n, const int64_t* rows, std::vector<DenseAmount>* out) {
+    out->assign((size_t)n, DenseAmount());
+    std::vector<int64_t> v((size_t)n * (size_t)D);
+    std::vector<uint32_t> pr((size_t)n);
+    for (size_t k = 0; k < pages.size(); ++k) {
+      int32_t rc = kt_fetch_pod_requests(pages[k], n, rows, v.data(), pr.data());
+      if (rc != KT_OK) return rc;
+      for (int64_t i = 0; i < n; ++i) {
+        std::memcpy((*out)[(size_t)i].v + k * (size_t)D, &v[(size_t)i * D], sizeof(int64_t) * (size_t)D);
+        (*out)[(size_t)i].present[k] = pr[(size_t)i];
+      }
+    }
+    for (auto& a : *out) a.has_count = 1, a.count = 1;
+    return KT_OK;
+  }
+
+  bool upsert_namespace(size_t k, const std::string& name, int32_t row, std::string* err);
+  bool upsert_pod(size_t k, const Pod& pod, int64_t row, uint32_t ns32, std::string* err);
+  bool upsert_throttle(size_t k, const Throttle& thr, int32_t row, uint32_t ns32, std::vector<std::string>* msgs, uint64_t* fp,
+                       std::string* err);
+  bool add_page(std::string* err);
 };
 
 KubeThrottler::~KubeThrottler() {
-  if (p_ && p_->e) kt_engine_destroy(p_->e);
+  if (!p_) return;
+  for (kt_engine* pe : p_->pages) kt_engine_destroy(pe);
 }
 
 std::unique_ptr<KubeThrottler> NewPlugin(const PluginArgs& args, std::string* err) {
@@ -437,7 +494,7 @@ std::unique_ptr<KubeThrottler> NewPlugin(const PluginArgs& args, std::string* er
   k->p_.reset(new KubeThrottler::Impl());
   auto& p = *k->p_;
   p.args = args;
-  kt_config cfg{};
+  kt_config& cfg = p.cfg;
   cfg.n_dims = p.D;
   cfg.max_labels = args.maxLabels;
   cfg.pod_capacity = args.podCapacity;
@@ -450,82 +507,49 @@ std::unique_ptr<KubeThrottler> NewPlugin(const PluginArgs& args, std::string* er
     if (err) *err = std::string("kt_engine_create: ") + std::to_string(rc) + ": " + kt_last_error(nullptr);
     return nullptr;
   }
+  p.pages.push_back(p.e);
   p.ns_rows.cap = args.namespaceCapacity;
   p.pod_rows.cap = args.podCapacity;
   p.thr_rows.cap = args.throttleCapacity;
   p.thr_by_row.resize((size_t)args.throttleCapacity);
   p.thr_live.assign((size_t)args.throttleCapacity, 0);
   p.thr_msgs.resize((size_t)args.throttleCapacity);
+  p.count_part.resize((size_t)args.throttleCapacity);
+  p.spec_fp.assign((size_t)args.throttleCapacity, 0);
   for (auto& kv : args.resourceScales) {
-    int d, s;
-    p.dim_of(kv.first, &d, &s, nullptr);
+    DimRef r;
+    if (!p.dim_of(kv.first, &r, err)) return nullptr;
   }
   return k;
 }
 
 // ---------------------------------------------------------------------------------------------------
-// informer feed
+// pages: one engine per KT_MAX_DIMS resource names, every page fed every namespace, pod and throttle
 // ---------------------------------------------------------------------------------------------------
-bool KubeThrottler::OnNamespaceAdd(const Namespace& ns, std::string* err) {
-  std::lock_guard<std::recursive_mutex> lk(p_->mu);
-  auto& p = *p_;
-  const int64_t row = p.ns_rows.acquire(ns.name);
-  if (row < 0) { if (err) *err = "namespace capacity exhausted"; return false; }
+bool KubeThrottler::Impl::upsert_namespace(size_t k, const std::string& name, int32_t row, std::string* err) {
+  auto it = ns_objs.find(name);
   std::vector<uint32_t> keys, pairs;
-  for (auto& kv : ns.labels) keys.push_back(p.key_id(kv.first)), pairs.push_back(p.pair_id(kv.first, kv.second));
+  if (it != ns_objs.end())
+    for (auto& kv : it->second.labels) keys.push_back(key_id(kv.first)), pairs.push_back(pair_id(kv.first, kv.second));
   uint32_t off[2] = {0, (uint32_t)keys.size()};
-  uint8_t valid = 1;
+  // the Namespace OBJECT is gone (or was never seen): the id stays (pods may still reference it), marked invalid
+  uint8_t valid = it != ns_objs.end() ? 1 : 0;
   keys.push_back(0), pairs.push_back(0);
   kt_snapshot b{};
-  b.D = p.D;
+  b.D = D;
   b.n_ns = 1;
   b.ns_valid = &valid;
   b.ns_label_off = off;
   b.ns_label_key = keys.data();
   b.ns_label_pair = pairs.data();
-  const int32_t r32 = (int32_t)row;
-  int32_t rc = kt_upsert_namespaces(p.e, &b, &r32);
-  if (rc != KT_OK) { if (err) *err = p.engine_error(rc); return false; }
+  int32_t rc = kt_upsert_namespaces(pages[k], &b, &row);
+  if (rc != KT_OK) { if (err) *err = engine_error(rc, pages[k]); return false; }
   return true;
 }
 
-bool KubeThrottler::OnNamespaceDelete(const std::string& name, std::string* err) {
-  std::lock_guard<std::recursive_mutex> lk(p_->mu);
-  auto& p = *p_;
-  const int64_t row = p.ns_rows.find(name);
-  if (row < 0) return true;
-  // keep the id (pods may still reference it): the Namespace OBJECT is gone => mark invalid
-  uint32_t off[2] = {0, 0}, zero = 0;
-  uint8_t valid = 0;
-  kt_snapshot b{};
-  b.D = p.D;
-  b.n_ns = 1;
-  b.ns_valid = &valid;
-  b.ns_label_off = off;
-  b.ns_label_key = &zero;
-  b.ns_label_pair = &zero;
-  const int32_t r32 = (int32_t)row;
-  int32_t rc = kt_upsert_namespaces(p.e, &b, &r32);
-  if (rc != KT_OK) { if (err) *err = p.engine_error(rc); return false; }
-  return true;
-}
-
-bool KubeThrottler::OnPodAdd(const Pod& pod, std::string* err) {
-  std::lock_guard<std::recursive_mutex> lk(p_->mu);
-  auto& p = *p_;
-  // the pod's namespace id must exist even when no Namespace object was seen (then it stays invalid)
-  int64_t ns_row = p.ns_rows.find(pod.ns);
-  if (ns_row < 0) {
-    ns_row = p.ns_rows.acquire(pod.ns);
-    if (ns_row < 0) { if (err) *err = "namespace capacity exhausted"; return false; }
-    if (!OnNamespaceDelete(pod.ns, err)) return false;  // registers the id as "no Namespace object"
-  }
-  if ((int)pod.labels.size() > p.args.maxLabels) { if (err) *err = "pod has more labels than maxLabels"; return false; }
-  const int64_t row = p.pod_rows.acquire(pod.Key());
-  if (row < 0) { if (err) *err = "pod capacity exhausted"; return false; }
-  const int D = p.D;
+bool KubeThrottler::Impl::upsert_pod(size_t k, const Pod& pod, int64_t row, uint32_t ns32, std::string* err) {
   std::vector<uint32_t> keys, pairs;
-  for (auto& kv : pod.labels) keys.push_back(p.key_id(kv.first)), pairs.push_back(p.pair_id(kv.first, kv.second));
+  for (auto& kv : pod.labels) keys.push_back(key_id(kv.first)), pairs.push_back(pair_id(kv.first, kv.second));
   uint32_t loff[2] = {0, (uint32_t)keys.size()};
   keys.push_back(0), pairs.push_back(0);
   const size_t nc = pod.containers.size() + pod.initContainers.size();
@@ -535,28 +559,27 @@ bool KubeThrottler::OnPodAdd(const Pod& pod, std::string* err) {
   size_t c = 0;
   for (auto& ic : pod.initContainers) {
     c_init[c] = 1;
-    if (!p.fill_row(ic.requests, &c_req[c * D], &c_present[c], err)) return false;
+    if (!fill_row(ic.requests, (int)k, &c_req[c * D], &c_present[c], err)) return false;
     ++c;
   }
   for (auto& ct : pod.containers) {
-    if (!p.fill_row(ct.requests, &c_req[c * D], &c_present[c], err)) return false;
+    if (!fill_row(ct.requests, (int)k, &c_req[c * D], &c_present[c], err)) return false;
     ++c;
   }
   uint32_t coff[2] = {0, (uint32_t)nc};
   std::vector<int64_t> ovh(D, 0);
   uint32_t ovh_present = 0;
   if (pod.hasOverhead) {
-    if (!p.fill_row(pod.overhead, ovh.data(), &ovh_present, err)) return false;
+    if (!fill_row(pod.overhead, (int)k, ovh.data(), &ovh_present, err)) return false;
     ovh_present |= 0x80000000u;
   }
-  uint32_t ns32 = (uint32_t)ns_row;
   uint32_t flags = KT_POD_VALID;
-  if (pod.schedulerName == p.args.targetSchedulerName) flags |= KT_POD_SCHED_MATCH;
+  if (pod.schedulerName == args.targetSchedulerName) flags |= KT_POD_SCHED_MATCH;
   if (!pod.nodeName.empty()) flags |= KT_POD_SCHEDULED;
   if (pod.phase == "Succeeded" || pod.phase == "Failed") flags |= KT_POD_FINISHED;
   kt_snapshot b{};
   b.D = D;
-  b.L = p.args.maxLabels;
+  b.L = args.maxLabels;
   b.n_pods = 1;
   b.pod_ns = &ns32;
   b.pod_flags = &flags;
@@ -569,24 +592,8 @@ bool KubeThrottler::OnPodAdd(const Pod& pod, std::string* err) {
   b.ctr_req = c_req.data();
   b.pod_ovh_present = &ovh_present;
   b.pod_ovh = ovh.data();
-  int32_t rc = kt_upsert_pods(p.e, &b, &row);
-  if (rc != KT_OK) { if (err) *err = p.engine_error(rc); return false; }
-  p.pods[pod.Key()] = pod;
-  return true;
-}
-
-bool KubeThrottler::OnPodDelete(const std::string& key, std::string* err) {
-  std::lock_guard<std::recursive_mutex> lk(p_->mu);
-  auto& p = *p_;
-  const int64_t row = p.pod_rows.find(key);
-  if (row < 0) return true;
-  auto known = p.pods.find(key);
-  if (known != p.pods.end() && known->second.schedulerName == p.args.targetSchedulerName && !known->second.nodeName.empty())
-    Unreserve(known->second);  // "observe the deleted pod is now scheduled. controller should unreserve it."
-  int32_t rc = kt_delete_pods(p.e, 1, &row);
-  if (rc != KT_OK) { if (err) *err = p.engine_error(rc); return false; }
-  p.pod_rows.release(key);
-  p.pods.erase(key);
+  int32_t rc = kt_upsert_pods(pages[k], &b, &row);
+  if (rc != KT_OK) { if (err) *err = engine_error(rc, pages[k]); return false; }
   return true;
 }
 
@@ -614,32 +621,20 @@ struct ReqPool {
 };
 }  // namespace
 
-bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
-  std::lock_guard<std::recursive_mutex> lk(p_->mu);
-  auto& p = *p_;
-  const int D = p.D;
-  int64_t ns_row = 0;
-  if (!thr.cluster) {
-    ns_row = p.ns_rows.find(thr.ns);
-    if (ns_row < 0) {
-      ns_row = p.ns_rows.acquire(thr.ns);
-      if (ns_row < 0) { if (err) *err = "namespace capacity exhausted"; return false; }
-      if (!OnNamespaceDelete(thr.ns, err)) return false;
-    }
-  }
-  const std::string tk = Impl::thr_key(thr);
-  const bool existed = p.thr_rows.find(tk) >= 0;
-  const int64_t row = p.thr_rows.acquire(tk);
-  if (row < 0) { if (err) *err = "throttle capacity exhausted"; return false; }
+// msgs / fp (nullable): the reference's override messages and their fingerprint (the same for every page)
+bool KubeThrottler::Impl::upsert_throttle(size_t k, const Throttle& thr, int32_t r32, uint32_t ns32, std::vector<std::string>* msgs_out,
+                                          uint64_t* fp_out, std::string* err) {
   DenseAmount spec;
-  if (!p.fill_amount(thr.threshold, &spec, err)) return false;
+  if (!fill_amount(thr.threshold, (int)k, &spec, err)) return false;
   // overrides: parse instants once; unparsable ones are flagged and produce the reference's messages
   const size_t no = thr.overrides.size();
   std::vector<int64_t> ob(no + 1, KT_ZERO_TIME_S), oe(no + 1, KT_ZERO_TIME_S), ov((no + 1) * D, 0), ocount(no + 1, 0);
   std::vector<int32_t> obn(no + 1, 0), oen(no + 1, 0);
   std::vector<uint8_t> oflags(no + 1, 0), ohas(no + 1, 0);
   std::vector<uint32_t> opresent(no + 1, 0);
-  std::vector<std::string> msgs;
+  std::vector<std::string> local_msgs;
+  std::vector<std::string>& msgs = msgs_out ? *msgs_out : local_msgs;
+  msgs.clear();
   for (size_t j = 0; j < no; ++j) {
     const auto& o = thr.overrides[j];
     std::string perr;
@@ -658,9 +653,9 @@ bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
       else ob[j] = KT_ZERO_TIME_S, obn[j] = 0;
     }
     DenseAmount a;
-    if (!p.fill_amount(o.threshold, &a, err)) return false;
+    if (!fill_amount(o.threshold, (int)k, &a, err)) return false;
     std::memcpy(&ov[j * D], a.v, sizeof(int64_t) * D);
-    opresent[j] = a.present;
+    opresent[j] = a.present[0];
     ocount[j] = a.count;
     ohas[j] = a.has_count;
   }
@@ -677,7 +672,7 @@ bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
     bool ok = true;
     for (auto& kv : sel.matchLabels) {
       if (!valid_label_key(kv.first) || !valid_label_value(kv.second)) ok = false;
-      pool.add(KT_OP_IN, p.key_id(kv.first), {p.pair_id(kv.first, kv.second)});
+      pool.add(KT_OP_IN, key_id(kv.first), {pair_id(kv.first, kv.second)});
     }
     for (auto& e : sel.matchExpressions) {
       int op = e.op == "In" ? KT_OP_IN : e.op == "NotIn" ? KT_OP_NOT_IN : e.op == "Exists" ? KT_OP_EXISTS
@@ -689,9 +684,9 @@ bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
       std::vector<uint32_t> vals;
       for (auto& v : e.values) {
         if (!valid_label_value(v)) ok = false;
-        vals.push_back(p.pair_id(e.key, v));
+        vals.push_back(pair_id(e.key, v));
       }
-      pool.add((uint8_t)op, p.key_id(e.key), vals);
+      pool.add((uint8_t)op, key_id(e.key), vals);
     }
     return ok;
   };
@@ -702,8 +697,8 @@ bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
     tno[j + 1] = (uint32_t)(nreq.val_off.size() - 1);
   }
   uint32_t flags = KT_THR_VALID | (thr.cluster ? KT_THR_CLUSTER : 0u);
-  if (thr.throttlerName == p.args.name) flags |= KT_THR_RESPONSIBLE;  // isResponsibleFor (throttle_controller.go:213-215)
-  uint32_t ns32 = (uint32_t)ns_row, zero32 = 0, ooff[2] = {0, (uint32_t)no}, toff[2] = {0, (uint32_t)nt};
+  if (thr.throttlerName == args.name) flags |= KT_THR_RESPONSIBLE;  // isResponsibleFor (throttle_controller.go:213-215)
+  uint32_t zero32 = 0, ooff[2] = {0, (uint32_t)no}, toff[2] = {0, (uint32_t)nt};
   uint64_t zero64 = 0;
   DenseAmount empty;
   kt_snapshot b{};
@@ -711,8 +706,8 @@ bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
   b.n_thr = 1;
   b.thr_flags = &flags;
   b.thr_ns = &ns32;
-  b.thr_spec = kt_amounts{spec.v, &spec.present, &spec.count, &spec.has_count};
-  b.thr_calc = kt_amounts{empty.v, &empty.present, &empty.count, &empty.has_count};
+  b.thr_spec = kt_amounts{spec.v, &spec.present[0], &spec.count, &spec.has_count};
+  b.thr_calc = kt_amounts{empty.v, &empty.present[0], &empty.count, &empty.has_count};
   b.thr_used = b.thr_calc;
   b.thr_reserved = b.thr_calc;
   b.thr_thrl_flag = &zero32;
@@ -732,16 +727,169 @@ bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
   b.term_nreq_off = tno.data();
   b.preq = preq.view();
   b.nreq = nreq.view();
+  int32_t rc = kt_upsert_throttles(pages[k], &b, &r32);
+  if (rc != KT_OK) { if (err) *err = engine_error(rc, pages[k]); return false; }
+  if (fp_out) *fp_out = spec_fp;
+  return true;
+}
+
+// Page k is created the first time a resource name fits none of pages 0..k-1.  It is fed what the host's caches hold —
+// namespaces, pods, throttles (each with ITS names: none of them names the new page's first name, so they carry nothing
+// there yet) and the reserved amounts — and every throttle row that has an applied status gets that status's count part
+// (kt_set_status): its own names carry nothing yet, so the page's state is exact.  Rows are kept aligned with page 0,
+// the highest throttle row ever used included (kt_paged_* require the same throttle-row count on every page).
+bool KubeThrottler::Impl::add_page(std::string* err) {
+  if (pages.size() >= (size_t)kMaxPages) {
+    if (err) *err = "more than " + std::to_string(D * kMaxPages) + " distinct resource names";
+    return false;
+  }
+  kt_engine* ne = nullptr;
+  int32_t rc = kt_engine_create(&cfg, &ne);
+  if (rc != KT_OK) {
+    if (err) *err = std::string("kt_engine_create: ") + std::to_string(rc) + ": " + kt_last_error(nullptr);
+    return false;
+  }
+  pages.push_back(ne);
+  const size_t k = pages.size() - 1;
+  for (auto& kv : ns_rows.row_of)
+    if (!upsert_namespace(k, kv.first, (int32_t)kv.second, err)) return false;
+  for (auto& kv : pod_rows.row_of) {
+    auto pit = pods.find(kv.first);
+    if (pit == pods.end()) continue;
+    if (!upsert_pod(k, pit->second, kv.second, (uint32_t)ns_rows.find(pit->second.ns), err)) return false;
+  }
+  for (int32_t t = 0; t < (int32_t)thr_rows.next; ++t) {
+    if (thr_live[(size_t)t]) {
+      const Throttle& thr = thr_by_row[(size_t)t];
+      const uint32_t ns32 = thr.cluster ? 0u : (uint32_t)ns_rows.find(thr.ns);
+      if (!upsert_throttle(k, thr, t, ns32, nullptr, nullptr, err)) return false;
+      const CountPart& c = count_part[(size_t)t];
+      if (c.set) {
+        DenseAmount used, calc;
+        used.count = c.used_count, used.has_count = c.used_has;
+        calc.count = c.calc_count, calc.has_count = c.calc_has;
+        uint8_t at = c.calc_at_nonzero, pod = c.thrl_pod;
+        uint32_t zero = 0;
+        uint64_t fp = c.msgs_fp;
+        kt_status st{};
+        st.used = kt_amounts{used.v, &used.present[0], &used.count, &used.has_count};
+        st.calc = kt_amounts{calc.v, &calc.present[0], &calc.count, &calc.has_count};
+        st.calc_at_nonzero = &at;
+        st.thrl_flag = &zero;
+        st.thrl_has = &zero;
+        st.thrl_pod = &pod;
+        st.msgs_fp = &fp;
+        if ((rc = kt_set_status(ne, 1, &t, &st)) != KT_OK) { if (err) *err = engine_error(rc, ne); return false; }
+      }
+    } else if (t == (int32_t)thr_rows.next - 1) {  // the highest row page 0 ever held is free now: hold it, then free it
+      Throttle placeholder;
+      if (!upsert_throttle(k, placeholder, t, 0u, nullptr, nullptr, err)) return false;
+      if ((rc = kt_delete_throttles(ne, 1, &t)) != KT_OK) { if (err) *err = engine_error(rc, ne); return false; }
+    }
+  }
+  for (auto& kv : reserved)
+    if (!push_reserved(kv.first, err, (int)k)) return false;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// informer feed
+// ---------------------------------------------------------------------------------------------------
+bool KubeThrottler::OnNamespaceAdd(const Namespace& ns, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  const int64_t row = p.ns_rows.acquire(ns.name);
+  if (row < 0) { if (err) *err = "namespace capacity exhausted"; return false; }
+  p.ns_objs[ns.name] = ns;
+  for (size_t k = 0; k < p.pages.size(); ++k)
+    if (!p.upsert_namespace(k, ns.name, (int32_t)row, err)) return false;
+  return true;
+}
+
+bool KubeThrottler::OnNamespaceDelete(const std::string& name, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  const int64_t row = p.ns_rows.find(name);
+  if (row < 0) return true;
+  p.ns_objs.erase(name);
+  for (size_t k = 0; k < p.pages.size(); ++k)
+    if (!p.upsert_namespace(k, name, (int32_t)row, err)) return false;
+  return true;
+}
+
+bool KubeThrottler::OnPodAdd(const Pod& pod, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  // every resource name of the pod first: a name that fits no page opens one, fed with what the caches hold so far
+  for (auto& ic : pod.initContainers)
+    if (!p.register_names(ic.requests, err)) return false;
+  for (auto& ct : pod.containers)
+    if (!p.register_names(ct.requests, err)) return false;
+  if (pod.hasOverhead && !p.register_names(pod.overhead, err)) return false;
+  // the pod's namespace id must exist even when no Namespace object was seen (then it stays invalid)
+  int64_t ns_row = p.ns_rows.find(pod.ns);
+  if (ns_row < 0) {
+    ns_row = p.ns_rows.acquire(pod.ns);
+    if (ns_row < 0) { if (err) *err = "namespace capacity exhausted"; return false; }
+    if (!OnNamespaceDelete(pod.ns, err)) return false;  // registers the id as "no Namespace object"
+  }
+  if ((int)pod.labels.size() > p.args.maxLabels) { if (err) *err = "pod has more labels than maxLabels"; return false; }
+  const int64_t row = p.pod_rows.acquire(pod.Key());
+  if (row < 0) { if (err) *err = "pod capacity exhausted"; return false; }
+  for (size_t k = 0; k < p.pages.size(); ++k)
+    if (!p.upsert_pod(k, pod, row, (uint32_t)ns_row, err)) return false;
+  p.pods[pod.Key()] = pod;
+  return true;
+}
+
+bool KubeThrottler::OnPodDelete(const std::string& key, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  const int64_t row = p.pod_rows.find(key);
+  if (row < 0) return true;
+  auto known = p.pods.find(key);
+  if (known != p.pods.end() && known->second.schedulerName == p.args.targetSchedulerName && !known->second.nodeName.empty())
+    Unreserve(known->second);  // "observe the deleted pod is now scheduled. controller should unreserve it."
+  for (kt_engine* pe : p.pages) {
+    int32_t rc = kt_delete_pods(pe, 1, &row);
+    if (rc != KT_OK) { if (err) *err = p.engine_error(rc, pe); return false; }
+  }
+  p.pod_rows.release(key);
+  p.pods.erase(key);
+  return true;
+}
+
+bool KubeThrottler::OnThrottleAdd(const Throttle& thr, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  if (!p.register_names(thr.threshold, err)) return false;
+  for (auto& o : thr.overrides)
+    if (!p.register_names(o.threshold, err)) return false;
+  int64_t ns_row = 0;
+  if (!thr.cluster) {
+    ns_row = p.ns_rows.find(thr.ns);
+    if (ns_row < 0) {
+      ns_row = p.ns_rows.acquire(thr.ns);
+      if (ns_row < 0) { if (err) *err = "namespace capacity exhausted"; return false; }
+      if (!OnNamespaceDelete(thr.ns, err)) return false;
+    }
+  }
+  const std::string tk = Impl::thr_key(thr);
+  const int64_t row = p.thr_rows.acquire(tk);
+  if (row < 0) { if (err) *err = "throttle capacity exhausted"; return false; }
   const int32_t r32 = (int32_t)row;
   // The row's stored status starts empty (calculatedAt zero => CheckThrottledFor falls back to spec.threshold,
   // throttle_types.go:129-132) until the next ReconcileAll — the reference enqueues a reconcile for the
   // throttle on the very same Add/Update event (throttle_controller.go:401-417).
-  (void)existed;
-  int32_t rc = kt_upsert_throttles(p.e, &b, &r32);
-  if (rc != KT_OK) { if (err) *err = p.engine_error(rc); return false; }
+  std::vector<std::string> msgs;
+  uint64_t fp = 0;
+  for (size_t k = 0; k < p.pages.size(); ++k)
+    if (!p.upsert_throttle(k, thr, r32, (uint32_t)ns_row, &msgs, &fp, err)) return false;
   p.thr_by_row[(size_t)row] = thr;
   p.thr_live[(size_t)row] = 1;
   p.thr_msgs[(size_t)row] = msgs;
+  p.spec_fp[(size_t)row] = fp;
+  p.count_part[(size_t)row] = CountPart();
   p.written.erase(tk);
   if (!p.push_reserved(r32, err)) return false;
   return true;
@@ -754,10 +902,13 @@ bool KubeThrottler::OnThrottleDelete(const std::string& key, bool cluster, std::
   const int64_t row = p.thr_rows.find(tk);
   if (row < 0) return true;
   const int32_t r32 = (int32_t)row;
-  int32_t rc = kt_delete_throttles(p.e, 1, &r32);
-  if (rc != KT_OK) { if (err) *err = p.engine_error(rc); return false; }
+  for (kt_engine* pe : p.pages) {
+    int32_t rc = kt_delete_throttles(pe, 1, &r32);
+    if (rc != KT_OK) { if (err) *err = p.engine_error(rc, pe); return false; }
+  }
   p.thr_rows.release(tk);
   p.thr_live[(size_t)row] = 0;
+  p.count_part[(size_t)row] = CountPart();
   p.reserved.erase(r32);
   p.written.erase(tk);
   return true;
@@ -787,6 +938,16 @@ static bool check_one(KubeThrottler::Impl& p, const Pod& pod, KubeThrottler* sel
   int32_t T = 0;
   kt_throttle_rows(p.e, &T);
   row_out->assign((size_t)std::max(T, 1), 0);
+  p.last_row_pending = -1;
+  if (p.pages.size() > 1) {  // more than one page: the pages combined (kt_paged_check)
+    const int32_t rc = kt_paged_check(p.pages.data(), (int32_t)p.pages.size(), 1, &row, /*isThrottledOnEqual=*/0, summary, row_out->data());
+    if (rc != KT_OK) {
+      if (err) *err = p.engine_error(rc);
+      return false;
+    }
+    row_out->resize((size_t)T);
+    return true;
+  }
   // the verdict first: one pod, summary word only = the engine's few-pod path (no copy, no stream synchronisation, not
   // queued behind a running reconcile); the status row is only needed to word the reasons of a pod that is not allowed
   int32_t rc = row_always ? KT_OK : kt_check(p.e, 1, &row, /*isThrottledOnEqual=*/0, summary, nullptr);
@@ -890,12 +1051,11 @@ Status KubeThrottler::Reserve(const Pod& pod) {
     st.reasons.push_back("Failed to reserve pod=" + pod.Key() + (err.empty() ? "" : ": " + err));
     return st;
   }
-  // ResourceAmountOfPod as the engine holds it
-  DenseAmount amt;
+  // ResourceAmountOfPod as the engines hold it
+  std::vector<DenseAmount> amts;
   const int64_t prow = p.pod_rows.find(pod.Key());
-  kt_fetch_pod_requests(p.e, 1, &prow, amt.v, &amt.present);
-  amt.has_count = 1;
-  amt.count = 1;
+  p.fetch_pod_amounts(1, &prow, &amts);
+  const DenseAmount& amt = amts[0];
   for (size_t t = 0; t < row.size(); ++t) {
     if (row[t] == KT_STATUS_NOT_AFFECTED) continue;  // affectedThrottles (throttle_controller.go:271-292)
     p.reserved[(int32_t)t][pod.Key()] = amt;
@@ -928,12 +1088,11 @@ bool KubeThrottler::OnPodUpdate(const Pod& old_pod, const Pod& new_pod, std::str
   if (!OnPodAdd(new_pod, err)) return false;  // from here on the engine holds the new object
   const bool ok_after = check_one(p, new_pod, this, &after, &s_after, &ignored) && KT_SUMMARY_VERDICT(s_after) != KT_VERDICT_ERROR;
   if (!ok_before || !ok_after) return true;
-  DenseAmount amt;  // ResourceAmountOfPod(newPod), as the engine computed it
+  std::vector<DenseAmount> amts;  // ResourceAmountOfPod(newPod), as the engines computed it
   const int64_t prow = p.pod_rows.find(new_pod.Key());
-  int32_t rc = kt_fetch_pod_requests(p.e, 1, &prow, amt.v, &amt.present);
+  int32_t rc = p.fetch_pod_amounts(1, &prow, &amts);
   if (rc != KT_OK) { if (err) *err = p.engine_error(rc); return false; }
-  amt.has_count = 1;
-  amt.count = 1;
+  const DenseAmount& amt = amts[0];
   const size_t n = std::max(before.size(), after.size());
   for (size_t t = 0; t < n; ++t) {
     const bool was = t < before.size() && before[t] != KT_STATUS_NOT_AFFECTED;
@@ -984,11 +1143,16 @@ std::vector<Status> KubeThrottler::AdmitQueue(const std::vector<std::string>& po
     kt_throttle_rows(p.e, &T);
     std::vector<uint64_t> summary(m);
     std::vector<uint8_t> status(m * (size_t)(T > 0 ? T : 1));
-    std::vector<int64_t> req(m * (size_t)p.D);
-    std::vector<uint32_t> present(m);
-    int32_t rc = kt_admit_launch(p.e, (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT, nullptr);
-    if (rc == KT_OK) rc = kt_check_fetch(p.e, (int64_t)m, summary.data(), T > 0 ? status.data() : nullptr);
-    if (rc == KT_OK) rc = kt_fetch_pod_requests(p.e, (int64_t)m, rows.data() + i0, req.data(), present.data());
+    std::vector<DenseAmount> amts;
+    int32_t rc;
+    if (p.pages.size() == 1) {
+      rc = kt_admit_launch(p.e, (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT, nullptr);
+      if (rc == KT_OK) rc = kt_check_fetch(p.e, (int64_t)m, summary.data(), T > 0 ? status.data() : nullptr);
+    } else {  // every page: the verdicts combined, the reservations on every page (kt_paged_admit)
+      rc = kt_paged_admit(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT,
+                          summary.data(), T > 0 ? status.data() : nullptr);
+    }
+    if (rc == KT_OK) rc = p.fetch_pod_amounts((int64_t)m, rows.data() + i0, &amts);
     if (rc != KT_OK) {
       for (size_t i = i0; i < i1; ++i) out[i].code = Error, out[i].reasons = {p.engine_error(rc)};
       return;
@@ -1005,11 +1169,7 @@ std::vector<Status> KubeThrottler::AdmitQueue(const std::vector<std::string>& po
         out[i].reasons = block_reasons(p, row, (size_t)T);
         out[i].events = block_events(p, row, (size_t)T);
       } else {
-        DenseAmount amt;
-        for (int d = 0; d < p.D; ++d) amt.v[d] = req[j * (size_t)p.D + d];
-        amt.present = present[j];
-        amt.has_count = 1;
-        amt.count = 1;
+        const DenseAmount& amt = amts[j];
         for (int32_t t = 0; t < T; ++t)
           if (row[t] != KT_STATUS_NOT_AFFECTED) p.reserved[t][pod_keys[i]] = amt;  // the engine already holds the totals
       }
@@ -1058,8 +1218,37 @@ bool KubeThrottler::ReconcileAll(const std::string& now_rfc3339, std::map<std::s
   st.thrl_has = thas.data();
   st.thrl_pod = tpod.data();
   st.error = terr.data();
-  int32_t rc = kt_reconcile_launch(p.e, now_s, now_ns, KT_RECONCILE_APPLY, nullptr);
-  if (rc == KT_OK) rc = kt_reconcile_fetch(p.e, T, &st);
+  // pages 1..: their own names' used / throttled (page_out[k]); the count part, the flags and the next override are page 0's
+  const size_t NP = p.pages.size();
+  std::vector<std::vector<int64_t>> puv(NP), pucount(NP), pcv(NP), pccount(NP);
+  std::vector<std::vector<uint32_t>> pupresent(NP), pcpresent(NP), ptflag(NP), pthas(NP);
+  std::vector<std::vector<uint8_t>> puhas(NP), pchas(NP), pupdated(NP), ptpod(NP), pterr(NP);
+  std::vector<kt_status> page_out(NP, st);
+  for (size_t k = 1; k < NP; ++k) {
+    puv[k].resize(N * D), pucount[k].resize(N), pcv[k].resize(N * D), pccount[k].resize(N);
+    pupresent[k].resize(N), pcpresent[k].resize(N), ptflag[k].resize(N), pthas[k].resize(N);
+    puhas[k].resize(N), pchas[k].resize(N), pupdated[k].resize(N), ptpod[k].resize(N), pterr[k].resize(N);
+    kt_status& o = page_out[k];
+    o.used = kt_amounts{puv[k].data(), pupresent[k].data(), pucount[k].data(), puhas[k].data()};
+    o.calc = kt_amounts{pcv[k].data(), pcpresent[k].data(), pccount[k].data(), pchas[k].data()};
+    o.calc_at_nonzero = pupdated[k].data();
+    o.thrl_flag = ptflag[k].data();
+    o.thrl_has = pthas[k].data();
+    o.thrl_pod = ptpod[k].data();
+    o.error = pterr[k].data();
+  }
+  std::vector<uint8_t> updated0(N);  // page 0's own "replaced" flag: what ITS stored calculatedAt follows
+  int32_t rc;
+  if (NP == 1) {
+    rc = kt_reconcile_launch(p.e, now_s, now_ns, KT_RECONCILE_APPLY, nullptr);
+    if (rc == KT_OK) rc = kt_reconcile_fetch(p.e, T, &st);
+    updated0 = updated;
+  } else {
+    std::vector<uint8_t> replaced_any(N), error_any(N);
+    rc = kt_paged_reconcile(p.pages.data(), (int32_t)NP, now_s, now_ns, KT_RECONCILE_APPLY, T, page_out.data(), replaced_any.data(), error_any.data());
+    updated0 = updated;
+    for (size_t t = 0; t < N; ++t) updated[t] = replaced_any[t], terr[t] = error_any[t];
+  }
   std::vector<int64_t> nx_s((size_t)T + 1);
   std::vector<int32_t> nx_ns((size_t)T + 1);
   std::vector<uint8_t> nx_has((size_t)T + 1);
@@ -1113,9 +1302,24 @@ bool KubeThrottler::ReconcileAll(const std::string& now_rfc3339, std::map<std::s
       }
     }
   }
-  std::vector<std::string> dim_name((size_t)D);
-  std::vector<int> dim_scale((size_t)D, 0);
-  for (auto& kv : p.dims) dim_name[(size_t)kv.second.first] = kv.first, dim_scale[(size_t)kv.second.first] = kv.second.second;
+  // the count part of every applied status, kept for a page that is created later (Impl::add_page); page 0's calculatedAt
+  // becomes non-zero when page 0's calculatedThreshold is replaced, its messages then are the spec's
+  for (int32_t t = 0; t < T; ++t) {
+    if (!p.thr_live[(size_t)t] || p.thr_by_row[(size_t)t].throttlerName != p.args.name || terr[(size_t)t]) continue;
+    CountPart& c = p.count_part[(size_t)t];
+    c.set = true;
+    c.used_count = ucount[(size_t)t], c.used_has = uhas[(size_t)t];
+    c.calc_count = ccount[(size_t)t], c.calc_has = chas[(size_t)t];
+    c.thrl_pod = tpod[(size_t)t];
+    if (updated0[(size_t)t]) c.calc_at_nonzero = 1, c.msgs_fp = p.spec_fp[(size_t)t];
+  }
+  const size_t n_names = (size_t)D * NP;
+  std::vector<std::string> dim_name(n_names);
+  std::vector<int> dim_scale(n_names, 0);
+  for (auto& kv : p.dims) {
+    const size_t g = (size_t)kv.second.page * (size_t)D + (size_t)kv.second.dim;
+    dim_name[g] = kv.first, dim_scale[g] = kv.second.scale;
+  }
   for (int32_t t = 0; t < T; ++t) {
     if (!p.thr_live[(size_t)t] || p.thr_by_row[(size_t)t].throttlerName != p.args.name) continue;
     ThrottleStatus s;
@@ -1128,16 +1332,22 @@ bool KubeThrottler::ReconcileAll(const std::string& now_rfc3339, std::map<std::s
     s.hasNextOverride = nx_has[(size_t)t] != 0;  // NextOverrideHappensIn -> enqueueAfter (throttle_controller.go:201-208)
     s.nextOverrideSec = nx_s[(size_t)t];
     s.nextOverrideNsec = nx_ns[(size_t)t];
-    for (int d = 0; d < D; ++d) {
-      if ((upresent[t] >> d) & 1u) {
-        Quantity q;
-        q.nano = (__int128)uv[(size_t)t * D + d];
-        for (int k = 0; k < 9 + dim_scale[d]; ++k) q.nano *= 10;
-        auto f = p.dim_format.find(dim_name[d]);
-        if (f != p.dim_format.end()) q.format = f->second;
-        s.used[dim_name[d]] = q;
+    for (size_t pg = 0; pg < NP; ++pg) {  // each name from the page that owns it
+      const uint32_t up = pg ? pupresent[pg][(size_t)t] : upresent[t];
+      const int64_t* uvp = pg ? puv[pg].data() : uv.data();
+      const uint32_t th = pg ? pthas[pg][(size_t)t] : thas[t], tf = pg ? ptflag[pg][(size_t)t] : tflag[t];
+      for (int d = 0; d < D; ++d) {
+        const size_t g = pg * (size_t)D + (size_t)d;
+        if ((up >> d) & 1u) {
+          Quantity q;
+          q.nano = (__int128)uvp[(size_t)t * D + d];
+          for (int k = 0; k < 9 + dim_scale[g]; ++k) q.nano *= 10;
+          auto f = p.dim_format.find(dim_name[g]);
+          if (f != p.dim_format.end()) q.format = f->second;
+          s.used[dim_name[g]] = q;
+        }
+        if ((th >> d) & 1u) s.throttledRequests[dim_name[g]] = (tf >> d) & 1u;
       }
-      if ((thas[t] >> d) & 1u) s.throttledRequests[dim_name[d]] = (tflag[t] >> d) & 1u;
     }
     if (!s.error) {  // a reconcile error returns before any status is built (throttle_controller.go:103-106)
       ThrottleStatus& prev = p.written[Impl::thr_key(p.thr_by_row[(size_t)t])];

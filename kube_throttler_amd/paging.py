@@ -124,3 +124,31 @@ class PagedEngine:
         got = np.where(summary == 2, S.VERDICT_ERROR, np.where((summary & 1) != 0, S.VERDICT_BLOCK, S.VERDICT_ALLOW)).astype(np.uint8)
         assert (got == v).all(), "kt_paged_check: summary words disagree with the combined status rows"
         return status, v
+
+    def admit(self, rows=None, on_equal=False, commit=False):
+        """The queue ``rows`` (default: every pod row in order) admitted in order through kt_paged_admit: PreFilter at each
+        pod's turn against the reserved amounts the pods before it left, Reserve on Success on every page (``commit`` keeps
+        the result) -> (status matrix [n][throttles] at each pod's turn, verdict per pod), combined over the pages."""
+        if rows is None:
+            rows = np.arange(self.pages[0].snapshot.n_pods, dtype=np.int64)
+        status, summary = E.paged_admit(self.engines, rows, on_equal=on_equal, commit=commit)
+        v = np.where(summary == 2, S.VERDICT_ERROR, np.where((summary & 1) != 0, S.VERDICT_BLOCK, S.VERDICT_ALLOW)).astype(np.uint8)
+        ok = v != S.VERDICT_ERROR  # (an error row keeps page 0's precomputed status row; its summary word says error)
+        assert (verdicts(status)[ok] == v[ok]).all(), "kt_paged_admit: summary words disagree with the combined status rows"
+        return status, v
+
+    def fetch_reserved(self) -> list:
+        """Reserved amounts per throttle row, put together by resource NAME from the pages (like combine_reconcile):
+        {"resourceCounts": {"pod": n}?, "resourceRequests": {name: Fraction}?}."""
+        tabs = [e.fetch_reserved() for e in self.engines]
+        out = []
+        for i in range(len(self.pages[0].thr_names)):
+            row = {}
+            for b, tab in zip(self.pages, tabs):
+                d = b.amount_to_dict(tab, i)
+                if "resourceCounts" in d:
+                    row["resourceCounts"] = d["resourceCounts"]
+                if "resourceRequests" in d:
+                    row.setdefault("resourceRequests", {}).update(d["resourceRequests"])
+            out.append(row)
+        return out
