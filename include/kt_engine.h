@@ -354,10 +354,10 @@ int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now
  * reserved amounts of every page as the pods admitted before it left them, its verdict the combination above over every page,
  * and on Success ResourceAmountOfPod(pod) added to every affected throttle in every page (each page its own names' amounts; the
  * pod count in every page).  One kt_check of page 0 (which throttles affect which pod: the selector side is the same in every
- * page) and ONE kernel (kt_admit_paged: one wave, the selector scan once per pod, the name part of the four steps evaluated
+ * page) and ONE kernel (kt_admit, the kernel of kt_admit_launch: one wave, the selector scan once per pod, the name part of the four steps evaluated
  * against every page) on page 0's stream.  Synchronous: out_summary [n] and out_status [n][throttle rows] (both nullable)
- * receive what PreFilter returned for pod i AT ITS TURN, combined over the pages; n_pages == 1 gives exactly
- * kt_admit_launch + kt_check_fetch.  flags: KT_ADMIT_COMMIT keeps every page's resulting reserved amounts (kt_fetch_reserved
+ * receive what PreFilter returned for pod i AT ITS TURN, combined over the pages; n_pages == 1 is
+ * kt_admit_launch + kt_check_fetch (the same launch, synchronous).  flags: KT_ADMIT_COMMIT keeps every page's resulting reserved amounts (kt_fetch_reserved
  * per page); without it the call is a dry run.  Duplicate pods: as for kt_admit_launch, every admitted pod ADDS its amount, so
  * a pod whose amount is already reserved, or that occurs twice in the queue, must not be in it.
  * Refused: pages with different throttle-row counts or an engine named twice (KT_ERR_INVALID_ARGUMENT), pages on different

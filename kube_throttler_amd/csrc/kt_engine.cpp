@@ -379,6 +379,7 @@ int32_t kt_engine_destroy(kt_engine* e) {
   e->d_few_ticket.release();
   for (auto& ev : e->recs_ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (e->admit_pages_ev) (void)hipEventDestroy(e->admit_pages_ev);
   if (e->small_stream) (void)hipStreamDestroy(e->small_stream);
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   for (auto& sl : e->ev_slots) {

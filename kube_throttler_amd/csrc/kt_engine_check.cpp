@@ -44,7 +44,7 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
       (pod_rows && e->d_rows.cap < (size_t)n + 1)) {
     if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // buffers may still be in use
     KT_HIP(e, e->d_summary.reserve((size_t)n + 1));
-    if (want_status) KT_HIP(e, e->d_status.reserve((size_t)n * T + 64));  // slack: kt_admit_sequential reads rows 16 bytes at a time
+    if (want_status) KT_HIP(e, e->d_status.reserve((size_t)n * T + 64));  // slack: kt_admit reads rows 16 bytes at a time
     if (pod_rows) KT_HIP(e, e->d_rows.reserve((size_t)n + 1));
   }
   // a handful of pods (one PreFilter call): rows by value, one workgroup per index chunk, summaries to pinned memory
@@ -220,32 +220,56 @@ int32_t kt_sweep_launch(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t fl
 // ---------------------------------------------------------------------------------------------------
 // sequential admission with reservation
 // ---------------------------------------------------------------------------------------------------
+// The queue in order over n_pages >= 1 page engines (one page: the engine itself), on page 0's stream s: one status-matrix check
+// of page 0, then one kt_admit launch.  The caller holds every page's launch lock and has set the device; the results stay on the
+// device behind page 0's check slot (kt_check_fetch).
+static int32_t admit_locked(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
+                            hipStream_t s) {
+  kt_engine* e0 = pages[0];
+  const int32_t T = e0->thr_rows_hi;
+  for (int32_t k = 0; k < n_pages; ++k)
+    if (pages[k]->wide)
+      return pages[k]->fail(KT_ERR_UNSUPPORTED, "admit queue: the stored `used` of page %d is wider than int64 (kt_admit reads int64 tables)", k);
+  if ((double)n * (double)T > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "admit queue: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  // (a) who affects whom, for the whole queue in parallel, from page 0 (selectors, namespaces and responsibility are the same
+  //     in every page; statuses against the current reserved amounts)
+  int32_t rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  if (rc != KT_OK || n == 0 || T == 0) return rc;
+  // (b) the queue in order, one wave, every page's reserved amounts side by side in LDS
+  if (!e0->admit_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->admit_pages_ev, hipEventDisableTiming));
+  KT_HIP(e0, hipEventSynchronize(e0->admit_pages_ev));  // the previous launch's copy has read h_admit_pages
+  e0->h_admit_pages.resize((size_t)n_pages);
+  for (int32_t k = 0; k < n_pages; ++k) {
+    const kt_engine* e = pages[k];
+    e0->h_admit_pages[(size_t)k] = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  }
+  const bool commit = (flags & KT_ADMIT_COMMIT) != 0;
+  KT_HIP(e0, e0->d_admit.reserve(kt::admit_paged_state_bytes(T, e0->h_admit_pages.data(), n_pages) + 64));
+  KT_HIP(e0, e0->d_admit_pages.reserve(sizeof(kt::AdmitPage) * (size_t)n_pages));
+  static const bool force_global = getenv("KT_ADMIT_FORCE_GLOBAL") != nullptr;  // test hook: HBM-resident state
+  hipError_t herr = hipSuccess;
+  const bool launched = kt::launch_admit(e0->h_admit_pages.data(), n_pages, (kt::AdmitPage*)e0->d_admit_pages.p, e0->admit_pages_ev, n,
+                                         pod_rows ? e0->d_rows.p : nullptr, T, on_equal != 0, commit, e0->d_status.p, e0->d_summary.p,
+                                         e0->d_admit.p, force_global, s, &herr);
+  if (herr != hipSuccess) return e0->fail(KT_ERR_DEVICE, "admit queue: copy of the page descriptors: %s", hipGetErrorString(herr));
+  if (!launched) return e0->fail(KT_ERR_UNSUPPORTED, "admit queue: %d throttle rows exceed the kernel's LDS list", T);
+  KT_HIP(e0, hipGetLastError());
+  if (commit)
+    for (int32_t k = 0; k < n_pages; ++k) {
+      kt_engine* e = pages[k];
+      e->reserved_dev_newer = true;
+      std::lock_guard<std::mutex> g(e->recs_mu);
+      e->recs_valid = false;
+    }
+  return KT_OK;
+}
+
 int32_t kt_admit_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags, void* stream) {
   if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
-  hipStream_t s = pick_stream(e, stream);
-  if (e->wide)
-    return e->fail(KT_ERR_UNSUPPORTED, "admit queue: the stored `used` of this engine is wider than int64 (kt_admit_sequential reads int64 tables)");
-  if ((double)n * (double)e->thr_rows_hi > 2147483648.0)
-    return e->fail(KT_ERR_OUT_OF_RANGE, "admit queue: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, e->thr_rows_hi);
-  // (a) who affects whom, for the whole queue in parallel (statuses against the current reserved amounts)
-  int32_t rc = check_launch_locked(e, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
-  if (rc != KT_OK || n == 0 || e->thr_rows_hi == 0) return rc;
-  // (b) the queue in order, one wave, reserved amounts in LDS
-  const bool commit = (flags & KT_ADMIT_COMMIT) != 0;
-  KT_HIP(e, e->d_admit.reserve(kt::admit_state_bytes(e->thr_rows_hi, e->D) + 64));
-  static const bool force_global = getenv("KT_ADMIT_FORCE_GLOBAL") != nullptr;  // test hook: HBM-resident state
-  if (!kt::launch_admit(e->pods, n, pod_rows ? e->d_rows.p : nullptr, e->tt, e->thr_rows_hi, e->D, on_equal != 0, commit,
-                        e->d_status.p, e->d_summary.p, e->d_admit.p, force_global, s))
-    return e->fail(KT_ERR_UNSUPPORTED, "admit queue: %d throttle rows exceed the kernel's LDS list", e->thr_rows_hi);
-  KT_HIP(e, hipGetLastError());
-  if (commit) {
-    e->reserved_dev_newer = true;
-    std::lock_guard<std::mutex> g(e->recs_mu);
-    e->recs_valid = false;
-  }
-  return KT_OK;
+  return admit_locked(&e, 1, n, pod_rows, on_equal, flags, pick_stream(e, stream));
 }
 
 int32_t kt_fetch_reserved(kt_engine* e, int32_t n, const int32_t* rows, const kt_amounts* out) {
@@ -449,7 +473,7 @@ int32_t kt_paged_check(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
   return KT_OK;
 }
 
-// kt_admit_launch over the pages: one kt_admit_paged launch on page 0's stream after one status-matrix check of page 0
+// kt_admit_launch over several engines, synchronous: what is specific to more than one engine, then admit_locked
 int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
                        uint64_t* out_summary, uint8_t* out_status) {
   if (!pages || n_pages < 1 || n < 0) return KT_ERR_INVALID_ARGUMENT;
@@ -469,8 +493,6 @@ int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
     kt_engine* e = pages[k];
     if (e->thr_rows_hi != T) return e->fail(KT_ERR_INVALID_ARGUMENT, "page %d holds %d throttle rows, page 0 %d: every page holds every throttle", k, e->thr_rows_hi, T);
     if (e->device != e0->device) return e->fail(KT_ERR_UNSUPPORTED, "paged admit: page %d is on device %d, page 0 on %d", k, e->device, e0->device);
-    if (e->wide)
-      return e->fail(KT_ERR_UNSUPPORTED, "paged admit: the stored `used` of page %d is wider than int64 (kt_admit_paged reads int64 tables)", k);
     if (pod_rows) {
       for (int64_t i = 0; i < n; ++i)
         if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "page %d: pod row %lld", k, (long long)pod_rows[i]);
@@ -478,8 +500,6 @@ int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
       return e->fail(KT_ERR_OUT_OF_RANGE, "page %d: n=%lld > pod_capacity", k, (long long)n);
     }
   }
-  if ((double)n * (double)T > 2147483648.0)
-    return e0->fail(KT_ERR_OUT_OF_RANGE, "paged admit: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
   if (n == 0) return KT_OK;
   KT_HIP(e0, hipSetDevice(e0->device));
   hipStream_t s = pick_stream(e0, nullptr);
@@ -494,39 +514,12 @@ int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
     if (e->last_stream && e->last_stream != e->own_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
     order_behind_ingest(e, s);
   }
-  // (a) who affects whom, from page 0 (selectors, namespaces and responsibility are the same in every page)
-  int32_t rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
-  if (rc != KT_OK) return rc;
+  const int32_t rc = admit_locked(pages, n_pages, n, pod_rows, on_equal, flags, s);
   e0->check_ready = false;  // the call used page 0's check slot (as kt_affected_pods): a pending kt_check_launch is gone
-  // the descriptors' host copy lives until the stream synchronisation below (hipMemcpyAsync from pageable memory)
-  std::vector<kt::AdmitPage> desc((size_t)n_pages);
-  if (T > 0) {
-    // (b) the queue in order, one wave, every page's reserved amounts side by side
-    for (int32_t k = 0; k < n_pages; ++k) {
-      const kt_engine* e = pages[k];
-      desc[k] = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
-    }
-    const bool commit = (flags & KT_ADMIT_COMMIT) != 0;
-    KT_HIP(e0, e0->d_admit.reserve(kt::admit_paged_state_bytes(T, desc.data(), n_pages) + 64));
-    KT_HIP(e0, e0->d_admit_pages.reserve(sizeof(kt::AdmitPage) * (size_t)n_pages));
-    static const bool force_global = getenv("KT_ADMIT_FORCE_GLOBAL") != nullptr;  // test hook: HBM-resident state
-    hipError_t herr = hipSuccess;
-    const bool launched = kt::launch_admit_paged(desc.data(), n_pages, (kt::AdmitPage*)e0->d_admit_pages.p, n, pod_rows ? e0->d_rows.p : nullptr,
-                                                 T, on_equal != 0, commit, e0->d_status.p, e0->d_summary.p, e0->d_admit.p, force_global, s, &herr);
-    if (herr != hipSuccess) return e0->fail(KT_ERR_DEVICE, "paged admit: copy of the page descriptors: %s", hipGetErrorString(herr));
-    if (!launched) return e0->fail(KT_ERR_UNSUPPORTED, "paged admit: %d throttle rows exceed the kernel's LDS list", T);
-    KT_HIP(e0, hipGetLastError());
-    if (commit)
-      for (int32_t k = 0; k < n_pages; ++k) {
-        kt_engine* e = pages[k];
-        e->reserved_dev_newer = true;
-        std::lock_guard<std::mutex> g(e->recs_mu);
-        e->recs_valid = false;
-      }
-  }
+  if (rc != KT_OK) return rc;
   if (out_summary) KT_HIP(e0, hipMemcpyAsync(out_summary, e0->d_summary.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   if (out_status && T > 0) KT_HIP(e0, hipMemcpyAsync(out_status, e0->d_status.p, (size_t)n * (size_t)T, hipMemcpyDeviceToHost, s));
-  KT_HIP(e0, hipStreamSynchronize(s));  // (also: from here on `desc` is no longer read)
+  KT_HIP(e0, hipStreamSynchronize(s));
   return KT_OK;
 }
 

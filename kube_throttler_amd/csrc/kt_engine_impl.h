@@ -305,8 +305,13 @@ struct kt_engine {
 
   // ---- reconcile state
   DevBuf<unsigned long long> d_partial;
-  DevBuf<uint8_t> d_admit;  // HBM-resident state of kt_admit_sequential when it does not fit LDS
-  DevBuf<uint8_t> d_admit_pages;  // page descriptors of kt_paged_admit (on page 0)
+  DevBuf<uint8_t> d_admit;  // HBM-resident state of kt_admit when it does not fit LDS (on page 0: every page's)
+  DevBuf<uint8_t> d_admit_pages;  // page descriptors of kt_admit (on page 0)
+  // Host copy of the descriptors, the source of an ASYNCHRONOUS copy to d_admit_pages (kt_admit_launch returns before the stream
+  // has run).  Rule: written only by admit_locked (op_mu held), and only after admit_pages_ev — recorded right behind the last
+  // copy that read it — has completed; freed only after that too (kt_engine_destroy synchronises first).
+  std::vector<kt::AdmitPage> h_admit_pages;
+  hipEvent_t admit_pages_ev = nullptr;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;

@@ -19,22 +19,12 @@
 //   output  per-pod summary words, the rewritten matrix, and (commit) the reserved tables in HBM.
 // When the state does not fit in LDS (thousands of throttles) it lives in an HBM scratch buffer instead (same code,
 // L2 latency per step).
+// There is ONE kernel, kt_admit<DT, IN_LDS>, over n_pages >= 1 page descriptors in device memory (a page = an engine of
+// <= 16 resource names): kt_admit_launch is the one-page case of kt_paged_admit.  Step (2) is the name part of every page
+// OR-ed with the count part of page 0, step (4) reserves on every page.
 #include "kt_index_device.h"
 
 namespace kt {
-
-struct AdmitArgs {
-  const uint32_t* pod_flags;
-  const int64_t* req;
-  const int64_t* rows;  // nullable: queue position -> pod table row
-  int64_t n;
-  ThrTables tt;
-  unsigned char* scratch;  // state in HBM when it does not fit LDS (nullable)
-  uint8_t* status;    // [n][T] in/out
-  uint64_t* summary;  // [n] out
-  int32_t T, D, DS, on_equal, commit;
-  uint32_t off_rv, off_rc, off_rp, off_list, list_cap;
-};
 
 struct AdmitPagedArgs {
   const AdmitPage* pages;  // [n_pages] in device memory (ThrTables is too large to pass by value per page)
@@ -150,93 +140,6 @@ __device__ __forceinline__ uint32_t admit_affected(const uint8_t* row, int T, ld
   return n_aff;
 }
 
-template <int DT, bool IN_LDS>
-__global__ __launch_bounds__(kWave) void kt_admit_sequential(const AdmitArgs a) {
-  KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
-  const AdmitState<IN_LDS> st = admit_state_at<IN_LDS>(lds, a.scratch, a.off_rv, a.off_rc, a.off_rp);
-  lds_u32wp list = (lds_u32wp)(lds + a.off_list);            // affected throttles of the current pod
-  const int T = a.T, D = a.D;
-  const uint32_t lane = threadIdx.x;
-  const ThrTables& tt = a.tt;
-  admit_load_state(st, tt, T, D);
-  if (!IN_LDS) __threadfence();
-  constexpr int MPW = kWave / DT;
-  const uint32_t d = lane % DT, ml = lane / DT;
-  const bool d_in = (int)d < D;
-  const bool eq = a.on_equal != 0;
-  for (int64_t i = 0; i < a.n; ++i) {
-    const int64_t p = a.rows ? a.rows[i] : i;
-    const uint32_t fl = a.pod_flags[p];
-    const uint32_t present = fl >> kPresentShift;
-    uint8_t* row = a.status + i * T;
-    // ---- (1) affected throttles: nonzero bytes of the matrix row, 16 per lane and chunk
-    bool err;
-    const uint32_t n_aff = admit_affected(row, T, list, a.list_cap, &err);
-    if (__ballot(err) != 0ull || !(fl & kPodValid) || n_aff > a.list_cap) {
-      // error row (selector / namespace error, plugin.go:154-168), empty row, or a pod affected by more
-      // throttles than the list holds: the pre-computed summary stands and nothing is reserved
-      continue;
-    }
-    // ---- (2) lane = (affected throttle, dimension)
-    uint32_t n_exc = 0, n_act = 0, n_ins = 0;
-    const int64_t v = d_in ? a.req[p * a.DS + d] : 0;
-    const bool nz = v != 0;
-    for (uint32_t base = 0; base < n_aff; base += MPW) {
-      const uint32_t j = base + ml;
-      const bool vv = j < n_aff;
-      const uint32_t t = list[vv ? j : 0u];
-      const uint32_t tf = tt.flags[t];
-      // threshold := status.calculatedThreshold if calculatedAt != zero else spec.threshold (throttle_types.go:129-132)
-      const AmountTab& th = (tf & kThrCalcAtNonzero) ? tt.calc : tt.spec;
-      const uint32_t th_p = th.present[t], u_p = tt.used.present[t], r_pw = st.ld_p(t);
-      const bool eq3 = (tf & kThrCluster) ? eq : true;  // throttle_types.go:143 vs clusterthrottle_types.go:45
-      uint32_t bits = 0;
-      if (vv && d_in && ((th_p >> d) & 1u)) {
-        const int64_t tv = th.v[(size_t)t * D + d];
-        const int64_t uv = ((u_p >> d) & 1u) ? tt.used.v[(size_t)t * D + d] : 0;
-        const int64_t rvd = st.ld_v(t * D + d);
-        if (nz && v > tv) bits |= 1u;                                                        // step 1
-        if (nz && (((u_p | r_pw) >> d) & 1u) && admit_cmp((__int128)uv + rvd, tv, eq3)) bits |= 2u;    // step 3
-        if (nz && admit_cmp((__int128)uv + v + rvd, tv, eq)) bits |= 4u;                               // step 4
-      }
-      if (vv && nz && ((tt.thrl_flag[t] & tt.thrl_has[t]) >> d) & 1u) bits |= 2u;            // step 2
-      if (vv && d == 0) {  // resourceCounts.pod
-        const bool th_hc = th.has_count[t] != 0;
-        const int64_t th_c = th.count[t];
-        const bool u_hc = tt.used.has_count[t] != 0, r_hc = (r_pw >> 31) != 0;
-        const int64_t u_c = u_hc ? tt.used.count[t] : 0, r_c = st.ld_c(t);
-        if (th_hc && 1 > th_c) bits |= 1u;
-        if ((tf & kThrThrottledPod) || (th_hc && (u_hc || r_hc) && admit_cmp((__int128)u_c + r_c, th_c, eq3))) bits |= 2u;
-        if (th_hc && admit_cmp((__int128)u_c + 1 + r_c, th_c, eq)) bits |= 4u;
-      }
-#pragma unroll
-      for (int o = DT / 2; o >= 1; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, o);
-      const uint32_t st = (bits & 1u) ? 4u : (bits & 2u) ? 2u : (bits & 4u) ? 3u : 1u;
-      const bool lead = vv && d == 0;
-      if (lead) row[t] = (uint8_t)st;
-      n_exc += (uint32_t)__popcll(__ballot(lead && st == 4u));
-      n_act += (uint32_t)__popcll(__ballot(lead && st == 2u));
-      n_ins += (uint32_t)__popcll(__ballot(lead && st == 3u));
-    }
-    if (lane == 0) a.summary[i] = pack_summary(n_exc, n_act, n_ins, false);
-    // ---- (4) Success: Reserve on every affected throttle
-    if ((n_exc | n_act | n_ins) == 0) {
-      for (uint32_t base = 0; base < n_aff; base += MPW) {
-        const uint32_t j = base + ml;
-        if (j < n_aff) {
-          const uint32_t t = list[j];
-          if (d_in && ((present >> d) & 1u)) st.st_v(t * D + d, st.ld_v(t * D + d) + v);
-          if (d == 0) {
-            st.st_c(t, st.ld_c(t) + 1);
-            st.st_p(t, st.ld_p(t) | present | 0x80000000u);
-          }
-        }
-      }
-    }
-  }
-  if (a.commit) admit_store_state(st, tt, T, D);
-}
-
 // a page descriptor by value: read through the constant address space (nothing writes the descriptors while the kernel
 // runs), so the wave-uniform fields come in with scalar loads into SGPRs
 __device__ __forceinline__ AdmitPage admit_page(const AdmitPage* pages, int k) {
@@ -247,19 +150,93 @@ __device__ __forceinline__ AdmitPage admit_page(const AdmitPage* pages, int k) {
 #endif
 }
 
-// ---- the paged form (kt_paged_admit): one wave, the queue in order, every page's state side by side.  Page 0's status matrix
-// gives the affected list once per pod (selectors, namespaces and responsibility are the same in every page); the name part of
-// the four steps is evaluated against every page's tables and reserved state and OR-ed before the reduction (exceeds > active >
-// insufficient, as kt_paged_check combines), the count part once, on page 0; Success reserves on every page.
+// threshold := status.calculatedThreshold if calculatedAt != zero else spec.threshold (throttle_types.go:129-132)
+__device__ __forceinline__ const AmountTab& admit_threshold(const ThrTables& tt, uint32_t tf) { return (tf & kThrCalcAtNonzero) ? tt.calc : tt.spec; }
+// isThrottledOnEqual of step 3: always for a Throttle, the caller's for a ClusterThrottle (throttle_types.go:143 vs
+// clusterthrottle_types.go:45)
+__device__ __forceinline__ bool admit_eq3(uint32_t tf, bool eq) { return (tf & kThrCluster) ? eq : true; }
+
+// (2) resourceCounts.pod of throttle t -> verdict bits (1 exceeds, 2 active, 4 insufficient)
+template <bool IN_LDS>
+__device__ __forceinline__ uint32_t admit_count_bits(const ThrTables& tt, const AdmitState<IN_LDS>& st, uint32_t t, bool eq) {
+  const uint32_t tf = tt.flags[t];
+  const AmountTab& th = admit_threshold(tt, tf);
+  const bool eq3 = admit_eq3(tf, eq);
+  const bool th_hc = th.has_count[t] != 0;
+  const int64_t th_c = th.count[t];
+  const bool u_hc = tt.used.has_count[t] != 0, r_hc = (st.ld_p(t) >> 31) != 0;
+  const int64_t u_c = u_hc ? tt.used.count[t] : 0, r_c = st.ld_c(t);
+  uint32_t bits = 0;
+  if (th_hc && 1 > th_c) bits |= 1u;
+  if ((tf & kThrThrottledPod) || (th_hc && (u_hc || r_hc) && admit_cmp((__int128)u_c + r_c, th_c, eq3))) bits |= 2u;
+  if (th_hc && admit_cmp((__int128)u_c + 1 + r_c, th_c, eq)) bits |= 4u;
+  return bits;
+}
+
+// (2) the name part of one page for lane (t, d): the four CheckThrottledFor steps of dimension d of the page's names for
+// pod row p against the page's threshold / status.used / status.throttled and its CURRENT reserved row -> verdict bits
+template <bool IN_LDS>
+__device__ __forceinline__ uint32_t admit_name_bits(const AdmitPage& pg, const AdmitState<IN_LDS>& st, int64_t p, uint32_t t, uint32_t d,
+                                                    bool eq) {
+  const ThrTables& tt = pg.tt;
+  const int D = pg.D;
+  if ((int)d >= D) return 0u;
+  const int64_t v = pg.req[p * pg.DS + d];
+  if (v == 0) return 0u;  // steps 1-4 of a name the pod does not request
+  const uint32_t tf = tt.flags[t];
+  const AmountTab& th = admit_threshold(tt, tf);
+  const bool eq3 = admit_eq3(tf, eq);
+  const uint32_t th_p = th.present[t], u_p = tt.used.present[t], r_pw = st.ld_p(t);
+  uint32_t bits = 0;
+  if ((th_p >> d) & 1u) {
+    const int64_t tv = th.v[(size_t)t * D + d];
+    const int64_t uv = ((u_p >> d) & 1u) ? tt.used.v[(size_t)t * D + d] : 0;
+    const int64_t rvd = st.ld_v(t * D + d);
+    if (v > tv) bits |= 1u;                                                               // step 1
+    if ((((u_p | r_pw) >> d) & 1u) && admit_cmp((__int128)uv + rvd, tv, eq3)) bits |= 2u;  // step 3
+    if (admit_cmp((__int128)uv + v + rvd, tv, eq)) bits |= 4u;                             // step 4
+  }
+  if (((tt.thrl_flag[t] & tt.thrl_has[t]) >> d) & 1u) bits |= 2u;                         // step 2
+  return bits;
+}
+
+// (4) Reserve on one page: its own names' amounts of pod row p, the count and has_count, on every affected throttle
 template <int DT, bool IN_LDS>
-__global__ __launch_bounds__(kWave) void kt_admit_paged(const AdmitPagedArgs a) {
+__device__ __forceinline__ void admit_reserve(const AdmitPage& pg, const AdmitState<IN_LDS>& st, int64_t p, lds_u32wp list, uint32_t n_aff) {
+  constexpr int MPW = kWave / DT;
+  const uint32_t d = threadIdx.x % DT, ml = threadIdx.x / DT;
+  const int D = pg.D;
+  const uint32_t present = pg.pod_flags[p] >> kPresentShift;
+  const bool d_in = (int)d < D;
+  const int64_t v = d_in ? pg.req[p * pg.DS + d] : 0;
+  for (uint32_t base = 0; base < n_aff; base += MPW) {
+    const uint32_t j = base + ml;
+    if (j < n_aff) {
+      const uint32_t t = list[j];
+      if (d_in && ((present >> d) & 1u)) st.st_v(t * D + d, st.ld_v(t * D + d) + v);
+      if (d == 0) {
+        st.st_c(t, st.ld_c(t) + 1);
+        st.st_p(t, st.ld_p(t) | present | 0x80000000u);
+      }
+    }
+  }
+}
+
+// One wave, the queue in order, the state of every page (an engine of <= 16 resource names; one page is the plain engine) side
+// by side.  Page 0's status matrix gives the affected list once per pod (selectors, namespaces and responsibility are the same
+// in every page); the name part of the four steps is evaluated against every page's tables and reserved state and OR-ed before
+// the reduction (exceeds > active > insufficient, as kt_paged_check combines), the count part once, on page 0; Success
+// reserves on every page.
+template <int DT, bool IN_LDS>
+__global__ __launch_bounds__(kWave) void kt_admit(const AdmitPagedArgs a) {
   KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
-  lds_u32wp list = (lds_u32wp)(lds + a.off_list);
+  lds_u32wp list = (lds_u32wp)(lds + a.off_list);  // affected throttles of the current pod
   const int T = a.T, n_pages = a.n_pages;
   const uint32_t lane = threadIdx.x;
+  auto state_of = [&](const AdmitPage& pg) { return admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp); };
   for (int k = 0; k < n_pages; ++k) {
     const AdmitPage pg = admit_page(a.pages, k);
-    admit_load_state(admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp), pg.tt, T, pg.D);
+    admit_load_state(state_of(pg), pg.tt, T, pg.D);
   }
   if (!IN_LDS) __threadfence();
   constexpr int MPW = kWave / DT;
@@ -268,9 +245,15 @@ __global__ __launch_bounds__(kWave) void kt_admit_paged(const AdmitPagedArgs a) 
   for (int64_t i = 0; i < a.n; ++i) {
     const int64_t p = a.rows ? a.rows[i] : i;
     uint8_t* row = a.status + i * T;
+    // ---- (1) affected throttles: nonzero bytes of the matrix row, 16 per lane and chunk
     bool err;
     const uint32_t n_aff = admit_affected(row, T, list, a.list_cap, &err);
-    if (__ballot(err) != 0ull || !(admit_page(a.pages, 0).pod_flags[p] & kPodValid) || n_aff > a.list_cap) continue;  // page 0's summary stands
+    if (__ballot(err) != 0ull || !(admit_page(a.pages, 0).pod_flags[p] & kPodValid) || n_aff > a.list_cap) {
+      // error row (selector / namespace error, plugin.go:154-168), empty row, or a pod affected by more
+      // throttles than the list holds: the pre-computed summary stands and nothing is reserved
+      continue;
+    }
+    // ---- (2) lane = (affected throttle, dimension), over every page
     uint32_t n_exc = 0, n_act = 0, n_ins = 0;
     for (uint32_t base = 0; base < n_aff; base += MPW) {
       const uint32_t j = base + ml;
@@ -279,38 +262,14 @@ __global__ __launch_bounds__(kWave) void kt_admit_paged(const AdmitPagedArgs a) 
       uint32_t bits = 0;
       for (int k = 0; k < n_pages; ++k) {
         const AdmitPage pg = admit_page(a.pages, k);
-        const ThrTables& tt = pg.tt;
-        const int D = pg.D;
         if (!vv) continue;
-        const AdmitState<IN_LDS> st = admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp);
-        const uint32_t tf = tt.flags[t];
-        const AmountTab& th = (tf & kThrCalcAtNonzero) ? tt.calc : tt.spec;
-        const bool eq3 = (tf & kThrCluster) ? eq : true;
-        if (k == 0 && d == 0) {  // resourceCounts.pod: the same in every page, evaluated on page 0
-          const bool th_hc = th.has_count[t] != 0;
-          const int64_t th_c = th.count[t];
-          const bool u_hc = tt.used.has_count[t] != 0, r_hc = (st.ld_p(t) >> 31) != 0;
-          const int64_t u_c = u_hc ? tt.used.count[t] : 0, r_c = st.ld_c(t);
-          if (th_hc && 1 > th_c) bits |= 1u;
-          if ((tf & kThrThrottledPod) || (th_hc && (u_hc || r_hc) && admit_cmp((__int128)u_c + r_c, th_c, eq3))) bits |= 2u;
-          if (th_hc && admit_cmp((__int128)u_c + 1 + r_c, th_c, eq)) bits |= 4u;
-        }
-        if ((int)d >= D) continue;  // name part: dimension d of every page
-        const int64_t v = pg.req[p * pg.DS + d];
-        if (v == 0) continue;  // steps 1-4 of a name the pod does not request
-        const uint32_t th_p = th.present[t], u_p = tt.used.present[t], r_pw = st.ld_p(t);
-        if ((th_p >> d) & 1u) {
-          const int64_t tv = th.v[(size_t)t * D + d];
-          const int64_t uv = ((u_p >> d) & 1u) ? tt.used.v[(size_t)t * D + d] : 0;
-          const int64_t rvd = st.ld_v(t * D + d);
-          if (v > tv) bits |= 1u;                                                               // step 1
-          if ((((u_p | r_pw) >> d) & 1u) && admit_cmp((__int128)uv + rvd, tv, eq3)) bits |= 2u;  // step 3
-          if (admit_cmp((__int128)uv + v + rvd, tv, eq)) bits |= 4u;                             // step 4
-        }
-        if (((tt.thrl_flag[t] & tt.thrl_has[t]) >> d) & 1u) bits |= 2u;                         // step 2
+        const AdmitState<IN_LDS> st = state_of(pg);
+        if (k == 0 && d == 0) bits |= admit_count_bits(pg.tt, st, t, eq);  // the same in every page
+        bits |= admit_name_bits(pg, st, p, t, d, eq);
       }
 #pragma unroll
       for (int o = DT / 2; o >= 1; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, o);
+      // ---- (3) the status the pod met on throttle t, the summary word as PreFilter would return it at this point
       const uint32_t stc = (bits & 1u) ? 4u : (bits & 2u) ? 2u : (bits & 4u) ? 3u : 1u;
       const bool lead = vv && d == 0;
       if (lead) row[t] = (uint8_t)stc;
@@ -320,31 +279,16 @@ __global__ __launch_bounds__(kWave) void kt_admit_paged(const AdmitPagedArgs a) 
     }
     if (lane == 0) a.summary[i] = pack_summary(n_exc, n_act, n_ins, false);
     if ((n_exc | n_act | n_ins) != 0) continue;
-    // Success: Reserve on every page (its own names' amounts; the count and has_count in every page)
+    // ---- (4) Success: Reserve on every page
     for (int k = 0; k < n_pages; ++k) {
       const AdmitPage pg = admit_page(a.pages, k);
-      const int D = pg.D;
-      const AdmitState<IN_LDS> st = admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp);
-      const uint32_t present = pg.pod_flags[p] >> kPresentShift;
-      const bool d_in = (int)d < D;
-      const int64_t v = d_in ? pg.req[p * pg.DS + d] : 0;
-      for (uint32_t base = 0; base < n_aff; base += MPW) {
-        const uint32_t j = base + ml;
-        if (j < n_aff) {
-          const uint32_t t = list[j];
-          if (d_in && ((present >> d) & 1u)) st.st_v(t * D + d, st.ld_v(t * D + d) + v);
-          if (d == 0) {
-            st.st_c(t, st.ld_c(t) + 1);
-            st.st_p(t, st.ld_p(t) | present | 0x80000000u);
-          }
-        }
-      }
+      admit_reserve<DT>(pg, state_of(pg), p, list, n_aff);
     }
   }
   if (a.commit)
     for (int k = 0; k < n_pages; ++k) {
       const AdmitPage pg = admit_page(a.pages, k);
-      admit_store_state(admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp), pg.tt, T, pg.D);
+      admit_store_state(state_of(pg), pg.tt, T, pg.D);
     }
 }
 
@@ -353,47 +297,16 @@ size_t admit_state_bytes(int T, int D) {
   return ((size_t)T * D * 8 + 15) / 16 * 16 + ((size_t)T * 8 + 15) / 16 * 16 + ((size_t)T * 4 + 15) / 16 * 16;
 }
 
-// scratch: admit_state_bytes(T, D) bytes of device memory, used when the state does not fit in LDS (or when forced)
-bool launch_admit(const PodTable& pods, int64_t n, const int64_t* rows_dev, const ThrTables& tt, int T, int D,
-                  bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global,
-                  hipStream_t s) {
-  const size_t list_bytes = ((size_t)T * 4 + 15) / 16 * 16;
-  const bool in_lds = !force_global && admit_state_bytes(T, D) + list_bytes <= (size_t)kMaxLds;
-  if (!in_lds && (!scratch || list_bytes > (size_t)kMaxLds)) return false;
-  AdmitArgs a{};
-  a.pod_flags = pods.flags, a.req = pods.req, a.rows = rows_dev, a.n = n, a.tt = tt;
-  a.status = status, a.summary = summary, a.scratch = (unsigned char*)scratch;
-  a.T = T, a.D = D, a.DS = pods.DS, a.on_equal = on_equal ? 1 : 0, a.commit = commit ? 1 : 0;
-  uint32_t o = 0;
-  auto take = [&](size_t bytes) { uint32_t r = o; o += (uint32_t)((bytes + 15) & ~(size_t)15); return r; };
-  a.off_rv = take((size_t)T * D * 8);  // offsets inside LDS or inside the scratch buffer
-  a.off_rc = take((size_t)T * 8);
-  a.off_rp = take((size_t)T * 4);
-  a.list_cap = (uint32_t)T;  // a pod can be affected by every throttle
-  if (!in_lds) o = 0;
-  a.off_list = take((size_t)a.list_cap * 4);
-  const int DT = dt_bucket(D);
-  const size_t lds_bytes = o;
-#define KT_ADMIT_CASE(DT_)                                                                                        \
-  {                                                                                                              \
-    auto kfn = in_lds ? kt_admit_sequential<DT_, true> : kt_admit_sequential<DT_, false>;                        \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
-    hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a);                                              \
-  }
-  if (DT == 4) KT_ADMIT_CASE(4) else if (DT == 8) KT_ADMIT_CASE(8) else KT_ADMIT_CASE(16)
-#undef KT_ADMIT_CASE
-  return true;
-}
-
 size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages) {
   size_t b = 0;
   for (int k = 0; k < n_pages; ++k) b += admit_state_bytes(T, pages[k].D);
   return b;
 }
 
-bool launch_admit_paged(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, int64_t n, const int64_t* rows_dev, int T,
-                        bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global,
-                        hipStream_t s, hipError_t* hip_err) {
+// scratch: admit_paged_state_bytes bytes of device memory, used when the state does not fit in LDS (or when forced)
+bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
+                  bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global, hipStream_t s,
+                  hipError_t* hip_err) {
   *hip_err = hipSuccess;
   const size_t list_bytes = ((size_t)T * 4 + 15) / 16 * 16;
   const bool in_lds = !force_global && admit_paged_state_bytes(T, pages, n_pages) + list_bytes <= (size_t)kMaxLds;
@@ -411,14 +324,15 @@ bool launch_admit_paged(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, int
   AdmitPagedArgs a{};
   a.pages = pages_dev, a.n_pages = n_pages, a.rows = rows_dev, a.n = n, a.scratch = (unsigned char*)scratch;
   a.status = status, a.summary = summary, a.T = T, a.on_equal = on_equal ? 1 : 0, a.commit = commit ? 1 : 0;
-  a.list_cap = (uint32_t)T;
+  a.list_cap = (uint32_t)T;  // a pod can be affected by every throttle
   a.off_list = take((size_t)a.list_cap * 4);
   const size_t lds_bytes = o;
   if ((*hip_err = hipMemcpyAsync(pages_dev, pages, sizeof(AdmitPage) * (size_t)n_pages, hipMemcpyHostToDevice, s)) != hipSuccess) return false;
+  if ((*hip_err = hipEventRecord(pages_copied, s)) != hipSuccess) return false;
   const int DT = dt_bucket(maxD);
 #define KT_ADMIT_CASE(DT_)                                                                                        \
   {                                                                                                              \
-    auto kfn = in_lds ? kt_admit_paged<DT_, true> : kt_admit_paged<DT_, false>;                                  \
+    auto kfn = in_lds ? kt_admit<DT_, true> : kt_admit<DT_, false>;                                              \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
     hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a);                                              \
   }

@@ -81,17 +81,12 @@ void launch_prepare_check(const ThrTables& tt, int T, int D, int DT, bool on_equ
 void launch_check_dense(const PodTable& pods, int64_t n, const int64_t* rows_dev, const SelProgram& sp, bool keys,
                         const void* recs, uint64_t* summary, uint8_t* status, hipStream_t s);
 
-// sequential admission of a pod queue with reservation (kt_kernels_admit.hip); the mutable state (reserved amounts of
-// all throttles) lives in LDS when it fits, else in `scratch` (admit_state_bytes)
-size_t admit_state_bytes(int T, int D);
-bool launch_admit(const PodTable& pods, int64_t n, const int64_t* rows_dev, const ThrTables& tt, int T, int D,
-                  bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global,
-                  hipStream_t s);
-
-// the multi-page form (kt_paged_admit): one descriptor per page, the offsets are filled in by the launcher, which also
-// copies the descriptors to pages_dev (n_pages entries of device memory).  The state of all pages lives in LDS while
-// admit_paged_state_bytes + the list fit, else in `scratch` (admit_paged_state_bytes bytes).  false: the list does not fit
-// LDS, or (*hip_err != hipSuccess) the copy of the descriptors failed
+// sequential admission of a pod queue with reservation (kt_kernels_admit.hip) over n_pages >= 1 pages (a page = an engine
+// of <= 16 resource names; kt_admit_launch is one page): one descriptor per page, the offsets are filled in by the launcher,
+// which also copies the descriptors to pages_dev (n_pages entries of device memory) and records pages_copied behind that
+// copy: `pages` must stay unmodified until the event has completed.  The mutable state (reserved amounts of all throttles
+// of every page) lives in LDS while admit_paged_state_bytes + the list fit, else in `scratch` (admit_paged_state_bytes
+// bytes).  false: the list does not fit LDS, or (*hip_err != hipSuccess) the copy of the descriptors failed
 struct AdmitPage {
   const uint32_t* pod_flags;  // the page's pod flags (presence bits of ITS names)
   const int64_t* req;         // [pods][DS]
@@ -99,10 +94,11 @@ struct AdmitPage {
   int32_t D, DS;
   uint32_t off_rv, off_rc, off_rp;
 };
+size_t admit_state_bytes(int T, int D);  // one page
 size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages);
-bool launch_admit_paged(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, int64_t n, const int64_t* rows_dev, int T,
-                        bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global,
-                        hipStream_t s, hipError_t* hip_err);
+bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
+                  bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global, hipStream_t s,
+                  hipError_t* hip_err);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

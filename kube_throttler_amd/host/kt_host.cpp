@@ -1110,7 +1110,7 @@ bool KubeThrottler::OnPodUpdate(const Pod& old_pod, const Pod& new_pod, std::str
 }
 
 // One scheduling pass over a queue of pending pods IN ORDER: PreFilter, and on Success Reserve — a single engine
-// launch (kt_admit_launch) instead of 2 x n calls.  The reserved cache is updated exactly as n
+// launch (kt_paged_admit) instead of 2 x n calls.  The reserved cache is updated exactly as n
 // Reserve calls would have (reserved_resource_amounts.go:66-77), so Unreserve keeps working pod by pod.
 std::vector<Status> KubeThrottler::AdmitQueue(const std::vector<std::string>& pod_keys) {
   std::lock_guard<std::recursive_mutex> lk(p_->mu);
@@ -1144,14 +1144,9 @@ std::vector<Status> KubeThrottler::AdmitQueue(const std::vector<std::string>& po
     std::vector<uint64_t> summary(m);
     std::vector<uint8_t> status(m * (size_t)(T > 0 ? T : 1));
     std::vector<DenseAmount> amts;
-    int32_t rc;
-    if (p.pages.size() == 1) {
-      rc = kt_admit_launch(p.e, (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT, nullptr);
-      if (rc == KT_OK) rc = kt_check_fetch(p.e, (int64_t)m, summary.data(), T > 0 ? status.data() : nullptr);
-    } else {  // every page: the verdicts combined, the reservations on every page (kt_paged_admit)
-      rc = kt_paged_admit(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT,
-                          summary.data(), T > 0 ? status.data() : nullptr);
-    }
+    // every page (pages[0] == e; usually the only one): the verdicts combined, the reservations on every page
+    int32_t rc = kt_paged_admit(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0,
+                                KT_ADMIT_COMMIT, summary.data(), T > 0 ? status.data() : nullptr);
     if (rc == KT_OK) rc = p.fetch_pod_amounts((int64_t)m, rows.data() + i0, &amts);
     if (rc != KT_OK) {
       for (size_t i = i0; i < i1; ++i) out[i].code = Error, out[i].reasons = {p.engine_error(rc)};

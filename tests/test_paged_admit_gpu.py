@@ -53,7 +53,7 @@ def test_paged_admit_equals_the_manifest_model(seed, on_equal, oracle_mod):
 
 
 def test_paged_admit_equals_the_manifest_model_with_hbm_state():
-    """The same distinct pages with every page's state in the HBM scratch buffer (kt_admit_paged<DT, false>): the hook is
+    """The same distinct pages with every page's state in the HBM scratch buffer (kt_admit<DT, false>): the hook is
     read once per process, so the cases run in a child."""
     import os
     import subprocess
@@ -105,6 +105,27 @@ def _identical_pages(n_thr, n_pages, D=8, head_room=2):
 
 def test_one_page_is_kt_admit_launch():
     _identical_pages(64, 1)
+
+
+def test_two_launches_back_to_back_then_one_fetch():
+    """kt_admit_launch is asynchronous and reads its page descriptor from device memory, copied there from engine-owned host
+    storage: a second launch that follows without a fetch must neither disturb the first one's copy nor be disturbed by it.  The
+    one fetch returns the SECOND queue's result, equal to what a fresh engine gives for that queue."""
+    snap, queue = _workload(64)
+    first, second = queue[:700], queue[500:][::-1].copy()  # different queues, overlapping, different lengths
+    eng, fresh = E.Engine.for_snapshot(snap), E.Engine.for_snapshot(snap)
+    try:
+        for q in (first, second):  # dry runs: the reserved amounts stay as loaded
+            eng._ck(E.lib().kt_admit_launch(eng._h, len(q), q.ctypes.data, 0, 0, None))
+        status, summary = eng.check_fetch(len(second), want_status=True)
+        want_status, want_summary = fresh.admit(second, commit=False)
+        np.testing.assert_array_equal(summary, want_summary)
+        np.testing.assert_array_equal(status, want_status)
+        verdict = S.summary_fields(summary)[0]
+        assert (verdict == S.VERDICT_ALLOW).any() and (verdict == S.VERDICT_BLOCK).any()
+    finally:
+        eng.close()
+        fresh.close()
 
 
 def test_state_beyond_lds_lives_in_hbm():
