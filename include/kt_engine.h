@@ -288,6 +288,37 @@ int32_t kt_affected_pods(kt_engine* e, int64_t n, const int64_t* pod_rows, int32
 #define KT_ADMIT_COMMIT 0x1u
 int32_t kt_admit_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
                         void* stream);
+/* ---- gang admission: the queue cut into CONSECUTIVE gangs that are admitted all or nothing (a batch / ML job whose pods
+ *      only run together).  Gang g = queue positions [gang_off[g], gang_off[g + 1]); for g = 0..n_gangs-1 IN ORDER:
+ *      (1) every member, in order, gets PreFilter (plugin.go:148-215) against the stored status plus the CURRENT reserved
+ *          amounts — those of admitted members of its own gang included — and, on Success, Reserve (plugin.go:217-239),
+ *          exactly as kt_admit_launch does;
+ *      (2) all members are evaluated, also behind one that failed: each reports what it met at its turn;
+ *      (3) the gang is admitted iff every member's verdict is Success (an Error verdict, an invalid pod row or a pod
+ *          affected by more throttles than the kernel's list holds fails its gang).  Otherwise every member that reserved
+ *          gets Unreserve (plugin.go:240-257 -> [Cluster]ThrottleController.UnReserve -> reservedResourceAmounts.removePod,
+ *          reserved_resource_amounts.go:79-90) on every throttle (and every page) before the next gang starts: the reserved
+ *          amounts are then exactly what they were before the gang — values, pod count, WHICH resource names are present
+ *          and whether a count is present (the reference recomputes the total over the remaining pod map,
+ *          reserved_resource_amounts.go:148-156: a name only a rolled-back pod brought in disappears again);
+ *      (4) out_summary[i] / out_status[i][*] (kt_check_fetch) stay what PreFilter returned at the pod's turn, also in a
+ *          gang that is rolled back; out_admitted[g] (kt_admit_gangs_fetch) = 1 admitted, 0 rolled back;
+ *      (5) KT_ADMIT_COMMIT keeps the final reserved amounts, without it the call is a dry run.
+ *      A gang of one pod is kt_admit_launch's admission of that pod (a failed single pod reserved nothing).  One launch:
+ *      the rollback runs in the kernel that walks the queue (kt_admit_gangs, the gang form of kt_admit), on the state it
+ *      holds in LDS; it costs the entries the gang touched, not a copy of the state.
+ *      gang_off: [n_gangs + 1], gang_off[0] == 0, gang_off[n_gangs] == n, strictly increasing — an empty gang, offsets
+ *      that decrease or do not span the queue are KT_ERR_INVALID_ARGUMENT before anything is launched; n_gangs == 0 only
+ *      with n == 0.  Everything kt_admit_launch refuses is refused alike (wide `used`, n x throttle_rows > 2^31), and its
+ *      duplicate-pod rule holds: a pod whose amount is already reserved, or that is named twice, must not be in the
+ *      queue (the C++ plugin mirror's AdmitGangs takes such a gang through PreFilter / Reserve / Unreserve per member).
+ *      The gang form keeps 4 x throttle_rows more bytes of state per page, and 4 x throttle_rows once, than kt_admit_launch
+ *      (the LDS / HBM crossover of kt_admit_launch itself is unchanged).
+ *      kt_admit_gangs_fetch synchronises; KT_ERR_NOT_READY without a pending gang launch (a later kt_admit_launch /
+ *      kt_paged_admit* on the engine drops it). -------------------------------------------------------------------------- */
+int32_t kt_admit_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                              int32_t on_equal, uint32_t flags, void* stream);
+int32_t kt_admit_gangs_fetch(kt_engine* e, int64_t n_gangs, uint8_t* out_admitted);
 /* Current reserved amounts of n throttle rows (after kt_set_reserved / kt_admit_launch(KT_ADMIT_COMMIT)). */
 int32_t kt_fetch_reserved(kt_engine* e, int32_t n, const int32_t* throttle_rows, const kt_amounts* out);
 int32_t kt_throttle_rows(kt_engine* e, int32_t* out_rows);
@@ -369,6 +400,13 @@ int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now
  * plus the list fits 160 KiB, beyond that in HBM on page 0. */
 int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
                        uint64_t* out_summary, uint8_t* out_status);
+/* kt_admit_gangs_launch over the pages, synchronous, as kt_paged_admit is kt_admit_launch over the pages (the same refusals,
+ * locking and ordering; n_pages == 1 is kt_admit_gangs_launch + kt_check_fetch + kt_admit_gangs_fetch): a gang that is not
+ * admitted as a whole is rolled back on every page.  out_summary [n], out_status [n][throttle rows] and out_gang_admitted
+ * [n_gangs] are all nullable. */
+int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                             const int64_t* gang_off, int32_t on_equal, uint32_t flags, uint64_t* out_summary, uint8_t* out_status,
+                             uint8_t* out_gang_admitted);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

@@ -331,6 +331,44 @@ func (e *Engine) Admit(rows []int64, onEqual, commit bool) (summary []uint64, st
 	return summary, status[:len(rows)*T], nil
 }
 
+// AdmitGangs is Admit over a queue cut into consecutive gangs (kt_admit_gangs_launch): gang g = rows[gangOff[g]:gangOff[g+1]],
+// admitted all or nothing — every member gets PreFilter and, on Success, Reserve; when one did not succeed every member that
+// reserved gets Unreserve (plugin.go:240-257) before the next gang starts.  summary / status are what PreFilter answered at each
+// pod's turn (also in a rolled-back gang), admitted[g] says whether gang g stays reserved.  The duplicate-pod rule of Admit holds.
+func (e *Engine) AdmitGangs(rows []int64, gangOff []int64, onEqual, commit bool) (summary []uint64, status []uint8, admitted []bool, err error) {
+	// the slices are indexed below: never take &s[0] of an empty one, and refuse offsets the library would refuse anyway
+	if len(gangOff) == 0 {
+		return nil, nil, nil, fmt.Errorf("AdmitGangs: gangOff needs at least the closing offset (len(gangs)+1 entries)")
+	}
+	nGangs := len(gangOff) - 1
+	if gangOff[0] != 0 || gangOff[nGangs] != int64(len(rows)) {
+		return nil, nil, nil, fmt.Errorf("AdmitGangs: gangOff spans [%d, %d], the queue [0, %d]", gangOff[0], gangOff[nGangs], len(rows))
+	}
+	var flags C.uint32_t
+	if commit {
+		flags = C.KT_ADMIT_COMMIT
+	}
+	if rc := C.kt_admit_gangs_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(nGangs), (*C.int64_t)(unsafe.Pointer(&gangOff[0])),
+		b2i(onEqual), flags, nil); rc != C.KT_OK {
+		return nil, nil, nil, e.err(rc)
+	}
+	T := e.ThrottleRows()
+	summary = make([]uint64, len(rows)+1)
+	status = make([]uint8, len(rows)*T+1)
+	flagsOut := make([]uint8, nGangs+1)
+	if rc := C.kt_check_fetch(e.h, C.int64_t(len(rows)), (*C.uint64_t)(unsafe.Pointer(&summary[0])), u8(status)); rc != C.KT_OK {
+		return nil, nil, nil, e.err(rc)
+	}
+	if rc := C.kt_admit_gangs_fetch(e.h, C.int64_t(nGangs), u8(flagsOut)); rc != C.KT_OK {
+		return nil, nil, nil, e.err(rc)
+	}
+	admitted = make([]bool, nGangs)
+	for g := range admitted {
+		admitted[g] = flagsOut[g] != 0
+	}
+	return summary[:len(rows)], status[:len(rows)*T], admitted, nil
+}
+
 // PagedAdmit is Admit over the pages of a cluster with more than 16 resource names (kt_paged_admit): one engine per page of
 // <= 16 names, pages[0] first; verdicts and status rows are combined over the pages, and with commit every page keeps its
 // reserved amounts.  The same duplicate-pod rule as Admit: a pod already reserved, or twice in rows, must not be in the queue.

@@ -223,10 +223,14 @@ int32_t kt_sweep_launch(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t fl
 // The queue in order over n_pages >= 1 page engines (one page: the engine itself), on page 0's stream s: one status-matrix check
 // of page 0, then one kt_admit launch.  The caller holds every page's launch lock and has set the device; the results stay on the
 // device behind page 0's check slot (kt_check_fetch).
+// Gangs (n_gangs >= 0 with gang_off, else -1: the plain queue): validated by the caller (gangs_valid); page 0 keeps the offsets and the
+// gang bytes on the device (kt_admit_gangs_fetch).
 static int32_t admit_locked(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
-                            hipStream_t s) {
+                            hipStream_t s, int64_t n_gangs = -1, const int64_t* gang_off = nullptr) {
   kt_engine* e0 = pages[0];
   const int32_t T = e0->thr_rows_hi;
+  const bool gangs = n_gangs >= 0;
+  e0->gang_ready = false;
   for (int32_t k = 0; k < n_pages; ++k)
     if (pages[k]->wide)
       return pages[k]->fail(KT_ERR_UNSUPPORTED, "admit queue: the stored `used` of page %d is wider than int64 (kt_admit reads int64 tables)", k);
@@ -234,8 +238,20 @@ static int32_t admit_locked(kt_engine* const* pages, int32_t n_pages, int64_t n,
     return e0->fail(KT_ERR_OUT_OF_RANGE, "admit queue: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
   // (a) who affects whom, for the whole queue in parallel, from page 0 (selectors, namespaces and responsibility are the same
   //     in every page; statuses against the current reserved amounts)
+  if (gangs && n_gangs > 0) {
+    // the offsets go up in front of the check launch: the caller's memory is not referenced after return
+    if (e0->d_gang_off.cap < (size_t)n_gangs + 1 || e0->d_gang_out.cap < (size_t)n_gangs) {
+      if (e0->last_stream) KT_HIP(e0, hipStreamSynchronize(e0->last_stream));  // the buffers may still be in use
+      KT_HIP(e0, e0->d_gang_off.reserve((size_t)n_gangs + 1));
+      KT_HIP(e0, e0->d_gang_out.reserve((size_t)n_gangs));
+    }
+    KT_HIP(e0, hipMemcpyAsync(e0->d_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s));
+    KT_HIP(e0, hipStreamSynchronize(s));
+    e0->h_gang_off.assign(gang_off, gang_off + n_gangs + 1);
+  }
   int32_t rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
-  if (rc != KT_OK || n == 0 || T == 0) return rc;
+  if (rc == KT_OK && gangs) e0->gang_ready = true, e0->gang_n = n_gangs, e0->gang_on_device = n > 0 && T > 0;
+  if (rc != KT_OK || n == 0 || T == 0) return rc;  // (no throttle rows: a gang is admitted iff no member's PreFilter is an error)
   // (b) the queue in order, one wave, every page's reserved amounts side by side in LDS
   if (!e0->admit_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->admit_pages_ev, hipEventDisableTiming));
   KT_HIP(e0, hipEventSynchronize(e0->admit_pages_ev));  // the previous launch's copy has read h_admit_pages
@@ -245,13 +261,15 @@ static int32_t admit_locked(kt_engine* const* pages, int32_t n_pages, int64_t n,
     e0->h_admit_pages[(size_t)k] = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
   }
   const bool commit = (flags & KT_ADMIT_COMMIT) != 0;
-  KT_HIP(e0, e0->d_admit.reserve(kt::admit_paged_state_bytes(T, e0->h_admit_pages.data(), n_pages) + 64));
+  KT_HIP(e0, e0->d_admit.reserve(kt::admit_paged_state_bytes(T, e0->h_admit_pages.data(), n_pages) + (gangs ? kt::admit_gang_extra_bytes(T, n_pages) : 0) + 64));
   KT_HIP(e0, e0->d_admit_pages.reserve(sizeof(kt::AdmitPage) * (size_t)n_pages));
   static const bool force_global = getenv("KT_ADMIT_FORCE_GLOBAL") != nullptr;  // test hook: HBM-resident state
   hipError_t herr = hipSuccess;
+  const kt::AdmitGangs ga{e0->d_gang_off.p, n_gangs, e0->d_gang_out.p};
   const bool launched = kt::launch_admit(e0->h_admit_pages.data(), n_pages, (kt::AdmitPage*)e0->d_admit_pages.p, e0->admit_pages_ev, n,
                                          pod_rows ? e0->d_rows.p : nullptr, T, on_equal != 0, commit, e0->d_status.p, e0->d_summary.p,
-                                         e0->d_admit.p, force_global, s, &herr);
+                                         e0->d_admit.p, force_global, s, &herr, gangs ? &ga : nullptr);
+  if (herr != hipSuccess || !launched) e0->gang_ready = false;
   if (herr != hipSuccess) return e0->fail(KT_ERR_DEVICE, "admit queue: copy of the page descriptors: %s", hipGetErrorString(herr));
   if (!launched) return e0->fail(KT_ERR_UNSUPPORTED, "admit queue: %d throttle rows exceed the kernel's LDS list", T);
   KT_HIP(e0, hipGetLastError());
@@ -270,6 +288,68 @@ int32_t kt_admit_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_
   LaunchLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
   return admit_locked(&e, 1, n, pod_rows, on_equal, flags, pick_stream(e, stream));
+}
+
+// gang_off[0] == 0, gang_off[n_gangs] == n, strictly increasing (no empty gang); n_gangs == 0 only with n == 0
+static int32_t gangs_valid(kt_engine* e, int64_t n, int64_t n_gangs, const int64_t* gang_off) {
+  if (n_gangs == 0) {
+    if (n != 0) return e->fail(KT_ERR_INVALID_ARGUMENT, "admit gangs: no gangs for a queue of %lld pods", (long long)n);
+    if (gang_off && gang_off[0] != 0) return e->fail(KT_ERR_INVALID_ARGUMENT, "admit gangs: gang_off[0] = %lld, not 0", (long long)gang_off[0]);
+    return KT_OK;
+  }
+  if (!gang_off) return e->fail(KT_ERR_INVALID_ARGUMENT, "admit gangs: gang_off is NULL");
+  if (gang_off[0] != 0) return e->fail(KT_ERR_INVALID_ARGUMENT, "admit gangs: gang_off[0] = %lld, not 0", (long long)gang_off[0]);
+  for (int64_t g = 0; g < n_gangs; ++g) {
+    if (gang_off[g + 1] == gang_off[g])
+      return e->fail(KT_ERR_INVALID_ARGUMENT, "admit gangs: gang %lld is empty (gang_off[%lld] = gang_off[%lld] = %lld)", (long long)g, (long long)g,
+                     (long long)(g + 1), (long long)gang_off[g]);
+    if (gang_off[g + 1] < gang_off[g])
+      return e->fail(KT_ERR_INVALID_ARGUMENT, "admit gangs: gang_off[%lld] = %lld is below gang_off[%lld] = %lld", (long long)(g + 1),
+                     (long long)gang_off[g + 1], (long long)g, (long long)gang_off[g]);
+  }
+  if (gang_off[n_gangs] != n)
+    return e->fail(KT_ERR_INVALID_ARGUMENT, "admit gangs: gang_off[%lld] = %lld, not n = %lld", (long long)n_gangs, (long long)gang_off[n_gangs], (long long)n);
+  return KT_OK;
+}
+
+int32_t kt_admit_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int32_t on_equal,
+                              uint32_t flags, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  int32_t rc = gangs_valid(e, n, n_gangs, gang_off);
+  if (rc != KT_OK) return rc;
+  KT_HIP(e, hipSetDevice(e->device));
+  return admit_locked(&e, 1, n, pod_rows, on_equal, flags, pick_stream(e, stream), n_gangs, gang_off);
+}
+
+// the gang bytes of the last gang launch, under the launch lock; out nullable
+static int32_t gangs_fetch_locked(kt_engine* e, int64_t n_gangs, uint8_t* out) {
+  if (!e->gang_ready) return e->fail(KT_ERR_NOT_READY, "kt_admit_gangs_fetch before kt_admit_gangs_launch");
+  if (n_gangs < 0 || n_gangs > e->gang_n)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "n_gangs=%lld, the last gang launch had %lld gangs", (long long)n_gangs, (long long)e->gang_n);
+  hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
+  if (e->gang_on_device) {
+    if (n_gangs && out) KT_HIP(e, hipMemcpyAsync(out, e->d_gang_out.p, (size_t)n_gangs, hipMemcpyDeviceToHost, s));
+    KT_HIP(e, hipStreamSynchronize(s));
+    return KT_OK;
+  }
+  // no throttle rows: nothing was reserved; a gang is admitted iff every member's PreFilter answered Success
+  std::vector<uint64_t> sm((size_t)e->check_n + 1);
+  if (e->check_n) KT_HIP(e, hipMemcpyAsync(sm.data(), e->d_summary.p, (size_t)e->check_n * 8, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  for (int64_t g = 0; g < n_gangs && out; ++g) {
+    out[g] = 1;
+    for (int64_t i = e->h_gang_off[(size_t)g]; i < e->h_gang_off[(size_t)g + 1]; ++i)
+      if (sm[(size_t)i] != 0) out[g] = 0;
+  }
+  return KT_OK;
+}
+
+int32_t kt_admit_gangs_fetch(kt_engine* e, int64_t n_gangs, uint8_t* out_admitted) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  return gangs_fetch_locked(e, n_gangs, out_admitted);
 }
 
 int32_t kt_fetch_reserved(kt_engine* e, int32_t n, const int32_t* rows, const kt_amounts* out) {
@@ -473,9 +553,10 @@ int32_t kt_paged_check(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
   return KT_OK;
 }
 
-// kt_admit_launch over several engines, synchronous: what is specific to more than one engine, then admit_locked
-int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
-                       uint64_t* out_summary, uint8_t* out_status) {
+// kt_admit_launch / kt_admit_gangs_launch (n_gangs >= 0) over several engines, synchronous: what is specific to more than one engine,
+// then admit_locked
+static int32_t paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
+                           uint64_t* out_summary, uint8_t* out_status, int64_t n_gangs, const int64_t* gang_off, uint8_t* out_gang_admitted) {
   if (!pages || n_pages < 1 || n < 0) return KT_ERR_INVALID_ARGUMENT;
   for (int32_t k = 0; k < n_pages; ++k) {
     if (!pages[k]) return KT_ERR_INVALID_ARGUMENT;
@@ -489,6 +570,10 @@ int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
   for (kt_engine* e : by_addr) locks.emplace_back(new LaunchLock(e, /*force_exclusive=*/true));
   kt_engine* e0 = pages[0];
   const int32_t T = e0->thr_rows_hi;
+  if (n_gangs >= 0) {
+    const int32_t rcg = gangs_valid(e0, n, n_gangs, gang_off);
+    if (rcg != KT_OK) return rcg;
+  }
   for (int32_t k = 0; k < n_pages; ++k) {
     kt_engine* e = pages[k];
     if (e->thr_rows_hi != T) return e->fail(KT_ERR_INVALID_ARGUMENT, "page %d holds %d throttle rows, page 0 %d: every page holds every throttle", k, e->thr_rows_hi, T);
@@ -514,13 +599,29 @@ int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
     if (e->last_stream && e->last_stream != e->own_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
     order_behind_ingest(e, s);
   }
-  const int32_t rc = admit_locked(pages, n_pages, n, pod_rows, on_equal, flags, s);
+  int32_t rc = admit_locked(pages, n_pages, n, pod_rows, on_equal, flags, s, n_gangs, gang_off);
   e0->check_ready = false;  // the call used page 0's check slot (as kt_affected_pods): a pending kt_check_launch is gone
   if (rc != KT_OK) return rc;
   if (out_summary) KT_HIP(e0, hipMemcpyAsync(out_summary, e0->d_summary.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   if (out_status && T > 0) KT_HIP(e0, hipMemcpyAsync(out_status, e0->d_status.p, (size_t)n * (size_t)T, hipMemcpyDeviceToHost, s));
+  if (n_gangs >= 0) {
+    rc = gangs_fetch_locked(e0, n_gangs, out_gang_admitted);  // (synchronises s)
+    e0->gang_ready = false;  // the results have been handed out
+    return rc;
+  }
   KT_HIP(e0, hipStreamSynchronize(s));
   return KT_OK;
+}
+
+int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
+                       uint64_t* out_summary, uint8_t* out_status) {
+  return paged_admit(pages, n_pages, n, pod_rows, on_equal, flags, out_summary, out_status, -1, nullptr, nullptr);
+}
+
+int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                             int32_t on_equal, uint32_t flags, uint64_t* out_summary, uint8_t* out_status, uint8_t* out_gang_admitted) {
+  if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  return paged_admit(pages, n_pages, n, pod_rows, on_equal, flags, out_summary, out_status, n_gangs, gang_off, out_gang_admitted);
 }
 
 int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now_s, int32_t now_ns, uint32_t flags, int32_t n,

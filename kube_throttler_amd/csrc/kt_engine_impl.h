@@ -312,6 +312,12 @@ struct kt_engine {
   // copy that read it — has completed; freed only after that too (kt_engine_destroy synchronises first).
   std::vector<kt::AdmitPage> h_admit_pages;
   hipEvent_t admit_pages_ev = nullptr;
+  // the last kt_admit_gangs_launch (on page 0): offsets and gang bytes on the device, the offsets on the host too
+  DevBuf<int64_t> d_gang_off;
+  DevBuf<uint8_t> d_gang_out;
+  std::vector<int64_t> h_gang_off;
+  bool gang_ready = false, gang_on_device = false;  // on_device false: no throttle rows, the bytes follow from the summaries
+  int64_t gang_n = 0;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;

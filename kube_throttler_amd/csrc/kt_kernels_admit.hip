@@ -22,6 +22,15 @@
 // There is ONE kernel, kt_admit<DT, IN_LDS>, over n_pages >= 1 page descriptors in device memory (a page = an engine of
 // <= 16 resource names): kt_admit_launch is the one-page case of kt_paged_admit.  Step (2) is the name part of every page
 // OR-ed with the count part of page 0, step (4) reserves on every page.
+//
+// Gangs (kt_admit_gangs<DT, IN_LDS>, kt_admit_gangs_launch): the queue is cut into consecutive groups that are admitted all or
+// nothing.  Every member is walked as above; when one of them was not admitted, every member that reserved gets Unreserve
+// (plugin.go:240-257 -> reservedResourceAmounts.removePod, reserved_resource_amounts.go:79-90) before the next gang starts.
+// The undo costs the touched entries only: values and counts by exact subtraction, the presence word from a copy taken when the
+// gang first touched the throttle (`rq`, 4 x T bytes per page, and one gang tag per throttle that says whether the copy is this
+// gang's: the reference recomputes the total over the remaining pods, reserved_resource_amounts.go:148-156, so a name only a
+// rolled-back pod brought in disappears again).  An admitted gang costs that copy and nothing else.  For the rollback the touched
+// throttles are re-derived from the members' matrix rows: step (3) rewrites nonzero bytes with nonzero bytes, the list is the same.
 #include "kt_index_device.h"
 
 namespace kt {
@@ -36,6 +45,14 @@ struct AdmitPagedArgs {
   uint64_t* summary;  // [n] out
   int32_t T, on_equal, commit;
   uint32_t off_list, list_cap;
+};
+// what the gang form (kt_admit_gangs) takes on top
+struct AdmitGangArgs {
+  const int64_t* gang_off;  // [n_gangs + 1] queue positions
+  int64_t n_gangs;
+  uint8_t* gang_out;        // [n_gangs] 1 admitted, 0 rolled back
+  uint32_t off_rq, rq_stride;  // page k's saved presence words at off_rq + k * rq_stride (LDS or scratch, as the state)
+  uint32_t off_tag;            // [T] 1 + the gang that saved the throttle's presence words last (0: none)
 };
 
 // the sums of used + reserved (+ the pod) are formed in 128 bits: an all-reduced `used` may come close to int64's end
@@ -86,6 +103,29 @@ __device__ __forceinline__ AdmitState<IN_LDS> admit_state_at(KT_LDS unsigned cha
   }
   return st;
 }
+// gangs: the presence words as they stood before the current gang touched the throttle, and the gang tags (same home as the state)
+template <bool IN_LDS>
+struct AdmitPresence;
+template <>
+struct AdmitPresence<true> {
+  KT_LDS uint32_t* rq;
+  __device__ __forceinline__ uint32_t ld(int i) const { return rq[i]; }
+  __device__ __forceinline__ void st(int i, uint32_t x) const { rq[i] = x; }
+};
+template <>
+struct AdmitPresence<false> {
+  uint32_t* rq;
+  __device__ __forceinline__ uint32_t ld(int i) const { return __hip_atomic_load(rq + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ __forceinline__ void st(int i, uint32_t x) const { __hip_atomic_store(rq + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+template <bool IN_LDS>
+__device__ __forceinline__ AdmitPresence<IN_LDS> admit_presence_at(KT_LDS unsigned char* lds, unsigned char* scratch, uint32_t off) {
+  AdmitPresence<IN_LDS> q;
+  if constexpr (IN_LDS) q.rq = (KT_LDS uint32_t*)(lds + off);
+  else q.rq = (uint32_t*)(scratch + off);
+  return q;
+}
+
 // reserved tables (HBM) -> state, and back (commit)
 template <bool IN_LDS>
 __device__ __forceinline__ void admit_load_state(const AdmitState<IN_LDS>& st, const ThrTables& tt, int T, int D) {
@@ -222,67 +262,145 @@ __device__ __forceinline__ void admit_reserve(const AdmitPage& pg, const AdmitSt
   }
 }
 
+// Unreserve on one page: (4) undone by exact subtraction on every affected throttle; the presence word goes back to what it
+// was before the gang (idempotent: a throttle several members touched is restored once per member)
+template <int DT, bool IN_LDS>
+__device__ __forceinline__ void admit_unreserve(const AdmitPage& pg, const AdmitState<IN_LDS>& st, const AdmitPresence<IN_LDS>& q, int64_t p,
+                                                lds_u32wp list, uint32_t n_aff) {
+  constexpr int MPW = kWave / DT;
+  const uint32_t d = threadIdx.x % DT, ml = threadIdx.x / DT;
+  const int D = pg.D;
+  const uint32_t present = pg.pod_flags[p] >> kPresentShift;
+  const bool d_in = (int)d < D;
+  const int64_t v = d_in ? pg.req[p * pg.DS + d] : 0;
+  for (uint32_t base = 0; base < n_aff; base += MPW) {
+    const uint32_t j = base + ml;
+    if (j < n_aff) {
+      const uint32_t t = list[j];
+      if (d_in && ((present >> d) & 1u)) st.st_v(t * D + d, st.ld_v(t * D + d) - v);
+      if (d == 0) {
+        st.st_c(t, st.ld_c(t) - 1);
+        st.st_p(t, q.ld(t));  // (saved by this gang: the member reserved on t)
+      }
+    }
+  }
+}
 // One wave, the queue in order, the state of every page (an engine of <= 16 resource names; one page is the plain engine) side
 // by side.  Page 0's status matrix gives the affected list once per pod (selectors, namespaces and responsibility are the same
 // in every page); the name part of the four steps is evaluated against every page's tables and reserved state and OR-ed before
 // the reduction (exceeds > active > insufficient, as kt_paged_check combines), the count part once, on page 0; Success
 // reserves on every page.
-template <int DT, bool IN_LDS>
-__global__ __launch_bounds__(kWave) void kt_admit(const AdmitPagedArgs a) {
+// GANGS: the queue positions [gang_off[g], gang_off[g + 1]) are admitted all or nothing, gang after gang; a gang with a member
+// that was not admitted is rolled back (every member that reserved: Unreserve on every page) before the next one starts.  The
+// per-pod outputs stay what PreFilter returned at the pod's turn.  Without GANGS the whole queue is one span that is never undone.
+template <int DT, bool IN_LDS, bool GANGS>
+__device__ __forceinline__ void admit_walk(const AdmitPagedArgs& a, const AdmitGangArgs& ga) {
   KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
   lds_u32wp list = (lds_u32wp)(lds + a.off_list);  // affected throttles of the current pod
   const int T = a.T, n_pages = a.n_pages;
   const uint32_t lane = threadIdx.x;
   auto state_of = [&](const AdmitPage& pg) { return admit_state_at<IN_LDS>(lds, a.scratch, pg.off_rv, pg.off_rc, pg.off_rp); };
+  auto kept_of = [&](int k) { return admit_presence_at<IN_LDS>(lds, a.scratch, ga.off_rq + (uint32_t)k * ga.rq_stride); };
   for (int k = 0; k < n_pages; ++k) {
     const AdmitPage pg = admit_page(a.pages, k);
     admit_load_state(state_of(pg), pg.tt, T, pg.D);
   }
+  const AdmitPresence<IN_LDS> tag = admit_presence_at<IN_LDS>(lds, a.scratch, ga.off_tag);
+  if constexpr (GANGS)
+    for (int t = (int)lane; t < T; t += kWave) tag.st(t, 0u);
   if (!IN_LDS) __threadfence();
   constexpr int MPW = kWave / DT;
   const uint32_t d = lane % DT, ml = lane / DT;
   const bool eq = a.on_equal != 0;
-  for (int64_t i = 0; i < a.n; ++i) {
-    const int64_t p = a.rows ? a.rows[i] : i;
-    uint8_t* row = a.status + i * T;
-    // ---- (1) affected throttles: nonzero bytes of the matrix row, 16 per lane and chunk
-    bool err;
-    const uint32_t n_aff = admit_affected(row, T, list, a.list_cap, &err);
-    if (__ballot(err) != 0ull || !(admit_page(a.pages, 0).pod_flags[p] & kPodValid) || n_aff > a.list_cap) {
-      // error row (selector / namespace error, plugin.go:154-168), empty row, or a pod affected by more
-      // throttles than the list holds: the pre-computed summary stands and nothing is reserved
-      continue;
+  const int64_t n_spans = GANGS ? ga.n_gangs : 1;
+  int64_t span_begin = 0, span_end = GANGS ? ga.gang_off[n_spans > 0 ? 1 : 0] : a.n;  // (gang_off[0] == 0)
+  for (int64_t g = 0; g < n_spans; ++g) {
+    const int64_t i0 = span_begin, i1 = span_end;
+    if constexpr (GANGS) {  // the next gang's end is asked for a gang ahead: its trip to HBM runs beside this gang's walk
+      span_begin = i1;
+      if (g + 1 < n_spans) span_end = ga.gang_off[g + 2];
     }
-    // ---- (2) lane = (affected throttle, dimension), over every page
-    uint32_t n_exc = 0, n_act = 0, n_ins = 0;
-    for (uint32_t base = 0; base < n_aff; base += MPW) {
-      const uint32_t j = base + ml;
-      const bool vv = j < n_aff;
-      const uint32_t t = list[vv ? j : 0u];
-      uint32_t bits = 0;
+    bool all_in = true;  // wave-uniform: every member so far was admitted
+    for (int64_t i = i0; i < i1; ++i) {
+      const int64_t p = a.rows ? a.rows[i] : i;
+      uint8_t* row = a.status + i * T;
+      // ---- (1) affected throttles: nonzero bytes of the matrix row, 16 per lane and chunk
+      bool err;
+      const uint32_t n_aff = admit_affected(row, T, list, a.list_cap, &err);
+      if (__ballot(err) != 0ull || !(admit_page(a.pages, 0).pod_flags[p] & kPodValid) || n_aff > a.list_cap) {
+        // error row (selector / namespace error, plugin.go:154-168), empty row, or a pod affected by more
+        // throttles than the list holds: the pre-computed summary stands and nothing is reserved
+        if constexpr (GANGS) all_in = false;
+        continue;
+      }
+      // ---- (2) lane = (affected throttle, dimension), over every page
+      uint32_t n_exc = 0, n_act = 0, n_ins = 0;
+      for (uint32_t base = 0; base < n_aff; base += MPW) {
+        const uint32_t j = base + ml;
+        const bool vv = j < n_aff;
+        const uint32_t t = list[vv ? j : 0u];
+        uint32_t bits = 0;
+        for (int k = 0; k < n_pages; ++k) {
+          const AdmitPage pg = admit_page(a.pages, k);
+          if (!vv) continue;
+          const AdmitState<IN_LDS> st = state_of(pg);
+          if (k == 0 && d == 0) bits |= admit_count_bits(pg.tt, st, t, eq);  // the same in every page
+          bits |= admit_name_bits(pg, st, p, t, d, eq);
+        }
+#pragma unroll
+        for (int o = DT / 2; o >= 1; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, o);
+        // ---- (3) the status the pod met on throttle t, the summary word as PreFilter would return it at this point
+        const uint32_t stc = (bits & 1u) ? 4u : (bits & 2u) ? 2u : (bits & 4u) ? 3u : 1u;
+        const bool lead = vv && d == 0;
+        if (lead) row[t] = (uint8_t)stc;
+        n_exc += (uint32_t)__popcll(__ballot(lead && stc == 4u));
+        n_act += (uint32_t)__popcll(__ballot(lead && stc == 2u));
+        n_ins += (uint32_t)__popcll(__ballot(lead && stc == 3u));
+      }
+      if constexpr (GANGS) {
+        // the rollback asks this word whether the pod reserved: written and read through L2, as the HBM state is
+        if (lane == 0) __hip_atomic_store(a.summary + i, pack_summary(n_exc, n_act, n_ins, false), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        if (lane == 0) a.summary[i] = pack_summary(n_exc, n_act, n_ins, false);
+      }
+      if ((n_exc | n_act | n_ins) != 0) {
+        if constexpr (GANGS) all_in = false;
+        continue;
+      }
+      // ---- (4) Success: Reserve on every page
+      if constexpr (GANGS) {  // the first touch of a throttle in this gang saves every page's presence word of it
+        const uint32_t gt = (uint32_t)g + 1u;
+        for (uint32_t j = lane; j < n_aff; j += kWave) {
+          const uint32_t t = list[j];
+          if (tag.ld(t) == gt) continue;
+          for (int k = 0; k < n_pages; ++k) kept_of(k).st(t, state_of(admit_page(a.pages, k)).ld_p(t));
+          tag.st(t, gt);
+        }
+      }
       for (int k = 0; k < n_pages; ++k) {
         const AdmitPage pg = admit_page(a.pages, k);
-        if (!vv) continue;
-        const AdmitState<IN_LDS> st = state_of(pg);
-        if (k == 0 && d == 0) bits |= admit_count_bits(pg.tt, st, t, eq);  // the same in every page
-        bits |= admit_name_bits(pg, st, p, t, d, eq);
+        admit_reserve<DT>(pg, state_of(pg), p, list, n_aff);
       }
-#pragma unroll
-      for (int o = DT / 2; o >= 1; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, o);
-      // ---- (3) the status the pod met on throttle t, the summary word as PreFilter would return it at this point
-      const uint32_t stc = (bits & 1u) ? 4u : (bits & 2u) ? 2u : (bits & 4u) ? 3u : 1u;
-      const bool lead = vv && d == 0;
-      if (lead) row[t] = (uint8_t)stc;
-      n_exc += (uint32_t)__popcll(__ballot(lead && stc == 4u));
-      n_act += (uint32_t)__popcll(__ballot(lead && stc == 2u));
-      n_ins += (uint32_t)__popcll(__ballot(lead && stc == 3u));
     }
-    if (lane == 0) a.summary[i] = pack_summary(n_exc, n_act, n_ins, false);
-    if ((n_exc | n_act | n_ins) != 0) continue;
-    // ---- (4) Success: Reserve on every page
-    for (int k = 0; k < n_pages; ++k) {
-      const AdmitPage pg = admit_page(a.pages, k);
-      admit_reserve<DT>(pg, state_of(pg), p, list, n_aff);
+    if constexpr (GANGS) {
+      if (lane == 0) ga.gang_out[g] = all_in ? 1 : 0;
+      if (!all_in) {
+        // ---- rolled back: Unreserve of every member that reserved.  A member reserved iff it was not skipped in (1) — decided
+        //      again from the same inputs (an error byte is never rewritten, nonzero bytes stay nonzero) — and its summary word,
+        //      read back through L2, says Success
+        for (int64_t i = i0; i < i1; ++i) {
+          const int64_t p = a.rows ? a.rows[i] : i;
+          const uint64_t w = __hip_atomic_load(a.summary + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (beside the row's trip)
+          bool err;
+          const uint32_t n_aff = admit_affected(a.status + i * T, T, list, a.list_cap, &err);
+          if (__ballot(err) != 0ull || !(admit_page(a.pages, 0).pod_flags[p] & kPodValid) || n_aff > a.list_cap) continue;
+          if (__ballot(w != 0ull) != 0ull) continue;
+          for (int k = 0; k < n_pages; ++k) {
+            const AdmitPage pg = admit_page(a.pages, k);
+            admit_unreserve<DT>(pg, state_of(pg), kept_of(k), p, list, n_aff);
+          }
+        }
+      }
     }
   }
   if (a.commit)
@@ -290,6 +408,16 @@ __global__ __launch_bounds__(kWave) void kt_admit(const AdmitPagedArgs a) {
       const AdmitPage pg = admit_page(a.pages, k);
       admit_store_state(state_of(pg), pg.tt, T, pg.D);
     }
+}
+
+// the two kernels: the plain queue, and the queue in gangs
+template <int DT, bool IN_LDS>
+__global__ __launch_bounds__(kWave) void kt_admit(const AdmitPagedArgs a) {
+  admit_walk<DT, IN_LDS, false>(a, AdmitGangArgs{});
+}
+template <int DT, bool IN_LDS>
+__global__ __launch_bounds__(kWave) void kt_admit_gangs(const AdmitPagedArgs a, const AdmitGangArgs ga) {
+  admit_walk<DT, IN_LDS, true>(a, ga);
 }
 
 // LDS: state + list when the state fits, else the list alone
@@ -303,13 +431,18 @@ size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages) {
   return b;
 }
 
-// scratch: admit_paged_state_bytes bytes of device memory, used when the state does not fit in LDS (or when forced)
+// gangs: one saved copy of the presence words per page and the gang tags, beside the state (LDS or scratch)
+size_t admit_gang_extra_bytes(int T, int n_pages) { return ((size_t)n_pages + 1) * (((size_t)T * 4 + 15) / 16 * 16); }
+
+// scratch: admit_paged_state_bytes (+ admit_gang_extra_bytes with gangs) bytes of device memory, used when the state does not
+// fit in LDS (or when forced).  gangs (nullable): the gang form, its extra state counted for it alone
 bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
                   bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global, hipStream_t s,
-                  hipError_t* hip_err) {
+                  hipError_t* hip_err, const AdmitGangs* gangs) {
   *hip_err = hipSuccess;
   const size_t list_bytes = ((size_t)T * 4 + 15) / 16 * 16;
-  const bool in_lds = !force_global && admit_paged_state_bytes(T, pages, n_pages) + list_bytes <= (size_t)kMaxLds;
+  const size_t extra = gangs ? admit_gang_extra_bytes(T, n_pages) : 0;
+  const bool in_lds = !force_global && admit_paged_state_bytes(T, pages, n_pages) + extra + list_bytes <= (size_t)kMaxLds;
   if (!in_lds && (!scratch || list_bytes > (size_t)kMaxLds)) return false;
   uint32_t o = 0;
   auto take = [&](size_t bytes) { uint32_t r = o; o += (uint32_t)((bytes + 15) & ~(size_t)15); return r; };
@@ -320,8 +453,15 @@ bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_
     pages[k].off_rp = take((size_t)T * 4);
     maxD = pages[k].D > maxD ? pages[k].D : maxD;
   }
-  if (!in_lds) o = 0;
   AdmitPagedArgs a{};
+  AdmitGangArgs ga{};
+  if (gangs) {  // behind every page's state
+    ga.rq_stride = (uint32_t)list_bytes;
+    ga.off_rq = take(extra);
+    ga.off_tag = ga.off_rq + (uint32_t)n_pages * ga.rq_stride;
+    ga.gang_off = gangs->off_dev, ga.n_gangs = gangs->n_gangs, ga.gang_out = gangs->out_dev;
+  }
+  if (!in_lds) o = 0;
   a.pages = pages_dev, a.n_pages = n_pages, a.rows = rows_dev, a.n = n, a.scratch = (unsigned char*)scratch;
   a.status = status, a.summary = summary, a.T = T, a.on_equal = on_equal ? 1 : 0, a.commit = commit ? 1 : 0;
   a.list_cap = (uint32_t)T;  // a pod can be affected by every throttle
@@ -331,7 +471,11 @@ bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_
   if ((*hip_err = hipEventRecord(pages_copied, s)) != hipSuccess) return false;
   const int DT = dt_bucket(maxD);
 #define KT_ADMIT_CASE(DT_)                                                                                        \
-  {                                                                                                              \
+  if (gangs) {                                                                                                   \
+    auto kfn = in_lds ? kt_admit_gangs<DT_, true> : kt_admit_gangs<DT_, false>;                                  \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
+    hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a, ga);                                          \
+  } else {                                                                                                       \
     auto kfn = in_lds ? kt_admit<DT_, true> : kt_admit<DT_, false>;                                              \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
     hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a);                                              \

@@ -96,9 +96,17 @@ struct AdmitPage {
 };
 size_t admit_state_bytes(int T, int D);  // one page
 size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages);
+// gangs (kt_admit_gangs_launch): the queue positions [off_dev[g], off_dev[g + 1]) are admitted all or nothing, out_dev[g] = 1
+// admitted / 0 rolled back; the gang form keeps admit_gang_extra_bytes more state (LDS, or scratch behind the pages' state)
+struct AdmitGangs {
+  const int64_t* off_dev;  // [n_gangs + 1] in device memory
+  int64_t n_gangs;
+  uint8_t* out_dev;        // [n_gangs]
+};
+size_t admit_gang_extra_bytes(int T, int n_pages);
 bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
                   bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global, hipStream_t s,
-                  hipError_t* hip_err);
+                  hipError_t* hip_err, const AdmitGangs* gangs = nullptr);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

@@ -40,7 +40,7 @@ EXPORTS = [
     "kt_check", "kt_upsert_namespace", "kt_upsert_pod", "kt_upsert_throttle", "kt_comm_unique_id", "kt_comm_init",
     "kt_comm_allreduce_partial", "kt_comm_destroy", "kt_reconcile_rows_launch", "kt_set_exchange_world", "kt_counter", "kt_reconcile_fetch_used_hi",
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
-    "kt_paged_admit",
+    "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
 ]
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
@@ -91,6 +91,31 @@ def paged_admit(engines, rows, on_equal=False, commit=False):
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_admit: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return status[:n, :T], summary[:n]
+
+
+def _gang_offsets(gang_off):
+    g = np.ascontiguousarray(gang_off, dtype=np.int64)
+    if g.ndim != 1 or len(g) < 1:
+        raise ValueError("gang_off: [n_gangs + 1] offsets, starting at 0 and ending at the queue length")
+    return g
+
+
+def paged_admit_gangs(engines, rows, gang_off, on_equal=False, commit=False):
+    """kt_paged_admit_gangs: the queue ``rows`` in consecutive gangs ``[gang_off[g], gang_off[g + 1])`` admitted all or nothing
+    over the page engines -> (status matrix [n][T] and summary words [n] at each pod's turn, admitted byte per gang)."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    T = engines[0].throttle_rows()
+    rows_a = np.ascontiguousarray(rows, dtype=np.int64)
+    g = _gang_offsets(gang_off)
+    n, ng = len(rows_a), len(g) - 1
+    status = np.zeros((max(n, 1), max(T, 1)), np.uint8)
+    summary = np.zeros(max(n, 1), np.uint64)
+    admitted = np.zeros(max(ng, 1), np.uint8)
+    rc = lib().kt_paged_admit_gangs(hs, len(engines), n, rows_a.ctypes.data if n else None, ng, g.ctypes.data, int(on_equal),
+                                    ADMIT_COMMIT if commit else 0, summary.ctypes.data, status.ctypes.data, admitted.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_admit_gangs: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return status[:n, :T], summary[:n], admitted[:ng]
 
 
 def paged_reconcile(engines, now, apply=True):
@@ -196,6 +221,10 @@ def lib():
         L.kt_reconcile_fetch_next_override.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_admit_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.kt_fetch_reserved.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(S.KtAmounts)]
+        L.kt_admit_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
+        L.kt_admit_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.kt_paged_admit_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -489,6 +518,22 @@ class Engine:
         n = len(a) if a is not None else n
         self._ck(lib().kt_admit_launch(self._h, n, p, int(on_equal), ADMIT_COMMIT if commit else 0, None))
         return self.check_fetch(n, want_status)
+
+    def admit_gangs(self, rows, gang_off, on_equal=False, commit=False, want_status=True):
+        """kt_admit_gangs_launch: the queue ``rows`` in consecutive gangs ``[gang_off[g], gang_off[g + 1])``, each admitted all or
+        nothing (a gang with a member that is not admitted is rolled back before the next one starts) ->
+        (status matrix, summary words — both as PreFilter answered at each pod's turn —, admitted byte per gang)."""
+        a, p = self._rows(rows, np.int64)
+        g = _gang_offsets(gang_off)
+        n, ng = len(a), len(g) - 1
+        self._ck(lib().kt_admit_gangs_launch(self._h, n, p, ng, g.ctypes.data, int(on_equal), ADMIT_COMMIT if commit else 0, None))
+        status, summary = self.check_fetch(n, want_status)
+        return status, summary, self.admit_gangs_fetch(ng)
+
+    def admit_gangs_fetch(self, n_gangs):
+        admitted = np.zeros(max(n_gangs, 1), np.uint8)
+        self._ck(lib().kt_admit_gangs_fetch(self._h, n_gangs, admitted.ctypes.data))
+        return admitted[:n_gangs]
 
     def fetch_reserved(self, rows=None) -> S.Amounts:
         rows = np.arange(self.throttle_rows(), dtype=np.int32) if rows is None else rows

@@ -1109,6 +1109,62 @@ bool KubeThrottler::OnPodUpdate(const Pod& old_pod, const Pod& new_pod, std::str
   return true;
 }
 
+// One engine launch over the queue positions [i0, i1) (every page: pages[0] == e, usually the only one — the verdicts combined,
+// the reservations on every page), committed; the pod-keyed reservation map receives what the engine reserved.  gang_off
+// (nullable; [g0, g1] into the queue, gang_off[g0] == i0, gang_off[g1] == i1): the segment in gangs (kt_paged_admit_gangs) — only
+// members of ADMITTED gangs enter the map, the engine has already taken the others' amounts out again; admitted[g] receives the flag.
+static void admit_engine_segment(KubeThrottler::Impl& p, const std::vector<std::string>& pod_keys, const std::vector<int64_t>& rows, size_t i0, size_t i1,
+                                 std::vector<Status>* out_p, const std::vector<int64_t>* gang_off, std::vector<uint8_t>* admitted, size_t g0 = 0,
+                                 size_t g1 = 0) {
+  std::vector<Status>& out = *out_p;
+  const size_t m = i1 - i0;
+  if (m == 0) return;
+  int32_t T = 0;
+  kt_throttle_rows(p.e, &T);
+  std::vector<uint64_t> summary(m);
+  std::vector<uint8_t> status(m * (size_t)(T > 0 ? T : 1));
+  std::vector<DenseAmount> amts;
+  std::vector<int64_t> off;      // the segment's gangs, relative to i0
+  std::vector<uint8_t> flags;
+  int32_t rc;
+  if (gang_off) {
+    for (size_t g = g0; g <= g1; ++g) off.push_back((*gang_off)[g] - (int64_t)i0);
+    flags.assign(g1 - g0, 0);
+    rc = kt_paged_admit_gangs(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, (int64_t)(g1 - g0), off.data(),
+                              /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT, summary.data(), T > 0 ? status.data() : nullptr, flags.data());
+  } else {
+    rc = kt_paged_admit(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT,
+                        summary.data(), T > 0 ? status.data() : nullptr);
+  }
+  if (rc == KT_OK) rc = p.fetch_pod_amounts((int64_t)m, rows.data() + i0, &amts);
+  if (rc != KT_OK) {
+    for (size_t i = i0; i < i1; ++i) out[i].code = Error, out[i].reasons = {p.engine_error(rc)};
+    return;
+  }
+  std::vector<uint8_t> keeps(m, 1);  // the pod's reservation stands (always, without gangs)
+  for (size_t g = 0; g + 1 < off.size(); ++g) {
+    (*admitted)[g0 + g] = flags[g];
+    for (int64_t j = off[g]; j < off[g + 1]; ++j) keeps[(size_t)j] = flags[g];
+  }
+  for (size_t j = 0; j < m; ++j) {
+    const size_t i = i0 + j;
+    const uint8_t* row = status.data() + j * (size_t)T;
+    const uint64_t v = KT_SUMMARY_VERDICT(summary[j]);
+    if (v == KT_VERDICT_ERROR) {
+      out[i].code = Error;
+      out[i].reasons.push_back("throttle check failed for pod " + pod_keys[i] + " (invalid selector or unknown namespace)");
+    } else if (v != KT_VERDICT_SUCCESS) {
+      out[i].code = UnschedulableAndUnresolvable;
+      out[i].reasons = block_reasons(p, row, (size_t)T);
+      out[i].events = block_events(p, row, (size_t)T);
+    } else if (keeps[j]) {
+      const DenseAmount& amt = amts[j];
+      for (int32_t t = 0; t < T; ++t)
+        if (row[t] != KT_STATUS_NOT_AFFECTED) p.reserved[t][pod_keys[i]] = amt;  // the engine already holds the totals
+    }
+  }
+}
+
 // One scheduling pass over a queue of pending pods IN ORDER: PreFilter, and on Success Reserve — a single engine
 // launch (kt_paged_admit) instead of 2 x n calls.  The reserved cache is updated exactly as n
 // Reserve calls would have (reserved_resource_amounts.go:66-77), so Unreserve keeps working pod by pod.
@@ -1136,40 +1192,7 @@ std::vector<Status> KubeThrottler::AdmitQueue(const std::vector<std::string>& po
       if (kv.second.count(key)) return true;
     return false;
   };
-  auto admit_segment = [&](size_t i0, size_t i1) {
-    const size_t m = i1 - i0;
-    if (m == 0) return;
-    int32_t T = 0;
-    kt_throttle_rows(p.e, &T);
-    std::vector<uint64_t> summary(m);
-    std::vector<uint8_t> status(m * (size_t)(T > 0 ? T : 1));
-    std::vector<DenseAmount> amts;
-    // every page (pages[0] == e; usually the only one): the verdicts combined, the reservations on every page
-    int32_t rc = kt_paged_admit(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, /*isThrottledOnEqual=*/0,
-                                KT_ADMIT_COMMIT, summary.data(), T > 0 ? status.data() : nullptr);
-    if (rc == KT_OK) rc = p.fetch_pod_amounts((int64_t)m, rows.data() + i0, &amts);
-    if (rc != KT_OK) {
-      for (size_t i = i0; i < i1; ++i) out[i].code = Error, out[i].reasons = {p.engine_error(rc)};
-      return;
-    }
-    for (size_t j = 0; j < m; ++j) {
-      const size_t i = i0 + j;
-      const uint8_t* row = status.data() + j * (size_t)T;
-      const uint64_t v = KT_SUMMARY_VERDICT(summary[j]);
-      if (v == KT_VERDICT_ERROR) {
-        out[i].code = Error;
-        out[i].reasons.push_back("throttle check failed for pod " + pod_keys[i] + " (invalid selector or unknown namespace)");
-      } else if (v != KT_VERDICT_SUCCESS) {
-        out[i].code = UnschedulableAndUnresolvable;
-        out[i].reasons = block_reasons(p, row, (size_t)T);
-        out[i].events = block_events(p, row, (size_t)T);
-      } else {
-        const DenseAmount& amt = amts[j];
-        for (int32_t t = 0; t < T; ++t)
-          if (row[t] != KT_STATUS_NOT_AFFECTED) p.reserved[t][pod_keys[i]] = amt;  // the engine already holds the totals
-      }
-    }
-  };
+  auto admit_segment = [&](size_t i0, size_t i1) { admit_engine_segment(p, pod_keys, rows, i0, i1, &out, nullptr, nullptr); };
   size_t seg0 = 0;
   std::set<std::string> in_segment;
   for (size_t i = 0; i < n; ++i) {
@@ -1186,6 +1209,76 @@ std::vector<Status> KubeThrottler::AdmitQueue(const std::vector<std::string>& po
   }
   admit_segment(seg0, n);
   return out;
+}
+
+// A scheduling pass over a queue of GANGS (jobs whose pods only run together), in order: every member gets PreFilter and, on
+// Success, Reserve; a gang with a member that did not succeed gets Unreserve for all its members (plugin.go:240-257) before the next
+// gang is looked at — ONE engine launch per segment (kt_paged_admit_gangs) instead of up to 3 x n calls.  Segments end on gang
+// boundaries; a gang that holds a pod which is already reserved, or one named twice (in the gang or earlier in the segment), goes the
+// plain way — the engine's walk would add that pod's amount a second time (see AdmitQueue).
+GangAdmission KubeThrottler::AdmitGangs(const std::vector<std::vector<std::string>>& gangs) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  GangAdmission res;
+  std::vector<std::string> pod_keys;
+  std::vector<int64_t> gang_off{0};
+  for (auto& g : gangs) {
+    pod_keys.insert(pod_keys.end(), g.begin(), g.end());
+    gang_off.push_back((int64_t)pod_keys.size());
+  }
+  const size_t n = pod_keys.size(), G = gangs.size();
+  res.status.assign(n, Status{});
+  res.admitted.assign(G, 0);
+  std::vector<int64_t> rows(n);
+  for (size_t i = 0; i < n; ++i) {
+    rows[i] = p.pod_rows.find(pod_keys[i]);
+    if (rows[i] < 0) {
+      for (auto& st : res.status) st.code = Error, st.reasons = {"pod " + pod_keys[i] + " is not known to the plugin (OnPodAdd first)"};
+      return res;
+    }
+  }
+  auto already_reserved = [&](const std::string& key) {
+    for (auto& kv : p.reserved)
+      if (kv.second.count(key)) return true;
+    return false;
+  };
+  size_t seg0 = 0;  // first gang of the current engine segment
+  std::set<std::string> in_segment;
+  auto flush = [&](size_t g_end) {
+    if (g_end > seg0)
+      admit_engine_segment(p, pod_keys, rows, (size_t)gang_off[seg0], (size_t)gang_off[g_end], &res.status, &gang_off, &res.admitted, seg0, g_end);
+    in_segment.clear();
+  };
+  for (size_t g = 0; g < G; ++g) {
+    if (gangs[g].empty()) {  // nothing to place: admitted, and no engine gang (the C-ABI refuses empty ones)
+      flush(g);
+      res.admitted[g] = 1;
+      seg0 = g + 1;
+      continue;
+    }
+    bool plain = false;
+    std::set<std::string> own;
+    for (auto& key : gangs[g]) plain |= !own.insert(key).second || in_segment.count(key) || already_reserved(key);
+    if (!plain) {
+      in_segment.insert(own.begin(), own.end());
+      continue;
+    }
+    flush(g);
+    bool all = true;
+    for (int64_t i = gang_off[g]; i < gang_off[g + 1]; ++i) {
+      const Pod pod = p.pods.at(pod_keys[(size_t)i]);
+      Status& st = res.status[(size_t)i];
+      st = PreFilter(pod);
+      if (st.IsSuccess()) st = Reserve(pod);
+      all &= st.IsSuccess();
+    }
+    if (!all)
+      for (int64_t i = gang_off[g]; i < gang_off[g + 1]; ++i) Unreserve(p.pods.at(pod_keys[(size_t)i]));
+    res.admitted[g] = all ? 1 : 0;
+    seg0 = g + 1;
+  }
+  flush(G);
+  return res;
 }
 
 // ---------------------------------------------------------------------------------------------------

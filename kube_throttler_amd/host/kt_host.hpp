@@ -143,6 +143,13 @@ struct Status {
   bool IsSuccess() const { return code == Success; }
 };
 
+// AdmitGangs: what PreFilter / Reserve answered per pod (in the order of the flattened gangs), and per gang 1 admitted /
+// 0 rolled back (every member un-reserved)
+struct GangAdmission {
+  std::vector<Status> status;
+  std::vector<uint8_t> admitted;
+};
+
 // KubeThrottlerPluginArgs (pkg/scheduler_plugin/plugin_args.go:33-40) + engine sizing
 struct PluginArgs {
   std::string name;                 // throttler name (required)
@@ -186,6 +193,10 @@ class KubeThrottler {
   // ---- one scheduling pass over a queue of pending pods (by Key(), fed through OnPodAdd) in order: PreFilter and,
   // on Success, Reserve — ONE engine launch (kt_paged_admit) instead of 2 x n calls; same reserved bookkeeping
   std::vector<Status> AdmitQueue(const std::vector<std::string>& pod_keys);
+  // the same pass over GANGS, each admitted all or nothing: per member PreFilter and, on Success, Reserve; a gang with a member
+  // that did not succeed gets Unreserve for every member before the next gang — one engine launch per segment
+  // (kt_paged_admit_gangs).  Only members of admitted gangs are in the reservation map afterwards (Unreserve works pod by pod)
+  GangAdmission AdmitGangs(const std::vector<std::vector<std::string>>& gangs);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

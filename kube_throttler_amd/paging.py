@@ -137,6 +137,16 @@ class PagedEngine:
         assert (verdicts(status)[ok] == v[ok]).all(), "kt_paged_admit: summary words disagree with the combined status rows"
         return status, v
 
+    def admit_gangs(self, rows, gang_off, on_equal=False, commit=False):
+        """The queue ``rows`` in consecutive gangs ``[gang_off[g], gang_off[g + 1])`` through kt_paged_admit_gangs: every gang is
+        admitted as a whole or rolled back on every page before the next one starts -> (status matrix [n][throttles] at each
+        pod's turn, verdict per pod, admitted byte per gang), combined over the pages."""
+        status, summary, admitted = E.paged_admit_gangs(self.engines, rows, gang_off, on_equal=on_equal, commit=commit)
+        v = np.where(summary == 2, S.VERDICT_ERROR, np.where((summary & 1) != 0, S.VERDICT_BLOCK, S.VERDICT_ALLOW)).astype(np.uint8)
+        ok = v != S.VERDICT_ERROR  # (an error row keeps page 0's precomputed status row; its summary word says error)
+        assert (verdicts(status)[ok] == v[ok]).all(), "kt_paged_admit_gangs: summary words disagree with the combined status rows"
+        return status, v, admitted
+
     def fetch_reserved(self) -> list:
         """Reserved amounts per throttle row, put together by resource NAME from the pages (like combine_reconcile):
         {"resourceCounts": {"pod": n}?, "resourceRequests": {name: Fraction}?}."""
