@@ -359,6 +359,8 @@ const char* kt_kernel_name(kt_engine* e, int32_t kernel);
                                       (an unconvertible podSelector term; more than 512 selector terms) */
 #define KT_COUNTER_PACKED_WORDS 9   /* 64-bit words per pod of the packed fold the last full aggregate scan ran with (1..8; 0: the
                                       plain fold — a negative request, sums beyond int64, fields that do not fit) */
+#define KT_COUNTER_VIEW_BUILDS 10   /* builds of a scan view so far, the aggregate's or the check sweep's (a pod event that fits the
+                                      views is patched into them in place and does not count) */
 int64_t kt_counter(kt_engine* e, int32_t which);
 /* ---- More resource names than one engine has dimensions (KT_MAX_DIMS): PAGES.  The reference sums and compares any resource
  *      name (pkg/resourcelist/resourcelist.go:27-54, resource_amount.go:127-159).  The host builds the same cluster once per

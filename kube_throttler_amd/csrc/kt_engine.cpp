@@ -362,16 +362,11 @@ int32_t kt_engine_destroy(kt_engine* e) {
   if (e->pods.meta) (void)hipFree(e->pods.meta);
   e->d_latom.release();
   e->d_overflow.release();
-  e->d_countable.release();
-  e->d_order_all.release();
-  e->d_vc_meta.release(); e->d_va_meta.release(); e->d_carry.release();
-  e->d_vc_latom.release(); e->d_va_latom.release(); e->d_vc_req.release(); e->d_vc_pk.release();
-  e->d_pos_c.release(); e->d_pos_a.release(); e->d_view_dirty.release(); e->d_n_all.release();
-  e->d_ns_cursor.release(); e->d_range_a.release(); e->d_range_c.release();
+  e->views.release();
+  e->d_carry.release();
   e->d_slab_tag.release();
   e->d_row_mask.release();
   e->d_req_sums.release();
-  e->d_n_countable.release();
   e->d_ticket.release();
   if (e->h_small) (void)hipHostFree(e->h_small);
   if (e->h_few) (void)hipHostFree(e->h_few);
@@ -525,6 +520,7 @@ int64_t kt_counter(kt_engine* e, int32_t which) {
     case KT_COUNTER_INDEX_IMAGE_WORDS: return e->ctr_index_image_words.load(std::memory_order_relaxed);
     case KT_COUNTER_SLOW_THROTTLES: return e->ctr_slow_throttles.load(std::memory_order_relaxed);
     case KT_COUNTER_PACKED_WORDS: return e->ctr_packed_words.load(std::memory_order_relaxed);
+    case KT_COUNTER_VIEW_BUILDS: return e->ctr_view_builds.load(std::memory_order_relaxed);
     default: return -1;
   }
 }

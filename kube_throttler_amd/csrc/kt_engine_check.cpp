@@ -6,7 +6,6 @@
 // ---------------------------------------------------------------------------------------------------
 // check
 // ---------------------------------------------------------------------------------------------------
-// allow_small: false for callers that go on working on the device-side rows / summaries (kt_admit_launch)
 // The CheckRecs only depend on (stored status, reserved amounts, isThrottledOnEqual): rebuilt when one of them changed
 // since they were last built (by kt_prepare_check or by kt_finalize with APPLY)
 static int32_t ensure_check_recs(kt_engine* e, int32_t on_equal, int DT, hipStream_t s) {
@@ -27,6 +26,7 @@ static int32_t ensure_check_recs(kt_engine* e, int32_t on_equal, int DT, hipStre
   return KT_OK;
 }
 
+// allow_small: false for callers that go on working on the device-side rows / summaries (kt_admit_launch)
 static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
                                    hipStream_t s, bool allow_small = true) {
   if (pod_rows) {
@@ -80,42 +80,16 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
       // a sweep over every row of a multi-chunk index runs in namespace order (results stay indexed by pod row)
       const bool by_ns = !pod_rows && !small && n == e->pod_rows_hi && (e->dindex.n_chunks > 1 || e->sw[kSw_FORCE_NS_ORDER]) && !e->sw[kSw_NO_NS_ORDER];
       if (by_ns && (rc = settle_view_patches(e, s)) != KT_OK) return rc;
-      if (by_ns && (!e->order_all_valid || e->view_rows_a != e->pod_rows_hi)) {
-        KT_HIP(e, e->d_order_all.reserve((size_t)e->pod_rows_hi + 1));
-        KT_HIP(e, e->d_ns_cursor.reserve((size_t)e->sp.n_ns + 1));
-        KT_HIP(e, e->d_n_all.reserve(1));
-        kt::launch_order_rows_by_ns(e->pods, e->pod_rows_hi, /*countable_only=*/false, (uint32_t)e->sp.n_ns,
-                                    e->d_ns_cursor.p, e->d_order_all.p, e->d_n_all.p, s);
-        KT_HIP(e, hipGetLastError());
-        e->range_a_G = 0;
-        if (!e->sw[kSw_NO_WG_RANGES]) {  // every row is listed: the list holds pod_rows_hi records
-          // (planned on the host from a copy of the namespace ends — a view build is not a per-step cost, and the one GPU
-          //  thread the plan used to run on took 388 us, longer than the synchronisation and the walk here)
-          e->range_a_G = kt::check_sweep_blocks(e->pod_rows_hi);
-          KT_HIP(e, e->d_range_a.reserve((size_t)e->range_a_G + 2));
-          e->h_ns_end.resize((size_t)e->sp.n_ns + 1);
-          KT_HIP(e, hipMemcpyAsync(e->h_ns_end.data(), e->d_ns_cursor.p, (size_t)e->sp.n_ns * 8, hipMemcpyDeviceToHost, s));
-          KT_HIP(e, hipStreamSynchronize(s));
-          e->h_range.resize((size_t)e->range_a_G + 2);
-          kt::plan_wg_ranges(e->h_ns_end.data(), (uint32_t)e->sp.n_ns, e->pod_rows_hi, e->range_a_G, e->h_range.data());
-          KT_HIP(e, hipMemcpyAsync(e->d_range_a.p, e->h_range.data(), e->h_range.size() * 4, hipMemcpyHostToDevice, s));
-          KT_HIP(e, hipStreamSynchronize(s));
-        }
-        const size_t na = (size_t)e->pod_rows_hi + 1;
-        KT_HIP(e, e->d_va_meta.reserve(na));
-        KT_HIP(e, e->d_va_latom.reserve(na * (size_t)e->pods.LA));
-        KT_HIP(e, e->d_carry.reserve(na));
-        KT_HIP(e, e->d_pos_a.reserve(na));
-        KT_HIP(e, e->d_view_dirty.reserve(4));
-        if (!e->view_check_dirty) KT_HIP(e, hipMemsetAsync(e->d_view_dirty.p, 0, 4, s));
-        KT_HIP(e, hipMemsetAsync(e->d_pos_a.p, 0xFF, na * 4, s));
-        kt::launch_build_scan_view(e->pods, e->pod_rows_hi, e->d_order_all.p, e->d_va_meta.p, e->d_va_latom.p, nullptr, s, nullptr, nullptr, e->d_pos_a.p);
-        KT_HIP(e, hipGetLastError());
-        e->view_rows_a = e->pod_rows_hi;
-        e->order_all_valid = true;
+      ScanView& av = e->views.all_rows;
+      if (by_ns && (!av.valid || (int64_t)av.n != e->pod_rows_hi)) {  // every row is listed: the view holds pod_rows_hi records
+        const ViewSpec spec{/*countable_only=*/false, /*by_ns=*/true, kt::check_sweep_blocks, e->pod_rows_hi, /*requests=*/false};
+        KT_HIP(e, e->d_carry.reserve((size_t)e->pod_rows_hi + 1));
+        if ((rc = list_view_rows(e, av, spec, s)) != KT_OK) return rc;
+        if ((rc = copy_view_records(e, av, spec, /*headroom=*/0, s)) != KT_OK) return rc;
+        av.valid = true;
       }
-      kt::CheckByNs view{e->d_va_meta.p, e->d_va_latom.p, e->d_carry.p};
-      if (by_ns && e->range_a_G) view.wg_range = e->d_range_a.p, view.wg_range_G = e->range_a_G;
+      kt::CheckByNs view{av.meta.p, av.latom.p, e->d_carry.p};
+      if (by_ns && av.range_G) view.wg_range = av.range.p, view.wg_range_G = av.range_G;
       if (by_ns && !want_status && e->dindex.n_slow == 0 && e->n_overflow == 0 && e->dindex.n_chunks > 1 && !e->sw[kSw_NO_VERDICT_IMAGES]) {
         // the lean sweep of a multi-chunk program: TermInfo + WordVerdict of every word once per generation of CheckRecs
         // (one small launch) instead of once per (workgroup, chunk) — 256 x ~15 rebuilds of the same words
@@ -128,7 +102,7 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
         }
         view.wv_img = e->d_wvimg[b].p, view.wv_total_words = e->dindex.bm_words;
       }
-      const char* k = kt::launch_check_indexed(e->pods, n, by_ns ? e->d_order_all.p : pod_rows ? e->d_rows.p : nullptr, e->sp, e->d_sp.p, e->dindex,
+      const char* k = kt::launch_check_indexed(e->pods, n, by_ns ? av.rows.p : pod_rows ? e->d_rows.p : nullptr, e->sp, e->d_sp.p, e->dindex,
                                                e->recs_ptr(), e->d_summary.p, want_status ? e->d_status.p : nullptr, s,
                                                small ? &sm : nullptr, e->n_overflow != 0, by_ns ? &view : nullptr, e->sw[kSw_CHECK_ONE_PER_CU]);
       if (!k) return e->fail(KT_ERR_UNSUPPORTED, "%d throttle rows exceed the indexed check kernel's LDS budget (use kernel_variant 1)", e->thr_rows_hi);

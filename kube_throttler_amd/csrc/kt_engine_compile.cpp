@@ -210,7 +210,7 @@ int32_t compile_program(kt_engine* e, hipStream_t s) {
   KT_HIP(e, hipMemsetAsync(e->d_overflow.p, 0, 8, s));
   kt::launch_translate_pods(e->pods, e->pod_rows_hi, nullptr, 0, e->dindex, e->d_overflow.p, s);
   KT_HIP(e, hipGetLastError());
-  e->countable_valid = false, e->order_all_valid = false;  // the scan views hold copies of the atom rows
+  e->views.invalidate();  // the scan views hold copies of the atom rows
   KT_HIP(e, hipMemcpyAsync(&e->n_overflow, e->d_overflow.p, 8, hipMemcpyDeviceToHost, s));
   KT_HIP(e, hipStreamSynchronize(s));  // host vectors go out of scope
   e->sp.thr_term_off = e->d_thr_term_off.p;

@@ -32,67 +32,6 @@ int32_t kt_delete_namespaces(kt_engine* e, int32_t n, const int32_t* rows) {
   return KT_OK;
 }
 
-
-// ---- pod events applied to the scan views in place
-constexpr int64_t kPatchBatchMax = 65536;
-// can a batch of n pod rows (largest |request| per dimension batch_max, OR of the values batch_or, a negative value seen)
-// be applied to the current views?  The packed request words only hold what their plan was proved for.
-static bool views_patchable(const kt_engine* e, int64_t n, const unsigned __int128* batch_max, const uint64_t* batch_or, bool batch_neg) {
-  if (e->incremental || e->cfg.kernel_variant != 0 || e->program_dirty || n > kPatchBatchMax) return false;
-  if (!e->countable_valid && !e->order_all_valid) return false;  // nothing to patch: the next scan builds anyway
-  if (e->sw[kSw_NO_VIEW_PATCH]) return false;
-  if (e->countable_valid) {
-    if (e->d_vc_meta.p == nullptr || e->d_pos_c.p == nullptr) return false;
-    if (e->view_extra + n > e->view_cap_c - (int64_t)e->n_countable) return false;
-    if (e->pack.nw) {
-      if (batch_neg) return false;
-      for (int d = 0; d < e->D; ++d) {
-        if (batch_max[d] > e->max_abs[d]) return false;  // a field may be too narrow
-        if (e->pack.shift[d] && (batch_or[d] & ((1ull << e->pack.shift[d]) - 1ull))) return false;  // fewer common trailing zeros
-      }
-    } else if (!e->neg_seen && !batch_neg) {
-      // unpacked view of an engine that could pack: a rebuild decides again
-    }
-  }
-  return true;
-}
-// the views a pod event batch of n rows has to be applied to (host bookkeeping included: call once per batch)
-static kt::ViewPatch view_patch_of(kt_engine* e, int64_t n) {
-  kt::ViewPatch v{};
-  if (e->countable_valid) {
-    v.vc_meta = e->d_vc_meta.p, v.vc_latom = e->d_vc_latom.p, v.vc_req = e->pack.nw ? nullptr : e->d_vc_req.p, v.vc_pk = e->pack.nw ? e->d_vc_pk.p : nullptr;
-    v.vc_rows = e->d_countable.p, v.pos_c = e->d_pos_c.p, v.n_c = e->d_n_countable.p, v.cap_c = e->view_cap_c;
-    v.by_ns = e->countable_by_ns ? 1u : 0u;
-    v.pk = e->pack;
-    if (!e->countable_by_ns) e->view_extra += n;  // at most n appended
-  }
-  if (e->order_all_valid) {
-    v.va_meta = e->d_va_meta.p, v.va_latom = e->d_va_latom.p, v.pos_a = e->d_pos_a.p, v.rows_a = e->view_rows_a;
-  }
-  v.dirty = e->d_view_dirty.p;
-  if ((e->countable_valid && e->countable_by_ns) || e->order_all_valid) e->view_check_dirty = true;
-  return v;
-}
-static int32_t patch_views(kt_engine* e, int64_t n, const int64_t* rows_dev, int64_t row0, hipStream_t s) {
-  const kt::ViewPatch v = view_patch_of(e, n);
-  kt::launch_patch_scan_views(e->pods, n, rows_dev, row0, v, s);
-  KT_HIP(e, hipGetLastError());
-  return KT_OK;
-}
-// before a scan uses a namespace-ordered view that was patched: did an entry have to move?
-int32_t settle_view_patches(kt_engine* e, hipStream_t s) {
-  if (!e->view_check_dirty) return KT_OK;
-  uint32_t dirty = 0;
-  KT_HIP(e, hipMemcpyAsync(&dirty, e->d_view_dirty.p, 4, hipMemcpyDeviceToHost, s));
-  KT_HIP(e, hipStreamSynchronize(s));
-  if (dirty) {
-    e->countable_valid = false, e->order_all_valid = false;
-    KT_HIP(e, hipMemsetAsync(e->d_view_dirty.p, 0, 4, s));
-  }
-  e->view_check_dirty = false;
-  return KT_OK;
-}
-
 static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int64_t* rows) {
   const int D = e->D;
   if (b->D != D) return e->fail(KT_ERR_INVALID_ARGUMENT, "batch D=%d, engine D=%d", b->D, D);
@@ -142,10 +81,7 @@ static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int6
     e->max_abs[d] = std::max(batch_max[d], e->max_abs[d]);
     e->or_abs[d] |= batch_or[d];
   }
-  if (!patch) {
-    e->countable_valid = false;
-    e->order_all_valid = false;
-  }
+  if (!patch) e->views.invalidate();
   // the overflow guard's bound grows by what this batch brings; only when it passes 2^60 does the next reconcile count
   // exactly on the device (request_sums_in_range), which also forgets the overwritten and deleted pods again
   for (int d = 0; d < D; ++d) {
@@ -361,10 +297,7 @@ int32_t kt_delete_pods(kt_engine* e, int64_t n, const int64_t* rows) {
   const unsigned __int128 no_max[KT_MAX_DIMS] = {0};
   const uint64_t no_or[KT_MAX_DIMS] = {0};
   const bool patch = views_patchable(e, n, no_max, no_or, false);
-  if (!patch) {
-    e->countable_valid = false;
-    e->order_all_valid = false;
-  }
+  if (!patch) e->views.invalidate();
   if (e->incremental && e->program_dirty) e->agg_valid = false;
   unsigned long long spin_seq = 0ull;
   if (slot_path && n <= kt::kFeedSmallMax && !e->sw[kSw_NO_FEED_FUSION]) {
@@ -610,10 +543,9 @@ int32_t kt_load_snapshot(kt_engine* e, const kt_snapshot* s) {
   KT_HIP(e, hipMemsetAsync(e->pods.flags, 0, (size_t)e->cfg.pod_capacity * 4, e->own_stream));
   KT_HIP(e, hipMemsetAsync(e->pods.meta, 0, (size_t)e->cfg.pod_capacity * 8, e->own_stream));
   KT_HIP(e, hipStreamSynchronize(e->own_stream));
-  e->countable_valid = false;
+  e->views.invalidate();
   e->req_sums_valid = true;
   for (auto& b : e->req_sum_bound) b = 0;
-  e->order_all_valid = false;
   e->pod_rows_hi = 0;
   e->pod_ns_hi = 0;
   e->neg_seen = false;

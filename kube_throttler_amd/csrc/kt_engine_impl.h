@@ -5,6 +5,7 @@
 //   kt_engine_feed.cpp       state feed: namespaces, pods, throttles, status, reserved amounts, snapshots
 //   kt_engine_reconcile.cpp  aggregate / exchange (kt_comm_*) / finalize and their fetches
 //   kt_engine_check.cpp      PreFilter: sweeps, few-pod checks, admission queues, pages
+//   kt_engine_views.cpp      the scan views of the aggregate and the sweep: built, patched by pod events, settled
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -125,6 +126,46 @@ struct AmountDev {
   void release() { v.release(); present.release(); count.release(); has_count.release(); }
 };
 
+// A scan view: pod rows in scan order, scan-ordered copies of their records, the row -> record table and the record ranges of a
+// namespace-ordered scan's workgroups.  Built by list_view_rows + copy_view_records, patched in place by the pod events that fit.
+struct ScanView {
+  DevBuf<int64_t> rows;            // the listed pod rows (kt_order_rows_by_ns / kt_compact_countable)
+  DevBuf<unsigned long long> d_n;  // how many: the device's count ...
+  unsigned long long n = 0;        // ... and the host's copy of it as of the build (appended records are counted by `extra`)
+  DevBuf<uint64_t> meta;           // record copies, scan order: meta words,
+  DevBuf<uint16_t> latom;          //   atom rows,
+  DevBuf<int64_t> req;             //   request rows (pack.nw == 0) or
+  DevBuf<uint64_t> pk;             //   packed request words
+  kt::PackPlan pack;               // packed fold of the view (nw == 0: plain fold)
+  DevBuf<int32_t> pos;             // pod row -> its record (-1: not listed)
+  DevBuf<uint32_t> range;          // record ranges of the scan's workgroups, ends at namespace boundaries (plan_wg_ranges) ...
+  int range_G = 0;                 // ... and the grid they were planned for (0: none)
+  int64_t cap = 0;                 // records the copies hold
+  int64_t extra = 0;               // upper bound of the records appended since: a scan covers n + extra (zero = not countable)
+  bool by_ns = false;              // ordered by namespace (multi-chunk index) / ascending rows
+  bool valid = false;              // describes the current pod table
+  void release() { rows.release(); d_n.release(); meta.release(); latom.release(); req.release(); pk.release(); pos.release(); range.release(); }
+};
+// what differs between the builds of the two views
+struct ViewSpec {
+  bool countable_only;   // list the countable pods (pod events append records behind them) / every row
+  bool by_ns;            // namespace order / ascending rows
+  int (*grid)(int64_t);  // workgroups of the scan that will read n records: the ranges are planned for them
+  int64_t rows_cap;      // pod rows the list and the position table are sized for
+  bool requests;         // copy the requests too (the aggregate folds them; the check does not read them)
+};
+struct ScanViews {
+  ScanView countable;  // the aggregate's: namespace order for a multi-chunk index, ascending rows otherwise
+  ScanView all_rows;   // the lean PreFilter sweep's over a multi-chunk index: every row, namespace order
+  DevBuf<unsigned long long> d_ns_cursor;    // counting-sort scratch (one word per namespace row); left holding the namespace ends
+  std::vector<unsigned long long> h_ns_end;  // host copy of those ends (plan_wg_ranges)
+  std::vector<uint32_t> h_range;             // ... and the ranges planned from it, on their way to the device
+  DevBuf<uint32_t> d_dirty;  // raised by kt_patch_scan_views when an entry of a namespace-ordered view would have had to move
+  bool check_dirty = false;  // ... which may have happened: read it before the next scan (settle_view_patches)
+  void invalidate() { countable.valid = false, all_rows.valid = false; }
+  void release() { countable.release(); all_rows.release(); d_ns_cursor.release(); d_dirty.release(); }
+};
+
 struct AmountHostFlat {
   std::vector<int64_t> v;
   std::vector<uint32_t> present;
@@ -198,13 +239,10 @@ struct kt_engine {
   int64_t pod_rows_hi = 0;             // 1 + highest row ever upserted
   unsigned __int128 max_abs[KT_MAX_DIMS] = {0};  // max |effective request| bound per dimension
   uint64_t or_abs[KT_MAX_DIMS] = {0};            // OR of every |request| fed: its trailing zero bits are common to all of them
-  kt::PackPlan pack;                             // packed fold of the current scan view (nw == 0: plain fold)
-  std::vector<unsigned long long> h_ns_end;      // host copy of the namespace ends of a namespace-ordered list (plan_wg_ranges)
-  std::vector<uint32_t> h_range;                 // ... and the ranges planned from it, on their way to the device
+  ScanViews views;                               // what the full scans read (kt_engine_views.cpp)
   bool cut_plain = false;                        // a scan needed the plain fold: the index chunks stay cut for plain records
   void* cur_launch_lock = nullptr;               // the LaunchLock of the launch-side call in progress (set and cleared under op_mu)
-  std::atomic<int64_t> ctr_index_chunks{0}, ctr_index_words{0}, ctr_index_image_words{0}, ctr_ns_rows{0}, ctr_ns_word_visits{0}, ctr_ns_chunk_visits{0}, ctr_slow_throttles{0}, ctr_packed_words{0};
-  DevBuf<uint64_t> d_vc_pk;                      // packed request words of the countable list, scan order
+  std::atomic<int64_t> ctr_index_chunks{0}, ctr_index_words{0}, ctr_index_image_words{0}, ctr_ns_rows{0}, ctr_ns_word_visits{0}, ctr_ns_chunk_visits{0}, ctr_slow_throttles{0}, ctr_packed_words{0}, ctr_view_builds{0};
   DevBuf<uint16_t> d_latom;                      // pods.latom: rewritten per selector program (kt_translate_pods)
   DevBuf<unsigned long long> d_overflow;         // valid pods whose relevant atoms did not fit pods.LA
   unsigned long long n_overflow = 0;
@@ -229,36 +267,10 @@ struct kt_engine {
   bool overflow_in_flight = false;
   unsigned long long ingest_seq = 0;         // sequence numbers handed to the event kernels
   unsigned long long ingest_spin_seq = 0;    // != 0: the newest asynchronous feed call signals h_overflow[1] = this (settle_ingest spins)
-  DevBuf<int64_t> d_countable;                   // rows of the pods a reconcile scans (kt_compact_countable)
-  DevBuf<unsigned long long> d_n_countable;
-  unsigned long long n_countable = 0;
   bool req_sums_valid = true;                    // the requests of the current pods are proven to add up inside 2^60
   unsigned __int128 req_sum_bound[KT_MAX_DIMS] = {0};  // >= sum of |request| over the pods held, per dimension: the last exact
                                                  // device total + everything fed since (overwritten / deleted pods stay in)
   DevBuf<unsigned long long> d_req_sums;
-  // Pod events are applied to the scan lists / views IN PLACE (kt_patch_scan_views) as long as they fit what the views were
-  // built for; d_pos_c / d_pos_a map a pod row to its record.  view_cap_c: records the countable view holds; view_extra:
-  // upper bound of the records appended since it was built (the scan covers n_countable + view_extra records: what was
-  // not really appended is zero = not countable); view_check_dirty: a namespace-ordered view was patched — the kernel
-  // raises d_view_dirty when an entry would have had to move, read before the next scan
-  DevBuf<int32_t> d_pos_c, d_pos_a;
-  DevBuf<uint32_t> d_view_dirty;
-  DevBuf<unsigned long long> d_n_all;
-  int64_t view_cap_c = 0, view_extra = 0, view_rows_a = 0;
-  bool view_check_dirty = false;
-  bool countable_valid = false;                  // d_countable describes the current pod table
-  bool countable_by_ns = false;                  // ... ordered by namespace (multi-chunk index: kt_order_rows_by_ns)
-  DevBuf<int64_t> d_order_all;                   // every pod row ordered by namespace: the check sweep's scan order
-  bool order_all_valid = false;
-  DevBuf<unsigned long long> d_ns_cursor;        // counting-sort scratch (one word per namespace row)
-  // record ranges of the workgroups of a namespace-ordered scan, ends at namespace boundaries (plan_wg_ranges, host side): the all-rows
-  // list (check sweep) and the countable list (aggregate); *_G = the grid they were planned for (0: none)
-  DevBuf<uint32_t> d_range_a, d_range_c;
-  int range_a_G = 0, range_c_G = 0;
-  // scan-ordered copies of the listed pods' records (kt_build_scan_view): countable list / all-rows list
-  DevBuf<uint64_t> d_vc_meta, d_va_meta, d_carry;
-  DevBuf<uint16_t> d_vc_latom, d_va_latom;
-  DevBuf<int64_t> d_vc_req;
   DevBuf<uint8_t> d_row_mask;                    // kt_reconcile_rows_launch: the keys of the reconcile, a byte per throttle row
   DevBuf<uint32_t> d_slab_tag;                   // [chunks][256] epoch of the launch that last spilled a slab
   uint32_t slab_epoch = 0;
@@ -374,6 +386,7 @@ struct kt_engine {
   std::atomic<int64_t> few_served{0};
   std::atomic<int64_t> n_compiles{0};
   DevBuf<uint64_t> d_summary;
+  DevBuf<uint64_t> d_carry;           // namespace-ordered sweep (kt::CheckByNs): a word per listed row
   DevBuf<uint8_t> d_status;
   DevBuf<int64_t> d_rows;
   int64_t check_n = 0;
@@ -576,7 +589,12 @@ KT_INTERNAL void amount_to_table(const HostAmount& h, const kt_amounts& a, size_
 KT_INTERNAL kt::ReqBound req_bound(const kt_engine* e);
 KT_INTERNAL bool amount_in_bound(const HostAmount& a, int D);
 KT_INTERNAL void reqs_from_pool(const kt_reqs& pool, uint32_t b, uint32_t e_, std::vector<Req>& out);
-// (kt_engine_feed.cpp) before a scan uses a namespace-ordered view that was patched: did an entry have to move?
+// (kt_engine_views.cpp)
+KT_INTERNAL int32_t list_view_rows(kt_engine* e, ScanView& v, const ViewSpec& spec, hipStream_t s);
+KT_INTERNAL int32_t copy_view_records(kt_engine* e, ScanView& v, const ViewSpec& spec, int64_t headroom, hipStream_t s);
+KT_INTERNAL bool views_patchable(const kt_engine* e, int64_t n, const unsigned __int128* batch_max, const uint64_t* batch_or, bool batch_neg);
+KT_INTERNAL kt::ViewPatch view_patch_of(kt_engine* e, int64_t n);
+KT_INTERNAL int32_t patch_views(kt_engine* e, int64_t n, const int64_t* rows_dev, int64_t row0, hipStream_t s);
 KT_INTERNAL int32_t settle_view_patches(kt_engine* e, hipStream_t s);
 // (kt_engine_reconcile.cpp)
 KT_INTERNAL int32_t slab_tags(kt_engine* e, kt::AggScan& sc, hipStream_t s);

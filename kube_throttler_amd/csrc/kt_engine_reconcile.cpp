@@ -193,7 +193,7 @@ int32_t request_sums_in_range(kt_engine* e, hipStream_t s) {
       return e->fail(KT_ERR_OVERFLOW_RISK, "wide sums hold for up to 2^30 pods over all ranks");
     wide = true;
   }
-  if (wide != e->wide) e->countable_valid = false;  // packed request words only exist for sums inside int64
+  if (wide != e->wide) e->views.countable.valid = false;  // packed request words only exist for sums inside int64
   e->wide = wide;
   e->req_sums_valid = true;
   return KT_OK;
@@ -225,85 +225,40 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
   // a multi-chunk index is scanned in namespace order (tiles share their word lists, workgroups skip foreign chunks)
   const bool by_ns = (e->dindex.n_chunks > 1 || e->sw[kSw_FORCE_NS_ORDER]) && !e->sw[kSw_NO_NS_ORDER];
   if ((rc = settle_view_patches(e, s)) != KT_OK) return rc;
+  ScanView& cv = e->views.countable;
   // pod events appended records behind the listed ones; a scan that will gather through the row list instead of streaming
   // the view cannot tell them from the list's zeroed padding: list again
-  if (e->countable_valid && e->view_extra && !(!e->sw[kSw_NO_SCAN_VIEW] && (by_ns || e->dindex.n_chunks == 1))) e->countable_valid = false;
-  if (e->cfg.kernel_variant != 1 && (!e->countable_valid || e->countable_by_ns != by_ns)) {  // pods changed since the last scan: which rows does a reconcile look at
+  if (cv.valid && cv.extra && !(!e->sw[kSw_NO_SCAN_VIEW] && (by_ns || e->dindex.n_chunks == 1))) cv.valid = false;
+  if (e->cfg.kernel_variant != 1 && (!cv.valid || cv.by_ns != by_ns)) {  // pods changed since the last scan: which rows does a reconcile look at
     if (e->last_stream && e->last_stream != s) KT_HIP(e, hipStreamSynchronize(e->last_stream));
-    KT_HIP(e, e->d_countable.reserve((size_t)e->cfg.pod_capacity + 1));
-    KT_HIP(e, e->d_n_countable.reserve(1));
-    if (by_ns) {
-      KT_HIP(e, e->d_ns_cursor.reserve((size_t)e->sp.n_ns + 1));
-      kt::launch_order_rows_by_ns(e->pods, e->pod_rows_hi, /*countable_only=*/true, (uint32_t)e->sp.n_ns,
-                                  e->d_ns_cursor.p, e->d_countable.p, e->d_n_countable.p, s);
-    } else {
-      KT_HIP(e, hipMemsetAsync(e->d_n_countable.p, 0, 8, s));
-      kt::launch_compact_countable(e->pods, e->pod_rows_hi, e->d_countable.p, e->d_n_countable.p, s);
-    }
-    e->countable_by_ns = by_ns;
-    KT_HIP(e, hipGetLastError());
-    KT_HIP(e, hipMemcpyAsync(&e->n_countable, e->d_n_countable.p, 8, hipMemcpyDeviceToHost, s));
-    const bool plan_ranges = by_ns && !e->sw[kSw_NO_WG_RANGES];
-    if (plan_ranges) {  // the ends of the namespaces' records travel with the row count: the ranges are planned on the host
-      e->h_ns_end.resize((size_t)e->sp.n_ns + 1);
-      KT_HIP(e, hipMemcpyAsync(e->h_ns_end.data(), e->d_ns_cursor.p, (size_t)e->sp.n_ns * 8, hipMemcpyDeviceToHost, s));
-    }
-    KT_HIP(e, hipStreamSynchronize(s));
-    e->range_c_G = 0;
-    if (plan_ranges && e->n_countable > 0) {
-      e->range_c_G = kt::aggregate_blocks((int64_t)e->n_countable);
-      KT_HIP(e, e->d_range_c.reserve((size_t)e->range_c_G + 2));
-      e->h_range.resize((size_t)e->range_c_G + 2);
-      kt::plan_wg_ranges(e->h_ns_end.data(), (uint32_t)e->sp.n_ns, (int64_t)e->n_countable, e->range_c_G, e->h_range.data());
-      KT_HIP(e, hipMemcpyAsync(e->d_range_c.p, e->h_range.data(), e->h_range.size() * 4, hipMemcpyHostToDevice, s));
-      KT_HIP(e, hipStreamSynchronize(s));  // (1 KB; h_range is reused)
-    }
-    e->pack = kt::PackPlan();
-    // room for the pods that become countable before the next rebuild (kt_patch_scan_views appends them)
-    const int64_t headroom = std::min<int64_t>(std::max<int64_t>(65536, (int64_t)e->n_countable / 16), e->cfg.pod_capacity - (int64_t)e->n_countable);
+    const ViewSpec spec{/*countable_only=*/true, by_ns, kt::aggregate_blocks, e->cfg.pod_capacity, /*requests=*/true};
+    if ((rc = list_view_rows(e, cv, spec, s)) != KT_OK) return rc;
+    // between the two build steps, what follows from the number of listed rows: the view's headroom and its pack plan.
+    // Room for the pods that become countable before the next rebuild (kt_patch_scan_views appends them):
+    const int64_t headroom = std::min<int64_t>(std::max<int64_t>(65536, (int64_t)cv.n / 16), e->cfg.pod_capacity - (int64_t)cv.n);
     // will the full scans stream the scan view?  (The packed fold exists in that form only: a scan that gathers through the row
     // list — KT_NO_SCAN_VIEW, KT_NO_NS_ORDER on a multi-chunk index — folds plain records.)
-    const bool view_scan = !e->sw[kSw_NO_SCAN_VIEW] && (e->countable_by_ns || e->dindex.n_chunks == 1);
+    const bool view_scan = !e->sw[kSw_NO_SCAN_VIEW] && (cv.by_ns || e->dindex.n_chunks == 1);
     // packed fold (PackPlan, kt_index.h) when every request of this engine is non-negative and the fields fit: sized
     // for the pods ONE workgroup scans with one workgroup per CU (two per CU scan fewer)
+    cv.pack = kt::PackPlan();
     if (view_scan && !e->incremental && !e->wide && !e->sw[kSw_NO_PACK] && !e->dindex.has_long) {
-      const int64_t cap = (int64_t)e->n_countable + headroom;
+      const int64_t cap = (int64_t)cv.n + headroom;
       uint64_t slab_pods = kt::aggregate_slab_pods(cap, kt::aggregate_blocks(cap));
       // (planned ranges hold up to wg_range_cap records)
-      if (e->range_c_G) slab_pods = std::max<uint64_t>(slab_pods, (uint64_t)kt::wg_range_cap((int64_t)e->n_countable, e->range_c_G) + 64u);
-      e->pack = kt::make_pack_plan(e->D, e->max_abs, e->or_abs, e->neg_seen, slab_pods, /*pad_odd=*/true, kt::pack_max_words(e->D));
-      if (e->pack.nw && e->pack.rec_bytes > e->dindex.cut_thr_bytes) e->pack = kt::PackPlan();  // the slab areas hold records of that size
+      if (cv.range_G) slab_pods = std::max<uint64_t>(slab_pods, (uint64_t)kt::wg_range_cap((int64_t)cv.n, cv.range_G) + 64u);
+      cv.pack = kt::make_pack_plan(e->D, e->max_abs, e->or_abs, e->neg_seen, slab_pods, /*pad_odd=*/true, kt::pack_max_words(e->D));
+      if (cv.pack.nw && cv.pack.rec_bytes > e->dindex.cut_thr_bytes) cv.pack = kt::PackPlan();  // the slab areas hold records of that size
     }
-    if (!e->pack.nw && kt::agg_rec_bytes(e->D, e->incremental) > e->dindex.cut_thr_bytes) {
+    if (!cv.pack.nw && kt::agg_rec_bytes(e->D, e->incremental) > e->dindex.cut_thr_bytes) {
       // the plain fold is coming and the chunks were cut for the packed fold's records: cut again, for plain ones (once —
       // the engine then stays with plain-sized chunks), and start over on the new index
       upgrade_launch_lock(e);
       e->cut_plain = true, e->program_dirty = true;
-      e->countable_valid = false;
       return aggregate_locked(e, s, allow_fused);
     }
-    if (!e->sw[kSw_NO_SCAN_VIEW]) {
-      // scan-ordered copies of the listed pods' records: the scan streams them instead of gathering through the list
-      // (namespace order for a multi-chunk index, ascending rows otherwise)
-      e->view_cap_c = (int64_t)e->n_countable + headroom;
-      e->view_extra = 0;
-      const size_t nc = (size_t)e->view_cap_c + 1;
-      KT_HIP(e, e->d_vc_meta.reserve(nc));
-      KT_HIP(e, e->d_vc_latom.reserve(nc * (size_t)e->pods.LA));
-      if (e->pack.nw) KT_HIP(e, e->d_vc_pk.reserve(nc * (size_t)e->pack.stride));
-      else KT_HIP(e, e->d_vc_req.reserve(nc * (size_t)e->pods.DS));
-      KT_HIP(e, e->d_pos_c.reserve((size_t)e->cfg.pod_capacity + 1));
-      KT_HIP(e, e->d_view_dirty.reserve(4));
-      KT_HIP(e, hipMemsetAsync(e->d_pos_c.p, 0xFF, ((size_t)e->cfg.pod_capacity + 1) * 4, s));
-      // the records past the listed ones are "no pod" until something is appended there
-      KT_HIP(e, hipMemsetAsync(e->d_vc_meta.p + e->n_countable, 0, (size_t)(headroom + 1) * 8, s));
-      KT_HIP(e, hipMemsetAsync(e->d_countable.p + e->n_countable, 0, (size_t)(headroom + 1) * 8, s));
-      if (!e->view_check_dirty) KT_HIP(e, hipMemsetAsync(e->d_view_dirty.p, 0, 4, s));
-      kt::launch_build_scan_view(e->pods, (int64_t)e->n_countable, e->d_countable.p, e->d_vc_meta.p, e->d_vc_latom.p,
-                                 e->pack.nw ? nullptr : e->d_vc_req.p, s, e->pack.nw ? &e->pack : nullptr, e->d_vc_pk.p, e->d_pos_c.p);
-      KT_HIP(e, hipGetLastError());
-    }
-    e->countable_valid = true;
+    if (!e->sw[kSw_NO_SCAN_VIEW] && (rc = copy_view_records(e, cv, spec, headroom, s)) != KT_OK) return rc;
+    cv.valid = true;
   }
   if (words && e->clean_partial != (const void*)e->partial()) KT_HIP(e, hipMemsetAsync(e->partial(), 0, words * 8, s));
   e->clean_partial = nullptr;
@@ -316,7 +271,7 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
     const bool defer = allow_fused && !e->incremental && !e->wide && e->dindex.n_chunks == 1 && !e->sw[kSw_NO_FUSED];
     auto after_scan = [&]() {  // the slab reduction is its own kernel: time it as its own family
       tl.stop_now();
-      if (!(defer && e->pack.nw)) tr.reset(new TimedLaunch(e, KT_KERNEL_REDUCE, s));
+      if (!(defer && cv.pack.nw)) tr.reset(new TimedLaunch(e, KT_KERNEL_REDUCE, s));
     };
     // wide sums: two scans, the low 32-bit limb of every request into the first block, the rest into the second
     const int n_pass = e->wide ? 2 : 1;
@@ -328,26 +283,26 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
         e->last_kernel[KT_KERNEL_AGGREGATE] = "kt_aggregate_dense";
       } else {
         kt::AggScan sc;
-        sc.n = (int64_t)e->n_countable, sc.rows = e->d_countable.p, sc.counts = e->incremental, sc.nonneg = !e->neg_seen;
+        sc.n = (int64_t)cv.n, sc.rows = cv.rows.p, sc.counts = e->incremental, sc.nonneg = !e->neg_seen;
         sc.overflow_pods = e->n_overflow != 0;
         sc.small_window = e->sw[kSw_AGG_SMALL_WINDOW];
         sc.limb = limb;
         // contiguous tile ranges over the scan view; with a single chunk the order of the list does not matter
-        sc.by_ns = !e->sw[kSw_NO_SCAN_VIEW] && (e->countable_by_ns || e->dindex.n_chunks == 1);
+        sc.by_ns = !e->sw[kSw_NO_SCAN_VIEW] && (cv.by_ns || e->dindex.n_chunks == 1);
         // (records appended behind the listed ones by pod events exist in the VIEW only: a scan that gathers through the
         //  row list — KT_NO_NS_ORDER on a multi-chunk index — must not run over the list's zeroed padding = pod row 0)
-        if (sc.by_ns) sc.n += e->view_extra;
-        if (sc.by_ns) sc.v_meta = e->d_vc_meta.p, sc.v_latom = e->d_vc_latom.p, sc.v_req = e->pack.nw ? nullptr : e->d_vc_req.p;
-        if (sc.by_ns && e->pack.nw) sc.pk = &e->pack, sc.v_pk = e->d_vc_pk.p;
-        if (sc.by_ns && e->countable_by_ns && e->range_c_G) sc.wg_range = e->d_range_c.p, sc.wg_range_G = e->range_c_G;
+        if (sc.by_ns) sc.n += cv.extra;
+        if (sc.by_ns) sc.v_meta = cv.meta.p, sc.v_latom = cv.latom.p, sc.v_req = cv.pack.nw ? nullptr : cv.req.p;
+        if (sc.by_ns && cv.pack.nw) sc.pk = &cv.pack, sc.v_pk = cv.pk.p;
+        if (sc.by_ns && cv.by_ns && cv.range_G) sc.wg_range = cv.range.p, sc.wg_range_G = cv.range_G;
         if ((rc = slab_tags(e, sc, s)) != KT_OK) return rc;
         sc.defer_reduce = defer && sc.pk != nullptr;
         const char* k = kt::launch_aggregate_indexed(e->pods, sc, e->sp, e->d_sp.p, e->dindex, target, e->d_slab.p, s,
                                                      pass == 0 ? std::function<void()>(after_scan) : std::function<void()>());
         if (!k) return e->fail(KT_ERR_UNSUPPORTED, "a chunk of the selector index exceeds the aggregate kernel's LDS budget (use kernel_variant 1)");
         e->last_kernel[KT_KERNEL_AGGREGATE] = k;
-        e->ctr_packed_words.store(sc.launched_packed ? (int64_t)e->pack.nw : 0, std::memory_order_relaxed);
-        if (sc.defer_reduce && sc.launched_packed) e->fused_pending = true, e->fused_nb = sc.launched_blocks, e->fused_epoch = sc.epoch, e->fused_pack = e->pack;
+        e->ctr_packed_words.store(sc.launched_packed ? (int64_t)cv.pack.nw : 0, std::memory_order_relaxed);
+        if (sc.defer_reduce && sc.launched_packed) e->fused_pending = true, e->fused_nb = sc.launched_blocks, e->fused_epoch = sc.epoch, e->fused_pack = cv.pack;
         e->last_kernel[KT_KERNEL_REDUCE] = e->fused_pending ? "(in kt_reduce_finalize_packed)" : sc.launched_packed ? "kt_reduce_packed_slabs" : "kt_reduce_bitmap_slabs";
       }
     }

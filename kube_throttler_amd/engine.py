@@ -44,6 +44,7 @@ EXPORTS = [
 ]
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
+COUNTER_VIEW_BUILDS = 10
 
 
 def partial_layout(n_dims: int) -> dict:
@@ -424,6 +425,10 @@ class Engine:
     def packed_words(self) -> int:
         """64-bit words per pod of the packed fold the last full aggregate scan ran with (0: the plain fold)."""
         return int(lib().kt_counter(self._h, COUNTER_PACKED_WORDS))
+
+    def view_builds(self) -> int:
+        """Scan view builds so far (either view); pod events that fit the views are patched in and do not count."""
+        return int(lib().kt_counter(self._h, COUNTER_VIEW_BUILDS))
 
     def partial_words(self) -> int:
         return self.throttle_rows() * partial_layout(self.D)["stride"]

@@ -594,7 +594,8 @@ def test_pod_events_between_sweeps(budget, dims, oracle_mod, monkeypatch):
     """The scan lists and scan-ordered record copies (namespace order with a multi-chunk index) are rebuilt after pod
     events: adds, updates that move pods to other namespaces / labels / requests, deletes and a throttle change between
     full sweeps of a NON-incremental engine — every reconcile + check equals the oracle on the pods currently held.
-    (16 dimensions: the view records carry eight packed words — kt_patch_scan_views and the rebuilds with that stride.)"""
+    (16 dimensions: the view records carry eight packed words — kt_patch_scan_views and the rebuilds with that stride.)
+    KT_COUNTER_VIEW_BUILDS after every sweep pins which rounds rebuilt a view and which were patched in place."""
     if budget:
         monkeypatch.setenv("KT_CHUNK_BUDGET", str(budget))
     base = W.generate(W.small(seed=73, n_pods=2600, n_thr=96, n_cluster=48, D=dims))
@@ -636,7 +637,9 @@ def test_pod_events_between_sweeps(budget, dims, oracle_mod, monkeypatch):
             # the stored status is the engine's: keep base's copy in step for the next round's oracle
             base.thr_used, base.thr_calc = snap.thr_used, snap.thr_calc
             base.thr_flags, base.thr_thrl_flag, base.thr_thrl_has = snap.thr_flags, snap.thr_thrl_flag, snap.thr_thrl_has
+            view_builds.append(eng.view_builds() - sum(view_builds))
 
+        view_builds = []
         sweep()
         if dims > 8:
             assert eng.packed_words() > 4, eng.packed_words()
@@ -645,7 +648,7 @@ def test_pod_events_between_sweeps(budget, dims, oracle_mod, monkeypatch):
         eng.upsert_pods(_permute_pods(base, state[add_rows]), rows=add_rows)
         sweep()
         upd_rows = rng.choice(2100, 500, replace=False)
-        state[upd_rows] = rng.integers(2100, 2600, 500)      # other namespaces, labels, requests, phases
+        state[upd_rows] = rng.integers(2100, 2599, 500)      # other namespaces, labels, requests, phases (pod 2599 comes later)
         eng.upsert_pods(_permute_pods(base, state[upd_rows]), rows=upd_rows)
         sweep()
         del_rows = rng.choice(2000, 400, replace=False).astype(np.int64)
@@ -676,8 +679,23 @@ def test_pod_events_between_sweeps(budget, dims, oracle_mod, monkeypatch):
         base.thr_flags[r0] &= 0xFFFFFFFF ^ S.THR_RESPONSIBLE              # program recompile: atoms re-translated, views rebuilt
         eng.upsert_throttles(base.throttle_batch([r0]), rows=np.array([r0], dtype=np.int32))
         sweep()
+        print("view builds per sweep:", (budget, dims), view_builds)
+        assert view_builds == _VIEW_BUILDS_BETWEEN_SWEEPS[budget, dims]
     finally:
         eng.close()
+
+
+# test_pod_events_between_sweeps: scan view builds (KT_COUNTER_VIEW_BUILDS) per sweep, by (budget, dims).  The sweeps follow: the
+# first feed, 600 adds, 500 updates, 400 deletes, five rounds of 12 single-pod events, pod 2599, one more pod, a throttle
+# event that leaves the selectors alone, a recompile.
+# Recorded on an MI355X.  One chunk: only the countable view exists; every round of single-pod events is patched in (0), pod
+# 2599 rebuilds (1).  Several chunks: both views, rebuilt together (2); the deletes and the throttle event leave them standing.
+_VIEW_BUILDS_BETWEEN_SWEEPS = {
+    (None, 8): [1, 1, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 1],
+    (5000, 8): [2, 2, 2, 0, 2, 2, 2, 2, 2, 2, 2, 0, 2],
+    (None, 16): [1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1],
+    (9000, 16): [2, 2, 2, 0, 2, 2, 2, 2, 2, 2, 2, 0, 2],
+}
 
 
 def _permute_pods(snap, rows):
