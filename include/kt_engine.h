@@ -319,6 +319,35 @@ int32_t kt_admit_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_
 int32_t kt_admit_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
                               int32_t on_equal, uint32_t flags, void* stream);
 int32_t kt_admit_gangs_fetch(kt_engine* e, int64_t n_gangs, uint8_t* out_admitted);
+/* ---- headroom: how many copies of a pod the throttles still admit — what a Deployment, Job or autoscaler asks before it
+ *      creates pods.  headroom(pod, cap, on_equal) is the number of LEADING Success verdicts kt_admit_launch returns, as a dry
+ *      run (no KT_ADMIT_COMMIT), for the queue [pod] * cap against the stored status and the current reserved amounts:
+ *      PreFilter (plugin.go:148-215) and, on Success, Reserve (plugin.go:217-239 -> [Cluster]ThrottleController.Reserve,
+ *      throttle_controller.go:271-300 -> reservedResourceAmounts.addPod, reserved_resource_amounts.go:66-77), copy after copy —
+ *      every copy adds ResourceAmountOfPod(pod) once to every throttle that affects the pod, and the next copy's
+ *      CheckThrottledFor sees it in steps 3 and 4 (throttle_types.go:142-150).  out_copies[i] lies in [0, cap].
+ *      out_limiting[i] is the lowest throttle row whose status is not KT_STATUS_NOT_THROTTLED in the row PreFilter returns
+ *      for the first copy that is NOT admitted; -1 when all cap copies are admitted.  A pod whose PreFilter is an Error
+ *      (selector / namespace error, plugin.go:154-168) and an invalid pod row report 0 copies and -1; a pod no throttle
+ *      affects reports cap and -1.  The copies are FURTHER pods of the same shape: a pod whose own amount is already part of
+ *      the reserved totals is answered as the totals stand.
+ *      The number has a closed form per (pod, throttle, resource name) — the minimum over the affecting throttles, and there
+ *      over the pod count and every requested name, of the copies that amount alone lets through — so nothing is walked in
+ *      sequence: one kt_check launch with the status matrix (which throttles affect which pod) and one launch of kt_headroom
+ *      (csrc/kt_kernels_headroom.hip), one wave per pod.  The call never changes reserved amounts, stored status or a pending
+ *      reconcile.
+ *      pod_rows == NULL: rows [0, n); n == 0 is KT_OK and launches nothing.  cap outside [1, KT_HEADROOM_MAX_CAP] is
+ *      KT_ERR_INVALID_ARGUMENT; n x throttle_rows > 2^31 (the status matrix) KT_ERR_OUT_OF_RANGE; a stored `used` wider than
+ *      int64 KT_ERR_UNSUPPORTED, as for kt_admit_launch.
+ *      kt_headroom_fetch synchronises (out_limiting nullable); KT_ERR_NOT_READY without a pending kt_headroom_launch.  The
+ *      launch uses the engine's ONE check slot: a kt_check_launch that was pending is dropped (as with kt_affected_pods), and
+ *      a later kt_check_launch / kt_check / kt_sweep_launch / kt_admit_launch / kt_admit_gangs_launch / kt_paged_admit* /
+ *      kt_affected_pods on the engine drops a pending kt_headroom_launch.  The one exception is a kt_check that the few-pod
+ *      path serves (at most 8 named pods, no status matrix: KT_COUNTER_FEW_CHECKS): it runs beside the slot on buffers of its
+ *      own, and a pending kt_headroom_launch, like a pending kt_check_launch, stays fetchable behind it. ------------------ */
+#define KT_HEADROOM_MAX_CAP 0x7FFFFFFF
+int32_t kt_headroom_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, int64_t cap, void* stream);
+int32_t kt_headroom_fetch(kt_engine* e, int64_t n, int64_t* out_copies, int32_t* out_limiting /* nullable */);
 /* Current reserved amounts of n throttle rows (after kt_set_reserved / kt_admit_launch(KT_ADMIT_COMMIT)). */
 int32_t kt_fetch_reserved(kt_engine* e, int32_t n, const int32_t* throttle_rows, const kt_amounts* out);
 int32_t kt_throttle_rows(kt_engine* e, int32_t* out_rows);
@@ -409,6 +438,13 @@ int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
 int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
                              const int64_t* gang_off, int32_t on_equal, uint32_t flags, uint64_t* out_summary, uint8_t* out_status,
                              uint8_t* out_gang_admitted);
+/* kt_headroom_launch over the pages, synchronous (n_pages == 1 is kt_headroom_launch + kt_headroom_fetch): the copies of
+ * pod_rows[i] that every page's names and the pod count (page 0) still admit — the name part is the minimum over the pages —
+ * and the limiting throttle row.  One kt_check of page 0 and ONE kt_headroom launch over every page's tables on page 0's stream.
+ * Refusals, locking (every page exclusively, in address order) and ordering are kt_paged_admit's; cap as for
+ * kt_headroom_launch.  Uses page 0's check slot.  out_copies [n] and out_limiting [n] are both nullable. */
+int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal,
+                          int64_t cap, int64_t* out_copies, int32_t* out_limiting);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

@@ -369,6 +369,27 @@ func (e *Engine) AdmitGangs(rows []int64, gangOff []int64, onEqual, commit bool)
 	return summary[:len(rows)], status[:len(rows)*T], admitted, nil
 }
 
+// Headroom answers, for every pod row of rows, how many copies of that pod the throttles still admit (kt_headroom_launch +
+// kt_headroom_fetch): the number of leading Success verdicts a dry-run Admit of cap copies of the pod would return against the
+// stored status and the current reserved amounts, in [0, cap], and the lowest throttle row that blocks the next copy (-1: all
+// cap copies fit, or the pod's PreFilter is an error — then copies is 0).  Nothing is reserved.  cap in [1, 2^31-1].  The call
+// takes the engine's one check slot, like Admit.
+func (e *Engine) Headroom(rows []int64, onEqual bool, cap int64) (copies []int64, limiting []int32, err error) {
+	if len(rows) == 0 {
+		return nil, nil, nil
+	}
+	if rc := C.kt_headroom_launch(e.h, C.int64_t(len(rows)), i64(rows), b2i(onEqual), C.int64_t(cap), nil); rc != C.KT_OK {
+		return nil, nil, e.err(rc)
+	}
+	copies = make([]int64, len(rows))
+	limiting = make([]int32, len(rows))
+	if rc := C.kt_headroom_fetch(e.h, C.int64_t(len(rows)), (*C.int64_t)(unsafe.Pointer(&copies[0])),
+		(*C.int32_t)(unsafe.Pointer(&limiting[0]))); rc != C.KT_OK {
+		return nil, nil, e.err(rc)
+	}
+	return copies, limiting, nil
+}
+
 // PagedAdmit is Admit over the pages of a cluster with more than 16 resource names (kt_paged_admit): one engine per page of
 // <= 16 names, pages[0] first; verdicts and status rows are combined over the pages, and with commit every page keeps its
 // reserved amounts.  The same duplicate-pod rule as Admit: a pod already reserved, or twice in rows, must not be in the queue.

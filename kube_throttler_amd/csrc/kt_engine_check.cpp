@@ -29,6 +29,7 @@ static int32_t ensure_check_recs(kt_engine* e, int32_t on_equal, int DT, hipStre
 // allow_small: false for callers that go on working on the device-side rows / summaries (kt_admit_launch)
 static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
                                    hipStream_t s, bool allow_small = true) {
+  e->headroom_ready = false;  // the one check slot is taken: a pending kt_headroom_launch is gone
   if (pod_rows) {
     for (int64_t i = 0; i < n; ++i)
       if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity)
@@ -185,6 +186,7 @@ int32_t kt_sweep_launch(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t fl
   e->last_kernel[KT_KERNEL_AGGREGATE] = "(in kt_sweep_bitmap)";
   e->last_kernel[KT_KERNEL_REDUCE] = "(in kt_reduce_finalize_packed)";
   e->check_n = n, e->check_in_h_small = false, e->check_T = e->thr_rows_hi, e->check_has_status = false, e->check_ready = true;
+  e->headroom_ready = false;
   e->fused_pending = true, e->fused_nb = launched, e->fused_epoch = sc.epoch, e->fused_pack = plan;
   e->agg_pending = true, e->agg_words = words, e->agg_gen = e->program_gen;
   e->last_stream = s;
@@ -527,31 +529,29 @@ int32_t kt_paged_check(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
   return KT_OK;
 }
 
-// kt_admit_launch / kt_admit_gangs_launch (n_gangs >= 0) over several engines, synchronous: what is specific to more than one engine,
-// then admit_locked
-static int32_t paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
-                           uint64_t* out_summary, uint8_t* out_status, int64_t n_gangs, const int64_t* gang_off, uint8_t* out_gang_admitted) {
+// What the calls over several page engines share (kt_paged_admit, kt_paged_admit_gangs, kt_paged_headroom; `what` words the errors).
+// paged_lock: every page exclusively, in address order — two paged calls over overlapping pages cannot deadlock
+typedef std::vector<std::unique_ptr<LaunchLock>> PageLocks;
+static int32_t paged_lock(const char* what, kt_engine* const* pages, int32_t n_pages, int64_t n, PageLocks& locks) {
   if (!pages || n_pages < 1 || n < 0) return KT_ERR_INVALID_ARGUMENT;
   for (int32_t k = 0; k < n_pages; ++k) {
     if (!pages[k]) return KT_ERR_INVALID_ARGUMENT;
     for (int32_t j = 0; j < k; ++j)
-      if (pages[j] == pages[k]) return pages[k]->fail(KT_ERR_INVALID_ARGUMENT, "paged admit: the engine of page %d is also page %d", k, j);
+      if (pages[j] == pages[k]) return pages[k]->fail(KT_ERR_INVALID_ARGUMENT, "%s: the engine of page %d is also page %d", what, k, j);
   }
-  // every page exclusively, in address order: two paged calls over overlapping pages cannot deadlock
   std::vector<kt_engine*> by_addr(pages, pages + n_pages);
   std::sort(by_addr.begin(), by_addr.end(), std::less<kt_engine*>());
-  std::vector<std::unique_ptr<LaunchLock>> locks;
   for (kt_engine* e : by_addr) locks.emplace_back(new LaunchLock(e, /*force_exclusive=*/true));
+  return KT_OK;
+}
+// paged_same_cluster: every page holds every throttle row and every pod row of the queue, on one device
+static int32_t paged_same_cluster(const char* what, kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows) {
   kt_engine* e0 = pages[0];
   const int32_t T = e0->thr_rows_hi;
-  if (n_gangs >= 0) {
-    const int32_t rcg = gangs_valid(e0, n, n_gangs, gang_off);
-    if (rcg != KT_OK) return rcg;
-  }
   for (int32_t k = 0; k < n_pages; ++k) {
     kt_engine* e = pages[k];
     if (e->thr_rows_hi != T) return e->fail(KT_ERR_INVALID_ARGUMENT, "page %d holds %d throttle rows, page 0 %d: every page holds every throttle", k, e->thr_rows_hi, T);
-    if (e->device != e0->device) return e->fail(KT_ERR_UNSUPPORTED, "paged admit: page %d is on device %d, page 0 on %d", k, e->device, e0->device);
+    if (e->device != e0->device) return e->fail(KT_ERR_UNSUPPORTED, "%s: page %d is on device %d, page 0 on %d", what, k, e->device, e0->device);
     if (pod_rows) {
       for (int64_t i = 0; i < n; ++i)
         if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "page %d: pod row %lld", k, (long long)pod_rows[i]);
@@ -559,21 +559,44 @@ static int32_t paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, 
       return e->fail(KT_ERR_OUT_OF_RANGE, "page %d: n=%lld > pod_capacity", k, (long long)n);
     }
   }
-  if (n == 0) return KT_OK;
+  return KT_OK;
+}
+// paged_order: the kernel reads every page's tables on page 0's stream *s.  Uploads of host-side status / reserved rows
+// (ensure_ready) and earlier launches of page k ran on page k's streams: they are SYNCHRONISED here (the calls are synchronous
+// anyway); the newest feed kernel of page k is ordered before the launch on the device (order_behind_ingest).
+static int32_t paged_order(kt_engine* const* pages, int32_t n_pages, hipStream_t* s) {
+  kt_engine* e0 = pages[0];
   KT_HIP(e0, hipSetDevice(e0->device));
-  hipStream_t s = pick_stream(e0, nullptr);
-  // Ordering: the kernel reads every page's tables on page 0's stream.  Uploads of host-side status / reserved rows (ensure_ready)
-  // and earlier launches of page k ran on page k's streams: they are SYNCHRONISED here (the call is synchronous anyway); the
-  // newest feed kernel of page k is ordered before the launch on the device (order_behind_ingest).
+  *s = pick_stream(e0, nullptr);
   for (int32_t k = 1; k < n_pages; ++k) {
     kt_engine* e = pages[k];
     int32_t rc = ensure_ready(e, e->own_stream);
     if (rc != KT_OK) return rc;
     KT_HIP(e, hipStreamSynchronize(e->own_stream));
     if (e->last_stream && e->last_stream != e->own_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
-    order_behind_ingest(e, s);
+    order_behind_ingest(e, *s);
   }
-  int32_t rc = admit_locked(pages, n_pages, n, pod_rows, on_equal, flags, s, n_gangs, gang_off);
+  return KT_OK;
+}
+
+// kt_admit_launch / kt_admit_gangs_launch (n_gangs >= 0) over several engines, synchronous: what is specific to more than one engine,
+// then admit_locked
+static int32_t paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
+                           uint64_t* out_summary, uint8_t* out_status, int64_t n_gangs, const int64_t* gang_off, uint8_t* out_gang_admitted) {
+  PageLocks locks;
+  int32_t rc = paged_lock("paged admit", pages, n_pages, n, locks);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = pages[0];
+  const int32_t T = e0->thr_rows_hi;
+  if (n_gangs >= 0) {
+    const int32_t rcg = gangs_valid(e0, n, n_gangs, gang_off);
+    if (rcg != KT_OK) return rcg;
+  }
+  if ((rc = paged_same_cluster("paged admit", pages, n_pages, n, pod_rows)) != KT_OK) return rc;
+  if (n == 0) return KT_OK;
+  hipStream_t s = nullptr;
+  if ((rc = paged_order(pages, n_pages, &s)) != KT_OK) return rc;
+  rc = admit_locked(pages, n_pages, n, pod_rows, on_equal, flags, s, n_gangs, gang_off);
   e0->check_ready = false;  // the call used page 0's check slot (as kt_affected_pods): a pending kt_check_launch is gone
   if (rc != KT_OK) return rc;
   if (out_summary) KT_HIP(e0, hipMemcpyAsync(out_summary, e0->d_summary.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
@@ -596,6 +619,100 @@ int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n
                              int32_t on_equal, uint32_t flags, uint64_t* out_summary, uint8_t* out_status, uint8_t* out_gang_admitted) {
   if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
   return paged_admit(pages, n_pages, n, pod_rows, on_equal, flags, out_summary, out_status, n_gangs, gang_off, out_gang_admitted);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// headroom: how many copies of a pod the throttles still admit (kt_kernels_headroom.hip)
+// ---------------------------------------------------------------------------------------------------
+// Over n_pages >= 1 page engines (one page: the engine itself) on page 0's stream s: one status-matrix check of page 0 (who
+// affects whom), then one kt_headroom launch over the page descriptors kt_admit reads.  The caller holds every page's launch lock
+// and has set the device; the results stay on the device behind page 0 (kt_headroom_fetch).  Nothing of any page is changed.
+static int32_t headroom_locked(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, int64_t cap,
+                               hipStream_t s) {
+  kt_engine* e0 = pages[0];
+  const int32_t T = e0->thr_rows_hi;
+  e0->headroom_ready = false;
+  for (int32_t k = 0; k < n_pages; ++k)
+    if (pages[k]->wide)
+      return pages[k]->fail(KT_ERR_UNSUPPORTED, "headroom: the stored `used` of page %d is wider than int64 (kt_headroom reads int64 tables)", k);
+  if ((double)n * (double)T > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "headroom: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  if (n == 0) {  // nothing is launched
+    e0->headroom_ready = true, e0->headroom_n = 0;
+    return KT_OK;
+  }
+  if (e0->d_headroom_copies.cap < (size_t)n || e0->d_headroom_limiting.cap < (size_t)n) {
+    // a launch that was never fetched may still be writing the old buffers, on the stream it was given: that is last_stream
+    // until the check below replaces it (admit_locked does the same before it reallocates)
+    if (e0->last_stream) KT_HIP(e0, hipStreamSynchronize(e0->last_stream));
+    KT_HIP(e0, e0->d_headroom_copies.reserve((size_t)n));
+    KT_HIP(e0, e0->d_headroom_limiting.reserve((size_t)n));
+  }
+  int32_t rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e0->check_ready = false;  // the slot holds this call's rows (as with kt_affected_pods): a pending kt_check_launch is gone
+  if (rc != KT_OK) return rc;
+  if (!e0->admit_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->admit_pages_ev, hipEventDisableTiming));
+  KT_HIP(e0, hipEventSynchronize(e0->admit_pages_ev));  // the previous launch's copy has read h_admit_pages
+  e0->h_admit_pages.resize((size_t)n_pages);
+  for (int32_t k = 0; k < n_pages; ++k) {
+    const kt_engine* e = pages[k];
+    e0->h_admit_pages[(size_t)k] = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  }
+  KT_HIP(e0, e0->d_admit_pages.reserve(sizeof(kt::AdmitPage) * (size_t)n_pages));
+  hipError_t herr = hipSuccess;
+  if (!kt::launch_headroom(e0->h_admit_pages.data(), n_pages, (kt::AdmitPage*)e0->d_admit_pages.p, e0->admit_pages_ev, n,
+                           pod_rows ? e0->d_rows.p : nullptr, T, on_equal != 0, (uint32_t)cap, e0->d_status.p, e0->d_summary.p,
+                           e0->d_headroom_copies.p, e0->d_headroom_limiting.p, s, &herr))
+    return e0->fail(KT_ERR_DEVICE, "headroom: copy of the page descriptors: %s", hipGetErrorString(herr));
+  KT_HIP(e0, hipGetLastError());
+  e0->headroom_ready = true, e0->headroom_n = n;
+  return KT_OK;
+}
+
+static inline bool headroom_cap_ok(int64_t cap) { return cap >= 1 && cap <= (int64_t)KT_HEADROOM_MAX_CAP; }
+
+int32_t kt_headroom_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, int64_t cap, void* stream) {
+  if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  if (!headroom_cap_ok(cap)) return e->fail(KT_ERR_INVALID_ARGUMENT, "headroom: cap = %lld, not in [1, %d]", (long long)cap, KT_HEADROOM_MAX_CAP);
+  KT_HIP(e, hipSetDevice(e->device));
+  return headroom_locked(&e, 1, n, pod_rows, on_equal, cap, pick_stream(e, stream));
+}
+
+// the results of the last headroom launch, under the launch lock; both outputs nullable
+static int32_t headroom_fetch_locked(kt_engine* e, int64_t n, int64_t* out_copies, int32_t* out_limiting) {
+  if (!e->headroom_ready) return e->fail(KT_ERR_NOT_READY, "kt_headroom_fetch before kt_headroom_launch");
+  if (n < 0 || n > e->headroom_n) return e->fail(KT_ERR_OUT_OF_RANGE, "n=%lld, the last headroom launch had %lld pods", (long long)n, (long long)e->headroom_n);
+  if (n == 0) return KT_OK;
+  hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
+  if (out_copies) KT_HIP(e, hipMemcpyAsync(out_copies, e->d_headroom_copies.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (out_limiting) KT_HIP(e, hipMemcpyAsync(out_limiting, e->d_headroom_limiting.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
+int32_t kt_headroom_fetch(kt_engine* e, int64_t n, int64_t* out_copies, int32_t* out_limiting) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  return headroom_fetch_locked(e, n, out_copies, out_limiting);
+}
+
+int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, int64_t cap,
+                          int64_t* out_copies, int32_t* out_limiting) {
+  PageLocks locks;
+  int32_t rc = paged_lock("paged headroom", pages, n_pages, n, locks);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = pages[0];
+  if (!headroom_cap_ok(cap)) return e0->fail(KT_ERR_INVALID_ARGUMENT, "headroom: cap = %lld, not in [1, %d]", (long long)cap, KT_HEADROOM_MAX_CAP);
+  if ((rc = paged_same_cluster("paged headroom", pages, n_pages, n, pod_rows)) != KT_OK) return rc;
+  if (n == 0) return KT_OK;
+  hipStream_t s = nullptr;
+  if ((rc = paged_order(pages, n_pages, &s)) != KT_OK) return rc;
+  if ((rc = headroom_locked(pages, n_pages, n, pod_rows, on_equal, cap, s)) != KT_OK) return rc;
+  rc = headroom_fetch_locked(e0, n, out_copies, out_limiting);  // (synchronises s)
+  e0->headroom_ready = false;  // the results have been handed out
+  return rc;
 }
 
 int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now_s, int32_t now_ns, uint32_t flags, int32_t n,

@@ -330,6 +330,11 @@ struct kt_engine {
   std::vector<int64_t> h_gang_off;
   bool gang_ready = false, gang_on_device = false;  // on_device false: no throttle rows, the bytes follow from the summaries
   int64_t gang_n = 0;
+  // the last kt_headroom_launch (on page 0): copies and limiting throttle row per pod, on the device until kt_headroom_fetch
+  DevBuf<int64_t> d_headroom_copies;
+  DevBuf<int32_t> d_headroom_limiting;
+  bool headroom_ready = false;
+  int64_t headroom_n = 0;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;

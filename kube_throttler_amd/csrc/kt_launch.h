@@ -107,6 +107,12 @@ size_t admit_gang_extra_bytes(int T, int n_pages);
 bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
                   bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global, hipStream_t s,
                   hipError_t* hip_err, const AdmitGangs* gangs = nullptr);
+// how many copies of each pod the throttles still admit (kt_kernels_headroom.hip): one wave per pod over the same page descriptors
+// (the state offsets are not used: nothing is mutable), copied and guarded by pages_copied as launch_admit does.  status / summary:
+// page 0's check of the same rows; copies [n], limiting [n] out; cap in [1, 2^31 - 1].  false: *hip_err says why
+bool launch_headroom(const AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
+                     bool on_equal, uint32_t cap, const uint8_t* status, const uint64_t* summary, int64_t* copies, int32_t* limiting,
+                     hipStream_t s, hipError_t* hip_err);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

@@ -41,7 +41,9 @@ EXPORTS = [
     "kt_comm_allreduce_partial", "kt_comm_destroy", "kt_reconcile_rows_launch", "kt_set_exchange_world", "kt_counter", "kt_reconcile_fetch_used_hi",
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
+    "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom",
 ]
+HEADROOM_MAX_CAP = 0x7FFFFFFF
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
 COUNTER_VIEW_BUILDS = 10
@@ -117,6 +119,22 @@ def paged_admit_gangs(engines, rows, gang_off, on_equal=False, commit=False):
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_admit_gangs: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return status[:n, :T], summary[:n], admitted[:ng]
+
+
+def paged_headroom(engines, rows, cap, on_equal=False):
+    """kt_paged_headroom: how many copies of each pod of ``rows`` the throttles still admit over the page engines — the leading
+    Success verdicts of a dry-run admission of ``[pod] * cap`` — -> (copies int64 [n] in [0, cap], limiting throttle row
+    int32 [n], -1 when all ``cap`` copies are admitted)."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    rows_a = np.ascontiguousarray(rows, dtype=np.int64)
+    n = len(rows_a)
+    copies = np.zeros(max(n, 1), np.int64)
+    limiting = np.zeros(max(n, 1), np.int32)
+    rc = lib().kt_paged_headroom(hs, len(engines), n, rows_a.ctypes.data if n else None, int(on_equal), int(cap),
+                                 copies.ctypes.data, limiting.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_headroom: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return copies[:n], limiting[:n]
 
 
 def paged_reconcile(engines, now, apply=True):
@@ -226,6 +244,10 @@ def lib():
         L.kt_admit_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.kt_paged_admit_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kt_headroom_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
+        L.kt_headroom_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.kt_paged_headroom.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                        C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -539,6 +561,25 @@ class Engine:
         admitted = np.zeros(max(n_gangs, 1), np.uint8)
         self._ck(lib().kt_admit_gangs_fetch(self._h, n_gangs, admitted.ctypes.data))
         return admitted[:n_gangs]
+
+    # ---- headroom: how many copies of a pod the throttles still admit
+    def headroom_launch(self, n, rows=None, cap=1, on_equal=False, stream=None):
+        a, p = self._rows(rows, np.int64)
+        self._ck(lib().kt_headroom_launch(self._h, n, p, int(on_equal), int(cap), stream))
+
+    def headroom_fetch(self, n, want_limiting=True):
+        copies = np.zeros(max(n, 1), np.int64)
+        limiting = np.zeros(max(n, 1), np.int32) if want_limiting else None
+        self._ck(lib().kt_headroom_fetch(self._h, n, copies.ctypes.data, None if limiting is None else limiting.ctypes.data))
+        return copies[:n], (None if limiting is None else limiting[:n])
+
+    def headroom(self, rows=None, n=None, *, cap, on_equal=False):
+        """kt_headroom_launch + kt_headroom_fetch: per pod the number of leading Success verdicts a dry-run admission of
+        ``[pod] * cap`` returns, and the lowest throttle row that stops the next copy (-1: all ``cap`` are admitted) ->
+        (copies int64 [n], limiting int32 [n]).  Reserved amounts and stored status are left as they are."""
+        n = len(rows) if rows is not None else n
+        self.headroom_launch(n, rows, cap, on_equal)
+        return self.headroom_fetch(n)
 
     def fetch_reserved(self, rows=None) -> S.Amounts:
         rows = np.arange(self.throttle_rows(), dtype=np.int32) if rows is None else rows

@@ -1211,6 +1211,30 @@ std::vector<Status> KubeThrottler::AdmitQueue(const std::vector<std::string>& po
   return out;
 }
 
+// How many further pods of this pod's shape PreFilter + Reserve would admit in a row, and the throttle that stops the next one:
+// kt_paged_headroom over the mirror's pages (the closed form of a dry-run kt_paged_admit of [pod] * cap).  The reserved totals
+// are read as they stand — a reservation the pod itself already holds counts like any other — and nothing is changed.
+HeadroomResult KubeThrottler::Headroom(const std::string& pod_key, int64_t cap) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  HeadroomResult out;
+  const int64_t row = p.pod_rows.find(pod_key);
+  if (row < 0) {
+    out.error = "pod " + pod_key + " is not known to the plugin (OnPodAdd first)";
+    return out;
+  }
+  int64_t copies = 0;
+  int32_t limiting = -1;
+  const int32_t rc = kt_paged_headroom(p.pages.data(), (int32_t)p.pages.size(), 1, &row, /*isThrottledOnEqual=*/0, cap, &copies, &limiting);
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    return out;
+  }
+  out.copies = copies;
+  if (limiting >= 0 && (size_t)limiting < p.thr_by_row.size() && p.thr_live[(size_t)limiting]) out.limiting = p.thr_by_row[(size_t)limiting].Key();
+  return out;
+}
+
 // A scheduling pass over a queue of GANGS (jobs whose pods only run together), in order: every member gets PreFilter and, on
 // Success, Reserve; a gang with a member that did not succeed gets Unreserve for all its members (plugin.go:240-257) before the next
 // gang is looked at — ONE engine launch per segment (kt_paged_admit_gangs) instead of up to 3 x n calls.  Segments end on gang

@@ -150,6 +150,14 @@ struct GangAdmission {
   std::vector<uint8_t> admitted;
 };
 
+// Headroom: how many further pods of a pod's shape the throttles still admit, and the throttle that stops the next one
+struct HeadroomResult {
+  int64_t copies = 0;     // in [0, cap]
+  std::string limiting;   // Throttle::Key() of the lowest-row throttle that blocks copy number `copies`; empty: none (all cap fit,
+                          // or the pod's PreFilter is an Error)
+  std::string error;      // not empty: the call failed (unknown pod, engine error) and copies is 0
+};
+
 // KubeThrottlerPluginArgs (pkg/scheduler_plugin/plugin_args.go:33-40) + engine sizing
 struct PluginArgs {
   std::string name;                 // throttler name (required)
@@ -197,6 +205,13 @@ class KubeThrottler {
   // that did not succeed gets Unreserve for every member before the next gang — one engine launch per segment
   // (kt_paged_admit_gangs).  Only members of admitted gangs are in the reservation map afterwards (Unreserve works pod by pod)
   GangAdmission AdmitGangs(const std::vector<std::vector<std::string>>& gangs);
+
+  // ---- how many replicas fit: the number of pods of pod_key's shape (same namespace, labels and requests) that PreFilter +
+  // Reserve would admit one after the other right now, at most cap (1 .. KT_HEADROOM_MAX_CAP), and the throttle that stops the
+  // next one — ONE engine call (kt_paged_headroom over the mirror's pages) instead of a dry-run queue of cap pods.  Nothing is
+  // reserved.  The copies are FURTHER pods: a pod whose own amount is already part of the reserved totals (Reserve was called for
+  // it) is answered as the totals stand, its reservation counts against the copies like anybody else's.
+  HeadroomResult Headroom(const std::string& pod_key, int64_t cap);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

@@ -94,6 +94,143 @@ def status_manifest(pages, results, i, now_text: str, previous: dict | None = No
     return st
 
 
+# ---- headroom: how many copies of a pod the throttles still admit (kt_paged_headroom), restated over the pages' snapshots
+def _pool_arrays(pool):
+    return pool.arrays() if hasattr(pool, "arrays") else (pool.op, pool.key, pool.val_off, pool.val)
+
+
+def _selector_matches(pool, r0, r1, keys, pairs) -> bool:
+    """labels.Requirement.Matches over requirements [r0, r1) of a pool (the conjunction; an empty selector matches)."""
+    op, key, val_off, val = _pool_arrays(pool)
+    for r in range(r0, r1):
+        has = int(key[r]) in keys
+        hit = has and any(int(v) in pairs for v in val[int(val_off[r]):int(val_off[r + 1])])
+        o = int(op[r])
+        if not {S.OP_IN: hit, S.OP_NOT_IN: not hit, S.OP_EXISTS: has, S.OP_DOES_NOT_EXIST: not has}.get(o, False):
+            return False
+    return True
+
+
+def affected_throttles(snap, p):
+    """(error, ascending throttle rows) — the throttles PreFilter evaluates for pod row ``p``: affectedThrottles
+    (throttle_controller.go:248-269), then affectedClusterThrottles (clusterthrottle_controller.go:272-298: the namespace
+    object must exist); a selector that does not convert, reached before a term matched, is an error (plugin.go:154-168)."""
+    ns = int(snap.pod_ns[p])
+    l0, l1 = int(snap.pod_label_off[p]), int(snap.pod_label_off[p + 1])
+    keys = {int(k) for k in snap.pod_label_key[l0:l1]}
+    pairs = {int(k) for k in snap.pod_label_pair[l0:l1]}
+    need = S.THR_VALID | S.THR_RESPONSIBLE
+    ns_ok = ns < snap.n_ns and bool(snap.ns_valid[ns])
+    if ns_ok:
+        n0, n1 = int(snap.ns_label_off[ns]), int(snap.ns_label_off[ns + 1])
+        ns_keys = {int(k) for k in snap.ns_label_key[n0:n1]}
+        ns_pairs = {int(k) for k in snap.ns_label_pair[n0:n1]}
+    out = []
+    for cluster in (False, True):
+        if cluster and not ns_ok:
+            return True, []
+        for t in range(snap.n_thr):
+            f = int(snap.thr_flags[t])
+            if (f & need) != need or bool(f & S.THR_CLUSTER) != cluster or (not cluster and int(snap.thr_ns[t]) != ns):
+                continue
+            for g in range(int(snap.thr_term_off[t]), int(snap.thr_term_off[t + 1])):
+                tf = int(snap.term_flags[g])
+                if cluster and ((tf & S.TERM_NS_SEL_INVALID) or not _selector_matches(
+                        snap.nreq, int(snap.term_nreq_off[g]), int(snap.term_nreq_off[g + 1]), ns_keys, ns_pairs)):
+                    continue  # (the namespace side swallows a conversion error: clusterthrottle_selector.go:63-69)
+                if tf & S.TERM_POD_SEL_INVALID:
+                    return True, []
+                if _selector_matches(snap.preq, int(snap.term_preq_off[g]), int(snap.term_preq_off[g + 1]), keys, pairs):
+                    out.append(t)
+                    break
+    return False, sorted(out)
+
+
+def pod_requests(snap, p):
+    """ResourceAmountOfPod's requests of pod row ``p`` over the snapshot's names (resourcelist.go:27-46): max(init containers)
+    against sum(containers), plus overhead -> {dim: value}; a name is present when any of them names it."""
+    init, run = {}, {}
+    for c in range(int(snap.pod_ctr_off[p]), int(snap.pod_ctr_off[p + 1])):
+        for d in range(snap.D):
+            if int(snap.ctr_present[c]) >> d & 1:
+                v = int(snap.ctr_req[c, d])
+                if snap.ctr_init[c]:
+                    init[d] = max(init[d], v) if d in init else v
+                else:
+                    run[d] = run.get(d, 0) + v
+    for d, v in init.items():
+        run[d] = max(run[d], v) if d in run else v
+    if int(snap.pod_ovh_present[p]) >> 31:
+        for d in range(snap.D):
+            if int(snap.pod_ovh_present[p]) >> d & 1:
+                run[d] = run.get(d, 0) + int(snap.pod_ovh[p, d])
+    return run
+
+
+def _copies_of_amount(v, brings, th_has, tv, uv, rv, present0, flagged, eq3, eq, cap) -> int:
+    """The leading copies of a run of identical pods that ONE amount of one throttle lets through (a resource name with
+    request ``v``, or the pod count with ``v`` = 1): copy j is checked against used + reserved + j * v by the four steps of
+    CheckThrottledFor (throttle_types.go:128-153), and from copy 1 on the amount is present because the pod brought it in."""
+    va = v if brings else 0
+
+    def passes(j):
+        if flagged:  # step 2
+            return False
+        if not th_has:
+            return True
+        if v > tv:  # step 1
+            return False
+        s = uv + rv + j * va
+        if (present0 or (j > 0 and brings)) and (s >= tv if eq3 else s > tv):  # step 3
+            return False
+        return not (s + v >= tv if eq else s + v > tv)  # step 4
+
+    if not passes(0):
+        return 0
+    if not th_has or va <= 0:  # the sums do not grow: copies 1.. fare as copy 1 does, or better
+        return cap if passes(1) else 1
+    # the sums grow: step 4 of a copy implies its step 3, the copies that pass are those with s + (j + 1) v < (<=) tv
+    return max(0, min(cap, (tv - uv - rv - (1 if eq else 0)) // v))
+
+
+def headroom_of(pages, pod_row, cap, on_equal=False):
+    """kt_paged_headroom for one pod, in closed form over the page bundles' snapshots (no GPU): the number of leading
+    Success verdicts a dry-run admission of ``[pod] * cap`` returns — the minimum over the affecting throttles, and there over
+    the pod count and every requested resource name of every page, of the copies that amount alone lets through — and the
+    lowest throttle row that stops the next copy (-1 when all ``cap`` are admitted) -> (copies, limiting)."""
+    snap0 = pages[0].snapshot
+    p = int(pod_row)
+    if not (0 <= p < snap0.n_pods) or not int(snap0.pod_flags[p]) & S.POD_VALID:
+        return 0, -1
+    err, affected = affected_throttles(snap0, p)
+    if err:
+        return 0, -1
+    eq = bool(on_equal)
+    reqs = [pod_requests(b.snapshot, p) for b in pages]
+    best, limiting = cap, -1
+    for t in affected:
+        f = int(snap0.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        th = snap0.thr_calc if f & S.THR_CALC_AT_NONZERO else snap0.thr_spec
+        u_hc, r_hc = bool(snap0.thr_used.has_count[t]), bool(snap0.thr_reserved.has_count[t])
+        h = _copies_of_amount(1, True, bool(th.has_count[t]), int(th.count[t]), int(snap0.thr_used.count[t]) if u_hc else 0,
+                              int(snap0.thr_reserved.count[t]) if r_hc else 0, u_hc or r_hc, bool(f & S.THR_THROTTLED_POD), eq3, eq, cap)
+        for b, req in zip(pages, reqs):
+            s = b.snapshot
+            th = s.thr_calc if int(s.thr_flags[t]) & S.THR_CALC_AT_NONZERO else s.thr_spec
+            for d, v in req.items():
+                if v == 0:
+                    continue  # a name the pod does not request (rq.IsZero(), resource_amount.go:46-65)
+                bit = lambda w: bool(int(w) >> d & 1)
+                u_p, r_p = bit(s.thr_used.present[t]), bit(s.thr_reserved.present[t])
+                h = min(h, _copies_of_amount(v, True, bit(th.present[t]), int(th.v[t, d]), int(s.thr_used.v[t, d]) if u_p else 0,
+                                             int(s.thr_reserved.v[t, d]) if r_p else 0, u_p or r_p,
+                                             bit(int(s.thr_thrl_flag[t]) & int(s.thr_thrl_has[t])), eq3, eq, cap))
+        if h < best:
+            best, limiting = h, t
+    return best, limiting
+
+
 class PagedEngine:
     """One HIP engine per page of a ``ClusterState.build_pages()`` result; reconcile and check run on every page (the
     selector scan is repeated per page: the price of more than 16 resource names) and come back combined."""
@@ -146,6 +283,12 @@ class PagedEngine:
         ok = v != S.VERDICT_ERROR  # (an error row keeps page 0's precomputed status row; its summary word says error)
         assert (verdicts(status)[ok] == v[ok]).all(), "kt_paged_admit_gangs: summary words disagree with the combined status rows"
         return status, v, admitted
+
+    def headroom(self, rows, cap, on_equal=False):
+        """How many copies of each pod of ``rows`` the throttles still admit, through kt_paged_headroom: the leading Success
+        verdicts of a dry-run admission of ``[pod] * cap`` with every page's names -> (copies [n], limiting throttle row [n],
+        -1 when all ``cap`` are admitted).  Nothing is reserved."""
+        return E.paged_headroom(self.engines, rows, cap, on_equal=on_equal)
 
     def fetch_reserved(self) -> list:
         """Reserved amounts per throttle row, put together by resource NAME from the pages (like combine_reconcile):
