@@ -348,6 +348,53 @@ int32_t kt_admit_gangs_fetch(kt_engine* e, int64_t n_gangs, uint8_t* out_admitte
 #define KT_HEADROOM_MAX_CAP 0x7FFFFFFF
 int32_t kt_headroom_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, int64_t cap, void* stream);
 int32_t kt_headroom_fetch(kt_engine* e, int64_t n, int64_t* out_copies, int32_t* out_limiting /* nullable */);
+/* ---- preempt: the shortest victim prefix that lets a blocked pod through — what priority preemption asks, and what the
+ *      scheduler's own preemption never asks of throttles (PreFilter answers UnschedulableAndUnresolvable).
+ *      A pod is COUNTED when VALID & SCHED_MATCH & SCHEDULED & !FINISHED (throttle_controller.go:217-219).  For preemptor
+ *      p = pod_rows[i] and the caller-ordered candidates c_0 .. c_{m-1} = cand_rows (typically by ascending priority; the engine
+ *      has no priority field and needs none), state S_k is the cluster in which c_0 .. c_{k-1} no longer exist and every
+ *      responsible throttle has been reconciled at `now`: affectedPods -> used = fold ResourceAmount.Add, CalculateThreshold(now),
+ *      throttled = IsThrottled(used, true) (throttle_controller.go:116-133, throttle_types.go:65-106, resource_amount.go:127-159).
+ *      Reserved amounts are unchanged; a throttle whose reconcile reports an error keeps its stored status in every S_k, as
+ *      kt_reconcile_fetch's `error` byte defines.
+ *      out_prefix[i] is the smallest k in [0, m_eff] for which PreFilter(p) (plugin.go:148-215) in S_k is Success: 0 = p already
+ *      passes against a fresh reconcile; KT_PREEMPT_NONE = no prefix helps (pod-requests-exceeds-threshold, candidates exhausted,
+ *      a p whose PreFilter is an Error, an invalid pod row).  m_eff: the list is CUT before the first candidate whose own check
+ *      row is an Error or whose row is invalid — deleting such a pod could change a throttle's reconcile error, which this query
+ *      does not model.  Candidates that are not counted, or that no throttle affecting p matches, contribute nothing; they may
+ *      be in the list and are never in the victim mask.
+ *      out_victims[i][j] (nullable, [n][n_cand]) is 1 iff j < out_prefix[i], c_j is counted and at least one throttle that affects
+ *      p matches c_j: deleting exactly the masked pods gives p the same verdict as deleting the whole prefix (no assumption
+ *      about the signs of requests).  Row i is all zero when out_prefix[i] <= 0.
+ *      Presence is exact (resource_amount.go:91-110,151-155): a resource name stays present in `used` only while a remaining
+ *      counted pod carries it — decided by exact contributor counts, not by stored presence bits — and the pod count of `used`
+ *      is present only while a pod is counted.  Every k is evaluated (no bisection): one kt_check launch with the status matrix
+ *      over pod_rows ++ cand_rows, an aggregate and a dry finalize at `now` of the call's own, and one launch of kt_preempt
+ *      (csrc/kt_kernels_preempt.hip), one wave per preemptor, lane = candidate position.  The aggregate is the dense scan (its
+ *      partial rows count every contributor; the indexed scan of a rescanning engine only marks names as seen): its cost grows
+ *      with pods x throttles.
+ *      The call is a dry run: stored status and reserved amounts are not changed.
+ *      Refused before anything is launched: n_cand < 0, a preemptor that is also a candidate, a candidate named twice, a missing
+ *      row array (KT_ERR_INVALID_ARGUMENT); n x throttle_rows, n_cand x throttle_rows or their sum — the bytes of the one check's
+ *      matrix — > 2^31 (KT_ERR_OUT_OF_RANGE); `used` wider than int64, a KT_VARIANT_INCREMENTAL engine, an exchange world above 1
+ *      (KT_ERR_UNSUPPORTED).  Where pod batches since the last aggregate leave it unknown whether `used` still fits int64, the one
+ *      thing that runs before the refusal is the kernel that sums the |requests|; the check slot, the reconcile report and the
+ *      result buffers are untouched by a refused call.  n == 0 is KT_OK and launches
+ *      nothing; n_cand == 0 answers 0 or KT_PREEMPT_NONE per pod.  kt_preempt_fetch synchronises; KT_ERR_NOT_READY without a
+ *      pending kt_preempt_launch.
+ *      Slots: the launch uses the engine's ONE check slot exactly as kt_headroom_launch does — a pending kt_check_launch or
+ *      kt_headroom_launch is dropped, and a later kt_check_launch / kt_check (other than the few-pod path) / kt_sweep_launch /
+ *      kt_admit* / kt_headroom_launch / kt_affected_pods drops a pending kt_preempt_launch.  Its dry finalize writes the reconcile
+ *      result buffers: the report of a pending kt_reconcile_launch / kt_finalize_launch is dropped (kt_reconcile_fetch answers
+ *      KT_ERR_NOT_READY; a status stored with KT_RECONCILE_APPLY stays stored).  Its aggregate runs beside the partial buffer:
+ *      a pending kt_aggregate_launch keeps its sums.  The results live in buffers of their own, so a kt_reconcile_launch issued
+ *      on the same stream after the launch leaves it fetchable.
+ *      Out of scope: the paged form (more than KT_MAX_DIMS resource names), a "reprieve" pass that shrinks the victim set
+ *      further, several ranks. ------------------------------------------------------------------------------------------ */
+#define KT_PREEMPT_NONE (-1)
+int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
+                          int32_t now_ns, int32_t on_equal, void* stream);
+int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* out_victims /* [n][n_cand], nullable */);
 /* Current reserved amounts of n throttle rows (after kt_set_reserved / kt_admit_launch(KT_ADMIT_COMMIT)). */
 int32_t kt_fetch_reserved(kt_engine* e, int32_t n, const int32_t* throttle_rows, const kt_amounts* out);
 int32_t kt_throttle_rows(kt_engine* e, int32_t* out_rows);

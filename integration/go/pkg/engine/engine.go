@@ -22,6 +22,7 @@ import "C"
 
 import (
 	"fmt"
+	"sync"
 	"time"
 	"unsafe"
 )
@@ -43,6 +44,7 @@ const (
 type Engine struct {
 	h    *C.kt_engine
 	dims int
+	mu   sync.Mutex // the engine's ONE check slot: every method that takes it (Check, AffectedPods, Admit, AdmitGangs, Headroom, Preempt) holds mu from its launch to its fetch; Verdict's one-pod check runs beside the slot and takes no lock
 }
 
 // New creates an engine for `dims` resource names (<= 16), pods with up to maxLabels labels and the given row capacities.
@@ -290,6 +292,8 @@ func (e *Engine) ThrottleRows() int {
 // (throttle_controller.go:349-397, clusterthrottle_controller.go:378-425) for one or many pods: status[i*T+t] is the
 // CheckThrottleStatus code of (pod i, throttle row t).  kt_check = launch + fetch under ONE engine lock.
 func (e *Engine) Check(podRows []int64, onEqual bool) (summary []uint64, status []uint8, err error) {
+	e.mu.Lock() // the check slot is one per engine: see mu
+	defer e.mu.Unlock()
 	if len(podRows) == 0 {
 		return nil, nil, nil
 	}
@@ -306,6 +310,8 @@ func (e *Engine) Check(podRows []int64, onEqual bool) (summary []uint64, status 
 // AffectedPods answers "does throttle j's selector match pod i as held now" (affectedPods restricted to the named rows:
 // throttle_controller.go:221-246) — what unreserveAffectedPods iterates over behind a reconcile.
 func (e *Engine) AffectedPods(podRows []int64, throttleRows []int32) ([]uint8, error) {
+	e.mu.Lock() // the check slot is one per engine: see mu
+	defer e.mu.Unlock()
 	out := make([]uint8, len(podRows)*len(throttleRows)+1)
 	if rc := C.kt_affected_pods(e.h, C.int64_t(len(podRows)), i64(podRows), C.int32_t(len(throttleRows)), i32(throttleRows), u8(out)); rc != C.KT_OK {
 		return nil, e.err(rc)
@@ -315,6 +321,8 @@ func (e *Engine) AffectedPods(podRows []int64, throttleRows []int32) ([]uint8, e
 
 // Admit runs PreFilter + Reserve for rows[i] IN ORDER in one launch (plugin.go:148-239); a dry run unless commit.
 func (e *Engine) Admit(rows []int64, onEqual, commit bool) (summary []uint64, status []uint8, err error) {
+	e.mu.Lock() // the check slot is one per engine: see mu
+	defer e.mu.Unlock()
 	var flags C.uint32_t
 	if commit {
 		flags = C.KT_ADMIT_COMMIT
@@ -336,6 +344,8 @@ func (e *Engine) Admit(rows []int64, onEqual, commit bool) (summary []uint64, st
 // reserved gets Unreserve (plugin.go:240-257) before the next gang starts.  summary / status are what PreFilter answered at each
 // pod's turn (also in a rolled-back gang), admitted[g] says whether gang g stays reserved.  The duplicate-pod rule of Admit holds.
 func (e *Engine) AdmitGangs(rows []int64, gangOff []int64, onEqual, commit bool) (summary []uint64, status []uint8, admitted []bool, err error) {
+	e.mu.Lock() // the check slot is one per engine: see mu
+	defer e.mu.Unlock()
 	// the slices are indexed below: never take &s[0] of an empty one, and refuse offsets the library would refuse anyway
 	if len(gangOff) == 0 {
 		return nil, nil, nil, fmt.Errorf("AdmitGangs: gangOff needs at least the closing offset (len(gangs)+1 entries)")
@@ -375,6 +385,8 @@ func (e *Engine) AdmitGangs(rows []int64, gangOff []int64, onEqual, commit bool)
 // cap copies fit, or the pod's PreFilter is an error — then copies is 0).  Nothing is reserved.  cap in [1, 2^31-1].  The call
 // takes the engine's one check slot, like Admit.
 func (e *Engine) Headroom(rows []int64, onEqual bool, cap int64) (copies []int64, limiting []int32, err error) {
+	e.mu.Lock() // the check slot is one per engine: see mu
+	defer e.mu.Unlock()
 	if len(rows) == 0 {
 		return nil, nil, nil
 	}
@@ -388,6 +400,31 @@ func (e *Engine) Headroom(rows []int64, onEqual bool, cap int64) (copies []int64
 		return nil, nil, e.err(rc)
 	}
 	return copies, limiting, nil
+}
+
+// Preempt answers, for every blocked pod row of rows, the shortest prefix of the caller-ordered candidate list cands (typically
+// ascending priority) whose deletion, followed by a reconcile of every throttle at now, makes PreFilter Success
+// (kt_preempt_launch + kt_preempt_fetch): prefix[i] in [0, len(cands)], 0 = the pod already passes against a fresh reconcile,
+// -1 = no prefix helps; victims[i*len(cands)+j] = 1 for the counted candidates below the prefix that a throttle affecting the pod
+// matches.  A dry run: nothing is deleted, stored status and reserved amounts stay.  Launch and fetch run under e.mu, which every other user of
+// the check slot (Check, AffectedPods, Admit, AdmitGangs, Headroom) takes as well: no goroutine drops another's pending launch.  Not compiled in this repository (no Go toolchain in its build).
+func (e *Engine) Preempt(rows, cands []int64, nowS int64, nowNs int32, onEqual bool) (prefix []int64, victims []uint8, err error) {
+	if len(rows) == 0 {
+		return nil, nil, nil
+	}
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	if rc := C.kt_preempt_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(len(cands)), i64(cands), C.int64_t(nowS),
+		C.int32_t(nowNs), b2i(onEqual), nil); rc != C.KT_OK {
+		return nil, nil, e.err(rc)
+	}
+	prefix = make([]int64, len(rows))
+	victims = make([]uint8, len(rows)*len(cands)+1)
+	if rc := C.kt_preempt_fetch(e.h, C.int64_t(len(rows)), (*C.int64_t)(unsafe.Pointer(&prefix[0])),
+		(*C.uint8_t)(unsafe.Pointer(&victims[0]))); rc != C.KT_OK {
+		return nil, nil, e.err(rc)
+	}
+	return prefix, victims[:len(rows)*len(cands)], nil
 }
 
 // PagedAdmit is Admit over the pages of a cluster with more than 16 resource names (kt_paged_admit): one engine per page of

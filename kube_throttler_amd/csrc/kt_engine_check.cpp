@@ -30,6 +30,7 @@ static int32_t ensure_check_recs(kt_engine* e, int32_t on_equal, int DT, hipStre
 static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
                                    hipStream_t s, bool allow_small = true) {
   e->headroom_ready = false;  // the one check slot is taken: a pending kt_headroom_launch is gone
+  e->preempt_ready = false;   // ... and a pending kt_preempt_launch
   if (pod_rows) {
     for (int64_t i = 0; i < n; ++i)
       if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity)
@@ -186,7 +187,7 @@ int32_t kt_sweep_launch(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t fl
   e->last_kernel[KT_KERNEL_AGGREGATE] = "(in kt_sweep_bitmap)";
   e->last_kernel[KT_KERNEL_REDUCE] = "(in kt_reduce_finalize_packed)";
   e->check_n = n, e->check_in_h_small = false, e->check_T = e->thr_rows_hi, e->check_has_status = false, e->check_ready = true;
-  e->headroom_ready = false;
+  e->headroom_ready = false, e->preempt_ready = false;
   e->fused_pending = true, e->fused_nb = launched, e->fused_epoch = sc.epoch, e->fused_pack = plan;
   e->agg_pending = true, e->agg_words = words, e->agg_gen = e->program_gen;
   e->last_stream = s;
@@ -713,6 +714,89 @@ int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, c
   rc = headroom_fetch_locked(e0, n, out_copies, out_limiting);  // (synchronises s)
   e0->headroom_ready = false;  // the results have been handed out
   return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// preempt: the shortest victim prefix that lets a blocked pod through (kt_kernels_preempt.hip)
+// ---------------------------------------------------------------------------------------------------
+int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
+                          int32_t now_ns, int32_t on_equal, void* stream) {
+  if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  if (n_cand < 0) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt: n_cand = %lld", (long long)n_cand);
+  if ((n > 0 && !pod_rows) || (n_cand > 0 && !cand_rows)) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt: pod_rows / cand_rows missing");
+  for (int64_t i = 0; i < n + n_cand; ++i) {
+    const int64_t r = i < n ? pod_rows[i] : cand_rows[i - n];
+    if (r < 0 || r >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "preempt: pod row %lld", (long long)r);
+  }
+  {
+    std::vector<int64_t> sorted(cand_rows, cand_rows + n_cand);
+    std::sort(sorted.begin(), sorted.end());
+    for (int64_t j = 1; j < n_cand; ++j)
+      if (sorted[(size_t)j] == sorted[(size_t)j - 1])
+        return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt: pod row %lld is a candidate twice", (long long)sorted[(size_t)j]);
+    for (int64_t i = 0; i < n; ++i)
+      if (std::binary_search(sorted.begin(), sorted.end(), pod_rows[i]))
+        return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt: pod row %lld is a preemptor and a candidate", (long long)pod_rows[i]);
+  }
+  const int32_t T = e->thr_rows_hi;  // (moved by throttle batches only, under this lock: ensure_ready below does not change it)
+  // the issue's two products, and their sum: the one matrix this call launches holds (n + n_cand) x throttle_rows bytes
+  if ((double)n * (double)T > 2147483648.0 || (double)n_cand * (double)T > 2147483648.0 || ((double)n + (double)n_cand) * (double)T > 2147483648.0)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "preempt: (n + n_cand) x throttle_rows = (%lld + %lld) x %d exceeds 2^31 matrix bytes", (long long)n,
+                   (long long)n_cand, T);
+  if (e->incremental) return e->fail(KT_ERR_UNSUPPORTED, "preempt: not for KT_VARIANT_INCREMENTAL engines");
+  if (e->exchange_world > 1) return e->fail(KT_ERR_UNSUPPORTED, "preempt: the engine exchanges partials with %d ranks (one rank only)", e->exchange_world);
+  if (e->wide && e->req_sums_valid) return e->fail(KT_ERR_UNSUPPORTED, "preempt: `used` is wider than int64 (kt_preempt reads int64 sums)");
+  e->preempt_ready = false;
+  if (n == 0) {  // nothing is launched
+    e->preempt_ready = true, e->preempt_n = 0, e->preempt_m = n_cand;
+    return KT_OK;
+  }
+  KT_HIP(e, hipSetDevice(e->device));
+  hipStream_t s = pick_stream(e, stream);
+  // pod batches since the last aggregate may have pushed the sums beyond int64: found out here (the |request| sums kernel, when
+  // they are not known), before the check slot or any result buffer is touched
+  int32_t rc = ensure_ready(e, s);
+  if (rc == KT_OK) rc = request_sums_in_range(e, s);
+  if (rc != KT_OK) return rc;
+  if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "preempt: `used` is wider than int64 (kt_preempt reads int64 sums)");
+  const size_t vic = (size_t)n * (size_t)n_cand;
+  if (e->d_preempt_prefix.cap < (size_t)n || e->d_preempt_victims.cap < vic + 1) {
+    // a launch that was never fetched may still be writing the old buffers, on the stream it was given (as kt_headroom_launch)
+    if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+    KT_HIP(e, e->d_preempt_prefix.reserve((size_t)n));
+    KT_HIP(e, e->d_preempt_victims.reserve(vic + 1));
+  }
+  // ONE check over preemptors ++ candidates: which throttles match which pod, and the error rows
+  std::vector<int64_t> rows((size_t)(n + n_cand));
+  std::copy(pod_rows, pod_rows + n, rows.begin());
+  std::copy(cand_rows, cand_rows + n_cand, rows.begin() + n);
+  rc = check_launch_locked(e, n + n_cand, rows.data(), on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e->check_ready = false;  // the slot holds this call's rows (as with kt_affected_pods): a pending kt_check_launch is gone
+  if (rc != KT_OK) return rc;
+  if ((rc = preempt_reconcile_locked(e, now_s, now_ns, s)) != KT_OK) return rc;
+  const kt::AdmitPage pg{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  kt::launch_preempt(pg, n, n_cand, e->d_rows.p, e->thr_rows_hi, on_equal != 0, e->d_status.p, e->d_summary.p, e->d_preempt_partial.p,
+                     e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p, e->d_preempt_victims.p, s);
+  KT_HIP(e, hipGetLastError());
+  e->last_stream = s;
+  e->preempt_ready = true, e->preempt_n = n, e->preempt_m = n_cand;
+  return KT_OK;
+}
+
+int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* out_victims) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (!e->preempt_ready) return e->fail(KT_ERR_NOT_READY, "kt_preempt_fetch before kt_preempt_launch");
+  if (n < 0 || n > e->preempt_n) return e->fail(KT_ERR_OUT_OF_RANGE, "n=%lld, the last preempt launch had %lld pods", (long long)n, (long long)e->preempt_n);
+  if (n == 0) return KT_OK;
+  hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
+  if (out_prefix) KT_HIP(e, hipMemcpyAsync(out_prefix, e->d_preempt_prefix.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (out_victims && e->preempt_m)
+    KT_HIP(e, hipMemcpyAsync(out_victims, e->d_preempt_victims.p, (size_t)n * (size_t)e->preempt_m, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
 }
 
 int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now_s, int32_t now_ns, uint32_t flags, int32_t n,

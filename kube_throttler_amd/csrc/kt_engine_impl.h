@@ -335,6 +335,13 @@ struct kt_engine {
   DevBuf<int32_t> d_headroom_limiting;
   bool headroom_ready = false;
   int64_t headroom_n = 0;
+  // the last kt_preempt_launch: prefix per preemptor and the victim bytes [n][n_cand], on the device until kt_preempt_fetch;
+  // d_preempt_partial: the partial rows of its own aggregate (exact contributor counts), never the engine's partial buffer
+  DevBuf<int64_t> d_preempt_prefix;
+  DevBuf<uint8_t> d_preempt_victims;
+  DevBuf<unsigned long long> d_preempt_partial;
+  bool preempt_ready = false;
+  int64_t preempt_n = 0, preempt_m = 0;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;
@@ -604,6 +611,7 @@ KT_INTERNAL int32_t settle_view_patches(kt_engine* e, hipStream_t s);
 // (kt_engine_reconcile.cpp)
 KT_INTERNAL int32_t slab_tags(kt_engine* e, kt::AggScan& sc, hipStream_t s);
 KT_INTERNAL int32_t request_sums_in_range(kt_engine* e, hipStream_t s);
+KT_INTERNAL int32_t preempt_reconcile_locked(kt_engine* e, int64_t now_s, int32_t now_ns, hipStream_t s);
 KT_INTERNAL int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused = false);
 KT_INTERNAL int32_t delta_scan(kt_engine* e, int64_t n, const int64_t* rows_dev, int64_t row0, int sign, hipStream_t s);
 KT_INTERNAL int32_t finalize_locked(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t flags, hipStream_t s, bool consume = false,

@@ -402,6 +402,35 @@ int32_t finalize_locked(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t fl
   return KT_OK;
 }
 
+// The reconcile half of kt_preempt_launch: an aggregate of its own and a dry finalize at `now`, both beside the engine's partial
+// buffer (a pending kt_aggregate_launch keeps its sums).  kt_preempt needs EXACT per-name contributor counts — a name stays
+// present in `used` only while a remaining counted pod carries it — and the indexed scan of a rescanning engine only marks a
+// name as seen (presence masks per slab, zero-key marks of the packed fold; exact counts are the incremental engines' record
+// layout, which the index chunks are not cut for).  So this aggregate is the dense scan, which adds 1 per contributor: every
+// counted pod walks every throttle's terms, as the reference does.  The finalize writes the reconcile result buffers: a pending
+// kt_reconcile_launch's report is gone afterwards.
+int32_t preempt_reconcile_locked(kt_engine* e, int64_t now_s, int32_t now_ns, hipStream_t s) {
+  int32_t rc = request_sums_in_range(e, s);
+  if (rc != KT_OK) return rc;
+  if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "preempt: `used` is wider than int64 (kt_preempt reads int64 sums)");
+  const size_t words = (size_t)e->thr_rows_hi * kt::partial_stride(e->D);
+  if (e->d_preempt_partial.cap < words + 1) {
+    if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // an unfetched launch may still read the old buffer
+    KT_HIP(e, e->d_preempt_partial.reserve(words + 1));
+  }
+  e->reconcile_ready = false;
+  if (!words) return KT_OK;
+  KT_HIP(e, hipMemsetAsync(e->d_preempt_partial.p, 0, words * 8, s));
+  kt::launch_aggregate_dense(e->pods, e->pod_rows_hi, e->sp, e->uses_keys, e->d_preempt_partial.p, s, /*limb=*/0);
+  kt::ReconcileOut out{e->d_out_used.tab(), e->d_out_calc.tab(), e->d_out_used_hi.p, e->d_out_calc_updated.p, e->d_out_thrl_flag.p,
+                       e->d_out_thrl_has.p, e->d_out_thrl_pod.p, e->d_out_error.p, e->d_out_next_s.p, e->d_out_next_ns.p};
+  kt::launch_finalize(e->tt, e->sp, e->D, e->d_preempt_partial.p, /*consume=*/false, now_s, now_ns, /*apply=*/false, out, nullptr, 0, false,
+                      req_bound(e), s);
+  KT_HIP(e, hipGetLastError());
+  e->last_stream = s;
+  return KT_OK;
+}
+
 int32_t kt_aggregate_launch(kt_engine* e, void* stream) {
   if (!e) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);

@@ -113,6 +113,12 @@ bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_
 bool launch_headroom(const AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
                      bool on_equal, uint32_t cap, const uint8_t* status, const uint64_t* summary, int64_t* copies, int32_t* limiting,
                      hipStream_t s, hipError_t* hip_err);
+// the shortest victim prefix per preemptor (kt_kernels_preempt.hip): one wave per preemptor.  rows_dev [n + m]: the preemptors,
+// then the candidates; status / summary: ONE check over those rows; partial: aggregate rows with exact per-name contributor counts;
+// calc / calc_updated / error: a dry finalize at `now`; prefix [n] and victims [n][m] out
+void launch_preempt(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int T, bool on_equal, const uint8_t* status,
+                    const uint64_t* summary, const unsigned long long* partial, const AmountTab& calc, const uint8_t* calc_updated,
+                    const uint8_t* error, int64_t* prefix, uint8_t* victims, hipStream_t s);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

@@ -41,9 +41,10 @@ EXPORTS = [
     "kt_comm_allreduce_partial", "kt_comm_destroy", "kt_reconcile_rows_launch", "kt_set_exchange_world", "kt_counter", "kt_reconcile_fetch_used_hi",
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
-    "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom",
+    "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
+PREEMPT_NONE = -1
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
 COUNTER_VIEW_BUILDS = 10
@@ -248,6 +249,9 @@ def lib():
         L.kt_headroom_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.kt_paged_headroom.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                         C.c_void_p]
+        L.kt_preempt_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_void_p]
+        L.kt_preempt_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -580,6 +584,28 @@ class Engine:
         n = len(rows) if rows is not None else n
         self.headroom_launch(n, rows, cap, on_equal)
         return self.headroom_fetch(n)
+
+    # ---- preempt: the shortest victim prefix that lets a blocked pod through
+    def preempt_launch(self, pod_rows, cand_rows, now, on_equal=False, stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        c, q = self._rows(cand_rows, np.int64)
+        self._ck(lib().kt_preempt_launch(self._h, len(a), p if len(a) else None, len(c), q if len(c) else None, int(now[0]), int(now[1]),
+                                         int(on_equal), stream))
+
+    def preempt_fetch(self, n, n_cand, want_victims=True):
+        prefix = np.zeros(max(n, 1), np.int64)
+        flat = np.zeros(max(n * n_cand, 1), np.uint8) if want_victims else None
+        self._ck(lib().kt_preempt_fetch(self._h, n, prefix.ctypes.data, None if flat is None else flat.ctypes.data))
+        return prefix[:n], (None if flat is None else flat[:n * n_cand].reshape(n, n_cand))
+
+    def preempt(self, pod_rows, cand_rows, now, on_equal=False, want_victims=True):
+        """kt_preempt_launch + kt_preempt_fetch: per preemptor the smallest k for which the pod passes PreFilter once the
+        candidates ``cand_rows[:k]`` are gone and every throttle has been reconciled at ``now`` (0: it already passes against a
+        fresh reconcile, PREEMPT_NONE: no prefix helps), and the victim bytes [n][n_cand] — 1 for the counted candidates below
+        the prefix that a throttle affecting the pod matches -> (prefix int64 [n], victims uint8 [n][n_cand] or None).  A dry
+        run: stored status and reserved amounts stay as they are."""
+        self.preempt_launch(pod_rows, cand_rows, now, on_equal)
+        return self.preempt_fetch(len(pod_rows), len(cand_rows), want_victims)
 
     def fetch_reserved(self, rows=None) -> S.Amounts:
         rows = np.arange(self.throttle_rows(), dtype=np.int32) if rows is None else rows

@@ -1235,6 +1235,46 @@ HeadroomResult KubeThrottler::Headroom(const std::string& pod_key, int64_t cap) 
   return out;
 }
 
+// Which of the candidates have to go before this pod passes PreFilter: kt_preempt_launch + kt_preempt_fetch on the mirror's one
+// engine (isThrottledOnEqual = false, as PreFilter).  The reserved totals are read as they stand and nothing is changed.
+PreemptResult KubeThrottler::Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys,
+                                     const std::string& now_rfc3339) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  PreemptResult out;
+  if (p.pages.size() > 1) {
+    out.error = "Preempt: the mirror runs on " + std::to_string(p.pages.size()) + " pages (more than " + std::to_string(p.D) +
+                " resource names); the preemption query has no paged form";
+    return out;
+  }
+  int64_t now_s;
+  int32_t now_ns;
+  if (!ParseRFC3339(now_rfc3339, &now_s, &now_ns, &out.error)) return out;
+  const int64_t row = p.pod_rows.find(pod_key);
+  if (row < 0) {
+    out.error = "pod " + pod_key + " is not known to the plugin (OnPodAdd first)";
+    return out;
+  }
+  std::vector<int64_t> cand(candidate_keys.size());
+  for (size_t j = 0; j < cand.size(); ++j)
+    if ((cand[j] = p.pod_rows.find(candidate_keys[j])) < 0) {
+      out.error = "candidate " + candidate_keys[j] + " is not known to the plugin (OnPodAdd first)";
+      return out;
+    }
+  int64_t prefix = KT_PREEMPT_NONE;
+  std::vector<uint8_t> mask(cand.size() + 1);
+  int32_t rc = kt_preempt_launch(p.e, 1, &row, (int64_t)cand.size(), cand.data(), now_s, now_ns, /*isThrottledOnEqual=*/0, nullptr);
+  if (rc == KT_OK) rc = kt_preempt_fetch(p.e, 1, &prefix, mask.data());
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    return out;
+  }
+  out.none = prefix < 0;
+  for (size_t j = 0; j < cand.size(); ++j)
+    if (mask[j]) out.victims.push_back(candidate_keys[j]);
+  return out;
+}
+
 // A scheduling pass over a queue of GANGS (jobs whose pods only run together), in order: every member gets PreFilter and, on
 // Success, Reserve; a gang with a member that did not succeed gets Unreserve for all its members (plugin.go:240-257) before the next
 // gang is looked at — ONE engine launch per segment (kt_paged_admit_gangs) instead of up to 3 x n calls.  Segments end on gang

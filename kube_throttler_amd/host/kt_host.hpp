@@ -158,6 +158,14 @@ struct HeadroomResult {
   std::string error;      // not empty: the call failed (unknown pod, engine error) and copies is 0
 };
 
+// Preempt: the pods that would have to go before a blocked pod passes PreFilter
+struct PreemptResult {
+  bool none = false;                 // no prefix of the candidates lets the pod through (victims is empty)
+  std::vector<std::string> victims;  // Pod::Key() of the candidates to delete, in the caller's order; empty and !none: the pod
+                                     // already passes against a fresh reconcile
+  std::string error;                 // not empty: the call failed (unknown pod, a paged mirror, engine error)
+};
+
 // KubeThrottlerPluginArgs (pkg/scheduler_plugin/plugin_args.go:33-40) + engine sizing
 struct PluginArgs {
   std::string name;                 // throttler name (required)
@@ -212,6 +220,14 @@ class KubeThrottler {
   // reserved.  The copies are FURTHER pods: a pod whose own amount is already part of the reserved totals (Reserve was called for
   // it) is answered as the totals stand, its reservation counts against the copies like anybody else's.
   HeadroomResult Headroom(const std::string& pod_key, int64_t cap);
+
+  // ---- who has to go: the shortest prefix of `candidate_keys` (the caller's order, typically ascending priority) whose deletion,
+  // followed by a reconcile of every throttle at `now` (RFC3339), lets pod_key through PreFilter — ONE engine call
+  // (kt_preempt_launch + kt_preempt_fetch) instead of delete + ReconcileAll + PreFilter per victim tried.  The victims are the
+  // candidates of that prefix that count in a throttle affecting the pod; the others of the prefix may stay.  A dry run: no pod is
+  // deleted, no status and no reservation changes.  A mirror that runs on pages (more than KT_MAX_DIMS resource names) answers an
+  // error: the engine has no paged form of the query.
+  PreemptResult Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys, const std::string& now_rfc3339);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

@@ -231,6 +231,191 @@ def headroom_of(pages, pod_row, cap, on_equal=False):
     return best, limiting
 
 
+# ---- preempt: the shortest victim prefix that lets a blocked pod through (kt_preempt_launch), in closed form on a Snapshot ----
+_COUNTABLE = S.POD_VALID | S.POD_SCHED_MATCH | S.POD_SCHEDULED
+
+
+def _throttle_walk(snap, t, p):
+    """(matched, error) of throttle row ``t``'s selector on pod row ``p``: terms in order, the first match wins, a podSelector
+    that does not convert and is reached before a match is an error (throttle_selector.go:30-54,
+    clusterthrottle_selector.go:44-87)."""
+    f = int(snap.thr_flags[t])
+    need = S.THR_VALID | S.THR_RESPONSIBLE
+    if (f & need) != need:
+        return False, False
+    ns = int(snap.pod_ns[p])
+    cluster = bool(f & S.THR_CLUSTER)
+    if cluster:
+        if not (ns < snap.n_ns and bool(snap.ns_valid[ns])):
+            return False, False
+        n0, n1 = int(snap.ns_label_off[ns]), int(snap.ns_label_off[ns + 1])
+        ns_keys = {int(k) for k in snap.ns_label_key[n0:n1]}
+        ns_pairs = {int(k) for k in snap.ns_label_pair[n0:n1]}
+    elif int(snap.thr_ns[t]) != ns:
+        return False, False
+    l0, l1 = int(snap.pod_label_off[p]), int(snap.pod_label_off[p + 1])
+    keys = {int(k) for k in snap.pod_label_key[l0:l1]}
+    pairs = {int(k) for k in snap.pod_label_pair[l0:l1]}
+    for g in range(int(snap.thr_term_off[t]), int(snap.thr_term_off[t + 1])):
+        tf = int(snap.term_flags[g])
+        if cluster and ((tf & S.TERM_NS_SEL_INVALID) or not _selector_matches(
+                snap.nreq, int(snap.term_nreq_off[g]), int(snap.term_nreq_off[g + 1]), ns_keys, ns_pairs)):
+            continue
+        if tf & S.TERM_POD_SEL_INVALID:
+            return False, True
+        if _selector_matches(snap.preq, int(snap.term_preq_off[g]), int(snap.term_preq_off[g + 1]), keys, pairs):
+            return True, False
+    return False, False
+
+
+def _calculated_threshold(snap, t, now):
+    """CalculateThreshold(now) of throttle row ``t`` (throttle_types.go:65-106): the first active override wins per resource
+    name and for the pod count, and the merged override REPLACES spec.threshold -> ({dim: value}, count or None, parse error)."""
+    now = (int(now[0]), int(now[1]))
+    names, count, active, any_err = {}, None, False, False
+    for o in range(int(snap.thr_ovr_off[t]), int(snap.thr_ovr_off[t + 1])):
+        if int(snap.ovr_flags[o]) & S.OVR_PARSE_ERROR:
+            any_err = True
+            continue
+        begin = (int(snap.ovr_begin_s[o]), int(snap.ovr_begin_ns[o]))
+        end = (int(snap.ovr_end_s[o]), int(snap.ovr_end_ns[o]))
+        if not (begin <= now and (end == (S.ZERO_TIME_S, 0) or now <= end)):
+            continue
+        active = True
+        if count is None and snap.ovr_thr.has_count[o]:
+            count = int(snap.ovr_thr.count[o])
+        for d in range(snap.D):
+            if int(snap.ovr_thr.present[o]) >> d & 1 and d not in names:
+                names[d] = int(snap.ovr_thr.v[o, d])
+    if not active:
+        names = {d: int(snap.thr_spec.v[t, d]) for d in range(snap.D) if int(snap.thr_spec.present[t]) >> d & 1}
+        count = int(snap.thr_spec.count[t]) if snap.thr_spec.has_count[t] else None
+    return names, count, any_err
+
+
+def _amount_dict(tab, t, D):
+    return {d: int(tab.v[t, d]) for d in range(D) if int(tab.present[t]) >> d & 1}, (int(tab.count[t]) if tab.has_count[t] else None)
+
+
+def preempt_context(snap, now):
+    """What every preemptor of one kt_preempt_launch shares: per throttle row the sums of a fresh aggregate (values and
+    contributor counts per name, counted pods), whether its reconcile is an error, and the thresholds a check reads behind the
+    reconcile at ``now``; per pod row the throttles that match it."""
+    D, T = snap.D, snap.n_thr
+    match = {}  # pod row -> [throttle rows whose selector matches it]
+    thr = [dict(val={}, cnt={}, pods=0, error=False) for _ in range(T)]
+    for p in range(snap.n_pods):
+        fl = int(snap.pod_flags[p])
+        if not fl & S.POD_VALID:
+            continue
+        req = pod_requests(snap, p)
+        rows = []
+        for t in range(T):
+            m, err = _throttle_walk(snap, t, p)
+            if (fl & _COUNTABLE) == _COUNTABLE and err:
+                thr[t]["error"] = True
+            if m:
+                rows.append(t)
+                if (fl & _COUNTABLE) == _COUNTABLE and not fl & S.POD_FINISHED:
+                    thr[t]["pods"] += 1
+                    for d, v in req.items():
+                        thr[t]["val"][d] = thr[t]["val"].get(d, 0) + v
+                        thr[t]["cnt"][d] = thr[t]["cnt"].get(d, 0) + 1
+        match[p] = rows
+    for t in range(T):
+        f = int(snap.thr_flags[t])
+        calc, calc_count, any_err = _calculated_threshold(snap, t, now)
+        stored, stored_count = _amount_dict(snap.thr_calc, t, D)
+        fp = int(snap.thr_spec_msgs_fp[t]) if any_err else 0
+        replace = (calc, calc_count) != (stored, stored_count) or int(snap.thr_status_msgs_fp[t]) != fp
+        # threshold := status.calculatedThreshold once calculatedAt is set (the reconcile sets it when it replaces), else spec
+        use_calc = bool(f & S.THR_CALC_AT_NONZERO) or replace
+        thr[t]["calc"], thr[t]["calc_count"] = calc, calc_count
+        thr[t]["th"], thr[t]["th_count"] = (calc, calc_count) if use_calc else _amount_dict(snap.thr_spec, t, D)
+    return dict(match=match, thr=thr)
+
+
+def _amount_fails(vp, th, flagged, u_present, uv, r_present, rv, eq3, eq) -> bool:
+    """One amount of one throttle for the pod (a requested resource name, or the pod count with vp = 1): does one of the four
+    CheckThrottledFor steps (throttle_types.go:128-153) stop it.  ``th`` None: the threshold does not name the amount."""
+    if flagged:  # step 2
+        return True
+    if th is None:
+        return False
+    if vp > th:  # step 1
+        return True
+    s = (uv if u_present else 0) + (rv if r_present else 0)
+    if (u_present or r_present) and (s >= th if eq3 else s > th):  # step 3
+        return True
+    return s + vp >= th if eq else s + vp > th  # step 4
+
+
+def preempt_of(snap, pod_row, cand_rows, now, on_equal=False, ctx=None):
+    """kt_preempt_launch for one preemptor, in closed form on a Snapshot (no GPU) -> (prefix, victims [len(cand_rows)]).
+    prefix: the smallest k for which PreFilter(pod) is Success once the candidates ``cand_rows[:k]`` are gone and every
+    responsible throttle has been reconciled at ``now`` (reserved amounts unchanged; a throttle whose reconcile is an error keeps
+    its stored status); 0: the pod already passes against a fresh reconcile; -1: no prefix helps.  The list is cut before the
+    first candidate whose own PreFilter is an error or whose row is invalid.  victims[j] = 1 iff j < prefix, the candidate is
+    counted and a throttle that affects the pod matches it.  Deleting a prefix lowers every `used` by a prefix sum; a name stays
+    present only while a remaining counted pod carries it, the pod count only while a pod is counted."""
+    ctx = preempt_context(snap, now) if ctx is None else ctx
+    p, cands, eq = int(pod_row), [int(c) for c in cand_rows], bool(on_equal)
+    m = len(cands)
+    none = (-1, [0] * m)
+    if not (0 <= p < snap.n_pods) or not int(snap.pod_flags[p]) & S.POD_VALID:
+        return none
+    err, affected = affected_throttles(snap, p)
+    if err:
+        return none
+    m_eff = m
+    for j, c in enumerate(cands):
+        if not (0 <= c < snap.n_pods) or not int(snap.pod_flags[c]) & S.POD_VALID or affected_throttles(snap, c)[0]:
+            m_eff = j
+            break
+    counted = lambda c: (int(snap.pod_flags[c]) & (_COUNTABLE | S.POD_FINISHED)) == _COUNTABLE
+    req = {d: v for d, v in pod_requests(snap, p).items() if v != 0}
+    creq = [pod_requests(snap, c) if counted(c) else {} for c in cands[:m_eff]]
+    contributes = [[counted(c) and t in ctx["match"].get(c, ()) for c in cands[:m_eff]] for t in affected]
+    fails = [False] * (m_eff + 1)  # fails[k]: some (throttle, amount) stops the pod in S_k
+    for ti, t in enumerate(affected):
+        th = ctx["thr"][t]
+        f = int(snap.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+        if th["error"]:  # the stored status stays, in every S_k: the STORED calculatedThreshold once calculatedAt is set, else spec
+            used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+            sth, sth_count = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+            flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+            bad = _amount_fails(1, sth_count, bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0,
+                                res_count is not None, res_count or 0, eq3, eq)
+            for d, v in req.items():
+                bad = bad or _amount_fails(v, sth.get(d), bool(flg >> d & 1), d in used, used.get(d, 0), d in res, res.get(d, 0), eq3, eq)
+            if bad:
+                return none
+            continue
+        val, cnt, pods = dict(th["val"]), dict(th["cnt"]), th["pods"]
+        for k in range(m_eff + 1):
+            if k > 0 and contributes[ti][k - 1]:
+                pods -= 1
+                for d, v in creq[k - 1].items():
+                    val[d] -= v
+                    cnt[d] -= 1
+            u_hc = pods > 0
+            cc = th["calc_count"]
+            bad = _amount_fails(1, th["th_count"], cc is not None and u_hc and pods >= cc, u_hc, pods, res_count is not None, res_count or 0, eq3, eq)
+            for d, v in req.items():
+                u_pr = cnt.get(d, 0) > 0
+                cv = th["calc"].get(d)
+                bad = bad or _amount_fails(v, th["th"].get(d), cv is not None and u_pr and val[d] >= cv, u_pr, val.get(d, 0), d in res,
+                                           res.get(d, 0), eq3, eq)
+            fails[k] = fails[k] or bad
+    prefix = next((k for k in range(m_eff + 1) if not fails[k]), -1)
+    victims = [0] * m
+    for j in range(max(prefix, 0)):
+        victims[j] = int(any(contributes[ti][j] for ti in range(len(affected))))
+    return prefix, victims
+
+
 class PagedEngine:
     """One HIP engine per page of a ``ClusterState.build_pages()`` result; reconcile and check run on every page (the
     selector scan is repeated per page: the price of more than 16 resource names) and come back combined."""
