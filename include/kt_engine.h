@@ -389,12 +389,37 @@ int32_t kt_headroom_fetch(kt_engine* e, int64_t n, int64_t* out_copies, int32_t*
  *      KT_ERR_NOT_READY; a status stored with KT_RECONCILE_APPLY stays stored).  Its aggregate runs beside the partial buffer:
  *      a pending kt_aggregate_launch keeps its sums.  The results live in buffers of their own, so a kt_reconcile_launch issued
  *      on the same stream after the launch leaves it fetchable.
- *      Out of scope: the paged form (more than KT_MAX_DIMS resource names), a "reprieve" pass that shrinks the victim set
- *      further, several ranks. ------------------------------------------------------------------------------------------ */
+ *      Out of scope: the paged form (more than KT_MAX_DIMS resource names), several ranks (the reprieve pass that shrinks the
+ *      victim set further is kt_preempt_reprieve_launch below). --------------------------------------------------------- */
 #define KT_PREEMPT_NONE (-1)
 int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
                           int32_t now_ns, int32_t on_equal, void* stream);
 int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* out_victims /* [n][n_cand], nullable */);
+/* ---- preempt, reprieved: the prefix of kt_preempt_launch with its victim mask shrunk to a minimal set — the second half of
+ *      what kube-scheduler's selectVictimsOnNode does for every preemption: starting from "all potential victims removed", the
+ *      victims are put back one by one, most important first, and each stays back as long as the preemptor still fits.
+ *      Notation as for kt_preempt_launch.  For preemptor p let k = out_prefix and M the prefix victim mask defined there.  k <= 0:
+ *      the row is all zero, as there.  Otherwise V = M, and for j = k-1, k-2, .., 0 in that order, for each j with M[j] = 1, let
+ *      V' = V \ {c_j}: state S(V') is the cluster in which exactly the pods of V' no longer exist and every responsible throttle
+ *      has been reconciled at `now` (reserved amounts unchanged; a throttle whose reconcile is an error keeps its stored status, the
+ *      rule of S_k).  If PreFilter(p) is Success in S(V'), V := V' — c_j is reprieved — otherwise c_j stays a victim.
+ *      out_victims[i][j] = 1 iff c_j is in V at the end; out_prefix is what kt_preempt_launch reports.
+ *      Presence in `used` is exact, as in the prefix query: putting a pod back increments the contributor count of every resource
+ *      name it carries, a name is present iff its count is positive, and the pod count of `used` is present iff a pod is counted.
+ *      The definition is operational — the walk, step by step, with no monotonicity assumption — so requests of either sign are
+ *      answered as the walk answers them.  For non-negative requests the result is minimal: putting any single remaining victim
+ *      back makes p fail; and the last masked candidate is never reprieved (the prefix is the shortest).
+ *      The call is kt_preempt_launch followed, on the same stream, by ONE launch of kt_preempt_reprieve
+ *      (csrc/kt_kernels_reprieve.hip) that rewrites the victim bytes in place: one wave per preemptor, lanes = the reconciled
+ *      throttles that affect it, each holding the `used` of its throttle in the current state (in LDS; a list that outgrows it
+ *      lives in a workspace of the engine's own, grown like the result buffers only once the stream of an unfetched launch has
+ *      drained).  A preemptor with prefix <= 0 costs one load.  The walk is sequential per preemptor and independent across them.
+ *      m_eff, the list cut, every refusal and its code, "a refused call leaves the check slot, the reconcile report and the
+ *      result buffers alone", n == 0 and n_cand == 0, and the slot rules are those of kt_preempt_launch: the two launches share
+ *      the one pending result, fetched with kt_preempt_fetch — a later launch of either kind replaces it.
+ *      Out of scope: the paged form, several ranks. --------------------------------------------------------------------- */
+int32_t kt_preempt_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
+                                   int32_t now_ns, int32_t on_equal, void* stream);
 /* Current reserved amounts of n throttle rows (after kt_set_reserved / kt_admit_launch(KT_ADMIT_COMMIT)). */
 int32_t kt_fetch_reserved(kt_engine* e, int32_t n, const int32_t* throttle_rows, const kt_amounts* out);
 int32_t kt_throttle_rows(kt_engine* e, int32_t* out_rows);

@@ -44,7 +44,7 @@ const (
 type Engine struct {
 	h    *C.kt_engine
 	dims int
-	mu   sync.Mutex // the engine's ONE check slot: every method that takes it (Check, AffectedPods, Admit, AdmitGangs, Headroom, Preempt) holds mu from its launch to its fetch; Verdict's one-pod check runs beside the slot and takes no lock
+	mu   sync.Mutex // the engine's ONE check slot: every method that takes it (Check, AffectedPods, Admit, AdmitGangs, Headroom, Preempt, PreemptReprieve) holds mu from its launch to its fetch; Verdict's one-pod check runs beside the slot and takes no lock
 }
 
 // New creates an engine for `dims` resource names (<= 16), pods with up to maxLabels labels and the given row capacities.
@@ -409,13 +409,35 @@ func (e *Engine) Headroom(rows []int64, onEqual bool, cap int64) (copies []int64
 // matches.  A dry run: nothing is deleted, stored status and reserved amounts stay.  Launch and fetch run under e.mu, which every other user of
 // the check slot (Check, AffectedPods, Admit, AdmitGangs, Headroom) takes as well: no goroutine drops another's pending launch.  Not compiled in this repository (no Go toolchain in its build).
 func (e *Engine) Preempt(rows, cands []int64, nowS int64, nowNs int32, onEqual bool) (prefix []int64, victims []uint8, err error) {
+	return e.preempt(rows, cands, nowS, nowNs, onEqual, false)
+}
+
+// PreemptReprieve is Preempt with the reprieve pass behind it (kt_preempt_reprieve_launch + kt_preempt_fetch): prefix is what
+// Preempt answers; the victims of each prefix are put back one by one, the last of the list first, and each stays back as long as
+// the pod still passes PreFilter against a fresh reconcile at now — what remains is a minimal set (with non-negative requests no
+// single one of them can stay).  A dry run like Preempt, and like Preempt under e.mu from its launch to its fetch.  Not compiled in
+// this repository (no Go toolchain in its build).
+func (e *Engine) PreemptReprieve(rows, cands []int64, nowS int64, nowNs int32, onEqual bool) (prefix []int64, victims []uint8, err error) {
+	return e.preempt(rows, cands, nowS, nowNs, onEqual, true)
+}
+
+// preempt is the one body of Preempt and PreemptReprieve: the launch (with or without the reprieve pass) and kt_preempt_fetch,
+// under e.mu from the one to the other.
+func (e *Engine) preempt(rows, cands []int64, nowS int64, nowNs int32, onEqual, reprieve bool) (prefix []int64, victims []uint8, err error) {
 	if len(rows) == 0 {
 		return nil, nil, nil
 	}
 	e.mu.Lock()
 	defer e.mu.Unlock()
-	if rc := C.kt_preempt_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(len(cands)), i64(cands), C.int64_t(nowS),
-		C.int32_t(nowNs), b2i(onEqual), nil); rc != C.KT_OK {
+	var rc C.int32_t
+	if reprieve {
+		rc = C.kt_preempt_reprieve_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(len(cands)), i64(cands), C.int64_t(nowS),
+			C.int32_t(nowNs), b2i(onEqual), nil)
+	} else {
+		rc = C.kt_preempt_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(len(cands)), i64(cands), C.int64_t(nowS),
+			C.int32_t(nowNs), b2i(onEqual), nil)
+	}
+	if rc != C.KT_OK {
 		return nil, nil, e.err(rc)
 	}
 	prefix = make([]int64, len(rows))

@@ -1,7 +1,9 @@
 // kt_admit_common.h — what the admission kernels (kt_kernels_admit.hip: kt_admit, kt_admit_gangs) and the headroom kernel
 // (kt_kernels_headroom.hip: kt_headroom) share, gfx950: the affected-throttle list of a status-matrix row, the page descriptor
-// by value, the effective threshold and step 3's isThrottledOnEqual of a throttle, the 128-bit comparison.  The page descriptor
-// itself (AdmitPage) is host-visible: kt_launch.h.
+// by value, the effective threshold and step 3's isThrottledOnEqual of a throttle, the 128-bit comparison; and what the preemption
+// kernels (kt_kernels_preempt.hip: kt_preempt, kt_kernels_reprieve.hip: kt_preempt_reprieve) share: the four steps for one amount
+// against `used` as it stands in some state, the wave scan, the chunk and grid sizes.  The page descriptor itself (AdmitPage) is
+// host-visible: kt_launch.h.
 #pragma once
 #include "kt_index_device.h"
 
@@ -64,5 +66,31 @@ __device__ __forceinline__ const AmountTab& admit_threshold(const ThrTables& tt,
 // isThrottledOnEqual of step 3: always for a Throttle, the caller's for a ClusterThrottle (throttle_types.go:143 vs
 // clusterthrottle_types.go:45)
 __device__ __forceinline__ bool admit_eq3(uint32_t tf, bool eq) { return (tf & kThrCluster) ? eq : true; }
+
+constexpr int kPreemptChunk = kWave * 16;  // matrix bytes per chunk = entries the chunk list holds
+constexpr int kPreemptMaxBlocks = 2048;    // 256 CUs x 8 one-wave workgroups; more preemptors than that: the grid strides
+constexpr uint32_t kCounted = kPodValid | kPodSchedMatch | kPodScheduled;  // ... and not kPodFinished (throttle_controller.go:217-219)
+
+// One amount of one throttle for the preemptor (a resource name it requests with vp != 0, or the pod count with vp = 1)
+// against `used` as it stands in some S_k: does one of the four CheckThrottledFor steps stop the pod
+__device__ __forceinline__ bool preempt_fails(int64_t vp, bool th_has, int64_t tv, bool flagged, bool u_pres, int64_t uv, bool r_has, int64_t rv,
+                                              bool eq3, bool eq) {
+  if (flagged) return true;   // step 2: status.throttled of the fresh reconcile
+  if (!th_has) return false;  // the threshold does not name the amount
+  if (vp > tv) return true;   // step 1
+  const __int128 s = (__int128)(u_pres ? uv : 0) + (r_has ? rv : 0);
+  if ((u_pres || r_has) && admit_cmp(s, tv, eq3)) return true;  // step 3
+  return admit_cmp(s + vp, tv, eq);                             // step 4
+}
+
+template <class V>
+__device__ __forceinline__ V wave_inclusive_scan(V x, uint32_t lane) {
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const V y = __shfl_up(x, o);
+    if (lane >= (uint32_t)o) x += y;
+  }
+  return x;
+}
 
 }  // namespace kt

@@ -717,12 +717,13 @@ int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, c
 }
 
 // ---------------------------------------------------------------------------------------------------
-// preempt: the shortest victim prefix that lets a blocked pod through (kt_kernels_preempt.hip)
+// preempt: the shortest victim prefix that lets a blocked pod through (kt_kernels_preempt.hip), and the reprieve pass that shrinks
+// its victim mask to a minimal set (kt_kernels_reprieve.hip)
 // ---------------------------------------------------------------------------------------------------
-int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
-                          int32_t now_ns, int32_t on_equal, void* stream) {
-  if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
-  LaunchLock lk(e);
+// kt_preempt_launch and, with `reprieve`, kt_preempt_reprieve_launch: the same refusals, the same launches, and behind them on the
+// same stream the one launch of kt_preempt_reprieve that rewrites the victim bytes in place.  The caller holds the launch lock.
+static int32_t preempt_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
+                              int32_t now_ns, int32_t on_equal, void* stream, bool reprieve) {
   if (n_cand < 0) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt: n_cand = %lld", (long long)n_cand);
   if ((n > 0 && !pod_rows) || (n_cand > 0 && !cand_rows)) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt: pod_rows / cand_rows missing");
   for (int64_t i = 0; i < n + n_cand; ++i) {
@@ -761,11 +762,14 @@ int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int6
   if (rc != KT_OK) return rc;
   if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "preempt: `used` is wider than int64 (kt_preempt reads int64 sums)");
   const size_t vic = (size_t)n * (size_t)n_cand;
-  if (e->d_preempt_prefix.cap < (size_t)n || e->d_preempt_victims.cap < vic + 1) {
+  // the reprieve kernel's list state where it can outgrow LDS (0 bytes: it cannot, or nothing is walked)
+  const size_t ws = reprieve && n_cand > 0 ? kt::reprieve_ws_bytes(T, e->D, n, e->reprieve_lds_cap_limit) : 0;
+  if (e->d_preempt_prefix.cap < (size_t)n || e->d_preempt_victims.cap < vic + 1 || (ws != 0 && e->d_reprieve_ws.cap < ws)) {
     // a launch that was never fetched may still be writing the old buffers, on the stream it was given (as kt_headroom_launch)
     if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
     KT_HIP(e, e->d_preempt_prefix.reserve((size_t)n));
     KT_HIP(e, e->d_preempt_victims.reserve(vic + 1));
+    if (ws != 0) KT_HIP(e, e->d_reprieve_ws.reserve(ws));
   }
   // ONE check over preemptors ++ candidates: which throttles match which pod, and the error rows
   std::vector<int64_t> rows((size_t)(n + n_cand));
@@ -779,9 +783,29 @@ int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int6
   kt::launch_preempt(pg, n, n_cand, e->d_rows.p, e->thr_rows_hi, on_equal != 0, e->d_status.p, e->d_summary.p, e->d_preempt_partial.p,
                      e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p, e->d_preempt_victims.p, s);
   KT_HIP(e, hipGetLastError());
+  if (reprieve) {
+    kt::launch_preempt_reprieve(pg, n, n_cand, e->d_rows.p, e->thr_rows_hi, on_equal != 0, e->d_status.p, e->d_preempt_partial.p,
+                                e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p, e->d_preempt_victims.p,
+                                ws != 0 ? e->d_reprieve_ws.p : nullptr, e->reprieve_lds_cap_limit, s);
+    KT_HIP(e, hipGetLastError());
+  }
   e->last_stream = s;
   e->preempt_ready = true, e->preempt_n = n, e->preempt_m = n_cand;
   return KT_OK;
+}
+
+int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
+                          int32_t now_ns, int32_t on_equal, void* stream) {
+  if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  return preempt_locked(e, n, pod_rows, n_cand, cand_rows, now_s, now_ns, on_equal, stream, /*reprieve=*/false);
+}
+
+int32_t kt_preempt_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
+                                   int32_t now_ns, int32_t on_equal, void* stream) {
+  if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  return preempt_locked(e, n, pod_rows, n_cand, cand_rows, now_s, now_ns, on_equal, stream, /*reprieve=*/true);
 }
 
 int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* out_victims) {

@@ -41,32 +41,6 @@ struct PreemptArgs {
   int32_t T, on_equal;
 };
 
-constexpr int kPreemptChunk = kWave * 16;  // matrix bytes per chunk = entries the chunk list holds
-constexpr int kPreemptMaxBlocks = 2048;    // 256 CUs x 8 one-wave workgroups; more preemptors than that: the grid strides
-constexpr uint32_t kCounted = kPodValid | kPodSchedMatch | kPodScheduled;  // ... and not kPodFinished (throttle_controller.go:217-219)
-
-// One amount of one throttle for the preemptor (a resource name it requests with vp != 0, or the pod count with vp = 1)
-// against `used` as it stands in some S_k: does one of the four CheckThrottledFor steps stop the pod
-__device__ __forceinline__ bool preempt_fails(int64_t vp, bool th_has, int64_t tv, bool flagged, bool u_pres, int64_t uv, bool r_has, int64_t rv,
-                                              bool eq3, bool eq) {
-  if (flagged) return true;   // step 2: status.throttled of the fresh reconcile
-  if (!th_has) return false;  // the threshold does not name the amount
-  if (vp > tv) return true;   // step 1
-  const __int128 s = (__int128)(u_pres ? uv : 0) + (r_has ? rv : 0);
-  if ((u_pres || r_has) && admit_cmp(s, tv, eq3)) return true;  // step 3
-  return admit_cmp(s + vp, tv, eq);                             // step 4
-}
-
-template <class V>
-__device__ __forceinline__ V wave_inclusive_scan(V x, uint32_t lane) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const V y = __shfl_up(x, o);
-    if (lane >= (uint32_t)o) x += y;
-  }
-  return x;
-}
-
 template <int DT>
 __global__ __launch_bounds__(kWave) void kt_preempt(const PreemptArgs a) {
   __shared__ uint32_t chunk_list[kPreemptChunk];

@@ -119,6 +119,15 @@ bool launch_headroom(const AdmitPage* pages, int n_pages, AdmitPage* pages_dev, 
 void launch_preempt(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int T, bool on_equal, const uint8_t* status,
                     const uint64_t* summary, const unsigned long long* partial, const AmountTab& calc, const uint8_t* calc_updated,
                     const uint8_t* error, int64_t* prefix, uint8_t* victims, hipStream_t s);
+// the reprieve pass behind it (kt_kernels_reprieve.hip): one wave per preemptor walks its masked victims back, last first, and
+// rewrites victims [n][m] in place; prefix is read.  The list of a preemptor's reconciled affecting throttles lives in LDS up to
+// reprieve_lds_cap(D, limit) entries (limit: a test hook that lowers the capacity, 0 = none), beyond that in `ws`:
+// reprieve_ws_bytes bytes of device memory (0: no list can outgrow LDS, ws may be null)
+uint32_t reprieve_lds_cap(int D, uint32_t limit);
+size_t reprieve_ws_bytes(int T, int D, int64_t n, uint32_t lds_cap_limit);
+void launch_preempt_reprieve(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int T, bool on_equal, const uint8_t* status,
+                             const unsigned long long* partial, const AmountTab& calc, const uint8_t* calc_updated, const uint8_t* error,
+                             const int64_t* prefix, uint8_t* victims, void* ws, uint32_t lds_cap_limit, hipStream_t s);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

@@ -42,6 +42,7 @@ EXPORTS = [
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
+    "kt_preempt_reprieve_launch",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -252,6 +253,7 @@ def lib():
         L.kt_preempt_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_void_p]
         L.kt_preempt_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.kt_preempt_reprieve_launch.argtypes = L.kt_preempt_launch.argtypes
         _LIB = L
     return _LIB
 
@@ -592,19 +594,29 @@ class Engine:
         self._ck(lib().kt_preempt_launch(self._h, len(a), p if len(a) else None, len(c), q if len(c) else None, int(now[0]), int(now[1]),
                                          int(on_equal), stream))
 
+    def preempt_reprieve_launch(self, pod_rows, cand_rows, now, on_equal=False, stream=None):
+        """kt_preempt_reprieve_launch: kt_preempt_launch and, behind it on the same stream, the reprieve pass that shrinks the
+        victim bytes to a minimal set; fetched with ``preempt_fetch``."""
+        a, p = self._rows(pod_rows, np.int64)
+        c, q = self._rows(cand_rows, np.int64)
+        self._ck(lib().kt_preempt_reprieve_launch(self._h, len(a), p if len(a) else None, len(c), q if len(c) else None, int(now[0]),
+                                                  int(now[1]), int(on_equal), stream))
+
     def preempt_fetch(self, n, n_cand, want_victims=True):
         prefix = np.zeros(max(n, 1), np.int64)
         flat = np.zeros(max(n * n_cand, 1), np.uint8) if want_victims else None
         self._ck(lib().kt_preempt_fetch(self._h, n, prefix.ctypes.data, None if flat is None else flat.ctypes.data))
         return prefix[:n], (None if flat is None else flat[:n * n_cand].reshape(n, n_cand))
 
-    def preempt(self, pod_rows, cand_rows, now, on_equal=False, want_victims=True):
+    def preempt(self, pod_rows, cand_rows, now, on_equal=False, want_victims=True, reprieve=False):
         """kt_preempt_launch + kt_preempt_fetch: per preemptor the smallest k for which the pod passes PreFilter once the
         candidates ``cand_rows[:k]`` are gone and every throttle has been reconciled at ``now`` (0: it already passes against a
         fresh reconcile, PREEMPT_NONE: no prefix helps), and the victim bytes [n][n_cand] — 1 for the counted candidates below
         the prefix that a throttle affecting the pod matches -> (prefix int64 [n], victims uint8 [n][n_cand] or None).  A dry
-        run: stored status and reserved amounts stay as they are."""
-        self.preempt_launch(pod_rows, cand_rows, now, on_equal)
+        run: stored status and reserved amounts stay as they are.  ``reprieve``: the victims are walked back, last first, and
+        each stays back as long as the pod still passes (kt_preempt_reprieve_launch) — the prefix is the same, the victim bytes
+        are a minimal set."""
+        (self.preempt_reprieve_launch if reprieve else self.preempt_launch)(pod_rows, cand_rows, now, on_equal)
         return self.preempt_fetch(len(pod_rows), len(cand_rows), want_victims)
 
     def fetch_reserved(self, rows=None) -> S.Amounts:

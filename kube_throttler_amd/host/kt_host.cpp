@@ -1238,7 +1238,7 @@ HeadroomResult KubeThrottler::Headroom(const std::string& pod_key, int64_t cap) 
 // Which of the candidates have to go before this pod passes PreFilter: kt_preempt_launch + kt_preempt_fetch on the mirror's one
 // engine (isThrottledOnEqual = false, as PreFilter).  The reserved totals are read as they stand and nothing is changed.
 PreemptResult KubeThrottler::Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys,
-                                     const std::string& now_rfc3339) {
+                                     const std::string& now_rfc3339, bool reprieve) {
   std::lock_guard<std::recursive_mutex> lk(p_->mu);
   auto& p = *p_;
   PreemptResult out;
@@ -1263,7 +1263,9 @@ PreemptResult KubeThrottler::Preempt(const std::string& pod_key, const std::vect
     }
   int64_t prefix = KT_PREEMPT_NONE;
   std::vector<uint8_t> mask(cand.size() + 1);
-  int32_t rc = kt_preempt_launch(p.e, 1, &row, (int64_t)cand.size(), cand.data(), now_s, now_ns, /*isThrottledOnEqual=*/0, nullptr);
+  // with `reprieve` the same launch plus the walk that puts victims back, behind it on the same stream; one fetch either way
+  int32_t rc = (reprieve ? kt_preempt_reprieve_launch : kt_preempt_launch)(p.e, 1, &row, (int64_t)cand.size(), cand.data(), now_s, now_ns,
+                                                                           /*isThrottledOnEqual=*/0, nullptr);
   if (rc == KT_OK) rc = kt_preempt_fetch(p.e, 1, &prefix, mask.data());
   if (rc != KT_OK) {
     out.error = p.engine_error(rc);

@@ -227,7 +227,11 @@ class KubeThrottler {
   // candidates of that prefix that count in a throttle affecting the pod; the others of the prefix may stay.  A dry run: no pod is
   // deleted, no status and no reservation changes.  A mirror that runs on pages (more than KT_MAX_DIMS resource names) answers an
   // error: the engine has no paged form of the query.
-  PreemptResult Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys, const std::string& now_rfc3339);
+  // `reprieve` (kt_preempt_reprieve_launch, still one engine call): the victims of that prefix are then put back one by one, the last
+  // of the list first, and each stays back as long as the pod still passes — the second half of the scheduler's selectVictimsOnNode.
+  // The names that remain are a minimal set: with non-negative requests no single one of them can stay.
+  PreemptResult Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys, const std::string& now_rfc3339,
+                        bool reprieve = false);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

@@ -350,14 +350,16 @@ def _amount_fails(vp, th, flagged, u_present, uv, r_present, rv, eq3, eq) -> boo
     return s + vp >= th if eq else s + vp > th  # step 4
 
 
-def preempt_of(snap, pod_row, cand_rows, now, on_equal=False, ctx=None):
+def preempt_of(snap, pod_row, cand_rows, now, on_equal=False, ctx=None, reprieve=False):
     """kt_preempt_launch for one preemptor, in closed form on a Snapshot (no GPU) -> (prefix, victims [len(cand_rows)]).
     prefix: the smallest k for which PreFilter(pod) is Success once the candidates ``cand_rows[:k]`` are gone and every
     responsible throttle has been reconciled at ``now`` (reserved amounts unchanged; a throttle whose reconcile is an error keeps
     its stored status); 0: the pod already passes against a fresh reconcile; -1: no prefix helps.  The list is cut before the
     first candidate whose own PreFilter is an error or whose row is invalid.  victims[j] = 1 iff j < prefix, the candidate is
     counted and a throttle that affects the pod matches it.  Deleting a prefix lowers every `used` by a prefix sum; a name stays
-    present only while a remaining counted pod carries it, the pod count only while a pod is counted."""
+    present only while a remaining counted pod carries it, the pod count only while a pod is counted.
+    ``reprieve`` (kt_preempt_reprieve_launch): the masked victims are then put back one by one, the last first, and each stays back
+    as long as the pod still passes every affecting throttle; victims is what remains."""
     ctx = preempt_context(snap, now) if ctx is None else ctx
     p, cands, eq = int(pod_row), [int(c) for c in cand_rows], bool(on_equal)
     m = len(cands)
@@ -413,7 +415,57 @@ def preempt_of(snap, pod_row, cand_rows, now, on_equal=False, ctx=None):
     victims = [0] * m
     for j in range(max(prefix, 0)):
         victims[j] = int(any(contributes[ti][j] for ti in range(len(affected))))
+    if reprieve and prefix > 0:
+        _reprieve(snap, ctx, affected, contributes, creq, req, eq, prefix, victims)
     return prefix, victims
+
+
+def _reprieve(snap, ctx, affected, contributes, creq, req, eq, prefix, victims):
+    """The reprieve walk on the sums of ``preempt_context``: per reconciled affecting throttle the `used` of the state without the
+    masked victims; position prefix - 1 first, a victim is put back where every throttle that matches it still lets the pod
+    through with its amounts added (the others do not change: they pass already).  ``victims`` is rewritten in place."""
+    live = []  # [throttle row, its index in `contributes`, values, contributor counts, counted pods]
+    for ti, t in enumerate(affected):
+        th = ctx["thr"][t]
+        if th["error"]:  # keeps its stored status whoever is deleted: it passed, or the prefix would not be positive
+            continue
+        val, cnt, pods = dict(th["val"]), dict(th["cnt"]), th["pods"]
+        for j in range(prefix):
+            if victims[j] and contributes[ti][j]:
+                pods -= 1
+                for d, v in creq[j].items():
+                    val[d] -= v
+                    cnt[d] -= 1
+        live.append([t, ti, val, cnt, pods])
+    for j in range(prefix - 1, -1, -1):
+        if not victims[j]:
+            continue
+        back = []
+        for entry in live:
+            t, ti, val, cnt, pods = entry
+            if not contributes[ti][j]:
+                continue
+            val, cnt, pods = dict(val), dict(cnt), pods + 1
+            for d, v in creq[j].items():
+                val[d] = val.get(d, 0) + v
+                cnt[d] = cnt.get(d, 0) + 1
+            th = ctx["thr"][t]
+            eq3 = eq if int(snap.thr_flags[t]) & S.THR_CLUSTER else True
+            res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+            cc = th["calc_count"]
+            bad = _amount_fails(1, th["th_count"], cc is not None and pods >= cc, True, pods, res_count is not None, res_count or 0, eq3, eq)
+            for d, v in req.items():
+                u_pr = cnt.get(d, 0) > 0
+                cv = th["calc"].get(d)
+                bad = bad or _amount_fails(v, th["th"].get(d), cv is not None and u_pr and val.get(d, 0) >= cv, u_pr, val.get(d, 0), d in res,
+                                           res.get(d, 0), eq3, eq)
+            if bad:
+                break
+            back.append((entry, val, cnt, pods))
+        else:
+            victims[j] = 0
+            for entry, val, cnt, pods in back:
+                entry[2:] = [val, cnt, pods]
 
 
 class PagedEngine:
