@@ -420,6 +420,61 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
  *      Out of scope: the paged form, several ranks. --------------------------------------------------------------------- */
 int32_t kt_preempt_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
                                    int32_t now_ns, int32_t on_equal, void* stream);
+/* ---- forecast: the first instant at which a blocked pod passes — the one axis no other query looks along.
+ *      temporaryThresholdOverrides make every threshold a step function of the clock (throttle_types.go:65-106,
+ *      temporary_threshold_override.go:57-70): a pod that PreFilter rejects now may pass when a night-time override begins or a
+ *      freeze window ends.  For pod p = pod_rows[i] and the instants t_0 < t_1 < .. < t_{m-1} (inst_s / inst_ns, m = n_inst), state
+ *      R_t is the cluster as the engine holds it now with every valid and responsible throttle reconciled at instant t:
+ *      affectedPods -> used = fold ResourceAmount.Add, CalculateThreshold(t), throttled = IsThrottled(used, true), and the rule
+ *      "calculatedThreshold is replaced only if threshold or messages differ by value, and calculatedAt becomes non-zero only then"
+ *      (throttle_controller.go:116-133).  Reserved amounts are unchanged; a throttle whose reconcile reports an error keeps its
+ *      stored status in every R_t, as kt_reconcile_fetch's `error` byte defines.  This is exactly what
+ *      kt_reconcile_launch(t, KT_RECONCILE_APPLY) followed by kt_check would report if each t were applied to the state as it is
+ *      now, and not on top of the previous instant.
+ *      out_verdicts[i][k] (nullable, [n][n_inst]) is the KT_VERDICT_* of PreFilter(p) (plugin.go:148-215) in R_{t_k};
+ *      out_first[i] is the smallest k whose verdict is KT_VERDICT_SUCCESS, or KT_FORECAST_NONE.  A pod whose PreFilter is an
+ *      Error, or whose row is invalid, reports KT_VERDICT_ERROR at every instant and KT_FORECAST_NONE; a pod no throttle affects
+ *      reports Success at every instant and 0.  With inst = [now], out_first == 0 exactly where kt_preempt_launch at `now`
+ *      reports prefix 0.
+ *      Two facts of the reconcile the kernel depends on (finalize_throttle in csrc/kt_kernels_finalize.hip, at its "replace the
+ *      stored calculatedThreshold" step):
+ *        (1) after a reconcile the check reads status.calculatedThreshold iff the stored calculatedAt was already non-zero or this
+ *            reconcile replaces it; it reads spec.threshold otherwise (throttle_types.go:129-132).  A never-reconciled throttle
+ *            whose computed threshold equals the empty stored one by value therefore keeps being read through spec.threshold.
+ *        (2) the messages fingerprint of CalculateThreshold depends on parse errors only and never on t; the comparison of the
+ *            threshold by value does depend on t.
+ *      An override is active at t iff begin <= t && (end is zero || t <= end): BOTH ends are inclusive; an override with a parse
+ *      error is never active.  The first active override wins per resource name and for the pod count; an active override that
+ *      omits a name leaves it unthrottled; without an active override spec.threshold holds.
+ *      One kt_check launch with the status matrix over pod_rows, the aggregate and dry finalize (at t_0) of kt_preempt_launch —
+ *      the dense scan with exact contributor counts, and the `error` bytes — and one launch of kt_forecast
+ *      (csrc/kt_kernels_forecast.hip): one wave per pod, lane = instant position, every instant judged in parallel.
+ *      The call is a dry run: stored status and reserved amounts are not changed.
+ *      Refused before anything is launched: n_inst < 1, instants that are not strictly ascending, an inst_ns outside [0, 10^9), a
+ *      missing array (KT_ERR_INVALID_ARGUMENT); n x throttle_rows or n x n_inst > 2^31 (KT_ERR_OUT_OF_RANGE); `used` wider than
+ *      int64, a KT_VARIANT_INCREMENTAL engine, an exchange world above 1 (KT_ERR_UNSUPPORTED; the |request| sums probe runs first
+ *      where the sums are not known, as for kt_preempt_launch).  A refused call leaves the check slot, the reconcile report and all
+ *      result buffers alone.  n == 0 is KT_OK and launches nothing.  kt_forecast_fetch synchronises; KT_ERR_NOT_READY without a
+ *      pending kt_forecast_launch.
+ *      Slots: those of kt_preempt_launch — the launch uses the engine's ONE check slot (a pending kt_check_launch or
+ *      kt_headroom_launch is dropped; a later user of the slot drops a pending forecast), its dry finalize drops the report of a
+ *      pending kt_reconcile_launch, a pending kt_aggregate_launch keeps its sums.  The results live in buffers of their own, grown
+ *      only once the stream of an unfetched launch has drained: a pending forecast and a pending kt_preempt_launch result are
+ *      independent — after one launch of each, in either order, both are fetchable.
+ *      Out of scope: the paged form (more than KT_MAX_DIMS resource names), several ranks. -------------------------------- */
+#define KT_FORECAST_NONE (-1)
+int32_t kt_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns,
+                           int32_t on_equal, void* stream);
+int32_t kt_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, uint8_t* out_verdicts /* [n][n_inst], nullable */);
+/* The sorted, distinct instants in (from, until] at which the CalculateThreshold of some valid and responsible throttle can change:
+ * every parsed non-zero `begin` of an override, and for every parsed non-zero `end` the instant end + 1 ns — the FIRST instant at
+ * which the override is no longer active.  That is deliberately not the `end` that NextOverrideHappensIn
+ * (kt_reconcile_fetch_next_override) reports: at `end` itself the override is still active (both ends are inclusive).  Overrides
+ * with a parse error contribute nothing.  Writes the earliest min(total, cap) instants to out_s / out_ns and the full count to
+ * *out_total; cap == 0 with NULL arrays just counts.  Host-only: reads the engine's host copy of the throttle specs under the
+ * launch lock and launches nothing.  Together with `now` in front, the instants a host passes to kt_forecast_launch. */
+int32_t kt_override_instants(kt_engine* e, int64_t from_s, int32_t from_ns, int64_t until_s, int32_t until_ns, int64_t cap, int64_t* out_s,
+                             int32_t* out_ns, int64_t* out_total);
 /* Current reserved amounts of n throttle rows (after kt_set_reserved / kt_admit_launch(KT_ADMIT_COMMIT)). */
 int32_t kt_fetch_reserved(kt_engine* e, int32_t n, const int32_t* throttle_rows, const kt_amounts* out);
 int32_t kt_throttle_rows(kt_engine* e, int32_t* out_rows);

@@ -31,6 +31,7 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
                                    hipStream_t s, bool allow_small = true) {
   e->headroom_ready = false;  // the one check slot is taken: a pending kt_headroom_launch is gone
   e->preempt_ready = false;   // ... and a pending kt_preempt_launch
+  e->forecast_ready = false;  // ... and a pending kt_forecast_launch
   if (pod_rows) {
     for (int64_t i = 0; i < n; ++i)
       if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity)
@@ -187,7 +188,7 @@ int32_t kt_sweep_launch(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t fl
   e->last_kernel[KT_KERNEL_AGGREGATE] = "(in kt_sweep_bitmap)";
   e->last_kernel[KT_KERNEL_REDUCE] = "(in kt_reduce_finalize_packed)";
   e->check_n = n, e->check_in_h_small = false, e->check_T = e->thr_rows_hi, e->check_has_status = false, e->check_ready = true;
-  e->headroom_ready = false, e->preempt_ready = false;
+  e->headroom_ready = false, e->preempt_ready = false, e->forecast_ready = false;
   e->fused_pending = true, e->fused_nb = launched, e->fused_epoch = sc.epoch, e->fused_pack = plan;
   e->agg_pending = true, e->agg_words = words, e->agg_gen = e->program_gen;
   e->last_stream = s;
@@ -775,8 +776,10 @@ static int32_t preempt_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, 
   std::vector<int64_t> rows((size_t)(n + n_cand));
   std::copy(pod_rows, pod_rows + n, rows.begin());
   std::copy(cand_rows, cand_rows + n_cand, rows.begin() + n);
+  const bool forecast_was_ready = e->forecast_ready;  // its result lives in buffers this call does not write: it stays fetchable
   rc = check_launch_locked(e, n + n_cand, rows.data(), on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
   e->check_ready = false;  // the slot holds this call's rows (as with kt_affected_pods): a pending kt_check_launch is gone
+  e->forecast_ready = forecast_was_ready;
   if (rc != KT_OK) return rc;
   if ((rc = preempt_reconcile_locked(e, now_s, now_ns, s)) != KT_OK) return rc;
   const kt::AdmitPage pg{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
@@ -820,6 +823,132 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
   if (out_victims && e->preempt_m)
     KT_HIP(e, hipMemcpyAsync(out_victims, e->d_preempt_victims.p, (size_t)n * (size_t)e->preempt_m, hipMemcpyDeviceToHost, s));
   KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// forecast: the first instant at which a blocked pod passes (kt_kernels_forecast.hip)
+// ---------------------------------------------------------------------------------------------------
+// The caller holds the launch lock.  Every refusal comes before the check slot, the reconcile report or a result buffer is touched.
+static int32_t forecast_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns,
+                               int32_t on_equal, void* stream) {
+  if (n_inst < 1) return e->fail(KT_ERR_INVALID_ARGUMENT, "forecast: n_inst = %lld", (long long)n_inst);
+  if ((n > 0 && !pod_rows) || !inst_s || !inst_ns) return e->fail(KT_ERR_INVALID_ARGUMENT, "forecast: pod_rows / inst_s / inst_ns missing");
+  for (int64_t k = 0; k < n_inst; ++k) {
+    if (inst_ns[k] < 0 || inst_ns[k] >= 1000000000) return e->fail(KT_ERR_INVALID_ARGUMENT, "forecast: inst_ns[%lld] = %d", (long long)k, inst_ns[k]);
+    if (k && !(inst_s[k - 1] < inst_s[k] || (inst_s[k - 1] == inst_s[k] && inst_ns[k - 1] < inst_ns[k])))
+      return e->fail(KT_ERR_INVALID_ARGUMENT, "forecast: the instants are not strictly ascending at position %lld", (long long)k);
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "forecast: pod row %lld", (long long)pod_rows[i]);
+  const int32_t T = e->thr_rows_hi;  // (moved by throttle batches only, under this lock: ensure_ready below does not change it)
+  if ((double)n * (double)T > 2147483648.0)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "forecast: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  if ((double)n * (double)n_inst > 2147483648.0)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "forecast: n x n_inst = %lld x %lld exceeds 2^31 verdict bytes", (long long)n, (long long)n_inst);
+  if (e->incremental) return e->fail(KT_ERR_UNSUPPORTED, "forecast: not for KT_VARIANT_INCREMENTAL engines");
+  if (e->exchange_world > 1) return e->fail(KT_ERR_UNSUPPORTED, "forecast: the engine exchanges partials with %d ranks (one rank only)", e->exchange_world);
+  if (e->wide && e->req_sums_valid) return e->fail(KT_ERR_UNSUPPORTED, "forecast: `used` is wider than int64 (kt_forecast reads int64 sums)");
+  if (n == 0) {  // nothing is launched
+    e->forecast_ready = true, e->forecast_n = 0, e->forecast_m = n_inst;
+    return KT_OK;
+  }
+  KT_HIP(e, hipSetDevice(e->device));
+  hipStream_t s = pick_stream(e, stream);
+  // pod batches since the last aggregate may have pushed the sums beyond int64: found out here (the |request| sums kernel, when
+  // they are not known), before the check slot or any result buffer is touched
+  int32_t rc = ensure_ready(e, s);
+  if (rc == KT_OK) rc = request_sums_in_range(e, s);
+  if (rc != KT_OK) return rc;
+  if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "forecast: `used` is wider than int64 (kt_forecast reads int64 sums)");
+  e->forecast_ready = false;
+  const size_t ver = (size_t)n * (size_t)n_inst;
+  if (e->d_forecast_first.cap < (size_t)n || e->d_forecast_verdicts.cap < ver + 1 || e->d_forecast_inst_s.cap < (size_t)n_inst ||
+      e->d_forecast_inst_ns.cap < (size_t)n_inst) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_preempt_launch)
+    if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+    KT_HIP(e, e->d_forecast_first.reserve((size_t)n));
+    KT_HIP(e, e->d_forecast_verdicts.reserve(ver + 1));
+    KT_HIP(e, e->d_forecast_inst_s.reserve((size_t)n_inst));
+    KT_HIP(e, e->d_forecast_inst_ns.reserve((size_t)n_inst));
+  }
+  // the instants travel on the launch's stream, behind an earlier forecast's kernel; the caller's memory is not referenced after
+  // return (the synchronisation is the one behind the check's row copy, and one of the call's own for safety)
+  KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_s.p, inst_s, (size_t)n_inst * 8, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_ns.p, inst_ns, (size_t)n_inst * 4, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  // ONE check over the pods: which throttles affect which pod, and the error rows.  The preempt result lives in buffers this
+  // call does not write: it stays fetchable
+  const bool preempt_was_ready = e->preempt_ready;
+  rc = check_launch_locked(e, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e->check_ready = false;  // the slot holds this call's rows (as with kt_preempt_launch): a pending kt_check_launch is gone
+  e->preempt_ready = preempt_was_ready;
+  if (rc != KT_OK) return rc;
+  // the aggregate with exact contributor counts and the error bytes; the dry finalize runs at t_0
+  if ((rc = preempt_reconcile_locked(e, inst_s[0], inst_ns[0], s)) != KT_OK) return rc;
+  const kt::AdmitPage pg{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  kt::launch_forecast(pg, n, n_inst, e->d_rows.p, e->d_forecast_inst_s.p, e->d_forecast_inst_ns.p, T, on_equal != 0, e->d_status.p, e->d_summary.p,
+                      e->d_preempt_partial.p, e->d_out_error.p, e->d_forecast_first.p, e->d_forecast_verdicts.p, s);
+  KT_HIP(e, hipGetLastError());
+  e->last_stream = s;
+  e->forecast_ready = true, e->forecast_n = n, e->forecast_m = n_inst;
+  return KT_OK;
+}
+
+int32_t kt_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns,
+                           int32_t on_equal, void* stream) {
+  if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  return forecast_locked(e, n, pod_rows, n_inst, inst_s, inst_ns, on_equal, stream);
+}
+
+int32_t kt_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, uint8_t* out_verdicts) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (!e->forecast_ready) return e->fail(KT_ERR_NOT_READY, "kt_forecast_fetch before kt_forecast_launch");
+  if (n < 0 || n > e->forecast_n) return e->fail(KT_ERR_OUT_OF_RANGE, "n=%lld, the last forecast launch had %lld pods", (long long)n, (long long)e->forecast_n);
+  if (n == 0) return KT_OK;
+  hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
+  if (out_first) KT_HIP(e, hipMemcpyAsync(out_first, e->d_forecast_first.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (out_verdicts) KT_HIP(e, hipMemcpyAsync(out_verdicts, e->d_forecast_verdicts.p, (size_t)n * (size_t)e->forecast_m, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
+// Host-only: the instants in (from, until] at which some valid and responsible throttle's CalculateThreshold can change — every
+// parsed non-zero begin, and end + 1 ns for every parsed non-zero end: the first instant at which IsActive is false (at `end`
+// itself, the instant NextOverrideHappensIn reports, the override is still active)
+int32_t kt_override_instants(kt_engine* e, int64_t from_s, int32_t from_ns, int64_t until_s, int32_t until_ns, int64_t cap, int64_t* out_s,
+                             int32_t* out_ns, int64_t* out_total) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  if (cap < 0 || (cap > 0 && (!out_s || !out_ns)) || !out_total) return e->fail(KT_ERR_INVALID_ARGUMENT, "override_instants: cap = %lld, arrays missing", (long long)cap);
+  typedef std::pair<int64_t, int32_t> Inst;
+  const Inst from(from_s, from_ns), until(until_s, until_ns);
+  std::vector<Inst> v;
+  auto add = [&](int64_t s_, int32_t ns_) {
+    const Inst t(s_, ns_);
+    if (from < t && !(until < t)) v.push_back(t);
+  };
+  const uint32_t need = KT_THR_VALID | KT_THR_RESPONSIBLE;
+  for (int32_t t = 0; t < e->thr_rows_hi; ++t) {
+    const HostThrottle& h = e->thr[(size_t)t];
+    if ((h.flags & need) != need) continue;
+    for (const Override& ov : h.ovr) {
+      if (ov.flags & kt::kOvrParseError) continue;
+      if (!(ov.begin_s == kt::kZeroTimeS && ov.begin_ns == 0)) add(ov.begin_s, ov.begin_ns);
+      if (!(ov.end_s == kt::kZeroTimeS && ov.end_ns == 0)) {
+        if (ov.end_ns == 999999999) add(ov.end_s + 1, 0);
+        else add(ov.end_s, ov.end_ns + 1);
+      }
+    }
+  }
+  std::sort(v.begin(), v.end());
+  v.erase(std::unique(v.begin(), v.end()), v.end());
+  *out_total = (int64_t)v.size();
+  const int64_t w = std::min<int64_t>((int64_t)v.size(), cap);
+  for (int64_t k = 0; k < w; ++k) out_s[k] = v[(size_t)k].first, out_ns[k] = v[(size_t)k].second;
   return KT_OK;
 }
 

@@ -346,6 +346,14 @@ struct kt_engine {
   DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
   bool preempt_ready = false;
   int64_t preempt_n = 0, preempt_m = 0;
+  // the last kt_forecast_launch: first passing position per pod and the verdict bytes [n][n_inst], on the device until
+  // kt_forecast_fetch — buffers of their own: a pending forecast and a pending preempt result do not disturb each other;
+  // d_forecast_inst_*: the instants as the kernel reads them
+  DevBuf<int64_t> d_forecast_first, d_forecast_inst_s;
+  DevBuf<int32_t> d_forecast_inst_ns;
+  DevBuf<uint8_t> d_forecast_verdicts;
+  bool forecast_ready = false;
+  int64_t forecast_n = 0, forecast_m = 0;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;

@@ -128,6 +128,12 @@ size_t reprieve_ws_bytes(int T, int D, int64_t n, uint32_t lds_cap_limit);
 void launch_preempt_reprieve(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int T, bool on_equal, const uint8_t* status,
                              const unsigned long long* partial, const AmountTab& calc, const uint8_t* calc_updated, const uint8_t* error,
                              const int64_t* prefix, uint8_t* victims, void* ws, uint32_t lds_cap_limit, hipStream_t s);
+// the first instant at which a pod passes (kt_kernels_forecast.hip): one wave per pod, lane = instant position.  rows_dev [n];
+// inst_s / inst_ns [m] in device memory, strictly ascending; status / summary: ONE check over those rows; partial: aggregate rows
+// with exact per-name contributor counts; error: the error bytes of a dry finalize; first [n] and verdicts [n][m] out
+void launch_forecast(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, const int64_t* inst_s, const int32_t* inst_ns, int T,
+                     bool on_equal, const uint8_t* status, const uint64_t* summary, const unsigned long long* partial, const uint8_t* error,
+                     int64_t* first, uint8_t* verdicts, hipStream_t s);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

@@ -42,10 +42,11 @@ EXPORTS = [
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
-    "kt_preempt_reprieve_launch",
+    "kt_preempt_reprieve_launch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
+FORECAST_NONE = -1
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
 COUNTER_VIEW_BUILDS = 10
@@ -254,6 +255,10 @@ def lib():
                                         C.c_void_p]
         L.kt_preempt_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.kt_preempt_reprieve_launch.argtypes = L.kt_preempt_launch.argtypes
+        L.kt_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.kt_forecast_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.kt_override_instants.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -618,6 +623,44 @@ class Engine:
         are a minimal set."""
         (self.preempt_reprieve_launch if reprieve else self.preempt_launch)(pod_rows, cand_rows, now, on_equal)
         return self.preempt_fetch(len(pod_rows), len(cand_rows), want_victims)
+
+    # ---- forecast: the first instant at which a blocked pod passes
+    def forecast_launch(self, pod_rows, instants, on_equal=False, stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        inst_s = np.ascontiguousarray([int(t[0]) for t in instants], dtype=np.int64)
+        inst_ns = np.ascontiguousarray([int(t[1]) for t in instants], dtype=np.int32)
+        m = len(inst_s)
+        self._ck(lib().kt_forecast_launch(self._h, len(a), p if len(a) else None, m, inst_s.ctypes.data if m else None,
+                                          inst_ns.ctypes.data if m else None, int(on_equal), stream))
+
+    def forecast_fetch(self, n, n_inst, want_verdicts=True):
+        first = np.zeros(max(n, 1), np.int64)
+        flat = np.zeros(max(n * n_inst, 1), np.uint8) if want_verdicts else None
+        self._ck(lib().kt_forecast_fetch(self._h, n, first.ctypes.data, None if flat is None else flat.ctypes.data))
+        return first[:n], (None if flat is None else flat[:n * n_inst].reshape(n, n_inst))
+
+    def forecast(self, pod_rows, instants, on_equal=False, want_verdicts=True):
+        """kt_forecast_launch + kt_forecast_fetch: per pod the KT_VERDICT_* of PreFilter once every valid and responsible throttle
+        has been reconciled at each of the strictly ascending ``instants`` [(seconds, nanoseconds)] — each on the state as it is
+        now, not on top of the previous instant — and the first position whose verdict is Success (FORECAST_NONE: none) ->
+        (first int64 [n], verdicts uint8 [n][n_inst] or None).  A dry run: stored status and reserved amounts stay as they are."""
+        self.forecast_launch(pod_rows, instants, on_equal)
+        return self.forecast_fetch(len(pod_rows), len(instants), want_verdicts)
+
+    def override_instants(self, from_, until, cap=None):
+        """kt_override_instants: the sorted, distinct instants in (from_, until] at which some valid and responsible throttle's
+        CalculateThreshold can change (every override ``begin``, and ``end`` + 1 ns) -> ([(seconds, nanoseconds)], total).
+        ``cap``: at most so many (the earliest) are returned; None: all of them."""
+        total = C.c_int64(0)
+        args = (int(from_[0]), int(from_[1]), int(until[0]), int(until[1]))
+        if cap is None:
+            self._ck(lib().kt_override_instants(self._h, *args, 0, None, None, C.byref(total)))
+            cap = total.value
+        out_s, out_ns = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)
+        self._ck(lib().kt_override_instants(self._h, *args, int(cap), out_s.ctypes.data if cap else None, out_ns.ctypes.data if cap else None,
+                                            C.byref(total)))
+        k = min(int(cap), total.value)
+        return [(int(a), int(b)) for a, b in zip(out_s[:k], out_ns[:k])], total.value
 
     def fetch_reserved(self, rows=None) -> S.Amounts:
         rows = np.arange(self.throttle_rows(), dtype=np.int32) if rows is None else rows

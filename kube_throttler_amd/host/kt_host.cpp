@@ -5,7 +5,9 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cstdio>
 #include <cstring>
+#include <ctime>
 
 namespace kth {
 
@@ -1274,6 +1276,63 @@ PreemptResult KubeThrottler::Preempt(const std::string& pod_key, const std::vect
   out.none = prefix < 0;
   for (size_t j = 0; j < cand.size(); ++j)
     if (mask[j]) out.victims.push_back(candidate_keys[j]);
+  return out;
+}
+
+// When does this pod pass PreFilter: the override boundaries of the window from the engine's host copy of the specs
+// (kt_override_instants: every begin, and end + 1 ns — the first instant an override is no longer active), `now` in front, one
+// kt_forecast_launch + kt_forecast_fetch over them on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).
+RetryAfterResult KubeThrottler::RetryAfter(const std::string& pod_key, const std::string& now_rfc3339, int64_t horizon_seconds) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  RetryAfterResult out;
+  if (p.pages.size() > 1) {
+    out.error = "RetryAfter: the mirror runs on " + std::to_string(p.pages.size()) + " pages (more than " + std::to_string(p.D) +
+                " resource names); the forecast query has no paged form";
+    return out;
+  }
+  int64_t now_s;
+  int32_t now_ns;
+  if (!ParseRFC3339(now_rfc3339, &now_s, &now_ns, &out.error)) return out;
+  if (horizon_seconds < 0) {
+    out.error = "RetryAfter: horizon " + std::to_string(horizon_seconds) + " s";
+    return out;
+  }
+  const int64_t row = p.pod_rows.find(pod_key);
+  if (row < 0) {
+    out.error = "pod " + pod_key + " is not known to the plugin (OnPodAdd first)";
+    return out;
+  }
+  int64_t total = 0;
+  int32_t rc = kt_override_instants(p.e, now_s, now_ns, now_s + horizon_seconds, now_ns, 0, nullptr, nullptr, &total);
+  std::vector<int64_t> inst_s((size_t)total + 1);
+  std::vector<int32_t> inst_ns((size_t)total + 1);
+  inst_s[0] = now_s, inst_ns[0] = now_ns;
+  if (rc == KT_OK && total > 0)
+    rc = kt_override_instants(p.e, now_s, now_ns, now_s + horizon_seconds, now_ns, total, inst_s.data() + 1, inst_ns.data() + 1, &total);
+  const int64_t m = (int64_t)inst_s.size();
+  int64_t first = KT_FORECAST_NONE;
+  out.verdicts_at.assign((size_t)m, 0);
+  if (rc == KT_OK) rc = kt_forecast_launch(p.e, 1, &row, m, inst_s.data(), inst_ns.data(), /*isThrottledOnEqual=*/0, nullptr);
+  if (rc == KT_OK) rc = kt_forecast_fetch(p.e, 1, &first, out.verdicts_at.data());
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    out.verdicts_at.clear();
+    return out;
+  }
+  for (int64_t k = 0; k < m; ++k) out.instants.emplace_back(inst_s[(size_t)k], inst_ns[(size_t)k]);
+  out.has = first >= 0;
+  if (out.has) {
+    out.instantSec = inst_s[(size_t)first], out.instantNsec = inst_ns[(size_t)first];
+    const time_t tt = (time_t)out.instantSec;
+    struct tm g;
+    gmtime_r(&tt, &g);
+    char buf[64];
+    size_t n = strftime(buf, sizeof buf, "%Y-%m-%dT%H:%M:%S", &g);
+    if (out.instantNsec) n += (size_t)snprintf(buf + n, sizeof buf - n, ".%09d", out.instantNsec);
+    snprintf(buf + n, sizeof buf - n, "Z");
+    out.instant = buf;
+  }
   return out;
 }
 

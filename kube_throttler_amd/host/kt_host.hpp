@@ -166,6 +166,18 @@ struct PreemptResult {
   std::string error;                 // not empty: the call failed (unknown pod, a paged mirror, engine error)
 };
 
+// RetryAfter: the first instant at which a blocked pod passes PreFilter, among `now` and the override boundaries up to the horizon
+struct RetryAfterResult {
+  bool has = false;              // some instant of the window lets the pod through: `instant` is the first
+  int64_t instantSec = 0;        // the instant (Unix seconds, nanoseconds); == now: the pod passes against a fresh reconcile
+  int32_t instantNsec = 0;
+  std::string instant;           // ... as RFC3339 (UTC, with nanoseconds where they are not zero)
+  // the instants that were judged — now, then every override boundary in (now, now + horizon] — and the KT_VERDICT_* of each
+  std::vector<std::pair<int64_t, int32_t>> instants;
+  std::vector<uint8_t> verdicts_at;
+  std::string error;             // not empty: the call failed (unknown pod, a paged mirror, engine error)
+};
+
 // KubeThrottlerPluginArgs (pkg/scheduler_plugin/plugin_args.go:33-40) + engine sizing
 struct PluginArgs {
   std::string name;                 // throttler name (required)
@@ -232,6 +244,10 @@ class KubeThrottler {
   // The names that remain are a minimal set: with non-negative requests no single one of them can stay.
   PreemptResult Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys, const std::string& now_rfc3339,
                         bool reprieve = false);
+  // The first instant in [now, now + horizon] at which PreFilter(pod) is Success if every throttle were reconciled then
+  // (temporaryThresholdOverrides begin and end): kt_override_instants for the boundaries, ONE kt_forecast_launch over
+  // now ++ boundaries.  What a PreFilter rejection path asks to set a backoff.  A dry run; a mirror on several pages refuses.
+  RetryAfterResult RetryAfter(const std::string& pod_key, const std::string& now_rfc3339, int64_t horizon_seconds);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

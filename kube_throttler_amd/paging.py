@@ -468,6 +468,90 @@ def _reprieve(snap, ctx, affected, contributes, creq, req, eq, prefix, victims):
                 entry[2:] = [val, cnt, pods]
 
 
+# ---- forecast: the first instant at which a blocked pod passes (kt_forecast_launch), in closed form on a Snapshot ----
+def _instant(t):
+    return int(t[0]), int(t[1])
+
+
+def override_instants_of(snap, from_, until):
+    """kt_override_instants on a Snapshot (no GPU): the sorted, distinct instants in (from_, until] at which the
+    CalculateThreshold of some valid and responsible throttle can change — every parsed non-zero ``begin`` and, for every parsed
+    non-zero ``end``, the instant end + 1 ns: the first at which the override is no longer active (both ends are inclusive).
+    Overrides with a parse error contribute nothing -> [(seconds, nanoseconds)]."""
+    lo, hi = _instant(from_), _instant(until)
+    need = S.THR_VALID | S.THR_RESPONSIBLE
+    zero = (S.ZERO_TIME_S, 0)
+    out = set()
+    for t in range(snap.n_thr):
+        if (int(snap.thr_flags[t]) & need) != need:
+            continue
+        for o in range(int(snap.thr_ovr_off[t]), int(snap.thr_ovr_off[t + 1])):
+            if int(snap.ovr_flags[o]) & S.OVR_PARSE_ERROR:
+                continue
+            begin = (int(snap.ovr_begin_s[o]), int(snap.ovr_begin_ns[o]))
+            end = (int(snap.ovr_end_s[o]), int(snap.ovr_end_ns[o]))
+            if begin != zero:
+                out.add(begin)
+            if end != zero:
+                out.add((end[0] + 1, 0) if end[1] == 999_999_999 else (end[0], end[1] + 1))
+    return sorted(t for t in out if lo < t <= hi)
+
+
+def forecast_of(snap, pod_row, instants, on_equal=False, ctx=None):
+    """kt_forecast_launch for one pod, in closed form on a Snapshot (no GPU) -> (first, verdicts [len(instants)]).
+    verdicts[k]: the KT_VERDICT_* of PreFilter(pod) once every valid and responsible throttle has been reconciled at
+    ``instants[k]`` on the state as it is now (reserved amounts unchanged; a throttle whose reconcile is an error keeps its stored
+    status at every instant); first: the smallest k with Success, or -1.  `used` does not depend on the instant: ``ctx`` is
+    ``preempt_context``'s aggregate (any ``now``: only its sums, error marks and match lists are read).  Per throttle and instant:
+    CalculateThreshold (the first active override wins per name and for the count), replaced only where it differs from the
+    stored calculatedThreshold by value or in its messages, read by the check iff calculatedAt was non-zero or it is replaced."""
+    inst = [_instant(t) for t in instants]
+    ctx = preempt_context(snap, inst[0]) if ctx is None else ctx
+    p, eq, m = int(pod_row), bool(on_equal), len(inst)
+    if not (0 <= p < snap.n_pods) or not int(snap.pod_flags[p]) & S.POD_VALID:
+        return -1, [S.VERDICT_ERROR] * m
+    err, affected = affected_throttles(snap, p)
+    if err:
+        return -1, [S.VERDICT_ERROR] * m
+    req = {d: v for d, v in pod_requests(snap, p).items() if v != 0}
+    fails = [False] * m
+    for t in affected:
+        th = ctx["thr"][t]
+        f = int(snap.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+        if th["error"]:  # the stored status, at every instant
+            used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+            sth, sth_count = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+            flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+            bad = _amount_fails(1, sth_count, bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0,
+                                res_count is not None, res_count or 0, eq3, eq)
+            for d, v in req.items():
+                bad = bad or _amount_fails(v, sth.get(d), bool(flg >> d & 1), d in used, used.get(d, 0), d in res, res.get(d, 0), eq3, eq)
+            if bad:
+                fails = [True] * m
+                break
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        u_hc = pods > 0
+        stored = _amount_dict(snap.thr_calc, t, snap.D)
+        spec, spec_count = _amount_dict(snap.thr_spec, t, snap.D)
+        for k, at in enumerate(inst):
+            calc, cc, any_err = _calculated_threshold(snap, t, at)
+            fp = int(snap.thr_spec_msgs_fp[t]) if any_err else 0
+            replace = (calc, cc) != stored or int(snap.thr_status_msgs_fp[t]) != fp
+            rd, rd_count = (calc, cc) if (f & S.THR_CALC_AT_NONZERO) or replace else (spec, spec_count)
+            bad = _amount_fails(1, rd_count, cc is not None and u_hc and pods >= cc, u_hc, pods, res_count is not None, res_count or 0, eq3, eq)
+            for d, v in req.items():
+                u_pr = cnt.get(d, 0) > 0
+                cv = calc.get(d)
+                bad = bad or _amount_fails(v, rd.get(d), cv is not None and u_pr and val.get(d, 0) >= cv, u_pr, val.get(d, 0), d in res,
+                                           res.get(d, 0), eq3, eq)
+            fails[k] = fails[k] or bad
+    verdicts_ = [S.VERDICT_BLOCK if b else S.VERDICT_ALLOW for b in fails]
+    return next((k for k in range(m) if not fails[k]), -1), verdicts_
+
+
 class PagedEngine:
     """One HIP engine per page of a ``ClusterState.build_pages()`` result; reconcile and check run on every page (the
     selector scan is repeated per page: the price of more than 16 resource names) and come back combined."""
@@ -526,6 +610,14 @@ class PagedEngine:
         verdicts of a dry-run admission of ``[pod] * cap`` with every page's names -> (copies [n], limiting throttle row [n],
         -1 when all ``cap`` are admitted).  Nothing is reserved."""
         return E.paged_headroom(self.engines, rows, cap, on_equal=on_equal)
+
+    def forecast(self, pod_rows, instants, on_equal=False, want_verdicts=True):
+        """kt_forecast_launch through the one engine of a cluster that fits a page; the forecast has no paged form (more than
+        KT_MAX_DIMS resource names): refused with KT_ERR_UNSUPPORTED, nothing is launched."""
+        if len(self.engines) != 1:
+            raise E.EngineError(-7, f"forecast: the cluster runs on {len(self.engines)} pages (more than {S.KT_MAX_DIMS} resource "
+                                    "names); the forecast query has no paged form")
+        return self.engines[0].forecast(pod_rows, instants, on_equal, want_verdicts)
 
     def fetch_reserved(self) -> list:
         """Reserved amounts per throttle row, put together by resource NAME from the pages (like combine_reconcile):
