@@ -517,6 +517,8 @@ const char* kt_kernel_name(kt_engine* e, int32_t kernel);
                                       plain fold — a negative request, sums beyond int64, fields that do not fit) */
 #define KT_COUNTER_VIEW_BUILDS 10   /* builds of a scan view so far, the aggregate's or the check sweep's (a pod event that fits the
                                       views is patched into them in place and does not count) */
+#define KT_COUNTER_AGG_WORKGROUPS 11 /* workgroups (= slabs) of the last full aggregate scan's launch: up to 256 at one workgroup per CU,
+                                      up to 512 in the two-per-CU form of single-chunk packed scans (KT_AGG_ONE_PER_CU=1 keeps one) */
 int64_t kt_counter(kt_engine* e, int32_t which);
 /* ---- More resource names than one engine has dimensions (KT_MAX_DIMS): PAGES.  The reference sums and compares any resource
  *      name (pkg/resourcelist/resourcelist.go:27-54, resource_amount.go:127-159).  The host builds the same cluster once per

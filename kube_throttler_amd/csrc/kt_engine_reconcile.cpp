@@ -229,6 +229,16 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
   // pod events appended records behind the listed ones; a scan that will gather through the row list instead of streaming
   // the view cannot tell them from the list's zeroed padding: list again
   if (cv.valid && cv.extra && !(!e->sw[kSw_NO_SCAN_VIEW] && (by_ns || e->dindex.n_chunks == 1))) cv.valid = false;
+  // Two workgroups per CU (kt_aggregate_bitmap_one): single-chunk programs whose packed scan needs nothing that form drops.  The
+  // view's words are planned for it — each workgroup scans half as many pods — so a view planned that way is built again when the
+  // form has become impossible (an overflow pod arrived)
+  // (two_view: the scan will be a packed one over a single chunk's view at all; two_launch: what the launch will say of itself —
+  //  aggregate_two_per_cu_fits is the one list of the form's conditions, asked here and by launch_aggregate_indexed)
+  const bool two_view = !e->sw[kSw_NO_SCAN_VIEW] && !e->sw[kSw_NO_PACK] && e->cfg.kernel_variant != 1 && !by_ns && !e->incremental && !e->wide &&
+                        e->dindex.n_chunks == 1;
+  const kt::AggTwoLaunch two_launch{!e->sw[kSw_AGG_ONE_PER_CU], e->sw[kSw_AGG_SMALL_WINDOW], e->n_overflow != 0, e->pods.LA};
+  if (cv.valid && cv.pack.headroom >= (uint32_t)kt::kPackHeadroomBitsTwo && !(two_view && kt::aggregate_two_per_cu_fits(e->dindex, cv.pack, two_launch)))
+    cv.valid = false;
   if (e->cfg.kernel_variant != 1 && (!cv.valid || cv.by_ns != by_ns)) {  // pods changed since the last scan: which rows does a reconcile look at
     if (e->last_stream && e->last_stream != s) KT_HIP(e, hipStreamSynchronize(e->last_stream));
     const ViewSpec spec{/*countable_only=*/true, by_ns, kt::aggregate_blocks, e->cfg.pod_capacity, /*requests=*/true};
@@ -249,6 +259,15 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
       if (cv.range_G) slab_pods = std::max<uint64_t>(slab_pods, (uint64_t)kt::wg_range_cap((int64_t)cv.n, cv.range_G) + 64u);
       cv.pack = kt::make_pack_plan(e->D, e->max_abs, e->or_abs, e->neg_seen, slab_pods, /*pad_odd=*/true, kt::pack_max_words(e->D));
       if (cv.pack.nw && cv.pack.rec_bytes > e->dindex.cut_thr_bytes) cv.pack = kt::PackPlan();  // the slab areas hold records of that size
+      if (two_view && cv.pack.nw) {
+        // the smaller record where the engine's value ranges have one: at most three words + the zero-key word (32 bytes, no
+        // padding unit: the kernel skews its table instead), 9 bits of headroom for 512 slabs, fields sized for the pods one of
+        // 512 workgroups scans.  No such plan, or LDS / the slab area do not take it twice: the launch stays one per CU.
+        const uint64_t slab_pods2 = kt::aggregate_slab_pods(cap, kt::aggregate_blocks(cap, kt::kAggWorkgroupsTwo));
+        const kt::PackPlan two = kt::make_pack_plan(e->D, e->max_abs, e->or_abs, e->neg_seen, slab_pods2, /*pad_odd=*/false, /*max_words=*/3,
+                                                    kt::kPackHeadroomBitsTwo);
+        if (two.nw && kt::aggregate_two_per_cu_fits(e->dindex, two, two_launch)) cv.pack = two;
+      }
     }
     if (!cv.pack.nw && kt::agg_rec_bytes(e->D, e->incremental) > e->dindex.cut_thr_bytes) {
       // the plain fold is coming and the chunks were cut for the packed fold's records: cut again, for plain ones (once —
@@ -284,8 +303,9 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
       } else {
         kt::AggScan sc;
         sc.n = (int64_t)cv.n, sc.rows = cv.rows.p, sc.counts = e->incremental, sc.nonneg = !e->neg_seen;
-        sc.overflow_pods = e->n_overflow != 0;
-        sc.small_window = e->sw[kSw_AGG_SMALL_WINDOW];
+        sc.overflow_pods = two_launch.overflow_pods;
+        sc.small_window = two_launch.small_window;
+        sc.one_per_cu = !two_launch.enabled;
         sc.limb = limb;
         // contiguous tile ranges over the scan view; with a single chunk the order of the list does not matter
         sc.by_ns = !e->sw[kSw_NO_SCAN_VIEW] && (cv.by_ns || e->dindex.n_chunks == 1);
@@ -299,8 +319,10 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
         sc.defer_reduce = defer && sc.pk != nullptr;
         const char* k = kt::launch_aggregate_indexed(e->pods, sc, e->sp, e->d_sp.p, e->dindex, target, e->d_slab.p, s,
                                                      pass == 0 ? std::function<void()>(after_scan) : std::function<void()>());
+        if (!k && sc.refused) return e->fail(KT_ERR_OUT_OF_RANGE, "aggregate launch refused: %s", sc.refused);
         if (!k) return e->fail(KT_ERR_UNSUPPORTED, "a chunk of the selector index exceeds the aggregate kernel's LDS budget (use kernel_variant 1)");
         e->last_kernel[KT_KERNEL_AGGREGATE] = k;
+        e->ctr_agg_workgroups.store((int64_t)sc.launched_blocks, std::memory_order_relaxed);
         e->ctr_packed_words.store(sc.launched_packed ? (int64_t)cv.pack.nw : 0, std::memory_order_relaxed);
         if (sc.defer_reduce && sc.launched_packed) e->fused_pending = true, e->fused_nb = sc.launched_blocks, e->fused_epoch = sc.epoch, e->fused_pack = cv.pack;
         e->last_kernel[KT_KERNEL_REDUCE] = e->fused_pending ? "(in kt_reduce_finalize_packed)" : sc.launched_packed ? "kt_reduce_packed_slabs" : "kt_reduce_bitmap_slabs";
@@ -329,6 +351,7 @@ int32_t delta_scan(kt_engine* e, int64_t n, const int64_t* rows_dev, int64_t row
   int32_t rc = slab_tags(e, sc, s);
   if (rc != KT_OK) return rc;
   const char* k = kt::launch_aggregate_indexed(e->pods, sc, e->sp, e->d_sp.p, e->dindex, e->d_agg.p, e->d_slab.p, s, nullptr);
+  if (!k && sc.refused) return e->fail(KT_ERR_OUT_OF_RANGE, "aggregate launch refused: %s", sc.refused);
   if (!k) return e->fail(KT_ERR_UNSUPPORTED, "a chunk of the selector index exceeds the aggregate kernel's LDS budget");
   KT_HIP(e, hipGetLastError());
   return KT_OK;

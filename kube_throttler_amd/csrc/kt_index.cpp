@@ -1192,9 +1192,11 @@ struct Cutter {
         oo += align16(bytes[k]);
       }
       ch.img_off = (uint32_t)img0, ch.img_bytes = (uint32_t)o;
-      ch.slab_off = (uint32_t)(slab_run / 16);  // one table per (chunk, workgroup), 256 workgroups at most
-      // ... or 512 workgroups with packed records of half the size (PackPlan): their rounding to 16 bytes needs the slack
-      slab_run += 256ull * (((uint64_t)ch.n_thr * thr_bytes + 15) & ~15ull) + 8192ull;
+      // one table per (chunk, workgroup): kAggWorkgroups tables of records of the size the chunks are cut for (thr_bytes: plain
+      // records, or the packed fold's where a program of several chunks was cut for those).  Nothing else is promised: a launch
+      // with other records or more workgroups checks its slabs against this area (launch_aggregate_indexed)
+      ch.slab_off = (uint32_t)(slab_run / 16);
+      slab_run += agg_slab_area_bytes(ch.n_thr, thr_bytes);
       mx.lds = std::max(mx.lds, (size_t)ch.lds_bytes), mx.thr = std::max(mx.thr, (size_t)ch.n_thr), mx.nw = std::max(mx.nw, (size_t)nw);
       out.bm_max_lds = std::max(out.bm_max_lds, ch.lds_bytes);
       out.bm_max_thr = std::max(out.bm_max_thr, ch.n_thr);
@@ -1333,12 +1335,12 @@ void release_index(IndexDev& d) {
 }
 
 PackPlan make_pack_plan(int D, const unsigned __int128* max_abs, const uint64_t* or_abs, bool neg_seen, uint64_t n_slab_pods, bool pad_odd,
-                        uint32_t max_words) {
+                        uint32_t max_words, int headroom_bits) {
   PackPlan pk;
-  if (neg_seen || D < 1 || D > 16 || n_slab_pods == 0) return pk;
+  if (neg_seen || D < 1 || D > 16 || n_slab_pods == 0 || headroom_bits < 1 || headroom_bits > 16) return pk;
   const int MW = (int)std::min<uint32_t>(max_words ? max_words : 1u, kPackMaxWords);
   auto bitlen = [](unsigned __int128 x) { int b = 0; while (x) ++b, x >>= 1; return b; };
-  constexpr int H = kPackHeadroomBits;
+  const int H = headroom_bits;
   // fields in placement order per word: dimension (-1: the pod count), position, width
   struct F { int d; uint32_t pos, w; };
   std::vector<F> fields[kPackMaxWords];
@@ -1375,6 +1377,7 @@ PackPlan make_pack_plan(int D, const unsigned __int128* max_abs, const uint64_t*
     }
   }
   pk.nw = nw;
+  pk.headroom = (uint32_t)H;
   pk.stride = nw <= 2 ? 2u : nw <= 4 ? 4u : 8u;
   uint32_t units = nw + 1u;
   if (pad_odd && !(units & 1u)) ++units;

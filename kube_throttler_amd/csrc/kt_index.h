@@ -202,18 +202,20 @@ struct PackPlan {
                            // request-key masks of pods that carry a key with the value 0 (+ padding)
   uint8_t word[16] = {0}, pos[16] = {0}, width[16] = {0}, shift[16] = {0};
   uint8_t cnt_width = 0;   // the pod count sits in word 0 from bit 0
-  // Summing whole words over the slabs (kPackHeadroomBits: up to 256 of them) without taking the fields apart first:
+  // Summing whole words over the slabs (up to 2^headroom of them) without taking the fields apart first:
   // the TOP field of a word (from bit top_pos[k] up) is shifted out and summed by itself; the fields below it alternate
   // between two classes (even[k] = mask of the 1st, 3rd, ... field of word k), and every field is at least
-  // kPackHeadroomBits wide — so inside `word & even[k]` (and `word & low[k] & ~even[k]`, low[k] = bits below the top
-  // field) every field has that many zero bits above it, and the sum of 256 such words carries nowhere.  desc[d] /
+  // `headroom` bits wide — so inside `word & even[k]` (and `word & low[k] & ~even[k]`, low[k] = bits below the top
+  // field) every field has that many zero bits above it, and the sum of 2^headroom such words carries nowhere.  desc[d] /
   // cnt_desc: where the lane of dimension d / the pod count is found afterwards (pack_desc).
   uint64_t even[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint8_t top_pos[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t desc[16] = {0};
   uint32_t cnt_desc = 0;
+  uint32_t headroom = 0;   // zero bits above every field of a class: the plan holds for sums over up to 2^headroom slabs (8 or 9)
 };
-constexpr int kPackHeadroomBits = 8;
+constexpr int kPackHeadroomBits = 8;      // the plans of launches with one workgroup per CU
+constexpr int kPackHeadroomBitsTwo = 9;   // ... and of the two-per-CU form of the packed aggregate (up to 512 slabs)
 constexpr uint32_t kPackMaxWords = 8;
 // What an engine of D dimensions asks of the packed fold: up to 4 words at D <= 8 (every fold form takes those — 40-byte records
 // at most, half of the plain 80), up to 8 beyond (kt_aggregate_bitmap's NW = 8 instantiations: 72-byte records against 144)
@@ -228,9 +230,11 @@ __host__ __device__ inline uint32_t pack_desc(uint32_t word, uint32_t cls, uint3
 }
 // or_abs[d]: OR of every |request| fed for dimension d (its trailing zeros are common to all of them);
 // pad_odd: pad the record to an odd number of 8-byte words (LDS bank spread) instead of the smallest size
-// max_words: the most words the caller's fold takes (4: the fused sweep's and the plain instantiations; 8: kt_aggregate_bitmap's NW = 8)
+// max_words: the most words the caller's fold takes (4: the fused sweep's and the plain instantiations; 8: kt_aggregate_bitmap's NW = 8;
+//            3: the two-per-CU form, whose records are 32 bytes at most)
+// headroom_bits: log2 of the most slabs the reduction sums (PackPlan::headroom)
 PackPlan make_pack_plan(int D, const unsigned __int128* max_abs, const uint64_t* or_abs, bool neg_seen, uint64_t n_slab_pods, bool pad_odd,
-                        uint32_t max_words = kPackMaxWords);
+                        uint32_t max_words = kPackMaxWords, int headroom_bits = kPackHeadroomBits);
 
 // what kt_patch_scan_views (kt_kernels.hip) needs of the scan views a pod event batch is applied to in place
 struct ViewPatch {
@@ -350,14 +354,39 @@ struct AggScan {
   int limb = 0;                  // wide sums: the limb of every request this scan adds (limb_of, kt_device.h)
   bool small_window = false;     // test switch: fold through rank windows of 64 records whatever fits (kt_kernels_aggregate.hip)
   bool defer_reduce = false;     // packed scans: leave the slabs as they are — kt_reduce_finalize_packed takes them from there
+  bool one_per_cu = false;       // keep the launch at one workgroup per CU whatever would fit twice (KT_AGG_ONE_PER_CU)
   mutable int launched_blocks = 0;  // out: workgroups (= slabs per chunk) of the scan launch
   mutable bool launched_packed = false;
+  mutable const char* refused = nullptr;  // out: why launch_aggregate_indexed returned nullptr, where it is not the LDS budget
 };
-constexpr uint32_t kSlabTagStride = 256;  // workgroups an aggregate launch may have (one per CU)
-// workgroups of an aggregate launch over n listed pods, and the most pods one of them scans (the packed fields are sized
-// for it)
+// The most workgroups (= slabs per chunk) of an aggregate launch: one per CU, or two in the single-chunk two-per-CU form of the
+// packed fold.  The slab tags, the slab areas and the grids all take their limit from these.
+constexpr int kAggWorkgroups = 256, kAggWorkgroupsTwo = 512;
+constexpr uint32_t kSlabTagStride = kAggWorkgroupsTwo;
+// A chunk's slab area: one table of plain-cut records per workgroup of a one-per-CU launch, and some slack for the rounding of
+// other record sizes to 16 bytes.  A launch with other records or more workgroups runs only where its slabs fit this
+// (launch_aggregate_indexed checks): 512 workgroups with 32-byte packed records fit the area cut for 80-byte plain ones.
+inline uint64_t agg_slab_area_bytes(uint32_t n_thr, uint32_t thr_bytes) {
+  return (uint64_t)kAggWorkgroups * (((uint64_t)n_thr * thr_bytes + 15) & ~15ull) + 8192ull;
+}
+// workgroups of an aggregate launch over n listed pods (at most max_wg; kAggWorkgroups when not given), and the most pods one
+// of them scans (the packed fields are sized for it)
 int aggregate_blocks(int64_t n_rows);
+int aggregate_blocks(int64_t n_rows, int max_wg);
 uint64_t aggregate_slab_pods(int64_t n_rows, int blocks);
+// Can a single-chunk packed scan with plan pk run two workgroups per CU (kt_aggregate_bitmap_one)?  The ONE list of that form's
+// conditions: the engine asks it when it plans the pack (aggregate_locked), launch_aggregate_indexed when it dispatches, both
+// with the same AggTwoLaunch — so a view planned for the form is never handed to a launch that cannot take it.  The form is
+// switched on, nothing asks for what it drops (rank windows of the test switch, overflow pods, more than 8 atom slots, a slow
+// list, `slow` term shapes, runs that span words, five-key terms), the plan is one of at most three words with 9 bits of
+// headroom, two LDS footprints fit one CU and 512 slabs fit the chunk's slab area.
+struct AggTwoLaunch {
+  bool enabled;        // the engine's switches let the form run
+  bool small_window;   // AggScan::small_window
+  bool overflow_pods;  // AggScan::overflow_pods
+  int pod_LA;          // PodTable::LA
+};
+bool aggregate_two_per_cu_fits(const IndexDev& ix, const PackPlan& pk, const AggTwoLaunch& launch);
 // sp_dev: device-resident copy of sp.  Both return the symbol of the scan kernel they dispatched, nullptr when a chunk
 // does not fit the kernel's LDS.  after_scan (nullable) is invoked on the host right after the scan kernel is enqueued
 // and before the slab reduction kernel — the engine uses it to bracket the two kernels with separate timing events.

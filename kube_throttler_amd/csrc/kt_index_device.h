@@ -89,50 +89,65 @@ __device__ inline uint32_t walk_slow_mem(const SelProgram& sp, int t, const uint
 //   * lane = unit, wave = slab class: wave w reads the tile out of slabs w, w + 16, ... (at most 256 slabs: sixteen loads
 //     per lane, issued as one batch) — every load instruction of a wave covers 512 contiguous bytes, the slab area is read
 //     exactly once and fully coalesced (one wave per record with lane = slab, the first version of this reduction, moved
-//     a cache line per 8-byte word: ~80 MB through L2 for 10 MB of slabs);
+//     a cache line per 8-byte word: ~80 MB through L2 for 10 MB of slabs).  Behind the two-per-CU scan (at most 512 slabs)
+//     the tile is half as wide and the halves of a wave split the wave's slabs: still sixteen loads per lane in one batch,
+//     2 x 256 contiguous bytes per load instruction (RecSlabLoads<32>);
 //   * the words are never taken apart per slab: every word is split into its top field (shifted down) and the two
-//     classes of the fields below it (PackPlan::even — every field then has kPackHeadroomBits of zeros above it) and
+//     classes of the fields below it (PackPlan::even — every field then has PackPlan::headroom zero bits above it) and
 //     summed whole; the unit behind the words is the OR of the key masks of pods that carry a key with the value 0;
 //   * the sixteen waves meet in LDS: tot[unit][class].
 // Slabs a namespace-ordered scan left alone (multi-chunk programs: most of them) are skipped by their tags, wave-uniformly.
 // packed_field() then lets the lane of (record, dimension) cut its total out of tot — no loop over dimensions anywhere.
 constexpr int kRecBlock = 1024, kRecWaves = kRecBlock / 64, kRecTileUnits = 64;
-constexpr int kMaxSlabsPerRecord = 1 << kPackHeadroomBits;
-static_assert(kMaxSlabsPerRecord == 16 * kRecWaves, "sixteen slabs per wave");
 struct RecSumsLds {
   unsigned long long red[kRecWaves][kRecTileUnits][kPackClasses];
   unsigned long long tot[kRecTileUnits][kPackClasses];
 };
 // Three steps, so that a caller can place its own loads between them (vmcnt counts in order):
 //   record_slabs_live   which of this wave's slabs this launch spilled (tag loads: multi-chunk programs only)
-//   record_slabs_issue  the sixteen loads of this lane's unit.  row0: the tile's first byte in slab 0; n_units: units of
-//                       the tile that exist (whole records)
+//   record_slabs_issue  the sixteen loads of this lane's unit, one batch.  row0: the tile's first byte in slab 0; n_units: units
+//                       of the tile that exist (whole records)
 //   block_record_sums   class sums, the meeting in LDS (two barriers: every thread of the block must call)
+// NL: slabs per wave — 16 (up to 256 slabs: one workgroup per CU), or 32 (up to 512: the two-per-CU scan).  With 32 the tile is
+// HALF as wide (32 units) and the two halves of a wave take the even and the odd of the wave's 32 slabs: a lane still issues
+// sixteen loads as one batch, a block still reads about as many bytes as it does of 256 slabs, and twice as many blocks share
+// the slab area.  (Thirty-two loads per lane over 64-unit tiles would leave 63 blocks with 260 KB each at 1k throttles — a
+// quarter of the CUs — and 32 live 64-bit values per lane on the finalizing waves.)
+template <int NL>
 struct RecSlabLoads {
-  uint32_t live;  // bit i: slab (wave + 16 i) was spilled by this launch
+  static_assert(NL == 16 || NL == 32, "sixteen or thirty-two slabs per wave");
+  static constexpr uint32_t kHalves = NL / 16, kTileUnits = kRecTileUnits / kHalves;
+  uint32_t live;  // bit j: slab (wave + 16 j) was spilled by this launch
   unsigned long long v[16];
 };
-__device__ __forceinline__ void record_slabs_live(int n_slabs, const uint32_t* tag, uint32_t epoch, int check_tags, RecSlabLoads& sl) {
+template <int NL>
+__device__ __forceinline__ void record_slabs_live(int n_slabs, const uint32_t* tag, uint32_t epoch, int check_tags, RecSlabLoads<NL>& sl) {
   const uint32_t lane = threadIdx.x & 63u, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int s = (int)(w + 16u * lane);
-  bool ok = lane < 16u && s < n_slabs;
+  bool ok = lane < (uint32_t)NL && s < n_slabs;
   if (ok && check_tags) ok = tag[s] == epoch;
   sl.live = (uint32_t)__ballot(ok);
 }
-__device__ __forceinline__ void record_slabs_issue(const unsigned char* row0, size_t pitch, uint32_t n_units, RecSlabLoads& sl) {
+template <int NL>
+__device__ __forceinline__ void record_slabs_issue(const unsigned char* row0, size_t pitch, uint32_t n_units, RecSlabLoads<NL>& sl) {
+  constexpr uint32_t H = RecSlabLoads<NL>::kHalves, TU = RecSlabLoads<NL>::kTileUnits;
   const uint32_t lane = threadIdx.x & 63u, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const bool mine = lane < n_units;
-  const unsigned char* q = row0 + (size_t)w * pitch + (size_t)lane * 8u;
+  const uint32_t u = lane & (TU - 1u), h = lane / TU;  // this lane's unit of the tile; its half takes slabs wave + 16 (H i + h)
+  const bool mine = u < n_units;
+  const unsigned char* q = row0 + (size_t)(w + 16u * h) * pitch + (size_t)u * 8u;
+  const uint32_t live = sl.live >> h;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     sl.v[i] = 0ull;
-    if (mine && ((sl.live >> i) & 1u)) sl.v[i] = *(const unsigned long long*)(q + (size_t)(16 * i) * pitch);
+    if (mine && ((live >> (H * i)) & 1u)) sl.v[i] = *(const unsigned long long*)(q + (size_t)(16 * H * i) * pitch);
   }
 }
-__device__ __forceinline__ void block_record_sums(const RecSlabLoads& sl, const PackPlan& pk, RecSumsLds& lds) {
+template <int NL>
+__device__ __forceinline__ void block_record_sums(const RecSlabLoads<NL>& sl, const PackPlan& pk, RecSumsLds& lds) {
+  constexpr uint32_t H = RecSlabLoads<NL>::kHalves, TU = RecSlabLoads<NL>::kTileUnits;
   const uint32_t x = threadIdx.x, lane = x & 63u, w = __builtin_amdgcn_readfirstlane(x >> 6);
   const uint32_t units = pk.rec_bytes >> 3, nw = pk.nw;
-  const uint32_t k = lane % units;  // what this unit is: word k of its record, the key-mask unit (k == nw), padding
+  const uint32_t k = (lane & (TU - 1u)) % units;  // what this unit is: word k of its record, the key-mask unit (k == nw), padding
   // this lane's word: mask of its even fields, of everything below its top field, position of the top field
   // (key-mask unit, padding: everything in class 0)
   unsigned long long ev = ~0ull, low = ~0ull;
@@ -152,15 +167,17 @@ __device__ __forceinline__ void block_record_sums(const RecSlabLoads& sl, const 
   lds.red[w][lane][1] = b;
   lds.red[w][lane][2] = word ? c : 0ull;
   __syncthreads();
-  if (x < (uint32_t)(kPackClasses * kRecTileUnits)) {
+  if (x < (uint32_t)kPackClasses * TU) {
     const uint32_t u = x / kPackClasses, cl = x % kPackClasses;
     const bool is_or = u % units == nw;
     unsigned long long t = 0ull;
 #pragma unroll
-    for (int ww = 0; ww < kRecWaves; ++ww) {
-      const unsigned long long r = lds.red[ww][u][cl];
-      t = is_or ? (t | r) : t + r;
-    }
+    for (int ww = 0; ww < kRecWaves; ++ww)
+#pragma unroll
+      for (uint32_t hh = 0; hh < H; ++hh) {
+        const unsigned long long r = lds.red[ww][hh * TU + u][cl];
+        t = is_or ? (t | r) : t + r;
+      }
     lds.tot[u][cl] = t;
   }
   __syncthreads();

@@ -145,8 +145,9 @@ __device__ __attribute__((noinline)) void agg_walk_without_rank(const SelProgram
 //     ds_add_u64 where the plain fold issues one per non-zero dimension plus the pod count; the record is nw words + the
 //     OR of the key masks of pods that carry a key with the value 0.  Full scans over the scan view only (no counts mode,
 //     no negative requests, sign +1).
-// (One workgroup per CU: two packed ones fit when the record is squeezed to 32 bytes, but the 64-VGPR form spills and the
-//  32-byte stride lands 8 records on one bank group — measured 33 us against 24 us at 1M x 1k.)
+// (One workgroup per CU.  THIS kernel compiled for 64 VGPRs spills half of its live state, and a plain table of 32-byte
+//  records lands eight records on one bank group — 33 us against 24 us at 1M x 1k when that was tried.  Single-chunk packed
+//  scans run two per CU through a body of their own instead: kt_aggregate_bitmap_one, below.)
 // WIN: the table holds a WINDOW of the chunk's records at a time (BmAggArgs::win_recs) and the tiles are scanned once per window;
 //      its own instantiation, so that the kernels whose tables fit (every BASELINE configuration) do not pay the window test of
 //      every fold step — measured as one loop with a run-time window: aggregate 0.458 -> 0.481 ms on the configs[4] shard.
@@ -477,6 +478,193 @@ __global__ __launch_bounds__(kBlockIx) void kt_aggregate_bitmap(const BmAggArgs 
   }
 }
 
+// kt_aggregate_bitmap_one — the packed fold of kt_aggregate_bitmap for programs of ONE chunk, two workgroups per CU (8 waves per
+// SIMD, 64 VGPRs), as kt_check_bitmap's ONE form is for the sweep.  At 1M pods x 1k throttles the scan is a chain of dependent
+// trips to memory per round of tiles: 9 375 tiles over 254 workgroups of 16 waves are three rounds per wave, over 508 workgroups
+// two.  A body of its own — the generic kernel compiled for 64 VGPRs spills half of its live state:
+//   kept    : one chunk, the scan view streamed in list order (contiguous tile ranges per workgroup), the packed fold with the
+//             word queue, records of up to three words + the zero-key word (32 bytes: two tables fit beside two images);
+//   dropped : the chunk loop, planned ranges and the tile counter, slab tags, rank windows, the plain fold, counts / sign /
+//             limbs, the slow list, `slow` term shapes and overflow pods (no pod row, no raw labels: the record is all a lane
+//             needs) — launch_aggregate_indexed dispatches this form only where none of that is asked for.
+// 32-byte records put word 0 of eight consecutive records on eight bank pairs and nothing in between, so the table is SKEWED:
+// 8 bytes of padding after every eight records (a.skew) — word 0 of 64 consecutive records then covers all 32 bank pairs, as the
+// 40-byte records of the one-per-CU form do.  The spill takes the skew out again: the slab is the plain array of records.
+struct BmAggOneArgs {
+  const uint64_t* v_meta;  // the scan view: record j = meta word, atom row, packed request words
+  const uint16_t* v_latom;
+  const uint64_t* v_pk;
+  unsigned char* slab;     // this chunk's slab area
+  BmIndexArgs ix;
+  BmChunk ch;              // the chunk's descriptor by value
+  uint32_t n_rows, tpb;    // records of the view; tiles per workgroup
+  uint32_t off_rank, off_tab, off_seg;
+  uint32_t tab_bytes;      // the skewed table
+  uint32_t pk_nw, pk_stride, pk_rec, skew;
+};
+__device__ __forceinline__ uint32_t agg_one_rec_off(uint32_t r, uint32_t rec, uint32_t skew) { return __umul24(r, rec) + (skew ? (r >> 3) << 3 : 0u); }
+
+template <bool VETO, int NEED>
+__global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmAggOneArgs a) {
+  // (the word queue: four words beside the simple scan, three beside the rich one — its veto plane and 2-bit counters take the
+  //  registers of the fourth: 20 B of scratch with it)
+  constexpr int LA = 8, NW = 3, kWq = VETO ? 3 : 4;
+  KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const uint32_t n_rows = a.n_rows;
+  const uint32_t n_wtiles = (n_rows + kWave - 1u) / kWave;
+  // (a workgroup without tiles still spills its zeroed table: the reduction reads every launched workgroup's slab)
+  const uint32_t t_lo = min(blockIdx.x * a.tpb, n_wtiles), t_hi = min(t_lo + a.tpb, n_wtiles);
+  const BmChunk& ch = a.ch;
+  const uint32_t rec = a.pk_rec, skew = a.skew, pk_nw = a.pk_nw;
+  KT_LDS const uint16_t* trank = (KT_LDS const uint16_t*)(lds + a.off_rank);
+  KT_LDS unsigned char* tab = lds + a.off_tab;
+  struct Rec {
+    uint64_t meta;
+    u32x4 raw;
+    unsigned long long pw[NW];
+  };
+  auto fetch_tile = [&](uint32_t wt) {  // always from valid addresses: lanes past the end re-read the last record and are off
+    Rec r;
+    const uint32_t ic = min(wt * kWave + lane, n_rows - 1u);
+    r.meta = a.v_meta[ic];
+    r.raw = *(const u32x4*)(a.v_latom + (uint64_t)ic * LA);
+    const u64x2* q = (const u64x2*)(a.v_pk + (uint64_t)ic * a.pk_stride);
+    const u64x2 q0 = q[0];
+    r.pw[0] = q0.x, r.pw[1] = q0.y, r.pw[2] = 0ull;
+    if (a.pk_stride > 2u) r.pw[2] = q[1].x;
+    return r;
+  };
+  // ---- prologue: the table zeroed, image + ranks in as one batch of loads, the run masks of the words
+  for (uint32_t i = threadIdx.x; i < a.tab_bytes / 4; i += kBlockIx) ((lds_u32wp)tab)[i] = 0u;
+  {
+    const StageSeg segs[2] = {chunk_image_segment(a.ix, ch),
+                              StageSeg{a.off_rank, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_term_rank), ch.n_words * 8u}};
+    lds_stage_segments<2, 4>(lds, segs);
+  }
+  if (ch.has_adj) {  // (see kt_aggregate_bitmap: lowest / highest number of every run of one group's terms)
+    const uint16_t* g_rank = (const uint16_t*)(a.ix.blob + ch.img_off + ch.off_term_rank);
+    for (uint32_t w = wave; w < ch.n_words; w += (uint32_t)(kBlockIx / kWave)) {
+      const uint32_t tr = g_rank[w * 64u + lane];
+      const uint32_t tp = (uint32_t)__shfl_up((int)tr, 1), tn = (uint32_t)__shfl_down((int)tr, 1);
+      const bool adj = (tr & kRankAdj) != 0u;
+      const bool same_prev = lane > 0u && adj && tp == tr, same_next = lane < 63u && adj && tn == tr;
+      const uint64_t m_lo = __ballot(!same_prev), m_hi = __ballot(!same_next);
+      if (lane < 2u) ((lds_u64wp)(lds + a.off_seg))[w * 2u + lane] = lane == 0u ? m_lo : m_hi;
+    }
+  }
+  const BmView bm = open_chunk<VETO>(lds, a.ix, ch);
+  __syncthreads();
+  const bool seg_on = ch.has_adj != 0u;
+  KT_LDS const u64x2* segp = (KT_LDS const u64x2*)(lds + a.off_seg);
+  for (uint32_t wt = t_lo + wave; wt < t_hi; wt += (uint32_t)(kBlockIx / kWave)) {
+    const Rec cur = fetch_tile(wt);
+    const bool in = wt * kWave + lane < n_rows;
+    const uint64_t meta = cur.meta;
+    const uint32_t st = (uint32_t)(meta >> kMetaStateShift) & 0xFu;
+    // shouldCountIn && isNotFinished (throttle_controller.go:217-219, pod_util.go:26-28)
+    const bool counted = in && (st & (kPodValid | kPodSchedMatch | kPodScheduled | kPodFinished)) == (kPodValid | kPodSchedMatch | kPodScheduled);
+    if (__ballot(counted) == 0ull) continue;  // (wave-uniform: nobody of the tile counts)
+    const uint32_t ns = counted ? (uint32_t)(meta & kMetaNsMask) : 0u;
+    const uint32_t present = (uint32_t)(meta >> kMetaPresentShift) & 0xFFFFu;
+    const uint32_t zero_keys = present & ~(uint32_t)(meta >> kMetaNzShift) & 0xFFFFu;  // keys carried with the value 0
+    unsigned long long pw[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) pw[k] = cur.pw[k];
+    const u32x4 raw[1] = {cur.raw};
+    uint32_t ro[LA];
+    atom_row_offsets<LA>(raw, ro);
+    // the word queue of kt_aggregate_bitmap's packed fold
+    uint64_t qx[kWq];
+    typedef typename std::conditional<(kWq > 3), uint64_t, uint32_t>::type qw_t;  // word numbers, 10 bits each, newest lowest
+    qw_t qw = 0;
+    uint32_t qn = 0u;
+#pragma unroll
+    for (int k = 0; k < kWq; ++k) qx[k] = 0ull;
+    auto flush = [&]() {
+      while (__ballot(qn != 0u) != 0ull) {
+        const bool has = qn != 0u;
+        const uint32_t cw = ((uint32_t)qw & 1023u) * 64u;
+        const uint32_t c = cw + (uint32_t)__ffsll((unsigned long long)qx[0]) - 1u;
+        qx[0] &= qx[0] - 1ull;
+        const uint32_t r = trank[has ? c : 0u] & 0x7FFFu;
+        if (has && qx[0] == 0ull) {  // the newest word is used up: the older ones move up
+#pragma unroll
+          for (int k = 0; k + 1 < kWq; ++k) qx[k] = qx[k + 1];
+          qx[kWq - 1] = 0ull;
+          qw >>= 10;
+          qn -= 1u;
+        }
+        if (has) {
+          KT_LDS unsigned char* rp = tab + agg_one_rec_off(r, rec, skew);
+          lds_u64wp tv = (lds_u64wp)rp;
+          lds_add64(tv, pw[0]);
+          if (pk_nw > 1u) lds_add64(tv + 1, pw[1]);
+          if (pk_nw > 2u) lds_add64(tv + 2, pw[2]);
+          if (zero_keys) (void)__hip_atomic_fetch_or((lds_u32wp)(rp + pk_nw * 8u), zero_keys, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    };
+    scan_tile<LA, VETO, NEED, false>(
+        bm, counted, ns, ro, [&](bool, uint32_t) {}, [&](uint32_t) { return true; },
+        [&](uint32_t w, uint64_t x, const u64x2& seg) -> uint64_t {
+          if (seg_on) {  // a throttle with several terms is counted once: the lowest match of every run
+            const uint64_t v = x | seg.y;
+            x = andn_64(x, v - seg.x);
+          }
+          if (__ballot(x != 0ull && qn >= (uint32_t)kWq) != 0ull) flush();
+          if (x != 0ull) {
+#pragma unroll
+            for (int k = kWq - 1; k > 0; --k) qx[k] = qx[k - 1];
+            qx[0] = x;
+            qw = (qw_t)(qw << 10) | (qw_t)w;
+            qn += 1u;
+          }
+          return 0ull;
+        },
+        [&](uint32_t w) -> u64x2 { return seg_on ? segp[w] : u64x2{0ull, 0ull}; });
+    flush();
+  }
+  __syncthreads();  // spill the table as this workgroup's slab: the plain array of records, coalesced 16-byte stores
+  const uint32_t slab_pitch = (ch.n_thr * rec + 15u) & ~15u;
+  u32x4* dst = (u32x4*)(a.slab + (size_t)blockIdx.x * slab_pitch);
+  for (uint32_t i = threadIdx.x; i < slab_pitch / 16u; i += kBlockIx) {
+    // (skewed tables hold 32-byte records: piece i is half of record i / 2, the pad sits behind every eight records)
+    KT_LDS const u32x2* src = (KT_LDS const u32x2*)(tab + i * 16u + (skew ? (i >> 4) << 3 : 0u));
+    const u32x2 lo = src[0], hi = src[1];
+    dst[i] = u32x4{lo.x, lo.y, hi.x, hi.y};
+  }
+}
+
+// LDS of the two-per-CU form: ranks, the (skewed) table of packed records, the run masks, the image
+static BmAggOneArgs make_bm_agg_one_args(const IndexDev& ix, const PackPlan& pk, uint32_t* total) {
+  BmAggOneArgs a{};
+  uint32_t o = 0;
+  auto take = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
+  a.pk_nw = pk.nw, a.pk_stride = pk.stride, a.pk_rec = pk.rec_bytes, a.skew = pk.rec_bytes == 32u ? 1u : 0u;
+  a.off_rank = take(ix.bm_max_words * 64u * 2u);
+  a.tab_bytes = (ix.bm_max_thr * pk.rec_bytes + (a.skew ? ((ix.bm_max_thr + 7u) >> 3) * 8u : 0u) + 15u) & ~15u;
+  a.off_tab = take(a.tab_bytes);
+  a.off_seg = take(ix.bm_max_words * 16u);
+  plan_bitmap_index(ix, a.ix, take);
+  *total = o;
+  return a;
+}
+
+bool aggregate_two_per_cu_fits(const IndexDev& ix, const PackPlan& pk, const AggTwoLaunch& launch) {
+  if (!launch.enabled || launch.small_window || launch.overflow_pods || launch.pod_LA > 8) return false;
+  if (ix.n_chunks != 1 || ix.h_chunks.size() != 1 || ix.n_slow != 0 || ix.has_long || ix.la > 8u || ix.max_need > 3u) return false;
+  if (!pk.nw || pk.nw > 3u || pk.rec_bytes > 32u || pk.headroom < (uint32_t)kPackHeadroomBitsTwo) return false;
+  const BmChunk& ch = ix.h_chunks[0];
+  if (ch.has_slow || ch.n_thr == 0u) return false;
+  uint32_t total = 0;
+  (void)make_bm_agg_one_args(ix, pk, &total);
+  if (2u * total > (uint32_t)kMaxLds) return false;
+  const uint64_t pitch = ((uint64_t)ch.n_thr * pk.rec_bytes + 15u) & ~15ull;
+  return (uint64_t)kAggWorkgroupsTwo * pitch <= agg_slab_area_bytes(ch.n_thr, ix.cut_thr_bytes);
+}
+
 // kt_reduce_bitmap_slabs — partial[t][*] += sum over the workgroups' slabs of t's chunk.  Every slab is an array of
 // per-throttle records (agg_rec_bytes).  grid = (piece groups, chunks, slab splits): a wave streams 64 consecutive
 // 16-byte pieces of the chunk's table (1 KB, fully coalesced) over its share of the slabs, the block's four waves meet
@@ -559,18 +747,19 @@ __global__ __launch_bounds__(256) void kt_reduce_bitmap_slabs(const unsigned cha
 // whole words, class by class — into LDS; then thread = (record, dimension) cuts its total out of the sums and adds it to
 // the partial buffer (several groups of one throttle meet there): a dozen atomics per record, issued by a dozen lanes at
 // once.  check_tags = 0: every workgroup spilled every chunk (single-chunk programs) — no tag reads.
+template <int NL>  // slabs per wave: 16 (up to 256 slabs), 32 over half-wide tiles (the two-per-CU scan's up to 512)
 __global__ __launch_bounds__(kRecBlock) void kt_reduce_packed_slabs(const unsigned char* slab, const BmChunk* chunks, const uint32_t* rank_t,
                                                                    int n_slabs, int D, const PackPlan pk, const uint32_t* slab_tag, uint32_t epoch,
                                                                    int check_tags, unsigned long long* partial) {
   __shared__ RecSumsLds lds;
   const BmChunk ch = chunks[blockIdx.y];
-  const uint32_t units = pk.rec_bytes >> 3, rb = (uint32_t)kRecTileUnits / units;
+  const uint32_t units = pk.rec_bytes >> 3, rb = RecSlabLoads<NL>::kTileUnits / units;
   const uint32_t rec0 = blockIdx.x * rb;
   if (rec0 >= ch.n_thr) return;  // block-uniform
   const uint32_t nrec = min(rb, ch.n_thr - rec0);
   const uint32_t x = threadIdx.x, g = x >> 4, d = x & 15u;  // thread = (record g of the tile, dimension d)
   const size_t pitch = ((size_t)ch.n_thr * pk.rec_bytes + 15u) & ~(size_t)15u;
-  RecSlabLoads sl;
+  RecSlabLoads<NL> sl;
   record_slabs_live(n_slabs, slab_tag + blockIdx.y * kSlabTagStride, epoch, check_tags, sl);
   uint32_t t = 0;
   if (g < nrec) t = rank_t[ch.rank0 + rec0 + g];
@@ -606,11 +795,14 @@ __global__ __launch_bounds__(kRecBlock) void kt_reduce_packed_slabs(const unsign
     else KT_AGG_BM_LAUNCH(16, LA_, VETO_, NEED_, true, true)                                                  \
   }
 
-static_assert(kCUs <= kMaxSlabsPerRecord, "packed_record_sums takes four slabs per lane");
-int aggregate_blocks(int64_t n_rows) {
+static_assert(kAggWorkgroups == kCUs && kAggWorkgroupsTwo == 2 * kCUs, "one or two workgroups per CU");
+static_assert(kAggWorkgroups <= 16 * kRecWaves && kAggWorkgroupsTwo <= 32 * kRecWaves, "the packed reductions take 16 or 32 slabs per wave");
+static_assert(kAggWorkgroups <= 1 << kPackHeadroomBits && kAggWorkgroupsTwo <= 1 << kPackHeadroomBitsTwo, "headroom of the packed fields");
+int aggregate_blocks(int64_t n_rows, int max_wg) {
   int64_t b = (n_rows + kBlockIx - 1) / kBlockIx;
-  return (int)(b < 1 ? 1 : b > kCUs ? kCUs : b);
+  return (int)(b < 1 ? 1 : b > max_wg ? max_wg : b);
 }
+int aggregate_blocks(int64_t n_rows) { return aggregate_blocks(n_rows, kAggWorkgroups); }
 // the most pods one workgroup of an aggregate launch scans: contiguous tile ranges (scan view) or a stride over the tiles
 uint64_t aggregate_slab_pods(int64_t n_rows, int blocks) {
   const int64_t tiles = (n_rows + kWave - 1) / kWave;
@@ -638,7 +830,16 @@ const char* launch_aggregate_indexed(const PodTable& pods, const AggScan& sc, co
                       bm_args.pk.rec_bytes <= ix.cut_thr_bytes && !ix.has_long;
   if (bm_args.v_pk != nullptr && !packed) return nullptr;  // the engine only hands over packed words it may use
   if (!packed && agg_rec_bytes(pods.D, sc.counts) > ix.cut_thr_bytes) return nullptr;
-  int nb = aggregate_blocks(n_rows);
+  // Two workgroups per CU (kt_aggregate_bitmap_one) where the engine planned the pack for it and nothing asks for what that form
+  // drops — unless the caller keeps the launch at one per CU (KT_AGG_ONE_PER_CU: A/B runs and a parity test)
+  // (no rank windows there: two footprints of that form fit one CU, so one table fits beside the image)
+  const bool two_per_cu = packed && aggregate_two_per_cu_fits(ix, bm_args.pk, AggTwoLaunch{!sc.one_per_cu, sc.small_window, sc.overflow_pods, LA});
+  if (packed && bm_args.pk.headroom >= (uint32_t)kPackHeadroomBitsTwo && !two_per_cu) {
+    sc.refused = "the packed words were planned for two workgroups per CU and this launch cannot run that form";
+    return nullptr;  // (its fields hold the sums of half a one-per-CU workgroup's pods; the engine plans again before it gets here)
+  }
+  int nb = aggregate_blocks(n_rows, two_per_cu ? kAggWorkgroupsTwo : kAggWorkgroups);
+  if (two_per_cu) bm_args.wg_range = nullptr;
   if (bm_args.ix.by_ns && bm_args.wg_range) {
     // planned ranges: one per workgroup of the full grid (a workgroup whose range is empty returns: multi-chunk programs only,
     // whose reductions go by the slab tags)
@@ -650,8 +851,41 @@ const char* launch_aggregate_indexed(const PodTable& pods, const AggScan& sc, co
     const int64_t tiles = (n_rows + kWave - 1) / kWave, tpb = (tiles + nb - 1) / nb;
     nb = (int)((tiles + tpb - 1) / tpb);
   }
+  {  // the slabs of this launch inside every chunk's slab area (cut for ix.cut_thr_bytes per record and kAggWorkgroups slabs)
+    const uint32_t rec_bytes = packed ? bm_args.pk.rec_bytes : agg_rec_bytes(pods.D, sc.counts);
+    for (const BmChunk& ch : ix.h_chunks)
+      if ((uint64_t)nb * (((uint64_t)ch.n_thr * rec_bytes + 15u) & ~15ull) > agg_slab_area_bytes(ch.n_thr, ix.cut_thr_bytes)) {
+        sc.refused = "the slabs of the launch's workgroups do not fit the chunk's slab area";
+        return nullptr;
+      }
+  }
   dim3 g_(nb), b_(kBlockIx);
   const size_t lds_bm = bm_total;
+  if (two_per_cu) {
+    uint32_t one_total = 0;
+    BmAggOneArgs oa = make_bm_agg_one_args(ix, bm_args.pk, &one_total);
+    const BmChunk& ch = ix.h_chunks[0];
+    oa.v_meta = sc.v_meta, oa.v_latom = sc.v_latom, oa.v_pk = sc.v_pk, oa.ch = ch;
+    oa.slab = slab + (size_t)ch.slab_off * 16;
+    oa.n_rows = (uint32_t)n_rows;
+    oa.tpb = (uint32_t)((((n_rows + kWave - 1) / kWave) + nb - 1) / nb);
+    static const bool dbg_one = getenv("KT_DEBUG_LDS") != nullptr;
+    if (dbg_one)
+      fprintf(stderr, "kt_aggregate_bitmap_one: lds=%u (2 per CU) workgroups=%d tiles per workgroup=%u nw=%u rec=%u skew=%u\n", one_total, nb, oa.tpb,
+              oa.pk_nw, oa.pk_rec, oa.skew);
+#define KT_AGG_ONE_LAUNCH(VETO_, NEED_)                                                                          \
+  {                                                                                                             \
+    auto kfn = kt_aggregate_bitmap_one<VETO_, NEED_>;                                                           \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)one_total);    \
+    hipLaunchKernelGGL(kfn, g_, b_, one_total, s, oa);                                                          \
+  }
+#ifdef KT_FAST_BUILD
+    KT_AGG_ONE_LAUNCH(false, 2)
+#else
+    if (!ix.rich) KT_AGG_ONE_LAUNCH(false, 2) else KT_AGG_ONE_LAUNCH(true, 3)
+#endif
+#undef KT_AGG_ONE_LAUNCH
+  } else {
   const bool windowed = bm_args.win_recs != 0u;
   const bool wide_pk = packed && bm_args.pk.nw > 4u;  // 5..8 packed words: the DT = 16 instantiations of the packed fold
   static const bool dbg_lds = getenv("KT_DEBUG_LDS") != nullptr;
@@ -671,14 +905,18 @@ const char* launch_aggregate_indexed(const PodTable& pods, const AggScan& sc, co
   else if (LA <= 16) { if (DT <= 8) KT_AGG_BM_CASE(8, 16, true, 3) else KT_AGG_BM_CASE(16, 16, true, 3) }
   else { if (DT <= 8) KT_AGG_BM_CASE(8, 32, true, 3) else KT_AGG_BM_CASE(16, 32, true, 3) }
 #endif
+  }
   if (after_scan) after_scan();
   sc.launched_blocks = nb, sc.launched_packed = packed;
   if (packed && sc.defer_reduce) {
     // the caller goes on with kt_reduce_finalize_packed
   } else if (packed) {
-    const uint32_t rb_ = (uint32_t)kRecTileUnits / (bm_args.pk.rec_bytes >> 3);  // records per block
-    if (ix.bm_max_thr > 0)
-      hipLaunchKernelGGL(kt_reduce_packed_slabs, dim3((ix.bm_max_thr + rb_ - 1u) / rb_, ix.n_chunks), dim3(kRecBlock), 0, s, slab,
+    const uint32_t rb_ = (uint32_t)(nb > 16 * kRecWaves ? kRecTileUnits / 2 : kRecTileUnits) / (bm_args.pk.rec_bytes >> 3);  // records per block
+    if (ix.bm_max_thr > 0 && nb > 16 * kRecWaves)
+      hipLaunchKernelGGL(kt_reduce_packed_slabs<32>, dim3((ix.bm_max_thr + rb_ - 1u) / rb_, ix.n_chunks), dim3(kRecBlock), 0, s, slab,
+                         ix.bm_chunks, ix.bm_rank_t, nb, pods.D, bm_args.pk, sc.slab_tag, sc.epoch, ix.n_chunks > 1 ? 1 : 0, partial);
+    else if (ix.bm_max_thr > 0)
+      hipLaunchKernelGGL(kt_reduce_packed_slabs<16>, dim3((ix.bm_max_thr + rb_ - 1u) / rb_, ix.n_chunks), dim3(kRecBlock), 0, s, slab,
                          ix.bm_chunks, ix.bm_rank_t, nb, pods.D, bm_args.pk, sc.slab_tag, sc.epoch, ix.n_chunks > 1 ? 1 : 0, partial);
   } else {
     const uint32_t max_pieces = ix.bm_max_thr * (agg_rec_bytes(pods.D, sc.counts) / 16u);

@@ -494,7 +494,7 @@ struct FusedReduceArgs {
   PackPlan pk;
   BmChunk ch0;             // n_chunks == 1: the chunk's descriptor by value (one dependent load less)
 };
-template <int DT>
+template <int DT, int NL>  // NL: slabs per wave of the reduction (RecSlabLoads: 16, or 32 over half-wide tiles behind a two-per-CU scan)
 __global__ __launch_bounds__(kRecBlock) void kt_reduce_finalize_packed(const FusedReduceArgs f, ThrTables tt, int T, int D, unsigned long long* partial,
                                                                       int consume, int64_t now_s, int32_t now_ns, int apply, ReconcileOut out,
                                                                       CheckRec<DT>* recs, int rec_eq, const ReqBound vmax, const uint8_t* row_mask) {
@@ -516,7 +516,7 @@ __global__ __launch_bounds__(kRecBlock) void kt_reduce_finalize_packed(const Fus
       ch.n_thr = __builtin_amdgcn_readfirstlane(cp->n_thr), ch.rank0 = __builtin_amdgcn_readfirstlane(cp->rank0);
       ch.slab_off = __builtin_amdgcn_readfirstlane(cp->slab_off);
     }
-    const uint32_t units = f.pk.rec_bytes >> 3, rb = (uint32_t)kRecTileUnits / units;
+    const uint32_t units = f.pk.rec_bytes >> 3, rb = RecSlabLoads<NL>::kTileUnits / units;
     const uint32_t rec0 = blockIdx.x * rb;
     if (rec0 >= ch.n_thr) return;  // block-uniform
     const uint32_t nrec = min(rb, ch.n_thr - rec0);
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(kRecBlock) void kt_reduce_finalize_packed(const Fus
     // the slab tags (multi-chunk programs only), the record's throttle, the sixteen slab words — then, the throttle
     // known, its stored state; the slab words are summed and exchanged through LDS while that last batch is in flight.
     const size_t pitch = ((size_t)ch.n_thr * f.pk.rec_bytes + 15u) & ~(size_t)15u;
-    RecSlabLoads sl;
+    RecSlabLoads<NL> sl;
     record_slabs_live(f.n_slabs, f.slab_tag + blockIdx.y * kSlabTagStride, f.epoch, f.check_tags, sl);
     const unsigned char* row0 = f.slab + (size_t)ch.slab_off * 16 + (size_t)rec0 * f.pk.rec_bytes;
     if (!fin) {  // (its own copy of the code: the waits of the finalizing waves must not be planned for both kinds)
@@ -631,13 +631,20 @@ void launch_reduce_finalize_packed(const ThrTables& tt, const SelProgram& sp, in
   f.scan_adds_rows = scan_adds_rows ? 1 : 0;
   if (ix.n_chunks == 1 && !ix.h_chunks.empty()) f.ch0 = ix.h_chunks[0];
   const int DT = recs ? rec_DT : (D <= 4 ? 4 : D <= 8 ? 8 : 16);
-  const uint32_t rb = (uint32_t)kRecTileUnits / (pk.rec_bytes >> 3), per_ng = (uint32_t)(kRecBlock / DT);
+  const bool many = n_slabs > 16 * kRecWaves;  // more than 256 slabs (the two-per-CU scan): tiles of 32 units
+  const uint32_t rb = (uint32_t)(many ? kRecTileUnits / 2 : kRecTileUnits) / (pk.rec_bytes >> 3), per_ng = (uint32_t)(kRecBlock / DT);
   const uint32_t gx = std::max((ix.bm_max_thr + rb - 1u) / rb, (ix.n_nogroup + per_ng - 1u) / per_ng);
   const dim3 g(gx ? gx : 1u, ix.n_chunks + (ix.n_nogroup ? 1u : 0u)), b(kRecBlock);  // the extra row: throttles without a group
   const int eq = rec_eq ? 1 : 0;
-  if (DT == 4) hipLaunchKernelGGL(kt_reduce_finalize_packed<4>, g, b, 0, s, f, tt, sp.T, D, partial, consume ? 1 : 0, now_s, now_ns, apply ? 1 : 0, out, (CheckRec<4>*)recs, eq, vmax, row_mask);
-  else if (DT == 8) hipLaunchKernelGGL(kt_reduce_finalize_packed<8>, g, b, 0, s, f, tt, sp.T, D, partial, consume ? 1 : 0, now_s, now_ns, apply ? 1 : 0, out, (CheckRec<8>*)recs, eq, vmax, row_mask);
-  else hipLaunchKernelGGL(kt_reduce_finalize_packed<16>, g, b, 0, s, f, tt, sp.T, D, partial, consume ? 1 : 0, now_s, now_ns, apply ? 1 : 0, out, (CheckRec<16>*)recs, eq, vmax, row_mask);
+#define KT_RFP_LAUNCH(DT_, NL_)                                                                                                                    \
+  hipLaunchKernelGGL((kt_reduce_finalize_packed<DT_, NL_>), g, b, 0, s, f, tt, sp.T, D, partial, consume ? 1 : 0, now_s, now_ns, apply ? 1 : 0, out, \
+                     (CheckRec<DT_>*)recs, eq, vmax, row_mask)
+  if (many) {
+    if (DT == 4) KT_RFP_LAUNCH(4, 32); else if (DT == 8) KT_RFP_LAUNCH(8, 32); else KT_RFP_LAUNCH(16, 32);
+  } else {
+    if (DT == 4) KT_RFP_LAUNCH(4, 16); else if (DT == 8) KT_RFP_LAUNCH(8, 16); else KT_RFP_LAUNCH(16, 16);
+  }
+#undef KT_RFP_LAUNCH
 }
 
 // ---------------------------------------------------------------------------------------------------

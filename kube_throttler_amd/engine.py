@@ -49,6 +49,7 @@ PREEMPT_NONE = -1
 FORECAST_NONE = -1
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
+COUNTER_AGG_WORKGROUPS = 11
 COUNTER_VIEW_BUILDS = 10
 
 
@@ -458,6 +459,10 @@ class Engine:
     def packed_words(self) -> int:
         """64-bit words per pod of the packed fold the last full aggregate scan ran with (0: the plain fold)."""
         return int(lib().kt_counter(self._h, COUNTER_PACKED_WORDS))
+
+    def aggregate_workgroups(self) -> int:
+        """Workgroups of the last full aggregate scan's launch (more than 256: the two-per-CU form ran)."""
+        return int(lib().kt_counter(self._h, COUNTER_AGG_WORKGROUPS))
 
     def view_builds(self) -> int:
         """Scan view builds so far (either view); pod events that fit the views are patched in and do not count."""
