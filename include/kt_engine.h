@@ -420,6 +420,46 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
  *      Out of scope: the paged form, several ranks. --------------------------------------------------------------------- */
 int32_t kt_preempt_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
                                    int32_t now_ns, int32_t on_equal, void* stream);
+/* ---- preempt, for gangs: the shortest victim prefix that lets a WHOLE gang in — where kt_preempt_launch and kt_admit_gangs_launch
+ *      meet.  The maximum of the members' own prefixes is not the answer: each admitted member RESERVES against the throttles the
+ *      later members meet (plugin.go:217-239, reservedResourceAmounts.addPod).
+ *      Notation as for kt_preempt_launch: counted pods, the candidates c_0 .. c_{m-1} = cand_rows, state S_k, the m_eff cut, "a
+ *      throttle whose reconcile is an error keeps its stored status in every S_k", exact presence from contributor counts.  Gang g
+ *      is the queue positions [gang_off[g], gang_off[g + 1]) of pod_rows, as in kt_admit_gangs_launch.  Gangs are judged
+ *      INDEPENDENTLY of each other, each against the stored reserved amounts: a query about alternatives, not a queue (a pod may be
+ *      a member of several gangs).
+ *      out_prefix[g] is the smallest k in [0, m_eff] for which a dry kt_admit_gangs_launch of the one gang g would admit it with
+ *      S_k as the stored status: its members get PreFilter in order, each sees the reserved amounts as stored plus what the earlier
+ *      members of its own gang reserved at their turn, and every verdict is Success.  Reserve is exactly kt_admit's: for every
+ *      throttle whose byte in the member's matrix row is nonzero the pod's value is added for every name it carries, the presence
+ *      word is OR-ed with ALL names it carries (zero-valued ones included), the pod count gets +1 and becomes present.
+ *      KT_PREEMPT_NONE: no k works, a member's PreFilter is an Error, or a member's row is invalid.
+ *      out_victims[g][j] (nullable, [n_gangs][n_cand]) is 1 iff j < out_prefix[g], c_j is counted and a throttle that affects at
+ *      least one member matches c_j; the row is all zero when the prefix is <= 0.
+ *      out_blocker[g] (nullable) is the queue position (index into pod_rows) of the first member whose verdict is not Success when
+ *      the gang is walked in S_0 — all earlier members were admitted, so the sums it met are exact — and -1 when out_prefix[g] == 0.
+ *      A gang of one pod reports exactly what kt_preempt_launch reports for that pod.
+ *      The verdict is in closed form and two-dimensional: deleting a prefix lowers `used` by a prefix sum over the candidates,
+ *      being admitted raises `reserved` by a prefix sum over the members.  One kt_check launch over pod_rows ++ cand_rows, the
+ *      aggregate and dry finalize of kt_preempt_launch, and one launch of kt_preempt_gangs (csrc/kt_kernels_preempt_gangs.hip):
+ *      one wave per gang, lane = candidate position, the scans once per throttle and block of 64 candidates, the member loop
+ *      wave-uniform.  Every k is evaluated, sums are formed in 128 bits; requests of either sign are answered as the definition
+ *      answers them.  The call is a dry run: stored status and reserved amounts are not changed.
+ *      Refused before anything is launched: every gang_off defect kt_admit_gangs_launch refuses, a pod named twice within ONE
+ *      gang, a member that is also a candidate, a candidate named twice, a missing array, n_cand < 0 (KT_ERR_INVALID_ARGUMENT);
+ *      the 2^31 matrix rule of kt_preempt_launch on n, n_cand and their sum (KT_ERR_OUT_OF_RANGE); `used` wider than int64, a
+ *      KT_VARIANT_INCREMENTAL engine, an exchange world above 1 (KT_ERR_UNSUPPORTED; the |request| sums kernel runs first where the
+ *      sums are unknown).  A refused call leaves the check slot, the reconcile report and every result buffer alone.  n == 0 is
+ *      allowed only with n_gangs == 0: KT_OK, nothing is launched.
+ *      Slots: the launch uses the check slot and the reconcile report exactly as kt_preempt_launch does, and its result SHARES the
+ *      one pending preempt result, as kt_preempt_reprieve_launch does: a later launch of any of the three replaces it.
+ *      kt_preempt_fetch after a gang launch answers KT_ERR_NOT_READY, and so does kt_preempt_gangs_fetch after a plain launch; a
+ *      pending kt_forecast_launch stays fetchable.  kt_preempt_gangs_fetch synchronises.
+ *      Out of scope: a reprieve pass for gangs, the paged form, several ranks. -------------------------------------------- */
+int32_t kt_preempt_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
+                                const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream);
+int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefix /* [n_gangs], nullable */,
+                               uint8_t* out_victims /* [n_gangs][n_cand], nullable */, int64_t* out_blocker /* [n_gangs], nullable */);
 /* ---- forecast: the first instant at which a blocked pod passes — the one axis no other query looks along.
  *      temporaryThresholdOverrides make every threshold a step function of the clock (throttle_types.go:65-106,
  *      temporary_threshold_override.go:57-70): a pod that PreFilter rejects now may pass when a night-time override begins or a

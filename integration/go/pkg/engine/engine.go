@@ -44,7 +44,7 @@ const (
 type Engine struct {
 	h    *C.kt_engine
 	dims int
-	mu   sync.Mutex // the engine's ONE check slot: every method that takes it (Check, AffectedPods, Admit, AdmitGangs, Headroom, Preempt, PreemptReprieve) holds mu from its launch to its fetch; Verdict's one-pod check runs beside the slot and takes no lock
+	mu   sync.Mutex // the engine's ONE check slot: every method that takes it (Check, AffectedPods, Admit, AdmitGangs, Headroom, Preempt, PreemptReprieve, PreemptGangs) holds mu from its launch to its fetch; Verdict's one-pod check runs beside the slot and takes no lock
 }
 
 // New creates an engine for `dims` resource names (<= 16), pods with up to maxLabels labels and the given row capacities.
@@ -447,6 +447,36 @@ func (e *Engine) preempt(rows, cands []int64, nowS int64, nowNs int32, onEqual, 
 		return nil, nil, e.err(rc)
 	}
 	return prefix, victims[:len(rows)*len(cands)], nil
+}
+
+// PreemptGangs answers, for every gang rows[gangOff[g]:gangOff[g+1]], the shortest prefix of the caller-ordered candidate list
+// cands whose deletion, followed by a reconcile of every throttle at now, lets a dry AdmitGangs of that one gang admit it — each
+// admitted member reserves against the throttles the later members meet, so the answer is not the longest of the members' own
+// prefixes (kt_preempt_gangs_launch + kt_preempt_gangs_fetch).  prefix[g] as for Preempt (-1 also when a member's PreFilter is an
+// Error or its row is invalid); victims[g*len(cands)+j] = 1 for the counted candidates below the prefix that a throttle affecting
+// some member matches; blocker[g] = the index into rows of the first member that is not admitted with nothing deleted, -1 where
+// prefix[g] == 0.  Gangs are judged independently of each other, each against the stored reserved amounts.  A dry run like
+// Preempt, and like Preempt under e.mu from its launch to its fetch; the result shares Preempt's pending slot.  Not compiled in
+// this repository (no Go toolchain in its build).
+func (e *Engine) PreemptGangs(rows, gangOff, cands []int64, nowS int64, nowNs int32, onEqual bool) (prefix []int64, victims []uint8, blocker []int64, err error) {
+	if len(gangOff) < 2 {
+		return nil, nil, nil, nil
+	}
+	nGangs := len(gangOff) - 1
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	if rc := C.kt_preempt_gangs_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(nGangs), i64(gangOff), C.int64_t(len(cands)),
+		i64(cands), C.int64_t(nowS), C.int32_t(nowNs), b2i(onEqual), nil); rc != C.KT_OK {
+		return nil, nil, nil, e.err(rc)
+	}
+	prefix = make([]int64, nGangs)
+	blocker = make([]int64, nGangs)
+	victims = make([]uint8, nGangs*len(cands)+1)
+	if rc := C.kt_preempt_gangs_fetch(e.h, C.int64_t(nGangs), (*C.int64_t)(unsafe.Pointer(&prefix[0])),
+		(*C.uint8_t)(unsafe.Pointer(&victims[0])), (*C.int64_t)(unsafe.Pointer(&blocker[0]))); rc != C.KT_OK {
+		return nil, nil, nil, e.err(rc)
+	}
+	return prefix, victims[:nGangs*len(cands)], blocker, nil
 }
 
 // PagedAdmit is Admit over the pages of a cluster with more than 16 resource names (kt_paged_admit): one engine per page of

@@ -1,9 +1,12 @@
 // kt_admit_common.h — what the admission kernels (kt_kernels_admit.hip: kt_admit, kt_admit_gangs) and the headroom kernel
 // (kt_kernels_headroom.hip: kt_headroom) share, gfx950: the affected-throttle list of a status-matrix row, the page descriptor
 // by value, the effective threshold and step 3's isThrottledOnEqual of a throttle, the 128-bit comparison; and what the preemption
-// kernels (kt_kernels_preempt.hip: kt_preempt, kt_kernels_reprieve.hip: kt_preempt_reprieve) share: the four steps for one amount
-// against `used` as it stands in some state, the wave scan, the chunk and grid sizes.  The page descriptor itself (AdmitPage) is
-// host-visible: kt_launch.h.
+// kernels (kt_kernels_preempt.hip: kt_preempt, kt_kernels_reprieve.hip: kt_preempt_reprieve, kt_kernels_preempt_gangs.hip:
+// kt_preempt_gangs) share: the four steps for one amount against `used` as it stands in some state, the wave scan, the chunk and
+// grid sizes; and what kt_preempt and kt_preempt_gangs share on top: their arguments, the list cut, which rows keep their stored
+// status and which threshold a check reads behind the reconcile, the pieces of the k >= 1 block body (a lane's candidate, the
+// scans with their carries, `used` with a prefix gone against one amount) and the derivation of prefix and victim mask from the
+// verdict bits.  The page descriptor itself (AdmitPage) is host-visible: kt_launch.h.
 #pragma once
 #include "kt_index_device.h"
 
@@ -11,6 +14,21 @@ namespace kt {
 
 // the sums of used + reserved (+ the pod) are formed in 128 bits: an all-reduced `used` may come close to int64's end
 __device__ __forceinline__ bool admit_cmp(__int128 a, int64_t b, bool eq) { return eq ? a >= (__int128)b : a > (__int128)b; }
+
+// The marked bytes (bit k of nzm: byte b0 + k) of every lane go behind n_aff in the list (ballot/mbcnt append; entries beyond
+// list_cap are counted, not written); returns the wave-uniform new count
+__device__ __forceinline__ uint32_t admit_append_marked(uint32_t nzm, int b0, lds_u32wp list, uint32_t list_cap, uint32_t n_aff) {
+  while (__ballot(nzm != 0) != 0ull) {
+    const bool has = nzm != 0;
+    const uint32_t k = (uint32_t)__ffs((int)nzm) - 1u;
+    nzm &= nzm - 1u;
+    const uint64_t mk = __ballot(has);
+    const uint32_t pos = n_aff + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+    if (has && pos < list_cap) list[pos] = (uint32_t)b0 + k;
+    n_aff += (uint32_t)__popcll(mk);
+  }
+  return n_aff;
+}
 
 // One chunk (kWave x 16 bytes from byte c0) of a pod's status-matrix row: its nonzero bytes are appended to the
 // affected-throttle list behind n_aff (16 bytes per lane, ballot/mbcnt append; entries beyond list_cap are counted, not
@@ -29,16 +47,28 @@ __device__ __forceinline__ uint32_t admit_affected_chunk(const uint8_t* row, int
     if (b0 + k < T && byte != 0) nzm |= 1u << k;
     *err |= (b0 + k < T) && byte == 255u;
   }
-  while (__ballot(nzm != 0) != 0ull) {
-    const bool has = nzm != 0;
-    const uint32_t k = (uint32_t)__ffs((int)nzm) - 1u;
-    nzm &= nzm - 1u;
-    const uint64_t mk = __ballot(has);
-    const uint32_t pos = n_aff + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-    if (has && pos < list_cap) list[pos] = (uint32_t)b0 + k;
-    n_aff += (uint32_t)__popcll(mk);
-  }
-  return n_aff;
+  return admit_append_marked(nzm, b0, list, list_cap, n_aff);
+}
+
+// The gang form: one chunk of the UNION of the rows of queue positions [i0, i1) — a byte counts when it is nonzero in some
+// member's row; *err |= some member's row holds an error byte in the chunk (per lane: ballot it)
+__device__ __forceinline__ uint32_t gang_affected_chunk(const uint8_t* status, int64_t i0, int64_t i1, int T, int c0, lds_u32wp list,
+                                                        uint32_t list_cap, uint32_t n_aff, bool* err) {
+  const uint32_t lane = threadIdx.x % kWave;
+  const int b0 = c0 + (int)lane * 16;
+  uint32_t nzm = 0;  // bit k: byte k is nonzero in some member's row
+  if (b0 < T)
+    for (int64_t i = i0; i < i1; ++i) {
+      const u32x4 v = *(const u32x4*)(status + i * (int64_t)T + b0);  // the buffer has slack past the last row
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const uint32_t byte = (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
+        if (b0 + k < T && byte != 0) nzm |= 1u << k;
+        *err |= (b0 + k < T) && byte == 255u;
+      }
+    }
+  return admit_append_marked(nzm, b0, list, list_cap, n_aff);
 }
 
 // (1) of a pod: the nonzero bytes of its status-matrix row -> the affected-throttle list, chunk after chunk; returns the
@@ -91,6 +121,109 @@ __device__ __forceinline__ V wave_inclusive_scan(V x, uint32_t lane) {
     if (lane >= (uint32_t)o) x += y;
   }
   return x;
+}
+
+// ---- what kt_preempt and kt_preempt_gangs share --------------------------------------------------------------------------------
+struct PreemptArgs {
+  AdmitPage pg;                       // pod flags, request rows and the throttle tables of the engine (state offsets unused)
+  const int64_t* rows;                // [n + m] pod table rows: the preemptors (the gangs' members), then the candidates
+  int64_t n, m;
+  const uint8_t* status;              // [n + m][T]
+  const uint64_t* summary;            // [n + m]
+  const unsigned long long* partial;  // [T][partial_stride(D)], exact contributor counts
+  AmountTab calc;                     // the dry finalize's status.calculatedThreshold at `now`
+  const uint8_t* calc_updated;        // [T] it replaces the stored one (calculatedAt := now)
+  const uint8_t* error;               // [T] the reconcile is an error: the stored status stays
+  int64_t* prefix;                    // [n] out ([n_gangs] for the gang form)
+  uint8_t* victims;                   // [n][m] out (and the kernel's per-position verdict bits while it runs)
+  int32_t T, on_equal;
+};
+
+// m_eff: the list ends before the first candidate whose PreFilter is an error or whose row is invalid (wave-uniform)
+__device__ __forceinline__ int64_t preempt_m_eff(const PreemptArgs& a, uint32_t lane) {
+  for (int64_t q0 = 0; q0 < a.m; q0 += kWave) {
+    const int64_t q = q0 + lane;
+    bool bad = false;
+    if (q < a.m) bad = a.summary[a.n + q] == 2ull || !(a.pg.pod_flags[a.rows[a.n + q]] & kPodValid);
+    const uint64_t mk = __ballot(bad);
+    if (mk != 0ull) return q0 + (__ffsll((long long)mk) - 1);
+  }
+  return a.m;
+}
+
+// a throttle whose reconcile is an error keeps its stored status: nothing of it depends on k
+__device__ __forceinline__ bool preempt_row_stored(uint32_t tf, uint8_t error_byte) {
+  return error_byte != 0 || (tf & (kThrValid | kThrResponsible)) != (kThrValid | kThrResponsible);
+}
+// the threshold the check reads behind the reconcile: calculatedThreshold once calculatedAt is set, else spec
+__device__ __forceinline__ const AmountTab& preempt_threshold(const ThrTables& tt, const AmountTab& calc, uint32_t tf, uint8_t calc_updated) {
+  return ((tf & kThrCalcAtNonzero) || calc_updated) ? calc : tt.spec;
+}
+
+// the lane's candidate in a block of kWave positions, seen from throttle t: contrib = it is counted and t matches it
+struct PreemptCand {
+  int64_t c;
+  uint32_t fl;
+  bool in, contrib;
+};
+__device__ __forceinline__ PreemptCand preempt_cand(const PreemptArgs& a, uint32_t t, int64_t q, int64_t m_eff) {
+  PreemptCand L;
+  L.in = q < m_eff;
+  L.c = L.in ? a.rows[a.n + q] : 0;
+  L.fl = L.in ? a.pg.pod_flags[L.c] : 0u;
+  const uint8_t sb = L.in ? a.status[(a.n + q) * (int64_t)a.T + t] : (uint8_t)0;
+  L.contrib = L.in && (L.fl & (kCounted | kPodFinished)) == kCounted && sb != 0;
+  return L;
+}
+// the counted pods of t among the candidates up to and including the lane's (the carry: those of the earlier blocks)
+__device__ __forceinline__ int64_t preempt_scan_pods(const PreemptCand& L, uint32_t lane, int64_t& car) {
+  const int64_t pre = car + (int64_t)wave_inclusive_scan<uint32_t>(L.contrib ? 1u : 0u, lane);
+  car = __shfl(pre, kWave - 1);
+  return pre;
+}
+// ... and of name d their value and how many of them carry it
+__device__ __forceinline__ void preempt_scan_name(const PreemptArgs& a, const PreemptCand& L, int d, uint32_t lane, int64_t& car_v, uint32_t& car_c,
+                                                  int64_t* pre_v, uint32_t* pre_c) {
+  const bool has = L.contrib && (((L.fl >> kPresentShift) >> d) & 1u);
+  const int64_t v = has ? a.pg.req[L.c * a.pg.DS + d] : 0;
+  *pre_v = car_v + wave_inclusive_scan<int64_t>(v, lane);
+  *pre_c = car_c + wave_inclusive_scan<uint32_t>(has ? 1u : 0u, lane);
+  car_v = __shfl(*pre_v, kWave - 1), car_c = (uint32_t)__shfl((int)*pre_c, kWave - 1);
+}
+// `used` of a reconciled throttle with u_c counted pods left: the pod count against it (the fresh reconcile's throttled flag is
+// IsThrottled(used, true) against the calculated threshold)
+__device__ __forceinline__ bool preempt_count_fails(bool th_hc, int64_t th_c, bool c_hc, int64_t c_c, int64_t u_c, bool r_hc, int64_t r_c, bool eq3,
+                                                    bool eq) {
+  const bool u_hc = u_c > 0;
+  return preempt_fails(1, th_hc, th_c, c_hc && u_hc && u_c >= c_c, u_hc, u_c, r_hc, r_c, eq3, eq);
+}
+// ... and a name the pod requests with vp: u_v its value in `used`, u_n how many remaining counted pods carry it (presence is
+// exact: the name stays in `used` only while one does)
+__device__ __forceinline__ bool preempt_name_fails(int64_t vp, bool th_has, int64_t tv, bool c_has, int64_t cv, int64_t u_v, int64_t u_n, bool r_has,
+                                                   int64_t rv, bool eq3, bool eq) {
+  const bool u_pr = u_n > 0;
+  return preempt_fails(vp, th_has, tv, c_has && u_pr && u_v >= cv, u_pr, u_v, r_has, rv, eq3, eq);
+}
+
+// The verdict bits of a row of the victim buffer (bit 1: some pair fails at k = position + 1; bit 0: the candidate is counted and
+// matched) -> the prefix (0 when nothing fails in S_0, else the first position whose fail bit is clear + 1, else -1; -1 at once
+// when !ok) and the victim bytes in place: j < prefix && bit 0
+__device__ __forceinline__ int64_t preempt_answer(uint8_t* vic, int64_t m, int64_t m_eff, bool ok, bool fail0, uint32_t lane) {
+  int64_t ans = -1;
+  if (ok) {
+    if (!fail0) ans = 0;
+    else
+      for (int64_t q0 = 0; q0 < m_eff; q0 += kWave) {
+        const int64_t q = q0 + lane;
+        const uint64_t mk = __ballot(q < m_eff && !(vic[q] & 2u));
+        if (mk != 0ull) {
+          ans = q0 + __ffsll((long long)mk);  // the first passing position + 1 = the prefix length
+          break;
+        }
+      }
+  }
+  for (int64_t q = lane; q < m; q += kWave) vic[q] = (q < ans && (vic[q] & 1u)) ? (uint8_t)1 : (uint8_t)0;
+  return ans;
 }
 
 }  // namespace kt

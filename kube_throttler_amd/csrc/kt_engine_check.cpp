@@ -751,7 +751,7 @@ static int32_t preempt_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, 
   if (e->wide && e->req_sums_valid) return e->fail(KT_ERR_UNSUPPORTED, "preempt: `used` is wider than int64 (kt_preempt reads int64 sums)");
   e->preempt_ready = false;
   if (n == 0) {  // nothing is launched
-    e->preempt_ready = true, e->preempt_n = 0, e->preempt_m = n_cand;
+    e->preempt_ready = true, e->preempt_gangs = false, e->preempt_n = 0, e->preempt_m = n_cand;
     return KT_OK;
   }
   KT_HIP(e, hipSetDevice(e->device));
@@ -793,7 +793,7 @@ static int32_t preempt_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, 
     KT_HIP(e, hipGetLastError());
   }
   e->last_stream = s;
-  e->preempt_ready = true, e->preempt_n = n, e->preempt_m = n_cand;
+  e->preempt_ready = true, e->preempt_gangs = false, e->preempt_n = n, e->preempt_m = n_cand;
   return KT_OK;
 }
 
@@ -815,13 +815,123 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
   if (!e) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
-  if (!e->preempt_ready) return e->fail(KT_ERR_NOT_READY, "kt_preempt_fetch before kt_preempt_launch");
+  if (!e->preempt_ready || e->preempt_gangs) return e->fail(KT_ERR_NOT_READY, "kt_preempt_fetch before kt_preempt_launch");
   if (n < 0 || n > e->preempt_n) return e->fail(KT_ERR_OUT_OF_RANGE, "n=%lld, the last preempt launch had %lld pods", (long long)n, (long long)e->preempt_n);
   if (n == 0) return KT_OK;
   hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
   if (out_prefix) KT_HIP(e, hipMemcpyAsync(out_prefix, e->d_preempt_prefix.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   if (out_victims && e->preempt_m)
     KT_HIP(e, hipMemcpyAsync(out_victims, e->d_preempt_victims.p, (size_t)n * (size_t)e->preempt_m, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// preempt, for gangs: the shortest victim prefix that lets a whole gang through (kt_kernels_preempt_gangs.hip)
+// ---------------------------------------------------------------------------------------------------
+// kt_preempt_gangs_launch: the refusals of preempt_locked in its order (with the gang defects in front, and "a pod twice" asked
+// per gang), then the same launches with kt_preempt_gangs in kt_preempt's place.  The result shares the one pending preempt result;
+// preempt_gangs tells the fetches apart.  The caller holds the launch lock.
+static int32_t preempt_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
+                                    const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream) {
+  int32_t rc = gangs_valid(e, n, n_gangs, gang_off);
+  if (rc != KT_OK) return rc;
+  if (n_cand < 0) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: n_cand = %lld", (long long)n_cand);
+  if ((n > 0 && !pod_rows) || (n_cand > 0 && !cand_rows)) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod_rows / cand_rows missing");
+  for (int64_t i = 0; i < n + n_cand; ++i) {
+    const int64_t r = i < n ? pod_rows[i] : cand_rows[i - n];
+    if (r < 0 || r >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "preempt gangs: pod row %lld", (long long)r);
+  }
+  {
+    std::vector<int64_t> sorted(cand_rows, cand_rows + n_cand);
+    std::sort(sorted.begin(), sorted.end());
+    for (int64_t j = 1; j < n_cand; ++j)
+      if (sorted[(size_t)j] == sorted[(size_t)j - 1])
+        return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod row %lld is a candidate twice", (long long)sorted[(size_t)j]);
+    for (int64_t i = 0; i < n; ++i)
+      if (std::binary_search(sorted.begin(), sorted.end(), pod_rows[i]))
+        return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod row %lld is a member and a candidate", (long long)pod_rows[i]);
+    // gangs are alternatives: a pod may be in several of them, but not twice in one (it would reserve twice)
+    for (int64_t g = 0; g < n_gangs; ++g) {
+      sorted.assign(pod_rows + gang_off[g], pod_rows + gang_off[g + 1]);
+      std::sort(sorted.begin(), sorted.end());
+      for (size_t j = 1; j < sorted.size(); ++j)
+        if (sorted[j] == sorted[j - 1])
+          return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod row %lld is in gang %lld twice", (long long)sorted[j], (long long)g);
+    }
+  }
+  const int32_t T = e->thr_rows_hi;  // (moved by throttle batches only, under this lock: ensure_ready below does not change it)
+  if ((double)n * (double)T > 2147483648.0 || (double)n_cand * (double)T > 2147483648.0 || ((double)n + (double)n_cand) * (double)T > 2147483648.0)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "preempt gangs: (n + n_cand) x throttle_rows = (%lld + %lld) x %d exceeds 2^31 matrix bytes", (long long)n,
+                   (long long)n_cand, T);
+  if (e->incremental) return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: not for KT_VARIANT_INCREMENTAL engines");
+  if (e->exchange_world > 1)
+    return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: the engine exchanges partials with %d ranks (one rank only)", e->exchange_world);
+  if (e->wide && e->req_sums_valid) return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: `used` is wider than int64 (kt_preempt_gangs reads int64 sums)");
+  if (n == 0) {  // (no gangs) nothing is launched
+    e->preempt_ready = true, e->preempt_gangs = true, e->preempt_n = 0, e->preempt_m = n_cand;
+    return KT_OK;
+  }
+  KT_HIP(e, hipSetDevice(e->device));
+  hipStream_t s = pick_stream(e, stream);
+  // the |request| sums probe where the sums are unknown, before the check slot or any result buffer is touched (as preempt_locked)
+  rc = ensure_ready(e, s);
+  if (rc == KT_OK) rc = request_sums_in_range(e, s);
+  if (rc != KT_OK) return rc;
+  if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: `used` is wider than int64 (kt_preempt_gangs reads int64 sums)");
+  const size_t vic = (size_t)n_gangs * (size_t)n_cand;
+  if (e->d_preempt_prefix.cap < (size_t)n_gangs || e->d_preempt_victims.cap < vic + 1 || e->d_preempt_blocker.cap < (size_t)n_gangs ||
+      e->d_preempt_gang_off.cap < (size_t)n_gangs + 1) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_preempt_launch)
+    if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+    KT_HIP(e, e->d_preempt_prefix.reserve((size_t)n_gangs));
+    KT_HIP(e, e->d_preempt_victims.reserve(vic + 1));
+    KT_HIP(e, e->d_preempt_blocker.reserve((size_t)n_gangs));
+    KT_HIP(e, e->d_preempt_gang_off.reserve((size_t)n_gangs + 1));
+  }
+  // the offsets travel on the launch's stream, behind an earlier launch's kernel; the caller's memory is not referenced after return
+  KT_HIP(e, hipMemcpyAsync(e->d_preempt_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  // ONE check over members ++ candidates: which throttles match which pod, and the error rows
+  std::vector<int64_t> rows((size_t)(n + n_cand));
+  std::copy(pod_rows, pod_rows + n, rows.begin());
+  std::copy(cand_rows, cand_rows + n_cand, rows.begin() + n);
+  const bool forecast_was_ready = e->forecast_ready;  // its result lives in buffers this call does not write: it stays fetchable
+  rc = check_launch_locked(e, n + n_cand, rows.data(), on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e->check_ready = false;  // the slot holds this call's rows (as with kt_preempt_launch): a pending kt_check_launch is gone
+  e->forecast_ready = forecast_was_ready;
+  if (rc != KT_OK) return rc;
+  if ((rc = preempt_reconcile_locked(e, now_s, now_ns, s)) != KT_OK) return rc;
+  const kt::AdmitPage pg{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  kt::launch_preempt_gangs(pg, n, n_cand, e->d_rows.p, n_gangs, e->d_preempt_gang_off.p, e->thr_rows_hi, on_equal != 0, e->d_status.p, e->d_summary.p,
+                           e->d_preempt_partial.p, e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p,
+                           e->d_preempt_victims.p, e->d_preempt_blocker.p, s);
+  KT_HIP(e, hipGetLastError());
+  e->last_stream = s;
+  e->preempt_ready = true, e->preempt_gangs = true, e->preempt_n = n_gangs, e->preempt_m = n_cand;
+  return KT_OK;
+}
+
+int32_t kt_preempt_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
+                                const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  return preempt_gangs_locked(e, n, pod_rows, n_gangs, gang_off, n_cand, cand_rows, now_s, now_ns, on_equal, stream);
+}
+
+int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefix, uint8_t* out_victims, int64_t* out_blocker) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (!e->preempt_ready || !e->preempt_gangs) return e->fail(KT_ERR_NOT_READY, "kt_preempt_gangs_fetch before kt_preempt_gangs_launch");
+  if (n_gangs < 0 || n_gangs > e->preempt_n)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "n_gangs=%lld, the last preempt gangs launch had %lld gangs", (long long)n_gangs, (long long)e->preempt_n);
+  if (n_gangs == 0) return KT_OK;
+  hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
+  if (out_prefix) KT_HIP(e, hipMemcpyAsync(out_prefix, e->d_preempt_prefix.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
+  if (out_victims && e->preempt_m)
+    KT_HIP(e, hipMemcpyAsync(out_victims, e->d_preempt_victims.p, (size_t)n_gangs * (size_t)e->preempt_m, hipMemcpyDeviceToHost, s));
+  if (out_blocker) KT_HIP(e, hipMemcpyAsync(out_blocker, e->d_preempt_blocker.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
   KT_HIP(e, hipStreamSynchronize(s));
   return KT_OK;
 }

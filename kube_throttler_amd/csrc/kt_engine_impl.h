@@ -346,6 +346,10 @@ struct kt_engine {
   DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
   bool preempt_ready = false;
   int64_t preempt_n = 0, preempt_m = 0;
+  // kt_preempt_gangs_launch shares that one pending result (prefix and victim bytes per GANG, preempt_n = the gangs); the kind tag
+  // says which fetch may read it.  Its offsets and the blocking member per gang live in buffers of their own
+  bool preempt_gangs = false;
+  DevBuf<int64_t> d_preempt_gang_off, d_preempt_blocker;
   // the last kt_forecast_launch: first passing position per pod and the verdict bytes [n][n_inst], on the device until
   // kt_forecast_fetch — buffers of their own: a pending forecast and a pending preempt result do not disturb each other;
   // d_forecast_inst_*: the instants as the kernel reads them

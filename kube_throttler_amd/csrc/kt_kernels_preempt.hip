@@ -26,21 +26,6 @@
 
 namespace kt {
 
-struct PreemptArgs {
-  AdmitPage pg;                       // pod flags, request rows and the throttle tables of the engine (state offsets unused)
-  const int64_t* rows;                // [n + m] pod table rows: the preemptors, then the candidates
-  int64_t n, m;
-  const uint8_t* status;              // [n + m][T]
-  const uint64_t* summary;            // [n + m]
-  const unsigned long long* partial;  // [T][partial_stride(D)], exact contributor counts
-  AmountTab calc;                     // the dry finalize's status.calculatedThreshold at `now`
-  const uint8_t* calc_updated;        // [T] it replaces the stored one (calculatedAt := now)
-  const uint8_t* error;               // [T] the reconcile is an error: the stored status stays
-  int64_t* prefix;                    // [n] out
-  uint8_t* victims;                   // [n][m] out (and the kernel's per-position verdict bits while it runs)
-  int32_t T, on_equal;
-};
-
 template <int DT>
 __global__ __launch_bounds__(kWave) void kt_preempt(const PreemptArgs a) {
   __shared__ uint32_t chunk_list[kPreemptChunk];
@@ -51,18 +36,7 @@ __global__ __launch_bounds__(kWave) void kt_preempt(const PreemptArgs a) {
   const ThrTables& tt = a.pg.tt;
   const int stride = partial_stride(D);
   const int64_t n = a.n, m = a.m;
-  // m_eff: the list ends before the first candidate whose PreFilter is an error or whose row is invalid
-  int64_t m_eff = m;
-  for (int64_t q0 = 0; q0 < m; q0 += kWave) {
-    const int64_t q = q0 + lane;
-    bool bad = false;
-    if (q < m) bad = a.summary[n + q] == 2ull || !(a.pg.pod_flags[a.rows[n + q]] & kPodValid);
-    const uint64_t mk = __ballot(bad);
-    if (mk != 0ull) {
-      m_eff = q0 + (__ffsll((long long)mk) - 1);
-      break;
-    }
-  }
+  const int64_t m_eff = preempt_m_eff(a, lane);  // the list ends before the first candidate whose PreFilter is an error or whose row is invalid
   for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {  // (wave-uniform: one preemptor per wave and turn)
     const int64_t p = a.rows[i];
     uint8_t* vic = a.victims + i * m;
@@ -79,10 +53,8 @@ __global__ __launch_bounds__(kWave) void kt_preempt(const PreemptArgs a) {
       for (uint32_t ai = 0; ai < n_c && !err && !never; ++ai) {
         const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[ai]);
         const uint32_t tf = tt.flags[t];
-        // a throttle whose reconcile is an error keeps its stored status: nothing of it depends on k
-        const bool stored = a.error[t] != 0 || (tf & (kThrValid | kThrResponsible)) != (kThrValid | kThrResponsible);
-        // the threshold the check reads behind the reconcile: calculatedThreshold once calculatedAt is set, else spec
-        const AmountTab& th = ((tf & kThrCalcAtNonzero) || a.calc_updated[t]) ? a.calc : tt.spec;
+        const bool stored = preempt_row_stored(tf, a.error[t]);
+        const AmountTab& th = preempt_threshold(tt, a.calc, tf, a.calc_updated[t]);
         const bool eq3 = admit_eq3(tf, eq);
         const bool th_hc = th.has_count[t] != 0, c_hc = a.calc.has_count[t] != 0, r_hc = tt.reserved.has_count[t] != 0;
         const int64_t th_c = th.count[t], c_c = a.calc.count[t], r_c = tt.reserved.count[t];
@@ -115,13 +87,11 @@ __global__ __launch_bounds__(kWave) void kt_preempt(const PreemptArgs a) {
           }
           never = f;
         } else {  // k = 0
-          const bool u_hc = pods_total > 0;
-          bool f = preempt_fails(1, th_hc, th_c, c_hc && u_hc && pods_total >= c_c, u_hc, pods_total, r_hc, r_c, eq3, eq);
+          bool f = preempt_count_fails(th_hc, th_c, c_hc, c_c, pods_total, r_hc, r_c, eq3, eq);
 #pragma unroll
           for (int d = 0; d < DT; ++d) {
             if (!need[d]) continue;
-            const bool u_pr = tot_c[d] > 0, c_pd = (c_p >> d) & 1u;
-            f |= preempt_fails(vp[d], (th_p >> d) & 1u, tv[d], c_pd && u_pr && tot_v[d] >= cv[d], u_pr, tot_v[d], (r_p >> d) & 1u, rv[d], eq3, eq);
+            f |= preempt_name_fails(vp[d], (th_p >> d) & 1u, tv[d], (c_p >> d) & 1u, cv[d], tot_v[d], tot_c[d], (r_p >> d) & 1u, rv[d], eq3, eq);
           }
           fail0 |= f;
         }
@@ -132,52 +102,27 @@ __global__ __launch_bounds__(kWave) void kt_preempt(const PreemptArgs a) {
         for (int d = 0; d < DT; ++d) car_v[d] = 0, car_c[d] = 0u;
         for (int64_t q0 = 0; q0 < m_eff && !never; q0 += kWave) {
           const int64_t q = q0 + lane;
-          const bool in = q < m_eff;
-          const int64_t c = in ? a.rows[n + q] : 0;
-          const uint32_t fl = in ? a.pg.pod_flags[c] : 0u;
-          const uint8_t sb = in ? a.status[(n + q) * (int64_t)T + t] : (uint8_t)0;
-          const bool contrib = in && (fl & (kCounted | kPodFinished)) == kCounted && sb != 0;
+          const PreemptCand L = preempt_cand(a, t, q, m_eff);
           bool f = false;
           if (!stored) {
-            const int64_t pre_pods = car_pods + (int64_t)wave_inclusive_scan<uint32_t>(contrib ? 1u : 0u, lane);
-            car_pods = __shfl(pre_pods, kWave - 1);
-            const int64_t u_c = pods_total - pre_pods;
-            const bool u_hc = u_c > 0;
-            f = preempt_fails(1, th_hc, th_c, c_hc && u_hc && u_c >= c_c, u_hc, u_c, r_hc, r_c, eq3, eq);
+            const int64_t pre_pods = preempt_scan_pods(L, lane, car_pods);
+            f = preempt_count_fails(th_hc, th_c, c_hc, c_c, pods_total - pre_pods, r_hc, r_c, eq3, eq);
 #pragma unroll
             for (int d = 0; d < DT; ++d) {
               if (!need[d]) continue;  // (wave-uniform)
-              const bool has = contrib && (((fl >> kPresentShift) >> d) & 1u);
-              const int64_t v = has ? a.pg.req[c * DS + d] : 0;
-              const int64_t pre_v = car_v[d] + wave_inclusive_scan<int64_t>(v, lane);
-              const uint32_t pre_c = car_c[d] + wave_inclusive_scan<uint32_t>(has ? 1u : 0u, lane);
-              car_v[d] = __shfl(pre_v, kWave - 1), car_c[d] = (uint32_t)__shfl((int)pre_c, kWave - 1);
-              // presence is exact: the name stays in `used` only while a remaining counted pod carries it
-              const bool u_pr = tot_c[d] - (int64_t)pre_c > 0;
-              const int64_t u_v = tot_v[d] - pre_v;
-              const bool c_pd = (c_p >> d) & 1u;
-              f |= preempt_fails(vp[d], (th_p >> d) & 1u, tv[d], c_pd && u_pr && u_v >= cv[d], u_pr, u_v, (r_p >> d) & 1u, rv[d], eq3, eq);
+              int64_t pre_v;
+              uint32_t pre_c;
+              preempt_scan_name(a, L, d, lane, car_v[d], car_c[d], &pre_v, &pre_c);
+              f |= preempt_name_fails(vp[d], (th_p >> d) & 1u, tv[d], (c_p >> d) & 1u, cv[d], tot_v[d] - pre_v, tot_c[d] - (int64_t)pre_c, (r_p >> d) & 1u,
+                                      rv[d], eq3, eq);
             }
           }
-          if (in && (contrib || f)) vic[q] |= (uint8_t)((contrib ? 1u : 0u) | (f ? 2u : 0u));
+          if (L.in && (L.contrib || f)) vic[q] |= (uint8_t)((L.contrib ? 1u : 0u) | (f ? 2u : 0u));
         }
       }
       __syncthreads();  // the next chunk rewrites the list
     }
-    int64_t ans = -1;
-    if (!err && !never) {
-      if (!fail0) ans = 0;
-      else
-        for (int64_t q0 = 0; q0 < m_eff; q0 += kWave) {
-          const int64_t q = q0 + lane;
-          const uint64_t mk = __ballot(q < m_eff && !(vic[q] & 2u));
-          if (mk != 0ull) {
-            ans = q0 + __ffsll((long long)mk);  // the first passing position + 1 = the prefix length
-            break;
-          }
-        }
-    }
-    for (int64_t q = lane; q < m; q += kWave) vic[q] = (q < ans && (vic[q] & 1u)) ? (uint8_t)1 : (uint8_t)0;
+    const int64_t ans = preempt_answer(vic, m, m_eff, !err && !never, fail0, lane);
     if (lane == 0) a.prefix[i] = ans;
   }
 }

@@ -119,6 +119,12 @@ bool launch_headroom(const AdmitPage* pages, int n_pages, AdmitPage* pages_dev, 
 void launch_preempt(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int T, bool on_equal, const uint8_t* status,
                     const uint64_t* summary, const unsigned long long* partial, const AmountTab& calc, const uint8_t* calc_updated,
                     const uint8_t* error, int64_t* prefix, uint8_t* victims, hipStream_t s);
+// the gang form (kt_kernels_preempt_gangs.hip): one wave per gang, the same inputs over members ++ candidates (n members in all);
+// gang g is the queue positions [gang_off_dev[g], gang_off_dev[g + 1]) of rows_dev (device memory).  prefix [n_gangs], victims
+// [n_gangs][m] and blocker [n_gangs] (the first member that is not Success in S_0, a queue position; -1 with prefix 0) out
+void launch_preempt_gangs(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int64_t n_gangs, const int64_t* gang_off_dev, int T,
+                          bool on_equal, const uint8_t* status, const uint64_t* summary, const unsigned long long* partial, const AmountTab& calc,
+                          const uint8_t* calc_updated, const uint8_t* error, int64_t* prefix, uint8_t* victims, int64_t* blocker, hipStream_t s);
 // the reprieve pass behind it (kt_kernels_reprieve.hip): one wave per preemptor walks its masked victims back, last first, and
 // rewrites victims [n][m] in place; prefix is read.  The list of a preemptor's reconciled affecting throttles lives in LDS up to
 // reprieve_lds_cap(D, limit) entries (limit: a test hook that lowers the capacity, 0 = none), beyond that in `ws`:

@@ -1279,6 +1279,54 @@ PreemptResult KubeThrottler::Preempt(const std::string& pod_key, const std::vect
   return out;
 }
 
+// Which of the candidates have to go before the whole gang is admitted: kt_preempt_gangs_launch + kt_preempt_gangs_fetch with the
+// members as ONE gang on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).  Nothing is changed.
+GangPreemptResult KubeThrottler::PreemptGang(const std::vector<std::string>& member_keys, const std::vector<std::string>& candidate_keys,
+                                             const std::string& now_rfc3339) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  GangPreemptResult res;
+  PreemptResult& out = res.preempt;
+  if (p.pages.size() > 1) {
+    out.error = "PreemptGang: the mirror runs on " + std::to_string(p.pages.size()) + " pages (more than " + std::to_string(p.D) +
+                " resource names); the preemption query has no paged form";
+    return res;
+  }
+  int64_t now_s;
+  int32_t now_ns;
+  if (!ParseRFC3339(now_rfc3339, &now_s, &now_ns, &out.error)) return res;
+  if (member_keys.empty()) {
+    out.error = "PreemptGang: a gang without members";
+    return res;
+  }
+  std::vector<int64_t> rows(member_keys.size()), cand(candidate_keys.size());
+  for (size_t i = 0; i < rows.size(); ++i)
+    if ((rows[i] = p.pod_rows.find(member_keys[i])) < 0) {
+      out.error = "pod " + member_keys[i] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+  for (size_t j = 0; j < cand.size(); ++j)
+    if ((cand[j] = p.pod_rows.find(candidate_keys[j])) < 0) {
+      out.error = "candidate " + candidate_keys[j] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+  const int64_t gang_off[2] = {0, (int64_t)rows.size()};
+  int64_t prefix = KT_PREEMPT_NONE, blocker = -1;
+  std::vector<uint8_t> mask(cand.size() + 1);
+  int32_t rc = kt_preempt_gangs_launch(p.e, (int64_t)rows.size(), rows.data(), 1, gang_off, (int64_t)cand.size(), cand.data(), now_s, now_ns,
+                                       /*isThrottledOnEqual=*/0, nullptr);
+  if (rc == KT_OK) rc = kt_preempt_gangs_fetch(p.e, 1, &prefix, mask.data(), &blocker);
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    return res;
+  }
+  out.none = prefix < 0;
+  for (size_t j = 0; j < cand.size(); ++j)
+    if (mask[j]) out.victims.push_back(candidate_keys[j]);
+  if (blocker >= 0 && (size_t)blocker < member_keys.size()) res.blocker = member_keys[(size_t)blocker];
+  return res;
+}
+
 // When does this pod pass PreFilter: the override boundaries of the window from the engine's host copy of the specs
 // (kt_override_instants: every begin, and end + 1 ns — the first instant an override is no longer active), `now` in front, one
 // kt_forecast_launch + kt_forecast_fetch over them on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).

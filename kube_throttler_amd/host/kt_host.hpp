@@ -166,6 +166,12 @@ struct PreemptResult {
   std::string error;                 // not empty: the call failed (unknown pod, a paged mirror, engine error)
 };
 
+// PreemptGang: the pods that would have to go before a whole gang is admitted, and the member that stops it as things stand
+struct GangPreemptResult {
+  PreemptResult preempt;  // none / victims / error as for Preempt, for the gang as a whole
+  std::string blocker;    // Pod::Key() of the first member that is not admitted with nothing deleted; empty: the gang already passes
+};
+
 // RetryAfter: the first instant at which a blocked pod passes PreFilter, among `now` and the override boundaries up to the horizon
 struct RetryAfterResult {
   bool has = false;              // some instant of the window lets the pod through: `instant` is the first
@@ -244,6 +250,14 @@ class KubeThrottler {
   // The names that remain are a minimal set: with non-negative requests no single one of them can stay.
   PreemptResult Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys, const std::string& now_rfc3339,
                         bool reprieve = false);
+  // ---- who has to go for a whole job: the shortest prefix of `candidate_keys` whose deletion, followed by a reconcile of every
+  // throttle at `now`, lets AdmitGangs({member_keys}) admit the gang — each admitted member reserves against the throttles the later
+  // members meet, so this is NOT the longest of the members' own prefixes.  ONE engine call (kt_preempt_gangs_launch +
+  // kt_preempt_gangs_fetch) instead of delete + ReconcileAll + AdmitGangs per prefix.  A dry run: nothing is deleted, reserved or
+  // stored, and the reserved totals are read as they stand.  A member named twice, a member among the candidates and a mirror on
+  // several pages answer an error.
+  GangPreemptResult PreemptGang(const std::vector<std::string>& member_keys, const std::vector<std::string>& candidate_keys,
+                                const std::string& now_rfc3339);
   // The first instant in [now, now + horizon] at which PreFilter(pod) is Success if every throttle were reconciled then
   // (temporaryThresholdOverrides begin and end): kt_override_instants for the boundaries, ONE kt_forecast_launch over
   // now ++ boundaries.  What a PreFilter rejection path asks to set a backoff.  A dry run; a mirror on several pages refuses.

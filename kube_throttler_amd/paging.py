@@ -468,6 +468,104 @@ def _reprieve(snap, ctx, affected, contributes, creq, req, eq, prefix, victims):
                 entry[2:] = [val, cnt, pods]
 
 
+# ---- preempt, for gangs: the shortest victim prefix that lets a whole gang in (kt_preempt_gangs_launch), in closed form ----
+def _gang_first_stopped(members, hit, reqs, thr_amounts, used, res, res_count, eq3, eq):
+    """One throttle against one state of its `used`: the position of the first member it affects (``hit``) and stops, every
+    earlier member it affects having reserved (None: it stops nobody).  ``thr_amounts``: (threshold names, threshold count);
+    ``used``: (count flagged, count present, count, {name: (flagged, present, value)})."""
+    (th, th_count), (c_flag, u_hc, u_c, names) = thr_amounts, used
+    rv, rp, rc, r_hc = dict(res), set(res), res_count or 0, res_count is not None
+    for j in range(len(members)):
+        if not hit[j]:
+            continue
+        bad = _amount_fails(1, th_count, c_flag, u_hc, u_c, r_hc, rc, eq3, eq)
+        for d, v in reqs[j].items():
+            if v == 0:
+                continue
+            flagged, u_pr, uv = names.get(d, (False, False, 0))
+            bad = bad or _amount_fails(v, th.get(d), flagged, u_pr, uv, d in rp, rv.get(d, 0), eq3, eq)
+        if bad:
+            return j
+        for d, v in reqs[j].items():  # Reserve: every name the pod carries becomes present, zero-valued ones included
+            rv[d] = rv.get(d, 0) + v
+            rp.add(d)
+        rc, r_hc = rc + 1, True
+    return None
+
+
+def preempt_gangs_of(snap, member_rows, cand_rows, now, on_equal=False, ctx=None):
+    """kt_preempt_gangs_launch for one gang, in closed form on a Snapshot (no GPU) -> (prefix, victims [len(cand_rows)], blocker).
+    prefix: the smallest k for which an in-order admission of ``member_rows`` — PreFilter, and on Success Reserve on every
+    throttle that affects the member — admits every member once the candidates ``cand_rows[:k]`` are gone and every responsible
+    throttle has been reconciled at ``now``; -1: no prefix does, a member's PreFilter is an Error or its row is invalid.
+    victims[j] = 1 iff j < prefix, the candidate is counted and a throttle that affects some member matches it.  blocker: the
+    position in ``member_rows`` of the first member that is not Success with nothing deleted (-1 when prefix == 0).
+    Per throttle the members meet `used` lowered by a prefix sum over the candidates and `reserved` raised by a prefix sum over
+    the earlier members it affects: both are formed directly, nothing is admitted step by step across throttles."""
+    ctx = preempt_context(snap, now) if ctx is None else ctx
+    members, cands, eq = [int(p) for p in member_rows], [int(c) for c in cand_rows], bool(on_equal)
+    m, g = len(cands), len(members)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap.n_pods and bool(int(snap.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    m_eff = m
+    for j, c in enumerate(cands):
+        if not (0 <= c < snap.n_pods) or not int(snap.pod_flags[c]) & S.POD_VALID or affected_throttles(snap, c)[0]:
+            m_eff = j
+            break
+    counted = lambda c: (int(snap.pod_flags[c]) & (_COUNTABLE | S.POD_FINISHED)) == _COUNTABLE
+    reqs = [pod_requests(snap, p) if 0 <= p < snap.n_pods else {} for p in members]
+    creq = [pod_requests(snap, c) if counted(c) else {} for c in cands[:m_eff]]
+    union = sorted(set().union(*affected)) if affected else []
+    contributes = [[counted(c) and t in ctx["match"].get(c, ()) for c in cands[:m_eff]] for t in union]
+    fails = [False] * (m_eff + 1)  # fails[k]: some (member, throttle, amount) stops the gang in S_k
+    never = bad_at is not None
+    block0 = g if bad_at is None else bad_at
+    for ti, t in enumerate(union):
+        th = ctx["thr"][t]
+        f = int(snap.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+        hit = [t in a for a in affected]
+        if th["error"]:  # the stored status stays, in every S_k
+            used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+            sth = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+            flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+            names = {d: (bool(flg >> d & 1), d in used, used.get(d, 0)) for d in range(snap.D)}
+            first = _gang_first_stopped(members, hit, reqs, sth, (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names),
+                                        res, res_count, eq3, eq)
+            if first is not None:
+                never, block0 = True, min(block0, first)
+            continue
+        val, cnt, pods = dict(th["val"]), dict(th["cnt"]), th["pods"]
+        for k in range(m_eff + 1):
+            if k > 0 and contributes[ti][k - 1]:
+                pods -= 1
+                for d, v in creq[k - 1].items():
+                    val[d] -= v
+                    cnt[d] -= 1
+            cc = th["calc_count"]
+            names = {}
+            for d in range(snap.D):
+                u_pr, cv = cnt.get(d, 0) > 0, th["calc"].get(d)
+                names[d] = (cv is not None and u_pr and val.get(d, 0) >= cv, u_pr, val.get(d, 0))
+            first = _gang_first_stopped(members, hit, reqs, (th["th"], th["th_count"]),
+                                        (cc is not None and pods > 0 and pods >= cc, pods > 0, pods, names), res, res_count, eq3, eq)
+            if first is not None:
+                fails[k] = True
+                if k == 0:
+                    block0 = min(block0, first)
+    prefix = -1 if never else next((k for k in range(m_eff + 1) if not fails[k]), -1)
+    victims = [0] * m
+    for j in range(max(prefix, 0)):
+        victims[j] = int(any(contributes[ti][j] for ti in range(len(union))))
+    return prefix, victims, (-1 if prefix == 0 or block0 >= g else block0)
+
+
 # ---- forecast: the first instant at which a blocked pod passes (kt_forecast_launch), in closed form on a Snapshot ----
 def _instant(t):
     return int(t[0]), int(t[1])
