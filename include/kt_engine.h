@@ -452,14 +452,45 @@ int32_t kt_preempt_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_r
  *      sums are unknown).  A refused call leaves the check slot, the reconcile report and every result buffer alone.  n == 0 is
  *      allowed only with n_gangs == 0: KT_OK, nothing is launched.
  *      Slots: the launch uses the check slot and the reconcile report exactly as kt_preempt_launch does, and its result SHARES the
- *      one pending preempt result, as kt_preempt_reprieve_launch does: a later launch of any of the three replaces it.
+ *      one pending preempt result, as kt_preempt_reprieve_launch does: a later launch of any of the preempt calls replaces it.
  *      kt_preempt_fetch after a gang launch answers KT_ERR_NOT_READY, and so does kt_preempt_gangs_fetch after a plain launch; a
  *      pending kt_forecast_launch stays fetchable.  kt_preempt_gangs_fetch synchronises.
- *      Out of scope: a reprieve pass for gangs, the paged form, several ranks. -------------------------------------------- */
+ *      Out of scope: the paged form, several ranks (the reprieve pass that shrinks a gang's victim set further is
+ *      kt_preempt_gangs_reprieve_launch below). ------------------------------------------------------------------------- */
 int32_t kt_preempt_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
                                 const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream);
 int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefix /* [n_gangs], nullable */,
                                uint8_t* out_victims /* [n_gangs][n_cand], nullable */, int64_t* out_blocker /* [n_gangs], nullable */);
+/* ---- preempt, for gangs, reprieved: the prefix of kt_preempt_gangs_launch with its victim mask shrunk to a minimal set — what
+ *      kt_preempt_reprieve_launch is to kt_preempt_launch.  The members' own reprieved sets do not compose into the gang's answer:
+ *      each admitted member reserves against the throttles the later members meet (two members asking 3 each under a threshold of
+ *      10 with four running pods of 2: each member alone keeps one victim, the gang needs two).
+ *      Notation as for kt_preempt_gangs_launch: counted pods, the candidates c_0 .. c_{m-1}, the m_eff cut, gang g = the queue
+ *      positions [gang_off[g], gang_off[g + 1]).  For gang g let k = out_prefix[g] and M the victim mask, exactly as
+ *      kt_preempt_gangs_launch reports them.  k <= 0: the row is all zero.  Otherwise V = M, and for j = k-1, k-2, .., 0 in that
+ *      order, for each j with M[j] = 1, let V' = V \ {c_j}: state S(V') is the cluster in which exactly the pods of V' no longer
+ *      exist and every responsible throttle has been reconciled at `now` (stored reserved amounts unchanged; a throttle whose
+ *      reconcile is an error, or that is not valid and responsible, keeps its stored status: the rule of S_k).  If a dry
+ *      kt_admit_gangs_launch of the one gang g, with S(V') as the stored status, admits it — members in order, each sees the
+ *      stored reservations plus what the earlier members of its gang reserved, every verdict Success; Reserve exactly kt_admit's:
+ *      the value of every name carried, the presence of all names carried (zero-valued ones included), count + 1 — then V := V',
+ *      c_j is reprieved; otherwise c_j stays a victim.
+ *      out_victims[g][j] = 1 iff c_j is in V at the end; out_prefix and out_blocker are what kt_preempt_gangs_launch reports.
+ *      Presence in `used` is exact, by contributor counts, as in kt_preempt_reprieve_launch.  The definition is the walk itself,
+ *      with no monotonicity assumption: requests of either sign are answered as the walk answers them.  Gangs are judged
+ *      independently of each other.  A gang of one pod yields byte for byte what kt_preempt_reprieve_launch yields for that pod.
+ *      The call is kt_preempt_gangs_launch followed, on the same stream, by ONE launch of kt_preempt_gangs_reprieve
+ *      (csrc/kt_kernels_preempt_gangs_reprieve.hip) that rewrites the victim bytes in place: one wave per gang, lanes = the
+ *      reconciled throttles that affect some member, each holding the `used` of its throttle in the current state (in LDS, or in
+ *      the engine's reprieve workspace where the list outgrows it) and judging the members in order on it under the reserved
+ *      prefix.  A gang with prefix <= 0 costs one load; n_cand == 0 launches no walk.
+ *      Every refusal, its code and its order, "a refused call leaves the check slot, the reconcile report and every result buffer
+ *      alone", n == 0 only with n_gangs == 0, and the slot rules are those of kt_preempt_gangs_launch.  The result is the one
+ *      pending gang result, fetched with kt_preempt_gangs_fetch: a later launch of any of the four preempt calls replaces it; a
+ *      pending kt_forecast_launch stays fetchable.
+ *      Out of scope: the paged form, several ranks. --------------------------------------------------------------------- */
+int32_t kt_preempt_gangs_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
+                                         const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream);
 /* ---- forecast: the first instant at which a blocked pod passes — the one axis no other query looks along.
  *      temporaryThresholdOverrides make every threshold a step function of the clock (throttle_types.go:65-106,
  *      temporary_threshold_override.go:57-70): a pod that PreFilter rejects now may pass when a night-time override begins or a

@@ -44,7 +44,7 @@ const (
 type Engine struct {
 	h    *C.kt_engine
 	dims int
-	mu   sync.Mutex // the engine's ONE check slot: every method that takes it (Check, AffectedPods, Admit, AdmitGangs, Headroom, Preempt, PreemptReprieve, PreemptGangs) holds mu from its launch to its fetch; Verdict's one-pod check runs beside the slot and takes no lock
+	mu   sync.Mutex // the engine's ONE check slot: every method that takes it (Check, AffectedPods, Admit, AdmitGangs, Headroom, Preempt, PreemptReprieve, PreemptGangs, PreemptGangsReprieve) holds mu from its launch to its fetch; Verdict's one-pod check runs beside the slot and takes no lock
 }
 
 // New creates an engine for `dims` resource names (<= 16), pods with up to maxLabels labels and the given row capacities.
@@ -459,14 +459,37 @@ func (e *Engine) preempt(rows, cands []int64, nowS int64, nowNs int32, onEqual, 
 // Preempt, and like Preempt under e.mu from its launch to its fetch; the result shares Preempt's pending slot.  Not compiled in
 // this repository (no Go toolchain in its build).
 func (e *Engine) PreemptGangs(rows, gangOff, cands []int64, nowS int64, nowNs int32, onEqual bool) (prefix []int64, victims []uint8, blocker []int64, err error) {
+	return e.preemptGangs(rows, gangOff, cands, nowS, nowNs, onEqual, false)
+}
+
+// PreemptGangsReprieve is PreemptGangs followed by the reprieve walk per gang (kt_preempt_gangs_reprieve_launch + the same
+// kt_preempt_gangs_fetch): prefix and blocker are what PreemptGangs answers, the victim bytes are what is left once the masked
+// candidates have been put back one by one, the last of the list first, each staying back as long as a dry AdmitGangs of the one
+// gang still admits it behind a reconcile at now.  The members' own PreemptReprieve sets do not compose into this one: every
+// admitted member reserves against the throttles the later members meet.  A gang of one pod gets what PreemptReprieve answers for
+// that pod.  Same refusals, slot rules and dry run as PreemptGangs.  Not compiled in this repository (no Go toolchain in its build).
+func (e *Engine) PreemptGangsReprieve(rows, gangOff, cands []int64, nowS int64, nowNs int32, onEqual bool) (prefix []int64, victims []uint8, blocker []int64, err error) {
+	return e.preemptGangs(rows, gangOff, cands, nowS, nowNs, onEqual, true)
+}
+
+// preemptGangs is the one body of PreemptGangs and PreemptGangsReprieve: the launch (with or without the reprieve pass) and
+// kt_preempt_gangs_fetch, under e.mu from the one to the other.
+func (e *Engine) preemptGangs(rows, gangOff, cands []int64, nowS int64, nowNs int32, onEqual, reprieve bool) (prefix []int64, victims []uint8, blocker []int64, err error) {
 	if len(gangOff) < 2 {
 		return nil, nil, nil, nil
 	}
 	nGangs := len(gangOff) - 1
 	e.mu.Lock()
 	defer e.mu.Unlock()
-	if rc := C.kt_preempt_gangs_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(nGangs), i64(gangOff), C.int64_t(len(cands)),
-		i64(cands), C.int64_t(nowS), C.int32_t(nowNs), b2i(onEqual), nil); rc != C.KT_OK {
+	var rc C.int32_t
+	if reprieve {
+		rc = C.kt_preempt_gangs_reprieve_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(nGangs), i64(gangOff), C.int64_t(len(cands)),
+			i64(cands), C.int64_t(nowS), C.int32_t(nowNs), b2i(onEqual), nil)
+	} else {
+		rc = C.kt_preempt_gangs_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(nGangs), i64(gangOff), C.int64_t(len(cands)),
+			i64(cands), C.int64_t(nowS), C.int32_t(nowNs), b2i(onEqual), nil)
+	}
+	if rc != C.KT_OK {
 		return nil, nil, nil, e.err(rc)
 	}
 	prefix = make([]int64, nGangs)

@@ -6,8 +6,14 @@
 // grid sizes; and what kt_preempt and kt_preempt_gangs share on top: their arguments, the list cut, which rows keep their stored
 // status and which threshold a check reads behind the reconcile, the pieces of the k >= 1 block body (a lane's candidate, the
 // scans with their carries, `used` with a prefix gone against one amount) and the derivation of prefix and victim mask from the
-// verdict bits.  The page descriptor itself (AdmitPage) is host-visible: kt_launch.h.
+// verdict bits; what kt_preempt_gangs and kt_preempt_gangs_reprieve share: the members of a gang in order on one throttle against one
+// state of `used` (gang_walk); and what the two reprieve kernels (kt_preempt_reprieve, kt_kernels_preempt_gangs_reprieve.hip:
+// kt_preempt_gangs_reprieve) share: arguments, the list's state in LDS or HBM with its sizes, the list (counted, then gathered) and
+// the walk over the masked positions, generic in who is judged.  The page descriptor itself (AdmitPage) is host-visible: kt_launch.h.
 #pragma once
+#include <algorithm>
+#include <type_traits>
+
 #include "kt_index_device.h"
 
 namespace kt {
@@ -224,6 +230,210 @@ __device__ __forceinline__ int64_t preempt_answer(uint8_t* vic, int64_t m, int64
   }
   for (int64_t q = lane; q < m; q += kWave) vic[q] = (q < ans && (vic[q] & 1u)) ? (uint8_t)1 : (uint8_t)0;
   return ans;
+}
+
+// ---- what kt_preempt_gangs and kt_preempt_gangs_reprieve share -----------------------------------------------------------------
+// `used` of one throttle as a lane (or the whole wave) sees it in some state: what the four steps read of it
+template <int DT>
+struct GangUsed {
+  bool c_flag, u_hc;     // the pod count: status.throttled, presence
+  int64_t u_c;
+  uint32_t flag_m, pr_m;  // per name: status.throttled, presence
+  int64_t u_v[DT];
+};
+
+// the throttle as the members meet it: threshold, step 3's on-equal, the stored reserved row
+template <int DT>
+struct GangThr {
+  bool th_hc, r_hc, eq3, eq;
+  int64_t th_c, r_c;
+  uint32_t th_p, r_p;
+  int64_t tv[DT], rv[DT];
+};
+
+// The members [i0, i1) in order on throttle t against one state of `used`: the first queue position whose member t affects and
+// stops (i1: none), every earlier member having reserved.  `a` is PreemptArgs or ReprieveArgs (page, rows, status matrix, T).
+// kt_preempt_gangs calls it with a wave-uniform throttle (everything but `u` is uniform), the gang reprieve with the lane's own.
+template <int DT, class ARGS>
+__device__ __forceinline__ int64_t gang_walk(const ARGS& a, uint32_t t, int64_t i0, int64_t i1, const GangThr<DT>& g, const GangUsed<DT>& u) {
+  const int D = a.pg.D, DS = a.pg.DS;
+  int64_t rv[DT], rc = g.r_hc ? g.r_c : 0;
+  uint32_t rp = g.r_p;
+  bool rhc = g.r_hc;
+#pragma unroll
+  for (int d = 0; d < DT; ++d) rv[d] = ((g.r_p >> d) & 1u) ? g.rv[d] : 0;
+  int64_t first = i1;
+  for (int64_t i = i0; i < i1; ++i) {
+    if (a.status[i * (int64_t)a.T + t] == 0) continue;  // t does not affect the member: no check, no reservation
+    const int64_t p = a.rows[i];
+    const uint32_t present = a.pg.pod_flags[p] >> kPresentShift;
+    bool f = preempt_fails(1, g.th_hc, g.th_c, u.c_flag, u.u_hc, u.u_c, rhc, rc, g.eq3, g.eq);
+#pragma unroll
+    for (int d = 0; d < DT; ++d) {
+      if (d >= D) continue;
+      const int64_t vp = a.pg.req[p * DS + d];
+      // a name the pod does not request passes every step
+      if (vp != 0) f |= preempt_fails(vp, (g.th_p >> d) & 1u, g.tv[d], (u.flag_m >> d) & 1u, (u.pr_m >> d) & 1u, u.u_v[d], (rp >> d) & 1u, rv[d], g.eq3, g.eq);
+      if ((present >> d) & 1u) rv[d] += vp;  // Reserve: the value of every name it carries ...
+    }
+    rp |= present & ((1u << D) - 1u);  // ... the presence of all of them, zero-valued ones included
+    rc += 1, rhc = true;
+    if (f && first == i1) first = i;
+  }
+  return first;
+}
+
+// ---- what kt_preempt_reprieve and kt_preempt_gangs_reprieve share --------------------------------------------------------------
+constexpr int kReprieveLdsBytes = 16 * 1024;         // the list's state in LDS: 20 KiB per wave with the chunk list, 8 waves per CU
+constexpr size_t kReprieveWsBudget = 64ull << 20;    // the HBM workspace of one launch: grid x slot bytes stay below (one slot at least)
+
+__host__ __device__ inline uint32_t reprieve_entry_bytes(int D) { return 12u + 12u * (uint32_t)D; }
+inline size_t reprieve_slot_bytes(int T, int D) { return ((size_t)T * reprieve_entry_bytes(D) + 15u) & ~(size_t)15u; }
+// the grid over n preemptors (gangs): kPreemptMaxBlocks at the most, and where a list may outgrow LDS no more than the workspace
+// budget has slots for
+inline int reprieve_blocks(int T, int D, int64_t n, uint32_t lds_cap) {
+  int64_t blocks = n < kPreemptMaxBlocks ? n : kPreemptMaxBlocks;
+  if ((uint32_t)T > lds_cap) {  // a list may outgrow LDS: every workgroup owns a slot
+    const int64_t fit = (int64_t)(kReprieveWsBudget / reprieve_slot_bytes(T, D));
+    blocks = std::min(blocks, std::max<int64_t>(fit, 1));
+  }
+  return (int)std::max<int64_t>(blocks, 1);
+}
+
+struct ReprieveArgs {
+  AdmitPage pg;                       // pod flags, request rows and the throttle tables of the engine (state offsets unused)
+  const int64_t* rows;                // [n + m] pod table rows: the preemptors (the gangs' members), then the candidates
+  int64_t n, m;
+  const uint8_t* status;              // [n + m][T]
+  const unsigned long long* partial;  // [T][partial_stride(D)], exact contributor counts
+  AmountTab calc;                     // the dry finalize's status.calculatedThreshold at `now`
+  const uint8_t* calc_updated;        // [T]
+  const uint8_t* error;               // [T]
+  const int64_t* prefix;              // [n] ([n_gangs]) as the prefix kernel left it
+  uint8_t* victims;                   // [n][m] ([n_gangs][m]) in: the prefix mask, out: the reprieved set
+  unsigned char* ws;                  // gridDim.x slots of ws_slot bytes (nullptr: T <= lds_cap, no list outgrows LDS)
+  size_t ws_slot;
+  int32_t T, on_equal;
+  uint32_t lds_cap;                   // entries the LDS state holds
+};
+
+// the list's state, field by field, in LDS or in HBM
+template <bool IN_LDS>
+struct ReprieveState {
+  typedef typename std::conditional<IN_LDS, KT_LDS int64_t*, int64_t*>::type p64;
+  typedef typename std::conditional<IN_LDS, KT_LDS uint32_t*, uint32_t*>::type p32;
+  typedef typename std::conditional<IN_LDS, KT_LDS unsigned char*, unsigned char*>::type pbyte;
+  p64 pods;  // [cap] counted pods
+  p64 uv;    // [D][cap] `used` value per resource name
+  p32 uc;    // [D][cap] contributors per resource name
+  p32 tl;    // [cap] throttle row
+  uint32_t cap;
+  __device__ __forceinline__ ReprieveState(pbyte base, uint32_t cap_, int D) : cap(cap_) {
+    pods = (p64)base;
+    uv = (p64)(base + (size_t)8 * cap_);
+    uc = (p32)(base + (size_t)8 * cap_ * (1 + D));
+    tl = uc + (size_t)D * cap_;
+  }
+};
+
+// a throttle whose reconcile is an error (or that nobody reconciles) keeps its stored status: nothing of it depends on V
+__device__ __forceinline__ bool reprieve_stored(const ReprieveArgs& a, uint32_t t) { return preempt_row_stored(a.pg.tt.flags[t], a.error[t]); }
+
+// The affecting throttles that are reconciled — chunk(c0, list, &err) appends one chunk of the matrix row (of the union of the
+// members' rows) to the chunk list: counted (ST = void) or gathered into the state with the aggregate's totals; returns the
+// wave-uniform list length
+template <int DT, bool GATHER, class ST, class CHUNK>
+__device__ __forceinline__ uint32_t reprieve_list(const ReprieveArgs& a, const CHUNK& chunk, lds_u32wp list, ST* st, uint32_t lane) {
+  const int T = a.T, D = a.pg.D;
+  const int stride = partial_stride(D);
+  uint32_t n_list = 0;
+  for (int c0 = 0; c0 < T; c0 += kPreemptChunk) {
+    bool err_c = false;  // (prefix > 0: the row holds no error byte)
+    const uint32_t n_c = chunk(c0, list, &err_c);
+    __syncthreads();  // (one wave: the list's entries are read by other lanes than wrote them)
+    for (uint32_t a0 = 0; a0 < n_c; a0 += kWave) {
+      const uint32_t ai = a0 + lane;
+      const uint32_t t = ai < n_c ? list[ai] : 0u;
+      const bool keep = ai < n_c && !reprieve_stored(a, t);
+      const uint64_t mk = __ballot(keep);
+      if constexpr (GATHER) {
+        const uint32_t e = n_list + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        if (keep && e < st->cap) {
+          const unsigned long long* prow = a.partial + (size_t)t * stride;
+          st->tl[e] = t;
+          st->pods[e] = (int64_t)prow[partial_off_pods(D)];
+#pragma unroll
+          for (int d = 0; d < DT; ++d) {
+            if (d >= D) continue;
+            st->uv[(size_t)d * st->cap + e] = (int64_t)prow[d];
+            st->uc[(size_t)d * st->cap + e] = (uint32_t)prow[partial_off_presence(D) + d];
+          }
+        }
+      }
+      n_list += (uint32_t)__popcll(mk);
+    }
+    __syncthreads();  // the next chunk rewrites the chunk list
+  }
+  return n_list;
+}
+
+// The walk over the masked positions below k of one row of the victim buffer, on a gathered list.  `track`: the names whose state
+// is kept (wave-uniform); judge.step<JUDGE, SIGN>(st, n_list, crow, cfl, cv, lane) is one candidate against the list — JUDGE: does
+// some entry whose throttle matches it stop whoever is judged with the candidate back (per lane: balloted here), nothing is
+// written; otherwise the candidate's amounts are added to (SIGN = 1) or taken off (SIGN = -1) the state of every such entry.
+template <int DT, class ST, class JUDGE>
+__device__ __forceinline__ void reprieve_walk_list(const ReprieveArgs& a, ST& st, uint32_t n_list, uint8_t* vic, int64_t k, uint32_t track,
+                                                   const JUDGE& judge, uint32_t lane) {
+  const int T = a.T, D = a.pg.D, DS = a.pg.DS;
+  const int64_t n = a.n;
+  int64_t cv[DT];
+#pragma unroll
+  for (int d = 0; d < DT; ++d) cv[d] = 0;
+  // the masked positions of one block of 64 candidates: their rows and flags come in with one load each
+  auto block = [&](int64_t q0, int64_t& c, uint32_t& fl) -> uint64_t {
+    const int64_t q = q0 + lane;
+    const bool in = q < k;
+    const bool masked = in && vic[q] != 0;
+    c = masked ? a.rows[n + q] : 0;
+    fl = masked ? a.pg.pod_flags[c] : 0u;
+    return __ballot(masked);
+  };
+  auto candidate = [&](int b, int64_t c, uint32_t fl, uint32_t& cfl) -> int64_t {
+    const int64_t cb = __shfl(c, b);
+    cfl = (uint32_t)__shfl((int)fl, b);
+#pragma unroll
+    for (int d = 0; d < DT; ++d)
+      if (d < D && ((track >> d) & 1u) && (((cfl >> kPresentShift) >> d) & 1u)) cv[d] = a.pg.req[cb * DS + d];
+    return cb;
+  };
+  // S_k: the totals minus every masked victim
+  for (int64_t q0 = 0; q0 < k; q0 += kWave) {
+    int64_t c;
+    uint32_t fl, cfl;
+    uint64_t mk = block(q0, c, fl);
+    while (mk != 0ull) {
+      const int b = __ffsll((long long)mk) - 1;
+      mk &= mk - 1ull;
+      candidate(b, c, fl, cfl);
+      (void)judge.template step<false, -1>(st, n_list, a.status + (n + q0 + b) * (int64_t)T, cfl, cv, lane);
+    }
+  }
+  // the walk: c_{k-1} first
+  for (int64_t q0 = ((k - 1) / kWave) * kWave; q0 >= 0; q0 -= kWave) {
+    int64_t c;
+    uint32_t fl, cfl;
+    uint64_t mk = block(q0, c, fl);
+    while (mk != 0ull) {
+      const int b = 63 - __clzll((long long)mk);
+      mk &= ~(1ull << b);
+      candidate(b, c, fl, cfl);
+      const uint8_t* crow = a.status + (n + q0 + b) * (int64_t)T;
+      const bool fail = judge.template step<true, 1>(st, n_list, crow, cfl, cv, lane);
+      if (__ballot(fail) != 0ull) continue;  // c_j stays a victim
+      (void)judge.template step<false, 1>(st, n_list, crow, cfl, cv, lane);
+      if (lane == 0) vic[q0 + b] = 0;
+    }
+  }
 }
 
 }  // namespace kt

@@ -827,13 +827,15 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// preempt, for gangs: the shortest victim prefix that lets a whole gang through (kt_kernels_preempt_gangs.hip)
+// preempt, for gangs: the shortest victim prefix that lets a whole gang through (kt_kernels_preempt_gangs.hip), and the reprieve
+// pass that shrinks its victim mask to a minimal set (kt_kernels_preempt_gangs_reprieve.hip)
 // ---------------------------------------------------------------------------------------------------
 // kt_preempt_gangs_launch: the refusals of preempt_locked in its order (with the gang defects in front, and "a pod twice" asked
 // per gang), then the same launches with kt_preempt_gangs in kt_preempt's place.  The result shares the one pending preempt result;
-// preempt_gangs tells the fetches apart.  The caller holds the launch lock.
+// preempt_gangs tells the fetches apart.  With `reprieve` (kt_preempt_gangs_reprieve_launch): behind them on the same stream the one
+// launch of kt_preempt_gangs_reprieve that rewrites the victim bytes in place.  The caller holds the launch lock.
 static int32_t preempt_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
-                                    const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream) {
+                                    const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream, bool reprieve) {
   int32_t rc = gangs_valid(e, n, n_gangs, gang_off);
   if (rc != KT_OK) return rc;
   if (n_cand < 0) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: n_cand = %lld", (long long)n_cand);
@@ -880,14 +882,17 @@ static int32_t preempt_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_
   if (rc != KT_OK) return rc;
   if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: `used` is wider than int64 (kt_preempt_gangs reads int64 sums)");
   const size_t vic = (size_t)n_gangs * (size_t)n_cand;
+  // the reprieve kernel's list state where it can outgrow LDS (0 bytes: it cannot, or nothing is walked)
+  const size_t ws = reprieve && n_cand > 0 ? kt::reprieve_ws_bytes(T, e->D, n_gangs, e->reprieve_lds_cap_limit) : 0;
   if (e->d_preempt_prefix.cap < (size_t)n_gangs || e->d_preempt_victims.cap < vic + 1 || e->d_preempt_blocker.cap < (size_t)n_gangs ||
-      e->d_preempt_gang_off.cap < (size_t)n_gangs + 1) {
+      e->d_preempt_gang_off.cap < (size_t)n_gangs + 1 || (ws != 0 && e->d_reprieve_ws.cap < ws)) {
     // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_preempt_launch)
     if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
     KT_HIP(e, e->d_preempt_prefix.reserve((size_t)n_gangs));
     KT_HIP(e, e->d_preempt_victims.reserve(vic + 1));
     KT_HIP(e, e->d_preempt_blocker.reserve((size_t)n_gangs));
     KT_HIP(e, e->d_preempt_gang_off.reserve((size_t)n_gangs + 1));
+    if (ws != 0) KT_HIP(e, e->d_reprieve_ws.reserve(ws));
   }
   // the offsets travel on the launch's stream, behind an earlier launch's kernel; the caller's memory is not referenced after return
   KT_HIP(e, hipMemcpyAsync(e->d_preempt_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s));
@@ -907,6 +912,12 @@ static int32_t preempt_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_
                            e->d_preempt_partial.p, e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p,
                            e->d_preempt_victims.p, e->d_preempt_blocker.p, s);
   KT_HIP(e, hipGetLastError());
+  if (reprieve) {
+    kt::launch_preempt_gangs_reprieve(pg, n, n_cand, e->d_rows.p, n_gangs, e->d_preempt_gang_off.p, e->thr_rows_hi, on_equal != 0, e->d_status.p,
+                                      e->d_preempt_partial.p, e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p,
+                                      e->d_preempt_victims.p, ws != 0 ? e->d_reprieve_ws.p : nullptr, e->reprieve_lds_cap_limit, s);
+    KT_HIP(e, hipGetLastError());
+  }
   e->last_stream = s;
   e->preempt_ready = true, e->preempt_gangs = true, e->preempt_n = n_gangs, e->preempt_m = n_cand;
   return KT_OK;
@@ -916,7 +927,14 @@ int32_t kt_preempt_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows
                                 const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream) {
   if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);
-  return preempt_gangs_locked(e, n, pod_rows, n_gangs, gang_off, n_cand, cand_rows, now_s, now_ns, on_equal, stream);
+  return preempt_gangs_locked(e, n, pod_rows, n_gangs, gang_off, n_cand, cand_rows, now_s, now_ns, on_equal, stream, /*reprieve=*/false);
+}
+
+int32_t kt_preempt_gangs_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
+                                         const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  return preempt_gangs_locked(e, n, pod_rows, n_gangs, gang_off, n_cand, cand_rows, now_s, now_ns, on_equal, stream, /*reprieve=*/true);
 }
 
 int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefix, uint8_t* out_victims, int64_t* out_blocker) {

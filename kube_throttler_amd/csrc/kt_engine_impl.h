@@ -206,7 +206,8 @@ extern thread_local std::string g_create_error;  // text of the last kt_engine_c
 // and again on kt_debug_reload_env, which tools/latency_bench.py calls after it flips one on a live engine — instead of by
 // getenv on every pod event and launch (getenv is not safe beside a setenv of another thread, and the pod event
 // path is tuned to a few microseconds).  Read at the same two moments, with a VALUE instead of a flag and therefore not in the
-// table: KT_REPRIEVE_LDS_CAP (kt_engine::reprieve_lds_cap_limit, a test hook of kt_preempt_reprieve_launch).
+// table: KT_REPRIEVE_LDS_CAP (kt_engine::reprieve_lds_cap_limit, a test hook of kt_preempt_reprieve_launch and
+// kt_preempt_gangs_reprieve_launch).
 enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSwCount };
 static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU"};
 struct kt_engine {
@@ -343,7 +344,7 @@ struct kt_engine {
   DevBuf<int64_t> d_preempt_prefix;
   DevBuf<uint8_t> d_preempt_victims;
   DevBuf<unsigned long long> d_preempt_partial;
-  DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
+  DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's and kt_preempt_gangs_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
   bool preempt_ready = false;
   int64_t preempt_n = 0, preempt_m = 0;
   // kt_preempt_gangs_launch shares that one pending result (prefix and victim bytes per GANG, preempt_n = the gangs); the kind tag

@@ -29,54 +29,7 @@ struct PreemptGangArgs {
   int64_t* blocker;         // [n_gangs] out
 };
 
-// `used` of one throttle as a lane (or the whole wave) sees it in some state: what the four steps read of it
-template <int DT>
-struct GangUsed {
-  bool c_flag, u_hc;     // the pod count: status.throttled, presence
-  int64_t u_c;
-  uint32_t flag_m, pr_m;  // per name: status.throttled, presence
-  int64_t u_v[DT];
-};
-
-// the throttle as the members meet it: threshold, step 3's on-equal, the stored reserved row
-template <int DT>
-struct GangThr {
-  bool th_hc, r_hc, eq3, eq;
-  int64_t th_c, r_c;
-  uint32_t th_p, r_p;
-  int64_t tv[DT], rv[DT];
-};
-
-// The members [i0, i1) in order on throttle t against one state of `used`: the first queue position whose member t affects and
-// stops (i1: none), every earlier member having reserved.  Uniform in everything but `u`.
-template <int DT>
-__device__ __forceinline__ int64_t gang_walk(const PreemptArgs& a, uint32_t t, int64_t i0, int64_t i1, const GangThr<DT>& g, const GangUsed<DT>& u) {
-  const int D = a.pg.D, DS = a.pg.DS;
-  int64_t rv[DT], rc = g.r_hc ? g.r_c : 0;
-  uint32_t rp = g.r_p;
-  bool rhc = g.r_hc;
-#pragma unroll
-  for (int d = 0; d < DT; ++d) rv[d] = ((g.r_p >> d) & 1u) ? g.rv[d] : 0;
-  int64_t first = i1;
-  for (int64_t i = i0; i < i1; ++i) {
-    if (a.status[i * (int64_t)a.T + t] == 0) continue;  // (wave-uniform) t does not affect the member: no check, no reservation
-    const int64_t p = a.rows[i];
-    const uint32_t present = a.pg.pod_flags[p] >> kPresentShift;
-    bool f = preempt_fails(1, g.th_hc, g.th_c, u.c_flag, u.u_hc, u.u_c, rhc, rc, g.eq3, g.eq);
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-      if (d >= D) continue;
-      const int64_t vp = a.pg.req[p * DS + d];
-      // a name the pod does not request passes every step
-      if (vp != 0) f |= preempt_fails(vp, (g.th_p >> d) & 1u, g.tv[d], (u.flag_m >> d) & 1u, (u.pr_m >> d) & 1u, u.u_v[d], (rp >> d) & 1u, rv[d], g.eq3, g.eq);
-      if ((present >> d) & 1u) rv[d] += vp;  // Reserve: the value of every name it carries ...
-    }
-    rp |= present & ((1u << D) - 1u);  // ... the presence of all of them, zero-valued ones included
-    rc += 1, rhc = true;
-    if (f && first == i1) first = i;
-  }
-  return first;
-}
+// (GangUsed, GangThr and gang_walk are kt_admit_common.h's: the gang reprieve judges with them too)
 
 template <int DT>
 __global__ __launch_bounds__(kWave) void kt_preempt_gangs(const PreemptArgs a, const PreemptGangArgs ga) {

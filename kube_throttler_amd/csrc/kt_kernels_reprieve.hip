@@ -33,28 +33,14 @@
 // contributor counts, [cap] throttle rows), so that the 64 lanes of a step touch consecutive words of LDS / HBM, and it is
 // updated in place by a second pass over the matched entries after the ballot — a lane may own several entries, and holding
 // their new values across the ballot would need a private array.  No lane indexes private memory dynamically: 0 bytes of scratch.
-#include <type_traits>
-
 #include "kt_admit_common.h"
 
 namespace kt {
 
-constexpr int kReprieveLdsBytes = 16 * 1024;         // the list's state in LDS: 20 KiB per wave with the chunk list, 8 waves per CU
-constexpr size_t kReprieveWsBudget = 64ull << 20;    // the HBM workspace of one launch: grid x slot bytes stay below (one slot at least)
-
-__host__ __device__ inline uint32_t reprieve_entry_bytes(int D) { return 12u + 12u * (uint32_t)D; }
-static inline size_t reprieve_slot_bytes(int T, int D) { return ((size_t)T * reprieve_entry_bytes(D) + 15u) & ~(size_t)15u; }
+// (the state's layout and sizes, ReprieveArgs, the list and the walk are kt_admit_common.h's: the gang form shares them)
 uint32_t reprieve_lds_cap(int D, uint32_t limit) {
   const uint32_t cap = (uint32_t)kReprieveLdsBytes / reprieve_entry_bytes(D);
   return limit != 0 && limit < cap ? limit : cap;
-}
-static inline int reprieve_blocks(int T, int D, int64_t n, uint32_t lds_cap) {
-  int64_t blocks = n < kPreemptMaxBlocks ? n : kPreemptMaxBlocks;
-  if ((uint32_t)T > lds_cap) {  // a list may outgrow LDS: every workgroup owns a slot
-    const int64_t fit = (int64_t)(kReprieveWsBudget / reprieve_slot_bytes(T, D));
-    blocks = std::min(blocks, std::max<int64_t>(fit, 1));
-  }
-  return (int)std::max<int64_t>(blocks, 1);
 }
 size_t reprieve_ws_bytes(int T, int D, int64_t n, uint32_t lds_cap_limit) {
   const uint32_t lds_cap = reprieve_lds_cap(D, lds_cap_limit);
@@ -62,191 +48,77 @@ size_t reprieve_ws_bytes(int T, int D, int64_t n, uint32_t lds_cap_limit) {
   return (size_t)reprieve_blocks(T, D, n, lds_cap) * reprieve_slot_bytes(T, D);
 }
 
-struct ReprieveArgs {
-  AdmitPage pg;                       // pod flags, request rows and the throttle tables of the engine (state offsets unused)
-  const int64_t* rows;                // [n + m] pod table rows: the preemptors, then the candidates
-  int64_t n, m;
-  const uint8_t* status;              // [n + m][T]
-  const unsigned long long* partial;  // [T][partial_stride(D)], exact contributor counts
-  AmountTab calc;                     // the dry finalize's status.calculatedThreshold at `now`
-  const uint8_t* calc_updated;        // [T]
-  const uint8_t* error;               // [T]
-  const int64_t* prefix;              // [n] as kt_preempt left it
-  uint8_t* victims;                   // [n][m] in: the prefix mask, out: the reprieved set
-  unsigned char* ws;                  // gridDim.x slots of ws_slot bytes (nullptr: T <= lds_cap, no list outgrows LDS)
-  size_t ws_slot;
-  int32_t T, on_equal;
-  uint32_t lds_cap;                   // entries the LDS state holds
-};
-
-// the list's state, field by field, in LDS or in HBM
-template <bool IN_LDS>
-struct ReprieveState {
-  typedef typename std::conditional<IN_LDS, KT_LDS int64_t*, int64_t*>::type p64;
-  typedef typename std::conditional<IN_LDS, KT_LDS uint32_t*, uint32_t*>::type p32;
-  typedef typename std::conditional<IN_LDS, KT_LDS unsigned char*, unsigned char*>::type pbyte;
-  p64 pods;  // [cap] counted pods
-  p64 uv;    // [D][cap] `used` value per resource name
-  p32 uc;    // [D][cap] contributors per resource name
-  p32 tl;    // [cap] throttle row
-  uint32_t cap;
-  __device__ __forceinline__ ReprieveState(pbyte base, uint32_t cap_, int D) : cap(cap_) {
-    pods = (p64)base;
-    uv = (p64)(base + (size_t)8 * cap_);
-    uc = (p32)(base + (size_t)8 * cap_ * (1 + D));
-    tl = uc + (size_t)D * cap_;
-  }
-};
-
-// a throttle whose reconcile is an error (or that nobody reconciles) keeps its stored status: nothing of it depends on V
-__device__ __forceinline__ bool reprieve_stored(const ReprieveArgs& a, uint32_t t) {
-  return a.error[t] != 0 || (a.pg.tt.flags[t] & (kThrValid | kThrResponsible)) != (kThrValid | kThrResponsible);
-}
-
-// the preemptor's affecting throttles that are reconciled: counted (ST = nullptr_t) or gathered into the state with the
-// aggregate's totals; returns the wave-uniform list length
-template <int DT, bool GATHER, class ST>
-__device__ __forceinline__ uint32_t reprieve_list(const ReprieveArgs& a, const uint8_t* row, lds_u32wp list, ST* st, uint32_t lane) {
-  const int T = a.T, D = a.pg.D;
-  const int stride = partial_stride(D);
-  uint32_t n_list = 0;
-  for (int c0 = 0; c0 < T; c0 += kPreemptChunk) {
-    bool err_c = false;  // (prefix > 0: the row holds no error byte)
-    const uint32_t n_c = admit_affected_chunk(row, T, c0, list, (uint32_t)kPreemptChunk, 0u, &err_c);
-    __syncthreads();  // (one wave: the list's entries are read by other lanes than wrote them)
-    for (uint32_t a0 = 0; a0 < n_c; a0 += kWave) {
-      const uint32_t ai = a0 + lane;
-      const uint32_t t = ai < n_c ? list[ai] : 0u;
-      const bool keep = ai < n_c && !reprieve_stored(a, t);
-      const uint64_t mk = __ballot(keep);
-      if constexpr (GATHER) {
-        const uint32_t e = n_list + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-        if (keep && e < st->cap) {
-          const unsigned long long* prow = a.partial + (size_t)t * stride;
-          st->tl[e] = t;
-          st->pods[e] = (int64_t)prow[partial_off_pods(D)];
+// one candidate against the list, for ONE preemptor with requests vp.  JUDGE: would some (throttle, amount) pair stop the
+// preemptor with the candidate back (per lane: ballot it), nothing is written.  Otherwise the candidate's amounts are added
+// (SIGN = 1) to or taken off (SIGN = -1) the state of every entry whose throttle matches it.
+template <int DT>
+struct ReprievePod {
+  const ReprieveArgs& a;
+  int64_t vp[DT];
+  template <bool JUDGE, int SIGN, class ST>
+  __device__ __forceinline__ bool step(ST& st, uint32_t n_list, const uint8_t* crow, uint32_t cfl, const int64_t (&cv)[DT], uint32_t lane) const {
+    const int D = a.pg.D;
+    const bool eq = a.on_equal != 0;
+    const ThrTables& tt = a.pg.tt;
+    bool fail = false;
+    for (uint32_t e = lane; e < n_list; e += kWave) {
+      const uint32_t t = st.tl[e];
+      if (crow[t] == 0) continue;
+      const int64_t pods = st.pods[e] + SIGN;
+      if constexpr (JUDGE) {
+        const uint32_t tf = tt.flags[t];
+        // the threshold the check reads behind the reconcile: calculatedThreshold once calculatedAt is set, else spec
+        const AmountTab& th = ((tf & kThrCalcAtNonzero) || a.calc_updated[t]) ? a.calc : tt.spec;
+        const bool eq3 = admit_eq3(tf, eq);
+        const uint32_t th_p = th.present[t], c_p = a.calc.present[t], r_p = tt.reserved.present[t];
+        const bool u_hc = pods > 0;
+        fail |= preempt_fails(1, th.has_count[t] != 0, th.count[t], a.calc.has_count[t] != 0 && u_hc && pods >= a.calc.count[t], u_hc, pods,
+                              tt.reserved.has_count[t] != 0, tt.reserved.count[t], eq3, eq);
 #pragma unroll
-          for (int d = 0; d < DT; ++d) {
-            if (d >= D) continue;
-            st->uv[(size_t)d * st->cap + e] = (int64_t)prow[d];
-            st->uc[(size_t)d * st->cap + e] = (uint32_t)prow[partial_off_presence(D) + d];
-          }
+        for (int d = 0; d < DT; ++d) {
+          if (d >= D || vp[d] == 0) continue;  // (wave-uniform)
+          // a name that neither threshold names passes every step
+          if (!(((th_p | c_p) >> d) & 1u)) continue;
+          const bool has = ((cfl >> kPresentShift) >> d) & 1u;
+          const int64_t u_v = st.uv[(size_t)d * st.cap + e] + (has ? cv[d] : 0);
+          // presence is exact: the name is in `used` while a counted pod carries it
+          const bool u_pr = st.uc[(size_t)d * st.cap + e] + (has ? 1u : 0u) > 0u;
+          const bool c_pd = (c_p >> d) & 1u;
+          fail |= preempt_fails(vp[d], (th_p >> d) & 1u, th.v[(size_t)t * D + d], c_pd && u_pr && u_v >= a.calc.v[(size_t)t * D + d], u_pr, u_v,
+                                (r_p >> d) & 1u, tt.reserved.v[(size_t)t * D + d], eq3, eq);
+        }
+      } else {
+        st.pods[e] = pods;
+#pragma unroll
+        for (int d = 0; d < DT; ++d) {
+          if (d >= D || vp[d] == 0) continue;  // (wave-uniform: only the names the preemptor requests are ever judged)
+          if (!(((cfl >> kPresentShift) >> d) & 1u)) continue;
+          st.uv[(size_t)d * st.cap + e] += SIGN * cv[d];
+          st.uc[(size_t)d * st.cap + e] += (uint32_t)SIGN;
         }
       }
-      n_list += (uint32_t)__popcll(mk);
     }
-    __syncthreads();  // the next chunk rewrites the chunk list
+    return fail;
   }
-  return n_list;
-}
-
-// one candidate against the list.  JUDGE: would some (throttle, amount) pair stop the preemptor with the candidate back
-// (per lane: ballot it), nothing is written.  Otherwise the candidate's amounts are added (SIGN = 1) to or taken off
-// (SIGN = -1) the state of every entry whose throttle matches it.
-template <int DT, bool JUDGE, int SIGN, class ST>
-__device__ __forceinline__ bool reprieve_step(const ReprieveArgs& a, ST& st, uint32_t n_list, const uint8_t* crow, uint32_t cfl,
-                                              const int64_t (&vp)[DT], const int64_t (&cv)[DT], uint32_t lane) {
-  const int D = a.pg.D;
-  const bool eq = a.on_equal != 0;
-  const ThrTables& tt = a.pg.tt;
-  bool fail = false;
-  for (uint32_t e = lane; e < n_list; e += kWave) {
-    const uint32_t t = st.tl[e];
-    if (crow[t] == 0) continue;
-    const int64_t pods = st.pods[e] + SIGN;
-    if constexpr (JUDGE) {
-      const uint32_t tf = tt.flags[t];
-      // the threshold the check reads behind the reconcile: calculatedThreshold once calculatedAt is set, else spec
-      const AmountTab& th = ((tf & kThrCalcAtNonzero) || a.calc_updated[t]) ? a.calc : tt.spec;
-      const bool eq3 = admit_eq3(tf, eq);
-      const uint32_t th_p = th.present[t], c_p = a.calc.present[t], r_p = tt.reserved.present[t];
-      const bool u_hc = pods > 0;
-      fail |= preempt_fails(1, th.has_count[t] != 0, th.count[t], a.calc.has_count[t] != 0 && u_hc && pods >= a.calc.count[t], u_hc, pods,
-                            tt.reserved.has_count[t] != 0, tt.reserved.count[t], eq3, eq);
-#pragma unroll
-      for (int d = 0; d < DT; ++d) {
-        if (d >= D || vp[d] == 0) continue;  // (wave-uniform)
-        // a name that neither threshold names passes every step
-        if (!(((th_p | c_p) >> d) & 1u)) continue;
-        const bool has = ((cfl >> kPresentShift) >> d) & 1u;
-        const int64_t u_v = st.uv[(size_t)d * st.cap + e] + (has ? cv[d] : 0);
-        // presence is exact: the name is in `used` while a counted pod carries it
-        const bool u_pr = st.uc[(size_t)d * st.cap + e] + (has ? 1u : 0u) > 0u;
-        const bool c_pd = (c_p >> d) & 1u;
-        fail |= preempt_fails(vp[d], (th_p >> d) & 1u, th.v[(size_t)t * D + d], c_pd && u_pr && u_v >= a.calc.v[(size_t)t * D + d], u_pr, u_v,
-                              (r_p >> d) & 1u, tt.reserved.v[(size_t)t * D + d], eq3, eq);
-      }
-    } else {
-      st.pods[e] = pods;
-#pragma unroll
-      for (int d = 0; d < DT; ++d) {
-        if (d >= D || vp[d] == 0) continue;  // (wave-uniform: only the names the preemptor requests are ever judged)
-        if (!(((cfl >> kPresentShift) >> d) & 1u)) continue;
-        st.uv[(size_t)d * st.cap + e] += SIGN * cv[d];
-        st.uc[(size_t)d * st.cap + e] += (uint32_t)SIGN;
-      }
-    }
-  }
-  return fail;
-}
+};
 
 template <int DT, bool IN_LDS>
 __device__ __forceinline__ void reprieve_walk(const ReprieveArgs& a, ReprieveState<IN_LDS> st, lds_u32wp list, int64_t i, int64_t k,
                                               uint32_t lane) {
-  const int T = a.T, D = a.pg.D, DS = a.pg.DS;
-  const int64_t n = a.n;
+  const int D = a.pg.D, DS = a.pg.DS;
   const int64_t p = a.rows[i];
-  uint8_t* vic = a.victims + i * a.m;
-  int64_t vp[DT], cv[DT];
+  ReprievePod<DT> pod{a, {}};
+  uint32_t track = 0;  // the names the preemptor requests
 #pragma unroll
-  for (int d = 0; d < DT; ++d) vp[d] = d < D ? a.pg.req[p * DS + d] : 0, cv[d] = 0;
-  const uint32_t n_list = reprieve_list<DT, true>(a, a.status + i * T, list, &st, lane);
+  for (int d = 0; d < DT; ++d) {
+    pod.vp[d] = d < D ? a.pg.req[p * DS + d] : 0;
+    track |= pod.vp[d] != 0 ? 1u << d : 0u;
+  }
+  const uint8_t* row = a.status + i * a.T;
+  const auto chunk = [&](int c0, lds_u32wp l, bool* err) { return admit_affected_chunk(row, a.T, c0, l, (uint32_t)kPreemptChunk, 0u, err); };
+  const uint32_t n_list = reprieve_list<DT, true>(a, chunk, list, &st, lane);
   __syncthreads();  // an entry is owned by lane (entry mod 64) from here on; another lane wrote it
-  // the masked positions of one block of 64 candidates: their rows and flags come in with one load each
-  auto block = [&](int64_t q0, int64_t& c, uint32_t& fl) -> uint64_t {
-    const int64_t q = q0 + lane;
-    const bool in = q < k;
-    const bool masked = in && vic[q] != 0;
-    c = masked ? a.rows[n + q] : 0;
-    fl = masked ? a.pg.pod_flags[c] : 0u;
-    return __ballot(masked);
-  };
-  auto candidate = [&](int b, int64_t c, uint32_t fl, uint32_t& cfl) -> int64_t {
-    const int64_t cb = __shfl(c, b);
-    cfl = (uint32_t)__shfl((int)fl, b);
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-      if (d < D && vp[d] != 0 && (((cfl >> kPresentShift) >> d) & 1u)) cv[d] = a.pg.req[cb * DS + d];
-    return cb;
-  };
-  // S_k: the totals minus every masked victim
-  for (int64_t q0 = 0; q0 < k; q0 += kWave) {
-    int64_t c;
-    uint32_t fl, cfl;
-    uint64_t mk = block(q0, c, fl);
-    while (mk != 0ull) {
-      const int b = __ffsll((long long)mk) - 1;
-      mk &= mk - 1ull;
-      candidate(b, c, fl, cfl);
-      (void)reprieve_step<DT, false, -1>(a, st, n_list, a.status + (n + q0 + b) * (int64_t)T, cfl, vp, cv, lane);
-    }
-  }
-  // the walk: c_{k-1} first
-  for (int64_t q0 = ((k - 1) / kWave) * kWave; q0 >= 0; q0 -= kWave) {
-    int64_t c;
-    uint32_t fl, cfl;
-    uint64_t mk = block(q0, c, fl);
-    while (mk != 0ull) {
-      const int b = 63 - __clzll((long long)mk);
-      mk &= ~(1ull << b);
-      candidate(b, c, fl, cfl);
-      const uint8_t* crow = a.status + (n + q0 + b) * (int64_t)T;
-      const bool fail = reprieve_step<DT, true, 1>(a, st, n_list, crow, cfl, vp, cv, lane);
-      if (__ballot(fail) != 0ull) continue;  // c_j stays a victim
-      (void)reprieve_step<DT, false, 1>(a, st, n_list, crow, cfl, vp, cv, lane);
-      if (lane == 0) vic[q0 + b] = 0;
-    }
-  }
+  reprieve_walk_list<DT>(a, st, n_list, a.victims + i * a.m, k, track, pod, lane);
 }
 
 template <int DT>
@@ -258,7 +130,9 @@ __global__ __launch_bounds__(kWave) void kt_preempt_reprieve(const ReprieveArgs 
   for (int64_t i = blockIdx.x; i < a.n; i += gridDim.x) {  // (wave-uniform: one preemptor per wave and turn)
     const int64_t k = a.prefix[i];
     if (k <= 0) continue;
-    const uint32_t n_list = reprieve_list<DT, false, void>(a, a.status + i * a.T, list, nullptr, lane);
+    const uint8_t* row = a.status + i * a.T;
+    const auto chunk = [&](int c0, lds_u32wp l, bool* err) { return admit_affected_chunk(row, a.T, c0, l, (uint32_t)kPreemptChunk, 0u, err); };
+    const uint32_t n_list = reprieve_list<DT, false, void>(a, chunk, list, nullptr, lane);
     if (n_list <= a.lds_cap)
       reprieve_walk<DT, true>(a, ReprieveState<true>((KT_LDS unsigned char*)state, a.lds_cap, a.pg.D), list, i, k, lane);
     else if (a.ws)  // (the launcher gives a workspace whenever T > lds_cap; n_list <= T)

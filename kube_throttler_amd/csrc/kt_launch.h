@@ -134,6 +134,13 @@ size_t reprieve_ws_bytes(int T, int D, int64_t n, uint32_t lds_cap_limit);
 void launch_preempt_reprieve(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int T, bool on_equal, const uint8_t* status,
                              const unsigned long long* partial, const AmountTab& calc, const uint8_t* calc_updated, const uint8_t* error,
                              const int64_t* prefix, uint8_t* victims, void* ws, uint32_t lds_cap_limit, hipStream_t s);
+// the reprieve pass behind the gang form (kt_kernels_preempt_gangs_reprieve.hip): one wave per gang walks its masked victims back,
+// last first, judging the members in order, and rewrites victims [n_gangs][m] in place; prefix [n_gangs] is read.  LDS capacity
+// and workspace as for launch_preempt_reprieve, sized with n_gangs in the place of n
+void launch_preempt_gangs_reprieve(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int64_t n_gangs, const int64_t* gang_off_dev,
+                                   int T, bool on_equal, const uint8_t* status, const unsigned long long* partial, const AmountTab& calc,
+                                   const uint8_t* calc_updated, const uint8_t* error, const int64_t* prefix, uint8_t* victims, void* ws,
+                                   uint32_t lds_cap_limit, hipStream_t s);
 // the first instant at which a pod passes (kt_kernels_forecast.hip): one wave per pod, lane = instant position.  rows_dev [n];
 // inst_s / inst_ns [m] in device memory, strictly ascending; status / summary: ONE check over those rows; partial: aggregate rows
 // with exact per-name contributor counts; error: the error bytes of a dry finalize; first [n] and verdicts [n][m] out

@@ -42,7 +42,7 @@ EXPORTS = [
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
-    "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
+    "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -258,6 +258,7 @@ def lib():
         L.kt_preempt_reprieve_launch.argtypes = L.kt_preempt_launch.argtypes
         L.kt_preempt_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                               C.c_int32, C.c_int32, C.c_void_p]
+        L.kt_preempt_gangs_reprieve_launch.argtypes = L.kt_preempt_gangs_launch.argtypes
         L.kt_preempt_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.kt_forecast_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -640,6 +641,15 @@ class Engine:
         self._ck(lib().kt_preempt_gangs_launch(self._h, len(a), p if len(a) else None, len(g) - 1, g.ctypes.data, len(c), q if len(c) else None,
                                                int(now[0]), int(now[1]), int(on_equal), stream))
 
+    def preempt_gangs_reprieve_launch(self, pod_rows, gang_off, cand_rows, now, on_equal=False, stream=None):
+        """kt_preempt_gangs_reprieve_launch: kt_preempt_gangs_launch and, behind it on the same stream, the reprieve pass that
+        shrinks every gang's victim bytes to a minimal set; fetched with ``preempt_gangs_fetch``."""
+        a, p = self._rows(pod_rows, np.int64)
+        c, q = self._rows(cand_rows, np.int64)
+        g = _gang_offsets(gang_off)
+        self._ck(lib().kt_preempt_gangs_reprieve_launch(self._h, len(a), p if len(a) else None, len(g) - 1, g.ctypes.data, len(c),
+                                                        q if len(c) else None, int(now[0]), int(now[1]), int(on_equal), stream))
+
     def preempt_gangs_fetch(self, n_gangs, n_cand, want_victims=True):
         prefix = np.zeros(max(n_gangs, 1), np.int64)
         blocker = np.zeros(max(n_gangs, 1), np.int64)
@@ -648,15 +658,17 @@ class Engine:
                                               blocker.ctypes.data))
         return prefix[:n_gangs], (None if flat is None else flat[:n_gangs * n_cand].reshape(n_gangs, n_cand)), blocker[:n_gangs]
 
-    def preempt_gangs(self, pod_rows, gang_off, cand_rows, now, on_equal=False, want_victims=True):
+    def preempt_gangs(self, pod_rows, gang_off, cand_rows, now, on_equal=False, want_victims=True, reprieve=False):
         """kt_preempt_gangs_launch + kt_preempt_gangs_fetch: per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` the smallest k for
         which an in-order admission of its members (each admitted member reserves against the throttles the later ones meet)
         admits all of them once the candidates ``cand_rows[:k]`` are gone and every throttle has been reconciled at ``now``
         (PREEMPT_NONE: no prefix does), the victim bytes, and the queue position of the first member that is not admitted with
         nothing deleted (-1 where the prefix is 0) -> (prefix int64 [n_gangs], victims uint8 [n_gangs][n_cand] or None, blocker
         int64 [n_gangs]).  Gangs are judged independently of each other, each against the stored reserved amounts.  A dry run:
-        stored status and reserved amounts stay as they are."""
-        self.preempt_gangs_launch(pod_rows, gang_off, cand_rows, now, on_equal)
+        stored status and reserved amounts stay as they are.  ``reprieve``: every gang's victims are walked back, last first, and
+        each stays back as long as the whole gang is still admitted (kt_preempt_gangs_reprieve_launch) — prefix and blocker are the
+        same, the victim bytes are a minimal set."""
+        (self.preempt_gangs_reprieve_launch if reprieve else self.preempt_gangs_launch)(pod_rows, gang_off, cand_rows, now, on_equal)
         return self.preempt_gangs_fetch(len(_gang_offsets(gang_off)) - 1, len(cand_rows), want_victims)
 
     # ---- forecast: the first instant at which a blocked pod passes

@@ -1282,7 +1282,7 @@ PreemptResult KubeThrottler::Preempt(const std::string& pod_key, const std::vect
 // Which of the candidates have to go before the whole gang is admitted: kt_preempt_gangs_launch + kt_preempt_gangs_fetch with the
 // members as ONE gang on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).  Nothing is changed.
 GangPreemptResult KubeThrottler::PreemptGang(const std::vector<std::string>& member_keys, const std::vector<std::string>& candidate_keys,
-                                             const std::string& now_rfc3339) {
+                                             const std::string& now_rfc3339, bool reprieve) {
   std::lock_guard<std::recursive_mutex> lk(p_->mu);
   auto& p = *p_;
   GangPreemptResult res;
@@ -1313,8 +1313,9 @@ GangPreemptResult KubeThrottler::PreemptGang(const std::vector<std::string>& mem
   const int64_t gang_off[2] = {0, (int64_t)rows.size()};
   int64_t prefix = KT_PREEMPT_NONE, blocker = -1;
   std::vector<uint8_t> mask(cand.size() + 1);
-  int32_t rc = kt_preempt_gangs_launch(p.e, (int64_t)rows.size(), rows.data(), 1, gang_off, (int64_t)cand.size(), cand.data(), now_s, now_ns,
-                                       /*isThrottledOnEqual=*/0, nullptr);
+  // with `reprieve` the same launch plus the walk that puts victims back, behind it on the same stream; one fetch either way
+  int32_t rc = (reprieve ? kt_preempt_gangs_reprieve_launch : kt_preempt_gangs_launch)(
+      p.e, (int64_t)rows.size(), rows.data(), 1, gang_off, (int64_t)cand.size(), cand.data(), now_s, now_ns, /*isThrottledOnEqual=*/0, nullptr);
   if (rc == KT_OK) rc = kt_preempt_gangs_fetch(p.e, 1, &prefix, mask.data(), &blocker);
   if (rc != KT_OK) {
     out.error = p.engine_error(rc);

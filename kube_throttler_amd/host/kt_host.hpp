@@ -256,8 +256,11 @@ class KubeThrottler {
   // kt_preempt_gangs_fetch) instead of delete + ReconcileAll + AdmitGangs per prefix.  A dry run: nothing is deleted, reserved or
   // stored, and the reserved totals are read as they stand.  A member named twice, a member among the candidates and a mirror on
   // several pages answer an error.
+  // `reprieve` (kt_preempt_gangs_reprieve_launch, still one engine call): the victims of that prefix are then put back one by one, the
+  // last of the list first, and each stays back as long as the whole gang is still admitted.  The members' own reprieved sets do not
+  // compose into this one: the later members meet what the earlier ones reserved.
   GangPreemptResult PreemptGang(const std::vector<std::string>& member_keys, const std::vector<std::string>& candidate_keys,
-                                const std::string& now_rfc3339);
+                                const std::string& now_rfc3339, bool reprieve = false);
   // The first instant in [now, now + horizon] at which PreFilter(pod) is Success if every throttle were reconciled then
   // (temporaryThresholdOverrides begin and end): kt_override_instants for the boundaries, ONE kt_forecast_launch over
   // now ++ boundaries.  What a PreFilter rejection path asks to set a backoff.  A dry run; a mirror on several pages refuses.

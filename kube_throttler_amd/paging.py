@@ -493,7 +493,56 @@ def _gang_first_stopped(members, hit, reqs, thr_amounts, used, res, res_count, e
     return None
 
 
-def preempt_gangs_of(snap, member_rows, cand_rows, now, on_equal=False, ctx=None):
+def _gang_reprieve(snap, ctx, members, union, affected, contributes, creq, reqs, eq, prefix, victims):
+    """The reprieve walk for a gang on the sums of ``preempt_context`` — ``_reprieve`` with ``_gang_first_stopped`` as the judge: per
+    reconciled throttle of the union the `used` of the state without the masked victims; position prefix - 1 first, a victim is put
+    back where every throttle that matches it still admits the members in order, under the reserved prefix, with its amounts added
+    (the others do not change: they pass already).  ``victims`` is rewritten in place."""
+    live = []  # [throttle row, its index in `contributes`, values, contributor counts, counted pods]
+    for ti, t in enumerate(union):
+        th = ctx["thr"][t]
+        if th["error"]:  # keeps its stored status whoever is deleted: it passed, or the prefix would not be positive
+            continue
+        val, cnt, pods = dict(th["val"]), dict(th["cnt"]), th["pods"]
+        for j in range(prefix):
+            if victims[j] and contributes[ti][j]:
+                pods -= 1
+                for d, v in creq[j].items():
+                    val[d] -= v
+                    cnt[d] -= 1
+        live.append([t, ti, val, cnt, pods])
+    for j in range(prefix - 1, -1, -1):
+        if not victims[j]:
+            continue
+        back = []
+        for entry in live:
+            t, ti, val, cnt, pods = entry
+            if not contributes[ti][j]:
+                continue
+            val, cnt, pods = dict(val), dict(cnt), pods + 1
+            for d, v in creq[j].items():
+                val[d] = val.get(d, 0) + v
+                cnt[d] = cnt.get(d, 0) + 1
+            th = ctx["thr"][t]
+            eq3 = eq if int(snap.thr_flags[t]) & S.THR_CLUSTER else True
+            res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+            cc = th["calc_count"]
+            names = {}
+            for d in range(snap.D):
+                u_pr, cv = cnt.get(d, 0) > 0, th["calc"].get(d)
+                names[d] = (cv is not None and u_pr and val.get(d, 0) >= cv, u_pr, val.get(d, 0))
+            first = _gang_first_stopped(members, [t in a for a in affected], reqs, (th["th"], th["th_count"]),
+                                        (cc is not None and pods > 0 and pods >= cc, pods > 0, pods, names), res, res_count, eq3, eq)
+            if first is not None:
+                break
+            back.append((entry, val, cnt, pods))
+        else:
+            victims[j] = 0
+            for entry, val, cnt, pods in back:
+                entry[2:] = [val, cnt, pods]
+
+
+def preempt_gangs_of(snap, member_rows, cand_rows, now, on_equal=False, ctx=None, reprieve=False):
     """kt_preempt_gangs_launch for one gang, in closed form on a Snapshot (no GPU) -> (prefix, victims [len(cand_rows)], blocker).
     prefix: the smallest k for which an in-order admission of ``member_rows`` — PreFilter, and on Success Reserve on every
     throttle that affects the member — admits every member once the candidates ``cand_rows[:k]`` are gone and every responsible
@@ -501,7 +550,9 @@ def preempt_gangs_of(snap, member_rows, cand_rows, now, on_equal=False, ctx=None
     victims[j] = 1 iff j < prefix, the candidate is counted and a throttle that affects some member matches it.  blocker: the
     position in ``member_rows`` of the first member that is not Success with nothing deleted (-1 when prefix == 0).
     Per throttle the members meet `used` lowered by a prefix sum over the candidates and `reserved` raised by a prefix sum over
-    the earlier members it affects: both are formed directly, nothing is admitted step by step across throttles."""
+    the earlier members it affects: both are formed directly, nothing is admitted step by step across throttles.
+    ``reprieve`` (kt_preempt_gangs_reprieve_launch): the masked victims are then put back one by one, the last first, and each
+    stays back as long as the in-order admission still admits every member; victims is what remains."""
     ctx = preempt_context(snap, now) if ctx is None else ctx
     members, cands, eq = [int(p) for p in member_rows], [int(c) for c in cand_rows], bool(on_equal)
     m, g = len(cands), len(members)
@@ -563,6 +614,8 @@ def preempt_gangs_of(snap, member_rows, cand_rows, now, on_equal=False, ctx=None
     victims = [0] * m
     for j in range(max(prefix, 0)):
         victims[j] = int(any(contributes[ti][j] for ti in range(len(union))))
+    if reprieve and prefix > 0:
+        _gang_reprieve(snap, ctx, members, union, affected, contributes, creq, reqs, eq, prefix, victims)
     return prefix, victims, (-1 if prefix == 0 or block0 >= g else block0)
 
 

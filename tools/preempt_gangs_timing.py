@@ -1,6 +1,7 @@
 """Times the gang preemption query (kt_preempt_gangs_launch) beside the composed path a caller has without it; the output is the
 record kept as profiles/preempt_gangs_timing.txt.
 usage: python tools/preempt_gangs_timing.py [--pods 20000] [--throttles 1000] [--dims 8] [--cands 1000] [--gangs 256] [--size 4] [--reps 5]
+                                            [--reprieve]
 
 On the seeded workload of tools/preempt_timing.py (thresholds a few pods below what is used, so that pending pods are blocked
 and victims help):
@@ -11,6 +12,15 @@ and victims help):
   composed 1 x m   a scratch engine: kt_delete_pods + kt_reconcile_launch(APPLY) + a dry kt_admit_gangs_launch of the one gang per
                    prefix step, the prefix length BISECTED (the fairest thing a caller can do today; it assumes the verdict is
                    monotone in k, which kt_preempt_gangs does not), the deleted pods fed back afterwards.  G gangs are G times that.
+--reprieve times the reprieve pass (kt_preempt_gangs_reprieve_launch) instead; its output is the record kept as
+profiles/preempt_gangs_reprieve_timing.txt:
+  counts           the gangs with a positive prefix, masked victims per such gang before and after the walk
+  reprieve / plain kt_preempt_gangs_reprieve_launch + kt_preempt_gangs_fetch against kt_preempt_gangs_launch + kt_preempt_gangs_fetch on
+                   the same inputs, for all gangs and for the one gang with the most masked victims; the two calls ALTERNATE within
+                   the run, so that drift of the machine hits both alike: the difference of the medians is the walk's share
+  composed 1 x m   a twin engine, starting from the prefix mask deleted (prefix and mask taken as given): per masked victim, last
+                   first, upsert it + kt_reconcile_launch(APPLY) + a dry kt_admit_gangs_launch of the one gang, and kt_delete_pods
+                   again where the gang is no longer admitted — the only exact way without the call
 Method: warm runs first, then the minimum and the median over --reps of the wall clock around the synchronous calls."""
 import argparse
 import os
@@ -24,6 +34,76 @@ from kube_throttler_amd import engine as E, snapshot as S  # noqa: E402
 from preempt_timing import NOW, timed, workload  # noqa: E402
 
 
+def alternated(call_a, call_b, reps):
+    """(min, median) ms of each of two calls, run in turns a, b, a, b, .. after one warm run of each."""
+    import time
+    call_a(), call_b()
+    ms = ([], [])
+    for _ in range(reps):
+        for which, call in enumerate((call_a, call_b)):
+            t0 = time.perf_counter()
+            call()
+            ms[which].append((time.perf_counter() - t0) * 1e3)
+    return tuple((min(x), float(np.median(x))) for x in ms)
+
+
+def reprieve_mode(a, snap, eng, members, off, cands, n_gangs):
+    prefix, mask, blocker = eng.preempt_gangs(members, off, cands, NOW)
+    prefix_r, left, blocker_r = eng.preempt_gangs(members, off, cands, NOW, reprieve=True)
+    assert np.array_equal(prefix, prefix_r) and np.array_equal(blocker, blocker_r) and (left <= mask).all()
+    masked, kept = mask.sum(axis=1), left.sum(axis=1)
+    pos = prefix > 0
+    if not pos.any():
+        print("no gang has a positive prefix: nothing to walk", flush=True)
+        return
+    print(f"answers over the gangs: positive prefix {int(pos.sum())} of {n_gangs} (longest {int(prefix.max())}); masked victims per such gang: "
+          f"mean {masked[pos].mean():.1f}, most {int(masked.max())}; after the walk: mean {kept[pos].mean():.1f}, most {int(kept.max())}", flush=True)
+    g = int(np.argmax(masked))  # the gang with the most masked victims: the longest walk
+    one, one_off = members[off[g]:off[g + 1]], np.array([0, a.size], np.int64)
+    t_all_r, t_all_p = alternated(lambda: eng.preempt_gangs(members, off, cands, NOW, reprieve=True),
+                                  lambda: eng.preempt_gangs(members, off, cands, NOW), a.reps)
+    t_one_r, t_one_p = alternated(lambda: eng.preempt_gangs(one, one_off, cands, NOW, reprieve=True),
+                                  lambda: eng.preempt_gangs(one, one_off, cands, NOW), a.reps)
+
+    twin = E.Engine.for_snapshot(snap)
+    victims = cands[mask[g] != 0]
+
+    def admitted():
+        twin.reconcile_launch(NOW, apply=True)
+        twin.synchronize()
+        return bool(twin.admit_gangs(one, one_off, commit=False, want_status=False)[2][0])
+
+    def composed():
+        twin.delete_pods(victims)
+        out = np.ones(len(victims), bool)
+        for j in range(len(victims) - 1, -1, -1):
+            twin.upsert_pods(snap.pod_batch(victims[j:j + 1]), rows=victims[j:j + 1])
+            if admitted():
+                out[j] = False
+            else:
+                twin.delete_pods(victims[j:j + 1])
+        twin.upsert_pods(snap.pod_batch(victims[out]), rows=victims[out])
+        return out
+
+    got = composed()
+    same = np.array_equal(victims[got], cands[left[g] != 0])
+    t_comp = timed(composed, a.reps)
+    print(f"reprieve, {n_gangs} gangs of {a.size} x {len(cands)} candidates, launch + fetch: min {t_all_r[0]:.3f} ms, median {t_all_r[1]:.3f} ms",
+          flush=True)
+    print(f"preempt gangs alone, the same call, alternated: min {t_all_p[0]:.3f} ms, median {t_all_p[1]:.3f} ms -> the walk adds "
+          f"{t_all_r[1] - t_all_p[1]:.3f} ms (medians)", flush=True)
+    print(f"reprieve, 1 gang of {a.size} x {len(cands)} candidates ({int(masked[g])} masked victims, {int(kept[g])} left), launch + fetch: "
+          f"min {t_one_r[0]:.3f} ms, median {t_one_r[1]:.3f} ms", flush=True)
+    print(f"preempt gangs alone, the same call, alternated: min {t_one_p[0]:.3f} ms, median {t_one_p[1]:.3f} ms -> the walk adds "
+          f"{t_one_r[1] - t_one_p[1]:.3f} ms (medians)", flush=True)
+    print(f"composed walk on a twin (per victim: upsert + reconcile(APPLY) + dry admit_gangs, delete again on a fail), 1 gang, "
+          f"{len(victims)} victims: min {t_comp[0]:.3f} ms, median {t_comp[1]:.3f} ms (same victims as the kernel: {same})", flush=True)
+    print(f"ratio composed / reprieve launch, one gang: {t_comp[1] / t_one_r[1]:.2f}x; composed / the walk's own share: "
+          f"{t_comp[1] / max(t_one_r[1] - t_one_p[1], 1e-3):.0f}x; {int(pos.sum())} gangs (composed = the walk above scaled to "
+          f"{int(masked.sum())} masked victims in all): {t_comp[1] / max(len(victims), 1) * masked.sum() / t_all_r[1]:.0f}x", flush=True)
+    twin.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pods", type=int, default=20000)
@@ -33,6 +113,7 @@ def main():
     ap.add_argument("--gangs", type=int, default=256)
     ap.add_argument("--size", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--reprieve", action="store_true")
     a = ap.parse_args()
 
     snap = workload(a.pods, a.throttles, a.dims)
@@ -48,6 +129,10 @@ def main():
     off = np.arange(n_gangs + 1, dtype=np.int64) * a.size
     print(f"library {E.version()}; pods {snap.n_pods}, throttle rows {eng.throttle_rows()}, D {snap.D}, candidates {len(cands)}, "
           f"gangs {n_gangs} of {a.size}, reps {a.reps}", flush=True)
+    if a.reprieve:
+        reprieve_mode(a, snap, eng, members, off, cands, n_gangs)
+        eng.close()
+        return
     prefix, _, blocker = eng.preempt_gangs(members, off, cands, NOW)
     single, _ = eng.preempt(members, cands, NOW)
     alone = single.reshape(n_gangs, a.size)
