@@ -104,6 +104,10 @@ int32_t kt_upsert_pods(kt_engine* e, const kt_snapshot* batch, const int64_t* po
 /* Throttles: spec (threshold, overrides, selector), stored status and reserved amounts of each row. */
 int32_t kt_upsert_throttles(kt_engine* e, const kt_snapshot* batch, const int32_t* thr_rows);
 int32_t kt_delete_namespaces(kt_engine* e, int32_t n, const int32_t* ns_rows);
+/* Pods leave by row.  A batch may name a row more than once, and rows that hold no pod (never fed, or deleted before — a Delete and
+ * the DeletedFinalStateUnknown tombstone of one pod, a work queue drained into one call); both are no-ops beyond the first: the
+ * rows end up empty and their pods are taken out of `used` once (incremental engines included).  Every row must lie inside
+ * pod_capacity. */
 int32_t kt_delete_pods(kt_engine* e, int64_t n, const int64_t* pod_rows);
 int32_t kt_delete_throttles(kt_engine* e, int32_t n, const int32_t* thr_rows);
 /* Clears everything and ingests a whole snapshot (rows = indices). */

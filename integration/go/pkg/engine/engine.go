@@ -124,7 +124,9 @@ func (e *Engine) UpsertPod(row int64, ns, flags uint32, keys, pairs []uint32, ct
 	return nil
 }
 
-// DeletePods replaces the pod informer's Delete handler.
+// DeletePods replaces the pod informer's Delete handler.  rows may be a drained work queue as it comes: a batch may name a row more
+// than once (a Delete and the DeletedFinalStateUnknown tombstone of one pod) and rows that hold no pod; both are no-ops beyond the
+// first, on incremental engines too.
 func (e *Engine) DeletePods(rows []int64) error {
 	if len(rows) == 0 {
 		return nil

@@ -1,6 +1,7 @@
 // kt_engine_feed.cpp — the state feed of the C-ABI: what the informer event handlers push (namespaces, pods, throttles, stored
 // status, reserved amounts, whole snapshots).  throttle_controller.go:400-536, clusterthrottle_controller.go:428-570.
 #include "kt_engine_impl.h"
+#include "kt_rows.h"
 
 int32_t kt_upsert_namespaces(kt_engine* e, const kt_snapshot* b, const int32_t* rows) {
   if (!e || !b) return KT_ERR_INVALID_ARGUMENT;
@@ -272,6 +273,13 @@ int32_t kt_delete_pods(kt_engine* e, int64_t n, const int64_t* rows) {
   for (int64_t i = 0; i < n; ++i)
     if (rows[i] < 0 || rows[i] >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "pod row %lld", (long long)rows[i]);
   if (n <= 0) return KT_OK;
+  // A batch may name a row more than once (coalesced informer events: a Delete, then the DeletedFinalStateUnknown tombstone of the
+  // same pod) and rows that hold no pod; both are no-ops beyond the first.  A rescanning engine gets that from the kernels: they
+  // write zeros, and the view patch rewrites a record from the same table content.  The delta scan of an incremental engine gathers
+  // through the list while the pods are still in the tables, so a row named twice would leave the maintained partials twice — and
+  // nothing rescans them afterwards: its list is made unique first (kt_rows.h; an ascending list, the usual case, stays as it is).
+  std::vector<int64_t> uniq_rows;
+  if (e->incremental) rows = kt::unique_rows(rows, n, uniq_rows, &n);
   const bool slot_path = (size_t)n * 8 <= kt_engine::kEvSlotBytes && !e->incremental && !e->sw[kSw_SYNC_INGEST];
   if (!slot_path || (e->last_stream && e->last_stream != e->own_stream)) {
     settle_ingest(e);

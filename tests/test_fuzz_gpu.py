@@ -175,7 +175,7 @@ def test_random_event_sequences(seed, oracle_mod, monkeypatch):
                 for i in range(size):
                     state[rows[i]] = src[i]
             elif kind < .85:   # deletes
-                rows = np.unique(r.integers(0, P, size)).astype(np.int64)
+                rows = r.integers(0, P, size).astype(np.int64)
                 eng.delete_pods(rows)
                 state[rows] = -1
             else:              # a Throttle event: the tables go up again (selectors unchanged), or a responsibility flip (recompile)
@@ -309,7 +309,7 @@ def test_concurrent_events_prefilters_and_reconciles(seed, oracle_mod, monkeypat
         if r.random() < .7:
             events.append(("up", r.integers(0, P, size).astype(np.int64), r.integers(0, n_src, size)))
         else:
-            events.append(("del", np.unique(r.integers(0, P, size)).astype(np.int64), None))
+            events.append(("del", r.integers(0, P, size).astype(np.int64), None))
     eng = E.Engine(base.D, max(base.L, 1), P, max(base.n_thr, 1), max(base.n_ns, 1), -1, variant)
     errors, stop = [], threading.Event()
     hung = False
