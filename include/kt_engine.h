@@ -594,6 +594,13 @@ const char* kt_kernel_name(kt_engine* e, int32_t kernel);
                                       views is patched into them in place and does not count) */
 #define KT_COUNTER_AGG_WORKGROUPS 11 /* workgroups (= slabs) of the last full aggregate scan's launch: up to 256 at one workgroup per CU,
                                       up to 512 in the two-per-CU form of single-chunk packed scans (KT_AGG_ONE_PER_CU=1 keeps one) */
+#define KT_COUNTER_MATCH_CACHE_BUILDS 12 /* full builds of the match cache so far: the per-pod matched-term words single-chunk programs
+                                            keep between PreFilter sweeps.  One after every compile and after a table clear; pod events refresh
+                                            their rows only and do not count (KT_NO_MATCH_CACHE=1: no table, the scans as before) */
+#define KT_COUNTER_MATCH_CACHE_SCANS 13  /* scans served from the match cache so far (the lean PreFilter sweep of every row; the aggregate
+                                            scan keeps its selector scan) */
+#define KT_COUNTER_MATCH_CACHE_PLANES 14 /* the longest namespace word list of the compiled single-chunk program, as the last sweep of every
+                                            row counted it (0: not counted yet, or several chunks): more than 4 = not cached */
 int64_t kt_counter(kt_engine* e, int32_t which);
 /* ---- More resource names than one engine has dimensions (KT_MAX_DIMS): PAGES.  The reference sums and compares any resource
  *      name (pkg/resourcelist/resourcelist.go:27-54, resource_amount.go:127-159).  The host builds the same cluster once per

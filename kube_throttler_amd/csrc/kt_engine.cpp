@@ -368,6 +368,9 @@ int32_t kt_engine_destroy(kt_engine* e) {
   e->d_overflow.release();
   e->views.release();
   e->d_carry.release();
+  e->d_mc.release();
+  if (e->h_mc_rows) (void)hipHostFree(e->h_mc_rows);
+  if (e->mc_rows_ev) (void)hipEventDestroy(e->mc_rows_ev);
   e->d_slab_tag.release();
   e->d_row_mask.release();
   e->d_req_sums.release();
@@ -529,6 +532,9 @@ int64_t kt_counter(kt_engine* e, int32_t which) {
     case KT_COUNTER_PACKED_WORDS: return e->ctr_packed_words.load(std::memory_order_relaxed);
     case KT_COUNTER_AGG_WORKGROUPS: return e->ctr_agg_workgroups.load(std::memory_order_relaxed);
     case KT_COUNTER_VIEW_BUILDS: return e->ctr_view_builds.load(std::memory_order_relaxed);
+    case KT_COUNTER_MATCH_CACHE_BUILDS: return e->ctr_mc_builds.load(std::memory_order_relaxed);
+    case KT_COUNTER_MATCH_CACHE_SCANS: return e->ctr_mc_scans.load(std::memory_order_relaxed);
+    case KT_COUNTER_MATCH_CACHE_PLANES: return e->ctr_mc_planes.load(std::memory_order_relaxed);
     default: return -1;
   }
 }

@@ -26,6 +26,66 @@ static int32_t ensure_check_recs(kt_engine* e, int32_t on_equal, int DT, hipStre
   return KT_OK;
 }
 
+// The match cache (kt_engine_impl.h), made current for a scan that will be enqueued on s right behind this call: built by one
+// launch over every row when the program was compiled or the tables cleared since, else the rows pod events upserted since are
+// refreshed by one launch of the list form.  mc.mw stays nullptr where there is no table: the switch, a program the cache does
+// not take (several chunks, slow shapes, overflow pods, more than 8 dimensions, a namespace word list longer than kMatchReplay, a
+// check footprint that does not fit one CU twice), nothing fed yet.
+int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc) {
+  mc = kt::MatchCacheArgs();
+  if (e->sw[kSw_NO_MATCH_CACHE] || e->cfg.kernel_variant != 0 || e->incremental || e->program_dirty || e->pod_rows_hi <= 0) return KT_OK;
+  if (!kt::match_cache_fits(e->dindex) || e->hindex.has_slow || e->n_overflow != 0 || e->pods.LA > 8 || !e->pods.latom) return KT_OK;
+  if (e->mc_planes_gen != e->program_gen) {  // the longest namespace word list of the (single) chunk: the planes a pod needs
+    const kt::BmChunk& ch = e->dindex.h_chunks[0];
+    const uint32_t* rng = (const uint32_t*)(e->hindex.bm_images.data() + ch.img_off + ch.off_nsl_rng);
+    uint32_t longest = 0;
+    for (uint32_t n = 0; n < e->hindex.n_ns; ++n) longest = std::max(longest, rng[2 * n + 1] - rng[2 * n]);
+    e->mc_planes = longest, e->mc_planes_gen = e->program_gen;
+    e->ctr_mc_planes.store((int64_t)longest, std::memory_order_relaxed);
+  }
+  const uint32_t planes = e->mc_planes;
+  // (the dispatch's own predicate: a table the sweep would not replay is neither built nor refreshed)
+  if (!kt::check_replays_match_cache(e->pods, e->sp, e->dindex, planes, e->n_overflow != 0, e->sw[kSw_CHECK_ONE_PER_CU])) return KT_OK;
+  const uint64_t stride = (uint64_t)e->cfg.pod_capacity;
+  if (!e->mc_valid || e->mc_gen != e->program_gen) {
+    if (e->d_mc.cap < (size_t)planes * stride) {
+      if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // an earlier scan may still read the old table
+      KT_HIP(e, e->d_mc.reserve((size_t)planes * stride));
+    }
+    order_behind_ingest(e, s);
+    if (!kt::launch_build_match_cache(e->pods, e->pod_rows_hi, nullptr, e->dindex, e->d_mc.p, stride, planes, s)) return KT_OK;
+    KT_HIP(e, hipGetLastError());
+    e->mc_valid = true, e->mc_gen = e->program_gen;
+    e->mc_pending.clear();
+    e->ctr_mc_builds.fetch_add(1, std::memory_order_relaxed);
+  } else if (!e->mc_pending.empty()) {
+    const size_t n = e->mc_pending.size();
+    // the kernel reads the list where it lies, in a pinned buffer of its own, as the feed kernels read their event slots: no
+    // copy and no host wait — the launch is all the first sweep after a pod event pays (a copy engine's trip in front of it
+    // cost 7 us where the launch costs 3.5: profiles/match_cache.txt); an event behind the refresh says when the buffer of the
+    // previous one is free again — long ago, as a rule
+    if (!e->h_mc_rows) {
+      KT_HIP(e, hipHostMalloc((void**)&e->h_mc_rows, (size_t)kPatchBatchMax * 8, hipHostMallocDefault));
+      KT_HIP(e, hipEventCreateWithFlags(&e->mc_rows_ev, hipEventDisableTiming));
+    } else if (e->mc_rows_ev_used) {
+      KT_HIP(e, hipEventSynchronize(e->mc_rows_ev));
+    }
+    memcpy(e->h_mc_rows, e->mc_pending.data(), n * 8);
+    order_behind_ingest(e, s);
+    if (!kt::launch_build_match_cache(e->pods, (int64_t)n, e->h_mc_rows, e->dindex, e->d_mc.p, stride, planes, s)) {
+      e->mc_valid = false;
+      e->mc_pending.clear();
+      return KT_OK;
+    }
+    KT_HIP(e, hipGetLastError());
+    KT_HIP(e, hipEventRecord(e->mc_rows_ev, s));
+    e->mc_rows_ev_used = true;
+    e->mc_pending.clear();
+  }
+  mc.mw = e->d_mc.p, mc.stride = stride, mc.planes = planes;
+  return KT_OK;
+}
+
 // allow_small: false for callers that go on working on the device-side rows / summaries (kt_admit_launch)
 static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
                                    hipStream_t s, bool allow_small = true) {
@@ -73,6 +133,14 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
   // the record layout follows the scan kernel that will read it
   const int DT = e->cfg.kernel_variant == 1 ? kt::dt_bucket(e->D) : kt::dt_bucket_ix(e->D);
   if ((rc = ensure_check_recs(e, on_equal, DT, s)) != KT_OK) return rc;
+  // the sweep of every row of a single-chunk program replays the match cache (the few-pod, small, row-subset and status-matrix
+  // forms neither read nor refresh it: the path from a pod event to its PreFilter stays as short as it was); a build or a
+  // refresh of the table is enqueued here, ahead of the check's timed launch
+  kt::MatchCacheArgs mc;
+  if (e->cfg.kernel_variant != 1 && !pod_rows && !small && !want_status && n > 0 && n <= e->cfg.pod_capacity && e->dindex.n_chunks == 1 &&
+      !e->sw[kSw_FORCE_NS_ORDER] && !e->sw[kSw_CHECK_ONE_PER_CU]) {
+    if ((rc = match_cache_for_scan(e, s, mc)) != KT_OK) return rc;
+  }
   {
     TimedLaunch tl(e, KT_KERNEL_CHECK, s);
     if (e->cfg.kernel_variant == 1)
@@ -107,7 +175,9 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
       }
       const char* k = kt::launch_check_indexed(e->pods, n, by_ns ? av.rows.p : pod_rows ? e->d_rows.p : nullptr, e->sp, e->d_sp.p, e->dindex,
                                                e->recs_ptr(), e->d_summary.p, want_status ? e->d_status.p : nullptr, s,
-                                               small ? &sm : nullptr, e->n_overflow != 0, by_ns ? &view : nullptr, e->sw[kSw_CHECK_ONE_PER_CU]);
+                                               small ? &sm : nullptr, e->n_overflow != 0, by_ns ? &view : nullptr, e->sw[kSw_CHECK_ONE_PER_CU],
+                                               mc.mw ? &mc : nullptr);
+      if (mc.used) e->ctr_mc_scans.fetch_add(1, std::memory_order_relaxed);
       if (!k) return e->fail(KT_ERR_UNSUPPORTED, "%d throttle rows exceed the indexed check kernel's LDS budget (use kernel_variant 1)", e->thr_rows_hi);
       e->last_kernel[KT_KERNEL_CHECK] = k;
     }

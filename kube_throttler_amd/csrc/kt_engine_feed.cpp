@@ -83,6 +83,16 @@ static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int6
     e->or_abs[d] |= batch_or[d];
   }
   if (!patch) e->views.invalidate();
+  // the match cache: these rows get new atom rows below — the next cached sweep refreshes their words first (a list that outgrows
+  // a patchable batch: the whole table is built again instead)
+  if (e->mc_valid) {
+    if ((int64_t)e->mc_pending.size() + n > kPatchBatchMax) {
+      e->mc_valid = false;
+      e->mc_pending.clear();
+    } else {
+      for (int64_t i = 0; i < n; ++i) e->mc_pending.push_back(rows ? rows[i] : i);
+    }
+  }
   // the overflow guard's bound grows by what this batch brings; only when it passes 2^60 does the next reconcile count
   // exactly on the device (request_sums_in_range), which also forgets the overwritten and deleted pods again
   for (int d = 0; d < D; ++d) {
@@ -552,6 +562,8 @@ int32_t kt_load_snapshot(kt_engine* e, const kt_snapshot* s) {
   KT_HIP(e, hipMemsetAsync(e->pods.meta, 0, (size_t)e->cfg.pod_capacity * 8, e->own_stream));
   KT_HIP(e, hipStreamSynchronize(e->own_stream));
   e->views.invalidate();
+  e->mc_valid = false;  // (the match cache holds words of the rows just cleared)
+  e->mc_pending.clear();
   e->req_sums_valid = true;
   for (auto& b : e->req_sum_bound) b = 0;
   e->pod_rows_hi = 0;

@@ -208,8 +208,8 @@ extern thread_local std::string g_create_error;  // text of the last kt_engine_c
 // path is tuned to a few microseconds).  Read at the same two moments, with a VALUE instead of a flag and therefore not in the
 // table: KT_REPRIEVE_LDS_CAP (kt_engine::reprieve_lds_cap_limit, a test hook of kt_preempt_reprieve_launch and
 // kt_preempt_gangs_reprieve_launch).
-enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSwCount };
-static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU"};
+enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSwCount };
+static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE"};
 struct kt_engine {
   bool sw[kSwCount] = {};  // EnvSwitch values (load_env_switches)
   uint32_t reprieve_lds_cap_limit = 0;  // KT_REPRIEVE_LDS_CAP (test hook, read with the switches): at most so many list entries of
@@ -246,8 +246,22 @@ struct kt_engine {
   ScanViews views;                               // what the full scans read (kt_engine_views.cpp)
   bool cut_plain = false;                        // a scan needed the plain fold: the index chunks stay cut for plain records
   void* cur_launch_lock = nullptr;               // the LaunchLock of the launch-side call in progress (set and cleared under op_mu)
-  std::atomic<int64_t> ctr_index_chunks{0}, ctr_index_words{0}, ctr_index_image_words{0}, ctr_ns_rows{0}, ctr_ns_word_visits{0}, ctr_ns_chunk_visits{0}, ctr_slow_throttles{0}, ctr_packed_words{0}, ctr_agg_workgroups{0}, ctr_view_builds{0};
+  std::atomic<int64_t> ctr_index_chunks{0}, ctr_index_words{0}, ctr_index_image_words{0}, ctr_ns_rows{0}, ctr_ns_word_visits{0}, ctr_ns_chunk_visits{0}, ctr_slow_throttles{0}, ctr_packed_words{0}, ctr_agg_workgroups{0}, ctr_view_builds{0}, ctr_mc_builds{0}, ctr_mc_scans{0}, ctr_mc_planes{0};
   DevBuf<uint16_t> d_latom;                      // pods.latom: rewritten per selector program (kt_translate_pods)
+  // The match cache (kt_index.h: MatchCacheArgs; kt_engine_check.cpp: match_cache_for_scan): per pod row, the matched terms of every
+  // word of its namespace's list.  Derived from the atom rows and the compiled index and from nothing else, so it is written
+  // where they are: void after every compile (mc_gen) and after a table clear (mc_valid), and the rows of every pod upsert wait
+  // in mc_pending for the next cached sweep, which refreshes them first (on its own stream).  Deletes need nothing: a replay is
+  // gated by the pod's valid bit, as the scan is.  Allocated by the first cached sweep of an eligible program.
+  DevBuf<uint64_t> d_mc;                         // [mc.planes][pod_capacity]
+  int64_t* h_mc_rows = nullptr;                  // pinned: the pending rows as the refresh launch reads them (kPatchBatchMax entries)
+  hipEvent_t mc_rows_ev = nullptr;               // behind the last refresh launch: the list buffer is free again
+  bool mc_rows_ev_used = false;
+  std::vector<int64_t> mc_pending;               // rows upserted since the table was last written (at most kPatchBatchMax)
+  bool mc_valid = false;
+  uint64_t mc_gen = ~0ull;                       // the program_gen the table was built for
+  uint64_t mc_planes_gen = ~0ull;                // ... and the one mc_planes was counted for
+  uint32_t mc_planes = 0;                        // the longest namespace word list of the program (0: not a cacheable program)
   DevBuf<unsigned long long> d_overflow;         // valid pods whose relevant atoms did not fit pods.LA
   unsigned long long n_overflow = 0;
   // Pod events without a stream synchronisation (round 4): a small batch is packed into one of kEvSlots pinned slots the
@@ -618,6 +632,10 @@ KT_INTERNAL void amount_to_table(const HostAmount& h, const kt_amounts& a, size_
 KT_INTERNAL kt::ReqBound req_bound(const kt_engine* e);
 KT_INTERNAL bool amount_in_bound(const HostAmount& a, int D);
 KT_INTERNAL void reqs_from_pool(const kt_reqs& pool, uint32_t b, uint32_t e_, std::vector<Req>& out);
+// (kt_engine_check.cpp) the program's match cache, current for a scan enqueued on s behind this call — mc.mw == nullptr: none
+KT_INTERNAL int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc);
+// a pod event batch no larger than this is applied to the scan views / queued for the match cache in place
+constexpr int64_t kPatchBatchMax = 65536;
 // (kt_engine_views.cpp)
 KT_INTERNAL int32_t list_view_rows(kt_engine* e, ScanView& v, const ViewSpec& spec, hipStream_t s);
 KT_INTERNAL int32_t copy_view_records(kt_engine* e, ScanView& v, const ViewSpec& spec, int64_t headroom, hipStream_t s);

@@ -66,7 +66,6 @@ int32_t copy_view_records(kt_engine* e, ScanView& v, const ViewSpec& spec, int64
 }
 
 // ---- pod events applied to the views in place
-constexpr int64_t kPatchBatchMax = 65536;
 // can a batch of n pod rows (largest |request| per dimension batch_max, OR of the values batch_or, a negative value seen)
 // be applied to the current views?  The packed request words only hold what their plan was proved for.
 bool views_patchable(const kt_engine* e, int64_t n, const unsigned __int128* batch_max, const uint64_t* batch_or, bool batch_neg) {

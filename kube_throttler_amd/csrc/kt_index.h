@@ -331,6 +331,19 @@ struct SelProgram;
 uint32_t aggregate_fixed_lds();
 uint32_t check_fixed_lds();
 uint32_t check_word_lds(int D);  // check: bytes per 64-bit word of term numbers beside the image (TermInfo + WordVerdict<DT>)
+// The match cache (kt_scan.h: replay_tile; kt_kernels_match.hip: the builder): per pod row, the matched terms of every entry of
+// its namespace's word list — mw[k][row], one plane per list position.  Programs of ONE chunk without slow shapes whose longest
+// list has at most kMatchPlanes entries; the engine owns the table and says when it is valid (kt_engine_check.cpp).  The lean
+// two-per-CU PreFilter sweep replays it; the aggregate scan does not (measured: profiles/match_cache.txt — through the view's
+// row list the planes are a second dependent trip per tile, and the cached form was no faster than its scan).
+constexpr int kMatchPlanes = 8;   // planes the table and its builder take
+constexpr int kMatchReplay = 4;   // planes the cached sweep holds in registers: programs with longer lists are not cached
+struct MatchCacheArgs {
+  const uint64_t* mw = nullptr;  // nullptr: no table (the scans run scan_tile)
+  uint64_t stride = 0;           // words per plane (the engine's pod capacity)
+  uint32_t planes = 0;           // planes in use: the longest namespace word list of the program (<= kMatchPlanes)
+  mutable bool used = false;     // out: the launch replayed the table
+};
 // which pods an aggregate scan covers and how they enter the target buffer
 struct AggScan {
   int64_t n = 0;                 // pods
@@ -424,6 +437,14 @@ struct CheckByNs {
   const uint32_t* wg_range = nullptr;
   int wg_range_G = 0;  // the workgroups the ranges were planned for (a launch with another grid ignores them)
 };
+// can a program be cached at all (what the builder asks of the index)?
+bool match_cache_fits(const IndexDev& ix);
+// ... and will the sweep of every row replay a table of `planes` planes (launch_check_indexed's own test, asked by the engine
+// BEFORE it builds or refreshes one: the lean two-per-CU form, 8 dimensions at most, lists of at most kMatchReplay words)?
+bool check_replays_match_cache(const PodTable& pods, const SelProgram& sp, const IndexDev& ix, uint32_t planes, bool overflow_pods, bool one_per_cu);
+// (re)writes the planes of pod rows [0, n) (rows_dev == nullptr) or of the n listed rows; false: not dispatchable
+bool launch_build_match_cache(const PodTable& pods, int64_t n, const int64_t* rows_dev, const IndexDev& ix, uint64_t* mw, uint64_t stride,
+                              uint32_t planes, hipStream_t s);
 int check_sweep_blocks(int64_t n);  // workgroups of a namespace-ordered lean sweep over n pod rows (one per CU)
 // the per-word check tables of the whole index in global memory: TermInfo [total_words][64], then WordVerdict [total_words]
 // (total_words = HostIndex::bm_words) — built once per generation of CheckRecs instead of once per (workgroup, chunk)
@@ -432,7 +453,7 @@ void launch_build_verdict_images(const IndexDev& ix, uint32_t total_words, const
 const char* launch_check_indexed(const PodTable& pods, int64_t n, const int64_t* rows_dev, const SelProgram& sp,
                           const SelProgram* sp_dev, const IndexDev& ix, const void* recs, uint64_t* summary,
                           uint8_t* status, hipStream_t s, const CheckSmall* small = nullptr, bool overflow_pods = false,
-                          const CheckByNs* by_ns = nullptr, bool one_per_cu = false);
+                          const CheckByNs* by_ns = nullptr, bool one_per_cu = false, const MatchCacheArgs* mc = nullptr);
 // kt_sweep: the PreFilter sweep of pod rows [0, n) and the packed reconcile scan of the same rows as ONE launch
 // (kt_check_bitmap's AGG instantiation: single-chunk programs without a slow list; pk sized for aggregate_slab_pods(n,
 // aggregate_blocks(n))).  The slabs are left for launch_reduce_finalize_packed (*launched_blocks of them).  nullptr: not

@@ -133,8 +133,14 @@ void launch_build_verdict_images(const IndexDev& ix, uint32_t total_words, const
 }
 
 // what a tile needs of its 64 pods before it can start (kt_check_bitmap's fetch_tile)
-template <int LA, int NV = 1>
-struct TileRec {
+template <bool CACHED>
+struct TileMatchWords {};
+template <>
+struct TileMatchWords<true> {
+  uint64_t mx[kMatchReplay];   // cached form: the pod's planes of the match cache (instead of the atom row)
+};
+template <int LA, int NV = 1, bool CACHED = false>
+struct TileRec : TileMatchWords<CACHED> {
   uint32_t p;                  // pod row
   uint64_t meta;
   u32x4 raw[LA / 8];           // atom row
@@ -188,6 +194,8 @@ struct BmCheckArgs {
   uint32_t off_rank, off_tab;
   uint32_t pk_nw, pk_rec;  // PackPlan::nw / rec_bytes
   uint32_t pk_dim[8];      // per dimension: shift | pos << 8 | word << 16 | (width != 0) << 24
+  // cached form (the CACHED instantiation): the match cache of the program, indexed by pod row
+  MatchCacheArgs mc;
 };
 
 static BmCheckArgs make_bm_check_args(const PodTable& pods, int64_t n, const int64_t* rows, const SelProgram& sp,
@@ -242,9 +250,16 @@ uint32_t check_word_lds(int D) { return 64u * 8u + (uint32_t)(D <= 8 ? sizeof(Wo
 //       matches, exactly as kt_aggregate_bitmap's packed instantiation does, and the workgroup spills its table of records
 //       as a slab for kt_reduce_finalize_packed.  One pass over the pod rows, one chunk prologue, one scan per pod where
 //       check + aggregate made two; the check's verdicts are those against the status stored BEFORE this reconcile.
-template <int DT, int LA, bool VETO, int NEED, int WPE, bool FULL, bool SMALL, bool ONE = false, bool AGG = false>
+// CACHED: the lean ONE sweep over rows [0, n) REPLAYS the pod's words of the match cache (a.mc; kt_scan.h: replay_tile) instead
+//       of scanning: no atom row is loaded, no bitmap row gathered, and of the image only the namespace lists are staged.  The
+//       prologue's TermInfo / WordVerdict, the settle and the drain are those of the uncached form: the words the table holds
+//       are exactly what its scan_tile would hand to them.  ONE instantiation — 8 dimensions, lists of at most kMatchReplay
+//       words: 63 VGPRs, 0 B of scratch (profiles/kernel_resources_match_cache.txt); 16 dimensions or a second batch of planes
+//       carried 8-52 B of scratch and were never measured to win: such programs keep the scan.
+template <int DT, int LA, bool VETO, int NEED, int WPE, bool FULL, bool SMALL, bool ONE = false, bool AGG = false, bool CACHED = false>
 __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckArgs a) {
   static_assert(!AGG || (ONE && !FULL && !SMALL && WPE < 8), "the fused sweep is the lean single-chunk form, one workgroup per CU");
+  static_assert(!CACHED || (ONE && !FULL && !SMALL && !AGG && WPE >= 8 && !VETO && NEED == 2 && DT == 8), "the cached form is the lean two-per-CU sweep (one instantiation: nothing of the scan's form is left in it)");
   // (pieces of the three rows per batch: 12 registers each — the whole rows of a 16-dimension engine would be 96 registers
   //  of a 128-register kernel: four pieces per batch at most, two batches there)
   constexpr int kDrainUnroll = WPE >= 8 ? 1 : (DT / 2 > 4 ? 4 : DT / 2);  // drains in the middle of a scan (the list ran full)
@@ -312,18 +327,19 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
     const uint32_t wt0 = SMALL ? (wave == 0 ? blockIdx.y : n_wtiles) : by_ns ? t_lo + wave : blockIdx.x * (kBlockIx / kWave) + wave;
     const uint32_t wt_step = SMALL ? n_wtiles : by_ns ? (uint32_t)(kBlockIx / kWave) : wstep;
     auto fetch_tile = [&](uint32_t wt) {
-      TileRec<LA, AGG ? DT : 1> r;
+      TileRec<LA, AGG ? DT : 1, CACHED> r;
       const uint32_t i = rec0 + wt * kWave + lane;
       const uint32_t ic = min(i, rec_end - 1u);
-      r.p = (SMALL && a.n_inline) ? (uint32_t)a.inline_rows[ic & 7u] : a.rows ? (uint32_t)a.rows[ic] : ic;
+      r.p = CACHED ? ic : (SMALL && a.n_inline) ? (uint32_t)a.inline_rows[ic & 7u] : a.rows ? (uint32_t)a.rows[ic] : ic;
       r.meta = by_ns ? a.v_meta[ic] : a.meta[r.p];
-      load_atoms<LA>(by_ns ? a.v_latom : a.latom, by_ns ? ic : r.p, r.raw);
+      if constexpr (CACHED) load_match_words(a.mc, r.p, r.mx);  // (with the meta word, not behind it: they hang off the row only)
+      else load_atoms<LA>(by_ns ? a.v_latom : a.latom, by_ns ? ic : r.p, r.raw);
       const unsigned long long* carry_w = by_ns ? (const unsigned long long*)a.carry + ic : (const unsigned long long*)a.summary + (by_ns ? r.p : i);
       r.carried = (!SMALL && !first && i < rec_end) ? __hip_atomic_load(carry_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
       if constexpr (AGG) load_requests<DT>(a.req, DS, (int64_t)r.p, r.v);  // every lane's: the row does not hang off the meta word
       return r;
     };
-    TileRec<LA, AGG ? DT : 1> cur{};
+    TileRec<LA, AGG ? DT : 1, CACHED> cur{};
     KT_PROF_T(t_b0);
     __syncthreads();  // nobody reads the previous image any more
     KT_PROF_T(t_b1);
@@ -340,6 +356,9 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
        // — sweeps of multi-chunk programs — the chunk's words of the TermInfo / WordVerdict tables kt_build_verdict_images left
       const u32x4* img0 = (const u32x4*)(a.ix.blob + ch.img_off);
       StageSeg segs[4] = {chunk_image_segment(a.ix, ch), StageSeg{0u, img0, 0u}, StageSeg{0u, img0, 0u}, StageSeg{0u, img0, 0u}};
+      // (cached form: of the image only the namespace lists, at their usual offsets — the rows and word headers are not read)
+      if constexpr (CACHED)
+        segs[0] = StageSeg{a.ix.lds_img + ch.off_nsl_rng, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_nsl_rng), (ch.lds_bytes - ch.off_nsl_rng) / 16u};
       if constexpr (AGG) segs[1] = StageSeg{a.off_rank, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_term_rank), ch.n_words * 8u};
       if (from_images) {
         segs[2] = StageSeg{a.off_tinfo, (const u32x4*)(a.wv_img + (size_t)ch.w0 * verdict_image_word_bytes<DT>()), ch.n_words * (64u * 8u / 16u)};
@@ -396,7 +415,7 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
       const uint64_t meta = cur.meta;
       u32x4 raw[LA / 8];
 #pragma unroll
-      for (int q = 0; q < LA / 8; ++q) raw[q] = cur.raw[q];
+      for (int q = 0; q < LA / 8; ++q) raw[q] = CACHED ? u32x4{0u, 0u, 0u, 0u} : cur.raw[q];
       // class counters so far (bit 1 = error) ride in the summary word (namespace order: the carry word) between chunks
       unsigned long long* carry_w = by_ns ? (unsigned long long*)a.carry + ic : (unsigned long long*)a.summary + si;
       const unsigned long long carried = cur.carried;
@@ -411,7 +430,7 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
       const uint32_t ns_ok_raw = a.ns_valid[ns];
       bool pod_err = (carried & 2ull) != 0;
       uint32_t ro[LA];
-      atom_row_offsets<LA>(raw, ro);
+      if constexpr (!CACHED) atom_row_offsets<LA>(raw, ro);
       uint32_t n_list = 0;  // wave-uniform
       uint32_t last_t = 0xFFFFFFFFu;
       // AGG: is the pod counted (shouldCountIn && isNotFinished: throttle_controller.go:217-219, pod_util.go:26-28), and
@@ -633,7 +652,10 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
         return term_match_mem(*a.sp, bm.term_g[c], a.lpair + (uint64_t)p * (uint32_t)a.LS, a.lkey + (uint64_t)p * (uint32_t)a.LS, a.LS);
       };
       auto peel_tight = [&](bool has, uint32_t c) { push(has, c); };
-      if constexpr (PREFETCH) {
+      if constexpr (CACHED) {
+        auto settle_word = [&](uint32_t w, uint64_t x, int) -> uint64_t { return settle(w, x, fetch(w)); };
+        replay_tile(bm, scan_on, ns, cur.mx, a.mc.planes, peel_tight, settle_word, ScanNoPrefetch());
+      } else if constexpr (PREFETCH) {
         scan_tile<LA, VETO, NEED, VETO>(
             bm, scan_on, ns, ro, peel_tight, confirm_slow,
             [&](uint32_t w, uint64_t x, const VerdictRegs& q) -> uint64_t { return settle(w, x, q); },
@@ -720,10 +742,19 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
     hipLaunchKernelGGL(kfn, g_, b_, lds_bytes, s, bm_args);                                                     \
   }
+// (the cached sweep is ONE instantiation whatever the program's form: VETO and NEED only shape scan_tile and open_chunk's veto
+//  offsets, and the replay runs neither — a rich program's table was built by kt_build_match_cache<true, 3>, its words are final)
+#define KT_BM_LAUNCH_CACHED()                                                                                   \
+  {                                                                                                             \
+    auto kfn = kt_check_bitmap<8, 8, false, 2, 8, false, false, true, false, true>;                             \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
+    hipLaunchKernelGGL(kfn, g_, b_, lds_bytes, s, bm_args);                                                     \
+  }
 #define KT_BM_CASE(DT_, LA_, VETO_, NEED_)                                                   \
   {                                                                                          \
     if (small) KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 4, true, true, false)                    \
     else if (full) KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 4, true, false, false)               \
+    else if (cached) KT_BM_LAUNCH_CACHED()                                                   \
     else if (two_per_cu) KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 8, false, false, true)         \
     else KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 4, false, false, false)                        \
   }
@@ -741,7 +772,8 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
 // beside the working buffers (a single throttle with thousands of terms)
 const char* launch_check_indexed(const PodTable& pods, int64_t n, const int64_t* rows_dev, const SelProgram& sp,
                           const SelProgram* sp_dev, const IndexDev& ix, const void* recs, uint64_t* summary,
-                          uint8_t* status, hipStream_t s, const CheckSmall* sm, bool overflow_pods, const CheckByNs* by_ns, bool one_per_cu) {
+                          uint8_t* status, hipStream_t s, const CheckSmall* sm, bool overflow_pods, const CheckByNs* by_ns, bool one_per_cu,
+                          const MatchCacheArgs* mc) {
   if (n <= 0) return "";
   const int DT = dt_bucket_ix(pods.D), LA = pods.LA;
   if (status) (void)hipMemsetAsync(status, 0, (size_t)n * (size_t)sp.T, s);
@@ -776,6 +808,10 @@ const char* launch_check_indexed(const PodTable& pods, int64_t n, const int64_t*
   // (16 / 32 atom slots: the 64-VGPR form carries 92-330 B of scratch where the 128-VGPR one has 20-144, at the same time —
   //  0.0805 against 0.0803 ms at 1M x 1k with 16 labels per pod: one per CU there)
   const bool two_per_cu = one && !full && !small && !need5 && !one_per_cu && LA <= 8 && 2 * bm_total <= (uint32_t)kMaxLds;
+  // the cached form: the two-per-CU sweep of rows [0, n) of a program the engine holds a valid match cache for
+  const bool cached = two_per_cu && DT <= 8 && mc != nullptr && mc->mw != nullptr && rows_dev == nullptr && mc->planes >= 1u &&
+                      mc->planes <= (uint32_t)kMatchReplay && (uint64_t)n <= mc->stride && match_cache_fits(ix);
+  if (cached) bm_args.mc = *mc, mc->used = true;
   int64_t nb = (n + kBlockIx - 1) / kBlockIx;
   const int64_t max_b = two_per_cu ? 2 * kCUs : kCUs;
   if (nb > max_b) nb = max_b;
@@ -799,6 +835,17 @@ const char* launch_check_indexed(const PodTable& pods, int64_t n, const int64_t*
   else { if (DT <= 8) KT_BM_CASE(8, 32, true, 3) else KT_BM_CASE(16, 32, true, 3) }
 #endif
   return small ? "kt_check_bitmap_small" : ix.n_chunks == 1 ? "kt_check_bitmap" : "kt_check_bitmap_chunked";
+}
+
+// launch_check_indexed's `cached` test for a lean sweep of every row, without a launch (the same conditions, in the same words)
+bool check_replays_match_cache(const PodTable& pods, const SelProgram& sp, const IndexDev& ix, uint32_t planes, bool overflow_pods, bool one_per_cu) {
+  uint32_t bm_total = 0;
+  (void)make_bm_check_args(pods, 1, nullptr, sp, nullptr, ix, nullptr, nullptr, nullptr, &bm_total);
+  if (bm_total > (uint32_t)kMaxLds) return false;
+  const bool full = ix.n_slow != 0 || overflow_pods || ix.has_long;
+  const bool need5 = ix.max_need > 3u;
+  const bool two_per_cu = ix.n_chunks == 1 && !full && !need5 && !one_per_cu && pods.LA <= 8 && 2 * bm_total <= (uint32_t)kMaxLds;
+  return two_per_cu && dt_bucket_ix(pods.D) <= 8 && planes >= 1u && planes <= (uint32_t)kMatchReplay && match_cache_fits(ix);
 }
 
 // kt_sweep: PreFilter sweep of rows [0, n) + the packed reconcile scan of the same rows in one launch (AGG instantiation).

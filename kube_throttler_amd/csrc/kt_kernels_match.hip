@@ -1,0 +1,111 @@
+// kt_kernels_match.hip — kt_build_match_cache: the match cache of single-chunk programs (kt_scan.h: replay_tile), gfx950.
+#include "kt_scan.h"
+
+namespace kt {
+
+// ---------------------------------------------------------------------------------------------------
+// kt_build_match_cache — mw[k][row] = what scan_tile hands to post() for entry rng.x + k of the namespace list of pod `row`:
+// the terms of that word the pod matches (exact: cached programs have no `slow` shapes).  Zero where the list is shorter and
+// for rows without a valid pod.  The chunk is staged as the ONE forms of the scans stage it, a wave owns a tile of 64 rows,
+// lane = row, and runs the very scan_tile of those forms with a post hook that stores the word and keeps nothing for the peel:
+// every lane that still has words advances in every round, so the (wave-uniform) round counter IS the lane's list position.
+//   rows == nullptr : rows [0, n)          (after a compile: one launch over every row ever fed)
+//   rows != nullptr : the n listed rows    (pod events: the rows whose atom rows were rewritten; a row may be listed twice —
+//                                           both lanes store the same words)
+// Runs where the atom rows are written and nowhere else: nothing a reconcile or a check changes enters these words.
+// ---------------------------------------------------------------------------------------------------
+struct MatchBuildArgs {
+  const uint64_t* meta;
+  const uint16_t* latom;
+  const int64_t* rows;
+  uint64_t* mw;
+  uint64_t stride;   // words per plane
+  uint32_t planes;   // planes to write (<= kMatchPlanes)
+  uint32_t n;        // rows [0, n) or list entries
+  uint32_t cap;      // rows a plane holds: a listed row at or beyond it is skipped
+  BmIndexArgs ix;
+  BmChunk ch;
+};
+
+template <bool VETO, int NEED>
+__global__ __launch_bounds__(kBlockIx) void kt_build_match_cache(const MatchBuildArgs a) {
+  constexpr int LA = 8;
+  KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const BmChunk& ch = a.ch;
+  {
+    const StageSeg segs[1] = {chunk_image_segment(a.ix, ch)};
+    lds_stage_segments<1, 4>(lds, segs);
+  }
+  const BmView bm = open_chunk<VETO>(lds, a.ix, ch);
+  __syncthreads();
+  const uint32_t n = a.n, planes = a.planes;
+  const uint32_t n_wtiles = (n + kWave - 1u) / kWave;
+  const uint32_t wstep = gridDim.x * (uint32_t)(kBlockIx / kWave);
+  for (uint32_t wt = blockIdx.x * (uint32_t)(kBlockIx / kWave) + wave; wt < n_wtiles; wt += wstep) {
+    // always from valid addresses: lanes past the end re-read the last entry and store nothing
+    const uint32_t i = wt * kWave + lane;
+    const uint32_t ic = min(i, n - 1u);
+    const uint32_t p = a.rows ? (uint32_t)a.rows[ic] : ic;
+    const bool in = i < n && p < a.cap;
+    const uint32_t pc = min(p, a.cap - 1u);
+    const uint64_t meta = a.meta[pc];
+    u32x4 raw[1];
+    load_atoms<LA>(a.latom, (int64_t)pc, raw);
+    const bool on = in && ((meta >> kMetaStateShift) & kPodValid) != 0;
+    const uint32_t ns = on ? (uint32_t)(meta & kMetaNsMask) : 0u;
+    uint32_t ro[LA];
+    atom_row_offsets<LA>(raw, ro);
+    uint64_t* q = a.mw + pc;
+    uint32_t round = 0u;  // wave-uniform
+    scan_tile<LA, VETO, NEED, false>(
+        bm, on, ns, ro, [&](bool, uint32_t) {}, [&](uint32_t) { return true; },
+        [&](uint32_t, uint64_t xx, int) -> uint64_t {
+          if (in && round < planes) q[(uint64_t)round * a.stride] = xx;
+          round += 1u;
+          return 0ull;
+        });
+    for (; round < planes; ++round)  // the planes past the longest list of the tile
+      if (in) q[(uint64_t)round * a.stride] = 0ull;
+  }
+}
+
+bool match_cache_fits(const IndexDev& ix) {
+  if (ix.n_chunks != 1 || ix.h_chunks.size() != 1 || ix.n_slow != 0 || ix.has_long || ix.la > 8u || ix.max_need > 3u) return false;
+  const BmChunk& ch = ix.h_chunks[0];
+  return !ch.has_slow && ch.n_words != 0u && ix.bm_max_lds <= (uint32_t)kMaxLds;
+}
+
+bool launch_build_match_cache(const PodTable& pods, int64_t n, const int64_t* rows_dev, const IndexDev& ix, uint64_t* mw, uint64_t stride,
+                              uint32_t planes, hipStream_t s) {
+  if (n <= 0) return true;
+  if (!match_cache_fits(ix) || pods.LA > 8 || !mw || planes == 0u || planes > (uint32_t)kMatchPlanes || stride == 0u || n > (int64_t)stride)
+    return false;
+  MatchBuildArgs a{};
+  a.meta = pods.meta, a.latom = pods.latom, a.rows = rows_dev, a.mw = mw, a.stride = stride, a.planes = planes;
+  a.n = (uint32_t)n, a.cap = (uint32_t)std::min<uint64_t>(stride, 0x80000000ull);
+  uint32_t o = 0;
+  auto take = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
+  plan_bitmap_index(ix, a.ix, take);
+  a.ch = ix.h_chunks[0];
+  const uint32_t lds_bytes = o;
+  const int64_t tiles = (n + kWave - 1) / kWave, per_wg = kBlockIx / kWave;
+  const int64_t nb = std::min<int64_t>((tiles + per_wg - 1) / per_wg, 2 * kCUs);
+  dim3 g_((unsigned)nb), b_(kBlockIx);
+#define KT_MATCH_LAUNCH(VETO_, NEED_)                                                                           \
+  {                                                                                                             \
+    auto kfn = kt_build_match_cache<VETO_, NEED_>;                                                              \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
+    hipLaunchKernelGGL(kfn, g_, b_, lds_bytes, s, a);                                                           \
+  }
+#ifdef KT_FAST_BUILD
+  KT_MATCH_LAUNCH(false, 2)
+#else
+  if (!ix.rich) KT_MATCH_LAUNCH(false, 2) else KT_MATCH_LAUNCH(true, 3)
+#endif
+#undef KT_MATCH_LAUNCH
+  return true;
+}
+
+}  // namespace kt

@@ -437,4 +437,54 @@ __device__ __forceinline__ void scan_tile(const BmView& b, bool lane_on, uint32_
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The match cache.  The word `xx` an advance of scan_tile hands to post() depends on the pod's atom row and namespace and on
+// the compiled index — on nothing a reconcile or a check changes — so single-chunk programs keep it per pod row, in a table
+// that is written where atom rows are written (kt_build_match_cache, kt_kernels_match.hip):
+//   mw[k][row] = the matched terms of entry rng.x + k of the namespace list of pod `row` (0 past the list's end, 0 for a row
+//                without a valid pod), k < kMatchPlanes: one plane per list position, a wave reads 512 contiguous bytes of it
+// and the ONE form of the PreFilter sweep replays it (replay_tile) instead of gathering the bitmap rows again.  (MatchCacheArgs,
+// kMatchPlanes: kt_index.h.)
+// ---------------------------------------------------------------------------------------------------
+
+// The planes of pod row p, one batch of loads from always-valid addresses; planes at or past `planes` are zero.  They hang off
+// the row index alone and are requested together with the meta word, not behind it.  (kMatchReplay = 4 planes are what the
+// 64-VGPR sweep holds without scratch: eight at once, or a second batch behind the first, cost it 28-52 B — programs with longer
+// lists keep their scan.)
+__device__ __forceinline__ void load_match_words(const MatchCacheArgs& m, uint32_t p, uint64_t (&x)[kMatchReplay]) {
+  const uint64_t* q = m.mw + p;
+#pragma unroll
+  for (int j = 0; j < kMatchReplay; ++j) {
+    x[j] = 0ull;
+    if ((uint32_t)j < m.planes) x[j] = q[(uint64_t)j * m.stride];  // (wave-uniform condition)
+  }
+}
+
+// scan_tile's contract for match / post / pre, fed from the table: list position k (wave-uniform) is one advance — a lane whose
+// list has an entry k takes its word number from the list and x = mx[k], the others take 0; a word in which no lane of the
+// tile has a bit is skipped; what post() returns goes through the same peel, ascending term numbers per lane.  No bitmap row,
+// no word header and no namespace mask is read: of the chunk image only nsl_rng / nsl have to be resident.
+template <class Match, class Post, class Pre>
+__device__ __forceinline__ void replay_tile(const BmView& b, bool lane_on, uint32_t ns, const uint64_t (&mx)[kMatchReplay], uint32_t planes,
+                                            Match&& match, Post&& post, Pre&& pre) {
+  const u32x2 rng = b.nsl_rng[ns];
+  const uint32_t len = lane_on ? min(rng.y - rng.x, planes) : 0u;
+#pragma unroll
+  for (int k_ = 0; k_ < kMatchReplay; ++k_) {
+    const uint32_t k = (uint32_t)k_;
+    if (k >= planes) break;  // wave-uniform
+    const bool adv = k < len;
+    uint64_t x = adv ? mx[k_] : 0ull;
+    if (__ballot(x != 0ull) == 0ull) continue;
+    const uint32_t w = b.nsl[adv ? rng.x + k : 0u].w;
+    x = post(w, x, pre(w));
+    while (__ballot(x != 0ull) != 0ull) {
+      const bool has = x != 0ull;
+      const uint32_t c = has ? w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u : 0u;
+      x &= x - 1ull;
+      match(has, c);
+    }
+  }
+}
+
 }  // namespace kt

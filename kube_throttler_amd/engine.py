@@ -51,6 +51,7 @@ COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS,
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
 COUNTER_AGG_WORKGROUPS = 11
 COUNTER_VIEW_BUILDS = 10
+COUNTER_MATCH_CACHE_BUILDS, COUNTER_MATCH_CACHE_SCANS, COUNTER_MATCH_CACHE_PLANES = 12, 13, 14
 
 
 def partial_layout(n_dims: int) -> dict:
@@ -471,6 +472,20 @@ class Engine:
     def view_builds(self) -> int:
         """Scan view builds so far (either view); pod events that fit the views are patched in and do not count."""
         return int(lib().kt_counter(self._h, COUNTER_VIEW_BUILDS))
+
+    def match_cache_builds(self) -> int:
+        """Full builds of the match cache so far (one per compile / table clear; pod events refresh their rows and do not count)."""
+        return int(lib().kt_counter(self._h, COUNTER_MATCH_CACHE_BUILDS))
+
+    def match_cache_planes(self) -> int:
+        """The longest namespace word list of the compiled single-chunk program as the last sweep of every row counted it (0: not
+        counted); programs with more than four are not cached."""
+        return int(lib().kt_counter(self._h, COUNTER_MATCH_CACHE_PLANES))
+
+    def match_cache_scans(self) -> int:
+        """PreFilter sweeps served from the match cache so far (0 under KT_NO_MATCH_CACHE=1 and for programs
+        the cache does not take: several chunks, slow shapes, a namespace word list longer than four, more than 8 dimensions)."""
+        return int(lib().kt_counter(self._h, COUNTER_MATCH_CACHE_SCANS))
 
     def partial_words(self) -> int:
         return self.throttle_rows() * partial_layout(self.D)["stride"]
