@@ -393,7 +393,7 @@ int32_t kt_headroom_fetch(kt_engine* e, int64_t n, int64_t* out_copies, int32_t*
  *      KT_ERR_NOT_READY; a status stored with KT_RECONCILE_APPLY stays stored).  Its aggregate runs beside the partial buffer:
  *      a pending kt_aggregate_launch keeps its sums.  The results live in buffers of their own, so a kt_reconcile_launch issued
  *      on the same stream after the launch leaves it fetchable.
- *      Out of scope: the paged form (more than KT_MAX_DIMS resource names), several ranks (the reprieve pass that shrinks the
+ *      More than KT_MAX_DIMS resource names: kt_paged_preempt.  Out of scope: several ranks (the reprieve pass that shrinks the
  *      victim set further is kt_preempt_reprieve_launch below). --------------------------------------------------------- */
 #define KT_PREEMPT_NONE (-1)
 int32_t kt_preempt_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
@@ -421,7 +421,7 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
  *      m_eff, the list cut, every refusal and its code, "a refused call leaves the check slot, the reconcile report and the
  *      result buffers alone", n == 0 and n_cand == 0, and the slot rules are those of kt_preempt_launch: the two launches share
  *      the one pending result, fetched with kt_preempt_fetch — a later launch of either kind replaces it.
- *      Out of scope: the paged form, several ranks. --------------------------------------------------------------------- */
+ *      More than KT_MAX_DIMS resource names: kt_paged_preempt with KT_PREEMPT_REPRIEVE.  Out of scope: several ranks. ---- */
 int32_t kt_preempt_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows, int64_t now_s,
                                    int32_t now_ns, int32_t on_equal, void* stream);
 /* ---- preempt, for gangs: the shortest victim prefix that lets a WHOLE gang in — where kt_preempt_launch and kt_admit_gangs_launch
@@ -656,6 +656,47 @@ int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n
  * kt_headroom_launch.  Uses page 0's check slot.  out_copies [n] and out_limiting [n] are both nullable. */
 int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal,
                           int64_t cap, int64_t* out_copies, int32_t* out_limiting);
+/* kt_preempt_launch and, with KT_PREEMPT_REPRIEVE in `flags`, kt_preempt_reprieve_launch over the pages, synchronous: their
+ * definitions on the cluster of ALL names — counted pods, S_k, the m_eff cut, the victim mask, exact presence by contributor
+ * counts, the operational walk with no monotonicity assumption, KT_PREEMPT_NONE.  n_pages == 1 returns byte for byte what
+ * kt_preempt_launch (kt_preempt_reprieve_launch) + kt_preempt_fetch return.  The answer is NOT a combination of per-page calls
+ * (with requests of either sign a page may pass at k, fail at k + 1 and pass again, so the maximum of the pages' prefixes is
+ * wrong), which is why the kernels see every page.  What pages add to the definition:
+ *   - every page reconciles its own names at `now`; the pod count is the same in every page and is judged once, on page 0;
+ *   - the name part of the four CheckThrottledFor steps combines by the rule above: a (throttle, k) pair fails iff the count
+ *     part or some page's name part fails;
+ *   - status.calculatedThreshold is replaced as a whole (throttle_controller.go:116-133 compares it by value over all names):
+ *     a throttle reads status.calculatedThreshold on EVERY page iff, on SOME page, calculatedAt is set in the stored status or
+ *     the dry reconcile replaces it; otherwise it reads spec.threshold on every page.  (The stored flag is part of the OR: the
+ *     answer stays right between a kt_paged_reconcile with KT_RECONCILE_APPLY and the host's status write-back, when the
+ *     pages' stored flags may disagree);
+ *   - a throttle keeps its stored status in every state iff its reconcile is an error on some page or it is not valid and
+ *     responsible; the stored status is then read on every page;
+ *   - which candidates are counted, which throttles match which pod, the error rows and m_eff come from ONE check of page 0
+ *     over pod_rows ++ cand_rows (the selector side is the same in every page; a pod-level error shows in every page).
+ * On page 0's stream, in order: that check; for every page its dense aggregate (beside its partial buffer) and its dry finalize
+ * at `now`; the copy of the page descriptors; one launch of kt_preempt_paged; with the flag one launch of
+ * kt_preempt_reprieve_paged (csrc/kt_kernels_preempt_paged.hip), whose list state is sized with the sum of the pages' names
+ * (in LDS, beyond that in a workspace of page 0).  out_prefix [n] and out_victims [n][n_cand] are both nullable.
+ * Refused before anything is launched, and before any page's check slot, reconcile report or result buffer is touched: what
+ * kt_paged_admit refuses about the page set (different throttle-row counts, an engine named twice: KT_ERR_INVALID_ARGUMENT;
+ * different devices: KT_ERR_UNSUPPORTED), what kt_preempt_launch refuses about its arguments (and flags other than
+ * KT_PREEMPT_REPRIEVE: KT_ERR_INVALID_ARGUMENT), and what it refuses about an engine, asked of every page: a
+ * KT_VARIANT_INCREMENTAL engine, an exchange world above 1, a `used` wider than int64 (KT_ERR_UNSUPPORTED) — as there, the one
+ * thing that may run first is a page's kernel that sums the |requests|.  n == 0 is KT_OK and launches nothing; n_cand == 0
+ * answers 0 or KT_PREEMPT_NONE per pod.  Locking (every page exclusively, in address order) and ordering are kt_paged_admit's.
+ * Slots: the call uses page 0's check slot (a pending kt_check_launch / kt_headroom_launch of page 0 is dropped) and page 0's
+ * preempt result buffers — the results are handed out by the call, so a preempt result that was pending on page 0 is gone
+ * afterwards (kt_preempt_fetch answers KT_ERR_NOT_READY) while a pending kt_forecast_launch of page 0 stays fetchable; every
+ * page's dry finalize writes that page's reconcile result buffers, so every page's pending reconcile report is dropped (a status
+ * stored with KT_RECONCILE_APPLY stays stored); a pending kt_aggregate_launch of any page keeps its sums.  The call is a dry
+ * run: stored status and reserved amounts of no page change.  A device error after the first launch is returned once the
+ * stream has drained; no page keeps a pending result.
+ * Out of scope: the gang forms and the forecast over pages, several ranks. */
+#define KT_PREEMPT_REPRIEVE 0x1u
+int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_cand,
+                         const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, uint32_t flags,
+                         int64_t* out_prefix /* [n], nullable */, uint8_t* out_victims /* [n][n_cand], nullable */);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

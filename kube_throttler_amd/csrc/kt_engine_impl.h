@@ -361,6 +361,11 @@ struct kt_engine {
   DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's and kt_preempt_gangs_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
   bool preempt_ready = false;
   int64_t preempt_n = 0, preempt_m = 0;
+  // kt_paged_preempt (on page 0): the page descriptors of kt_preempt_paged, on the device and — the source of an asynchronous copy,
+  // under the rule of h_admit_pages with preempt_pages_ev in admit_pages_ev's place — on the host
+  DevBuf<uint8_t> d_preempt_pages;
+  std::vector<kt::PreemptPage> h_preempt_pages;
+  hipEvent_t preempt_pages_ev = nullptr;
   // kt_preempt_gangs_launch shares that one pending result (prefix and victim bytes per GANG, preempt_n = the gangs); the kind tag
   // says which fetch may read it.  Its offsets and the blocking member per gang live in buffers of their own
   bool preempt_gangs = false;

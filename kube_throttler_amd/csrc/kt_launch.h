@@ -141,6 +141,28 @@ void launch_preempt_gangs_reprieve(const AdmitPage& pg, int64_t n, int64_t m, co
                                    int T, bool on_equal, const uint8_t* status, const unsigned long long* partial, const AmountTab& calc,
                                    const uint8_t* calc_updated, const uint8_t* error, const int64_t* prefix, uint8_t* victims, void* ws,
                                    uint32_t lds_cap_limit, hipStream_t s);
+// the victim prefix and its reprieve pass over n_pages >= 1 pages (kt_kernels_preempt_paged.hip).  One descriptor per page: the
+// page as kt_admit reads it (the state offsets are unused), and of that page's own dense aggregate and dry finalize at `now` the
+// partial rows with exact contributor counts, the calculated threshold and the calc_updated / error bytes.  launch_preempt_paged
+// copies the descriptors to pages_dev and records pages_copied behind the copy (`pages` stays unmodified until the event has
+// completed), then launches kt_preempt_paged: rows_dev [n + m], status / summary: ONE check of page 0 over those rows; prefix [n]
+// and victims [n][m] out, on page 0.  false: the copy failed (*hip_err).  launch_preempt_reprieve_paged, behind it on the same
+// stream, reads the same device descriptors; its list state is sized with the sum of the pages' D in D's place
+// (reprieve_paged_ws_bytes bytes of workspace, 0: no list can outgrow LDS)
+struct PreemptPage {
+  AdmitPage pg;
+  const unsigned long long* partial;  // [T][partial_stride(pg.D)]
+  AmountTab calc;
+  const uint8_t* calc_updated;        // [T]
+  const uint8_t* error;               // [T]
+};
+bool launch_preempt_paged(const PreemptPage* pages, int n_pages, PreemptPage* pages_dev, hipEvent_t pages_copied, int64_t n, int64_t m,
+                          const int64_t* rows_dev, int T, bool on_equal, const uint8_t* status, const uint64_t* summary, int64_t* prefix,
+                          uint8_t* victims, hipStream_t s, hipError_t* hip_err);
+size_t reprieve_paged_ws_bytes(int T, const PreemptPage* pages, int n_pages, int64_t n, uint32_t lds_cap_limit);
+void launch_preempt_reprieve_paged(const PreemptPage* pages, int n_pages, const PreemptPage* pages_dev, int64_t n, int64_t m, const int64_t* rows_dev,
+                                   int T, bool on_equal, const uint8_t* status, const int64_t* prefix, uint8_t* victims, void* ws,
+                                   uint32_t lds_cap_limit, hipStream_t s);
 // the first instant at which a pod passes (kt_kernels_forecast.hip): one wave per pod, lane = instant position.  rows_dev [n];
 // inst_s / inst_ns [m] in device memory, strictly ascending; status / summary: ONE check over those rows; partial: aggregate rows
 // with exact per-name contributor counts; error: the error bytes of a dry finalize; first [n] and verdicts [n][m] out

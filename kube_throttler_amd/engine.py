@@ -43,9 +43,11 @@ EXPORTS = [
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
+    "kt_paged_preempt",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
+PREEMPT_REPRIEVE = 0x1
 FORECAST_NONE = -1
 COUNTER_FEW_CHECKS, COUNTER_COMPILES, COUNTER_INDEX_CHUNKS, COUNTER_INDEX_WORDS, COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = range(6)
 COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUNTER_PACKED_WORDS = 6, 7, 8, 9
@@ -140,6 +142,27 @@ def paged_headroom(engines, rows, cap, on_equal=False):
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_headroom: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return copies[:n], limiting[:n]
+
+
+def paged_preempt(engines, pod_rows, cand_rows, now, on_equal=False, reprieve=False, want_victims=True):
+    """kt_paged_preempt: kt_preempt_launch (``reprieve``: kt_preempt_reprieve_launch) over the page engines, on the cluster of all
+    resource names -> (prefix int64 [n], victims uint8 [n][n_cand] or None).  prefix: the smallest k for which the pod passes
+    PreFilter once the candidates ``cand_rows[:k]`` are gone and every responsible throttle has been reconciled at ``now`` on
+    every page; 0: it already passes; PREEMPT_NONE: no prefix helps.  A throttle reads its calculated threshold on every page
+    when any page's reconcile replaces it (or any page has it stored), and keeps its stored status on every page when its
+    reconcile is an error on any page."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    a = np.ascontiguousarray(pod_rows, dtype=np.int64)
+    c = np.ascontiguousarray(cand_rows, dtype=np.int64)
+    n, m = len(a), len(c)
+    prefix = np.zeros(max(n, 1), np.int64)
+    flat = np.zeros(max(n * m, 1), np.uint8) if want_victims else None
+    rc = lib().kt_paged_preempt(hs, len(engines), n, a.ctypes.data if n else None, m, c.ctypes.data if m else None, int(now[0]), int(now[1]),
+                                int(on_equal), PREEMPT_REPRIEVE if reprieve else 0, prefix.ctypes.data,
+                                None if flat is None else flat.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_preempt: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return prefix[:n], (None if flat is None else flat[:n * m].reshape(n, m))
 
 
 def paged_reconcile(engines, now, apply=True):
@@ -253,6 +276,8 @@ def lib():
         L.kt_headroom_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.kt_paged_headroom.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                         C.c_void_p]
+        L.kt_paged_preempt.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                       C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.kt_preempt_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_void_p]
         L.kt_preempt_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -469,6 +469,149 @@ def _reprieve(snap, ctx, affected, contributes, creq, req, eq, prefix, victims):
 
 
 # ---- preempt, for gangs: the shortest victim prefix that lets a whole gang in (kt_preempt_gangs_launch), in closed form ----
+# ---- preempt over pages (kt_paged_preempt): the closed form over a list of page snapshots ----
+def paged_preempt_context(snaps, now):
+    """``preempt_context`` of every page, and per throttle row the two facts that hold for the throttle AS A WHOLE:
+    ``error`` — its reconcile is an error on some page: it keeps its stored status on every page — and ``use_calc`` —
+    status.calculatedThreshold is compared and replaced as a whole (throttle_controller.go:116-133), so the check reads the
+    calculated threshold on EVERY page iff on SOME page calculatedAt is set or the reconcile at ``now`` replaces it, and
+    spec.threshold on every page otherwise.  ``th`` / ``calc`` are keyed by (page, dim); the pod-count parts are page 0's."""
+    ctxs = [preempt_context(s, now) for s in snaps]
+    thr = []
+    for t in range(snaps[0].n_thr):
+        error = any(c["thr"][t]["error"] for c in ctxs)
+        use_calc, calcs = False, []
+        for s, c in zip(snaps, ctxs):
+            calc, calc_count, any_err = _calculated_threshold(s, t, now)
+            stored, stored_count = _amount_dict(s.thr_calc, t, s.D)
+            fp = int(s.thr_spec_msgs_fp[t]) if any_err else 0
+            replace = not c["thr"][t]["error"] and ((calc, calc_count) != (stored, stored_count) or int(s.thr_status_msgs_fp[t]) != fp)
+            use_calc = use_calc or bool(int(s.thr_flags[t]) & S.THR_CALC_AT_NONZERO) or replace
+            calcs.append((calc, calc_count))
+        th, cv, val, cnt = {}, {}, {}, {}
+        for k, (s, c) in enumerate(zip(snaps, ctxs)):
+            names = calcs[k][0] if use_calc else _amount_dict(s.thr_spec, t, s.D)[0]
+            th.update({(k, d): v for d, v in names.items()})
+            cv.update({(k, d): v for d, v in calcs[k][0].items()})
+            val.update({(k, d): v for d, v in c["thr"][t]["val"].items()})
+            cnt.update({(k, d): v for d, v in c["thr"][t]["cnt"].items()})
+        th_count = calcs[0][1] if use_calc else _amount_dict(snaps[0].thr_spec, t, snaps[0].D)[1]
+        thr.append(dict(error=error, use_calc=use_calc, th=th, th_count=th_count, calc=cv, calc_count=calcs[0][1], val=val, cnt=cnt,
+                        pods=ctxs[0]["thr"][t]["pods"]))
+    return dict(match=ctxs[0]["match"], thr=thr)
+
+
+def _paged_amounts(snaps, tab_name, t):
+    """A stored amount table's row ``t`` over the pages -> ({(page, dim): value}, page 0's count or None)."""
+    names = {}
+    for k, s in enumerate(snaps):
+        names.update({(k, d): v for d, v in _amount_dict(getattr(s, tab_name), t, s.D)[0].items()})
+    return names, _amount_dict(getattr(snaps[0], tab_name), t, snaps[0].D)[1]
+
+
+def paged_preempt_of(snaps, pod_row, cand_rows, now, on_equal=False, reprieve=False, ctx=None):
+    """kt_paged_preempt for one preemptor, in closed form over the page snapshots (no GPU) -> (prefix, victims [len(cand_rows)]):
+    ``preempt_of`` on the cluster of all names.  Which pods are counted, which throttles match which pod, the error rows and the
+    list cut are page 0's (the selector side is the same in every page); the pod count is judged once; a (throttle, k) pair
+    fails iff the count part or some page's name part fails.  The whole-threshold rule: a throttle reads the calculated
+    threshold on every page iff some page has calculatedAt set or replaces it at ``now``.  The whole-error rule: a throttle whose
+    reconcile is an error on some page keeps its stored status on every page.  With one page this is ``preempt_of``.
+    ``reprieve``: the walk of kt_preempt_reprieve_launch with the same joint judge — a victim is put back only if the pod still
+    passes every page with it back."""
+    snap0 = snaps[0]
+    ctx = paged_preempt_context(snaps, now) if ctx is None else ctx
+    p, cands, eq = int(pod_row), [int(c) for c in cand_rows], bool(on_equal)
+    m = len(cands)
+    none = (-1, [0] * m)
+    if not (0 <= p < snap0.n_pods) or not int(snap0.pod_flags[p]) & S.POD_VALID:
+        return none
+    err, affected = affected_throttles(snap0, p)
+    if err:
+        return none
+    m_eff = m
+    for j, c in enumerate(cands):
+        if not (0 <= c < snap0.n_pods) or not int(snap0.pod_flags[c]) & S.POD_VALID or affected_throttles(snap0, c)[0]:
+            m_eff = j
+            break
+    counted = lambda c: (int(snap0.pod_flags[c]) & (_COUNTABLE | S.POD_FINISHED)) == _COUNTABLE
+
+    def requests(c):
+        return {(k, d): v for k, s in enumerate(snaps) for d, v in pod_requests(s, c).items()}
+
+    req = {kd: v for kd, v in requests(p).items() if v != 0}
+    creq = [requests(c) if counted(c) else {} for c in cands[:m_eff]]
+    contributes = [[counted(c) and t in ctx["match"].get(c, ()) for c in cands[:m_eff]] for t in affected]
+
+    def judge(t, val, cnt, pods):
+        th = ctx["thr"][t]
+        eq3 = eq if int(snap0.thr_flags[t]) & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _paged_amounts(snaps, "thr_reserved", t)
+        u_hc, cc = pods > 0, th["calc_count"]
+        bad = _amount_fails(1, th["th_count"], cc is not None and u_hc and pods >= cc, u_hc, pods, res_count is not None, res_count or 0, eq3, eq)
+        for kd, v in req.items():
+            u_pr = cnt.get(kd, 0) > 0
+            cv = th["calc"].get(kd)
+            bad = bad or _amount_fails(v, th["th"].get(kd), cv is not None and u_pr and val.get(kd, 0) >= cv, u_pr, val.get(kd, 0), kd in res,
+                                       res.get(kd, 0), eq3, eq)
+        return bad
+
+    def moved(state, j, sign):
+        val, cnt, pods = dict(state[0]), dict(state[1]), state[2] + sign
+        for kd, v in creq[j].items():
+            val[kd] = val.get(kd, 0) + sign * v
+            cnt[kd] = cnt.get(kd, 0) + sign
+        return [val, cnt, pods]
+
+    fails = [False] * (m_eff + 1)  # fails[k]: some (throttle, amount) of some page stops the pod in S_k
+    for ti, t in enumerate(affected):
+        th = ctx["thr"][t]
+        if th["error"]:  # the stored status stays on every page, in every S_k
+            f = int(snap0.thr_flags[t])
+            eq3 = eq if f & S.THR_CLUSTER else True
+            res, res_count = _paged_amounts(snaps, "thr_reserved", t)
+            used, used_count = _paged_amounts(snaps, "thr_used", t)
+            sth, sth_count = _paged_amounts(snaps, "thr_calc" if th["use_calc"] else "thr_spec", t)
+            bad = _amount_fails(1, sth_count, bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0,
+                                res_count is not None, res_count or 0, eq3, eq)
+            for (k, d), v in req.items():
+                flg = int(snaps[k].thr_thrl_flag[t]) & int(snaps[k].thr_thrl_has[t])
+                bad = bad or _amount_fails(v, sth.get((k, d)), bool(flg >> d & 1), (k, d) in used, used.get((k, d), 0), (k, d) in res,
+                                           res.get((k, d), 0), eq3, eq)
+            if bad:
+                return none
+            continue
+        state = [th["val"], th["cnt"], th["pods"]]
+        for k in range(m_eff + 1):
+            if k > 0 and contributes[ti][k - 1]:
+                state = moved(state, k - 1, -1)
+            fails[k] = fails[k] or judge(t, *state)
+    prefix = next((k for k in range(m_eff + 1) if not fails[k]), -1)
+    victims = [0] * m
+    for j in range(max(prefix, 0)):
+        victims[j] = int(any(contributes[ti][j] for ti in range(len(affected))))
+    if reprieve and prefix > 0:
+        live = []  # [index in `contributes`, throttle row, state] of the reconciled affecting throttles, in S(the masked victims)
+        for ti, t in enumerate(affected):
+            th = ctx["thr"][t]
+            if th["error"]:
+                continue
+            state = [th["val"], th["cnt"], th["pods"]]
+            for j in range(prefix):
+                if victims[j] and contributes[ti][j]:
+                    state = moved(state, j, -1)
+            live.append([ti, t, state])
+        for j in range(prefix - 1, -1, -1):
+            if not victims[j]:
+                continue
+            back = [(entry, moved(entry[2], j, 1)) for entry in live if contributes[entry[0]][j]]
+            if any(judge(entry[1], *state) for entry, state in back):
+                continue  # some page of some throttle stops the pod with c_j back: it stays a victim
+            victims[j] = 0
+            for entry, state in back:
+                entry[2] = state
+    return prefix, victims
+
+
 def _gang_first_stopped(members, hit, reqs, thr_amounts, used, res, res_count, eq3, eq):
     """One throttle against one state of its `used`: the position of the first member it affects (``hit``) and stops, every
     earlier member it affects having reserved (None: it stops nobody).  ``thr_amounts``: (threshold names, threshold count);
@@ -761,6 +904,12 @@ class PagedEngine:
         verdicts of a dry-run admission of ``[pod] * cap`` with every page's names -> (copies [n], limiting throttle row [n],
         -1 when all ``cap`` are admitted).  Nothing is reserved."""
         return E.paged_headroom(self.engines, rows, cap, on_equal=on_equal)
+
+    def preempt(self, pod_rows, cand_rows, now, on_equal=False, reprieve=False, want_victims=True):
+        """The shortest victim prefix of the caller-ordered ``cand_rows`` that lets each pod of ``pod_rows`` through, over every
+        page's names, through kt_paged_preempt (``reprieve``: the victim mask shrunk to a minimal set by the reprieve walk) ->
+        (prefix [n], victims [n][n_cand] or None).  A dry run: nothing stored changes on any page."""
+        return E.paged_preempt(self.engines, pod_rows, cand_rows, now, on_equal=on_equal, reprieve=reprieve, want_victims=want_victims)
 
     def forecast(self, pod_rows, instants, on_equal=False, want_verdicts=True):
         """kt_forecast_launch through the one engine of a cluster that fits a page; the forecast has no paged form (more than
