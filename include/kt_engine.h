@@ -597,10 +597,13 @@ const char* kt_kernel_name(kt_engine* e, int32_t kernel);
 #define KT_COUNTER_MATCH_CACHE_BUILDS 12 /* full builds of the match cache so far: the per-pod matched-term words single-chunk programs
                                             keep between PreFilter sweeps.  One after every compile and after a table clear; pod events refresh
                                             their rows only and do not count (KT_NO_MATCH_CACHE=1: no table, the scans as before) */
-#define KT_COUNTER_MATCH_CACHE_SCANS 13  /* scans served from the match cache so far (the lean PreFilter sweep of every row; the aggregate
-                                            scan keeps its selector scan) */
+#define KT_COUNTER_MATCH_CACHE_SCANS 13  /* PreFilter sweeps served from the match cache so far (the lean sweep of every row; the aggregate
+                                            scans count in KT_COUNTER_MATCH_CACHE_AGG_SCANS) */
 #define KT_COUNTER_MATCH_CACHE_PLANES 14 /* the longest namespace word list of the compiled single-chunk program, as the last sweep of every
                                             row counted it (0: not counted yet, or several chunks): more than 4 = not cached */
+#define KT_COUNTER_MATCH_CACHE_AGG_SCANS 15 /* full aggregate scans that replayed the match cache so far: the two-per-CU form over the scan
+                                               view's planes (KT_NO_MATCH_CACHE_AGG=1 keeps the aggregate's selector scan while the sweep
+                                               still replays) */
 int64_t kt_counter(kt_engine* e, int32_t which);
 /* ---- More resource names than one engine has dimensions (KT_MAX_DIMS): PAGES.  The reference sums and compares any resource
  *      name (pkg/resourcelist/resourcelist.go:27-54, resource_amount.go:127-159).  The host builds the same cluster once per

@@ -536,6 +536,7 @@ int64_t kt_counter(kt_engine* e, int32_t which) {
     case KT_COUNTER_MATCH_CACHE_BUILDS: return e->ctr_mc_builds.load(std::memory_order_relaxed);
     case KT_COUNTER_MATCH_CACHE_SCANS: return e->ctr_mc_scans.load(std::memory_order_relaxed);
     case KT_COUNTER_MATCH_CACHE_PLANES: return e->ctr_mc_planes.load(std::memory_order_relaxed);
+    case KT_COUNTER_MATCH_CACHE_AGG_SCANS: return e->ctr_mc_agg_scans.load(std::memory_order_relaxed);
     default: return -1;
   }
 }

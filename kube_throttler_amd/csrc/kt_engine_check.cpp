@@ -28,7 +28,14 @@ static int32_t ensure_check_recs(kt_engine* e, int32_t on_equal, int DT, hipStre
 
 // The match cache (kt_engine_impl.h), made current for a scan that will be enqueued on s right behind this call: built by one
 // launch over every row when the program was compiled or the tables cleared since, else the rows pod events upserted since are
-// refreshed by one launch of the list form.  mc.mw stays nullptr where there is no table: the switch, a program the cache does
+// refreshed by one launch of the list form.  Either launch writes through to the planes of the countable scan view where those
+// are valid (ScanView::mx_valid) — also the full build: a table that went void under a valid view (more than kPatchBatchMax
+// pending rows) comes back with the view's planes current, no second gather.
+// Stream order of the write-through: the row -> record table and the appended records are written by kt_patch_scan_views on the
+// FEED's stream, this launch runs on the SCAN's.  The pair is ordered as the atom rows this launch reads always were — they are
+// written by the same feed launches: every launch-side call settles the feed on the host first (LaunchLock: settle_ingest) and
+// order_behind_ingest puts s behind the feed kernel's event on the device while that kernel may not have retired; the other way
+// round, the caller leaves s in last_stream and a feed call synchronises a last_stream that is not its own before it writes.  mc.mw stays nullptr where there is no table: the switch, a program the cache does
 // not take (several chunks, slow shapes, overflow pods, more than 8 dimensions, a namespace word list longer than kMatchReplay, a
 // check footprint that does not fit one CU twice), nothing fed yet.
 int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc) {
@@ -47,13 +54,22 @@ int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc
   // (the dispatch's own predicate: a table the sweep would not replay is neither built nor refreshed)
   if (!kt::check_replays_match_cache(e->pods, e->sp, e->dindex, planes, e->n_overflow != 0, e->sw[kSw_CHECK_ONE_PER_CU])) return KT_OK;
   const uint64_t stride = (uint64_t)e->cfg.pod_capacity;
+  ScanView& cv = e->views.countable;
+  kt::MatchViewPlanes vp;
+  if (cv.valid && cv.mx_valid && cv.mx.p && cv.pos.p && cv.mx_planes == planes && e->mc_gen == e->program_gen)
+    vp.mx = cv.mx.p, vp.pos = cv.pos.p, vp.stride = (uint64_t)cv.cap + 1u;
+  else
+    cv.mx_valid = false;  // (this call may write words the view's planes do not get: gathered again before they are replayed)
   if (!e->mc_valid || e->mc_gen != e->program_gen) {
     if (e->d_mc.cap < (size_t)planes * stride) {
       if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // an earlier scan may still read the old table
       KT_HIP(e, e->d_mc.reserve((size_t)planes * stride));
     }
     order_behind_ingest(e, s);
-    if (!kt::launch_build_match_cache(e->pods, e->pod_rows_hi, nullptr, e->dindex, e->d_mc.p, stride, planes, s)) return KT_OK;
+    if (!kt::launch_build_match_cache(e->pods, e->pod_rows_hi, nullptr, e->dindex, e->d_mc.p, stride, planes, s, &vp)) {
+      cv.mx_valid = false;
+      return KT_OK;
+    }
     KT_HIP(e, hipGetLastError());
     e->mc_valid = true, e->mc_gen = e->program_gen;
     e->mc_pending.clear();
@@ -72,8 +88,8 @@ int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc
     }
     memcpy(e->h_mc_rows, e->mc_pending.data(), n * 8);
     order_behind_ingest(e, s);
-    if (!kt::launch_build_match_cache(e->pods, (int64_t)n, e->h_mc_rows, e->dindex, e->d_mc.p, stride, planes, s)) {
-      e->mc_valid = false;
+    if (!kt::launch_build_match_cache(e->pods, (int64_t)n, e->h_mc_rows, e->dindex, e->d_mc.p, stride, planes, s, &vp)) {
+      e->mc_valid = false, cv.mx_valid = false;
       e->mc_pending.clear();
       return KT_OK;
     }

@@ -138,13 +138,19 @@ struct ScanView {
   DevBuf<uint64_t> pk;             //   packed request words
   kt::PackPlan pack;               // packed fold of the view (nw == 0: plain fold)
   DevBuf<int32_t> pos;             // pod row -> its record (-1: not listed)
+  // The countable view's planes of the match cache, plane-major: mx[k][j] = word k of record j = d_mc[k][rows[j]], stride cap + 1
+  // (kt::MatchViewPlanes).  Allocated when the cached aggregate will run; gathered behind a view build, kept current by the
+  // builder's write-through; mx_valid: they are the table's words for every record (void with every view build).
+  DevBuf<uint64_t> mx;
+  uint32_t mx_planes = 0;
+  bool mx_valid = false;
   DevBuf<uint32_t> range;          // record ranges of the scan's workgroups, ends at namespace boundaries (plan_wg_ranges) ...
   int range_G = 0;                 // ... and the grid they were planned for (0: none)
   int64_t cap = 0;                 // records the copies hold
   int64_t extra = 0;               // upper bound of the records appended since: a scan covers n + extra (zero = not countable)
   bool by_ns = false;              // ordered by namespace (multi-chunk index) / ascending rows
   bool valid = false;              // describes the current pod table
-  void release() { rows.release(); d_n.release(); meta.release(); latom.release(); req.release(); pk.release(); pos.release(); range.release(); }
+  void release() { rows.release(); d_n.release(); meta.release(); latom.release(); req.release(); pk.release(); pos.release(); range.release(); mx.release(); mx_valid = false; }
 };
 // what differs between the builds of the two views
 struct ViewSpec {
@@ -208,8 +214,8 @@ extern thread_local std::string g_create_error;  // text of the last kt_engine_c
 // path is tuned to a few microseconds).  Read at the same two moments, with a VALUE instead of a flag and therefore not in the
 // table: KT_REPRIEVE_LDS_CAP (kt_engine::reprieve_lds_cap_limit, a test hook of kt_preempt_reprieve_launch and
 // kt_preempt_gangs_reprieve_launch).
-enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSwCount };
-static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE"};
+enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSw_NO_MATCH_CACHE_AGG, kSwCount };
+static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE", "KT_NO_MATCH_CACHE_AGG"};
 struct kt_engine {
   bool sw[kSwCount] = {};  // EnvSwitch values (load_env_switches)
   uint32_t reprieve_lds_cap_limit = 0;  // KT_REPRIEVE_LDS_CAP (test hook, read with the switches): at most so many list entries of
@@ -246,13 +252,14 @@ struct kt_engine {
   ScanViews views;                               // what the full scans read (kt_engine_views.cpp)
   bool cut_plain = false;                        // a scan needed the plain fold: the index chunks stay cut for plain records
   void* cur_launch_lock = nullptr;               // the LaunchLock of the launch-side call in progress (set and cleared under op_mu)
-  std::atomic<int64_t> ctr_index_chunks{0}, ctr_index_words{0}, ctr_index_image_words{0}, ctr_ns_rows{0}, ctr_ns_word_visits{0}, ctr_ns_chunk_visits{0}, ctr_slow_throttles{0}, ctr_packed_words{0}, ctr_agg_workgroups{0}, ctr_view_builds{0}, ctr_mc_builds{0}, ctr_mc_scans{0}, ctr_mc_planes{0};
+  std::atomic<int64_t> ctr_index_chunks{0}, ctr_index_words{0}, ctr_index_image_words{0}, ctr_ns_rows{0}, ctr_ns_word_visits{0}, ctr_ns_chunk_visits{0}, ctr_slow_throttles{0}, ctr_packed_words{0}, ctr_agg_workgroups{0}, ctr_view_builds{0}, ctr_mc_builds{0}, ctr_mc_scans{0}, ctr_mc_planes{0}, ctr_mc_agg_scans{0};
   DevBuf<uint16_t> d_latom;                      // pods.latom: rewritten per selector program (kt_translate_pods)
   // The match cache (kt_index.h: MatchCacheArgs; kt_engine_check.cpp: match_cache_for_scan): per pod row, the matched terms of every
   // word of its namespace's list.  Derived from the atom rows and the compiled index and from nothing else, so it is written
   // where they are: void after every compile (mc_gen) and after a table clear (mc_valid), and the rows of every pod upsert wait
-  // in mc_pending for the next cached sweep, which refreshes them first (on its own stream).  Deletes need nothing: a replay is
-  // gated by the pod's valid bit, as the scan is.  Allocated by the first cached sweep of an eligible program.
+  // in mc_pending for the next cached scan — the aggregate of a reconcile or the sweep, whichever comes first — which refreshes
+  // them first (on its own stream).  Deletes need nothing: a replay is gated by the pod's state bits, as the scan is.  Allocated by
+  // the first cached scan of an eligible program.
   DevBuf<uint64_t> d_mc;                         // [mc.planes][pod_capacity]
   int64_t* h_mc_rows = nullptr;                  // pinned: the pending rows as the refresh launch reads them (kPatchBatchMax entries)
   hipEvent_t mc_rows_ev = nullptr;               // behind the last refresh launch: the list buffer is free again
@@ -637,7 +644,8 @@ KT_INTERNAL void amount_to_table(const HostAmount& h, const kt_amounts& a, size_
 KT_INTERNAL kt::ReqBound req_bound(const kt_engine* e);
 KT_INTERNAL bool amount_in_bound(const HostAmount& a, int D);
 KT_INTERNAL void reqs_from_pool(const kt_reqs& pool, uint32_t b, uint32_t e_, std::vector<Req>& out);
-// (kt_engine_check.cpp) the program's match cache, current for a scan enqueued on s behind this call — mc.mw == nullptr: none
+// (kt_engine_check.cpp) the program's match cache, current for a scan enqueued on s behind this call — mc.mw == nullptr: none;
+// the countable view's planes (ScanView::mx), where they are valid, are written through by the same launch
 KT_INTERNAL int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc);
 // a pod event batch no larger than this is applied to the scan views / queued for the match cache in place
 constexpr int64_t kPatchBatchMax = 65536;

@@ -239,6 +239,15 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
   const kt::AggTwoLaunch two_launch{!e->sw[kSw_AGG_ONE_PER_CU], e->sw[kSw_AGG_SMALL_WINDOW], e->n_overflow != 0, e->pods.LA};
   if (cv.valid && cv.pack.headroom >= (uint32_t)kt::kPackHeadroomBitsTwo && !(two_view && kt::aggregate_two_per_cu_fits(e->dindex, cv.pack, two_launch)))
     cv.valid = false;
+  // The match cache, made current BEFORE the view is rebuilt or used (one build or refresh launch per event batch: in a step the
+  // reconcile comes first, so the launch stands in front of the aggregate and the sweep behind it finds nothing pending).  Asked
+  // only where the two-per-CU form may run over the view — the form that replays — and under match_cache_for_scan's own
+  // conditions, the sweep's: the aggregate builds no table where the sweep would build none.
+  kt::MatchCacheArgs mc;
+  if (two_view && two_launch.enabled && !two_launch.small_window && !two_launch.overflow_pods && e->pods.LA <= 8 && !e->sw[kSw_NO_MATCH_CACHE_AGG] &&
+      !e->sw[kSw_CHECK_ONE_PER_CU]) {
+    if ((rc = match_cache_for_scan(e, s, mc)) != KT_OK) return rc;
+  }
   if (e->cfg.kernel_variant != 1 && (!cv.valid || cv.by_ns != by_ns)) {  // pods changed since the last scan: which rows does a reconcile look at
     if (e->last_stream && e->last_stream != s) KT_HIP(e, hipStreamSynchronize(e->last_stream));
     const ViewSpec spec{/*countable_only=*/true, by_ns, kt::aggregate_blocks, e->cfg.pod_capacity, /*requests=*/true};
@@ -279,6 +288,22 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
     if (!e->sw[kSw_NO_SCAN_VIEW] && (rc = copy_view_records(e, cv, spec, headroom, s)) != KT_OK) return rc;
     cv.valid = true;
   }
+  // Will this scan replay?  The view was planned for the two-per-CU form and the launch will take it (the one list of that form's
+  // conditions), the table is current and its planes fit the registers of the form.  The view's planes are then gathered from the
+  // table where they are not its words already: behind a view build, or when a table appeared under a valid view.
+  const bool replay = mc.mw != nullptr && mc.planes <= (uint32_t)kt::kMatchReplay && two_view && cv.valid && cv.pack.nw && cv.pk.p &&
+                      cv.pack.headroom >= (uint32_t)kt::kPackHeadroomBitsTwo && kt::aggregate_two_per_cu_fits(e->dindex, cv.pack, two_launch);
+  if (replay && !(cv.mx_valid && cv.mx_planes == mc.planes)) {
+    const size_t need = (size_t)mc.planes * ((size_t)cv.cap + 1);
+    if (cv.mx.cap < need) {
+      if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // an earlier scan may still read the old planes
+      KT_HIP(e, cv.mx.reserve(need));
+    }
+    const int64_t listed = std::min<int64_t>((int64_t)cv.n + cv.extra, cv.cap);
+    kt::launch_gather_match_planes(mc.mw, mc.stride, mc.planes, cv.rows.p, listed, cv.mx.p, (uint64_t)cv.cap + 1u, s);
+    KT_HIP(e, hipGetLastError());
+    cv.mx_planes = mc.planes, cv.mx_valid = true;
+  }
   if (words && e->clean_partial != (const void*)e->partial()) KT_HIP(e, hipMemsetAsync(e->partial(), 0, words * 8, s));
   e->clean_partial = nullptr;
   {
@@ -317,8 +342,10 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
         if (sc.by_ns && cv.by_ns && cv.range_G) sc.wg_range = cv.range.p, sc.wg_range_G = cv.range_G;
         if ((rc = slab_tags(e, sc, s)) != KT_OK) return rc;
         sc.defer_reduce = defer && sc.pk != nullptr;
+        if (replay && sc.by_ns && sc.v_pk && limb == 0) sc.v_mx = cv.mx.p, sc.mx_stride = (uint64_t)cv.cap + 1u, sc.mx_planes = cv.mx_planes;
         const char* k = kt::launch_aggregate_indexed(e->pods, sc, e->sp, e->d_sp.p, e->dindex, target, e->d_slab.p, s,
                                                      pass == 0 ? std::function<void()>(after_scan) : std::function<void()>());
+        if (sc.replayed) e->ctr_mc_agg_scans.fetch_add(1, std::memory_order_relaxed);
         if (!k && sc.refused) return e->fail(KT_ERR_OUT_OF_RANGE, "aggregate launch refused: %s", sc.refused);
         if (!k) return e->fail(KT_ERR_UNSUPPORTED, "a chunk of the selector index exceeds the aggregate kernel's LDS budget (use kernel_variant 1)");
         e->last_kernel[KT_KERNEL_AGGREGATE] = k;

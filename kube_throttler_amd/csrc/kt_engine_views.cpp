@@ -47,6 +47,7 @@ int32_t copy_view_records(kt_engine* e, ScanView& v, const ViewSpec& spec, int64
   ScanViews& vs = e->views;
   v.cap = (int64_t)v.n + headroom;
   v.extra = 0;
+  v.mx_valid = false;  // (the aggregate gathers the planes of the new records where it will replay them: aggregate_locked)
   const size_t nc = (size_t)v.cap + 1, np = (size_t)spec.rows_cap + 1;
   KT_HIP(e, v.meta.reserve(nc));
   KT_HIP(e, v.latom.reserve(nc * (size_t)e->pods.LA));

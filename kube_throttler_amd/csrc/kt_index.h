@@ -334,8 +334,10 @@ uint32_t check_word_lds(int D);  // check: bytes per 64-bit word of term numbers
 // The match cache (kt_scan.h: replay_tile; kt_kernels_match.hip: the builder): per pod row, the matched terms of every entry of
 // its namespace's word list — mw[k][row], one plane per list position.  Programs of ONE chunk without slow shapes whose longest
 // list has at most kMatchPlanes entries; the engine owns the table and says when it is valid (kt_engine_check.cpp).  The lean
-// two-per-CU PreFilter sweep replays it; the aggregate scan does not (measured: profiles/match_cache.txt — through the view's
-// row list the planes are a second dependent trip per tile, and the cached form was no faster than its scan).
+// two-per-CU PreFilter sweep replays it by pod row.  The two-per-CU aggregate scan replays it too, from a copy of the planes in
+// the ORDER OF ITS SCAN VIEW (ScanView::mx, MatchViewPlanes below: mx[k][j] = mw[k][rows[j]]) — through the view's row list the
+// planes were a second dependent trip per tile and that form was no faster than its scan (profiles/match_cache.txt section 1);
+// in view order they are requested with the record (profiles/agg_match_cache.txt).
 constexpr int kMatchPlanes = 8;   // planes the table and its builder take
 constexpr int kMatchReplay = 4;   // planes the cached sweep holds in registers: programs with longer lists are not cached
 struct MatchCacheArgs {
@@ -343,6 +345,15 @@ struct MatchCacheArgs {
   uint64_t stride = 0;           // words per plane (the engine's pod capacity)
   uint32_t planes = 0;           // planes in use: the longest namespace word list of the program (<= kMatchPlanes)
   mutable bool used = false;     // out: the launch replayed the table
+};
+// The planes of the countable scan view's records, plane-major with the view's record capacity (+ 1) as the stride.  Written by
+// two launches and no third: launch_gather_match_planes behind a view build, and kt_build_match_cache, which stores every word
+// it writes for a row also at the row's record (pos[row] >= 0: ScanView::pos — -1 says "no record"; the -2 with which
+// kt_patch_scan_views claims a row while it appends its record is gone when that launch has ended, and the builder runs behind it).
+struct MatchViewPlanes {
+  uint64_t* mx = nullptr;        // nullptr: the view keeps no planes
+  const int32_t* pos = nullptr;  // pod row -> record
+  uint64_t stride = 0;           // words per plane
 };
 // which pods an aggregate scan covers and how they enter the target buffer
 struct AggScan {
@@ -368,6 +379,10 @@ struct AggScan {
   bool small_window = false;     // test switch: fold through rank windows of 64 records whatever fits (kt_kernels_aggregate.hip)
   bool defer_reduce = false;     // packed scans: leave the slabs as they are — kt_reduce_finalize_packed takes them from there
   bool one_per_cu = false;       // keep the launch at one workgroup per CU whatever would fit twice (KT_AGG_ONE_PER_CU)
+  const uint64_t* v_mx = nullptr;  // the view's planes of the match cache (MatchViewPlanes), current for this launch — the two-per-CU
+  uint64_t mx_stride = 0;          //   form then replays them instead of scanning the selectors (nullptr: scan)
+  uint32_t mx_planes = 0;
+  mutable bool replayed = false;   // out: the launch replayed the planes
   mutable int launched_blocks = 0;  // out: workgroups (= slabs per chunk) of the scan launch
   mutable bool launched_packed = false;
   mutable const char* refused = nullptr;  // out: why launch_aggregate_indexed returned nullptr, where it is not the LDS budget
@@ -443,8 +458,12 @@ bool match_cache_fits(const IndexDev& ix);
 // BEFORE it builds or refreshes one: the lean two-per-CU form, 8 dimensions at most, lists of at most kMatchReplay words)?
 bool check_replays_match_cache(const PodTable& pods, const SelProgram& sp, const IndexDev& ix, uint32_t planes, bool overflow_pods, bool one_per_cu);
 // (re)writes the planes of pod rows [0, n) (rows_dev == nullptr) or of the n listed rows; false: not dispatchable
+// view (nullable): the planes of the countable scan view, written through for every row that has a record
 bool launch_build_match_cache(const PodTable& pods, int64_t n, const int64_t* rows_dev, const IndexDev& ix, uint64_t* mw, uint64_t stride,
-                              uint32_t planes, hipStream_t s);
+                              uint32_t planes, hipStream_t s, const MatchViewPlanes* view = nullptr);
+// mx[k][j] = mw[k][rows[j]] for the n listed records of a freshly built view (the table must be current on s)
+void launch_gather_match_planes(const uint64_t* mw, uint64_t stride, uint32_t planes, const int64_t* rows, int64_t n, uint64_t* mx,
+                                uint64_t mx_stride, hipStream_t s);
 int check_sweep_blocks(int64_t n);  // workgroups of a namespace-ordered lean sweep over n pod rows (one per CU)
 // the per-word check tables of the whole index in global memory: TermInfo [total_words][64], then WordVerdict [total_words]
 // (total_words = HostIndex::bm_words) — built once per generation of CheckRecs instead of once per (workgroup, chunk)

@@ -490,10 +490,21 @@ __global__ __launch_bounds__(kBlockIx) void kt_aggregate_bitmap(const BmAggArgs 
 // 32-byte records put word 0 of eight consecutive records on eight bank pairs and nothing in between, so the table is SKEWED:
 // 8 bytes of padding after every eight records (a.skew) — word 0 of 64 consecutive records then covers all 32 bank pairs, as the
 // 40-byte records of the one-per-CU form do.  The spill takes the skew out again: the slab is the plain array of records.
+// CACHED: the form REPLAYS the match cache (kt_scan.h: replay_tile) from the view's planes — a.v_mx[k][j], the matched terms of
+//         entry k of the namespace list of record j's pod, plane-major in VIEW order (ScanView::mx): a wave reads 512 contiguous
+//         bytes per plane, requested with the record's meta and request words and not behind them.  No atom row is loaded, of the
+//         image only the namespace lists are staged; run masks, word queue, fold and spill are those of the scan, which they meet
+//         through the same post hook.  The planes are final whatever the program's form: ONE instantiation serves simple and rich
+//         programs.  (The first tile of a wave stays BEHIND the prologue's barrier: requested ahead of it, the step was measured
+//         1.2 us slower at 1M pods, profiles/agg_match_cache.txt section 2 — as reasoned there, the tile's loads then stand in
+//         front of the staging loads in the wave's in-order load counter and the prologue waits for HBM instead of L2.)
 struct BmAggOneArgs {
   const uint64_t* v_meta;  // the scan view: record j = meta word, atom row, packed request words
   const uint16_t* v_latom;
   const uint64_t* v_pk;
+  const uint64_t* v_mx;    // CACHED: the view's planes of the match cache, [mx_planes][mx_stride]
+  uint64_t mx_stride;
+  uint32_t mx_planes;
   unsigned char* slab;     // this chunk's slab area
   BmIndexArgs ix;
   BmChunk ch;              // the chunk's descriptor by value
@@ -504,8 +515,9 @@ struct BmAggOneArgs {
 };
 __device__ __forceinline__ uint32_t agg_one_rec_off(uint32_t r, uint32_t rec, uint32_t skew) { return __umul24(r, rec) + (skew ? (r >> 3) << 3 : 0u); }
 
-template <bool VETO, int NEED>
+template <bool VETO, int NEED, bool CACHED = false>
 __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmAggOneArgs a) {
+  static_assert(!CACHED || (!VETO && NEED == 2), "the cached form is one instantiation: nothing of the scan's form is left in it");
   // (the word queue: four words beside the simple scan, three beside the rich one — its veto plane and 2-bit counters take the
   //  registers of the fourth: 20 B of scratch with it)
   constexpr int LA = 8, NW = 3, kWq = VETO ? 3 : 4;
@@ -522,14 +534,22 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
   KT_LDS unsigned char* tab = lds + a.off_tab;
   struct Rec {
     uint64_t meta;
-    u32x4 raw;
+    u32x4 raw;                  // scan: the atom row
+    uint64_t mx[kMatchReplay];  // CACHED: the record's planes instead
     unsigned long long pw[NW];
   };
   auto fetch_tile = [&](uint32_t wt) {  // always from valid addresses: lanes past the end re-read the last record and are off
-    Rec r;
+    Rec r{};
     const uint32_t ic = min(wt * kWave + lane, n_rows - 1u);
     r.meta = a.v_meta[ic];
-    r.raw = *(const u32x4*)(a.v_latom + (uint64_t)ic * LA);
+    if constexpr (CACHED) {
+      const uint64_t* q = a.v_mx + ic;
+#pragma unroll
+      for (int j = 0; j < kMatchReplay; ++j)
+        if ((uint32_t)j < a.mx_planes) r.mx[j] = q[(uint64_t)j * a.mx_stride];  // (wave-uniform condition)
+    } else {
+      r.raw = *(const u32x4*)(a.v_latom + (uint64_t)ic * LA);
+    }
     const u64x2* q = (const u64x2*)(a.v_pk + (uint64_t)ic * a.pk_stride);
     const u64x2 q0 = q[0];
     r.pw[0] = q0.x, r.pw[1] = q0.y, r.pw[2] = 0ull;
@@ -537,10 +557,13 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
     return r;
   };
   // ---- prologue: the table zeroed, image + ranks in as one batch of loads, the run masks of the words
+  //      (CACHED: of the image only its tail, the namespace lists — nsl_rng and nsl — as the cached sweep stages it)
   for (uint32_t i = threadIdx.x; i < a.tab_bytes / 4; i += kBlockIx) ((lds_u32wp)tab)[i] = 0u;
   {
-    const StageSeg segs[2] = {chunk_image_segment(a.ix, ch),
-                              StageSeg{a.off_rank, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_term_rank), ch.n_words * 8u}};
+    const StageSeg img = CACHED ? StageSeg{a.ix.lds_img + ch.off_nsl_rng, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_nsl_rng),
+                                           (ch.lds_bytes - ch.off_nsl_rng) / 16u}
+                                : chunk_image_segment(a.ix, ch);
+    const StageSeg segs[2] = {img, StageSeg{a.off_rank, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_term_rank), ch.n_words * 8u}};
     lds_stage_segments<2, 4>(lds, segs);
   }
   if (ch.has_adj) {  // (see kt_aggregate_bitmap: lowest / highest number of every run of one group's terms)
@@ -572,9 +595,6 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
     unsigned long long pw[NW];
 #pragma unroll
     for (int k = 0; k < NW; ++k) pw[k] = cur.pw[k];
-    const u32x4 raw[1] = {cur.raw};
-    uint32_t ro[LA];
-    atom_row_offsets<LA>(raw, ro);
     // the word queue of kt_aggregate_bitmap's packed fold
     uint64_t qx[kWq];
     typedef typename std::conditional<(kWq > 3), uint64_t, uint32_t>::type qw_t;  // word numbers, 10 bits each, newest lowest
@@ -606,24 +626,30 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
         }
       }
     };
-    scan_tile<LA, VETO, NEED, false>(
-        bm, counted, ns, ro, [&](bool, uint32_t) {}, [&](uint32_t) { return true; },
-        [&](uint32_t w, uint64_t x, const u64x2& seg) -> uint64_t {
-          if (seg_on) {  // a throttle with several terms is counted once: the lowest match of every run
-            const uint64_t v = x | seg.y;
-            x = andn_64(x, v - seg.x);
-          }
-          if (__ballot(x != 0ull && qn >= (uint32_t)kWq) != 0ull) flush();
-          if (x != 0ull) {
+    auto push_word = [&](uint32_t w, uint64_t x, const u64x2& seg) -> uint64_t {
+      if (seg_on) {  // a throttle with several terms is counted once: the lowest match of every run
+        const uint64_t v = x | seg.y;
+        x = andn_64(x, v - seg.x);
+      }
+      if (__ballot(x != 0ull && qn >= (uint32_t)kWq) != 0ull) flush();
+      if (x != 0ull) {
 #pragma unroll
-            for (int k = kWq - 1; k > 0; --k) qx[k] = qx[k - 1];
-            qx[0] = x;
-            qw = (qw_t)(qw << 10) | (qw_t)w;
-            qn += 1u;
-          }
-          return 0ull;
-        },
-        [&](uint32_t w) -> u64x2 { return seg_on ? segp[w] : u64x2{0ull, 0ull}; });
+        for (int k = kWq - 1; k > 0; --k) qx[k] = qx[k - 1];
+        qx[0] = x;
+        qw = (qw_t)(qw << 10) | (qw_t)w;
+        qn += 1u;
+      }
+      return 0ull;
+    };
+    auto run_masks = [&](uint32_t w) -> u64x2 { return seg_on ? segp[w] : u64x2{0ull, 0ull}; };
+    if constexpr (CACHED) {
+      replay_tile(bm, counted, ns, cur.mx, a.mx_planes, [&](bool, uint32_t) {}, push_word, run_masks);
+    } else {
+      const u32x4 raw[1] = {cur.raw};
+      uint32_t ro[LA];
+      atom_row_offsets<LA>(raw, ro);
+      scan_tile<LA, VETO, NEED, false>(bm, counted, ns, ro, [&](bool, uint32_t) {}, [&](uint32_t) { return true; }, push_word, run_masks);
+    }
     flush();
   }
   __syncthreads();  // spill the table as this workgroup's slab: the plain array of records, coalesced 16-byte stores
@@ -866,24 +892,34 @@ const char* launch_aggregate_indexed(const PodTable& pods, const AggScan& sc, co
     BmAggOneArgs oa = make_bm_agg_one_args(ix, bm_args.pk, &one_total);
     const BmChunk& ch = ix.h_chunks[0];
     oa.v_meta = sc.v_meta, oa.v_latom = sc.v_latom, oa.v_pk = sc.v_pk, oa.ch = ch;
+    // the cached form: the engine handed over the view's planes, current for this launch (full scans only: limb 0, and a packed
+    // plan over the streamed view is what brought the launch here)
+    const bool cached = sc.v_mx != nullptr && sc.limb == 0 && sc.mx_planes >= 1u && sc.mx_planes <= (uint32_t)kMatchReplay &&
+                        (uint64_t)n_rows <= sc.mx_stride && match_cache_fits(ix);
+    if (cached) oa.v_mx = sc.v_mx, oa.mx_stride = sc.mx_stride, oa.mx_planes = sc.mx_planes;
     oa.slab = slab + (size_t)ch.slab_off * 16;
     oa.n_rows = (uint32_t)n_rows;
     oa.tpb = (uint32_t)((((n_rows + kWave - 1) / kWave) + nb - 1) / nb);
     static const bool dbg_one = getenv("KT_DEBUG_LDS") != nullptr;
     if (dbg_one)
-      fprintf(stderr, "kt_aggregate_bitmap_one: lds=%u (2 per CU) workgroups=%d tiles per workgroup=%u nw=%u rec=%u skew=%u\n", one_total, nb, oa.tpb,
-              oa.pk_nw, oa.pk_rec, oa.skew);
-#define KT_AGG_ONE_LAUNCH(VETO_, NEED_)                                                                          \
+      fprintf(stderr, "kt_aggregate_bitmap_one: lds=%u (2 per CU) workgroups=%d tiles per workgroup=%u nw=%u rec=%u skew=%u cached=%d\n", one_total, nb,
+              oa.tpb, oa.pk_nw, oa.pk_rec, oa.skew, cached ? 1 : 0);
+#define KT_AGG_ONE_LAUNCH(VETO_, NEED_, ...)                                                                     \
   {                                                                                                             \
-    auto kfn = kt_aggregate_bitmap_one<VETO_, NEED_>;                                                           \
+    auto kfn = kt_aggregate_bitmap_one<VETO_, NEED_, ##__VA_ARGS__>;                                            \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)one_total);    \
     hipLaunchKernelGGL(kfn, g_, b_, one_total, s, oa);                                                          \
   }
+    if (cached) {
+      KT_AGG_ONE_LAUNCH(false, 2, true)
+      sc.replayed = true;
+    } else {
 #ifdef KT_FAST_BUILD
-    KT_AGG_ONE_LAUNCH(false, 2)
+      KT_AGG_ONE_LAUNCH(false, 2)
 #else
-    if (!ix.rich) KT_AGG_ONE_LAUNCH(false, 2) else KT_AGG_ONE_LAUNCH(true, 3)
+      if (!ix.rich) KT_AGG_ONE_LAUNCH(false, 2) else KT_AGG_ONE_LAUNCH(true, 3)
 #endif
+    }
 #undef KT_AGG_ONE_LAUNCH
   } else {
   const bool windowed = bm_args.win_recs != 0u;

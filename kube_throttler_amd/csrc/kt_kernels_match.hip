@@ -13,6 +13,9 @@ namespace kt {
 //   rows != nullptr : the n listed rows    (pod events: the rows whose atom rows were rewritten; a row may be listed twice —
 //                                           both lanes store the same words)
 // Runs where the atom rows are written and nowhere else: nothing a reconcile or a check changes enters these words.
+// Write-through (a.vx != nullptr): the countable scan view keeps the planes of its records in scan order (MatchViewPlanes,
+// kt_index.h) and every word stored for a row goes to the row's record as well — the row -> record table is read once per lane,
+// beside the meta word.
 // ---------------------------------------------------------------------------------------------------
 struct MatchBuildArgs {
   const uint64_t* meta;
@@ -23,6 +26,9 @@ struct MatchBuildArgs {
   uint32_t planes;   // planes to write (<= kMatchPlanes)
   uint32_t n;        // rows [0, n) or list entries
   uint32_t cap;      // rows a plane holds: a listed row at or beyond it is skipped
+  uint64_t* vx;      // nullable: the view's planes ...
+  const int32_t* vpos;  // ... its row -> record table (-1: no record) ...
+  uint64_t vstride;  // ... and its words per plane: a record at or beyond it is skipped
   BmIndexArgs ix;
   BmChunk ch;
 };
@@ -51,6 +57,7 @@ __global__ __launch_bounds__(kBlockIx) void kt_build_match_cache(const MatchBuil
     const bool in = i < n && p < a.cap;
     const uint32_t pc = min(p, a.cap - 1u);
     const uint64_t meta = a.meta[pc];
+    const int32_t vj = a.vx ? a.vpos[pc] : -1;
     u32x4 raw[1];
     load_atoms<LA>(a.latom, (int64_t)pc, raw);
     const bool on = in && ((meta >> kMetaStateShift) & kPodValid) != 0;
@@ -58,17 +65,43 @@ __global__ __launch_bounds__(kBlockIx) void kt_build_match_cache(const MatchBuil
     uint32_t ro[LA];
     atom_row_offsets<LA>(raw, ro);
     uint64_t* q = a.mw + pc;
+    const bool thru = in && vj >= 0 && (uint64_t)vj < a.vstride;  // (false everywhere without a view: vj = -1)
+    uint64_t* qv = a.vx + (thru ? (uint32_t)vj : 0u);
     uint32_t round = 0u;  // wave-uniform
     scan_tile<LA, VETO, NEED, false>(
         bm, on, ns, ro, [&](bool, uint32_t) {}, [&](uint32_t) { return true; },
         [&](uint32_t, uint64_t xx, int) -> uint64_t {
           if (in && round < planes) q[(uint64_t)round * a.stride] = xx;
+          if (thru && round < planes) qv[(uint64_t)round * a.vstride] = xx;
           round += 1u;
           return 0ull;
         });
-    for (; round < planes; ++round)  // the planes past the longest list of the tile
+    for (; round < planes; ++round) {  // the planes past the longest list of the tile
       if (in) q[(uint64_t)round * a.stride] = 0ull;
+      if (thru) qv[(uint64_t)round * a.vstride] = 0ull;
+    }
   }
+}
+
+// kt_gather_match_planes — the planes of a freshly built countable view: mx[k][j] = mw[k][rows[j]], thread = record
+__global__ __launch_bounds__(256) void kt_gather_match_planes(const uint64_t* mw, uint64_t stride, uint32_t planes, const int64_t* rows, int64_t n,
+                                                             uint64_t* mx, uint64_t mx_stride) {
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+    const uint64_t p = (uint64_t)rows[j];
+    if (p >= stride) continue;  // (never: the list holds rows of the pod table)
+    uint64_t x[kMatchReplay];
+#pragma unroll
+    for (int k = 0; k < kMatchReplay; ++k) x[k] = (uint32_t)k < planes ? mw[(uint64_t)k * stride + p] : 0ull;
+#pragma unroll
+    for (int k = 0; k < kMatchReplay; ++k)
+      if ((uint32_t)k < planes) mx[(uint64_t)k * mx_stride + (uint64_t)j] = x[k];
+  }
+}
+void launch_gather_match_planes(const uint64_t* mw, uint64_t stride, uint32_t planes, const int64_t* rows, int64_t n, uint64_t* mx,
+                                uint64_t mx_stride, hipStream_t s) {
+  if (n <= 0 || !mw || !mx || planes == 0u || planes > (uint32_t)kMatchReplay || (uint64_t)n > mx_stride) return;
+  const int64_t nb = std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(kt_gather_match_planes, dim3((unsigned)nb), dim3(256), 0, s, mw, stride, planes, rows, n, mx, mx_stride);
 }
 
 bool match_cache_fits(const IndexDev& ix) {
@@ -78,13 +111,14 @@ bool match_cache_fits(const IndexDev& ix) {
 }
 
 bool launch_build_match_cache(const PodTable& pods, int64_t n, const int64_t* rows_dev, const IndexDev& ix, uint64_t* mw, uint64_t stride,
-                              uint32_t planes, hipStream_t s) {
+                              uint32_t planes, hipStream_t s, const MatchViewPlanes* view) {
   if (n <= 0) return true;
   if (!match_cache_fits(ix) || pods.LA > 8 || !mw || planes == 0u || planes > (uint32_t)kMatchPlanes || stride == 0u || n > (int64_t)stride)
     return false;
   MatchBuildArgs a{};
   a.meta = pods.meta, a.latom = pods.latom, a.rows = rows_dev, a.mw = mw, a.stride = stride, a.planes = planes;
   a.n = (uint32_t)n, a.cap = (uint32_t)std::min<uint64_t>(stride, 0x80000000ull);
+  if (view && view->mx && view->pos && view->stride) a.vx = view->mx, a.vpos = view->pos, a.vstride = view->stride;
   uint32_t o = 0;
   auto take = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
   plan_bitmap_index(ix, a.ix, take);

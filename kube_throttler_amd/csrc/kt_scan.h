@@ -443,8 +443,9 @@ __device__ __forceinline__ void scan_tile(const BmView& b, bool lane_on, uint32_
 // that is written where atom rows are written (kt_build_match_cache, kt_kernels_match.hip):
 //   mw[k][row] = the matched terms of entry rng.x + k of the namespace list of pod `row` (0 past the list's end, 0 for a row
 //                without a valid pod), k < kMatchPlanes: one plane per list position, a wave reads 512 contiguous bytes of it
-// and the ONE form of the PreFilter sweep replays it (replay_tile) instead of gathering the bitmap rows again.  (MatchCacheArgs,
-// kMatchPlanes: kt_index.h.)
+// and the ONE form of the PreFilter sweep replays it (replay_tile) instead of gathering the bitmap rows again; the two-per-CU
+// aggregate replays a copy of the planes kept in the order of its scan view (MatchViewPlanes).  (MatchCacheArgs, kMatchPlanes:
+// kt_index.h.)
 // ---------------------------------------------------------------------------------------------------
 
 // The planes of pod row p, one batch of loads from always-valid addresses; planes at or past `planes` are zero.  They hang off

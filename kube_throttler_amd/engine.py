@@ -54,6 +54,7 @@ COUNTER_NS_CHUNK_VISITS, COUNTER_INDEX_IMAGE_WORDS, COUNTER_SLOW_THROTTLES, COUN
 COUNTER_AGG_WORKGROUPS = 11
 COUNTER_VIEW_BUILDS = 10
 COUNTER_MATCH_CACHE_BUILDS, COUNTER_MATCH_CACHE_SCANS, COUNTER_MATCH_CACHE_PLANES = 12, 13, 14
+COUNTER_MATCH_CACHE_AGG_SCANS = 15
 
 
 def partial_layout(n_dims: int) -> dict:
@@ -511,6 +512,11 @@ class Engine:
         """PreFilter sweeps served from the match cache so far (0 under KT_NO_MATCH_CACHE=1 and for programs
         the cache does not take: several chunks, slow shapes, a namespace word list longer than four, more than 8 dimensions)."""
         return int(lib().kt_counter(self._h, COUNTER_MATCH_CACHE_SCANS))
+
+    def match_cache_agg_scans(self) -> int:
+        """Full aggregate scans that replayed the match cache so far (0 under KT_NO_MATCH_CACHE_AGG=1 or KT_NO_MATCH_CACHE=1 and
+        wherever the aggregate does not run its two-per-CU form over a program the cache takes)."""
+        return int(lib().kt_counter(self._h, COUNTER_MATCH_CACHE_AGG_SCANS))
 
     def partial_words(self) -> int:
         return self.throttle_rows() * partial_layout(self.D)["stride"]
