@@ -705,6 +705,16 @@ int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, co
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */
 int32_t kt_debug_reload_env(kt_engine* e);
 
+/* Development aid: a copy of the match cache as the last cached scan left it, for tests of what its two copies owe each other
+ * (the view's words of record j are the table's words of pod row out_rows[j], in every plane, zeroes past a list's end included).
+ *   which = 0: the table.               n = the pod rows ever fed; out[k * cap + r] = word k of pod row r.
+ *   which = 1: the countable scan view. n = its records (the appended ones included); out[k * cap + j] = word k of record j,
+ *                                       out_rows[j] (nullable) = the pod row of record j.
+ * *out_n and *out_planes are always set; with cap = 0 nothing else is written (the sizing call), otherwise cap >= n is required
+ * (KT_ERR_OUT_OF_RANGE).  KT_ERR_NOT_READY where there is nothing current to copy: no table built for this program, rows still
+ * waiting for their refresh, or (which = 1) a view whose planes were not gathered.  Waits for the engine's last launch. */
+int32_t kt_debug_match_planes(kt_engine* e, int32_t which, int64_t cap, uint64_t* out, int64_t* out_rows, int64_t* out_n, int32_t* out_planes);
+
 #ifdef __cplusplus
 }
 #endif

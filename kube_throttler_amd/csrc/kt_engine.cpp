@@ -517,6 +517,40 @@ int32_t kt_debug_reload_env(kt_engine* e) {
   return KT_OK;
 }
 
+int32_t kt_debug_match_planes(kt_engine* e, int32_t which, int64_t cap, uint64_t* out, int64_t* out_rows, int64_t* out_n, int32_t* out_planes) {
+  if (!e || which < 0 || which > 1 || cap < 0 || !out_n || !out_planes || (cap > 0 && !out)) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+  *out_n = 0, *out_planes = 0;
+  const uint32_t planes = e->mc_planes;
+  if (!e->mc_valid || e->program_dirty || e->mc_gen != e->program_gen || e->mc_planes_gen != e->program_gen || !e->mc_pending.empty() || !e->d_mc.p ||
+      planes == 0u || planes > (uint32_t)kt::kMatchPlanes || e->d_mc.cap < (size_t)planes * (size_t)e->cfg.pod_capacity)
+    return e->fail(KT_ERR_NOT_READY, "no current match cache: none built for this program, or rows wait for their refresh");
+  const ScanView& cv = e->views.countable;
+  hipStream_t s = e->own_stream;
+  int64_t n = e->pod_rows_hi;
+  uint64_t stride = (uint64_t)e->cfg.pod_capacity;
+  const uint64_t* src = e->d_mc.p;
+  if (which == 1) {
+    if (!cv.valid || !cv.mx_valid || !cv.mx.p || !cv.rows.p || !cv.d_n.p || cv.mx_planes != planes || cv.mx.cap < (size_t)planes * ((size_t)cv.cap + 1))
+      return e->fail(KT_ERR_NOT_READY, "the countable scan view holds no current planes");
+    unsigned long long dn = 0;
+    KT_HIP(e, hipMemcpyAsync(&dn, cv.d_n.p, 8, hipMemcpyDeviceToHost, s));
+    KT_HIP(e, hipStreamSynchronize(s));
+    n = (int64_t)std::min<unsigned long long>(std::min<unsigned long long>(dn, cv.n + (unsigned long long)cv.extra), (unsigned long long)cv.cap);
+    stride = (uint64_t)cv.cap + 1u, src = cv.mx.p;
+  }
+  *out_n = n, *out_planes = (int32_t)planes;
+  if (cap == 0 || n == 0) return KT_OK;
+  if (cap < n) return e->fail(KT_ERR_OUT_OF_RANGE, "cap=%lld < %lld", (long long)cap, (long long)n);
+  for (uint32_t k = 0; k < planes; ++k)
+    KT_HIP(e, hipMemcpyAsync(out + (size_t)k * (size_t)cap, src + (size_t)k * stride, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (which == 1 && out_rows) KT_HIP(e, hipMemcpyAsync(out_rows, cv.rows.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
 int64_t kt_counter(kt_engine* e, int32_t which) {
   if (!e) return -1;
   switch (which) {

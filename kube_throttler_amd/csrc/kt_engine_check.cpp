@@ -61,6 +61,9 @@ int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc
   else
     cv.mx_valid = false;  // (this call may write words the view's planes do not get: gathered again before they are replayed)
   if (!e->mc_valid || e->mc_gen != e->program_gen) {
+    // (with vp set — the write-through of a FULL build — only in views of more than 2^20 records: the table goes void under a
+    //  valid view when more than kPatchBatchMax rows are pending in batches that all fit the view's headroom, cv.extra grows at
+    //  least as fast as the pending list, and the headroom passes kPatchBatchMax only as n / 16.  A compile voids the view too.)
     if (e->d_mc.cap < (size_t)planes * stride) {
       if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // an earlier scan may still read the old table
       KT_HIP(e, e->d_mc.reserve((size_t)planes * stride));

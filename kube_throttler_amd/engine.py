@@ -43,7 +43,7 @@ EXPORTS = [
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
-    "kt_paged_preempt",
+    "kt_paged_preempt", "kt_debug_match_planes",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -250,6 +250,7 @@ def lib():
         L.kt_partial_words.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.kt_partial_layout.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 5
         L.kt_debug_reload_env.argtypes = [C.c_void_p]
+        L.kt_debug_match_planes.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.kt_affected_pods.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.kt_paged_check.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.kt_paged_reconcile.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_int32,
@@ -476,6 +477,18 @@ class Engine:
     def reload_env(self):
         """kt_debug_reload_env: re-read the A/B switches (KT_NO_* environment variables) — they are read once, at creation."""
         self._ck(lib().kt_debug_reload_env(self._h))
+
+    def match_planes(self, view=False):
+        """kt_debug_match_planes: (words[planes, n], rows) — the match cache's table (view=False: n pod rows, rows = None) or the
+        planes of the countable scan view (view=True: n records and the pod row of each).  EngineError (not ready) where there
+        is nothing current to copy."""
+        n, planes = C.c_int64(), C.c_int32()
+        self._ck(lib().kt_debug_match_planes(self._h, int(view), 0, None, None, C.byref(n), C.byref(planes)))
+        cap = max(int(n.value), 1)
+        out = np.zeros((int(planes.value), cap), dtype=np.uint64)
+        rows = np.zeros(cap, dtype=np.int64)
+        self._ck(lib().kt_debug_match_planes(self._h, int(view), cap, out.ctypes.data, rows.ctypes.data if view else None, C.byref(n), C.byref(planes)))
+        return out[:, :int(n.value)], (rows[:int(n.value)] if view else None)
 
     def index_stats(self) -> dict:
         """The compiled selector index (after the first launch): LDS-sized chunks, 64-bit words of term numbers, namespace rows,

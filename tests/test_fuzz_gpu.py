@@ -24,7 +24,9 @@ pytestmark = pytest.mark.gpu
 PATH_SWITCHES = ("KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK",
                  "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_NO_VIEW_PATCH",
                  "KT_CHECK_ONE_PER_CU", "KT_INGEST_EVENT_WAIT", "KT_INGEST_TRUST_FENCE")
-SWITCHES = ("KT_CHUNK_BUDGET", "KT_AGG_SMALL_WINDOW", "KT_CUT_PLAN") + PATH_SWITCHES
+# the match cache's switches: the table off, the aggregate's replay off, the aggregate at one workgroup per CU (which cannot replay)
+CACHE_SWITCHES = ("KT_NO_MATCH_CACHE", "KT_NO_MATCH_CACHE_AGG", "KT_AGG_ONE_PER_CU")
+SWITCHES = ("KT_CHUNK_BUDGET", "KT_AGG_SMALL_WINDOW", "KT_CUT_PLAN") + PATH_SWITCHES + CACHE_SWITCHES
 
 
 def draw_case(seed):
@@ -64,6 +66,10 @@ def draw_case(seed):
         variant = E.VARIANT_DENSE  # the dense cross-check kernels (no index)
     if r2.random() < .02:
         kw["n_pods"] = int(r2.integers(60000, 200000))  # hundreds of workgroups: planned ranges, every slab in use
+    r3 = np.random.default_rng(seed ^ 0x3A7C4E)  # (a third stream: the shapes and switches above stay what they were)
+    if r3.random() < .4:
+        for k in r3.choice(CACHE_SWITCHES, size=int(r3.integers(1, 3)), replace=False):
+            env[str(k)] = "1"
     return kw, env, variant, post
 
 

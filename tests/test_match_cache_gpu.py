@@ -1,11 +1,14 @@
 """The match cache: single-chunk programs keep, per pod row, the matched terms of every word of the pod's namespace list, and the
-two-per-CU form of the PreFilter sweep replays that table instead of scanning the selectors again (the aggregate scan keeps its
-selector scan: its cached form was measured no faster and did not ship — profiles/match_cache.txt — so a step counts ONE cached scan).
+two-per-CU form of the PreFilter sweep replays that table instead of scanning the selectors again.  (The two-per-CU aggregate
+replays it too, from a copy of the planes in the order of its scan view: test_agg_match_cache_gpu.py, and with several planes
+test_match_cache_planes_gpu.py.  The cases here read the sweep's counter: the second element of assert_counters.)
 
 Every case runs two engines fed alike — one as it comes, one under KT_NO_MATCH_CACHE=1 — and compares the sweep's summary words of
 all rows and the reconcile result on all throttle rows between them, the reconcile on the responsible rows and the summary words
 with the oracle, and reads from the counters (full builds of the table, scans served from it) which path ran.
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -21,12 +24,14 @@ NOW = (1767225600, 0)
 COUNTER_NS_WORD_VISITS, COUNTER_NS_ROWS = E.COUNTER_NS_WORD_VISITS, E.COUNTER_NS_ROWS
 
 
-def shape_with_planes(lo, hi):
-    """(throttles, ClusterThrottles) of the configs[2] generator whose single-chunk program has a longest namespace word list of
-    lo..hi words, found by compiling small engines (KT_COUNTER_MATCH_CACHE_PLANES after one sweep) over a ladder of shapes."""
+@functools.lru_cache(maxsize=None)  # (once per process and question: the modules that import it share the answers)
+def shape_with_planes(lo, hi, preset=2):
+    """(throttles, ClusterThrottles) of the configs[2] generator (or another preset's) whose single-chunk program has a longest
+    namespace word list of lo..hi words, found by compiling small engines (KT_COUNTER_MATCH_CACHE_PLANES after one sweep) over a
+    ladder of shapes."""
     seen = []
     for n_thr, n_cluster in ((200, 100), (300, 150), (400, 200), (500, 400), (600, 500), (700, 640), (800, 740), (900, 840), (1100, 1040)):
-        snap = W.generate(cfg2_scaled(640, n_thr=n_thr, n_cluster=n_cluster))
+        snap = W.generate(cfg2_scaled(640, n_thr=n_thr, n_cluster=n_cluster, preset=preset))
         e = E.Engine.for_snapshot(snap, E.VARIANT_INDEXED)
         try:
             e.check(n=snap.n_pods, want_status=False)
@@ -89,7 +94,8 @@ def twin_for(snap, monkeypatch):
 @pytest.mark.parametrize("preset", [2, 3], ids=["configs2-simple", "configs3-rich"])
 def test_basic_parity(preset, oracle_mod, monkeypatch):
     """66 037 pods (a multiple of neither 64 nor 1024; the tiles straddle namespaces) x 48 throttles: one build, and the
-    sweep of the step replays the table.  Preset 3: vetoes and several terms per selector (run masks)."""
+    sweep of the step replays the table.  Preset 3: configs[3]'s generator — overrides; its selectors are as simple as configs[2]'s
+    (a program with vetoes, whose table kt_build_match_cache<true, 3> builds: the `vetoes` kind of test_match_cache_planes_gpu.py)."""
     snap = W.generate(cfg2_scaled(66_037, preset=preset))
     tw = twin_for(snap, monkeypatch)
     try:
