@@ -1,4 +1,5 @@
 // kt_kernels_check.hip — kt_check_bitmap: PreFilter for n pods through the exact term bitmaps of the selector index (gfx950).
+#include <cassert>
 #include <type_traits>
 
 #include "kt_scan.h"
@@ -133,14 +134,8 @@ void launch_build_verdict_images(const IndexDev& ix, uint32_t total_words, const
 }
 
 // what a tile needs of its 64 pods before it can start (kt_check_bitmap's fetch_tile)
-template <bool CACHED>
-struct TileMatchWords {};
-template <>
-struct TileMatchWords<true> {
-  uint64_t mx[kMatchReplay];   // cached form: the pod's planes of the match cache (instead of the atom row)
-};
-template <int LA, int NV = 1, bool CACHED = false>
-struct TileRec : TileMatchWords<CACHED> {
+template <int LA, int NV = 1>
+struct TileRec {
   uint32_t p;                  // pod row
   uint64_t meta;
   u32x4 raw[LA / 8];           // atom row
@@ -194,8 +189,6 @@ struct BmCheckArgs {
   uint32_t off_rank, off_tab;
   uint32_t pk_nw, pk_rec;  // PackPlan::nw / rec_bytes
   uint32_t pk_dim[8];      // per dimension: shift | pos << 8 | word << 16 | (width != 0) << 24
-  // cached form (the CACHED instantiation): the match cache of the program, indexed by pod row
-  MatchCacheArgs mc;
 };
 
 static BmCheckArgs make_bm_check_args(const PodTable& pods, int64_t n, const int64_t* rows, const SelProgram& sp,
@@ -250,16 +243,10 @@ uint32_t check_word_lds(int D) { return 64u * 8u + (uint32_t)(D <= 8 ? sizeof(Wo
 //       matches, exactly as kt_aggregate_bitmap's packed instantiation does, and the workgroup spills its table of records
 //       as a slab for kt_reduce_finalize_packed.  One pass over the pod rows, one chunk prologue, one scan per pod where
 //       check + aggregate made two; the check's verdicts are those against the status stored BEFORE this reconcile.
-// CACHED: the lean ONE sweep over rows [0, n) REPLAYS the pod's words of the match cache (a.mc; kt_scan.h: replay_tile) instead
-//       of scanning: no atom row is loaded, no bitmap row gathered, and of the image only the namespace lists are staged.  The
-//       prologue's TermInfo / WordVerdict, the settle and the drain are those of the uncached form: the words the table holds
-//       are exactly what its scan_tile would hand to them.  ONE instantiation — 8 dimensions, lists of at most kMatchReplay
-//       words: 63 VGPRs, 0 B of scratch (profiles/kernel_resources_match_cache.txt); 16 dimensions or a second batch of planes
-//       carried 8-52 B of scratch and were never measured to win: such programs keep the scan.
-template <int DT, int LA, bool VETO, int NEED, int WPE, bool FULL, bool SMALL, bool ONE = false, bool AGG = false, bool CACHED = false>
+// (The lean ONE sweep that REPLAYS the match cache is a kernel of its own: kt_check_bitmap_cached, below.)
+template <int DT, int LA, bool VETO, int NEED, int WPE, bool FULL, bool SMALL, bool ONE = false, bool AGG = false>
 __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckArgs a) {
   static_assert(!AGG || (ONE && !FULL && !SMALL && WPE < 8), "the fused sweep is the lean single-chunk form, one workgroup per CU");
-  static_assert(!CACHED || (ONE && !FULL && !SMALL && !AGG && WPE >= 8 && !VETO && NEED == 2 && DT == 8), "the cached form is the lean two-per-CU sweep (one instantiation: nothing of the scan's form is left in it)");
   // (pieces of the three rows per batch: 12 registers each — the whole rows of a 16-dimension engine would be 96 registers
   //  of a 128-register kernel: four pieces per batch at most, two batches there)
   constexpr int kDrainUnroll = WPE >= 8 ? 1 : (DT / 2 > 4 ? 4 : DT / 2);  // drains in the middle of a scan (the list ran full)
@@ -327,19 +314,18 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
     const uint32_t wt0 = SMALL ? (wave == 0 ? blockIdx.y : n_wtiles) : by_ns ? t_lo + wave : blockIdx.x * (kBlockIx / kWave) + wave;
     const uint32_t wt_step = SMALL ? n_wtiles : by_ns ? (uint32_t)(kBlockIx / kWave) : wstep;
     auto fetch_tile = [&](uint32_t wt) {
-      TileRec<LA, AGG ? DT : 1, CACHED> r;
+      TileRec<LA, AGG ? DT : 1> r;
       const uint32_t i = rec0 + wt * kWave + lane;
       const uint32_t ic = min(i, rec_end - 1u);
-      r.p = CACHED ? ic : (SMALL && a.n_inline) ? (uint32_t)a.inline_rows[ic & 7u] : a.rows ? (uint32_t)a.rows[ic] : ic;
+      r.p = (SMALL && a.n_inline) ? (uint32_t)a.inline_rows[ic & 7u] : a.rows ? (uint32_t)a.rows[ic] : ic;
       r.meta = by_ns ? a.v_meta[ic] : a.meta[r.p];
-      if constexpr (CACHED) load_match_words(a.mc, r.p, r.mx);  // (with the meta word, not behind it: they hang off the row only)
-      else load_atoms<LA>(by_ns ? a.v_latom : a.latom, by_ns ? ic : r.p, r.raw);
+      load_atoms<LA>(by_ns ? a.v_latom : a.latom, by_ns ? ic : r.p, r.raw);
       const unsigned long long* carry_w = by_ns ? (const unsigned long long*)a.carry + ic : (const unsigned long long*)a.summary + (by_ns ? r.p : i);
       r.carried = (!SMALL && !first && i < rec_end) ? __hip_atomic_load(carry_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
       if constexpr (AGG) load_requests<DT>(a.req, DS, (int64_t)r.p, r.v);  // every lane's: the row does not hang off the meta word
       return r;
     };
-    TileRec<LA, AGG ? DT : 1, CACHED> cur{};
+    TileRec<LA, AGG ? DT : 1> cur{};
     KT_PROF_T(t_b0);
     __syncthreads();  // nobody reads the previous image any more
     KT_PROF_T(t_b1);
@@ -356,9 +342,6 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
        // — sweeps of multi-chunk programs — the chunk's words of the TermInfo / WordVerdict tables kt_build_verdict_images left
       const u32x4* img0 = (const u32x4*)(a.ix.blob + ch.img_off);
       StageSeg segs[4] = {chunk_image_segment(a.ix, ch), StageSeg{0u, img0, 0u}, StageSeg{0u, img0, 0u}, StageSeg{0u, img0, 0u}};
-      // (cached form: of the image only the namespace lists, at their usual offsets — the rows and word headers are not read)
-      if constexpr (CACHED)
-        segs[0] = StageSeg{a.ix.lds_img + ch.off_nsl_rng, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_nsl_rng), (ch.lds_bytes - ch.off_nsl_rng) / 16u};
       if constexpr (AGG) segs[1] = StageSeg{a.off_rank, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_term_rank), ch.n_words * 8u};
       if (from_images) {
         segs[2] = StageSeg{a.off_tinfo, (const u32x4*)(a.wv_img + (size_t)ch.w0 * verdict_image_word_bytes<DT>()), ch.n_words * (64u * 8u / 16u)};
@@ -415,7 +398,7 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
       const uint64_t meta = cur.meta;
       u32x4 raw[LA / 8];
 #pragma unroll
-      for (int q = 0; q < LA / 8; ++q) raw[q] = CACHED ? u32x4{0u, 0u, 0u, 0u} : cur.raw[q];
+      for (int q = 0; q < LA / 8; ++q) raw[q] = cur.raw[q];
       // class counters so far (bit 1 = error) ride in the summary word (namespace order: the carry word) between chunks
       unsigned long long* carry_w = by_ns ? (unsigned long long*)a.carry + ic : (unsigned long long*)a.summary + si;
       const unsigned long long carried = cur.carried;
@@ -430,7 +413,7 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
       const uint32_t ns_ok_raw = a.ns_valid[ns];
       bool pod_err = (carried & 2ull) != 0;
       uint32_t ro[LA];
-      if constexpr (!CACHED) atom_row_offsets<LA>(raw, ro);
+      atom_row_offsets<LA>(raw, ro);
       uint32_t n_list = 0;  // wave-uniform
       uint32_t last_t = 0xFFFFFFFFu;
       // AGG: is the pod counted (shouldCountIn && isNotFinished: throttle_controller.go:217-219, pod_util.go:26-28), and
@@ -652,10 +635,7 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
         return term_match_mem(*a.sp, bm.term_g[c], a.lpair + (uint64_t)p * (uint32_t)a.LS, a.lkey + (uint64_t)p * (uint32_t)a.LS, a.LS);
       };
       auto peel_tight = [&](bool has, uint32_t c) { push(has, c); };
-      if constexpr (CACHED) {
-        auto settle_word = [&](uint32_t w, uint64_t x, int) -> uint64_t { return settle(w, x, fetch(w)); };
-        replay_tile(bm, scan_on, ns, cur.mx, a.mc.planes, peel_tight, settle_word, ScanNoPrefetch());
-      } else if constexpr (PREFETCH) {
+      if constexpr (PREFETCH) {
         scan_tile<LA, VETO, NEED, VETO>(
             bm, scan_on, ns, ro, peel_tight, confirm_slow,
             [&](uint32_t w, uint64_t x, const VerdictRegs& q) -> uint64_t { return settle(w, x, q); },
@@ -736,17 +716,253 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------------
+// kt_check_bitmap_cached — the lean sweep of rows [0, n) of a single-chunk program, two workgroups per CU, that REPLAYS the pod's
+// words of the match cache (kt_scan.h: replay_tile) instead of scanning: no atom row is loaded, no bitmap row gathered, and of
+// the image only the namespace lists are staged.  A body of its own beside kt_check_bitmap, as kt_aggregate_bitmap_one stands
+// beside kt_aggregate_bitmap — the instantiation of the generic template had 63 VGPRs, 9 spilled SGPRs and no register to spare:
+//   kept    : the prologue (TermInfo / WordVerdict per workgroup from the CheckRec flags), the settle per word, the tight-match
+//             list and its drain, the summary word — the words the table holds are exactly what scan_tile would hand to them;
+//   dropped : the chunk loop and the carry words, row lists and views, the slow list and overflow pods, the status matrix, the
+//             fold of the fused sweep; the chunk's descriptor travels in the arguments (no dependent scalar load in front of the
+//             prologue's loads), and the argument block holds only what this form reads.
+// One instantiation per plane count (PL <= kMatchReplay), 8 dimensions, whatever the program's form: VETO and NEED only shape
+// scan_tile, and the replay runs neither — a rich program's table was built by kt_build_match_cache<true, 3>, its words are final.
+// A tile's loads are one batch (ld_issued, kt_scan.h): the planes stand beside the meta word, not behind its arrival.  What a lane
+// settled in the replay joins the drain's counters in cnt[lane] — with `on` as bit 0 and the Error verdict as bit 1 — and the
+// summary word is cut from that word: no lane state but the counters is live across the drain.
+// (Two tiles of a wave in flight together with ONE drain per pair were built on this body and measured: they fit 64 VGPRs up to
+//  three planes only, and configs[2] and [3] have four — profiles/tile_pairs.txt, NEXT.md section 3.)
+struct BmCheckCachedArgs {
+  const uint64_t* meta;        // pod tables
+  const int64_t* req;
+  const void* recs;
+  uint64_t* summary;
+  const uint8_t* ns_valid;
+  const uint64_t* mw;          // the match cache: [planes][mw_stride], indexed by pod row
+  uint64_t mw_stride;
+  const unsigned char* blob;   // chunk images
+  BmChunk ch;                  // the chunk's descriptor by value
+  uint32_t n;
+  int32_t DS, T;
+  uint32_t lds_img, off_cnt, off_list, off_tinfo, off_wv;
+};
+static_assert(kTermRowMask == (1u << 20) - 1u && kWave == 64, "a list entry is lane << 20 | term number");
+
+// LDS of the form: cnt[64] per wave, the list, TermInfo + WordVerdict, the image (only its namespace lists are staged, at
+// their usual offsets)
+static BmCheckCachedArgs make_check_cached_args(const IndexDev& ix, uint32_t* total) {
+  BmCheckCachedArgs a{};
+  uint32_t o = 0;
+  auto take = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
+  a.off_cnt = take(kBlockIx * 8u);
+  a.off_list = take((kBlockIx / kWave) * kListCap * 4);
+  a.off_tinfo = take(ix.bm_max_words * 64u * 8u);
+  a.off_wv = take(ix.bm_max_words * (uint32_t)sizeof(WordVerdict<8>));
+  a.lds_img = take(ix.bm_max_lds);
+  *total = o;
+  return a;
+}
+
+template <int PL>
+__global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCheckCachedArgs a) {
+  static_assert(PL >= 1 && PL <= kMatchReplay, "one instantiation per plane count");
+  constexpr int DT = 8;
+  KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
+  const CheckRec<DT>* recs = (const CheckRec<DT>*)a.recs;
+  const u32x2* g_rflags = (const u32x2*)rec_flags<DT>((void*)a.recs, a.T);
+  const uint32_t n = a.n;
+  const int DS = a.DS;
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  lds_u64wp cnt = (lds_u64wp)(lds + a.off_cnt) + wave * kWave;  // [64] class counters coming back from the drain
+  lds_u32wp list = (lds_u32wp)(lds + a.off_list) + wave * kListCap;
+  KT_LDS u32x2* tinfo = (KT_LDS u32x2*)(lds + a.off_tinfo);
+  KT_LDS const unsigned char* wv = lds + a.off_wv;
+  const BmChunk& ch = a.ch;
+  const uint32_t n_wtiles = (n + kWave - 1) / kWave;
+  const uint32_t wstep = gridDim.x * (kBlockIx / kWave);
+  BmIndexArgs ixa{};
+  ixa.blob = a.blob, ixa.lds_img = a.lds_img;
+  const BmView bm = open_chunk<false>(lds, ixa, ch);
+  // ---- prologue, as the generic form's: the first term word of every thread AHEAD of the image's tail, the tables built in place
+  {
+    const uint32_t* term_t = (const uint32_t*)(a.blob + ch.img_off + ch.off_term_t);
+    uint32_t tt_first = 0u;
+    if (threadIdx.x < ch.n_words * 64u) tt_first = term_t[threadIdx.x];
+    const StageSeg segs[1] = {StageSeg{a.lds_img + ch.off_nsl_rng, (const u32x4*)(a.blob + ch.img_off + ch.off_nsl_rng), (ch.lds_bytes - ch.off_nsl_rng) / 16u}};
+    lds_stage_segments<1>(lds, segs);
+    for (uint32_t c = threadIdx.x; c < ch.n_words * 64u; c += kBlockIx)
+      build_term_verdicts<DT, true>(c == threadIdx.x ? tt_first : term_t[c], c, g_rflags, tinfo, (KT_LDS WordVerdict<DT>*)(lds + a.off_wv));
+  }
+  __syncthreads();
+  const bool seg_on = ch.has_adj != 0u;  // wave-uniform: some throttle of the chunk has several terms
+
+  struct Rec {
+    uint64_t meta;
+    uint64_t mx[kMatchReplay];
+  };
+  // (ld_issued: every load of a record stands where it is written — the planes are not moved behind the meta word's arrival)
+  auto fetch_tile = [&](uint32_t wt) {  // always from valid addresses: lanes past the end re-read the last row and are off
+    Rec r{};
+    const uint32_t ic = min(wt * kWave + lane, n - 1u);
+    r.meta = ld_issued(a.meta + ic);
+    const uint64_t* q = a.mw + ic;
+#pragma unroll
+    for (int j = 0; j < PL; ++j) r.mx[j] = ld_issued(q + (uint64_t)j * a.mw_stride);
+    return r;
+  };
+  for (uint32_t wt = blockIdx.x * (kBlockIx / kWave) + wave; wt < n_wtiles; wt += wstep) {
+    const Rec r = fetch_tile(wt);
+    cnt[lane] = 0ull;
+    uint32_t n_list = 0;  // wave-uniform
+
+    // ---- lane = listed (pod lane, term): the full comparison.  The pod row follows from the lane; the pod's non-zero mask is
+    //      read again from its meta word, with the rows (the same trip; the word has just been through L2)
+    auto drain = [&](auto unroll_tag) {
+      constexpr int UNROLL = decltype(unroll_tag)::value;
+      for (uint32_t base = 0; base < n_list; base += kWave) {
+        const uint32_t j = base + lane;
+        const bool vv = j < n_list;
+        const uint32_t e = list[vv ? j : 0u];
+        const uint32_t pl = e >> 20;
+        const u32x2 ti = tinfo[e & kTermRowMask];
+        const uint32_t t = ti.x & kTermRowMask;
+        const uint32_t prow = min(wt * kWave + pl, n - 1u);  // (a listed lane is on: its row is in range)
+        static_assert(kMetaNzShift == 48, "the non-zero mask is the meta word's top 16 bits");
+        const uint32_t pnz = ((const uint16_t*)(a.meta + prow))[3];
+        const CheckRec<DT>* rc = recs + t;
+        const kt_i64x2* xr = (const kt_i64x2*)(a.req + (uint64_t)prow * (uint32_t)DS);
+        const uint32_t sh_act = (ti.y >> kTiShActive) & 63u, sh_idle = (ti.y >> kTiShIdle) & 63u;
+        const uint32_t fx = (sh_act == 4u ? kRecExceedsByCount : 0u) | (sh_idle == 24u ? kRecActiveByCount : 0u) | (sh_idle == 44u ? kRecInsufficientByCount : 0u);
+        const uint32_t fy = ti.y & 0xFFFFu;
+        bool exc = false, ins = false;
+        if constexpr (UNROLL == 0) {
+          // the drain in the middle of a replay (the list ran full: more than 64 tight matches in a tile, where configs[2] has
+          // four or five): one dimension at a time, six registers — it runs with the replay's state waiting beside it
+#pragma unroll 1
+          for (int d = 0; d < DT; ++d) {
+            const int64_t x = a.req[(uint64_t)prow * (uint32_t)DS + (uint32_t)(d < DS ? d : 0)], th = rc->thr[d], hd = rc->head[d];
+            const bool nzd = (pnz >> d) & 1u;
+            exc |= nzd && x > th, ins |= nzd && x > hd;
+          }
+        } else {
+#pragma unroll 1
+        for (int q0 = 0; q0 < DT / 2; q0 += UNROLL) {
+          // one batch: UNROLL pieces of the three rows in flight together, nothing looks at a value before all are requested
+          kt_i64x2 x[UNROLL], th[UNROLL], hd[UNROLL];
+#pragma unroll
+          for (int u = 0; u < UNROLL; ++u) {
+            const int q = q0 + u;
+            x[u] = xr[2 * q < DS ? q : 0];  // pieces past the row re-read piece 0 and are masked by pnz
+            th[u] = *(const kt_i64x2*)(rc->thr + 2 * q);
+            hd[u] = *(const kt_i64x2*)(rc->head + 2 * q);
+          }
+#pragma unroll
+          for (int u = 0; u < UNROLL; ++u) {
+            const int q = q0 + u;
+            const bool nz0 = (pnz >> (2 * q)) & 1u, nz1 = (pnz >> (2 * q + 1)) & 1u;
+            exc |= (nz0 && x[u].x > th[u].x) || (nz1 && x[u].y > th[u].y);
+            ins |= (nz0 && x[u].x > hd[u].x) || (nz1 && x[u].y > hd[u].y);
+          }
+        }
+        }
+        exc |= (fx & kRecExceedsByCount) != 0, ins |= (fx & kRecInsufficientByCount) != 0;
+        const bool act = (fx & kRecActiveByCount) || (pnz & fy);
+        const uint32_t st = exc ? 4u : act ? 2u : ins ? 3u : 1u;
+        if (vv && st != 1u) lds_add64(cnt + pl, st == 4u ? 1ull << 4 : st == 2u ? 1ull << 24 : 1ull << 44);
+      }
+      n_list = 0;
+    };
+    auto push = [&](bool want, uint32_t e) {  // wave-wide append
+      const uint64_t mk = __ballot(want);
+      if (mk == 0ull) return;
+      if (want) list[n_list + lane_rank(mk)] = e;
+      n_list += (uint32_t)__popcll(mk);
+      if (n_list > kListCap - kWave) drain(std::integral_constant<int, 0>());  // (the list ran full, mid-tile)
+    };
+    // ---- the tile: every match that needs no comparison is settled per WORD with mask algebra (WordVerdict), the matches of
+    //      tight throttles are listed as (lane, term number)
+    {
+      const uint64_t meta = r.meta;
+      const bool on = wt * kWave + lane < n && ((meta >> kMetaStateShift) & kPodValid) != 0;
+      const uint32_t ns = on ? (uint32_t)(meta & kMetaNsMask) : 0u;
+      const uint32_t nz = (uint32_t)(meta >> kMetaNzShift) & 0xFFFFu;
+      // affectedClusterThrottles: the pod's Namespace object must exist (clusterthrottle_controller.go:273-276)
+      // (the byte is requested here and looked at behind the replay)
+      const uint32_t ns_ok_raw = a.ns_valid[ns];
+      auto nib_offset = [&](int q) { return (uint32_t)offsetof(WordVerdict<DT>, act_nib) + (uint32_t)q * 128u + ((nz >> (4 * q)) & 15u) * 8u; };
+      uint32_t n_exc = 0u, n_act = 0u, n_ins = 0u;
+      auto settle_word = [&](uint32_t w, uint64_t x, int) -> uint64_t {
+        KT_LDS const unsigned char* q = wv + __umul24(w, (uint32_t)sizeof(WordVerdict<DT>));
+        if (seg_on) {  // a throttle with several terms is reported once: the lowest match of every run
+          const u64x2 seg = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, seg_lo));
+          const uint64_t v = x | seg.y;
+          x = andn_64(x, v - seg.x);  // (= x & (v ^ (v - seg_lo)) & v, x being part of v)
+        }
+        const u64x2 te = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, tight));  // {tight, exc}
+        const u64x2 ai = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, act));    // {act, ins}
+        uint64_t act = *(KT_LDS const unsigned long long*)(q + nib_offset(0));  // (act-by-count is part of every entry of nibble 0's table)
+#pragma unroll
+        for (int k = 1; k < DT / 4; ++k) act |= *(KT_LDS const unsigned long long*)(q + nib_offset(k));
+        const uint64_t xe = and_not_and_64(x, te.x, te.y);  // not tight, exceeded by count
+        const uint64_t xf = and_not_not_64(x, te.x, te.y);  // settled here, not exceeded by count
+        const uint64_t xa = xf & act, xi = and_not_and_64(xf, act, ai.y);
+        n_exc = (uint32_t)__popc((uint32_t)xe) + ((uint32_t)__popc((uint32_t)(xe >> 32)) + n_exc);
+        n_act = (uint32_t)__popc((uint32_t)xa) + ((uint32_t)__popc((uint32_t)(xa >> 32)) + n_act);
+        n_ins = (uint32_t)__popc((uint32_t)xi) + ((uint32_t)__popc((uint32_t)(xi >> 32)) + n_ins);
+        return x & te.x;
+      };
+      replay_tile(bm, on, ns, r.mx, (uint32_t)PL, [&](bool has, uint32_t c) { push(has, lane << 20 | c); }, settle_word, ScanNoPrefetch());
+      // what the lane settled joins what drains have brought and will bring (counters from bit 4 up; bit 0: on, bit 1: Error)
+      const unsigned long long my = (unsigned long long)n_exc << 4 | (unsigned long long)n_act << 24 | (unsigned long long)n_ins << 44;
+      cnt[lane] += my | (on ? 1ull : 0ull) | ((on && ns_ok_raw == 0u) ? 2ull : 0ull);
+    }
+    if (n_list) drain(std::integral_constant<int, 2>());
+    // ---- lane = pod: the 8-byte summary word
+    if (wt * kWave + lane < n) {
+      const unsigned long long w = cnt[lane], c = w & ~3ull;
+      a.summary[wt * kWave + lane] = !(w & 1ull) ? 0ull : (w & 2ull) ? 2ull : (c | (c ? 1ull : 0ull));
+    }
+  }
+}
+
+static void launch_check_cached(const PodTable& pods, int64_t n, const SelProgram& sp, const IndexDev& ix, const void* recs, uint64_t* summary,
+                                const MatchCacheArgs& mc, dim3 grid, hipStream_t s) {
+  uint32_t total = 0;
+  BmCheckCachedArgs a = make_check_cached_args(ix, &total);
+  // (the form's footprint is the generic two-per-CU form's without its tile counter, so two of them fit where the caller found
+  //  that form to fit; a list entry is lane << 20 | term number, as in the generic kernel)
+  assert(2u * total <= (uint32_t)kMaxLds && (uint64_t)ix.bm_max_words * 64u <= (uint64_t)kTermRowMask + 1u);
+  a.meta = pods.meta, a.req = pods.req, a.recs = recs, a.summary = summary, a.ns_valid = sp.ns_valid;
+  a.mw = mc.mw, a.mw_stride = mc.stride;
+  a.blob = ix.bm_blob, a.ch = ix.h_chunks[0];
+  a.n = (uint32_t)n, a.DS = pods.DS, a.T = sp.T;
+  static const bool dbg_lds = getenv("KT_DEBUG_LDS") != nullptr;
+  if (dbg_lds) fprintf(stderr, "kt_check_bitmap_cached: lds=%u (2 per CU) workgroups=%u planes=%u\n", total, grid.x, mc.planes);
+#define KT_CHECK_CACHED_LAUNCH(PL_)                                                                             \
+  {                                                                                                             \
+    auto kfn = kt_check_bitmap_cached<PL_>;                                                                     \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);        \
+    hipLaunchKernelGGL(kfn, grid, dim3(kBlockIx), total, s, a);                                                 \
+  }
+  static_assert(kMatchReplay == 4, "one instantiation per plane count");
+#ifdef KT_FAST_BUILD
+  KT_CHECK_CACHED_LAUNCH(kMatchReplay)  // (the caller dispatches the form for tables of exactly that many planes)
+#else
+  switch (mc.planes) {
+    case 1: KT_CHECK_CACHED_LAUNCH(1) break;
+    case 2: KT_CHECK_CACHED_LAUNCH(2) break;
+    case 3: KT_CHECK_CACHED_LAUNCH(3) break;
+    default: KT_CHECK_CACHED_LAUNCH(4) break;
+  }
+#endif
+#undef KT_CHECK_CACHED_LAUNCH
+}
+
 #define KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, WPE_, FULL_, SMALL_, ONE_)                                         \
   {                                                                                                             \
     auto kfn = kt_check_bitmap<DT_, LA_, VETO_, NEED_, WPE_, FULL_, SMALL_, ONE_>;                              \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
-    hipLaunchKernelGGL(kfn, g_, b_, lds_bytes, s, bm_args);                                                     \
-  }
-// (the cached sweep is ONE instantiation whatever the program's form: VETO and NEED only shape scan_tile and open_chunk's veto
-//  offsets, and the replay runs neither — a rich program's table was built by kt_build_match_cache<true, 3>, its words are final)
-#define KT_BM_LAUNCH_CACHED()                                                                                   \
-  {                                                                                                             \
-    auto kfn = kt_check_bitmap<8, 8, false, 2, 8, false, false, true, false, true>;                             \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
     hipLaunchKernelGGL(kfn, g_, b_, lds_bytes, s, bm_args);                                                     \
   }
@@ -754,7 +970,7 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
   {                                                                                          \
     if (small) KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 4, true, true, false)                    \
     else if (full) KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 4, true, false, false)               \
-    else if (cached) KT_BM_LAUNCH_CACHED()                                                   \
+    else if (cached) launch_check_cached(pods, n, sp, ix, recs, summary, *mc, g_, s); \
     else if (two_per_cu) KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 8, false, false, true)         \
     else KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, 4, false, false, false)                        \
   }
@@ -811,7 +1027,10 @@ const char* launch_check_indexed(const PodTable& pods, int64_t n, const int64_t*
   // the cached form: the two-per-CU sweep of rows [0, n) of a program the engine holds a valid match cache for
   const bool cached = two_per_cu && DT <= 8 && mc != nullptr && mc->mw != nullptr && rows_dev == nullptr && mc->planes >= 1u &&
                       mc->planes <= (uint32_t)kMatchReplay && (uint64_t)n <= mc->stride && match_cache_fits(ix);
-  if (cached) bm_args.mc = *mc, mc->used = true;
+#ifdef KT_FAST_BUILD
+  if (cached && mc->planes != (uint32_t)kMatchReplay) return nullptr;  // (one instantiation: other shapes are not dispatchable)
+#endif
+  if (cached) mc->used = true;
   int64_t nb = (n + kBlockIx - 1) / kBlockIx;
   const int64_t max_b = two_per_cu ? 2 * kCUs : kCUs;
   if (nb > max_b) nb = max_b;

@@ -448,17 +448,12 @@ __device__ __forceinline__ void scan_tile(const BmView& b, bool lane_on, uint32_
 // kt_index.h.)
 // ---------------------------------------------------------------------------------------------------
 
-// The planes of pod row p, one batch of loads from always-valid addresses; planes at or past `planes` are zero.  They hang off
-// the row index alone and are requested together with the meta word, not behind it.  (kMatchReplay = 4 planes are what the
-// 64-VGPR sweep holds without scratch: eight at once, or a second batch behind the first, cost it 28-52 B — programs with longer
-// lists keep their scan.)
-__device__ __forceinline__ void load_match_words(const MatchCacheArgs& m, uint32_t p, uint64_t (&x)[kMatchReplay]) {
-  const uint64_t* q = m.mw + p;
-#pragma unroll
-  for (int j = 0; j < kMatchReplay; ++j) {
-    x[j] = 0ull;
-    if ((uint32_t)j < m.planes) x[j] = q[(uint64_t)j * m.stride];  // (wave-uniform condition)
-  }
+// A load that is ISSUED where it stands (the cached sweep's records: kMatchReplay = 4 planes are what a 64-VGPR scan holds without
+// scratch beside its state — programs with longer lists keep their scan): relaxed and of wavefront scope, it is the plain global_load,
+// but the compiler neither sinks it into the branch that first uses its value nor merges it with a neighbour — the loads of a
+// record stay one batch (s_waitcnt vmcnt(n) counts them down as they are used) instead of a chain behind the meta word.
+__device__ __forceinline__ uint64_t ld_issued(const uint64_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
 // scan_tile's contract for match / post / pre, fed from the table: list position k (wave-uniform) is one advance — a lane whose
