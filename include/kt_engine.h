@@ -536,7 +536,7 @@ int32_t kt_preempt_gangs_reprieve_launch(kt_engine* e, int64_t n, const int64_t*
  *      pending kt_reconcile_launch, a pending kt_aggregate_launch keeps its sums.  The results live in buffers of their own, grown
  *      only once the stream of an unfetched launch has drained: a pending forecast and a pending kt_preempt_launch result are
  *      independent — after one launch of each, in either order, both are fetchable.
- *      Out of scope: the paged form (more than KT_MAX_DIMS resource names), several ranks. -------------------------------- */
+ *      More than KT_MAX_DIMS resource names: kt_paged_forecast.  Out of scope: several ranks. ---------------------------- */
 #define KT_FORECAST_NONE (-1)
 int32_t kt_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns,
                            int32_t on_equal, void* stream);
@@ -695,11 +695,58 @@ int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, c
  * stored with KT_RECONCILE_APPLY stays stored); a pending kt_aggregate_launch of any page keeps its sums.  The call is a dry
  * run: stored status and reserved amounts of no page change.  A device error after the first launch is returned once the
  * stream has drained; no page keeps a pending result.
- * Out of scope: the gang forms and the forecast over pages, several ranks. */
+ * Out of scope: the gang forms over pages, several ranks. */
 #define KT_PREEMPT_REPRIEVE 0x1u
 int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_cand,
                          const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, uint32_t flags,
                          int64_t* out_prefix /* [n], nullable */, uint8_t* out_victims /* [n][n_cand], nullable */);
+/* kt_forecast_launch + kt_forecast_fetch over the pages, synchronous: their definition on the cluster of ALL names — R_k, the
+ * verdict bytes, KT_FORECAST_NONE, the error rows.  n_pages == 1 returns byte for byte what kt_forecast_launch +
+ * kt_forecast_fetch return.  The answer is NOT a combination of per-page calls: status.calculatedThreshold is compared and
+ * replaced as a whole, over all names (throttle_controller.go:116-133), so whether a throttle reads its calculated threshold or
+ * spec.threshold at instant t is one fact for all pages, and it changes from instant to instant (an override that names only a
+ * later page's resource replaces the threshold, and page 0 must then read a calculated threshold that omits its own names) —
+ * which is why the kernel sees every page.  Per affecting throttle (they come from ONE check of page 0 over pod_rows: the selector
+ * side is the same in every page, a pod-level error shows in every page):
+ *   - whole-throttle facts, an OR over the pages: `stored` — the dry reconcile is an error on some page, or the throttle is not
+ *     valid and responsible: the stored status is read on every page at every instant; `calc_at_any` — calculatedAt is set in
+ *     the stored status of some page (the answer stays right between a kt_paged_reconcile with KT_RECONCILE_APPLY and the
+ *     host's status write-back, when the pages' stored flags may disagree);
+ *   - a stored throttle is judged once over every page: the count part on page 0, every page's name part, against the stored
+ *     calculatedThreshold where calc_at_any holds and spec.threshold otherwise; a failure means the pod never passes;
+ *   - otherwise, per instant t_k, every page computes CalculateThreshold(t_k) over its names exactly as kt_forecast_launch does
+ *     (activity is decided by the instants, the same on every page; the first active override wins per name of that page) and
+ *     `differs` is the OR over the pages of: the page's calculated threshold differs by value from the page's stored one over its
+ *     names, or the page's messages fingerprint differs; page 0 adds the comparison of the pod count (the same in every page).
+ *     The throttle reads status.calculatedThreshold on EVERY page iff calc_at_any || differs, else spec.threshold on every
+ *     page; status.throttled is IsThrottled(used, true) against the calculated threshold either way.  The pod fails the throttle
+ *     at t_k iff the count part (page 0) or some page's name part of the four CheckThrottledFor steps fails against the threshold
+ *     read.  A page none of whose names the pod requests is still part of `differs`: it can replace the threshold for the others.
+ * The instants kt_override_instants reports are the same for every page — every page holds every override's times and parse flags
+ * — so a host asks page 0.
+ * On page 0's stream, in order: that check; for every page its dense aggregate (beside its partial buffer) and its dry finalize
+ * at t_0; the copy of the page descriptors; one launch of kt_forecast_paged (csrc/kt_kernels_forecast_paged.hip: one wave per
+ * pod, lane = instant position, the two fail accumulators and `differs` kept across the pages, one walk of the overrides per page
+ * and block of 64 instants); the copies out.  out_first [n] and out_verdicts [n][n_inst] are both nullable.
+ * Refused before anything is launched, and before any page's check slot, reconcile report or result buffer is touched: what
+ * kt_paged_admit refuses about the page set (different throttle-row counts, an engine named twice: KT_ERR_INVALID_ARGUMENT;
+ * different devices: KT_ERR_UNSUPPORTED), what kt_forecast_launch refuses about its arguments (n_inst < 1, instants that are not
+ * strictly ascending, an inst_ns outside [0, 10^9), a missing array: KT_ERR_INVALID_ARGUMENT; a pod row outside a page's
+ * capacity, n x throttle_rows or n x n_inst above 2^31: KT_ERR_OUT_OF_RANGE), and what it refuses about an engine, asked of every
+ * page: a KT_VARIANT_INCREMENTAL engine, an exchange world above 1, a `used` wider than int64 (KT_ERR_UNSUPPORTED) — as there,
+ * the one thing that may run first is a page's kernel that sums the |requests|.  n == 0 is KT_OK and launches nothing.  Locking
+ * (every page exclusively, in address order) and ordering are kt_paged_admit's.
+ * Slots: the call uses page 0's check slot (a pending kt_check_launch / kt_headroom_launch of page 0 is dropped) and page 0's
+ * forecast result buffers, grown only once the stream of an unfetched launch has drained — the results are handed out by the call,
+ * so a forecast that was pending on page 0 is gone afterwards (kt_forecast_fetch answers KT_ERR_NOT_READY) while a pending
+ * kt_preempt_launch result of page 0 stays fetchable; every page's dry finalize writes that page's reconcile result buffers, so
+ * every page's pending reconcile report is dropped (a status stored with KT_RECONCILE_APPLY stays stored); a pending
+ * kt_aggregate_launch of any page keeps its sums.  The call is a dry run: stored status and reserved amounts of no page change.
+ * A device error after the first launch is returned once the stream has drained; no page keeps a pending result.
+ * Out of scope: the gang preemption forms over pages, several ranks. */
+int32_t kt_paged_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
+                          const int32_t* inst_ns, int32_t on_equal, int64_t* out_first /* [n], nullable */,
+                          uint8_t* out_verdicts /* [n][n_inst], nullable */);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

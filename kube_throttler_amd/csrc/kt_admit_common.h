@@ -9,7 +9,9 @@
 // verdict bits; what kt_preempt_gangs and kt_preempt_gangs_reprieve share: the members of a gang in order on one throttle against one
 // state of `used` (gang_walk); and what the two reprieve kernels (kt_preempt_reprieve, kt_kernels_preempt_gangs_reprieve.hip:
 // kt_preempt_gangs_reprieve) share: arguments, the list's state in LDS or HBM with its sizes, the list (counted, then gathered) and
-// the walk over the masked positions, generic in who is judged.  The page descriptor itself (AdmitPage) is host-visible: kt_launch.h.
+// the walk over the masked positions, generic in who is judged; and what the two forecast kernels (kt_kernels_forecast.hip,
+// kt_kernels_forecast_paged.hip) share on top of the four steps: the comparison of two instants.  The page descriptors themselves
+// (AdmitPage, PreemptPage) are host-visible: kt_launch.h.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -97,6 +99,15 @@ __device__ __forceinline__ AdmitPage admit_page(const AdmitPage* pages, int k) {
 #endif
 }
 
+// a PreemptPage descriptor by value in the same way (kt_kernels_preempt_paged.hip, kt_kernels_forecast_paged.hip)
+__device__ __forceinline__ PreemptPage preempt_page(const PreemptPage* pages, int k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ((const __attribute__((address_space(4))) PreemptPage*)pages)[k];
+#else
+  return pages[k];
+#endif
+}
+
 // threshold := status.calculatedThreshold if calculatedAt != zero else spec.threshold (throttle_types.go:129-132)
 __device__ __forceinline__ const AmountTab& admit_threshold(const ThrTables& tt, uint32_t tf) { return (tf & kThrCalcAtNonzero) ? tt.calc : tt.spec; }
 // isThrottledOnEqual of step 3: always for a Throttle, the caller's for a ClusterThrottle (throttle_types.go:143 vs
@@ -118,6 +129,9 @@ __device__ __forceinline__ bool preempt_fails(int64_t vp, bool th_has, int64_t t
   if ((u_pres || r_has) && admit_cmp(s, tv, eq3)) return true;  // step 3
   return admit_cmp(s + vp, tv, eq);                             // step 4
 }
+
+// instant a <= instant b, (seconds, nanoseconds) each: the forecast kernels' override windows are inclusive at both ends
+__device__ __forceinline__ bool forecast_le(int64_t as, int32_t an, int64_t bs, int32_t bn) { return as != bs ? as < bs : an <= bn; }
 
 template <class V>
 __device__ __forceinline__ V wave_inclusive_scan(V x, uint32_t lane) {

@@ -918,6 +918,17 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
 // ---------------------------------------------------------------------------------------------------
 // preempt over pages: kt_preempt_launch / kt_preempt_reprieve_launch on the cluster of all names (kt_kernels_preempt_paged.hip)
 // ---------------------------------------------------------------------------------------------------
+// How a synchronous paged call (kt_paged_preempt, kt_paged_forecast) ends once it has launched on page 0's stream s: the stream is
+// drained, pages 1.. get back the last_stream they came with (`last`: nothing of the call stays pending on any page), and a
+// device error that shows only now is returned in KT_OK's place
+static int32_t paged_finish(const char* what, kt_engine* const* pages, int32_t n_pages, hipStream_t s, const std::vector<hipStream_t>& last,
+                            int32_t code) {
+  const hipError_t herr = hipStreamSynchronize(s);
+  for (int32_t k = 1; k < n_pages; ++k) pages[k]->last_stream = last[(size_t)k];
+  if (code == KT_OK && herr != hipSuccess) return pages[0]->fail(KT_ERR_DEVICE, "%s: %s", what, hipGetErrorString(herr));
+  return code;
+}
+
 int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_cand, const int64_t* cand_rows,
                          int64_t now_s, int32_t now_ns, int32_t on_equal, uint32_t flags, int64_t* out_prefix, uint8_t* out_victims) {
   PageLocks locks;
@@ -985,12 +996,7 @@ int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, co
   // pages 1.. get their own stream back as last_stream: nothing of this call stays pending on any page.
   std::vector<hipStream_t> last((size_t)n_pages);
   for (int32_t k = 0; k < n_pages; ++k) last[(size_t)k] = pages[k]->last_stream;
-  auto finish = [&](int32_t code) -> int32_t {
-    const hipError_t herr = hipStreamSynchronize(s);
-    for (int32_t k = 1; k < n_pages; ++k) pages[k]->last_stream = last[(size_t)k];
-    if (code == KT_OK && herr != hipSuccess) return e0->fail(KT_ERR_DEVICE, "paged preempt: %s", hipGetErrorString(herr));
-    return code;
-  };
+  auto finish = [&](int32_t code) -> int32_t { return paged_finish("paged preempt", pages, n_pages, s, last, code); };
   // ONE check of page 0 over preemptors ++ candidates: which throttles match which pod, and the error rows
   std::vector<int64_t> rows((size_t)(n + n_cand));
   std::copy(pod_rows, pod_rows + n, rows.begin());
@@ -1243,6 +1249,103 @@ int32_t kt_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, uint8_t* 
   if (out_verdicts) KT_HIP(e, hipMemcpyAsync(out_verdicts, e->d_forecast_verdicts.p, (size_t)n * (size_t)e->forecast_m, hipMemcpyDeviceToHost, s));
   KT_HIP(e, hipStreamSynchronize(s));
   return KT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// forecast over pages: kt_forecast_launch + kt_forecast_fetch on the cluster of all names (kt_kernels_forecast_paged.hip)
+// ---------------------------------------------------------------------------------------------------
+int32_t kt_paged_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
+                          const int32_t* inst_ns, int32_t on_equal, int64_t* out_first, uint8_t* out_verdicts) {
+  PageLocks locks;
+  int32_t rc = paged_lock("paged forecast", pages, n_pages, n, locks);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = pages[0];
+  // ---- refusals: nothing is launched and no slot of any page is touched before the last of them
+  if (n_inst < 1) return e0->fail(KT_ERR_INVALID_ARGUMENT, "forecast: n_inst = %lld", (long long)n_inst);
+  if ((n > 0 && !pod_rows) || !inst_s || !inst_ns) return e0->fail(KT_ERR_INVALID_ARGUMENT, "forecast: pod_rows / inst_s / inst_ns missing");
+  for (int64_t k = 0; k < n_inst; ++k) {
+    if (inst_ns[k] < 0 || inst_ns[k] >= 1000000000) return e0->fail(KT_ERR_INVALID_ARGUMENT, "forecast: inst_ns[%lld] = %d", (long long)k, inst_ns[k]);
+    if (k && !(inst_s[k - 1] < inst_s[k] || (inst_s[k - 1] == inst_s[k] && inst_ns[k - 1] < inst_ns[k])))
+      return e0->fail(KT_ERR_INVALID_ARGUMENT, "forecast: the instants are not strictly ascending at position %lld", (long long)k);
+  }
+  if ((rc = paged_same_cluster("paged forecast", pages, n_pages, n, pod_rows)) != KT_OK) return rc;  // (the rows are range-checked in place)
+  const int32_t T = e0->thr_rows_hi;
+  if ((double)n * (double)T > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "forecast: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  if ((double)n * (double)n_inst > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "forecast: n x n_inst = %lld x %lld exceeds 2^31 verdict bytes", (long long)n, (long long)n_inst);
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if (e->incremental) return e->fail(KT_ERR_UNSUPPORTED, "forecast: page %d: not for KT_VARIANT_INCREMENTAL engines", k);
+    if (e->exchange_world > 1)
+      return e->fail(KT_ERR_UNSUPPORTED, "forecast: page %d exchanges partials with %d ranks (one rank only)", k, e->exchange_world);
+    if (e->wide && e->req_sums_valid)
+      return e->fail(KT_ERR_UNSUPPORTED, "forecast: `used` of page %d is wider than int64 (kt_forecast_paged reads int64 sums)", k);
+  }
+  if (n == 0) return KT_OK;  // nothing is launched
+  hipStream_t s = nullptr;
+  if ((rc = paged_order(pages, n_pages, &s)) != KT_OK) return rc;
+  if ((rc = ensure_ready(e0, s)) != KT_OK) return rc;
+  // pod batches since a page's last aggregate may have pushed its sums beyond int64: found out here (the |request| sums kernel of
+  // that page, where they are not known), before the check slot, a reconcile report or a result buffer of any page is touched
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if ((rc = request_sums_in_range(e, s)) != KT_OK) return rc;
+    if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "forecast: `used` of page %d is wider than int64 (kt_forecast_paged reads int64 sums)", k);
+  }
+  // ---- from here on the call owns page 0's check slot and forecast result and every page's reconcile report
+  e0->forecast_ready = false;
+  if (!e0->preempt_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->preempt_pages_ev, hipEventDisableTiming));
+  KT_HIP(e0, hipEventSynchronize(e0->preempt_pages_ev));  // the previous call's copy has read h_preempt_pages
+  e0->h_preempt_pages.assign((size_t)n_pages, kt::PreemptPage{});
+  const size_t ver = (size_t)n * (size_t)n_inst;
+  if (e0->d_forecast_first.cap < (size_t)n || e0->d_forecast_verdicts.cap < ver + 1 || e0->d_forecast_inst_s.cap < (size_t)n_inst ||
+      e0->d_forecast_inst_ns.cap < (size_t)n_inst) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_forecast_launch)
+    if (e0->last_stream) KT_HIP(e0, hipStreamSynchronize(e0->last_stream));
+    KT_HIP(e0, e0->d_forecast_first.reserve((size_t)n));
+    KT_HIP(e0, e0->d_forecast_verdicts.reserve(ver + 1));
+    KT_HIP(e0, e0->d_forecast_inst_s.reserve((size_t)n_inst));
+    KT_HIP(e0, e0->d_forecast_inst_ns.reserve((size_t)n_inst));
+  }
+  KT_HIP(e0, e0->d_preempt_pages.reserve(sizeof(kt::PreemptPage) * (size_t)n_pages));
+  // Everything below runs on page 0's stream.  A failure after the first launch drains that stream before it is returned, and
+  // pages 1.. get their own stream back as last_stream: nothing of this call stays pending on any page.
+  std::vector<hipStream_t> last((size_t)n_pages);
+  for (int32_t k = 0; k < n_pages; ++k) last[(size_t)k] = pages[k]->last_stream;
+  auto finish = [&](int32_t code) -> int32_t { return paged_finish("paged forecast", pages, n_pages, s, last, code); };
+  hipError_t herr = hipSuccess;
+  // the instants travel on the same stream, behind an earlier forecast's kernel (the call returns behind finish: the caller's
+  // memory is not referenced afterwards)
+  if ((herr = hipMemcpyAsync(e0->d_forecast_inst_s.p, inst_s, (size_t)n_inst * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
+      (herr = hipMemcpyAsync(e0->d_forecast_inst_ns.p, inst_ns, (size_t)n_inst * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast: %s", hipGetErrorString(herr)));
+  // ONE check of page 0 over the pods: which throttles affect which pod, and the error rows.  The preempt result lives in buffers
+  // this call does not write: it stays fetchable
+  const bool preempt_was_ready = e0->preempt_ready;
+  rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e0->check_ready = false;  // the slot holds this call's rows (as with kt_forecast_launch): a pending kt_check_launch is gone
+  e0->preempt_ready = preempt_was_ready;
+  if (rc != KT_OK) return finish(rc);
+  // every page: its dense aggregate beside its partial buffer and its dry finalize at t_0 (its reconcile report is dropped)
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if ((rc = preempt_reconcile_locked(e, inst_s[0], inst_ns[0], s)) != KT_OK) return finish(rc);
+    kt::PreemptPage& pp = e0->h_preempt_pages[(size_t)k];
+    pp.pg = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+    pp.partial = e->d_preempt_partial.p, pp.calc = e->d_out_calc.tab(), pp.calc_updated = e->d_out_calc_updated.p, pp.error = e->d_out_error.p;
+  }
+  if (!kt::launch_forecast_paged(e0->h_preempt_pages.data(), n_pages, (kt::PreemptPage*)e0->d_preempt_pages.p, e0->preempt_pages_ev, n, n_inst,
+                                 e0->d_rows.p, e0->d_forecast_inst_s.p, e0->d_forecast_inst_ns.p, T, on_equal != 0, e0->d_status.p,
+                                 e0->d_summary.p, e0->d_forecast_first.p, e0->d_forecast_verdicts.p, s, &herr))
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast: copy of the page descriptors: %s", hipGetErrorString(herr)));
+  if ((herr = hipGetLastError()) != hipSuccess) return finish(e0->fail(KT_ERR_DEVICE, "paged forecast: %s", hipGetErrorString(herr)));
+  e0->last_stream = s;
+  if (out_first && (herr = hipMemcpyAsync(out_first, e0->d_forecast_first.p, (size_t)n * 8, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast: %s", hipGetErrorString(herr)));
+  if (out_verdicts && (herr = hipMemcpyAsync(out_verdicts, e0->d_forecast_verdicts.p, ver, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast: %s", hipGetErrorString(herr)));
+  return finish(KT_OK);  // (synchronises s; the results have been handed out: no forecast result is pending on page 0)
 }
 
 // Host-only: the instants in (from, until] at which some valid and responsible throttle's CalculateThreshold can change — every

@@ -368,8 +368,9 @@ struct kt_engine {
   DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's and kt_preempt_gangs_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
   bool preempt_ready = false;
   int64_t preempt_n = 0, preempt_m = 0;
-  // kt_paged_preempt (on page 0): the page descriptors of kt_preempt_paged, on the device and — the source of an asynchronous copy,
-  // under the rule of h_admit_pages with preempt_pages_ev in admit_pages_ev's place — on the host
+  // kt_paged_preempt and kt_paged_forecast (on page 0): the page descriptors of kt_preempt_paged / kt_forecast_paged, on the device
+  // and — the source of an asynchronous copy, under the rule of h_admit_pages with preempt_pages_ev in admit_pages_ev's place —
+  // on the host
   DevBuf<uint8_t> d_preempt_pages;
   std::vector<kt::PreemptPage> h_preempt_pages;
   hipEvent_t preempt_pages_ev = nullptr;
@@ -379,7 +380,8 @@ struct kt_engine {
   DevBuf<int64_t> d_preempt_gang_off, d_preempt_blocker;
   // the last kt_forecast_launch: first passing position per pod and the verdict bytes [n][n_inst], on the device until
   // kt_forecast_fetch — buffers of their own: a pending forecast and a pending preempt result do not disturb each other;
-  // d_forecast_inst_*: the instants as the kernel reads them
+  // d_forecast_inst_*: the instants as the kernel reads them.  kt_paged_forecast writes the same buffers of page 0 and hands
+  // the results out itself
   DevBuf<int64_t> d_forecast_first, d_forecast_inst_s;
   DevBuf<int32_t> d_forecast_inst_ns;
   DevBuf<uint8_t> d_forecast_verdicts;

@@ -41,8 +41,6 @@ struct ForecastArgs {
   int32_t T, on_equal;
 };
 
-__device__ __forceinline__ bool forecast_le(int64_t as, int32_t an, int64_t bs, int32_t bn) { return as != bs ? as < bs : an <= bn; }
-
 template <int DT>
 __global__ __launch_bounds__(kWave) void kt_forecast(const ForecastArgs a) {
   __shared__ uint32_t chunk_list[kPreemptChunk];

@@ -29,15 +29,6 @@
 
 namespace kt {
 
-// a page descriptor by value through the constant address space (as admit_page): the wave-uniform fields arrive in SGPRs
-__device__ __forceinline__ PreemptPage preempt_page(const PreemptPage* pages, int k) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return ((const __attribute__((address_space(4))) PreemptPage*)pages)[k];
-#else
-  return pages[k];
-#endif
-}
-
 struct PreemptPagedArgs {
   const PreemptPage* pages;  // [n_pages] in device memory
   int32_t n_pages;

@@ -43,7 +43,7 @@ EXPORTS = [
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
-    "kt_paged_preempt", "kt_debug_match_planes",
+    "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -164,6 +164,28 @@ def paged_preempt(engines, pod_rows, cand_rows, now, on_equal=False, reprieve=Fa
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_preempt: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return prefix[:n], (None if flat is None else flat[:n * m].reshape(n, m))
+
+
+def paged_forecast(engines, pod_rows, instants, on_equal=False, want_verdicts=True):
+    """kt_paged_forecast: kt_forecast_launch + kt_forecast_fetch over the page engines, on the cluster of all resource names ->
+    (first int64 [n], verdicts uint8 [n][n_inst] or None).  Per pod the KT_VERDICT_* of PreFilter once every valid and responsible
+    throttle has been reconciled at each of the strictly ascending ``instants`` on every page, and the first position whose
+    verdict is Success (FORECAST_NONE: none).  At each instant a throttle reads its calculated threshold on every page when any
+    page's reconcile replaces it (or any page has it stored), and keeps its stored status on every page when its reconcile is an
+    error on any page."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    a = np.ascontiguousarray(pod_rows, dtype=np.int64)
+    inst_s = np.ascontiguousarray([int(t[0]) for t in instants], dtype=np.int64)
+    inst_ns = np.ascontiguousarray([int(t[1]) for t in instants], dtype=np.int32)
+    n, m = len(a), len(inst_s)
+    first = np.zeros(max(n, 1), np.int64)
+    flat = np.zeros(max(n * m, 1), np.uint8) if want_verdicts else None
+    rc = lib().kt_paged_forecast(hs, len(engines), n, a.ctypes.data if n else None, m, inst_s.ctypes.data if m else None,
+                                 inst_ns.ctypes.data if m else None, int(on_equal), first.ctypes.data,
+                                 None if flat is None else flat.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_forecast: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return first[:n], (None if flat is None else flat[:n * m].reshape(n, m))
 
 
 def paged_reconcile(engines, now, apply=True):
@@ -288,6 +310,8 @@ def lib():
                                               C.c_int32, C.c_int32, C.c_void_p]
         L.kt_preempt_gangs_reprieve_launch.argtypes = L.kt_preempt_gangs_launch.argtypes
         L.kt_preempt_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kt_paged_forecast.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p]
         L.kt_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.kt_forecast_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.kt_override_instants.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,

@@ -846,6 +846,76 @@ def forecast_of(snap, pod_row, instants, on_equal=False, ctx=None):
     return next((k for k in range(m) if not fails[k]), -1), verdicts_
 
 
+# ---- forecast over pages (kt_paged_forecast): the closed form over a list of page snapshots ----
+def paged_forecast_of(snaps, pod_row, instants, on_equal=False, ctx=None):
+    """kt_paged_forecast for one pod, in closed form over the page snapshots (no GPU) -> (first, verdicts [len(instants)]):
+    ``forecast_of`` on the cluster of all names.  Which throttles affect the pod, the error rows and the pod count are page 0's
+    (the selector side is the same in every page); ``ctx`` is ``paged_preempt_context``'s (any ``now``: only its sums, error
+    marks and match lists are read).  Per affecting throttle:
+    the whole-error rule — its reconcile is an error on some page: the stored status is read on every page at every instant,
+    against the stored calculatedThreshold iff calculatedAt is set on SOME page, else spec.threshold, judged once;
+    the whole-threshold rule — status.calculatedThreshold is compared and replaced as a whole (throttle_controller.go:116-133):
+    at instant t every page computes CalculateThreshold(t) over its names; the throttle reads the calculated threshold on EVERY
+    page iff calculatedAt is set on some page, or on some page the calculated threshold differs by value from the stored one over
+    that page's names or the messages differ (page 0 adds the pod count, the same in every page); otherwise spec.threshold on every
+    page.  A page that holds nothing the pod asks for still takes part: it can replace the threshold for all the others.
+    The pod fails at t iff the count part or some page's name part of the four steps fails.  With one page this is ``forecast_of``."""
+    snap0 = snaps[0]
+    inst = [_instant(t) for t in instants]
+    ctx = paged_preempt_context(snaps, inst[0]) if ctx is None else ctx
+    p, eq, m = int(pod_row), bool(on_equal), len(inst)
+    if not (0 <= p < snap0.n_pods) or not int(snap0.pod_flags[p]) & S.POD_VALID:
+        return -1, [S.VERDICT_ERROR] * m
+    err, affected = affected_throttles(snap0, p)
+    if err:
+        return -1, [S.VERDICT_ERROR] * m
+    req = {(k, d): v for k, s in enumerate(snaps) for d, v in pod_requests(s, p).items() if v != 0}
+    fails = [False] * m
+    for t in affected:
+        th = ctx["thr"][t]
+        f = int(snap0.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _paged_amounts(snaps, "thr_reserved", t)
+        calc_at_any = any(int(s.thr_flags[t]) & S.THR_CALC_AT_NONZERO for s in snaps)
+        if th["error"]:  # the stored status of every page, at every instant
+            used, used_count = _paged_amounts(snaps, "thr_used", t)
+            sth, sth_count = _paged_amounts(snaps, "thr_calc" if calc_at_any else "thr_spec", t)
+            bad = _amount_fails(1, sth_count, bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0,
+                                res_count is not None, res_count or 0, eq3, eq)
+            for (k, d), v in req.items():
+                flg = int(snaps[k].thr_thrl_flag[t]) & int(snaps[k].thr_thrl_has[t])
+                bad = bad or _amount_fails(v, sth.get((k, d)), bool(flg >> d & 1), (k, d) in used, used.get((k, d), 0), (k, d) in res,
+                                           res.get((k, d), 0), eq3, eq)
+            if bad:
+                fails = [True] * m
+                break
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        u_hc = pods > 0
+        spec, spec_count = _paged_amounts(snaps, "thr_spec", t)
+        for j, at in enumerate(inst):
+            calc, cc, differs = {}, None, False
+            for k, s in enumerate(snaps):
+                names, count, any_err = _calculated_threshold(s, t, at)
+                stored, stored_count = _amount_dict(s.thr_calc, t, s.D)
+                fp = int(s.thr_spec_msgs_fp[t]) if any_err else 0
+                differs = differs or names != stored or int(s.thr_status_msgs_fp[t]) != fp
+                if k == 0:  # the count is the same in every page
+                    cc = count
+                    differs = differs or count != stored_count
+                calc.update({(k, d): v for d, v in names.items()})
+            rd, rd_count = (calc, cc) if calc_at_any or differs else (spec, spec_count)
+            bad = _amount_fails(1, rd_count, cc is not None and u_hc and pods >= cc, u_hc, pods, res_count is not None, res_count or 0, eq3, eq)
+            for kd, v in req.items():
+                u_pr = cnt.get(kd, 0) > 0
+                cv = calc.get(kd)
+                bad = bad or _amount_fails(v, rd.get(kd), cv is not None and u_pr and val.get(kd, 0) >= cv, u_pr, val.get(kd, 0), kd in res,
+                                           res.get(kd, 0), eq3, eq)
+            fails[j] = fails[j] or bad
+    verdicts_ = [S.VERDICT_BLOCK if b else S.VERDICT_ALLOW for b in fails]
+    return next((k for k in range(m) if not fails[k]), -1), verdicts_
+
+
 class PagedEngine:
     """One HIP engine per page of a ``ClusterState.build_pages()`` result; reconcile and check run on every page (the
     selector scan is repeated per page: the price of more than 16 resource names) and come back combined."""
@@ -912,12 +982,15 @@ class PagedEngine:
         return E.paged_preempt(self.engines, pod_rows, cand_rows, now, on_equal=on_equal, reprieve=reprieve, want_victims=want_victims)
 
     def forecast(self, pod_rows, instants, on_equal=False, want_verdicts=True):
-        """kt_forecast_launch through the one engine of a cluster that fits a page; the forecast has no paged form (more than
-        KT_MAX_DIMS resource names): refused with KT_ERR_UNSUPPORTED, nothing is launched."""
-        if len(self.engines) != 1:
-            raise E.EngineError(-7, f"forecast: the cluster runs on {len(self.engines)} pages (more than {S.KT_MAX_DIMS} resource "
-                                    "names); the forecast query has no paged form")
-        return self.engines[0].forecast(pod_rows, instants, on_equal, want_verdicts)
+        """The first of the strictly ascending ``instants`` at which each pod of ``pod_rows`` passes PreFilter, over every page's
+        names, through kt_paged_forecast -> (first [n], verdicts [n][n_inst] or None).  A dry run: nothing stored changes on any
+        page."""
+        return E.paged_forecast(self.engines, pod_rows, instants, on_equal=on_equal, want_verdicts=want_verdicts)
+
+    def override_instants(self, from_, until, cap=None):
+        """kt_override_instants of page 0 -> ([(seconds, nanoseconds)], total): every page holds every override's times and parse
+        flags, so the instants are the same on every page."""
+        return self.engines[0].override_instants(from_, until, cap)
 
     def fetch_reserved(self) -> list:
         """Reserved amounts per throttle row, put together by resource NAME from the pages (like combine_reconcile):
