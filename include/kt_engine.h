@@ -459,8 +459,8 @@ int32_t kt_preempt_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_r
  *      one pending preempt result, as kt_preempt_reprieve_launch does: a later launch of any of the preempt calls replaces it.
  *      kt_preempt_fetch after a gang launch answers KT_ERR_NOT_READY, and so does kt_preempt_gangs_fetch after a plain launch; a
  *      pending kt_forecast_launch stays fetchable.  kt_preempt_gangs_fetch synchronises.
- *      Out of scope: the paged form, several ranks (the reprieve pass that shrinks a gang's victim set further is
- *      kt_preempt_gangs_reprieve_launch below). ------------------------------------------------------------------------- */
+ *      More than KT_MAX_DIMS resource names: kt_paged_preempt_gangs.  Out of scope: several ranks (the reprieve pass that shrinks
+ *      a gang's victim set further is kt_preempt_gangs_reprieve_launch below). ------------------------------------------------- */
 int32_t kt_preempt_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
                                 const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream);
 int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefix /* [n_gangs], nullable */,
@@ -492,7 +492,7 @@ int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefi
  *      alone", n == 0 only with n_gangs == 0, and the slot rules are those of kt_preempt_gangs_launch.  The result is the one
  *      pending gang result, fetched with kt_preempt_gangs_fetch: a later launch of any of the four preempt calls replaces it; a
  *      pending kt_forecast_launch stays fetchable.
- *      Out of scope: the paged form, several ranks. --------------------------------------------------------------------- */
+ *      More than KT_MAX_DIMS resource names: kt_paged_preempt_gangs with KT_PREEMPT_REPRIEVE.  Out of scope: several ranks. -- */
 int32_t kt_preempt_gangs_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
                                          const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream);
 /* ---- forecast: the first instant at which a blocked pod passes — the one axis no other query looks along.
@@ -695,11 +695,60 @@ int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, c
  * stored with KT_RECONCILE_APPLY stays stored); a pending kt_aggregate_launch of any page keeps its sums.  The call is a dry
  * run: stored status and reserved amounts of no page change.  A device error after the first launch is returned once the
  * stream has drained; no page keeps a pending result.
- * Out of scope: the gang forms over pages, several ranks. */
+ * The gang forms over pages: kt_paged_preempt_gangs.  Out of scope: several ranks. */
 #define KT_PREEMPT_REPRIEVE 0x1u
 int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_cand,
                          const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, uint32_t flags,
                          int64_t* out_prefix /* [n], nullable */, uint8_t* out_victims /* [n][n_cand], nullable */);
+/* kt_preempt_gangs_launch (with KT_PREEMPT_REPRIEVE in `flags`: kt_preempt_gangs_reprieve_launch) + kt_preempt_gangs_fetch over the
+ * pages, synchronous: their definition, word for word, on the cluster of ALL names — S_k, the in-order admission of the members
+ * with Reserve on every throttle that affects the member, the list cut m_eff, the error rows, KT_PREEMPT_NONE, the victim mask,
+ * the blocker and the reprieve walk.  n_pages == 1 returns byte for byte what the single-engine calls return; a gang of one pod
+ * answers what kt_paged_preempt answers for that pod, plus the blocker.  The answer is NOT a combination of per-page calls, for
+ * kt_paged_preempt's three reasons and one of the gang's own: an admitted member reserves on EVERY page, so neither the maximum of
+ * the pages' own gang prefixes nor the maximum of the members' own paged prefixes is the gang's.  What pages add:
+ *   - ONE check of page 0 over pod_rows ++ cand_rows yields which throttles affect which member, which candidates are counted and
+ *     matched, the error rows, m_eff and "a member is an Error or invalid";
+ *   - the pod count is page 0's: the threshold's, `used`'s, the calculated threshold's and the stored and running reserved count;
+ *     a name part is judged on its own page;
+ *   - the gang passes in S_k iff, for every throttle of the union of the members' affecting throttles, the in-order member walk
+ *     passes on page 0 with the count part and passes the name part on every page;
+ *   - each page carries its own running reserved prefix, from that page's stored reserved row: a member the throttle affects adds
+ *     its value of every name of that page it carries, the presence of ALL that page's names it carries (zero-valued ones
+ *     included) and count + 1.  Judging member j with the reservations of all earlier affected members stays exact: the gang
+ *     passes only if every member passes every page;
+ *   - stored and use-calc are kt_paged_preempt's whole-throttle facts (an OR over the pages); a throttle that keeps its stored
+ *     status reads the STORED calculated threshold on every page, never a page's fresh one;
+ *   - out_blocker[g]: the minimum, over throttles AND pages, of the first stopped queue position in S_0 (an Error or invalid
+ *     member counts as stopped); -1 when out_prefix[g] == 0;
+ *   - out_victims[g][j] = 1 iff j < prefix, c_j is counted and a throttle affecting some member matches c_j (decided once, on
+ *     page 0); with the flag, what the reprieve walk leaves: the joint judge is an in-order admission of the gang over every page,
+ *     one verdict per candidate, and a candidate that is put back is put back on every page.
+ * On page 0's stream, in order: that check; for every page its dense aggregate (beside its partial buffer) and its dry finalize
+ * at `now`; the copy of the gang offsets and of the page descriptors; one launch of kt_preempt_gangs_paged; with the flag one
+ * launch of kt_preempt_gangs_reprieve_paged (csrc/kt_kernels_preempt_gangs_paged.hip), whose list state is sized with the sum of
+ * the pages' names (in LDS, beyond that in a workspace of page 0); the copies out.  out_prefix [n_gangs], out_victims
+ * [n_gangs][n_cand] and out_blocker [n_gangs] are all nullable.
+ * Refused before anything is allocated or launched, and before any page's check slot, reconcile report or result buffer is
+ * touched: what kt_paged_preempt refuses about the page set (different throttle-row counts, an engine named twice:
+ * KT_ERR_INVALID_ARGUMENT; different devices: KT_ERR_UNSUPPORTED), about the flags (KT_ERR_INVALID_ARGUMENT) and about every
+ * page's engine (a KT_VARIANT_INCREMENTAL engine, an exchange world above 1, a `used` wider than int64: KT_ERR_UNSUPPORTED — as
+ * there, the one thing that may run first is a page's kernel that sums the |requests|), and what kt_preempt_gangs_launch refuses
+ * about its arguments (every gang_off defect, a pod twice in one gang, a member that is also a candidate, a candidate twice, a
+ * missing array, n_cand < 0: KT_ERR_INVALID_ARGUMENT; a row that no page holds, n, n_cand or their sum times throttle_rows above
+ * 2^31: KT_ERR_OUT_OF_RANGE).  n == 0 is allowed only with n_gangs == 0: KT_OK, nothing is launched; n_cand == 0 answers 0 or
+ * KT_PREEMPT_NONE per gang, with blockers.  Locking (every page exclusively, in address order) and ordering are kt_paged_admit's.
+ * Slots are kt_paged_preempt's: the call uses page 0's check slot and page 0's preempt result buffers — the results are handed
+ * out by the call, so afterwards no preempt result is pending on page 0 for either fetch (kt_preempt_fetch and
+ * kt_preempt_gangs_fetch answer KT_ERR_NOT_READY) while a pending kt_forecast_launch of page 0 stays fetchable; every page's
+ * pending reconcile report is dropped; a pending kt_aggregate_launch of any page keeps its sums.  The call is a dry run: stored
+ * status and reserved amounts of no page change.  A device error after the first launch is returned once the stream has drained;
+ * no page keeps a pending result.
+ * Out of scope: several ranks. */
+int32_t kt_paged_preempt_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                               const int64_t* gang_off, int64_t n_cand, const int64_t* cand_rows, int64_t now_s, int32_t now_ns,
+                               int32_t on_equal, uint32_t flags, int64_t* out_prefix /* [n_gangs], nullable */,
+                               uint8_t* out_victims /* [n_gangs][n_cand], nullable */, int64_t* out_blocker /* [n_gangs], nullable */);
 /* kt_forecast_launch + kt_forecast_fetch over the pages, synchronous: their definition on the cluster of ALL names — R_k, the
  * verdict bytes, KT_FORECAST_NONE, the error rows.  n_pages == 1 returns byte for byte what kt_forecast_launch +
  * kt_forecast_fetch return.  The answer is NOT a combination of per-page calls: status.calculatedThreshold is compared and
@@ -743,7 +792,7 @@ int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, co
  * every page's pending reconcile report is dropped (a status stored with KT_RECONCILE_APPLY stays stored); a pending
  * kt_aggregate_launch of any page keeps its sums.  The call is a dry run: stored status and reserved amounts of no page change.
  * A device error after the first launch is returned once the stream has drained; no page keeps a pending result.
- * Out of scope: the gang preemption forms over pages, several ranks. */
+ * Out of scope: several ranks. */
 int32_t kt_paged_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
                           const int32_t* inst_ns, int32_t on_equal, int64_t* out_first /* [n], nullable */,
                           uint8_t* out_verdicts /* [n][n_inst], nullable */);

@@ -918,7 +918,7 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
 // ---------------------------------------------------------------------------------------------------
 // preempt over pages: kt_preempt_launch / kt_preempt_reprieve_launch on the cluster of all names (kt_kernels_preempt_paged.hip)
 // ---------------------------------------------------------------------------------------------------
-// How a synchronous paged call (kt_paged_preempt, kt_paged_forecast) ends once it has launched on page 0's stream s: the stream is
+// How a synchronous paged call (kt_paged_preempt, kt_paged_preempt_gangs, kt_paged_forecast) ends once it has launched on page 0's stream s: the stream is
 // drained, pages 1.. get back the last_stream they came with (`last`: nothing of the call stays pending on any page), and a
 // device error that shows only now is returned in KT_OK's place
 static int32_t paged_finish(const char* what, kt_engine* const* pages, int32_t n_pages, hipStream_t s, const std::vector<hipStream_t>& last,
@@ -1159,6 +1159,135 @@ int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefi
   if (out_blocker) KT_HIP(e, hipMemcpyAsync(out_blocker, e->d_preempt_blocker.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
   KT_HIP(e, hipStreamSynchronize(s));
   return KT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// preempt, for gangs, over pages: kt_preempt_gangs_launch / kt_preempt_gangs_reprieve_launch on the cluster of all names
+// (kt_kernels_preempt_gangs_paged.hip)
+// ---------------------------------------------------------------------------------------------------
+int32_t kt_paged_preempt_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                               int64_t n_cand, const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, uint32_t flags,
+                               int64_t* out_prefix, uint8_t* out_victims, int64_t* out_blocker) {
+  if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  PageLocks locks;
+  int32_t rc = paged_lock("paged preempt gangs", pages, n_pages, n, locks);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = pages[0];
+  // ---- refusals: nothing is allocated or launched and no slot of any page is touched before the last of them
+  if (flags & ~KT_PREEMPT_REPRIEVE) return e0->fail(KT_ERR_INVALID_ARGUMENT, "paged preempt gangs: flags = 0x%x", flags);
+  const bool reprieve = (flags & KT_PREEMPT_REPRIEVE) != 0;
+  if ((rc = gangs_valid(e0, n, n_gangs, gang_off)) != KT_OK) return rc;
+  if (n_cand < 0) return e0->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: n_cand = %lld", (long long)n_cand);
+  if ((n > 0 && !pod_rows) || (n_cand > 0 && !cand_rows)) return e0->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod_rows / cand_rows missing");
+  if ((rc = paged_same_cluster("paged preempt gangs", pages, n_pages, n, pod_rows)) != KT_OK) return rc;  // (the rows are range-checked
+  if ((rc = paged_same_cluster("paged preempt gangs", pages, n_pages, n_cand, cand_rows)) != KT_OK) return rc;  //  in place)
+  {
+    std::vector<int64_t> sorted(cand_rows, cand_rows + n_cand);
+    std::sort(sorted.begin(), sorted.end());
+    for (int64_t j = 1; j < n_cand; ++j)
+      if (sorted[(size_t)j] == sorted[(size_t)j - 1])
+        return e0->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod row %lld is a candidate twice", (long long)sorted[(size_t)j]);
+    for (int64_t i = 0; i < n; ++i)
+      if (std::binary_search(sorted.begin(), sorted.end(), pod_rows[i]))
+        return e0->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod row %lld is a member and a candidate", (long long)pod_rows[i]);
+    // gangs are alternatives: a pod may be in several of them, but not twice in one (it would reserve twice)
+    for (int64_t g = 0; g < n_gangs; ++g) {
+      sorted.assign(pod_rows + gang_off[g], pod_rows + gang_off[g + 1]);
+      std::sort(sorted.begin(), sorted.end());
+      for (size_t j = 1; j < sorted.size(); ++j)
+        if (sorted[j] == sorted[j - 1])
+          return e0->fail(KT_ERR_INVALID_ARGUMENT, "preempt gangs: pod row %lld is in gang %lld twice", (long long)sorted[j], (long long)g);
+    }
+  }
+  const int32_t T = e0->thr_rows_hi;
+  if ((double)n * (double)T > 2147483648.0 || (double)n_cand * (double)T > 2147483648.0 || ((double)n + (double)n_cand) * (double)T > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "preempt gangs: (n + n_cand) x throttle_rows = (%lld + %lld) x %d exceeds 2^31 matrix bytes", (long long)n,
+                    (long long)n_cand, T);
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if (e->incremental) return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: page %d: not for KT_VARIANT_INCREMENTAL engines", k);
+    if (e->exchange_world > 1)
+      return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: page %d exchanges partials with %d ranks (one rank only)", k, e->exchange_world);
+    if (e->wide && e->req_sums_valid)
+      return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: `used` of page %d is wider than int64 (kt_preempt_gangs_paged reads int64 sums)", k);
+  }
+  if (n == 0) return KT_OK;  // (no gangs) nothing is launched
+  hipStream_t s = nullptr;
+  if ((rc = paged_order(pages, n_pages, &s)) != KT_OK) return rc;
+  if ((rc = ensure_ready(e0, s)) != KT_OK) return rc;
+  // the |request| sums probe of every page where the sums are not known, before the check slot, a reconcile report or a result
+  // buffer of any page is touched (as kt_paged_preempt)
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if ((rc = request_sums_in_range(e, s)) != KT_OK) return rc;
+    if (e->wide)
+      return e->fail(KT_ERR_UNSUPPORTED, "preempt gangs: `used` of page %d is wider than int64 (kt_preempt_gangs_paged reads int64 sums)", k);
+  }
+  // ---- from here on the call owns page 0's check slot and preempt result and every page's reconcile report
+  e0->preempt_ready = false;
+  if (!e0->preempt_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->preempt_pages_ev, hipEventDisableTiming));
+  KT_HIP(e0, hipEventSynchronize(e0->preempt_pages_ev));  // the previous call's copy has read h_preempt_pages
+  e0->h_preempt_pages.resize((size_t)n_pages);
+  for (int32_t k = 0; k < n_pages; ++k)  // (D alone is read before the launches below fill in the rest)
+    e0->h_preempt_pages[(size_t)k].pg = kt::AdmitPage{pages[k]->pods.flags, pages[k]->pods.req, pages[k]->tt, pages[k]->D, pages[k]->pods.DS, 0u, 0u, 0u};
+  const size_t vic = (size_t)n_gangs * (size_t)n_cand;
+  const size_t ws =
+      reprieve && n_cand > 0 ? kt::reprieve_paged_ws_bytes(T, e0->h_preempt_pages.data(), n_pages, n_gangs, e0->reprieve_lds_cap_limit) : 0;
+  if (e0->d_preempt_prefix.cap < (size_t)n_gangs || e0->d_preempt_victims.cap < vic + 1 || e0->d_preempt_blocker.cap < (size_t)n_gangs ||
+      e0->d_preempt_gang_off.cap < (size_t)n_gangs + 1 || (ws != 0 && e0->d_reprieve_ws.cap < ws)) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_preempt_gangs_launch)
+    if (e0->last_stream) KT_HIP(e0, hipStreamSynchronize(e0->last_stream));
+    KT_HIP(e0, e0->d_preempt_prefix.reserve((size_t)n_gangs));
+    KT_HIP(e0, e0->d_preempt_victims.reserve(vic + 1));
+    KT_HIP(e0, e0->d_preempt_blocker.reserve((size_t)n_gangs));
+    KT_HIP(e0, e0->d_preempt_gang_off.reserve((size_t)n_gangs + 1));
+    if (ws != 0) KT_HIP(e0, e0->d_reprieve_ws.reserve(ws));
+  }
+  KT_HIP(e0, e0->d_preempt_pages.reserve(sizeof(kt::PreemptPage) * (size_t)n_pages));
+  // Everything below runs on page 0's stream.  A failure after the first launch drains that stream before it is returned, and
+  // pages 1.. get their own stream back as last_stream: nothing of this call stays pending on any page.
+  std::vector<hipStream_t> last((size_t)n_pages);
+  for (int32_t k = 0; k < n_pages; ++k) last[(size_t)k] = pages[k]->last_stream;
+  auto finish = [&](int32_t code) -> int32_t { return paged_finish("paged preempt gangs", pages, n_pages, s, last, code); };
+  // ONE check of page 0 over members ++ candidates: which throttles match which pod, and the error rows
+  std::vector<int64_t> rows((size_t)(n + n_cand));
+  std::copy(pod_rows, pod_rows + n, rows.begin());
+  std::copy(cand_rows, cand_rows + n_cand, rows.begin() + n);
+  const bool forecast_was_ready = e0->forecast_ready;  // its result lives in buffers this call does not write: it stays fetchable
+  rc = check_launch_locked(e0, n + n_cand, rows.data(), on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e0->check_ready = false;  // the slot holds this call's rows (as with kt_affected_pods): a pending kt_check_launch is gone
+  e0->forecast_ready = forecast_was_ready;
+  if (rc != KT_OK) return finish(rc);
+  // every page: its dense aggregate beside its partial buffer and its dry finalize at `now` (its reconcile report is dropped)
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if ((rc = preempt_reconcile_locked(e, now_s, now_ns, s)) != KT_OK) return finish(rc);
+    kt::PreemptPage& pp = e0->h_preempt_pages[(size_t)k];
+    pp.partial = e->d_preempt_partial.p, pp.calc = e->d_out_calc.tab(), pp.calc_updated = e->d_out_calc_updated.p, pp.error = e->d_out_error.p;
+  }
+  hipError_t herr = hipSuccess;
+  // the offsets travel on the same stream (the call is synchronous: the caller's memory outlives the copy)
+  if ((herr = hipMemcpyAsync(e0->d_preempt_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged preempt gangs: copy of the gang offsets: %s", hipGetErrorString(herr)));
+  if (!kt::launch_preempt_gangs_paged(e0->h_preempt_pages.data(), n_pages, (kt::PreemptPage*)e0->d_preempt_pages.p, e0->preempt_pages_ev, n, n_cand,
+                                      e0->d_rows.p, n_gangs, e0->d_preempt_gang_off.p, T, on_equal != 0, e0->d_status.p, e0->d_summary.p,
+                                      e0->d_preempt_prefix.p, e0->d_preempt_victims.p, e0->d_preempt_blocker.p, s, &herr))
+    return finish(e0->fail(KT_ERR_DEVICE, "paged preempt gangs: copy of the page descriptors: %s", hipGetErrorString(herr)));
+  if ((herr = hipGetLastError()) != hipSuccess) return finish(e0->fail(KT_ERR_DEVICE, "paged preempt gangs: %s", hipGetErrorString(herr)));
+  if (reprieve) {
+    kt::launch_preempt_gangs_reprieve_paged(e0->h_preempt_pages.data(), n_pages, (const kt::PreemptPage*)e0->d_preempt_pages.p, n, n_cand, e0->d_rows.p,
+                                            n_gangs, e0->d_preempt_gang_off.p, T, on_equal != 0, e0->d_status.p, e0->d_preempt_prefix.p,
+                                            e0->d_preempt_victims.p, ws != 0 ? e0->d_reprieve_ws.p : nullptr, e0->reprieve_lds_cap_limit, s);
+    if ((herr = hipGetLastError()) != hipSuccess) return finish(e0->fail(KT_ERR_DEVICE, "paged preempt gangs: %s", hipGetErrorString(herr)));
+  }
+  e0->last_stream = s;
+  if (out_prefix && (herr = hipMemcpyAsync(out_prefix, e0->d_preempt_prefix.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged preempt gangs: %s", hipGetErrorString(herr)));
+  if (out_victims && n_cand && (herr = hipMemcpyAsync(out_victims, e0->d_preempt_victims.p, vic, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged preempt gangs: %s", hipGetErrorString(herr)));
+  if (out_blocker && (herr = hipMemcpyAsync(out_blocker, e0->d_preempt_blocker.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged preempt gangs: %s", hipGetErrorString(herr)));
+  return finish(KT_OK);  // (synchronises s; the results have been handed out: no preempt result is pending on page 0)
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -368,7 +368,7 @@ struct kt_engine {
   DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's and kt_preempt_gangs_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
   bool preempt_ready = false;
   int64_t preempt_n = 0, preempt_m = 0;
-  // kt_paged_preempt and kt_paged_forecast (on page 0): the page descriptors of kt_preempt_paged / kt_forecast_paged, on the device
+  // kt_paged_preempt, kt_paged_preempt_gangs and kt_paged_forecast (on page 0): the page descriptors of the paged kernels, on the device
   // and — the source of an asynchronous copy, under the rule of h_admit_pages with preempt_pages_ev in admit_pages_ev's place —
   // on the host
   DevBuf<uint8_t> d_preempt_pages;

@@ -25,42 +25,12 @@
 //   throttle rows — bit 31 of a throttle row caches its use-calc fact).  The judge of a candidate loops over the pages inside the
 //   lane before the ONE ballot; the commit pass updates every page's fields.  IN_LDS = true: no list can outgrow LDS (throttle
 //   rows <= capacity) and the HBM path is not compiled in; false: the choice is made per preemptor, as kt_preempt_reprieve does.
-#include "kt_admit_common.h"
+#include "kt_preempt_paged_common.h"
 
 namespace kt {
 
-struct PreemptPagedArgs {
-  const PreemptPage* pages;  // [n_pages] in device memory
-  int32_t n_pages;
-  const int64_t* rows;       // [n + m] pod table rows (the same in every page): the preemptors, then the candidates
-  int64_t n, m;
-  const uint8_t* status;     // [n + m][T] page 0's check
-  const uint64_t* summary;   // [n + m]
-  int64_t* prefix;           // [n] out
-  uint8_t* victims;          // [n][m] out (and the per-position verdict bits while the kernel runs)
-  int32_t T, on_equal;
-};
-
-// what kt_preempt's helpers read, for page k
-__device__ __forceinline__ PreemptArgs preempt_page_args(const PreemptPagedArgs& a, int k) {
-  const PreemptPage pp = preempt_page(a.pages, k);
-  PreemptArgs r;
-  r.pg = pp.pg, r.rows = a.rows, r.n = a.n, r.m = a.m, r.status = a.status, r.summary = a.summary, r.partial = pp.partial, r.calc = pp.calc;
-  r.calc_updated = pp.calc_updated, r.error = pp.error, r.prefix = a.prefix, r.victims = a.victims, r.T = a.T, r.on_equal = a.on_equal;
-  return r;
-}
-
-// the facts of throttle t that hold for the throttle as a whole: the OR over the pages
-__device__ __forceinline__ void paged_thr_facts(const PreemptPage* pages, int n_pages, uint32_t t, bool* stored, bool* use_calc) {
-  bool st = false, uc = false;
-  for (int k = 0; k < n_pages; ++k) {
-    const PreemptPage pp = preempt_page(pages, k);
-    const uint32_t tf = pp.pg.tt.flags[t];
-    st |= preempt_row_stored(tf, pp.error[t]);
-    uc |= (tf & kThrCalcAtNonzero) != 0 || pp.calc_updated[t] != 0;
-  }
-  *stored = st, *use_calc = uc;
-}
+// (PreemptPagedArgs, preempt_page_args, paged_thr_facts, ReprievePagedArgs and reprieve_paged_list are kt_preempt_paged_common.h's:
+// the gang forms over pages read them too)
 
 template <int DT>
 __global__ __launch_bounds__(kWave) void kt_preempt_paged(const PreemptPagedArgs a) {
@@ -211,66 +181,6 @@ bool launch_preempt_paged(const PreemptPage* pages, int n_pages, PreemptPage* pa
 }
 
 // ---- the reprieve pass -------------------------------------------------------------------------------------------------------
-struct ReprievePagedArgs {
-  const PreemptPage* pages;  // [n_pages] in device memory, as the prefix kernel read them
-  int32_t n_pages, F;        // F: the flat name count, the sum of the pages' D
-  const int64_t* rows;       // [n + m]
-  int64_t n, m;
-  const uint8_t* status;     // [n + m][T]
-  const int64_t* prefix;     // [n] as kt_preempt_paged left it
-  uint8_t* victims;          // [n][m] in: the prefix mask, out: the reprieved set
-  unsigned char* ws;         // gridDim.x slots of ws_slot bytes (nullptr: T <= lds_cap)
-  size_t ws_slot;
-  int32_t T, on_equal;
-  uint32_t lds_cap;          // entries the LDS state holds
-};
-
-constexpr uint32_t kPagedUseCalc = 0x80000000u;  // bit 31 of a list entry's throttle row: it reads the calculated threshold
-
-// The affecting throttles that are reconciled on every page: counted (GATHER = false) or gathered into the state with every page's
-// totals; returns the wave-uniform list length
-template <int DT, bool GATHER, class ST>
-__device__ __forceinline__ uint32_t reprieve_paged_list(const ReprievePagedArgs& a, const uint8_t* row, lds_u32wp list, ST* st, uint32_t lane) {
-  const int T = a.T;
-  uint32_t n_list = 0;
-  for (int c0 = 0; c0 < T; c0 += kPreemptChunk) {
-    bool err_c = false;  // (prefix > 0: the row holds no error byte)
-    const uint32_t n_c = admit_affected_chunk(row, T, c0, list, (uint32_t)kPreemptChunk, 0u, &err_c);
-    __syncthreads();  // (one wave: the list's entries are read by other lanes than wrote them)
-    for (uint32_t a0 = 0; a0 < n_c; a0 += kWave) {
-      const uint32_t ai = a0 + lane;
-      const uint32_t t = ai < n_c ? list[ai] : 0u;
-      bool stored = false, use_calc = false;
-      if (ai < n_c) paged_thr_facts(a.pages, a.n_pages, t, &stored, &use_calc);
-      const bool keep = ai < n_c && !stored;
-      const uint64_t mk = __ballot(keep);
-      if constexpr (GATHER) {
-        const uint32_t e = n_list + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-        if (keep && e < st->cap) {
-          st->tl[e] = t | (use_calc ? kPagedUseCalc : 0u);
-          uint32_t fb = 0;  // the page's first flat name
-          for (int k = 0; k < a.n_pages; ++k) {
-            const PreemptPage pp = preempt_page(a.pages, k);
-            const int D = pp.pg.D;
-            const unsigned long long* prow = pp.partial + (size_t)t * partial_stride(D);
-            if (k == 0) st->pods[e] = (int64_t)prow[partial_off_pods(D)];
-#pragma unroll
-            for (int d = 0; d < DT; ++d) {
-              if (d >= D) continue;
-              st->uv[(size_t)(fb + d) * st->cap + e] = (int64_t)prow[d];
-              st->uc[(size_t)(fb + d) * st->cap + e] = (uint32_t)prow[partial_off_presence(D) + d];
-            }
-            fb += (uint32_t)D;
-          }
-        }
-      }
-      n_list += (uint32_t)__popcll(mk);
-    }
-    __syncthreads();  // the next chunk rewrites the chunk list
-  }
-  return n_list;
-}
-
 // Candidate row cb (status-matrix row crow) against the list, for preemptor row p.  JUDGE: would some (throttle, amount) pair of some
 // page stop the preemptor with the candidate back (per lane: ballot it), nothing is written.  Otherwise the candidate's amounts
 // are added (SIGN = 1) to or taken off (SIGN = -1) the state of every entry whose throttle matches it, on every page.
@@ -339,13 +249,18 @@ __device__ __forceinline__ bool reprieve_paged_step(const ReprievePagedArgs& a, 
   return fail;
 }
 
+// one chunk of preemptor i's own matrix row, for reprieve_paged_list
+__device__ __forceinline__ auto preemptor_chunk(const ReprievePagedArgs& a, int64_t i) {
+  return [&a, i](int c0, lds_u32wp l, bool* err) { return admit_affected_chunk(a.status + i * a.T, a.T, c0, l, (uint32_t)kPreemptChunk, 0u, err); };
+}
+
 template <int DT, bool IN_LDS>
 __device__ __forceinline__ void reprieve_paged_walk(const ReprievePagedArgs& a, ReprieveState<IN_LDS> st, lds_u32wp list, int64_t i, int64_t k,
                                                     uint32_t lane) {
   const int T = a.T;
   const int64_t n = a.n, p = a.rows[i];
   uint8_t* vic = a.victims + i * a.m;
-  const uint32_t n_list = reprieve_paged_list<DT, true>(a, a.status + i * T, list, &st, lane);
+  const uint32_t n_list = reprieve_paged_list<DT, true>(a, preemptor_chunk(a, i), list, &st, lane);
   __syncthreads();  // an entry is owned by lane (entry mod 64) from here on; another lane wrote it
   // the masked positions of one block of 64 candidates: their rows come in with one load
   auto block = [&](int64_t q0, int64_t& c) -> uint64_t {
@@ -393,7 +308,7 @@ __global__ __launch_bounds__(kWave) void kt_preempt_reprieve_paged(const Repriev
     if constexpr (IN_LDS) {  // (T <= lds_cap: no list outgrows LDS, nothing is counted first)
       reprieve_paged_walk<DT, true>(a, ReprieveState<true>((KT_LDS unsigned char*)state, a.lds_cap, a.F), list, i, k, lane);
     } else {
-      const uint32_t n_list = reprieve_paged_list<DT, false, void>(a, a.status + i * a.T, list, nullptr, lane);
+      const uint32_t n_list = reprieve_paged_list<DT, false, void>(a, preemptor_chunk(a, i), list, nullptr, lane);
       if (n_list <= a.lds_cap)
         reprieve_paged_walk<DT, true>(a, ReprieveState<true>((KT_LDS unsigned char*)state, a.lds_cap, a.F), list, i, k, lane);
       else if (a.ws)  // (the launcher gives a workspace whenever T > lds_cap; n_list <= T)
@@ -403,11 +318,6 @@ __global__ __launch_bounds__(kWave) void kt_preempt_reprieve_paged(const Repriev
   }
 }
 
-static int preempt_paged_names(const PreemptPage* pages, int n_pages) {
-  int F = 0;
-  for (int k = 0; k < n_pages; ++k) F += pages[k].pg.D;
-  return F > 0 ? F : 1;
-}
 size_t reprieve_paged_ws_bytes(int T, const PreemptPage* pages, int n_pages, int64_t n, uint32_t lds_cap_limit) {
   return reprieve_ws_bytes(T, preempt_paged_names(pages, n_pages), n, lds_cap_limit);
 }

@@ -163,6 +163,19 @@ size_t reprieve_paged_ws_bytes(int T, const PreemptPage* pages, int n_pages, int
 void launch_preempt_reprieve_paged(const PreemptPage* pages, int n_pages, const PreemptPage* pages_dev, int64_t n, int64_t m, const int64_t* rows_dev,
                                    int T, bool on_equal, const uint8_t* status, const int64_t* prefix, uint8_t* victims, void* ws,
                                    uint32_t lds_cap_limit, hipStream_t s);
+// the gang forms over the same descriptors (kt_kernels_preempt_gangs_paged.hip): one wave per gang.  rows_dev [n + m]: the members of
+// all gangs, then the candidates; gang g is the queue positions [gang_off_dev[g], gang_off_dev[g + 1]) (device memory); status /
+// summary: ONE check of page 0 over those rows.  launch_preempt_gangs_paged copies the descriptors and records pages_copied as
+// launch_preempt_paged does; prefix [n_gangs], victims [n_gangs][m] and blocker [n_gangs] out, on page 0.  false: the copy failed
+// (*hip_err).  launch_preempt_gangs_reprieve_paged, behind it on the same stream, reads the same device descriptors; LDS capacity
+// and workspace as for launch_preempt_reprieve_paged, sized with n_gangs in the place of n
+bool launch_preempt_gangs_paged(const PreemptPage* pages, int n_pages, PreemptPage* pages_dev, hipEvent_t pages_copied, int64_t n, int64_t m,
+                                const int64_t* rows_dev, int64_t n_gangs, const int64_t* gang_off_dev, int T, bool on_equal, const uint8_t* status,
+                                const uint64_t* summary, int64_t* prefix, uint8_t* victims, int64_t* blocker, hipStream_t s, hipError_t* hip_err);
+void launch_preempt_gangs_reprieve_paged(const PreemptPage* pages, int n_pages, const PreemptPage* pages_dev, int64_t n, int64_t m,
+                                         const int64_t* rows_dev, int64_t n_gangs, const int64_t* gang_off_dev, int T, bool on_equal,
+                                         const uint8_t* status, const int64_t* prefix, uint8_t* victims, void* ws, uint32_t lds_cap_limit,
+                                         hipStream_t s);
 // the first instant at which a pod passes (kt_kernels_forecast.hip): one wave per pod, lane = instant position.  rows_dev [n];
 // inst_s / inst_ns [m] in device memory, strictly ascending; status / summary: ONE check over those rows; partial: aggregate rows
 // with exact per-name contributor counts; error: the error bytes of a dry finalize; first [n] and verdicts [n][m] out

@@ -43,7 +43,7 @@ EXPORTS = [
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
-    "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes",
+    "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_paged_preempt_gangs",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -164,6 +164,29 @@ def paged_preempt(engines, pod_rows, cand_rows, now, on_equal=False, reprieve=Fa
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_preempt: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return prefix[:n], (None if flat is None else flat[:n * m].reshape(n, m))
+
+
+def paged_preempt_gangs(engines, pod_rows, gang_off, cand_rows, now, on_equal=False, reprieve=False, want_victims=True):
+    """kt_paged_preempt_gangs: kt_preempt_gangs_launch (``reprieve``: kt_preempt_gangs_reprieve_launch) over the page engines, on the
+    cluster of all resource names -> (prefix int64 [n_gangs], victims uint8 [n_gangs][n_cand] or None, blocker int64 [n_gangs]).
+    Per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` the smallest k for which an in-order admission — PreFilter, and on Success
+    Reserve on every page — admits every member once the candidates ``cand_rows[:k]`` are gone and every responsible throttle has
+    been reconciled at ``now`` on every page; 0: the gang already passes; PREEMPT_NONE: no prefix helps.  blocker: the queue
+    position of the first member that is not Success with nothing deleted, over every page (-1 when prefix == 0)."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    a = np.ascontiguousarray(pod_rows, dtype=np.int64)
+    c = np.ascontiguousarray(cand_rows, dtype=np.int64)
+    g = _gang_offsets(gang_off)
+    n, m, ng = len(a), len(c), len(g) - 1
+    prefix = np.zeros(max(ng, 1), np.int64)
+    blocker = np.zeros(max(ng, 1), np.int64)
+    flat = np.zeros(max(ng * m, 1), np.uint8) if want_victims else None
+    rc = lib().kt_paged_preempt_gangs(hs, len(engines), n, a.ctypes.data if n else None, ng, g.ctypes.data, m, c.ctypes.data if m else None,
+                                      int(now[0]), int(now[1]), int(on_equal), PREEMPT_REPRIEVE if reprieve else 0, prefix.ctypes.data,
+                                      None if flat is None else flat.ctypes.data, blocker.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_preempt_gangs: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return prefix[:ng], (None if flat is None else flat[:ng * m].reshape(ng, m)), blocker[:ng]
 
 
 def paged_forecast(engines, pod_rows, instants, on_equal=False, want_verdicts=True):
@@ -302,6 +325,8 @@ def lib():
                                         C.c_void_p]
         L.kt_paged_preempt.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
                                        C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.kt_paged_preempt_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_preempt_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_void_p]
         L.kt_preempt_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -762,6 +762,129 @@ def preempt_gangs_of(snap, member_rows, cand_rows, now, on_equal=False, ctx=None
     return prefix, victims, (-1 if prefix == 0 or block0 >= g else block0)
 
 
+# ---- preempt, for gangs, over pages (kt_paged_preempt_gangs): the closed form over a list of page snapshots ----
+def paged_preempt_gangs_of(snaps, member_rows, cand_rows, now, on_equal=False, reprieve=False, ctx=None):
+    """kt_paged_preempt_gangs for one gang, in closed form over the page snapshots (no GPU) -> (prefix, victims [len(cand_rows)],
+    blocker): ``preempt_gangs_of`` on the cluster of all names, ``ctx`` is ``paged_preempt_context``'s.  What pages add:
+      * which throttles affect which member, which candidates are counted and matched, the error rows, the list cut and "a member
+        is an Error or invalid" are page 0's (the selector side is the same in every page);
+      * the pod count — the threshold's, `used`'s, the calculated threshold's, the stored and the running reserved count — is
+        page 0's and is judged once; a name part is judged on its own page;
+      * the gang passes in S_k iff for every throttle of the union the in-order member walk passes the count part and the name
+        part of every page; each page carries its own reserved prefix from its stored reserved row, and a member the throttle
+        affects adds its value of every name it carries, the presence of all of them (zero-valued ones included) and count + 1;
+      * a throttle keeps its stored status on every page iff its reconcile is an error on some page, and reads the calculated
+        threshold on every page iff some page has calculatedAt set or replaces it at ``now`` (a stored throttle reads the STORED
+        calculated threshold);
+      * blocker: the minimum over throttles and pages of the first stopped position with nothing deleted (an Error or invalid
+        member counts as stopped), -1 when prefix == 0;
+      * victims[j] = 1 iff j < prefix, c_j is counted and a throttle affecting some member matches it.
+    Names are keyed (page, dim), so one walk of the members over all keys IS the walk on every page: the first member that some
+    page stops is the minimum of the pages' own first stopped members.  ``reprieve``: the walk of
+    kt_preempt_gangs_reprieve_launch with that joint judge.  With one snapshot this is ``preempt_gangs_of``."""
+    snap0 = snaps[0]
+    ctx = paged_preempt_context(snaps, now) if ctx is None else ctx
+    members, cands, eq = [int(p) for p in member_rows], [int(c) for c in cand_rows], bool(on_equal)
+    m, g = len(cands), len(members)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap0.n_pods and bool(int(snap0.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap0, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    m_eff = m
+    for j, c in enumerate(cands):
+        if not (0 <= c < snap0.n_pods) or not int(snap0.pod_flags[c]) & S.POD_VALID or affected_throttles(snap0, c)[0]:
+            m_eff = j
+            break
+    counted = lambda c: (int(snap0.pod_flags[c]) & (_COUNTABLE | S.POD_FINISHED)) == _COUNTABLE
+
+    def requests(c):
+        return {(k, d): v for k, s in enumerate(snaps) for d, v in pod_requests(s, c).items()}
+
+    keys = [(k, d) for k, s in enumerate(snaps) for d in range(s.D)]
+    reqs = [requests(p) if 0 <= p < snap0.n_pods else {} for p in members]
+    creq = [requests(c) if counted(c) else {} for c in cands[:m_eff]]
+    union = sorted(set().union(*affected)) if affected else []
+    contributes = [[counted(c) and t in ctx["match"].get(c, ()) for c in cands[:m_eff]] for t in union]
+
+    def first_stopped(t, state):
+        """the first member throttle ``t`` stops on some page against the reconciled `used` ``state`` = [values, counts, pods]"""
+        th = ctx["thr"][t]
+        val, cnt, pods = state
+        eq3 = eq if int(snap0.thr_flags[t]) & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _paged_amounts(snaps, "thr_reserved", t)
+        cc, names = th["calc_count"], {}
+        for kd in keys:
+            u_pr, cv = cnt.get(kd, 0) > 0, th["calc"].get(kd)
+            names[kd] = (cv is not None and u_pr and val.get(kd, 0) >= cv, u_pr, val.get(kd, 0))
+        return _gang_first_stopped(members, [t in a for a in affected], reqs, (th["th"], th["th_count"]),
+                                   (cc is not None and pods > 0 and pods >= cc, pods > 0, pods, names), res, res_count, eq3, eq)
+
+    def moved(state, j, sign):
+        val, cnt, pods = dict(state[0]), dict(state[1]), state[2] + sign
+        for kd, v in creq[j].items():
+            val[kd] = val.get(kd, 0) + sign * v
+            cnt[kd] = cnt.get(kd, 0) + sign
+        return [val, cnt, pods]
+
+    fails = [False] * (m_eff + 1)  # fails[k]: some (member, throttle, page, amount) stops the gang in S_k
+    never = bad_at is not None
+    block0 = g if bad_at is None else bad_at
+    for ti, t in enumerate(union):
+        th = ctx["thr"][t]
+        if th["error"]:  # the stored status stays on every page, in every S_k
+            f = int(snap0.thr_flags[t])
+            eq3 = eq if f & S.THR_CLUSTER else True
+            res, res_count = _paged_amounts(snaps, "thr_reserved", t)
+            used, used_count = _paged_amounts(snaps, "thr_used", t)
+            sth = _paged_amounts(snaps, "thr_calc" if th["use_calc"] else "thr_spec", t)
+            names = {}
+            for k, d in keys:
+                flg = int(snaps[k].thr_thrl_flag[t]) & int(snaps[k].thr_thrl_has[t])
+                names[(k, d)] = (bool(flg >> d & 1), (k, d) in used, used.get((k, d), 0))
+            first = _gang_first_stopped(members, [t in a for a in affected], reqs, sth,
+                                        (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names), res, res_count, eq3, eq)
+            if first is not None:
+                never, block0 = True, min(block0, first)
+            continue
+        state = [th["val"], th["cnt"], th["pods"]]
+        for k in range(m_eff + 1):
+            if k > 0 and contributes[ti][k - 1]:
+                state = moved(state, k - 1, -1)
+            first = first_stopped(t, state)
+            if first is not None:
+                fails[k] = True
+                if k == 0:
+                    block0 = min(block0, first)
+    prefix = -1 if never else next((k for k in range(m_eff + 1) if not fails[k]), -1)
+    victims = [0] * m
+    for j in range(max(prefix, 0)):
+        victims[j] = int(any(contributes[ti][j] for ti in range(len(union))))
+    if reprieve and prefix > 0:
+        live = []  # [index in `contributes`, throttle row, state] of the reconciled throttles of the union, in S(the masked victims)
+        for ti, t in enumerate(union):
+            th = ctx["thr"][t]
+            if th["error"]:  # keeps its stored status whoever is deleted: it passed, or the prefix would not be positive
+                continue
+            state = [th["val"], th["cnt"], th["pods"]]
+            for j in range(prefix):
+                if victims[j] and contributes[ti][j]:
+                    state = moved(state, j, -1)
+            live.append([ti, t, state])
+        for j in range(prefix - 1, -1, -1):
+            if not victims[j]:
+                continue
+            back = [(entry, moved(entry[2], j, 1)) for entry in live if contributes[entry[0]][j]]
+            if any(first_stopped(entry[1], state) is not None for entry, state in back):
+                continue  # some page of some throttle stops a member with c_j back: it stays a victim
+            victims[j] = 0
+            for entry, state in back:
+                entry[2] = state
+    return prefix, victims, (-1 if prefix == 0 or block0 >= g else block0)
+
+
 # ---- forecast: the first instant at which a blocked pod passes (kt_forecast_launch), in closed form on a Snapshot ----
 def _instant(t):
     return int(t[0]), int(t[1])
@@ -980,6 +1103,14 @@ class PagedEngine:
         page's names, through kt_paged_preempt (``reprieve``: the victim mask shrunk to a minimal set by the reprieve walk) ->
         (prefix [n], victims [n][n_cand] or None).  A dry run: nothing stored changes on any page."""
         return E.paged_preempt(self.engines, pod_rows, cand_rows, now, on_equal=on_equal, reprieve=reprieve, want_victims=want_victims)
+
+    def preempt_gangs(self, pod_rows, gang_off, cand_rows, now, on_equal=False, reprieve=False, want_victims=True):
+        """The shortest victim prefix of the caller-ordered ``cand_rows`` that lets each gang ``pod_rows[gang_off[g]:gang_off[g + 1]]``
+        in as a whole, over every page's names, through kt_paged_preempt_gangs (``reprieve``: the victim mask shrunk to a minimal set
+        by the reprieve walk) -> (prefix [n_gangs], victims [n_gangs][n_cand] or None, blocker [n_gangs]).  A dry run: nothing
+        stored changes on any page."""
+        return E.paged_preempt_gangs(self.engines, pod_rows, gang_off, cand_rows, now, on_equal=on_equal, reprieve=reprieve,
+                                     want_victims=want_victims)
 
     def forecast(self, pod_rows, instants, on_equal=False, want_verdicts=True):
         """The first of the strictly ascending ``instants`` at which each pod of ``pod_rows`` passes PreFilter, over every page's
