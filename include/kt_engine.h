@@ -541,6 +541,51 @@ int32_t kt_preempt_gangs_reprieve_launch(kt_engine* e, int64_t n, const int64_t*
 int32_t kt_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns,
                            int32_t on_equal, void* stream);
 int32_t kt_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, uint8_t* out_verdicts /* [n][n_inst], nullable */);
+/* ---- forecast, for gangs: the first instant at which a whole gang is admitted — what kt_preempt_gangs_launch is to
+ *      kt_preempt_launch.  The members' own forecasts do not compose into the gang's: each admitted member reserves against the
+ *      throttles the later members meet (two members asking 3 each with `used` 4 under a spec of 8: each member alone passes at
+ *      every instant, the gang only inside an override of 10).
+ *      Notation as for kt_forecast_launch: the instants t_0 < .. < t_{m-1}, state R_t, "a throttle whose reconcile is an error, or
+ *      that is not valid and responsible, keeps its stored status in every R_t", the two facts about the replace rule, both
+ *      override ends inclusive.  Gang g is the queue positions [gang_off[g], gang_off[g + 1]) of pod_rows, as in
+ *      kt_admit_gangs_launch.  Gangs are judged independently of each other, each against the stored reserved amounts; a pod may
+ *      be a member of several gangs.
+ *      out_verdicts[g][k] (nullable, [n_gangs][n_inst]) is KT_VERDICT_SUCCESS iff a dry kt_admit_gangs_launch of the one gang g,
+ *      with R_{t_k} as the stored status, admits it — members in order, each sees the stored reservations plus what the earlier
+ *      members of its gang reserved at their turn, every verdict Success; Reserve exactly kt_admit's: the value of every name
+ *      carried, the presence of all names carried (zero-valued ones included), count + 1, and the count becomes present — and
+ *      KT_VERDICT_UNSCHEDULABLE otherwise.  A gang with a member whose PreFilter is an Error, or whose row is invalid, reports
+ *      KT_VERDICT_ERROR at every instant.
+ *      out_first[g] (nullable) is the smallest k whose verdict is KT_VERDICT_SUCCESS, or KT_FORECAST_NONE.
+ *      out_blocker[g][k] (nullable, [n_gangs][n_inst]) is the queue position (index into pod_rows) of the first member that is not
+ *      Success when the gang is walked in R_{t_k} — an Error or invalid member is not Success; all earlier members were admitted,
+ *      so the sums it met are exact — and -1 where the verdict is Success.
+ *      A gang of one pod reports byte for byte what kt_forecast_launch reports for that pod (blocker: its own position where
+ *      blocked).  With inst = [now], out_first[g] == 0 exactly where kt_preempt_gangs_launch at `now` with no candidates reports
+ *      prefix 0, and out_blocker[g][0] equals its out_blocker[g].
+ *      One kt_check launch with the status matrix over pod_rows, the aggregate and dry finalize (at t_0) of kt_forecast_launch,
+ *      and one launch of kt_forecast_gangs (csrc/kt_kernels_forecast_gangs.hip): one wave per gang, lane = instant position, the
+ *      member loop wave-uniform — `used`, the request rows and the reserved prefix do not depend on the instant, only the
+ *      threshold values and the throttled flags are the lane's own.  The call is a dry run: stored status and reserved amounts
+ *      are not changed.
+ *      Refused before anything is launched, the instants first: n_inst < 1, instants that are not strictly ascending, an inst_ns
+ *      outside [0, 10^9), a missing array, every gang_off defect kt_admit_gangs_launch refuses, a pod named twice within ONE gang
+ *      (KT_ERR_INVALID_ARGUMENT); a pod row outside the capacity, n x throttle_rows or n_gangs x n_inst > 2^31
+ *      (KT_ERR_OUT_OF_RANGE); `used` wider than int64, a KT_VARIANT_INCREMENTAL engine, an exchange world above 1
+ *      (KT_ERR_UNSUPPORTED; the |request| sums probe runs first where the sums are not known).  A refused call leaves the check
+ *      slot, the reconcile report and every result buffer alone.  n == 0 is allowed only with n_gangs == 0: KT_OK, nothing is
+ *      launched.
+ *      Slots: those of kt_forecast_launch — the ONE check slot, its dry finalize drops a pending reconcile report, a pending
+ *      kt_aggregate_launch keeps its sums, a pending preempt result of any of the four kinds stays fetchable.  The result SHARES
+ *      the one pending forecast result, as the gang preempt calls share the preempt result: a later kt_forecast_launch,
+ *      kt_forecast_gangs_launch or kt_paged_forecast on the engine replaces it.  kt_forecast_fetch after a gang launch answers
+ *      KT_ERR_NOT_READY, and so does kt_forecast_gangs_fetch after a plain or paged launch.  kt_forecast_gangs_fetch synchronises.
+ *      Out of scope: more than KT_MAX_DIMS resource names (a later kt_paged_forecast_gangs), several ranks. -------------------- */
+int32_t kt_forecast_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_inst,
+                                 const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, void* stream);
+int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first /* [n_gangs], nullable */,
+                                uint8_t* out_verdicts /* [n_gangs][n_inst], nullable */,
+                                int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
 /* The sorted, distinct instants in (from, until] at which the CalculateThreshold of some valid and responsible throttle can change:
  * every parsed non-zero `begin` of an override, and for every parsed non-zero `end` the instant end + 1 ns — the FIRST instant at
  * which the override is no longer active.  That is deliberately not the `end` that NextOverrideHappensIn

@@ -387,6 +387,10 @@ struct kt_engine {
   DevBuf<uint8_t> d_forecast_verdicts;
   bool forecast_ready = false;
   int64_t forecast_n = 0, forecast_m = 0;
+  // kt_forecast_gangs_launch shares that one pending result (first and verdict bytes per GANG, forecast_n = the gangs); the kind
+  // tag says which fetch may read it.  Its offsets and the blocking member per gang and instant live in buffers of their own
+  bool forecast_gangs = false;
+  DevBuf<int64_t> d_forecast_gang_off, d_forecast_blocker;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;

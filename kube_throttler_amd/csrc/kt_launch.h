@@ -189,6 +189,14 @@ void launch_forecast(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* r
 bool launch_forecast_paged(const PreemptPage* pages, int n_pages, PreemptPage* pages_dev, hipEvent_t pages_copied, int64_t n, int64_t m,
                            const int64_t* rows_dev, const int64_t* inst_s, const int32_t* inst_ns, int T, bool on_equal, const uint8_t* status,
                            const uint64_t* summary, int64_t* first, uint8_t* verdicts, hipStream_t s, hipError_t* hip_err);
+// the first instant at which a whole gang is admitted (kt_kernels_forecast_gangs.hip): one wave per gang, lane = instant position.
+// rows_dev [n]: the members of all gangs; gang g is the queue positions [gang_off_dev[g], gang_off_dev[g + 1]) (device memory);
+// instants, status / summary, partial and error as for launch_forecast; first [n_gangs], verdicts [n_gangs][m] and blocker
+// [n_gangs][m] out
+void launch_forecast_gangs(const AdmitPage& pg, int64_t n_gangs, int64_t m, const int64_t* rows_dev, const int64_t* gang_off_dev,
+                           const int64_t* inst_s, const int32_t* inst_ns, int T, bool on_equal, const uint8_t* status, const uint64_t* summary,
+                           const unsigned long long* partial, const uint8_t* error, int64_t* first, uint8_t* verdicts, int64_t* blocker,
+                           hipStream_t s);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

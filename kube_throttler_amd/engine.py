@@ -42,7 +42,7 @@ EXPORTS = [
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
-    "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_override_instants",
+    "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_paged_preempt_gangs",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
@@ -339,6 +339,9 @@ def lib():
                                         C.c_void_p, C.c_void_p]
         L.kt_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.kt_forecast_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.kt_forecast_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                               C.c_int32, C.c_void_p]
+        L.kt_forecast_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_override_instants.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_int64)]
         _LIB = L
@@ -801,6 +804,36 @@ class Engine:
         (first int64 [n], verdicts uint8 [n][n_inst] or None).  A dry run: stored status and reserved amounts stay as they are."""
         self.forecast_launch(pod_rows, instants, on_equal)
         return self.forecast_fetch(len(pod_rows), len(instants), want_verdicts)
+
+    # ---- forecast, for gangs: the first instant at which a whole gang is admitted
+    def forecast_gangs_launch(self, pod_rows, gang_off, instants, on_equal=False, stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        g = _gang_offsets(gang_off)
+        inst_s = np.ascontiguousarray([int(t[0]) for t in instants], dtype=np.int64)
+        inst_ns = np.ascontiguousarray([int(t[1]) for t in instants], dtype=np.int32)
+        m = len(inst_s)
+        self._ck(lib().kt_forecast_gangs_launch(self._h, len(a), p if len(a) else None, len(g) - 1, g.ctypes.data, m,
+                                                inst_s.ctypes.data if m else None, inst_ns.ctypes.data if m else None, int(on_equal), stream))
+
+    def forecast_gangs_fetch(self, n_gangs, n_inst, want_verdicts=True, want_blocker=True):
+        first = np.zeros(max(n_gangs, 1), np.int64)
+        flat = np.zeros(max(n_gangs * n_inst, 1), np.uint8) if want_verdicts else None
+        blk = np.zeros(max(n_gangs * n_inst, 1), np.int64) if want_blocker else None
+        self._ck(lib().kt_forecast_gangs_fetch(self._h, n_gangs, first.ctypes.data, None if flat is None else flat.ctypes.data,
+                                               None if blk is None else blk.ctypes.data))
+        return (first[:n_gangs], (None if flat is None else flat[:n_gangs * n_inst].reshape(n_gangs, n_inst)),
+                (None if blk is None else blk[:n_gangs * n_inst].reshape(n_gangs, n_inst)))
+
+    def forecast_gangs(self, pod_rows, gang_off, instants, on_equal=False, want_verdicts=True, want_blocker=True):
+        """kt_forecast_gangs_launch + kt_forecast_gangs_fetch: per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` and per instant
+        the KT_VERDICT_* of an in-order admission of its members (each admitted member reserves against the throttles the later
+        ones meet) once every valid and responsible throttle has been reconciled at that instant, the first position whose
+        verdict is Success (FORECAST_NONE: none), and per instant the queue position of the first member that is not admitted
+        (-1 where the gang passes) -> (first int64 [n_gangs], verdicts uint8 [n_gangs][n_inst] or None, blocker int64
+        [n_gangs][n_inst] or None).  Gangs are judged independently of each other, each against the stored reserved amounts.
+        A dry run: stored status and reserved amounts stay as they are."""
+        self.forecast_gangs_launch(pod_rows, gang_off, instants, on_equal)
+        return self.forecast_gangs_fetch(len(_gang_offsets(gang_off)) - 1, len(instants), want_verdicts, want_blocker)
 
     def override_instants(self, from_, until, cap=None):
         """kt_override_instants: the sorted, distinct instants in (from_, until] at which some valid and responsible throttle's

@@ -1328,6 +1328,49 @@ GangPreemptResult KubeThrottler::PreemptGang(const std::vector<std::string>& mem
   return res;
 }
 
+// has / instantSec / instantNsec / instant of a RetryAfterResult from the first passing position (KT_FORECAST_NONE: none)
+static void retry_after_first(RetryAfterResult& out, int64_t first, const std::vector<int64_t>& inst_s, const std::vector<int32_t>& inst_ns) {
+  out.has = first >= 0;
+  if (!out.has) return;
+  out.instantSec = inst_s[(size_t)first], out.instantNsec = inst_ns[(size_t)first];
+  const time_t tt = (time_t)out.instantSec;
+  struct tm g;
+  gmtime_r(&tt, &g);
+  char buf[64];
+  size_t n = strftime(buf, sizeof buf, "%Y-%m-%dT%H:%M:%S", &g);
+  if (out.instantNsec) n += (size_t)snprintf(buf + n, sizeof buf - n, ".%09d", out.instantNsec);
+  snprintf(buf + n, sizeof buf - n, "Z");
+  out.instant = buf;
+}
+
+// What RetryAfter and RetryAfterGang (`who`) share in front of their launch: a mirror on pages refuses, `now` and the horizon are
+// checked, then inst = now ++ the override boundaries in (now, now + horizon] (kt_override_instants, twice: count, then fill).
+// false: *error says why (an engine error included)
+template <class IMPL>
+static bool retry_after_instants(IMPL& p, const char* who, const char* query, const std::string& now_rfc3339, int64_t horizon_seconds,
+                                 std::vector<int64_t>* inst_s, std::vector<int32_t>* inst_ns, std::string* error) {
+  if (p.pages.size() > 1) {
+    *error = std::string(who) + ": the mirror runs on " + std::to_string(p.pages.size()) + " pages (more than " + std::to_string(p.D) +
+             " resource names); the " + query + " has no paged form";
+    return false;
+  }
+  int64_t now_s;
+  int32_t now_ns;
+  if (!ParseRFC3339(now_rfc3339, &now_s, &now_ns, error)) return false;
+  if (horizon_seconds < 0) {
+    *error = std::string(who) + ": horizon " + std::to_string(horizon_seconds) + " s";
+    return false;
+  }
+  int64_t total = 0;
+  int32_t rc = kt_override_instants(p.e, now_s, now_ns, now_s + horizon_seconds, now_ns, 0, nullptr, nullptr, &total);
+  inst_s->assign((size_t)total + 1, 0), inst_ns->assign((size_t)total + 1, 0);
+  (*inst_s)[0] = now_s, (*inst_ns)[0] = now_ns;
+  if (rc == KT_OK && total > 0)
+    rc = kt_override_instants(p.e, now_s, now_ns, now_s + horizon_seconds, now_ns, total, inst_s->data() + 1, inst_ns->data() + 1, &total);
+  if (rc != KT_OK) *error = p.engine_error(rc);
+  return rc == KT_OK;
+}
+
 // When does this pod pass PreFilter: the override boundaries of the window from the engine's host copy of the specs
 // (kt_override_instants: every begin, and end + 1 ns — the first instant an override is no longer active), `now` in front, one
 // kt_forecast_launch + kt_forecast_fetch over them on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).
@@ -1335,34 +1378,18 @@ RetryAfterResult KubeThrottler::RetryAfter(const std::string& pod_key, const std
   std::lock_guard<std::recursive_mutex> lk(p_->mu);
   auto& p = *p_;
   RetryAfterResult out;
-  if (p.pages.size() > 1) {
-    out.error = "RetryAfter: the mirror runs on " + std::to_string(p.pages.size()) + " pages (more than " + std::to_string(p.D) +
-                " resource names); the forecast query has no paged form";
-    return out;
-  }
-  int64_t now_s;
-  int32_t now_ns;
-  if (!ParseRFC3339(now_rfc3339, &now_s, &now_ns, &out.error)) return out;
-  if (horizon_seconds < 0) {
-    out.error = "RetryAfter: horizon " + std::to_string(horizon_seconds) + " s";
-    return out;
-  }
+  std::vector<int64_t> inst_s;
+  std::vector<int32_t> inst_ns;
+  if (!retry_after_instants(p, "RetryAfter", "forecast query", now_rfc3339, horizon_seconds, &inst_s, &inst_ns, &out.error)) return out;
   const int64_t row = p.pod_rows.find(pod_key);
   if (row < 0) {
     out.error = "pod " + pod_key + " is not known to the plugin (OnPodAdd first)";
     return out;
   }
-  int64_t total = 0;
-  int32_t rc = kt_override_instants(p.e, now_s, now_ns, now_s + horizon_seconds, now_ns, 0, nullptr, nullptr, &total);
-  std::vector<int64_t> inst_s((size_t)total + 1);
-  std::vector<int32_t> inst_ns((size_t)total + 1);
-  inst_s[0] = now_s, inst_ns[0] = now_ns;
-  if (rc == KT_OK && total > 0)
-    rc = kt_override_instants(p.e, now_s, now_ns, now_s + horizon_seconds, now_ns, total, inst_s.data() + 1, inst_ns.data() + 1, &total);
   const int64_t m = (int64_t)inst_s.size();
   int64_t first = KT_FORECAST_NONE;
   out.verdicts_at.assign((size_t)m, 0);
-  if (rc == KT_OK) rc = kt_forecast_launch(p.e, 1, &row, m, inst_s.data(), inst_ns.data(), /*isThrottledOnEqual=*/0, nullptr);
+  int32_t rc = kt_forecast_launch(p.e, 1, &row, m, inst_s.data(), inst_ns.data(), /*isThrottledOnEqual=*/0, nullptr);
   if (rc == KT_OK) rc = kt_forecast_fetch(p.e, 1, &first, out.verdicts_at.data());
   if (rc != KT_OK) {
     out.error = p.engine_error(rc);
@@ -1370,19 +1397,57 @@ RetryAfterResult KubeThrottler::RetryAfter(const std::string& pod_key, const std
     return out;
   }
   for (int64_t k = 0; k < m; ++k) out.instants.emplace_back(inst_s[(size_t)k], inst_ns[(size_t)k]);
-  out.has = first >= 0;
-  if (out.has) {
-    out.instantSec = inst_s[(size_t)first], out.instantNsec = inst_ns[(size_t)first];
-    const time_t tt = (time_t)out.instantSec;
-    struct tm g;
-    gmtime_r(&tt, &g);
-    char buf[64];
-    size_t n = strftime(buf, sizeof buf, "%Y-%m-%dT%H:%M:%S", &g);
-    if (out.instantNsec) n += (size_t)snprintf(buf + n, sizeof buf - n, ".%09d", out.instantNsec);
-    snprintf(buf + n, sizeof buf - n, "Z");
-    out.instant = buf;
-  }
+  retry_after_first(out, first, inst_s, inst_ns);
   return out;
+}
+
+// When is this gang admitted: RetryAfter's instants, one kt_forecast_gangs_launch + kt_forecast_gangs_fetch with the members as ONE
+// gang on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).  Nothing is changed.
+GangRetryAfterResult KubeThrottler::RetryAfterGang(const std::vector<std::string>& member_keys, const std::string& now_rfc3339,
+                                                   int64_t horizon_seconds) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  GangRetryAfterResult res;
+  RetryAfterResult& out = res.retry;
+  std::vector<int64_t> inst_s;
+  std::vector<int32_t> inst_ns;
+  if (!retry_after_instants(p, "RetryAfterGang", "gang forecast", now_rfc3339, horizon_seconds, &inst_s, &inst_ns, &out.error)) return res;
+  if (member_keys.empty()) {
+    out.error = "RetryAfterGang: a gang without members";
+    return res;
+  }
+  std::vector<int64_t> rows(member_keys.size());
+  std::set<std::string> seen;
+  for (size_t i = 0; i < rows.size(); ++i) {
+    if ((rows[i] = p.pod_rows.find(member_keys[i])) < 0) {
+      out.error = "pod " + member_keys[i] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+    if (!seen.insert(member_keys[i]).second) {  // (it would reserve twice: the engine refuses it too)
+      out.error = "RetryAfterGang: pod " + member_keys[i] + " is a member twice";
+      return res;
+    }
+  }
+  const int64_t m = (int64_t)inst_s.size();
+  const int64_t gang_off[2] = {0, (int64_t)rows.size()};
+  int64_t first = KT_FORECAST_NONE;
+  std::vector<int64_t> blockers((size_t)m, -1);
+  out.verdicts_at.assign((size_t)m, 0);
+  int32_t rc = kt_forecast_gangs_launch(p.e, (int64_t)rows.size(), rows.data(), 1, gang_off, m, inst_s.data(), inst_ns.data(),
+                                        /*isThrottledOnEqual=*/0, nullptr);
+  if (rc == KT_OK) rc = kt_forecast_gangs_fetch(p.e, 1, &first, out.verdicts_at.data(), blockers.data());
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    out.verdicts_at.clear();
+    return res;
+  }
+  for (int64_t k = 0; k < m; ++k) {
+    out.instants.emplace_back(inst_s[(size_t)k], inst_ns[(size_t)k]);
+    const int64_t b = blockers[(size_t)k];
+    res.blockers_at.push_back(b >= 0 && (size_t)b < member_keys.size() ? member_keys[(size_t)b] : std::string());
+  }
+  retry_after_first(out, first, inst_s, inst_ns);
+  return res;
 }
 
 // A scheduling pass over a queue of GANGS (jobs whose pods only run together), in order: every member gets PreFilter and, on

@@ -184,6 +184,12 @@ struct RetryAfterResult {
   std::string error;             // not empty: the call failed (unknown pod, a paged mirror, engine error)
 };
 
+// RetryAfterGang: the first instant at which a whole gang is admitted, and the member that stops it at each judged instant
+struct GangRetryAfterResult {
+  RetryAfterResult retry;                // has / instant / instants / verdicts_at / error as for RetryAfter, for the gang as a whole
+  std::vector<std::string> blockers_at;  // per judged instant the Pod::Key() of the first member that is not admitted; empty: the gang passes
+};
+
 // KubeThrottlerPluginArgs (pkg/scheduler_plugin/plugin_args.go:33-40) + engine sizing
 struct PluginArgs {
   std::string name;                 // throttler name (required)
@@ -265,6 +271,12 @@ class KubeThrottler {
   // (temporaryThresholdOverrides begin and end): kt_override_instants for the boundaries, ONE kt_forecast_launch over
   // now ++ boundaries.  What a PreFilter rejection path asks to set a backoff.  A dry run; a mirror on several pages refuses.
   RetryAfterResult RetryAfter(const std::string& pod_key, const std::string& now_rfc3339, int64_t horizon_seconds);
+  // The same for a gang (a job whose pods only run together): the first instant in [now, now + horizon] at which an in-order
+  // admission of the members — each admitted member reserves against the throttles the later ones meet — admits all of them, and
+  // per judged instant the member that stops it.  kt_override_instants for the boundaries, ONE kt_forecast_gangs_launch over
+  // now ++ boundaries.  The members' own RetryAfter answers do not compose into this one.  A dry run; a member named twice, an
+  // unknown key, an empty gang and a mirror on several pages answer an error.
+  GangRetryAfterResult RetryAfterGang(const std::vector<std::string>& member_keys, const std::string& now_rfc3339, int64_t horizon_seconds);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

@@ -969,6 +969,69 @@ def forecast_of(snap, pod_row, instants, on_equal=False, ctx=None):
     return next((k for k in range(m) if not fails[k]), -1), verdicts_
 
 
+# ---- forecast, for gangs (kt_forecast_gangs_launch), in closed form on a Snapshot ----
+def forecast_gangs_of(snap, member_rows, instants, on_equal=False, ctx=None):
+    """kt_forecast_gangs_launch for one gang, in closed form on a Snapshot (no GPU) -> (first, verdicts [len(instants)], blockers
+    [len(instants)]).  verdicts[k]: Success iff an in-order admission of ``member_rows`` — PreFilter, and on Success Reserve on
+    every throttle that affects the member — admits every member once every valid and responsible throttle has been reconciled at
+    ``instants[k]`` on the state as it is now; Error at every instant when a member's PreFilter is an Error or its row is invalid.
+    blockers[k]: the position in ``member_rows`` of the first member that is not Success at that instant, -1 where the gang
+    passes; first: the smallest k with Success, or -1.  ``forecast_of``'s threshold per throttle and instant, met by the members
+    under ``_gang_first_stopped``'s reserved prefix; `used` and the reserved prefix do not depend on the instant.  ``ctx`` is
+    ``preempt_context``'s aggregate (any ``now``)."""
+    inst = [_instant(t) for t in instants]
+    ctx = preempt_context(snap, inst[0]) if ctx is None else ctx
+    members, eq, m = [int(p) for p in member_rows], bool(on_equal), len(inst)
+    g = len(members)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap.n_pods and bool(int(snap.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    reqs = [pod_requests(snap, p) if 0 <= p < snap.n_pods else {} for p in members]
+    stopped = [g if bad_at is None else bad_at] * m  # per instant the first member some throttle stops (g: none)
+    for t in (sorted(set().union(*affected)) if affected else []):
+        th = ctx["thr"][t]
+        f = int(snap.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+        hit = [t in a for a in affected]
+        if th["error"]:  # the stored status, at every instant
+            used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+            sth = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+            flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+            names = {d: (bool(flg >> d & 1), d in used, used.get(d, 0)) for d in range(snap.D)}
+            j = _gang_first_stopped(members, hit, reqs, sth, (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names),
+                                    res, res_count, eq3, eq)
+            if j is not None:
+                stopped = [min(s, j) for s in stopped]
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        stored = _amount_dict(snap.thr_calc, t, snap.D)
+        spec = _amount_dict(snap.thr_spec, t, snap.D)
+        for k, at in enumerate(inst):
+            calc, cc, any_err = _calculated_threshold(snap, t, at)
+            fp = int(snap.thr_spec_msgs_fp[t]) if any_err else 0
+            replace = (calc, cc) != stored or int(snap.thr_status_msgs_fp[t]) != fp
+            rd = (calc, cc) if (f & S.THR_CALC_AT_NONZERO) or replace else spec
+            names = {}
+            for d in range(snap.D):
+                u_pr, cv = cnt.get(d, 0) > 0, calc.get(d)
+                names[d] = (cv is not None and u_pr and val.get(d, 0) >= cv, u_pr, val.get(d, 0))
+            j = _gang_first_stopped(members, hit, reqs, rd, (cc is not None and pods > 0 and pods >= cc, pods > 0, pods, names), res, res_count,
+                                    eq3, eq)
+            if j is not None:
+                stopped[k] = min(stopped[k], j)
+    if bad_at is not None:
+        verdicts_ = [S.VERDICT_ERROR] * m
+    else:
+        verdicts_ = [S.VERDICT_BLOCK if s < g else S.VERDICT_ALLOW for s in stopped]
+    first = next((k for k in range(m) if verdicts_[k] == S.VERDICT_ALLOW), -1)
+    return first, verdicts_, [s if s < g else -1 for s in stopped]
+
+
 # ---- forecast over pages (kt_paged_forecast): the closed form over a list of page snapshots ----
 def paged_forecast_of(snaps, pod_row, instants, on_equal=False, ctx=None):
     """kt_paged_forecast for one pod, in closed form over the page snapshots (no GPU) -> (first, verdicts [len(instants)]):
