@@ -643,7 +643,8 @@ const char* kt_kernel_name(kt_engine* e, int32_t kernel);
                                             keep between PreFilter sweeps.  One after every compile and after a table clear; pod events refresh
                                             their rows only and do not count (KT_NO_MATCH_CACHE=1: no table, the scans as before) */
 #define KT_COUNTER_MATCH_CACHE_SCANS 13  /* PreFilter sweeps served from the match cache so far (the lean sweep of every row; the aggregate
-                                            scans count in KT_COUNTER_MATCH_CACHE_AGG_SCANS) */
+                                            scans count in KT_COUNTER_MATCH_CACHE_AGG_SCANS).  The sweep replays the table's 16-byte
+                                            match-code records; KT_NO_MATCH_CODES=1: its planes, counted alike */
 #define KT_COUNTER_MATCH_CACHE_PLANES 14 /* the longest namespace word list of the compiled single-chunk program, as the last sweep of every
                                             row counted it (0: not counted yet, or several chunks): more than 4 = not cached */
 #define KT_COUNTER_MATCH_CACHE_AGG_SCANS 15 /* full aggregate scans that replayed the match cache so far: the two-per-CU form over the scan
@@ -855,6 +856,19 @@ int32_t kt_debug_reload_env(kt_engine* e);
  * (KT_ERR_OUT_OF_RANGE).  KT_ERR_NOT_READY where there is nothing current to copy: no table built for this program, rows still
  * waiting for their refresh, or (which = 1) a view whose planes were not gathered.  Waits for the engine's last launch. */
 int32_t kt_debug_match_planes(kt_engine* e, int32_t which, int64_t cap, uint64_t* out, int64_t* out_rows, int64_t* out_n, int32_t* out_planes);
+
+/* Development aid: the match-code records beside that table (one 16-byte record per pod row: byte 0 the count 0..15 or 0xFF for
+ * "more than 15: read the planes", bytes 1..15 the codes k << 6 | bit in ascending order — the terms of plane k the PreFilter
+ * sweep's run rule leaves), for tests that decode them against the planes.  Same protocol as kt_debug_match_planes:
+ *   which = 0: out[2 * r], out[2 * r + 1] = the low and high eight bytes of the record of pod row r; out_rows is not written.
+ *   which = 1: the countable scan view's records (what the cached aggregate replays), record j of pod row out_rows[j] (nullable).
+ * KT_ERR_NOT_READY also where the table has more planes than a record can name (no records are kept). */
+int32_t kt_debug_match_codes(kt_engine* e, int32_t which, int64_t cap, uint64_t* out, int64_t* out_rows, int64_t* out_n);
+/* Development aid, host side only: what plane k means for the pods of namespace row ns_row in the compiled single-chunk program —
+ * *out_word = the word of term numbers at position k of the namespace's list (-1: the list is shorter), *out_lo / *out_hi = the
+ * run masks of that word the records are cut with (all ones where no throttle of the program has several terms: the rule
+ * x & ~((x | hi) - lo) then keeps everything).  KT_ERR_NOT_READY without a current single-chunk program. */
+int32_t kt_debug_match_runs(kt_engine* e, int32_t ns_row, int32_t k, int32_t* out_word, uint64_t* out_lo, uint64_t* out_hi);
 
 #ifdef __cplusplus
 }

@@ -369,6 +369,7 @@ int32_t kt_engine_destroy(kt_engine* e) {
   e->views.release();
   e->d_carry.release();
   e->d_mc.release();
+  e->d_mcodes.release();
   if (e->h_mc_rows) (void)hipHostFree(e->h_mc_rows);
   if (e->mc_rows_ev) (void)hipEventDestroy(e->mc_rows_ev);
   e->d_slab_tag.release();
@@ -549,6 +550,54 @@ int32_t kt_debug_match_planes(kt_engine* e, int32_t which, int64_t cap, uint64_t
     KT_HIP(e, hipMemcpyAsync(out + (size_t)k * (size_t)cap, src + (size_t)k * stride, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   if (which == 1 && out_rows) KT_HIP(e, hipMemcpyAsync(out_rows, cv.rows.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
+int32_t kt_debug_match_codes(kt_engine* e, int32_t which, int64_t cap, uint64_t* out, int64_t* out_rows, int64_t* out_n) {
+  if (!e || which < 0 || which > 1 || cap < 0 || !out_n || (cap > 0 && !out)) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+  *out_n = 0;
+  const uint32_t planes = e->mc_planes;
+  if (!e->mc_valid || e->program_dirty || e->mc_gen != e->program_gen || e->mc_planes_gen != e->program_gen || !e->mc_pending.empty() || !e->d_mcodes.p ||
+      planes == 0u || planes > (uint32_t)kt::kMatchReplay || e->d_mcodes.cap < (size_t)e->cfg.pod_capacity)
+    return e->fail(KT_ERR_NOT_READY, "no current match-code records: no table built for this program, or rows wait for their refresh");
+  int64_t n = e->pod_rows_hi;
+  const kt::MatchCodes* src = e->d_mcodes.p;
+  hipStream_t s = e->own_stream;
+  const ScanView& cv = e->views.countable;
+  if (which == 1) {
+    if (!cv.valid || !cv.mx_valid || !cv.mc_there || !cv.mc.p || !cv.rows.p || !cv.d_n.p || cv.mx_planes != planes || cv.mc.cap < (size_t)cv.cap + 1)
+      return e->fail(KT_ERR_NOT_READY, "the countable scan view holds no current match-code records");
+    unsigned long long dn = 0;
+    KT_HIP(e, hipMemcpyAsync(&dn, cv.d_n.p, 8, hipMemcpyDeviceToHost, s));
+    KT_HIP(e, hipStreamSynchronize(s));
+    n = (int64_t)std::min<unsigned long long>(std::min<unsigned long long>(dn, cv.n + (unsigned long long)cv.extra), (unsigned long long)cv.cap);
+    src = cv.mc.p;
+  }
+  *out_n = n;
+  if (cap == 0 || n == 0) return KT_OK;
+  if (cap < n) return e->fail(KT_ERR_OUT_OF_RANGE, "cap=%lld < %lld", (long long)cap, (long long)n);
+  KT_HIP(e, hipMemcpyAsync(out, src, (size_t)n * sizeof(kt::MatchCodes), hipMemcpyDeviceToHost, s));
+  if (which == 1 && out_rows) KT_HIP(e, hipMemcpyAsync(out_rows, cv.rows.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
+int32_t kt_debug_match_runs(kt_engine* e, int32_t ns_row, int32_t k, int32_t* out_word, uint64_t* out_lo, uint64_t* out_hi) {
+  if (!e || ns_row < 0 || k < 0 || !out_word || !out_lo || !out_hi) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  const kt::HostIndex& h = e->hindex;
+  if (e->program_dirty || h.bm_chunks.size() != 1 || (uint32_t)ns_row >= h.n_ns) return e->fail(KT_ERR_NOT_READY, "no current single-chunk program with that namespace row");
+  const kt::BmChunk& ch = h.bm_chunks[0];
+  const uint32_t* rng = (const uint32_t*)(h.bm_images.data() + ch.img_off + ch.off_nsl_rng);
+  const kt::NsWord* nsl = (const kt::NsWord*)(h.bm_images.data() + ch.img_off + ch.off_nsl);
+  *out_word = -1, *out_lo = ~0ull, *out_hi = ~0ull;
+  if ((uint32_t)k >= rng[2 * ns_row + 1] - rng[2 * ns_row]) return KT_OK;
+  const uint32_t w = nsl[rng[2 * ns_row] + (uint32_t)k].w;
+  *out_word = (int32_t)w;
+  if (ch.has_adj && h.bm_runs.size() >= ((size_t)ch.w0 + w + 1) * 2) *out_lo = h.bm_runs[((size_t)ch.w0 + w) * 2], *out_hi = h.bm_runs[((size_t)ch.w0 + w) * 2 + 1];
   return KT_OK;
 }
 

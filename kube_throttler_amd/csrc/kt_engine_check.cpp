@@ -56,20 +56,23 @@ int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc
   const uint64_t stride = (uint64_t)e->cfg.pod_capacity;
   ScanView& cv = e->views.countable;
   kt::MatchViewPlanes vp;
-  if (cv.valid && cv.mx_valid && cv.mx.p && cv.pos.p && cv.mx_planes == planes && e->mc_gen == e->program_gen)
-    vp.mx = cv.mx.p, vp.pos = cv.pos.p, vp.stride = (uint64_t)cv.cap + 1u;
+  const bool recs = kt::match_codes_fit(e->dindex, planes);  // does the table keep match-code records for this program
+  if (cv.valid && cv.mx_valid && cv.mx.p && cv.pos.p && cv.mx_planes == planes && e->mc_gen == e->program_gen &&
+      (!recs || (cv.mc_there && cv.mc.cap >= (size_t)cv.cap + 1)))
+    vp.mx = cv.mx.p, vp.pos = cv.pos.p, vp.stride = (uint64_t)cv.cap + 1u, vp.mc = recs ? cv.mc.p : nullptr;
   else
     cv.mx_valid = false;  // (this call may write words the view's planes do not get: gathered again before they are replayed)
   if (!e->mc_valid || e->mc_gen != e->program_gen) {
     // (with vp set — the write-through of a FULL build — only in views of more than 2^20 records: the table goes void under a
     //  valid view when more than kPatchBatchMax rows are pending in batches that all fit the view's headroom, cv.extra grows at
     //  least as fast as the pending list, and the headroom passes kPatchBatchMax only as n / 16.  A compile voids the view too.)
-    if (e->d_mc.cap < (size_t)planes * stride) {
+    if (e->d_mc.cap < (size_t)planes * stride || (recs && e->d_mcodes.cap < (size_t)stride)) {
       if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // an earlier scan may still read the old table
       KT_HIP(e, e->d_mc.reserve((size_t)planes * stride));
+      if (recs) KT_HIP(e, e->d_mcodes.reserve((size_t)stride));
     }
     order_behind_ingest(e, s);
-    if (!kt::launch_build_match_cache(e->pods, e->pod_rows_hi, nullptr, e->dindex, e->d_mc.p, stride, planes, s, &vp)) {
+    if (!kt::launch_build_match_cache(e->pods, e->pod_rows_hi, nullptr, e->dindex, e->d_mc.p, stride, planes, s, &vp, recs ? e->d_mcodes.p : nullptr)) {
       cv.mx_valid = false;
       return KT_OK;
     }
@@ -91,7 +94,7 @@ int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc
     }
     memcpy(e->h_mc_rows, e->mc_pending.data(), n * 8);
     order_behind_ingest(e, s);
-    if (!kt::launch_build_match_cache(e->pods, (int64_t)n, e->h_mc_rows, e->dindex, e->d_mc.p, stride, planes, s, &vp)) {
+    if (!kt::launch_build_match_cache(e->pods, (int64_t)n, e->h_mc_rows, e->dindex, e->d_mc.p, stride, planes, s, &vp, recs ? e->d_mcodes.p : nullptr)) {
       e->mc_valid = false, cv.mx_valid = false;
       e->mc_pending.clear();
       return KT_OK;
@@ -102,6 +105,8 @@ int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc
     e->mc_pending.clear();
   }
   mc.mw = e->d_mc.p, mc.stride = stride, mc.planes = planes;
+  // (the refresh path found the records' buffer as the build left it: both are reserved together, for the same capacity)
+  if (recs && e->d_mcodes.p && e->d_mcodes.cap >= (size_t)stride) mc.codes = e->d_mcodes.p;
   return KT_OK;
 }
 
@@ -159,6 +164,7 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
   if (e->cfg.kernel_variant != 1 && !pod_rows && !small && !want_status && n > 0 && n <= e->cfg.pod_capacity && e->dindex.n_chunks == 1 &&
       !e->sw[kSw_FORCE_NS_ORDER] && !e->sw[kSw_CHECK_ONE_PER_CU]) {
     if ((rc = match_cache_for_scan(e, s, mc)) != KT_OK) return rc;
+    if (e->sw[kSw_NO_MATCH_CODES]) mc.codes = nullptr;  // (the records stay current; the sweep replays the planes)
   }
   {
     TimedLaunch tl(e, KT_KERNEL_CHECK, s);

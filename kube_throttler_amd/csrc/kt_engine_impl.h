@@ -142,6 +142,10 @@ struct ScanView {
   // (kt::MatchViewPlanes).  Allocated when the cached aggregate will run; gathered behind a view build, kept current by the
   // builder's write-through; mx_valid: they are the table's words for every record (void with every view build).
   DevBuf<uint64_t> mx;
+  // ... and its match-code records, mc[j] = d_mcodes[rows[j]] (cap + 1 of them), written by the launches that write mx and valid
+  // with it (mx_valid) wherever mc_there says the table keeps records
+  DevBuf<kt::MatchCodes> mc;
+  bool mc_there = false;
   uint32_t mx_planes = 0;
   bool mx_valid = false;
   DevBuf<uint32_t> range;          // record ranges of the scan's workgroups, ends at namespace boundaries (plan_wg_ranges) ...
@@ -150,7 +154,7 @@ struct ScanView {
   int64_t extra = 0;               // upper bound of the records appended since: a scan covers n + extra (zero = not countable)
   bool by_ns = false;              // ordered by namespace (multi-chunk index) / ascending rows
   bool valid = false;              // describes the current pod table
-  void release() { rows.release(); d_n.release(); meta.release(); latom.release(); req.release(); pk.release(); pos.release(); range.release(); mx.release(); mx_valid = false; }
+  void release() { rows.release(); d_n.release(); meta.release(); latom.release(); req.release(); pk.release(); pos.release(); range.release(); mx.release(); mc.release(); mx_valid = false, mc_there = false; }
 };
 // what differs between the builds of the two views
 struct ViewSpec {
@@ -214,8 +218,8 @@ extern thread_local std::string g_create_error;  // text of the last kt_engine_c
 // path is tuned to a few microseconds).  Read at the same two moments, with a VALUE instead of a flag and therefore not in the
 // table: KT_REPRIEVE_LDS_CAP (kt_engine::reprieve_lds_cap_limit, a test hook of kt_preempt_reprieve_launch and
 // kt_preempt_gangs_reprieve_launch).
-enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSw_NO_MATCH_CACHE_AGG, kSwCount };
-static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE", "KT_NO_MATCH_CACHE_AGG"};
+enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSw_NO_MATCH_CACHE_AGG, kSw_NO_MATCH_CODES, kSw_NO_MATCH_CODES_AGG, kSwCount };
+static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE", "KT_NO_MATCH_CACHE_AGG", "KT_NO_MATCH_CODES", "KT_NO_MATCH_CODES_AGG"};
 struct kt_engine {
   bool sw[kSwCount] = {};  // EnvSwitch values (load_env_switches)
   uint32_t reprieve_lds_cap_limit = 0;  // KT_REPRIEVE_LDS_CAP (test hook, read with the switches): at most so many list entries of
@@ -261,6 +265,10 @@ struct kt_engine {
   // them first (on its own stream).  Deletes need nothing: a replay is gated by the pod's state bits, as the scan is.  Allocated by
   // the first cached scan of an eligible program.
   DevBuf<uint64_t> d_mc;                         // [mc.planes][pod_capacity]
+  // The match-code records (kt_match_codes.h): what the sweep replays of a table of at most kMatchReplay planes — one 16-byte
+  // record per pod row, written by the launches that write d_mc and valid exactly where it is (KT_NO_MATCH_CODES=1: the sweep
+  // replays the planes; the records are kept all the same, one library gives both sides of an A/B)
+  DevBuf<kt::MatchCodes> d_mcodes;               // [pod_capacity]
   int64_t* h_mc_rows = nullptr;                  // pinned: the pending rows as the refresh launch reads them (kPatchBatchMax entries)
   hipEvent_t mc_rows_ev = nullptr;               // behind the last refresh launch: the list buffer is free again
   bool mc_rows_ev_used = false;

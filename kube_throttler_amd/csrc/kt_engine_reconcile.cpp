@@ -299,10 +299,14 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
       if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));  // an earlier scan may still read the old planes
       KT_HIP(e, cv.mx.reserve(need));
     }
+    if (mc.codes && cv.mc.cap < (size_t)cv.cap + 1) {  // the view's match-code records beside its planes
+      if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+      KT_HIP(e, cv.mc.reserve((size_t)cv.cap + 1));
+    }
     const int64_t listed = std::min<int64_t>((int64_t)cv.n + cv.extra, cv.cap);
-    kt::launch_gather_match_planes(mc.mw, mc.stride, mc.planes, cv.rows.p, listed, cv.mx.p, (uint64_t)cv.cap + 1u, s);
+    kt::launch_gather_match_planes(mc.mw, mc.stride, mc.planes, cv.rows.p, listed, cv.mx.p, (uint64_t)cv.cap + 1u, s, mc.codes, cv.mc.p);
     KT_HIP(e, hipGetLastError());
-    cv.mx_planes = mc.planes, cv.mx_valid = true;
+    cv.mx_planes = mc.planes, cv.mx_valid = true, cv.mc_there = mc.codes != nullptr;
   }
   if (words && e->clean_partial != (const void*)e->partial()) KT_HIP(e, hipMemsetAsync(e->partial(), 0, words * 8, s));
   e->clean_partial = nullptr;
@@ -343,6 +347,10 @@ int32_t aggregate_locked(kt_engine* e, hipStream_t s, bool allow_fused) {
         if ((rc = slab_tags(e, sc, s)) != KT_OK) return rc;
         sc.defer_reduce = defer && sc.pk != nullptr;
         if (replay && sc.by_ns && sc.v_pk && limb == 0) sc.v_mx = cv.mx.p, sc.mx_stride = (uint64_t)cv.cap + 1u, sc.mx_planes = cv.mx_planes;
+        // ... from the view's match-code records where the table keeps them and one encoding serves both scans (the codes are cut with
+        // the SWEEP's run rule: a program whose aggregate runs differ keeps the plane replay)
+        if (sc.v_mx && mc.codes && cv.mc_there && cv.mc.p && e->dindex.runs_agree && !e->sw[kSw_NO_MATCH_CODES] && !e->sw[kSw_NO_MATCH_CODES_AGG])
+          sc.v_mc = cv.mc.p;
         const char* k = kt::launch_aggregate_indexed(e->pods, sc, e->sp, e->d_sp.p, e->dindex, target, e->d_slab.p, s,
                                                      pass == 0 ? std::function<void()>(after_scan) : std::function<void()>());
         if (sc.replayed) e->ctr_mc_agg_scans.fetch_add(1, std::memory_order_relaxed);

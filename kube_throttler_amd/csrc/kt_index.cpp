@@ -1059,6 +1059,7 @@ struct Cutter {
     for (const ChunkPlan& cp : plan_in) total_words += cp.words.size();
     out.bm_images.reserve(((size_t)Rp * total_words * 8 * fam + total_words * (sizeof(WordHdr) + 64 * 10 + 64)) * 5 / 4 + plan_in.size() * ((size_t)n_ns + 8) * 4 * 4);  // (one allocation instead of a regrowth per chunk)
     out.bm_chunk_ns.clear();
+    out.bm_runs.clear(), out.runs_agree = true;
     const uint32_t nsw = (n_ns + 31) / 32;
     out.ns_words = nsw ? nsw : 1u;
     out.bm_max_lds = 0, out.bm_max_thr = 0, out.bm_max_words = 0, out.bm_slab_bytes = 0;
@@ -1157,6 +1158,30 @@ struct Cutter {
       }
       ch.w0 = w_run;
       w_run += nw;
+      {
+        // The run masks of every word (HostIndex::bm_runs), as the scans' prologues build them by ballots: a number opens a run
+        // unless its predecessor IN THE WORD carries the same throttle (the sweep: kTermAdj, term_t row) / the same group (the
+        // aggregate: kRankAdj, rank), and closes one unless its successor does.  The table keeps the sweep's; runs_agree says
+        // whether the aggregate's are the same masks throughout.
+        out.bm_runs.resize((size_t)w_run * 2, 0ull);
+        for (uint32_t w = 0; w < nw; ++w) {
+          uint64_t t_lo = 0, t_hi = 0, r_lo = 0, r_hi = 0;
+          for (uint32_t k = 0; k < 64; ++k) {
+            const size_t c = (size_t)w * 64 + k;
+            const uint32_t tt = it[c];
+            if (!(tt & kTermReal)) continue;
+            auto same_t = [&](size_t o) { return (tt & kTermAdj) && (it[o] & kTermReal) && (it[o] & kTermAdj) && ((it[o] ^ tt) & kTermRowMask) == 0u; };
+            // (a rank entry has no `real` flag of its own: the aggregate's prologue compares the whole entry, rank and flag)
+            auto same_r = [&](size_t o) { return (ir[c] & kRankAdj) && ir[o] == ir[c]; };
+            if (!(k > 0 && same_t(c - 1))) t_lo |= 1ull << k;
+            if (!(k < 63 && same_t(c + 1))) t_hi |= 1ull << k;
+            if (!(k > 0 && same_r(c - 1))) r_lo |= 1ull << k;
+            if (!(k < 63 && same_r(c + 1))) r_hi |= 1ull << k;
+          }
+          out.bm_runs[((size_t)ch.w0 + w) * 2] = t_lo, out.bm_runs[((size_t)ch.w0 + w) * 2 + 1] = t_hi;
+          if (t_lo != r_lo || t_hi != r_hi) out.runs_agree = false;
+        }
+      }
       // planes of word columns: any[nw][Rp], then (rich) veto[veto_cols][Rp] — the columns of local words [0, nv) and the zero column
       irows.assign((size_t)Rp * (nw + veto_cols), 0ull);
       const size_t veto_plane = (size_t)Rp * nw;
@@ -1301,6 +1326,8 @@ hipError_t upload_index(const HostIndex& h, IndexDev& d, hipStream_t s) {
   if ((e = up(d.bm_rank_t, d.cap_bm_rank_t, h.bm_rank_t, s)) != hipSuccess) return e;
   if ((e = up(d.bm_chunk_ns, d.cap_bm_chunk_ns, h.bm_chunk_ns, s)) != hipSuccess) return e;
   d.ns_words = h.ns_words;
+  d.runs_agree = h.runs_agree;
+  if ((e = up(d.bm_runs, d.cap_bm_runs, h.bm_runs, s)) != hipSuccess) return e;
   if ((e = up(d.atom_table, d.cap_atom_table, h.atom_table, s)) != hipSuccess) return e;
   d.atom_mask = (uint32_t)h.atom_table.size() - 1;
   d.h_chunks = h.bm_chunks;
@@ -1316,8 +1343,9 @@ hipError_t upload_index(const HostIndex& h, IndexDev& d, hipStream_t s) {
   d.has_key_atoms = h.n_key_atoms ? 1u : 0u;
   d.la = h.la, d.rich = h.rich;
   if (getenv("KT_DEBUG_LDS"))
-    fprintf(stderr, "bitmap index: %u words, %u rows (veto %d, need %u), %zu chunks, largest LDS part %u B, largest chunk %u throttles / %u words, %zu slow throttles\n",
-            h.bm_words, h.bm_rows, (int)h.has_veto, h.max_need, h.bm_chunks.size(), h.bm_max_lds, h.bm_max_thr, h.bm_max_words, h.slow_thr.size());
+    fprintf(stderr, "bitmap index: %u words, %u rows (veto %d, need %u), %zu chunks, largest LDS part %u B, largest chunk %u throttles / %u words, %zu slow throttles, run masks of sweep and aggregate %s\n",
+            h.bm_words, h.bm_rows, (int)h.has_veto, h.max_need, h.bm_chunks.size(), h.bm_max_lds, h.bm_max_thr, h.bm_max_words, h.slow_thr.size(),
+            h.runs_agree ? "agree" : "differ");
   return hipSuccess;
 }
 
@@ -1330,6 +1358,7 @@ void release_index(IndexDev& d) {
   if (d.nogroup) (void)hipFree(d.nogroup);
   if (d.grp_arrive) (void)hipFree(d.grp_arrive);
   if (d.bm_chunk_ns) (void)hipFree(d.bm_chunk_ns);
+  if (d.bm_runs) (void)hipFree(d.bm_runs);
   if (d.atom_table) (void)hipFree(d.atom_table);
   d = IndexDev();
 }

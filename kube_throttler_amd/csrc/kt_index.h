@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "kt_device.h"
+#include "kt_match_codes.h"
 
 namespace kt {
 
@@ -160,6 +161,12 @@ struct HostIndex {
   std::vector<uint32_t> thr_ngrp;          // [T] groups (= ranks = slab records) of every throttle row (index_group_counts)
   std::vector<uint32_t> nogroup;           // throttle rows without any group: not live, or on the slow list
   std::vector<uint32_t> bm_chunk_ns;       // [chunks][ns_words] bit n: namespace n has words in the chunk
+  // The run masks of the PreFilter sweep per image word (BmChunk::w0 + local word): {seg_lo, seg_hi} = lowest / highest number of
+  // every run of one THROTTLE's terms (kTermAdj, same term_t row) — what the wordwise consumers apply as match_run_rule
+  // (kt_match_codes.h).  A side table, not part of the images: the builder of the match-code records stages it.
+  std::vector<uint64_t> bm_runs;           // [img_words][2]
+  // ... and whether the aggregate's runs — terms of one GROUP (kRankAdj, same term_rank) — are the same masks in every word
+  bool runs_agree = true;
   uint32_t ns_words = 0;                   // 32-bit words per row of bm_chunk_ns
   uint32_t bm_max_lds = 0, bm_max_thr = 0, bm_max_words = 0;
   uint64_t bm_slab_bytes = 0;  // aggregate scratch: one table per (chunk, workgroup)
@@ -271,6 +278,9 @@ struct IndexDev {
   size_t cap_thr_ngrp = 0, cap_nogroup = 0, cap_grp_arrive = 0;
   uint32_t* bm_chunk_ns = nullptr;
   uint32_t ns_words = 0;
+  uint64_t* bm_runs = nullptr;       // HostIndex::bm_runs
+  bool runs_agree = true;            // HostIndex::runs_agree
+  size_t cap_bm_runs = 0;
   uint64_t* atom_table = nullptr;
   uint32_t atom_mask = 0;
   std::vector<BmChunk> h_chunks;     // host copy (launch planning)
@@ -340,10 +350,13 @@ uint32_t check_word_lds(int D);  // check: bytes per 64-bit word of term numbers
 // in view order they are requested with the record (profiles/agg_match_cache.txt).
 constexpr int kMatchPlanes = 8;   // planes the table and its builder take
 constexpr int kMatchReplay = 4;   // planes the cached sweep holds in registers: programs with longer lists are not cached
+static_assert((uint32_t)kMatchReplay == kMatchCodeLists, "a match code names a list position in two bits");
 struct MatchCacheArgs {
   const uint64_t* mw = nullptr;  // nullptr: no table (the scans run scan_tile)
   uint64_t stride = 0;           // words per plane (the engine's pod capacity)
   uint32_t planes = 0;           // planes in use: the longest namespace word list of the program (<= kMatchPlanes)
+  const MatchCodes* codes = nullptr;  // [stride] the match-code record of every pod row (kt_match_codes.h), current wherever the planes
+                                      // are; nullptr: the sweep replays the planes (KT_NO_MATCH_CODES=1)
   mutable bool used = false;     // out: the launch replayed the table
 };
 // The planes of the countable scan view's records, plane-major with the view's record capacity (+ 1) as the stride.  Written by
@@ -352,6 +365,7 @@ struct MatchCacheArgs {
 // kt_patch_scan_views claims a row while it appends its record is gone when that launch has ended, and the builder runs behind it).
 struct MatchViewPlanes {
   uint64_t* mx = nullptr;        // nullptr: the view keeps no planes
+  MatchCodes* mc = nullptr;      // the view's match-code records, [stride] (nullable: the table keeps none)
   const int32_t* pos = nullptr;  // pod row -> record
   uint64_t stride = 0;           // words per plane
 };
@@ -382,6 +396,7 @@ struct AggScan {
   const uint64_t* v_mx = nullptr;  // the view's planes of the match cache (MatchViewPlanes), current for this launch — the two-per-CU
   uint64_t mx_stride = 0;          //   form then replays them instead of scanning the selectors (nullptr: scan)
   uint32_t mx_planes = 0;
+  const MatchCodes* v_mc = nullptr;  // ... and the view's match-code records, where the aggregate replays those (cached=2 in KT_DEBUG_LDS)
   mutable bool replayed = false;   // out: the launch replayed the planes
   mutable int launched_blocks = 0;  // out: workgroups (= slabs per chunk) of the scan launch
   mutable bool launched_packed = false;
@@ -460,10 +475,13 @@ bool check_replays_match_cache(const PodTable& pods, const SelProgram& sp, const
 // (re)writes the planes of pod rows [0, n) (rows_dev == nullptr) or of the n listed rows; false: not dispatchable
 // view (nullable): the planes of the countable scan view, written through for every row that has a record
 bool launch_build_match_cache(const PodTable& pods, int64_t n, const int64_t* rows_dev, const IndexDev& ix, uint64_t* mw, uint64_t stride,
-                              uint32_t planes, hipStream_t s, const MatchViewPlanes* view = nullptr);
+                              uint32_t planes, hipStream_t s, const MatchViewPlanes* view = nullptr, MatchCodes* codes = nullptr);
 // mx[k][j] = mw[k][rows[j]] for the n listed records of a freshly built view (the table must be current on s)
+// (codes / vmc nullable: vmc[j] = codes[rows[j]] as well)
 void launch_gather_match_planes(const uint64_t* mw, uint64_t stride, uint32_t planes, const int64_t* rows, int64_t n, uint64_t* mx,
-                                uint64_t mx_stride, hipStream_t s);
+                                uint64_t mx_stride, hipStream_t s, const MatchCodes* codes = nullptr, MatchCodes* vmc = nullptr);
+// can kt_build_match_cache write match-code records for this program (its run masks fit LDS beside the image)?
+bool match_codes_fit(const IndexDev& ix, uint32_t planes);
 int check_sweep_blocks(int64_t n);  // workgroups of a namespace-ordered lean sweep over n pod rows (one per CU)
 // the per-word check tables of the whole index in global memory: TermInfo [total_words][64], then WordVerdict [total_words]
 // (total_words = HostIndex::bm_words) — built once per generation of CheckRecs instead of once per (workgroup, chunk)

@@ -498,6 +498,11 @@ __global__ __launch_bounds__(kBlockIx) void kt_aggregate_bitmap(const BmAggArgs 
 //         programs.  (The first tile of a wave stays BEHIND the prologue's barrier: requested ahead of it, the step was measured
 //         1.2 us slower at 1M pods, profiles/agg_match_cache.txt section 2 — as reasoned there, the tile's loads then stand in
 //         front of the staging loads in the wave's in-order load counter and the prologue waits for HBM instead of L2.)
+// CODES (with CACHED): the form replays the view's match-code RECORDS (kt_match_codes.h; a.v_mc[j], view order) instead of its planes:
+//         per code the rank of term 64 w + bit and the LDS fold — the run rule is in the codes (the engine hands records over only
+//         where the sweep's runs and the aggregate's are the same masks: HostIndex::runs_agree), so the word queue, off_seg and the
+//         run-mask prologue leave this form.  A tile in which some counted lane's header says "more than 15" is replayed from the
+//         planes, every lane of it, plane by plane with the run masks of the index's side table (correct, not fast).
 struct BmAggOneArgs {
   const uint64_t* v_meta;  // the scan view: record j = meta word, atom row, packed request words
   const uint16_t* v_latom;
@@ -505,6 +510,8 @@ struct BmAggOneArgs {
   const uint64_t* v_mx;    // CACHED: the view's planes of the match cache, [mx_planes][mx_stride]
   uint64_t mx_stride;
   uint32_t mx_planes;
+  const MatchCodes* v_mc;  // CODES: the view's match-code records ...
+  const uint64_t* runs;    // ... and the {seg_lo, seg_hi} of the chunk's words for the tiles that fall back to the planes (nullable: no runs)
   unsigned char* slab;     // this chunk's slab area
   BmIndexArgs ix;
   BmChunk ch;              // the chunk's descriptor by value
@@ -515,9 +522,10 @@ struct BmAggOneArgs {
 };
 __device__ __forceinline__ uint32_t agg_one_rec_off(uint32_t r, uint32_t rec, uint32_t skew) { return __umul24(r, rec) + (skew ? (r >> 3) << 3 : 0u); }
 
-template <bool VETO, int NEED, bool CACHED = false>
+template <bool VETO, int NEED, bool CACHED = false, bool CODES = false>
 __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmAggOneArgs a) {
   static_assert(!CACHED || (!VETO && NEED == 2), "the cached form is one instantiation: nothing of the scan's form is left in it");
+  static_assert(!CODES || CACHED, "records are a form of the match cache");
   // (the word queue: four words beside the simple scan, three beside the rich one — its veto plane and 2-bit counters take the
   //  registers of the fourth: 20 B of scratch with it)
   constexpr int LA = 8, NW = 3, kWq = VETO ? 3 : 4;
@@ -542,7 +550,10 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
     Rec r{};
     const uint32_t ic = min(wt * kWave + lane, n_rows - 1u);
     r.meta = a.v_meta[ic];
-    if constexpr (CACHED) {
+    if constexpr (CODES) {
+      const u64x2 rc = *(const u64x2*)(a.v_mc + ic);  // (one 16-byte load: the record's two halves)
+      r.mx[0] = rc.x, r.mx[1] = rc.y;
+    } else if constexpr (CACHED) {
       const uint64_t* q = a.v_mx + ic;
 #pragma unroll
       for (int j = 0; j < kMatchReplay; ++j)
@@ -566,7 +577,7 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
     const StageSeg segs[2] = {img, StageSeg{a.off_rank, (const u32x4*)(a.ix.blob + ch.img_off + ch.off_term_rank), ch.n_words * 8u}};
     lds_stage_segments<2, 4>(lds, segs);
   }
-  if (ch.has_adj) {  // (see kt_aggregate_bitmap: lowest / highest number of every run of one group's terms)
+  if (ch.has_adj && !CODES) {  // (see kt_aggregate_bitmap: lowest / highest number of every run of one group's terms)
     const uint16_t* g_rank = (const uint16_t*)(a.ix.blob + ch.img_off + ch.off_term_rank);
     for (uint32_t w = wave; w < ch.n_words; w += (uint32_t)(kBlockIx / kWave)) {
       const uint32_t tr = g_rank[w * 64u + lane];
@@ -595,6 +606,54 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
     unsigned long long pw[NW];
 #pragma unroll
     for (int k = 0; k < NW; ++k) pw[k] = cur.pw[k];
+    if constexpr (CODES) {
+      auto fold = [&](bool has, uint32_t c) {  // one matched term of the lane: its group's record takes the pod's packed words
+        const uint32_t r = trank[has ? c : 0u] & 0x7FFFu;
+        if (has) {
+          KT_LDS unsigned char* rp = tab + agg_one_rec_off(r, rec, skew);
+          lds_u64wp tv = (lds_u64wp)rp;
+          lds_add64(tv, pw[0]);
+          if (pk_nw > 1u) lds_add64(tv + 1, pw[1]);
+          if (pk_nw > 2u) lds_add64(tv + 2, pw[2]);
+          if (zero_keys) (void)__hip_atomic_fetch_or((lds_u32wp)(rp + pk_nw * 8u), zero_keys, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      };
+      const u32x2 rng = bm.nsl_rng[ns];
+      const uint32_t len = counted ? min(rng.y - rng.x, a.mx_planes) : 0u;
+      // the word numbers of the lane's list as 16-bit fields, one batch of LDS reads (entries past the list's end: entry 0, never named)
+      uint32_t wn[kMatchReplay];
+#pragma unroll
+      for (int k = 0; k < kMatchReplay; ++k) wn[k] = bm.nsl[(uint32_t)k < len ? rng.x + (uint32_t)k : 0u].w;
+      const uint32_t w01 = wn[0] | wn[1] << 16, w23 = wn[2] | wn[3] << 16;
+      auto word_of = [&](uint32_t k) { const uint32_t wp = (k & 2u) ? w23 : w01; return (k & 1u) ? wp >> 16 : wp & 0xFFFFu; };
+      const uint32_t hdr = (uint32_t)cur.mx[0] & 0xFFu;
+      if (__ballot(counted && hdr == kMatchCodesOverflow) == 0ull) {
+        const uint32_t mine = counted ? hdr : 0u;
+        uint64_t lo = cur.mx[0] >> 8 | cur.mx[1] << 56, hi = cur.mx[1] >> 8;  // the record without its header: the next code in the low byte
+        for (uint32_t i = 0; __ballot(i < mine) != 0ull; ++i) {
+          const uint32_t cd = (uint32_t)lo & 0xFFu;
+          lo = lo >> 8 | hi << 56, hi >>= 8;
+          fold(i < mine, word_of(cd >> 6) * 64u + (cd & 63u));
+        }
+      } else {
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.mx_planes; ++k) {
+          const uint32_t ic = min(wt * kWave + lane, n_rows - 1u);
+          uint64_t x = k < len ? a.v_mx[(uint64_t)k * a.mx_stride + ic] : 0ull;
+          const uint32_t w = word_of(k);
+          if (a.runs) {
+            const uint64_t* sg = a.runs + 2u * (k < len ? w : 0u);
+            x = match_run_rule(x, sg[0], sg[1]);
+          }
+          while (__ballot(x != 0ull) != 0ull) {
+            const bool has = x != 0ull;
+            const uint32_t c = has ? w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u : 0u;
+            x &= x - 1ull;
+            fold(has, c);
+          }
+        }
+      }
+    } else {
     // the word queue of kt_aggregate_bitmap's packed fold
     uint64_t qx[kWq];
     typedef typename std::conditional<(kWq > 3), uint64_t, uint32_t>::type qw_t;  // word numbers, 10 bits each, newest lowest
@@ -651,6 +710,7 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_aggregate_bitmap_one(const BmA
       scan_tile<LA, VETO, NEED, false>(bm, counted, ns, ro, [&](bool, uint32_t) {}, [&](uint32_t) { return true; }, push_word, run_masks);
     }
     flush();
+    }
   }
   __syncthreads();  // spill the table as this workgroup's slab: the plain array of records, coalesced 16-byte stores
   const uint32_t slab_pitch = (ch.n_thr * rec + 15u) & ~15u;
@@ -897,20 +957,26 @@ const char* launch_aggregate_indexed(const PodTable& pods, const AggScan& sc, co
     const bool cached = sc.v_mx != nullptr && sc.limb == 0 && sc.mx_planes >= 1u && sc.mx_planes <= (uint32_t)kMatchReplay &&
                         (uint64_t)n_rows <= sc.mx_stride && match_cache_fits(ix);
     if (cached) oa.v_mx = sc.v_mx, oa.mx_stride = sc.mx_stride, oa.mx_planes = sc.mx_planes;
+    // ... and its records (the engine: only where the two scans' run rules are the same masks)
+    const bool codes = cached && sc.v_mc != nullptr && (!ch.has_adj || ix.bm_runs != nullptr);
+    if (codes) oa.v_mc = sc.v_mc, oa.runs = ch.has_adj ? ix.bm_runs + (size_t)ch.w0 * 2 : nullptr;
     oa.slab = slab + (size_t)ch.slab_off * 16;
     oa.n_rows = (uint32_t)n_rows;
     oa.tpb = (uint32_t)((((n_rows + kWave - 1) / kWave) + nb - 1) / nb);
     static const bool dbg_one = getenv("KT_DEBUG_LDS") != nullptr;
     if (dbg_one)
       fprintf(stderr, "kt_aggregate_bitmap_one: lds=%u (2 per CU) workgroups=%d tiles per workgroup=%u nw=%u rec=%u skew=%u cached=%d\n", one_total, nb,
-              oa.tpb, oa.pk_nw, oa.pk_rec, oa.skew, cached ? 1 : 0);
+              oa.tpb, oa.pk_nw, oa.pk_rec, oa.skew, codes ? 2 : cached ? 1 : 0);
 #define KT_AGG_ONE_LAUNCH(VETO_, NEED_, ...)                                                                     \
   {                                                                                                             \
     auto kfn = kt_aggregate_bitmap_one<VETO_, NEED_, ##__VA_ARGS__>;                                            \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)one_total);    \
     hipLaunchKernelGGL(kfn, g_, b_, one_total, s, oa);                                                          \
   }
-    if (cached) {
+    if (codes) {
+      KT_AGG_ONE_LAUNCH(false, 2, true, true)
+      sc.replayed = true;
+    } else if (cached) {
       KT_AGG_ONE_LAUNCH(false, 2, true)
       sc.replayed = true;
     } else {

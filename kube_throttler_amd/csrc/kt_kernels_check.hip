@@ -741,6 +741,8 @@ struct BmCheckCachedArgs {
   const uint8_t* ns_valid;
   const uint64_t* mw;          // the match cache: [planes][mw_stride], indexed by pod row
   uint64_t mw_stride;
+  const MatchCodes* codes;     // CODES: the match-code record of every pod row (kt_match_codes.h) ...
+  const uint64_t* runs;        // ... and the {seg_lo, seg_hi} of the chunk's words, for the tiles that fall back to the planes
   const unsigned char* blob;   // chunk images
   BmChunk ch;                  // the chunk's descriptor by value
   uint32_t n;
@@ -751,20 +753,32 @@ static_assert(kTermRowMask == (1u << 20) - 1u && kWave == 64, "a list entry is l
 
 // LDS of the form: cnt[64] per wave, the list, TermInfo + WordVerdict, the image (only its namespace lists are staged, at
 // their usual offsets)
-static BmCheckCachedArgs make_check_cached_args(const IndexDev& ix, uint32_t* total) {
+static BmCheckCachedArgs make_check_cached_args(const IndexDev& ix, uint32_t* total, bool codes = false) {
   BmCheckCachedArgs a{};
   uint32_t o = 0;
   auto take = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
   a.off_cnt = take(kBlockIx * 8u);
   a.off_list = take((kBlockIx / kWave) * kListCap * 4);
   a.off_tinfo = take(ix.bm_max_words * 64u * 8u);
-  a.off_wv = take(ix.bm_max_words * (uint32_t)sizeof(WordVerdict<8>));
+  a.off_wv = take(codes ? 0u : ix.bm_max_words * (uint32_t)sizeof(WordVerdict<8>));  // (the code form settles through TermInfo alone)
   a.lds_img = take(ix.bm_max_lds);
   *total = o;
   return a;
 }
 
-template <int PL>
+// CODES: the form that replays the match-code RECORD of a pod row (kt_match_codes.h) instead of its planes: 16 bytes per row
+// where PL planes are 8 PL, and the terms arrive as codes — the run rule already applied, no mask to peel.  Per code the lane
+// takes the word number of list position k (the up to four numbers of its namespace's list are read once per tile, as one batch,
+// and kept as 16-bit fields), reads TermInfo[64 w + bit] and either lists the match (kTiTight) or counts it by the counter shift
+// TermInfo names for the pod's non-zero mask: what settle_word derives from the WordVerdict masks, term by term — so the prologue
+// builds TermInfo only, and WordVerdict leaves the form's LDS.  The loop runs to the largest count of the tile, two codes per
+// round.  A tile in which some lane's record says "more than 15" (wave-uniform) is replayed from the planes, every lane of it:
+// plane by plane, loaded where they are used (correct, not fast: no row of the flagship programs has more than 13 terms), the
+// run rule from the index's side table in global memory, every bit through the same per-term step.
+// (A wave's tile requested one tile AHEAD of its use — the first before the prologue, every further one when its predecessor's
+//  replay begins; 50-52 VGPRs, no scratch — was built on this form and measured: 1.2 us per step SLOWER on configs[2] and [3],
+//  profiles/match_codes.txt section 2.  Not kept.)
+template <int PL, bool CODES = false>
 __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCheckCachedArgs a) {
   static_assert(PL >= 1 && PL <= kMatchReplay, "one instantiation per plane count");
   constexpr int DT = 8;
@@ -785,6 +799,25 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
   BmIndexArgs ixa{};
   ixa.blob = a.blob, ixa.lds_img = a.lds_img;
   const BmView bm = open_chunk<false>(lds, ixa, ch);
+  struct Rec {
+    uint64_t meta;
+    uint64_t mx[CODES ? 2 : kMatchReplay];  // CODES: the record's two halves
+  };
+  // (ld_issued: every load of a record stands where it is written — the planes are not moved behind the meta word's arrival)
+  auto fetch_tile = [&](uint32_t wt) {  // always from valid addresses: lanes past the end re-read the last row and are off
+    Rec r{};
+    const uint32_t ic = min(wt * kWave + lane, n - 1u);
+    r.meta = ld_issued(a.meta + ic);
+    if constexpr (CODES) {
+      const uint64_t* q = (const uint64_t*)(a.codes + ic);
+      r.mx[0] = ld_issued(q), r.mx[1] = ld_issued(q + 1);
+    } else {
+      const uint64_t* q = a.mw + ic;
+#pragma unroll
+      for (int j = 0; j < PL; ++j) r.mx[j] = ld_issued(q + (uint64_t)j * a.mw_stride);
+    }
+    return r;
+  };
   // ---- prologue, as the generic form's: the first term word of every thread AHEAD of the image's tail, the tables built in place
   {
     const uint32_t* term_t = (const uint32_t*)(a.blob + ch.img_off + ch.off_term_t);
@@ -793,25 +826,11 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
     const StageSeg segs[1] = {StageSeg{a.lds_img + ch.off_nsl_rng, (const u32x4*)(a.blob + ch.img_off + ch.off_nsl_rng), (ch.lds_bytes - ch.off_nsl_rng) / 16u}};
     lds_stage_segments<1>(lds, segs);
     for (uint32_t c = threadIdx.x; c < ch.n_words * 64u; c += kBlockIx)
-      build_term_verdicts<DT, true>(c == threadIdx.x ? tt_first : term_t[c], c, g_rflags, tinfo, (KT_LDS WordVerdict<DT>*)(lds + a.off_wv));
+      build_term_verdicts<DT, !CODES>(c == threadIdx.x ? tt_first : term_t[c], c, g_rflags, tinfo, (KT_LDS WordVerdict<DT>*)(lds + a.off_wv));
   }
   __syncthreads();
   const bool seg_on = ch.has_adj != 0u;  // wave-uniform: some throttle of the chunk has several terms
 
-  struct Rec {
-    uint64_t meta;
-    uint64_t mx[kMatchReplay];
-  };
-  // (ld_issued: every load of a record stands where it is written — the planes are not moved behind the meta word's arrival)
-  auto fetch_tile = [&](uint32_t wt) {  // always from valid addresses: lanes past the end re-read the last row and are off
-    Rec r{};
-    const uint32_t ic = min(wt * kWave + lane, n - 1u);
-    r.meta = ld_issued(a.meta + ic);
-    const uint64_t* q = a.mw + ic;
-#pragma unroll
-    for (int j = 0; j < PL; ++j) r.mx[j] = ld_issued(q + (uint64_t)j * a.mw_stride);
-    return r;
-  };
   for (uint32_t wt = blockIdx.x * (kBlockIx / kWave) + wave; wt < n_wtiles; wt += wstep) {
     const Rec r = fetch_tile(wt);
     cnt[lane] = 0ull;
@@ -891,31 +910,100 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
       // affectedClusterThrottles: the pod's Namespace object must exist (clusterthrottle_controller.go:273-276)
       // (the byte is requested here and looked at behind the replay)
       const uint32_t ns_ok_raw = a.ns_valid[ns];
-      auto nib_offset = [&](int q) { return (uint32_t)offsetof(WordVerdict<DT>, act_nib) + (uint32_t)q * 128u + ((nz >> (4 * q)) & 15u) * 8u; };
-      uint32_t n_exc = 0u, n_act = 0u, n_ins = 0u;
-      auto settle_word = [&](uint32_t w, uint64_t x, int) -> uint64_t {
-        KT_LDS const unsigned char* q = wv + __umul24(w, (uint32_t)sizeof(WordVerdict<DT>));
-        if (seg_on) {  // a throttle with several terms is reported once: the lowest match of every run
-          const u64x2 seg = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, seg_lo));
-          const uint64_t v = x | seg.y;
-          x = andn_64(x, v - seg.x);  // (= x & (v ^ (v - seg_lo)) & v, x being part of v)
-        }
-        const u64x2 te = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, tight));  // {tight, exc}
-        const u64x2 ai = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, act));    // {act, ins}
-        uint64_t act = *(KT_LDS const unsigned long long*)(q + nib_offset(0));  // (act-by-count is part of every entry of nibble 0's table)
+      // (what the lane settles by itself, as it sits in cnt[lane]: << 4 exceeds, << 24 active, << 44 insufficient)
+      unsigned long long my = 0ull;
+      if constexpr (CODES) {
+        const u32x2 rng = bm.nsl_rng[ns];
+        const uint32_t len = on ? min(rng.y - rng.x, (uint32_t)PL) : 0u;
+        // the word numbers of the lane's list, one batch of LDS reads (entries past the list's end read entry 0 and are never named)
+        uint32_t wn[PL];
 #pragma unroll
-        for (int k = 1; k < DT / 4; ++k) act |= *(KT_LDS const unsigned long long*)(q + nib_offset(k));
-        const uint64_t xe = and_not_and_64(x, te.x, te.y);  // not tight, exceeded by count
-        const uint64_t xf = and_not_not_64(x, te.x, te.y);  // settled here, not exceeded by count
-        const uint64_t xa = xf & act, xi = and_not_and_64(xf, act, ai.y);
-        n_exc = (uint32_t)__popc((uint32_t)xe) + ((uint32_t)__popc((uint32_t)(xe >> 32)) + n_exc);
-        n_act = (uint32_t)__popc((uint32_t)xa) + ((uint32_t)__popc((uint32_t)(xa >> 32)) + n_act);
-        n_ins = (uint32_t)__popc((uint32_t)xi) + ((uint32_t)__popc((uint32_t)(xi >> 32)) + n_ins);
-        return x & te.x;
-      };
-      replay_tile(bm, on, ns, r.mx, (uint32_t)PL, [&](bool has, uint32_t c) { push(has, lane << 20 | c); }, settle_word, ScanNoPrefetch());
-      // what the lane settled joins what drains have brought and will bring (counters from bit 4 up; bit 0: on, bit 1: Error)
-      const unsigned long long my = (unsigned long long)n_exc << 4 | (unsigned long long)n_act << 24 | (unsigned long long)n_ins << 44;
+        for (int k = 0; k < PL; ++k) wn[k] = bm.nsl[(uint32_t)k < len ? rng.x + (uint32_t)k : 0u].w;
+        static_assert(kTermRowMask >> 6 <= 0xFFFFu, "a word number is a 16-bit field");
+        const uint32_t w01 = wn[0] | (PL > 1 ? wn[PL > 1 ? 1 : 0] << 16 : 0u), w23 = (PL > 2 ? wn[PL > 2 ? 2 : 0] : 0u) | (PL > 3 ? wn[PL > 3 ? 3 : 0] << 16 : 0u);
+        // one matched term c of the lane (has): listed when its throttle is tight, else counted where TermInfo says
+        auto term = [&](bool has, uint32_t c, const u32x2 ti) {
+          const bool tight = (ti.y & kTiTight) != 0u;
+          const uint32_t sh = (nz & ti.y & 0xFFFFu) ? (ti.y >> kTiShActive) & 63u : (ti.y >> kTiShIdle) & 63u;
+          if (has && !tight && sh != 0u) my += 1ull << sh;  // (shift 0: not throttled, nothing to count)
+          push(has && tight, lane << 20 | c);
+        };
+        const uint32_t hdr = (uint32_t)r.mx[0] & 0xFFu;
+        if (__ballot(on && hdr == kMatchCodesOverflow) == 0ull) {
+          const uint32_t mine = on ? hdr : 0u;  // (a row without a valid pod may hold the record of the pod that left it)
+          // the largest count of the tile, bit by bit from the top (counts are 0..15): scalar
+          uint32_t top = 0u;
+          uint64_t among = ~0ull;
+#pragma unroll
+          for (int b = 3; b >= 0; --b) {
+            const uint64_t t = __ballot((mine >> b) & 1u) & among;
+            if (t != 0ull) among = t, top |= 1u << b;
+          }
+          uint64_t lo = r.mx[0] >> 8 | r.mx[1] << 56, hi = r.mx[1] >> 8;  // the record without its header: the next code in the low byte
+          auto number = [&](uint32_t cd) {  // code -> term number
+            const uint32_t wp = (cd & 0x80u) ? w23 : w01;
+            return ((cd & 0x40u) ? wp >> 16 : wp & 0xFFFFu) * 64u + (cd & 63u);
+          };
+          // codes per round: their TermInfo reads travel together (one per round: +0.4 us per step on configs[2], four: +0.8 us and
+          // five spilled SGPRs — profiles/match_codes.txt section 2)
+          constexpr uint32_t UN = 2;
+          for (uint32_t i = 0; i < top; i += UN) {
+            uint32_t c[UN];
+            u32x2 t[UN];
+#pragma unroll
+            for (uint32_t u = 0; u < UN; ++u) c[u] = number((uint32_t)(lo >> (8u * u)) & 0xFFu);
+            lo = lo >> (8u * UN) | hi << (64u - 8u * UN), hi >>= 8u * UN;
+#pragma unroll
+            for (uint32_t u = 0; u < UN; ++u) t[u] = tinfo[i + u < mine ? c[u] : 0u];
+#pragma unroll
+            for (uint32_t u = 0; u < UN; ++u) term(i + u < mine, c[u], t[u]);
+          }
+        } else {
+#pragma unroll 1
+          for (uint32_t k = 0; k < (uint32_t)PL; ++k) {
+            const uint32_t ic = min(wt * kWave + lane, n - 1u);
+            uint64_t x = k < len ? a.mw[(uint64_t)k * a.mw_stride + ic] : 0ull;
+            const uint32_t wp = (k & 2u) ? w23 : w01;
+            const uint32_t w = (k & 1u) ? wp >> 16 : wp & 0xFFFFu;
+            if (seg_on) {
+              const uint64_t* sg = a.runs + 2u * (k < len ? w : 0u);
+              x = match_run_rule(x, sg[0], sg[1]);
+            }
+            while (__ballot(x != 0ull) != 0ull) {
+              const bool has = x != 0ull;
+              const uint32_t c = has ? w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u : 0u;
+              x &= x - 1ull;
+              term(has, c, tinfo[c]);
+            }
+          }
+        }
+      } else {
+        auto nib_offset = [&](int q) { return (uint32_t)offsetof(WordVerdict<DT>, act_nib) + (uint32_t)q * 128u + ((nz >> (4 * q)) & 15u) * 8u; };
+        uint32_t n_exc = 0u, n_act = 0u, n_ins = 0u;
+        auto settle_word = [&](uint32_t w, uint64_t x, int) -> uint64_t {
+          KT_LDS const unsigned char* q = wv + __umul24(w, (uint32_t)sizeof(WordVerdict<DT>));
+          if (seg_on) {  // a throttle with several terms is reported once: the lowest match of every run
+            const u64x2 seg = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, seg_lo));
+            const uint64_t v = x | seg.y;
+            x = andn_64(x, v - seg.x);  // (= x & (v ^ (v - seg_lo)) & v, x being part of v)
+          }
+          const u64x2 te = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, tight));  // {tight, exc}
+          const u64x2 ai = *(KT_LDS const u64x2*)(q + offsetof(WordVerdict<DT>, act));    // {act, ins}
+          uint64_t act = *(KT_LDS const unsigned long long*)(q + nib_offset(0));  // (act-by-count is part of every entry of nibble 0's table)
+#pragma unroll
+          for (int k = 1; k < DT / 4; ++k) act |= *(KT_LDS const unsigned long long*)(q + nib_offset(k));
+          const uint64_t xe = and_not_and_64(x, te.x, te.y);  // not tight, exceeded by count
+          const uint64_t xf = and_not_not_64(x, te.x, te.y);  // settled here, not exceeded by count
+          const uint64_t xa = xf & act, xi = and_not_and_64(xf, act, ai.y);
+          n_exc = (uint32_t)__popc((uint32_t)xe) + ((uint32_t)__popc((uint32_t)(xe >> 32)) + n_exc);
+          n_act = (uint32_t)__popc((uint32_t)xa) + ((uint32_t)__popc((uint32_t)(xa >> 32)) + n_act);
+          n_ins = (uint32_t)__popc((uint32_t)xi) + ((uint32_t)__popc((uint32_t)(xi >> 32)) + n_ins);
+          return x & te.x;
+        };
+        replay_tile(bm, on, ns, r.mx, (uint32_t)PL, [&](bool has, uint32_t c) { push(has, lane << 20 | c); }, settle_word, ScanNoPrefetch());
+        // what the lane settled joins what drains have brought and will bring (counters from bit 4 up; bit 0: on, bit 1: Error)
+        my = (unsigned long long)n_exc << 4 | (unsigned long long)n_act << 24 | (unsigned long long)n_ins << 44;
+      }
       cnt[lane] += my | (on ? 1ull : 0ull) | ((on && ns_ok_raw == 0u) ? 2ull : 0ull);
     }
     if (n_list) drain(std::integral_constant<int, 2>());
@@ -930,22 +1018,26 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
 static void launch_check_cached(const PodTable& pods, int64_t n, const SelProgram& sp, const IndexDev& ix, const void* recs, uint64_t* summary,
                                 const MatchCacheArgs& mc, dim3 grid, hipStream_t s) {
   uint32_t total = 0;
-  BmCheckCachedArgs a = make_check_cached_args(ix, &total);
+  const bool codes = mc.codes != nullptr && (!ix.h_chunks[0].has_adj || ix.bm_runs != nullptr);
+  BmCheckCachedArgs a = make_check_cached_args(ix, &total, codes);
   // (the form's footprint is the generic two-per-CU form's without its tile counter, so two of them fit where the caller found
   //  that form to fit; a list entry is lane << 20 | term number, as in the generic kernel)
   assert(2u * total <= (uint32_t)kMaxLds && (uint64_t)ix.bm_max_words * 64u <= (uint64_t)kTermRowMask + 1u);
   a.meta = pods.meta, a.req = pods.req, a.recs = recs, a.summary = summary, a.ns_valid = sp.ns_valid;
   a.mw = mc.mw, a.mw_stride = mc.stride;
+  if (codes) a.codes = mc.codes, a.runs = ix.bm_runs ? ix.bm_runs + (size_t)ix.h_chunks[0].w0 * 2 : nullptr;
   a.blob = ix.bm_blob, a.ch = ix.h_chunks[0];
   a.n = (uint32_t)n, a.DS = pods.DS, a.T = sp.T;
   static const bool dbg_lds = getenv("KT_DEBUG_LDS") != nullptr;
-  if (dbg_lds) fprintf(stderr, "kt_check_bitmap_cached: lds=%u (2 per CU) workgroups=%u planes=%u\n", total, grid.x, mc.planes);
-#define KT_CHECK_CACHED_LAUNCH(PL_)                                                                             \
+  if (dbg_lds) fprintf(stderr, "kt_check_bitmap_cached: lds=%u (2 per CU) workgroups=%u planes=%u %s\n", total, grid.x, mc.planes, codes ? "match codes" : "planes");
+#define KT_CHECK_CACHED_LAUNCH_(PL_, CODES_)                                                                    \
   {                                                                                                             \
-    auto kfn = kt_check_bitmap_cached<PL_>;                                                                     \
+    auto kfn = kt_check_bitmap_cached<PL_, CODES_>;                                                             \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);        \
     hipLaunchKernelGGL(kfn, grid, dim3(kBlockIx), total, s, a);                                                 \
   }
+#define KT_CHECK_CACHED_LAUNCH(PL_) \
+  { if (codes) KT_CHECK_CACHED_LAUNCH_(PL_, true) else KT_CHECK_CACHED_LAUNCH_(PL_, false) }
   static_assert(kMatchReplay == 4, "one instantiation per plane count");
 #ifdef KT_FAST_BUILD
   KT_CHECK_CACHED_LAUNCH(kMatchReplay)  // (the caller dispatches the form for tables of exactly that many planes)
@@ -958,6 +1050,7 @@ static void launch_check_cached(const PodTable& pods, int64_t n, const SelProgra
   }
 #endif
 #undef KT_CHECK_CACHED_LAUNCH
+#undef KT_CHECK_CACHED_LAUNCH_
 }
 
 #define KT_BM_LAUNCH(DT_, LA_, VETO_, NEED_, WPE_, FULL_, SMALL_, ONE_)                                         \

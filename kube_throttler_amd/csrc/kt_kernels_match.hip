@@ -16,6 +16,10 @@ namespace kt {
 // Write-through (a.vx != nullptr): the countable scan view keeps the planes of its records in scan order (MatchViewPlanes,
 // kt_index.h) and every word stored for a row goes to the row's record as well — the row -> record table is read once per lane,
 // beside the meta word.
+// Match-code records (a.mc != nullptr; kt_match_codes.h): the lane also applies the sweep's run rule to every word it stores — the
+// run masks of the chunk's words are staged from the index's side table (BmIndexArgs-independent: a.runs) beside the image —
+// appends the codes of what is left to a record in registers and stores the record once behind the scan.  A row without a
+// valid pod gets count 0, a row listed twice stores the same record twice.  Only for tables of at most kMatchReplay planes.
 // ---------------------------------------------------------------------------------------------------
 struct MatchBuildArgs {
   const uint64_t* meta;
@@ -29,6 +33,10 @@ struct MatchBuildArgs {
   uint64_t* vx;      // nullable: the view's planes ...
   const int32_t* vpos;  // ... its row -> record table (-1: no record) ...
   uint64_t vstride;  // ... and its words per plane: a record at or beyond it is skipped
+  MatchCodes* vmc;       // nullable: the view's match-code records (write-through beside vx)
+  MatchCodes* mc;        // nullable: the match-code record of every pod row ...
+  const uint64_t* runs;  // ... and the {seg_lo, seg_hi} of the chunk's words they are cut with (nullable: no throttle has several terms)
+  uint32_t off_runs;     // ... in LDS
   BmIndexArgs ix;
   BmChunk ch;
 };
@@ -41,9 +49,11 @@ __global__ __launch_bounds__(kBlockIx) void kt_build_match_cache(const MatchBuil
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const BmChunk& ch = a.ch;
   {
-    const StageSeg segs[1] = {chunk_image_segment(a.ix, ch)};
-    lds_stage_segments<1, 4>(lds, segs);
+    const StageSeg segs[2] = {chunk_image_segment(a.ix, ch), StageSeg{a.off_runs, (const u32x4*)a.runs, a.runs ? ch.n_words : 0u}};
+    lds_stage_segments<2, 4>(lds, segs);
   }
+  const bool codes = a.mc != nullptr, seg_on = a.runs != nullptr;  // wave-uniform
+  KT_LDS const u64x2* runs = (KT_LDS const u64x2*)(lds + a.off_runs);
   const BmView bm = open_chunk<VETO>(lds, a.ix, ch);
   __syncthreads();
   const uint32_t n = a.n, planes = a.planes;
@@ -68,14 +78,29 @@ __global__ __launch_bounds__(kBlockIx) void kt_build_match_cache(const MatchBuil
     const bool thru = in && vj >= 0 && (uint64_t)vj < a.vstride;  // (false everywhere without a view: vj = -1)
     uint64_t* qv = a.vx + (thru ? (uint32_t)vj : 0u);
     uint32_t round = 0u;  // wave-uniform
+    MatchCodes rec{0ull, 0ull};
     scan_tile<LA, VETO, NEED, false>(
         bm, on, ns, ro, [&](bool, uint32_t) {}, [&](uint32_t) { return true; },
-        [&](uint32_t, uint64_t xx, int) -> uint64_t {
+        [&](uint32_t w, uint64_t xx, int) -> uint64_t {
           if (in && round < planes) q[(uint64_t)round * a.stride] = xx;
           if (thru && round < planes) qv[(uint64_t)round * a.vstride] = xx;
+          if (codes && round < kMatchCodeLists) {  // (a lane that did not advance has xx = 0; its w is stale but in range)
+            uint64_t x = xx;
+            if (seg_on) {
+              const u64x2 seg = runs[w];
+              x = match_run_rule(x, seg.x, seg.y);
+            }
+            while (x) {  // lane-divergent: a handful of bits
+              const uint32_t bit = (uint32_t)__ffsll((unsigned long long)x) - 1u;
+              x &= x - 1ull;
+              match_codes_append(rec, match_code(round, bit));
+            }
+          }
           round += 1u;
           return 0ull;
         });
+    if (codes && in) a.mc[pc] = rec;
+    if (codes && thru && a.vmc) a.vmc[(uint32_t)vj] = rec;
     for (; round < planes; ++round) {  // the planes past the longest list of the tile
       if (in) q[(uint64_t)round * a.stride] = 0ull;
       if (thru) qv[(uint64_t)round * a.vstride] = 0ull;
@@ -84,8 +109,9 @@ __global__ __launch_bounds__(kBlockIx) void kt_build_match_cache(const MatchBuil
 }
 
 // kt_gather_match_planes — the planes of a freshly built countable view: mx[k][j] = mw[k][rows[j]], thread = record
+// (codes / vmc, nullable: and the row's match-code record, vmc[j] = codes[rows[j]])
 __global__ __launch_bounds__(256) void kt_gather_match_planes(const uint64_t* mw, uint64_t stride, uint32_t planes, const int64_t* rows, int64_t n,
-                                                             uint64_t* mx, uint64_t mx_stride) {
+                                                             uint64_t* mx, uint64_t mx_stride, const MatchCodes* codes, MatchCodes* vmc) {
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
     const uint64_t p = (uint64_t)rows[j];
     if (p >= stride) continue;  // (never: the list holds rows of the pod table)
@@ -95,13 +121,15 @@ __global__ __launch_bounds__(256) void kt_gather_match_planes(const uint64_t* mw
 #pragma unroll
     for (int k = 0; k < kMatchReplay; ++k)
       if ((uint32_t)k < planes) mx[(uint64_t)k * mx_stride + (uint64_t)j] = x[k];
+    if (vmc) vmc[j] = codes[p];
   }
 }
 void launch_gather_match_planes(const uint64_t* mw, uint64_t stride, uint32_t planes, const int64_t* rows, int64_t n, uint64_t* mx,
-                                uint64_t mx_stride, hipStream_t s) {
+                                uint64_t mx_stride, hipStream_t s, const MatchCodes* codes, MatchCodes* vmc) {
   if (n <= 0 || !mw || !mx || planes == 0u || planes > (uint32_t)kMatchReplay || (uint64_t)n > mx_stride) return;
   const int64_t nb = std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(kt_gather_match_planes, dim3((unsigned)nb), dim3(256), 0, s, mw, stride, planes, rows, n, mx, mx_stride);
+  hipLaunchKernelGGL(kt_gather_match_planes, dim3((unsigned)nb), dim3(256), 0, s, mw, stride, planes, rows, n, mx, mx_stride, codes,
+                     codes ? vmc : nullptr);
 }
 
 bool match_cache_fits(const IndexDev& ix) {
@@ -110,19 +138,35 @@ bool match_cache_fits(const IndexDev& ix) {
   return !ch.has_slow && ch.n_words != 0u && ix.bm_max_lds <= (uint32_t)kMaxLds;
 }
 
+bool match_codes_fit(const IndexDev& ix, uint32_t planes) {
+  if (!match_cache_fits(ix) || planes == 0u || planes > (uint32_t)kMatchReplay) return false;
+  const BmChunk& ch = ix.h_chunks[0];
+  if (!ch.has_adj) return true;
+  // the image (16-byte granules) and the run masks of the chunk's words behind it
+  return ix.bm_runs != nullptr && ((ix.bm_max_lds + 15u) & ~15u) + ch.n_words * 16u <= (uint32_t)kMaxLds;
+}
+
 bool launch_build_match_cache(const PodTable& pods, int64_t n, const int64_t* rows_dev, const IndexDev& ix, uint64_t* mw, uint64_t stride,
-                              uint32_t planes, hipStream_t s, const MatchViewPlanes* view) {
+                              uint32_t planes, hipStream_t s, const MatchViewPlanes* view, MatchCodes* codes) {
   if (n <= 0) return true;
   if (!match_cache_fits(ix) || pods.LA > 8 || !mw || planes == 0u || planes > (uint32_t)kMatchPlanes || stride == 0u || n > (int64_t)stride)
     return false;
   MatchBuildArgs a{};
   a.meta = pods.meta, a.latom = pods.latom, a.rows = rows_dev, a.mw = mw, a.stride = stride, a.planes = planes;
   a.n = (uint32_t)n, a.cap = (uint32_t)std::min<uint64_t>(stride, 0x80000000ull);
-  if (view && view->mx && view->pos && view->stride) a.vx = view->mx, a.vpos = view->pos, a.vstride = view->stride;
+  if (view && view->mx && view->pos && view->stride) a.vx = view->mx, a.vpos = view->pos, a.vstride = view->stride, a.vmc = view->mc;
   uint32_t o = 0;
   auto take = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
   plan_bitmap_index(ix, a.ix, take);
   a.ch = ix.h_chunks[0];
+  // (records only where match_codes_fit says so — the engine asks the same question before it hands the buffer over; a program
+  //  whose run masks do not fit beside its image keeps its planes and gets no records)
+  if (codes && match_codes_fit(ix, planes)) {
+    a.mc = codes;
+    if (a.ch.has_adj) a.runs = ix.bm_runs + (size_t)a.ch.w0 * 2, a.off_runs = take(a.ch.n_words * 16u);
+  } else {
+    a.vmc = nullptr;
+  }
   const uint32_t lds_bytes = o;
   const int64_t tiles = (n + kWave - 1) / kWave, per_wg = kBlockIx / kWave;
   const int64_t nb = std::min<int64_t>((tiles + per_wg - 1) / per_wg, 2 * kCUs);

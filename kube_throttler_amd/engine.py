@@ -43,7 +43,7 @@ EXPORTS = [
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
-    "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_paged_preempt_gangs",
+    "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -296,6 +296,9 @@ def lib():
         L.kt_partial_layout.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 5
         L.kt_debug_reload_env.argtypes = [C.c_void_p]
         L.kt_debug_match_planes.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        if hasattr(L, "kt_debug_match_codes"):  # (KT_ENGINE_LIB may name an older build: the A/B runs of tools/gpu_ab.sh)
+            L.kt_debug_match_runs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            L.kt_debug_match_codes.argtypes =[C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.kt_affected_pods.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.kt_paged_check.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.kt_paged_reconcile.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_int32,
@@ -541,6 +544,24 @@ class Engine:
         rows = np.zeros(cap, dtype=np.int64)
         self._ck(lib().kt_debug_match_planes(self._h, int(view), cap, out.ctypes.data, rows.ctypes.data if view else None, C.byref(n), C.byref(planes)))
         return out[:, :int(n.value)], (rows[:int(n.value)] if view else None)
+
+    def match_codes(self, view=False):
+        """kt_debug_match_codes: (records[n, 16] as bytes, rows) — the match-code record of every pod row (byte 0: the count 0..15
+        or 0xFF for "read the planes"; bytes 1..15: codes k << 6 | bit, ascending), or (view=True) of every record of the countable
+        scan view, with the pod row of each.  EngineError (not ready) where there is nothing current to copy."""
+        n = C.c_int64()
+        self._ck(lib().kt_debug_match_codes(self._h, int(view), 0, None, None, C.byref(n)))
+        cap = max(int(n.value), 1)
+        out = np.zeros((cap, 16), dtype=np.uint8)
+        rows = np.zeros(cap, dtype=np.int64)
+        self._ck(lib().kt_debug_match_codes(self._h, int(view), cap, out.ctypes.data, rows.ctypes.data if view else None, C.byref(n)))
+        return out[:int(n.value)], (rows[:int(n.value)] if view else None)
+
+    def match_runs(self, ns_row, k):
+        """kt_debug_match_runs: (word, seg_lo, seg_hi) of plane k for the pods of namespace row ns_row (word -1: the list is shorter)."""
+        w, lo, hi = C.c_int32(), C.c_uint64(), C.c_uint64()
+        self._ck(lib().kt_debug_match_runs(self._h, int(ns_row), int(k), C.byref(w), C.byref(lo), C.byref(hi)))
+        return int(w.value), int(lo.value), int(hi.value)
 
     def index_stats(self) -> dict:
         """The compiled selector index (after the first launch): LDS-sized chunks, 64-bit words of term numbers, namespace rows,
