@@ -578,9 +578,9 @@ int32_t kt_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, uint8_t* 
  *      Slots: those of kt_forecast_launch — the ONE check slot, its dry finalize drops a pending reconcile report, a pending
  *      kt_aggregate_launch keeps its sums, a pending preempt result of any of the four kinds stays fetchable.  The result SHARES
  *      the one pending forecast result, as the gang preempt calls share the preempt result: a later kt_forecast_launch,
- *      kt_forecast_gangs_launch or kt_paged_forecast on the engine replaces it.  kt_forecast_fetch after a gang launch answers
+ *      kt_forecast_gangs_launch, kt_paged_forecast or kt_paged_forecast_gangs on the engine replaces it.  kt_forecast_fetch after a gang launch answers
  *      KT_ERR_NOT_READY, and so does kt_forecast_gangs_fetch after a plain or paged launch.  kt_forecast_gangs_fetch synchronises.
- *      Out of scope: more than KT_MAX_DIMS resource names (a later kt_paged_forecast_gangs), several ranks. -------------------- */
+ *      More than KT_MAX_DIMS resource names: kt_paged_forecast_gangs.  Out of scope: several ranks. ---------------------------- */
 int32_t kt_forecast_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_inst,
                                  const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, void* stream);
 int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first /* [n_gangs], nullable */,
@@ -842,6 +842,49 @@ int32_t kt_paged_preempt_gangs(kt_engine* const* pages, int32_t n_pages, int64_t
 int32_t kt_paged_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
                           const int32_t* inst_ns, int32_t on_equal, int64_t* out_first /* [n], nullable */,
                           uint8_t* out_verdicts /* [n][n_inst], nullable */);
+/* kt_forecast_gangs_launch + kt_forecast_gangs_fetch over pages, synchronous: what they return for the gangs [gang_off[g],
+ * gang_off[g + 1]) of pod_rows on the cluster of ALL names.  The definition (R_t, the dry kt_admit_gangs_launch of the one gang,
+ * Reserve, verdicts, first, blocker) is kt_forecast_gangs_launch's; the rules about pages are kt_paged_forecast's (ONE check of page
+ * 0 over pod_rows, `stored` and `calc_at_any` as an OR over the pages, `differs` as an OR over EVERY page, the throttle reads
+ * status.calculatedThreshold on every page iff calc_at_any || differs) and kt_paged_preempt_gangs' (an admitted member reserves on
+ * EVERY page, each page from its own stored reserved row: the value of every name of that page it carries, the presence of all
+ * of them, and on page 0 count + 1; the pod count is judged on page 0 only; the blocker is the minimum over throttles AND pages of
+ * the first stopped queue position — the first member that stops on some page has met exact reserved prefixes there, and no page
+ * stops an earlier one).
+ * The answer is NOT a combination of existing calls.  The members' own paged forecasts do not compose: each admitted member reserves
+ * against the throttles the later members meet (two members asking 3 each of a page-1 name with `used` 4 under a spec of 8: each
+ * member alone passes at every instant, the gang only inside an override of 10).  The pages' own gang forecasts do not compose
+ * either: the calculated threshold is replaced as a whole, so a page that holds nothing the gang requests can replace the
+ * threshold for the pages that do, at some instants and not at others.
+ * Identities:
+ *   - n_pages == 1 returns byte for byte what kt_forecast_gangs_launch + kt_forecast_gangs_fetch return on that engine;
+ *   - a gang of one pod reports byte for byte what kt_paged_forecast reports for that pod (blocker: its own position where it is
+ *     not Success);
+ *   - with inst = [now], out_first[g] == 0 exactly where kt_paged_preempt_gangs at `now` with no candidates reports prefix 0, and
+ *     out_blocker[g][0] equals its out_blocker[g].
+ * On page 0's stream, in order: that check; for every page its dense aggregate and its dry finalize at t_0; the copies of the gang
+ * offsets and the page descriptors; one launch of kt_forecast_gangs_paged (csrc/kt_kernels_forecast_gangs_paged.hip: one wave per
+ * gang, lane = instant position; per throttle and block of 64 instants one pass over the pages' overrides that settles `differs`,
+ * skipped where calc_at_any holds, and one pass that walks the members once per page); the copies out.  out_first [n_gangs],
+ * out_verdicts and out_blocker [n_gangs][n_inst] are all nullable.
+ * Refused before anything is launched, and before any page's check slot, reconcile report or result buffer is touched, the
+ * instants first: what kt_forecast_gangs_launch refuses about its arguments (n_inst < 1, instants that are not strictly ascending,
+ * an inst_ns outside [0, 10^9), a missing array, every gang_off defect, a pod named twice within ONE gang: KT_ERR_INVALID_ARGUMENT;
+ * a pod row outside a page's capacity, n x throttle_rows or n_gangs x n_inst above 2^31: KT_ERR_OUT_OF_RANGE), what kt_paged_forecast
+ * refuses about the page set (different throttle-row counts, an engine named twice: KT_ERR_INVALID_ARGUMENT; different devices:
+ * KT_ERR_UNSUPPORTED) and about every page's engine (a KT_VARIANT_INCREMENTAL engine, an exchange world above 1, a `used` wider
+ * than int64: KT_ERR_UNSUPPORTED) — as there, the one thing that may run first is a page's kernel that sums the |requests|.
+ * n == 0 is allowed only with n_gangs == 0: KT_OK, nothing is launched.  Locking and ordering are kt_paged_admit's.
+ * Slots: kt_paged_forecast's.  The call uses page 0's check slot and page 0's forecast result buffers and hands the results out:
+ * afterwards no forecast result of either kind is pending on page 0 (kt_forecast_fetch and kt_forecast_gangs_fetch answer
+ * KT_ERR_NOT_READY) while a pending preempt result of page 0 stays fetchable; every page's pending reconcile report is dropped; a
+ * pending kt_aggregate_launch of any page keeps its sums.  The call is a dry run: stored status and reserved amounts of no page
+ * change.  A device error after the first launch is returned once the stream has drained; no page keeps a pending result.
+ * Out of scope: several ranks. */
+int32_t kt_paged_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                const int64_t* gang_off, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal,
+                                int64_t* out_first /* [n_gangs], nullable */, uint8_t* out_verdicts /* [n_gangs][n_inst], nullable */,
+                                int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

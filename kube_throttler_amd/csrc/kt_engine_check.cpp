@@ -1299,7 +1299,8 @@ int32_t kt_paged_preempt_gangs(kt_engine* const* pages, int32_t n_pages, int64_t
 // ---------------------------------------------------------------------------------------------------
 // forecast: the first instant at which a blocked pod passes (kt_kernels_forecast.hip)
 // ---------------------------------------------------------------------------------------------------
-// what kt_forecast_launch and kt_forecast_gangs_launch refuse about their instants (and a missing array), in front of everything else
+// what kt_forecast_launch, kt_forecast_gangs_launch and kt_paged_forecast_gangs refuse about their instants (and a missing array), in
+// front of everything else
 static int32_t forecast_instants_valid(kt_engine* e, bool rows_missing, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns) {
   if (n_inst < 1) return e->fail(KT_ERR_INVALID_ARGUMENT, "forecast: n_inst = %lld", (long long)n_inst);
   if (rows_missing || !inst_s || !inst_ns) return e->fail(KT_ERR_INVALID_ARGUMENT, "forecast: pod_rows / inst_s / inst_ns missing");
@@ -1596,6 +1597,123 @@ int32_t kt_paged_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, c
   if (out_verdicts && (herr = hipMemcpyAsync(out_verdicts, e0->d_forecast_verdicts.p, ver, hipMemcpyDeviceToHost, s)) != hipSuccess)
     return finish(e0->fail(KT_ERR_DEVICE, "paged forecast: %s", hipGetErrorString(herr)));
   return finish(KT_OK);  // (synchronises s; the results have been handed out: no forecast result is pending on page 0)
+}
+
+// ---------------------------------------------------------------------------------------------------
+// forecast for gangs over pages: kt_forecast_gangs_launch + kt_forecast_gangs_fetch on the cluster of all names
+// (kt_kernels_forecast_gangs_paged.hip)
+// ---------------------------------------------------------------------------------------------------
+// kt_paged_forecast's scaffolding with forecast_gangs_locked's gang arguments: the instants first, then the gang defects and "a pod
+// twice" asked per gang, then the page set and every page's engine.
+int32_t kt_paged_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                const int64_t* gang_off, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal,
+                                int64_t* out_first, uint8_t* out_verdicts, int64_t* out_blocker) {
+  if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  PageLocks locks;
+  int32_t rc = paged_lock("paged forecast gangs", pages, n_pages, n, locks);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = pages[0];
+  // ---- refusals: nothing is launched and no slot of any page is touched before the last of them
+  if (int32_t bad = forecast_instants_valid(e0, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) return bad;
+  if ((rc = gangs_valid(e0, n, n_gangs, gang_off)) != KT_OK) return rc;
+  {
+    // gangs are judged independently: a pod may be in several of them, but not twice in one (it would reserve twice)
+    std::vector<int64_t> sorted;
+    for (int64_t g = 0; g < n_gangs; ++g) {
+      sorted.assign(pod_rows + gang_off[g], pod_rows + gang_off[g + 1]);
+      std::sort(sorted.begin(), sorted.end());
+      for (size_t j = 1; j < sorted.size(); ++j)
+        if (sorted[j] == sorted[j - 1])
+          return e0->fail(KT_ERR_INVALID_ARGUMENT, "forecast gangs: pod row %lld is in gang %lld twice", (long long)sorted[j], (long long)g);
+    }
+  }
+  if ((rc = paged_same_cluster("paged forecast gangs", pages, n_pages, n, pod_rows)) != KT_OK) return rc;  // (the rows are range-checked in place)
+  const int32_t T = e0->thr_rows_hi;
+  if ((double)n * (double)T > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "forecast gangs: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  if ((double)n_gangs * (double)n_inst > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "forecast gangs: n_gangs x n_inst = %lld x %lld exceeds 2^31 verdict bytes", (long long)n_gangs,
+                    (long long)n_inst);
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if (e->incremental) return e->fail(KT_ERR_UNSUPPORTED, "forecast gangs: page %d: not for KT_VARIANT_INCREMENTAL engines", k);
+    if (e->exchange_world > 1)
+      return e->fail(KT_ERR_UNSUPPORTED, "forecast gangs: page %d exchanges partials with %d ranks (one rank only)", k, e->exchange_world);
+    if (e->wide && e->req_sums_valid)
+      return e->fail(KT_ERR_UNSUPPORTED, "forecast gangs: `used` of page %d is wider than int64 (kt_forecast_gangs_paged reads int64 sums)", k);
+  }
+  if (n == 0) return KT_OK;  // (no gangs) nothing is launched
+  hipStream_t s = nullptr;
+  if ((rc = paged_order(pages, n_pages, &s)) != KT_OK) return rc;
+  if ((rc = ensure_ready(e0, s)) != KT_OK) return rc;
+  // the |request| sums probe of every page where the sums are not known, before the check slot, a reconcile report or a result
+  // buffer of any page is touched (as kt_paged_forecast)
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if ((rc = request_sums_in_range(e, s)) != KT_OK) return rc;
+    if (e->wide)
+      return e->fail(KT_ERR_UNSUPPORTED, "forecast gangs: `used` of page %d is wider than int64 (kt_forecast_gangs_paged reads int64 sums)", k);
+  }
+  // ---- from here on the call owns page 0's check slot and forecast result and every page's reconcile report
+  e0->forecast_ready = false, e0->forecast_gangs = false;
+  if (!e0->preempt_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->preempt_pages_ev, hipEventDisableTiming));
+  KT_HIP(e0, hipEventSynchronize(e0->preempt_pages_ev));  // the previous call's copy has read h_preempt_pages
+  e0->h_preempt_pages.assign((size_t)n_pages, kt::PreemptPage{});
+  const size_t ver = (size_t)n_gangs * (size_t)n_inst;
+  if (e0->d_forecast_first.cap < (size_t)n_gangs || e0->d_forecast_verdicts.cap < ver + 1 || e0->d_forecast_blocker.cap < ver ||
+      e0->d_forecast_inst_s.cap < (size_t)n_inst || e0->d_forecast_inst_ns.cap < (size_t)n_inst ||
+      e0->d_forecast_gang_off.cap < (size_t)n_gangs + 1) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_forecast_gangs_launch)
+    if (e0->last_stream) KT_HIP(e0, hipStreamSynchronize(e0->last_stream));
+    KT_HIP(e0, e0->d_forecast_first.reserve((size_t)n_gangs));
+    KT_HIP(e0, e0->d_forecast_verdicts.reserve(ver + 1));
+    KT_HIP(e0, e0->d_forecast_blocker.reserve(ver));
+    KT_HIP(e0, e0->d_forecast_inst_s.reserve((size_t)n_inst));
+    KT_HIP(e0, e0->d_forecast_inst_ns.reserve((size_t)n_inst));
+    KT_HIP(e0, e0->d_forecast_gang_off.reserve((size_t)n_gangs + 1));
+  }
+  KT_HIP(e0, e0->d_preempt_pages.reserve(sizeof(kt::PreemptPage) * (size_t)n_pages));
+  // Everything below runs on page 0's stream.  A failure after the first launch drains that stream before it is returned, and
+  // pages 1.. get their own stream back as last_stream: nothing of this call stays pending on any page.
+  std::vector<hipStream_t> last((size_t)n_pages);
+  for (int32_t k = 0; k < n_pages; ++k) last[(size_t)k] = pages[k]->last_stream;
+  auto finish = [&](int32_t code) -> int32_t { return paged_finish("paged forecast gangs", pages, n_pages, s, last, code); };
+  hipError_t herr = hipSuccess;
+  // the instants and the offsets travel on the same stream, behind an earlier forecast's kernel (the call returns behind finish:
+  // the caller's memory is not referenced afterwards)
+  if ((herr = hipMemcpyAsync(e0->d_forecast_inst_s.p, inst_s, (size_t)n_inst * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
+      (herr = hipMemcpyAsync(e0->d_forecast_inst_ns.p, inst_ns, (size_t)n_inst * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
+      (herr = hipMemcpyAsync(e0->d_forecast_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast gangs: %s", hipGetErrorString(herr)));
+  // ONE check of page 0 over the members of all gangs: which throttles affect which pod, and the error rows.  The preempt result
+  // lives in buffers this call does not write: it stays fetchable
+  const bool preempt_was_ready = e0->preempt_ready;
+  rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e0->check_ready = false;  // the slot holds this call's rows (as with kt_paged_forecast): a pending kt_check_launch is gone
+  e0->preempt_ready = preempt_was_ready;
+  if (rc != KT_OK) return finish(rc);
+  // every page: its dense aggregate beside its partial buffer and its dry finalize at t_0 (its reconcile report is dropped)
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if ((rc = preempt_reconcile_locked(e, inst_s[0], inst_ns[0], s)) != KT_OK) return finish(rc);
+    kt::PreemptPage& pp = e0->h_preempt_pages[(size_t)k];
+    pp.pg = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+    pp.partial = e->d_preempt_partial.p, pp.calc = e->d_out_calc.tab(), pp.calc_updated = e->d_out_calc_updated.p, pp.error = e->d_out_error.p;
+  }
+  if (!kt::launch_forecast_gangs_paged(e0->h_preempt_pages.data(), n_pages, (kt::PreemptPage*)e0->d_preempt_pages.p, e0->preempt_pages_ev, n_gangs,
+                                       n_inst, e0->d_rows.p, e0->d_forecast_gang_off.p, e0->d_forecast_inst_s.p, e0->d_forecast_inst_ns.p, T,
+                                       on_equal != 0, e0->d_status.p, e0->d_summary.p, e0->d_forecast_first.p, e0->d_forecast_verdicts.p,
+                                       e0->d_forecast_blocker.p, s, &herr))
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast gangs: copy of the page descriptors: %s", hipGetErrorString(herr)));
+  if ((herr = hipGetLastError()) != hipSuccess) return finish(e0->fail(KT_ERR_DEVICE, "paged forecast gangs: %s", hipGetErrorString(herr)));
+  e0->last_stream = s;
+  if (out_first && (herr = hipMemcpyAsync(out_first, e0->d_forecast_first.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast gangs: %s", hipGetErrorString(herr)));
+  if (out_verdicts && (herr = hipMemcpyAsync(out_verdicts, e0->d_forecast_verdicts.p, ver, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast gangs: %s", hipGetErrorString(herr)));
+  if (out_blocker && (herr = hipMemcpyAsync(out_blocker, e0->d_forecast_blocker.p, ver * 8, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return finish(e0->fail(KT_ERR_DEVICE, "paged forecast gangs: %s", hipGetErrorString(herr)));
+  return finish(KT_OK);  // (synchronises s; the results have been handed out: no forecast result of either kind is pending on page 0)
 }
 
 // Host-only: the instants in (from, until] at which some valid and responsible throttle's CalculateThreshold can change — every

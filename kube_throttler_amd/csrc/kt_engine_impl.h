@@ -376,7 +376,8 @@ struct kt_engine {
   DevBuf<unsigned char> d_reprieve_ws;  // kt_preempt_reprieve's and kt_preempt_gangs_reprieve's list state where it outgrows LDS (kt::reprieve_ws_bytes)
   bool preempt_ready = false;
   int64_t preempt_n = 0, preempt_m = 0;
-  // kt_paged_preempt, kt_paged_preempt_gangs and kt_paged_forecast (on page 0): the page descriptors of the paged kernels, on the device
+  // kt_paged_preempt, kt_paged_preempt_gangs, kt_paged_forecast and kt_paged_forecast_gangs (on page 0): the page descriptors of the
+  // paged kernels, on the device
   // and — the source of an asynchronous copy, under the rule of h_admit_pages with preempt_pages_ev in admit_pages_ev's place —
   // on the host
   DevBuf<uint8_t> d_preempt_pages;
@@ -397,6 +398,7 @@ struct kt_engine {
   int64_t forecast_n = 0, forecast_m = 0;
   // kt_forecast_gangs_launch shares that one pending result (first and verdict bytes per GANG, forecast_n = the gangs); the kind
   // tag says which fetch may read it.  Its offsets and the blocking member per gang and instant live in buffers of their own
+  // (kt_paged_forecast_gangs writes them on page 0 too and hands the results out itself: no kind is pending afterwards)
   bool forecast_gangs = false;
   DevBuf<int64_t> d_forecast_gang_off, d_forecast_blocker;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap

@@ -40,26 +40,6 @@ struct GangsPagedArgs {
   int64_t* blocker;         // [n_gangs] out (the prefix kernel)
 };
 
-// what gang_walk reads of one page
-struct GangPageView {
-  AdmitPage pg;
-  const int64_t* rows;
-  const uint8_t* status;
-  int32_t T;
-};
-
-// the names of page `pg` some member of [i0, i1) that throttle t affects requests with a non-zero value (wave-uniform loads)
-__device__ __forceinline__ uint32_t gang_page_requested(const AdmitPage& pg, const int64_t* rows, const uint8_t* status, int T, uint32_t t, int64_t i0,
-                                                        int64_t i1) {
-  uint32_t need = 0;
-  for (int64_t i = i0; i < i1; ++i) {
-    if (status[i * (int64_t)T + t] == 0) continue;
-    const int64_t p = rows[i];
-    for (int d = 0; d < pg.D; ++d) need |= pg.req[p * pg.DS + d] != 0 ? 1u << d : 0u;
-  }
-  return need;
-}
-
 template <int DT>
 __global__ __launch_bounds__(kWave) void kt_preempt_gangs_paged(const PreemptPagedArgs a, const GangsPagedArgs ga) {
   __shared__ uint32_t chunk_list[kPreemptChunk];

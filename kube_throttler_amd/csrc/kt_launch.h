@@ -197,6 +197,13 @@ void launch_forecast_gangs(const AdmitPage& pg, int64_t n_gangs, int64_t m, cons
                            const int64_t* inst_s, const int32_t* inst_ns, int T, bool on_equal, const uint8_t* status, const uint64_t* summary,
                            const unsigned long long* partial, const uint8_t* error, int64_t* first, uint8_t* verdicts, int64_t* blocker,
                            hipStream_t s);
+// ... over n_pages >= 1 pages (kt_kernels_forecast_gangs_paged.hip): the descriptors of launch_forecast_paged, copied to pages_dev and
+// guarded by pages_copied as there; status / summary: ONE check of page 0 over rows_dev [n], the members of all gangs; first
+// [n_gangs], verdicts [n_gangs][m] and blocker [n_gangs][m] out, on page 0.  false: the copy failed (*hip_err)
+bool launch_forecast_gangs_paged(const PreemptPage* pages, int n_pages, PreemptPage* pages_dev, hipEvent_t pages_copied, int64_t n_gangs, int64_t m,
+                                 const int64_t* rows_dev, const int64_t* gang_off_dev, const int64_t* inst_s, const int32_t* inst_ns, int T,
+                                 bool on_equal, const uint8_t* status, const uint64_t* summary, int64_t* first, uint8_t* verdicts, int64_t* blocker,
+                                 hipStream_t s, hipError_t* hip_err);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

@@ -41,6 +41,27 @@ __device__ __forceinline__ void paged_thr_facts(const PreemptPage* pages, int n_
   *stored = st, *use_calc = uc;
 }
 
+// ---- what the gang kernels over pages share (kt_kernels_preempt_gangs_paged.hip, kt_kernels_forecast_gangs_paged.hip) ------------------
+// what gang_walk reads of one page
+struct GangPageView {
+  AdmitPage pg;
+  const int64_t* rows;
+  const uint8_t* status;
+  int32_t T;
+};
+
+// the names of page `pg` some member of [i0, i1) that throttle t affects requests with a non-zero value (wave-uniform loads)
+__device__ __forceinline__ uint32_t gang_page_requested(const AdmitPage& pg, const int64_t* rows, const uint8_t* status, int T, uint32_t t, int64_t i0,
+                                                        int64_t i1) {
+  uint32_t need = 0;
+  for (int64_t i = i0; i < i1; ++i) {
+    if (status[i * (int64_t)T + t] == 0) continue;
+    const int64_t p = rows[i];
+    for (int d = 0; d < pg.D; ++d) need |= pg.req[p * pg.DS + d] != 0 ? 1u << d : 0u;
+  }
+  return need;
+}
+
 // ---- the reprieve pass -------------------------------------------------------------------------------------------------------
 struct ReprievePagedArgs {
   const PreemptPage* pages;  // [n_pages] in device memory, as the prefix kernel read them

@@ -1102,6 +1102,84 @@ def paged_forecast_of(snaps, pod_row, instants, on_equal=False, ctx=None):
     return next((k for k in range(m) if not fails[k]), -1), verdicts_
 
 
+# ---- forecast for gangs over pages (kt_paged_forecast_gangs): the closed form over a list of page snapshots ----
+def paged_forecast_gangs_of(snaps, member_rows, instants, on_equal=False, ctx=None):
+    """kt_paged_forecast_gangs for one gang, in closed form over the page snapshots (no GPU) -> (first, verdicts [len(instants)],
+    blockers [len(instants)]): ``forecast_gangs_of`` on the cluster of all names.  ``paged_forecast_of``'s threshold per throttle and
+    instant — the whole-error rule and the whole-threshold rule, `differs` over EVERY page — met by the members under the per-page
+    reserved prefix of ``paged_preempt_gangs_of``: names are keyed (page, dim), each page's prefix starts from its own stored
+    reserved row, a member the throttle affects adds its value of every name it carries, the presence of all of them and count +
+    1, and the pod count (threshold, `used`, reserved) is page 0's, judged once.  Which throttles affect which member and "a member
+    is an Error or invalid" are page 0's.  ``ctx`` is ``paged_preempt_context``'s (any ``now``: only its sums and error marks are
+    read).  With one snapshot this is ``forecast_gangs_of``; with one member ``paged_forecast_of``."""
+    snap0 = snaps[0]
+    inst = [_instant(t) for t in instants]
+    ctx = paged_preempt_context(snaps, inst[0]) if ctx is None else ctx
+    members, eq, m = [int(p) for p in member_rows], bool(on_equal), len(inst)
+    g = len(members)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap0.n_pods and bool(int(snap0.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap0, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    keys = [(k, d) for k, s in enumerate(snaps) for d in range(s.D)]
+    reqs = [{(k, d): v for k, s in enumerate(snaps) for d, v in pod_requests(s, p).items()} if 0 <= p < snap0.n_pods else {}
+            for p in members]
+    stopped = [g if bad_at is None else bad_at] * m  # per instant the first member some throttle stops on some page (g: none)
+    for t in (sorted(set().union(*affected)) if affected else []):
+        th = ctx["thr"][t]
+        f = int(snap0.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _paged_amounts(snaps, "thr_reserved", t)
+        hit = [t in a for a in affected]
+        calc_at_any = any(int(s.thr_flags[t]) & S.THR_CALC_AT_NONZERO for s in snaps)
+        # the whole-error rule, as the kernel states it: the reconcile is an error on some page, or some page holds the row as not
+        # valid and responsible (pages built by hand may disagree; page 0 holds it as both, or it would not affect anybody)
+        need = S.THR_VALID | S.THR_RESPONSIBLE
+        if th["error"] or any((int(s.thr_flags[t]) & need) != need for s in snaps):  # the stored status of every page, at every instant
+            used, used_count = _paged_amounts(snaps, "thr_used", t)
+            sth = _paged_amounts(snaps, "thr_calc" if calc_at_any else "thr_spec", t)
+            names = {}
+            for k, d in keys:
+                flg = int(snaps[k].thr_thrl_flag[t]) & int(snaps[k].thr_thrl_has[t])
+                names[(k, d)] = (bool(flg >> d & 1), (k, d) in used, used.get((k, d), 0))
+            j = _gang_first_stopped(members, hit, reqs, sth, (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names),
+                                    res, res_count, eq3, eq)
+            if j is not None:
+                stopped = [min(s, j) for s in stopped]
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        spec = _paged_amounts(snaps, "thr_spec", t)
+        for i, at in enumerate(inst):
+            calc, cc, differs = {}, None, False
+            for k, s in enumerate(snaps):
+                page_names, count, any_err = _calculated_threshold(s, t, at)
+                stored, stored_count = _amount_dict(s.thr_calc, t, s.D)
+                fp = int(s.thr_spec_msgs_fp[t]) if any_err else 0
+                differs = differs or page_names != stored or int(s.thr_status_msgs_fp[t]) != fp
+                if k == 0:  # the count is the same in every page
+                    cc = count
+                    differs = differs or count != stored_count
+                calc.update({(k, d): v for d, v in page_names.items()})
+            rd = (calc, cc) if calc_at_any or differs else spec
+            names = {}
+            for kd in keys:
+                u_pr, cv = cnt.get(kd, 0) > 0, calc.get(kd)
+                names[kd] = (cv is not None and u_pr and val.get(kd, 0) >= cv, u_pr, val.get(kd, 0))
+            j = _gang_first_stopped(members, hit, reqs, rd, (cc is not None and pods > 0 and pods >= cc, pods > 0, pods, names), res, res_count,
+                                    eq3, eq)
+            if j is not None:
+                stopped[i] = min(stopped[i], j)
+    if bad_at is not None:
+        verdicts_ = [S.VERDICT_ERROR] * m
+    else:
+        verdicts_ = [S.VERDICT_BLOCK if s < g else S.VERDICT_ALLOW for s in stopped]
+    first = next((k for k in range(m) if verdicts_[k] == S.VERDICT_ALLOW), -1)
+    return first, verdicts_, [s if s < g else -1 for s in stopped]
+
+
 class PagedEngine:
     """One HIP engine per page of a ``ClusterState.build_pages()`` result; reconcile and check run on every page (the
     selector scan is repeated per page: the price of more than 16 resource names) and come back combined."""
@@ -1180,6 +1258,14 @@ class PagedEngine:
         names, through kt_paged_forecast -> (first [n], verdicts [n][n_inst] or None).  A dry run: nothing stored changes on any
         page."""
         return E.paged_forecast(self.engines, pod_rows, instants, on_equal=on_equal, want_verdicts=want_verdicts)
+
+    def forecast_gangs(self, pod_rows, gang_off, instants, on_equal=False, want_verdicts=True, want_blocker=True):
+        """The first of the strictly ascending ``instants`` at which each gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` is admitted
+        as a whole, over every page's names, through kt_paged_forecast_gangs (any number of pages; one page goes through the same
+        call) -> (first [n_gangs], verdicts [n_gangs][n_inst] or None, blocker [n_gangs][n_inst] or None).  A dry run: nothing
+        stored changes on any page."""
+        return E.paged_forecast_gangs(self.engines, pod_rows, gang_off, instants, on_equal=on_equal, want_verdicts=want_verdicts,
+                                      want_blocker=want_blocker)
 
     def override_instants(self, from_, until, cap=None):
         """kt_override_instants of page 0 -> ([(seconds, nanoseconds)], total): every page holds every override's times and parse
