@@ -165,6 +165,7 @@ static int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_r
       !e->sw[kSw_FORCE_NS_ORDER] && !e->sw[kSw_CHECK_ONE_PER_CU]) {
     if ((rc = match_cache_for_scan(e, s, mc)) != KT_OK) return rc;
     if (e->sw[kSw_NO_MATCH_CODES]) mc.codes = nullptr;  // (the records stay current; the sweep replays the planes)
+    mc.tile_pairs = !e->sw[kSw_NO_TILE_PAIRS_CHECK];
   }
   {
     TimedLaunch tl(e, KT_KERNEL_CHECK, s);

@@ -357,6 +357,7 @@ struct MatchCacheArgs {
   uint32_t planes = 0;           // planes in use: the longest namespace word list of the program (<= kMatchPlanes)
   const MatchCodes* codes = nullptr;  // [stride] the match-code record of every pod row (kt_match_codes.h), current wherever the planes
                                       // are; nullptr: the sweep replays the planes (KT_NO_MATCH_CODES=1)
+  bool tile_pairs = true;        // the code form walks a wave's tiles two at a time, one drain per pair (KT_NO_TILE_PAIRS_CHECK=1: singles)
   mutable bool used = false;     // out: the launch replayed the table
 };
 // The planes of the countable scan view's records, plane-major with the view's record capacity (+ 1) as the stride.  Written by

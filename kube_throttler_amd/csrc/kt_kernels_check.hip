@@ -731,8 +731,9 @@ __global__ __launch_bounds__(kBlockIx, WPE) void kt_check_bitmap(const BmCheckAr
 // A tile's loads are one batch (ld_issued, kt_scan.h): the planes stand beside the meta word, not behind its arrival.  What a lane
 // settled in the replay joins the drain's counters in cnt[lane] — with `on` as bit 0 and the Error verdict as bit 1 — and the
 // summary word is cut from that word: no lane state but the counters is live across the drain.
-// (Two tiles of a wave in flight together with ONE drain per pair were built on this body and measured: they fit 64 VGPRs up to
-//  three planes only, and configs[2] and [3] have four — profiles/tile_pairs.txt, NEXT.md section 3.)
+// (Two tiles of a wave in flight together with ONE drain per pair were built on the PLANE form of this body and measured: they fit
+//  64 VGPRs up to three planes only, and configs[2] and [3] have four — profiles/tile_pairs.txt.  The CODE form below walks tile
+//  pairs: a record is three 8-byte words — profiles/tile_pairs_codes.txt.)
 struct BmCheckCachedArgs {
   const uint64_t* meta;        // pod tables
   const int64_t* req;
@@ -748,16 +749,17 @@ struct BmCheckCachedArgs {
   uint32_t n;
   int32_t DS, T;
   uint32_t lds_img, off_cnt, off_list, off_tinfo, off_wv;
+  uint32_t pairs;              // PAIRS: a wave walks its tiles two at a time; 0: singles from the same kernel (KT_NO_TILE_PAIRS_CHECK=1)
 };
-static_assert(kTermRowMask == (1u << 20) - 1u && kWave == 64, "a list entry is lane << 20 | term number");
+static_assert(kTermRowMask == (1u << 20) - 1u && kWave == 64 && 1 + 6 + 20 <= 32, "a list entry is slot << 26 | lane << 20 | term number");
 
-// LDS of the form: cnt[64] per wave, the list, TermInfo + WordVerdict, the image (only its namespace lists are staged, at
-// their usual offsets)
-static BmCheckCachedArgs make_check_cached_args(const IndexDev& ix, uint32_t* total, bool codes = false) {
+// LDS of the form: cnt[64] per wave ([2][64] where the wave walks tile pairs), the list, TermInfo + WordVerdict, the image (only
+// its namespace lists are staged, at their usual offsets)
+static BmCheckCachedArgs make_check_cached_args(const IndexDev& ix, uint32_t* total, bool codes = false, bool pairs = false) {
   BmCheckCachedArgs a{};
   uint32_t o = 0;
   auto take = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
-  a.off_cnt = take(kBlockIx * 8u);
+  a.off_cnt = take(kBlockIx * 8u * (pairs ? 2u : 1u));
   a.off_list = take((kBlockIx / kWave) * kListCap * 4);
   a.off_tinfo = take(ix.bm_max_words * 64u * 8u);
   a.off_wv = take(codes ? 0u : ix.bm_max_words * (uint32_t)sizeof(WordVerdict<8>));  // (the code form settles through TermInfo alone)
@@ -775,12 +777,21 @@ static BmCheckCachedArgs make_check_cached_args(const IndexDev& ix, uint32_t* to
 // round.  A tile in which some lane's record says "more than 15" (wave-uniform) is replayed from the planes, every lane of it:
 // plane by plane, loaded where they are used (correct, not fast: no row of the flagship programs has more than 13 terms), the
 // run rule from the index's side table in global memory, every bit through the same per-term step.
+// TILE PAIRS (PAIRS, an instantiation of its own, launched where some wave owns a second tile; a.pairs, a wave-uniform argument of
+// it: KT_NO_TILE_PAIRS_CHECK=1 clears it, so one kernel gives both sides of an A/B): with n > 524 288 rows most waves own two tiles, and each was
+// a chain of two dependent trips to memory — the record, then the drain's gathers.  A wave now takes its tiles two at a time: both
+// records are requested back to back behind the prologue's barrier (six 8-byte loads in front of the first wait that names one of
+// them), replayed one after the other into one list, and drained ONCE — two of the six trips of such a wave are gone.  55 VGPRs, no
+// scratch, five spilled SGPRs; its single path (an odd last tile, the switch) carries them too and measured 0.3 us per step slower
+// than the single form's 44 / 0 / 0, which is why sweeps in which no wave owns a second tile keep the single form.  A tile whose
+// record overflows falls back to the planes by itself; its neighbour still replays codes.
 // (A wave's tile requested one tile AHEAD of its use — the first before the prologue, every further one when its predecessor's
 //  replay begins; 50-52 VGPRs, no scratch — was built on this form and measured: 1.2 us per step SLOWER on configs[2] and [3],
 //  profiles/match_codes.txt section 2.  Not kept.)
-template <int PL, bool CODES = false>
+template <int PL, bool CODES = false, bool PAIRS = false>
 __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCheckCachedArgs a) {
   static_assert(PL >= 1 && PL <= kMatchReplay, "one instantiation per plane count");
+  static_assert(!PAIRS || CODES, "tile pairs are a form of the code replay");
   constexpr int DT = 8;
   KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
   const CheckRec<DT>* recs = (const CheckRec<DT>*)a.recs;
@@ -789,7 +800,9 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
   const int DS = a.DS;
   const uint32_t lane = threadIdx.x & (kWave - 1);
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  lds_u64wp cnt = (lds_u64wp)(lds + a.off_cnt) + wave * kWave;  // [64] class counters coming back from the drain
+  // [64] class counters coming back from the drain; pairs: [2][64], a tile pair's first tile in [0], its second in [1]
+  const bool pairs = PAIRS && a.pairs != 0u;  // wave-uniform (a kernel argument)
+  lds_u64wp cnt = (lds_u64wp)(lds + a.off_cnt) + wave * (PAIRS ? 2u * kWave : (uint32_t)kWave);
   lds_u32wp list = (lds_u32wp)(lds + a.off_list) + wave * kListCap;
   KT_LDS u32x2* tinfo = (KT_LDS u32x2*)(lds + a.off_tinfo);
   KT_LDS const unsigned char* wv = lds + a.off_wv;
@@ -831,23 +844,28 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
   __syncthreads();
   const bool seg_on = ch.has_adj != 0u;  // wave-uniform: some throttle of the chunk has several terms
 
-  for (uint32_t wt = blockIdx.x * (kBlockIx / kWave) + wave; wt < n_wtiles; wt += wstep) {
-    const Rec r = fetch_tile(wt);
-    cnt[lane] = 0ull;
-    uint32_t n_list = 0;  // wave-uniform
-
-    // ---- lane = listed (pod lane, term): the full comparison.  The pod row follows from the lane; the pod's non-zero mask is
-    //      read again from its meta word, with the rows (the same trip; the word has just been through L2)
-    auto drain = [&](auto unroll_tag) {
+  // A wave owns the tiles wt, wt + wstep, ...  PAIRS (with a.pairs): it walks them two at a time — both records requested as
+  // one batch, replayed one after the other into ONE list (an entry names its tile as `slot`), drained once; what a lane settled
+  // for the pair's first tile waits in cnt[0][lane], for its second in cnt[1][lane].  An odd last tile, and every tile of the
+  // other forms, goes alone: slot 0 all along.
+  uint32_t wt = blockIdx.x * (kBlockIx / kWave) + wave;  // the tile of slot 0
+  uint32_t n_list = 0;  // wave-uniform; the list is empty between tiles (pairs)
+  {
+    // ---- lane = listed (slot, pod lane, term): the full comparison.  The pod row follows from slot and lane; the pod's non-zero
+    //      mask is read again from its meta word, with the rows (the same trip; the word has just been through L2)
+    auto drain = [&](auto unroll_tag, auto pair_tag) {
       constexpr int UNROLL = decltype(unroll_tag)::value;
+      constexpr bool PAIR = decltype(pair_tag)::value;
       for (uint32_t base = 0; base < n_list; base += kWave) {
         const uint32_t j = base + lane;
         const bool vv = j < n_list;
         const uint32_t e = list[vv ? j : 0u];
-        const uint32_t pl = e >> 20;
+        const uint32_t sl = e >> 20;  // slot << 6 | lane: the entry's counter in cnt (singles: slot 0)
+        const uint32_t pl = PAIR ? sl & (kWave - 1u) : sl;
         const u32x2 ti = tinfo[e & kTermRowMask];
         const uint32_t t = ti.x & kTermRowMask;
-        const uint32_t prow = min(wt * kWave + pl, n - 1u);  // (a listed lane is on: its row is in range)
+        const uint32_t ptile = PAIR ? wt + (e >> 26) * wstep : wt;
+        const uint32_t prow = min(ptile * kWave + pl, n - 1u);  // (a listed lane is on: its row is in range)
         static_assert(kMetaNzShift == 48, "the non-zero mask is the meta word's top 16 bits");
         const uint32_t pnz = ((const uint16_t*)(a.meta + prow))[3];
         const CheckRec<DT>* rc = recs + t;
@@ -889,22 +907,23 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
         exc |= (fx & kRecExceedsByCount) != 0, ins |= (fx & kRecInsufficientByCount) != 0;
         const bool act = (fx & kRecActiveByCount) || (pnz & fy);
         const uint32_t st = exc ? 4u : act ? 2u : ins ? 3u : 1u;
-        if (vv && st != 1u) lds_add64(cnt + pl, st == 4u ? 1ull << 4 : st == 2u ? 1ull << 24 : 1ull << 44);
+        if (vv && st != 1u) lds_add64(cnt + sl, st == 4u ? 1ull << 4 : st == 2u ? 1ull << 24 : 1ull << 44);
       }
       n_list = 0;
     };
-    auto push = [&](bool want, uint32_t e) {  // wave-wide append
+    auto push = [&](bool want, uint32_t e, auto pair_tag) {  // wave-wide append
       const uint64_t mk = __ballot(want);
       if (mk == 0ull) return;
       if (want) list[n_list + lane_rank(mk)] = e;
       n_list += (uint32_t)__popcll(mk);
-      if (n_list > kListCap - kWave) drain(std::integral_constant<int, 0>());  // (the list ran full, mid-tile)
+      // (the list ran full, mid-tile; in a pair it may hold entries of both slots)
+      if (n_list > kListCap - kWave) drain(std::integral_constant<int, 0>(), pair_tag);
     };
-    // ---- the tile: every match that needs no comparison is settled per WORD with mask algebra (WordVerdict), the matches of
-    //      tight throttles are listed as (lane, term number)
-    {
+    // ---- a tile (wtile = wt + slot * wstep): every match that needs no comparison is settled per WORD with mask algebra
+    //      (WordVerdict) or per code through TermInfo, the matches of tight throttles are listed as (slot, lane, term number)
+    auto tile = [&](const Rec& r, const uint32_t wtile, const uint32_t slot, auto pair_tag) {
       const uint64_t meta = r.meta;
-      const bool on = wt * kWave + lane < n && ((meta >> kMetaStateShift) & kPodValid) != 0;
+      const bool on = wtile * kWave + lane < n && ((meta >> kMetaStateShift) & kPodValid) != 0;
       const uint32_t ns = on ? (uint32_t)(meta & kMetaNsMask) : 0u;
       const uint32_t nz = (uint32_t)(meta >> kMetaNzShift) & 0xFFFFu;
       // affectedClusterThrottles: the pod's Namespace object must exist (clusterthrottle_controller.go:273-276)
@@ -926,7 +945,7 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
           const bool tight = (ti.y & kTiTight) != 0u;
           const uint32_t sh = (nz & ti.y & 0xFFFFu) ? (ti.y >> kTiShActive) & 63u : (ti.y >> kTiShIdle) & 63u;
           if (has && !tight && sh != 0u) my += 1ull << sh;  // (shift 0: not throttled, nothing to count)
-          push(has && tight, lane << 20 | c);
+          push(has && tight, slot << 26 | lane << 20 | c, pair_tag);
         };
         const uint32_t hdr = (uint32_t)r.mx[0] & 0xFFu;
         if (__ballot(on && hdr == kMatchCodesOverflow) == 0ull) {
@@ -961,7 +980,7 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
         } else {
 #pragma unroll 1
           for (uint32_t k = 0; k < (uint32_t)PL; ++k) {
-            const uint32_t ic = min(wt * kWave + lane, n - 1u);
+            const uint32_t ic = min(wtile * kWave + lane, n - 1u);
             uint64_t x = k < len ? a.mw[(uint64_t)k * a.mw_stride + ic] : 0ull;
             const uint32_t wp = (k & 2u) ? w23 : w01;
             const uint32_t w = (k & 1u) ? wp >> 16 : wp & 0xFFFFu;
@@ -1000,17 +1019,43 @@ __global__ __launch_bounds__(kBlockIx, 8) void kt_check_bitmap_cached(const BmCh
           n_ins = (uint32_t)__popc((uint32_t)xi) + ((uint32_t)__popc((uint32_t)(xi >> 32)) + n_ins);
           return x & te.x;
         };
-        replay_tile(bm, on, ns, r.mx, (uint32_t)PL, [&](bool has, uint32_t c) { push(has, lane << 20 | c); }, settle_word, ScanNoPrefetch());
+        replay_tile(bm, on, ns, r.mx, (uint32_t)PL, [&](bool has, uint32_t c) { push(has, lane << 20 | c, pair_tag); }, settle_word, ScanNoPrefetch());
         // what the lane settled joins what drains have brought and will bring (counters from bit 4 up; bit 0: on, bit 1: Error)
         my = (unsigned long long)n_exc << 4 | (unsigned long long)n_act << 24 | (unsigned long long)n_ins << 44;
       }
-      cnt[lane] += my | (on ? 1ull : 0ull) | ((on && ns_ok_raw == 0u) ? 2ull : 0ull);
-    }
-    if (n_list) drain(std::integral_constant<int, 2>());
+      cnt[slot * kWave + lane] += my | (on ? 1ull : 0ull) | ((on && ns_ok_raw == 0u) ? 2ull : 0ull);
+    };
     // ---- lane = pod: the 8-byte summary word
-    if (wt * kWave + lane < n) {
-      const unsigned long long w = cnt[lane], c = w & ~3ull;
-      a.summary[wt * kWave + lane] = !(w & 1ull) ? 0ull : (w & 2ull) ? 2ull : (c | (c ? 1ull : 0ull));
+    auto summarise = [&](const uint32_t wtile, const uint32_t slot) {
+      if (wtile * kWave + lane < n) {
+        const unsigned long long w = cnt[slot * kWave + lane], c = w & ~3ull;
+        a.summary[wtile * kWave + lane] = !(w & 1ull) ? 0ull : (w & 2ull) ? 2ull : (c | (c ? 1ull : 0ull));
+      }
+    };
+    const std::false_type single;
+    const std::true_type paired;
+    while (wt < n_wtiles) {
+      if constexpr (PAIRS) {
+        if (pairs && wt + wstep < n_wtiles) {  // wave-uniform
+          // both records as ONE batch of loads: nothing looks at the first tile's words before the second's are requested
+          const Rec ra = fetch_tile(wt);
+          const Rec rb = fetch_tile(wt + wstep);
+          cnt[lane] = 0ull, cnt[kWave + lane] = 0ull;
+          tile(ra, wt, 0u, paired);
+          tile(rb, wt + wstep, 1u, paired);
+          if (n_list) drain(std::integral_constant<int, 2>(), paired);
+          summarise(wt, 0u);
+          summarise(wt + wstep, 1u);
+          wt += 2u * wstep;
+          continue;
+        }
+      }
+      const Rec r = fetch_tile(wt);
+      cnt[lane] = 0ull;
+      tile(r, wt, 0u, single);
+      if (n_list) drain(std::integral_constant<int, 2>(), single);
+      summarise(wt, 0u);
+      wt += wstep;
     }
   }
 }
@@ -1019,7 +1064,15 @@ static void launch_check_cached(const PodTable& pods, int64_t n, const SelProgra
                                 const MatchCacheArgs& mc, dim3 grid, hipStream_t s) {
   uint32_t total = 0;
   const bool codes = mc.codes != nullptr && (!ix.h_chunks[0].has_adj || ix.bm_runs != nullptr);
-  BmCheckCachedArgs a = make_check_cached_args(ix, &total, codes);
+  // the pair form: the code replay only, where some wave owns a second tile (the single form is the leaner kernel) and two
+  // workgroups with the second row of counters still share a CU; the switch keeps the form and clears its argument
+  bool pair_form = codes && ((uint64_t)n + kWave - 1u) / kWave > (uint64_t)grid.x * (kBlockIx / kWave);
+  if (pair_form) {
+    (void)make_check_cached_args(ix, &total, codes, true);
+    pair_form = 2u * total <= (uint32_t)kMaxLds;
+  }
+  BmCheckCachedArgs a = make_check_cached_args(ix, &total, codes, pair_form);
+  a.pairs = pair_form && mc.tile_pairs ? 1u : 0u;
   // (the form's footprint is the generic two-per-CU form's without its tile counter, so two of them fit where the caller found
   //  that form to fit; a list entry is lane << 20 | term number, as in the generic kernel)
   assert(2u * total <= (uint32_t)kMaxLds && (uint64_t)ix.bm_max_words * 64u <= (uint64_t)kTermRowMask + 1u);
@@ -1029,15 +1082,15 @@ static void launch_check_cached(const PodTable& pods, int64_t n, const SelProgra
   a.blob = ix.bm_blob, a.ch = ix.h_chunks[0];
   a.n = (uint32_t)n, a.DS = pods.DS, a.T = sp.T;
   static const bool dbg_lds = getenv("KT_DEBUG_LDS") != nullptr;
-  if (dbg_lds) fprintf(stderr, "kt_check_bitmap_cached: lds=%u (2 per CU) workgroups=%u planes=%u %s\n", total, grid.x, mc.planes, codes ? "match codes" : "planes");
-#define KT_CHECK_CACHED_LAUNCH_(PL_, CODES_)                                                                    \
+  if (dbg_lds) fprintf(stderr, "kt_check_bitmap_cached: lds=%u (2 per CU) workgroups=%u planes=%u %s pairs=%d\n", total, grid.x, mc.planes, codes ? "match codes" : "planes", (int)a.pairs);
+#define KT_CHECK_CACHED_LAUNCH_(PL_, CODES_, PAIRS_)                                                            \
   {                                                                                                             \
-    auto kfn = kt_check_bitmap_cached<PL_, CODES_>;                                                             \
+    auto kfn = kt_check_bitmap_cached<PL_, CODES_, PAIRS_>;                                                     \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);        \
     hipLaunchKernelGGL(kfn, grid, dim3(kBlockIx), total, s, a);                                                 \
   }
 #define KT_CHECK_CACHED_LAUNCH(PL_) \
-  { if (codes) KT_CHECK_CACHED_LAUNCH_(PL_, true) else KT_CHECK_CACHED_LAUNCH_(PL_, false) }
+  { if (pair_form) KT_CHECK_CACHED_LAUNCH_(PL_, true, true) else if (codes) KT_CHECK_CACHED_LAUNCH_(PL_, true, false) else KT_CHECK_CACHED_LAUNCH_(PL_, false, false) }
   static_assert(kMatchReplay == 4, "one instantiation per plane count");
 #ifdef KT_FAST_BUILD
   KT_CHECK_CACHED_LAUNCH(kMatchReplay)  // (the caller dispatches the form for tables of exactly that many planes)
