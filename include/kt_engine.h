@@ -352,6 +352,43 @@ int32_t kt_admit_gangs_fetch(kt_engine* e, int64_t n_gangs, uint8_t* out_admitte
 #define KT_HEADROOM_MAX_CAP 0x7FFFFFFF
 int32_t kt_headroom_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, int64_t cap, void* stream);
 int32_t kt_headroom_fetch(kt_engine* e, int64_t n, int64_t* out_copies, int32_t* out_limiting /* nullable */);
+/* ---- headroom, for gangs: how many copies of a whole gang the throttles still admit — what a batch controller asks before it
+ *      creates replicas of a job that scales in units of a gang (one launcher plus N workers, a JobSet replica, a Ray worker
+ *      group).  Gang g is pod_rows[gang_off[g] .. gang_off[g + 1]), as in kt_admit_gangs_launch.  headroom_gangs(gang, cap,
+ *      on_equal) is the number of LEADING admitted gangs in a dry kt_admit_gangs_launch (no KT_ADMIT_COMMIT) over a queue of cap
+ *      consecutive copies of the gang, against the stored status and the current reserved amounts.  Before the first gang that
+ *      is rolled back every earlier copy was admitted in full, so copy j meets on throttle t the stored reserved row of t plus
+ *      j x A_t, A_t = what one admitted copy reserves on t: a pod count of one per member t affects, the value of every resource
+ *      name such a member carries, and the presence of all those names, zero-valued ones included; from copy 1 on the count
+ *      and those names are present in `reserved`.  Given that, throttles are independent: the answer is the minimum over the
+ *      affecting throttles of h_t, the leading copies t alone lets through.  With non-negative requests passes_t(j) is monotone
+ *      in j, so h_t is found by search, and the judge of every probe is the gang walk of kt_admit_gangs itself.
+ *      out_copies[g] lies in [0, cap].  out_blocker[g] is the queue position (in pod_rows, as kt_forecast_gangs_fetch's
+ *      blockers) of the first member of copy out_copies[g] — the first copy that is not admitted — whose verdict at its turn is
+ *      not Success; -1 when all cap copies are admitted.  out_limiting[g] is the lowest throttle row whose status is not
+ *      KT_STATUS_NOT_THROTTLED in the row PreFilter returns to that member at its turn; -1 when there is no blocker or the
+ *      blocker's verdict is an Error.  A gang with a member whose PreFilter is an Error, or whose row is invalid, reports 0
+ *      copies; its blocker is the first position of copy 0 that is not Success (an earlier member a throttle stops counts).  A
+ *      gang no throttle affects reports cap, -1, -1.  Gangs are judged independently, each against the stored reserved amounts:
+ *      a pod may occur in several gangs; the copies are FURTHER pods of the same shapes.  A gang of one pod is
+ *      kt_headroom_launch on that pod, byte for byte, in out_copies and out_limiting.
+ *      One kt_check launch with the status matrix over the members, then one launch of kt_headroom_gangs
+ *      (csrc/kt_kernels_headroom_gangs.hip): one wave per gang, lane = a candidate number of copies, a 64-ary search per
+ *      throttle (six rounds at the most for cap = 2^31 - 1).  The call never changes reserved amounts, stored status or a
+ *      pending reconcile.
+ *      Refused before anything is launched, in this order: every gang_off defect kt_admit_gangs_launch refuses and a pod named
+ *      twice within one gang (KT_ERR_INVALID_ARGUMENT), a pod row outside the table (KT_ERR_OUT_OF_RANGE), cap outside
+ *      [1, KT_HEADROOM_MAX_CAP] (KT_ERR_INVALID_ARGUMENT), n x throttle_rows > 2^31 (KT_ERR_OUT_OF_RANGE), a stored `used` wider
+ *      than int64 (KT_ERR_UNSUPPORTED), and an engine that has been fed a negative request (KT_ERR_UNSUPPORTED: the search rests
+ *      on sums that only grow; kt_headroom_launch keeps serving such an engine pod by pod).  n == 0 is KT_OK and launches
+ *      nothing.
+ *      Slots: the engine's ONE check slot, exactly as kt_headroom_launch uses it.  A pending kt_headroom_launch and a pending
+ *      kt_headroom_gangs_launch replace each other, and a fetch of the other kind answers KT_ERR_NOT_READY.
+ *      kt_headroom_gangs_fetch synchronises. ------------------------------------------------------------------------------ */
+int32_t kt_headroom_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int32_t on_equal,
+                                 int64_t cap, void* stream);
+int32_t kt_headroom_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_copies, int32_t* out_limiting /* nullable */,
+                                int64_t* out_blocker /* nullable */);
 /* ---- preempt: the shortest victim prefix that lets a blocked pod through — what priority preemption asks, and what the
  *      scheduler's own preemption never asks of throttles (PreFilter answers UnschedulableAndUnresolvable).
  *      A pod is COUNTED when VALID & SCHED_MATCH & SCHEDULED & !FINISHED (throttle_controller.go:217-219).  For preemptor

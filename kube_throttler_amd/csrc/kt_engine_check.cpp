@@ -729,7 +729,7 @@ static int32_t headroom_locked(kt_engine* const* pages, int32_t n_pages, int64_t
                                hipStream_t s) {
   kt_engine* e0 = pages[0];
   const int32_t T = e0->thr_rows_hi;
-  e0->headroom_ready = false;
+  e0->headroom_ready = false, e0->headroom_gangs = false;
   for (int32_t k = 0; k < n_pages; ++k)
     if (pages[k]->wide)
       return pages[k]->fail(KT_ERR_UNSUPPORTED, "headroom: the stored `used` of page %d is wider than int64 (kt_headroom reads int64 tables)", k);
@@ -779,7 +779,7 @@ int32_t kt_headroom_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int
 
 // the results of the last headroom launch, under the launch lock; both outputs nullable
 static int32_t headroom_fetch_locked(kt_engine* e, int64_t n, int64_t* out_copies, int32_t* out_limiting) {
-  if (!e->headroom_ready) return e->fail(KT_ERR_NOT_READY, "kt_headroom_fetch before kt_headroom_launch");
+  if (!e->headroom_ready || e->headroom_gangs) return e->fail(KT_ERR_NOT_READY, "kt_headroom_fetch before kt_headroom_launch");
   if (n < 0 || n > e->headroom_n) return e->fail(KT_ERR_OUT_OF_RANGE, "n=%lld, the last headroom launch had %lld pods", (long long)n, (long long)e->headroom_n);
   if (n == 0) return KT_OK;
   hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
@@ -811,6 +811,91 @@ int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, c
   rc = headroom_fetch_locked(e0, n, out_copies, out_limiting);  // (synchronises s)
   e0->headroom_ready = false;  // the results have been handed out
   return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// headroom, for gangs: how many copies of a whole gang the throttles still admit (kt_kernels_headroom_gangs.hip)
+// ---------------------------------------------------------------------------------------------------
+// The gang defects of kt_admit_gangs_launch and "a pod twice" asked per gang (as the gang forecast), then headroom_locked's
+// refusals and its two launches with kt_headroom_gangs in kt_headroom's place.  The result shares the one pending headroom
+// result; headroom_gangs tells the fetches apart.
+int32_t kt_headroom_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int32_t on_equal,
+                                 int64_t cap, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  if (n > 0 && !pod_rows) return e->fail(KT_ERR_INVALID_ARGUMENT, "headroom gangs: pod_rows missing");
+  int32_t rc = gangs_valid(e, n, n_gangs, gang_off);
+  if (rc != KT_OK) return rc;
+  {
+    // gangs are judged independently: a pod may be in several of them, but not twice in one (it would reserve twice)
+    std::vector<int64_t> sorted;
+    for (int64_t g = 0; g < n_gangs; ++g) {
+      sorted.assign(pod_rows + gang_off[g], pod_rows + gang_off[g + 1]);
+      std::sort(sorted.begin(), sorted.end());
+      for (size_t j = 1; j < sorted.size(); ++j)
+        if (sorted[j] == sorted[j - 1])
+          return e->fail(KT_ERR_INVALID_ARGUMENT, "headroom gangs: pod row %lld is in gang %lld twice", (long long)sorted[j], (long long)g);
+    }
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity)
+      return e->fail(KT_ERR_OUT_OF_RANGE, "headroom gangs: pod row %lld", (long long)pod_rows[i]);
+  if (!headroom_cap_ok(cap))
+    return e->fail(KT_ERR_INVALID_ARGUMENT, "headroom gangs: cap = %lld, not in [1, %d]", (long long)cap, KT_HEADROOM_MAX_CAP);
+  const int32_t T = e->thr_rows_hi;
+  if ((double)n * (double)T > 2147483648.0)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "headroom gangs: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "headroom gangs: the stored `used` is wider than int64 (kt_headroom_gangs reads int64 tables)");
+  if (e->neg_seen)
+    return e->fail(KT_ERR_UNSUPPORTED,
+                   "headroom gangs: the engine has been fed a negative request; the search over the copies rests on sums that only grow "
+                   "(kt_headroom_launch serves such an engine pod by pod)");
+  e->headroom_ready = false, e->headroom_gangs = false;
+  if (n == 0) {  // (no gangs) nothing is launched
+    e->headroom_ready = true, e->headroom_gangs = true, e->headroom_n = 0;
+    return KT_OK;
+  }
+  KT_HIP(e, hipSetDevice(e->device));
+  hipStream_t s = pick_stream(e, stream);
+  if (e->d_headroom_copies.cap < (size_t)n_gangs || e->d_headroom_limiting.cap < (size_t)n_gangs || e->d_headroom_blocker.cap < (size_t)n_gangs ||
+      e->d_headroom_gang_off.cap < (size_t)n_gangs + 1) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_headroom_launch)
+    if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+    KT_HIP(e, e->d_headroom_copies.reserve((size_t)n_gangs));
+    KT_HIP(e, e->d_headroom_limiting.reserve((size_t)n_gangs));
+    KT_HIP(e, e->d_headroom_blocker.reserve((size_t)n_gangs));
+    KT_HIP(e, e->d_headroom_gang_off.reserve((size_t)n_gangs + 1));
+  }
+  // the offsets travel on the launch's stream, behind an earlier launch's kernel; the caller's memory is not referenced after return
+  KT_HIP(e, hipMemcpyAsync(e->d_headroom_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  // ONE check over the members of all gangs: which throttles affect which pod, and the error rows
+  rc = check_launch_locked(e, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e->check_ready = false;  // the slot holds this call's rows (as with kt_headroom_launch): a pending kt_check_launch is gone
+  if (rc != KT_OK) return rc;
+  const kt::AdmitPage pg{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  kt::launch_headroom_gangs(pg, n_gangs, e->d_rows.p, e->d_headroom_gang_off.p, T, on_equal != 0, (uint32_t)cap, e->d_status.p, e->d_summary.p,
+                            e->d_headroom_copies.p, e->d_headroom_limiting.p, e->d_headroom_blocker.p, s);
+  KT_HIP(e, hipGetLastError());
+  e->last_stream = s;
+  e->headroom_ready = true, e->headroom_gangs = true, e->headroom_n = n_gangs;
+  return KT_OK;
+}
+
+int32_t kt_headroom_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_copies, int32_t* out_limiting, int64_t* out_blocker) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (!e->headroom_ready || !e->headroom_gangs) return e->fail(KT_ERR_NOT_READY, "kt_headroom_gangs_fetch before kt_headroom_gangs_launch");
+  if (n_gangs < 0 || n_gangs > e->headroom_n)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "n_gangs=%lld, the last headroom gangs launch had %lld gangs", (long long)n_gangs, (long long)e->headroom_n);
+  if (n_gangs == 0) return KT_OK;
+  hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
+  if (out_copies) KT_HIP(e, hipMemcpyAsync(out_copies, e->d_headroom_copies.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
+  if (out_limiting) KT_HIP(e, hipMemcpyAsync(out_limiting, e->d_headroom_limiting.p, (size_t)n_gangs * 4, hipMemcpyDeviceToHost, s));
+  if (out_blocker) KT_HIP(e, hipMemcpyAsync(out_blocker, e->d_headroom_blocker.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

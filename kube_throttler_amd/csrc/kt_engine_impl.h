@@ -368,6 +368,10 @@ struct kt_engine {
   DevBuf<int32_t> d_headroom_limiting;
   bool headroom_ready = false;
   int64_t headroom_n = 0;
+  // kt_headroom_gangs_launch shares that one pending result (copies and limiting per GANG, headroom_n = the gangs); the kind tag
+  // says which fetch may read it.  Its offsets and the blocking member per gang live in buffers of their own
+  bool headroom_gangs = false;
+  DevBuf<int64_t> d_headroom_gang_off, d_headroom_blocker;
   // the last kt_preempt_launch: prefix per preemptor and the victim bytes [n][n_cand], on the device until kt_preempt_fetch;
   // d_preempt_partial: the partial rows of its own aggregate (exact contributor counts), never the engine's partial buffer
   DevBuf<int64_t> d_preempt_prefix;

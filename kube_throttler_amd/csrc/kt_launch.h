@@ -113,6 +113,12 @@ bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_
 bool launch_headroom(const AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
                      bool on_equal, uint32_t cap, const uint8_t* status, const uint64_t* summary, int64_t* copies, int32_t* limiting,
                      hipStream_t s, hipError_t* hip_err);
+// how many copies of each gang [gang_off[g], gang_off[g + 1]) the throttles still admit (kt_kernels_headroom_gangs.hip): one wave
+// per gang, lane = a candidate number of copies.  status / summary: ONE check over the members of all gangs; the stored tables of
+// the one page; copies [n_gangs], limiting [n_gangs], blocker [n_gangs] out; cap in [1, 2^31 - 1]
+void launch_headroom_gangs(const AdmitPage& pg, int64_t n_gangs, const int64_t* rows_dev, const int64_t* gang_off_dev, int T, bool on_equal,
+                           uint32_t cap, const uint8_t* status, const uint64_t* summary, int64_t* copies, int32_t* limiting, int64_t* blocker,
+                           hipStream_t s);
 // the shortest victim prefix per preemptor (kt_kernels_preempt.hip): one wave per preemptor.  rows_dev [n + m]: the preemptors,
 // then the candidates; status / summary: ONE check over those rows; partial: aggregate rows with exact per-name contributor counts;
 // calc / calc_updated / error: a dry finalize at `now`; prefix [n] and victims [n][m] out

@@ -44,7 +44,7 @@ EXPORTS = [
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
-    "kt_paged_forecast_gangs",
+    "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -353,6 +353,8 @@ def lib():
                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_headroom_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
         L.kt_headroom_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.kt_headroom_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
+        L.kt_headroom_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_paged_headroom.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                         C.c_void_p]
         L.kt_paged_preempt.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
@@ -763,6 +765,30 @@ class Engine:
         n = len(rows) if rows is not None else n
         self.headroom_launch(n, rows, cap, on_equal)
         return self.headroom_fetch(n)
+
+    # ---- headroom, for gangs: how many copies of a whole gang the throttles still admit
+    def headroom_gangs_launch(self, pod_rows, gang_off, cap=1, on_equal=False, stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        g = _gang_offsets(gang_off)
+        self._ck(lib().kt_headroom_gangs_launch(self._h, len(a), p if len(a) else None, len(g) - 1, g.ctypes.data, int(on_equal), int(cap), stream))
+
+    def headroom_gangs_fetch(self, n_gangs, want_limiting=True, want_blocker=True):
+        copies = np.zeros(max(n_gangs, 1), np.int64)
+        limiting = np.zeros(max(n_gangs, 1), np.int32) if want_limiting else None
+        blocker = np.zeros(max(n_gangs, 1), np.int64) if want_blocker else None
+        self._ck(lib().kt_headroom_gangs_fetch(self._h, n_gangs, copies.ctypes.data, None if limiting is None else limiting.ctypes.data,
+                                               None if blocker is None else blocker.ctypes.data))
+        return copies[:n_gangs], (None if limiting is None else limiting[:n_gangs]), (None if blocker is None else blocker[:n_gangs])
+
+    def headroom_gangs(self, pod_rows, gang_off, *, cap, on_equal=False):
+        """kt_headroom_gangs_launch + kt_headroom_gangs_fetch: per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` the number of
+        leading admitted gangs of a dry-run gang admission of ``cap`` consecutive copies of it, the lowest throttle row that stops
+        the first member of the next copy that is not admitted (-1: all ``cap`` copies are admitted, or that member's verdict is an
+        Error) and that member's queue position (-1: all are admitted) -> (copies int64 [n_gangs], limiting int32 [n_gangs],
+        blocker int64 [n_gangs]).  Gangs are judged independently of each other, each against the stored reserved amounts.
+        Reserved amounts and stored status are left as they are."""
+        self.headroom_gangs_launch(pod_rows, gang_off, cap, on_equal)
+        return self.headroom_gangs_fetch(len(_gang_offsets(gang_off)) - 1)
 
     # ---- preempt: the shortest victim prefix that lets a blocked pod through
     def preempt_launch(self, pod_rows, cand_rows, now, on_equal=False, stream=None):

@@ -1237,6 +1237,50 @@ HeadroomResult KubeThrottler::Headroom(const std::string& pod_key, int64_t cap) 
   return out;
 }
 
+// How many further replicas of this gang AdmitGangs would admit in a row, the throttle that stops the next one and the member it
+// stops: one kt_headroom_gangs_launch + kt_headroom_gangs_fetch with the members as ONE gang on the mirror's one engine
+// (isThrottledOnEqual = false, as PreFilter).  Nothing is changed.
+GangHeadroomResult KubeThrottler::HeadroomGang(const std::vector<std::string>& member_keys, int64_t cap) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  GangHeadroomResult res;
+  HeadroomResult& out = res.headroom;
+  if (p.pages.size() > 1) {
+    out.error = "HeadroomGang: the mirror runs on " + std::to_string(p.pages.size()) + " pages (more than " + std::to_string(p.D) +
+                " resource names); the gang headroom has no paged form";
+    return res;
+  }
+  if (member_keys.empty()) {
+    out.error = "HeadroomGang: a gang without members";
+    return res;
+  }
+  std::vector<int64_t> rows(member_keys.size());
+  std::set<std::string> seen;
+  for (size_t i = 0; i < rows.size(); ++i) {
+    if ((rows[i] = p.pod_rows.find(member_keys[i])) < 0) {
+      out.error = "pod " + member_keys[i] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+    if (!seen.insert(member_keys[i]).second) {  // (it would reserve twice: the engine refuses it too)
+      out.error = "HeadroomGang: pod " + member_keys[i] + " is a member twice";
+      return res;
+    }
+  }
+  const int64_t gang_off[2] = {0, (int64_t)rows.size()};
+  int64_t copies = 0, blocker = -1;
+  int32_t limiting = -1;
+  int32_t rc = kt_headroom_gangs_launch(p.e, (int64_t)rows.size(), rows.data(), 1, gang_off, /*isThrottledOnEqual=*/0, cap, nullptr);
+  if (rc == KT_OK) rc = kt_headroom_gangs_fetch(p.e, 1, &copies, &limiting, &blocker);
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    return res;
+  }
+  out.copies = copies;
+  if (limiting >= 0 && (size_t)limiting < p.thr_by_row.size() && p.thr_live[(size_t)limiting]) out.limiting = p.thr_by_row[(size_t)limiting].Key();
+  if (blocker >= 0 && (size_t)blocker < member_keys.size()) res.blocker = member_keys[(size_t)blocker];
+  return res;
+}
+
 // Which of the candidates have to go before this pod passes PreFilter: kt_preempt_launch + kt_preempt_fetch on the mirror's one
 // engine (isThrottledOnEqual = false, as PreFilter).  The reserved totals are read as they stand and nothing is changed.
 PreemptResult KubeThrottler::Preempt(const std::string& pod_key, const std::vector<std::string>& candidate_keys,

@@ -158,6 +158,13 @@ struct HeadroomResult {
   std::string error;      // not empty: the call failed (unknown pod, engine error) and copies is 0
 };
 
+// HeadroomGang: how many further replicas of a whole gang the throttles still admit, and who stops the next one
+struct GangHeadroomResult {
+  HeadroomResult headroom;  // copies / limiting / error as for Headroom, for the gang as a whole (limiting is empty too when the
+                            // blocker's PreFilter is an Error)
+  std::string blocker;      // Pod::Key() of the first member of replica number `copies` that is not admitted; empty: all cap fit
+};
+
 // Preempt: the pods that would have to go before a blocked pod passes PreFilter
 struct PreemptResult {
   bool none = false;                 // no prefix of the candidates lets the pod through (victims is empty)
@@ -244,6 +251,12 @@ class KubeThrottler {
   // reserved.  The copies are FURTHER pods: a pod whose own amount is already part of the reserved totals (Reserve was called for
   // it) is answered as the totals stand, its reservation counts against the copies like anybody else's.
   HeadroomResult Headroom(const std::string& pod_key, int64_t cap);
+  // ---- how many replicas of a whole job fit: the number of further gangs of the members' shapes that AdmitGangs would admit one
+  // after the other right now, at most cap — each admitted member reserves against the throttles the later members and the later
+  // replicas meet, so this is NOT the minimum of the members' own Headroom answers.  ONE engine call (kt_headroom_gangs_launch +
+  // kt_headroom_gangs_fetch) instead of a dry-run queue of cap x members pods.  Nothing is reserved; the reserved totals are read
+  // as they stand.  A member named twice, an unknown key, an empty gang and a mirror on several pages answer an error.
+  GangHeadroomResult HeadroomGang(const std::vector<std::string>& member_keys, int64_t cap);
 
   // ---- who has to go: the shortest prefix of `candidate_keys` (the caller's order, typically ascending priority) whose deletion,
   // followed by a reconcile of every throttle at `now` (RFC3339), lets pod_key through PreFilter — ONE engine call

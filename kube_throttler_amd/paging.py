@@ -1032,6 +1032,93 @@ def forecast_gangs_of(snap, member_rows, instants, on_equal=False, ctx=None):
     return first, verdicts_, [s if s < g else -1 for s in stopped]
 
 
+# ---- headroom, for gangs (kt_headroom_gangs_launch), as the kernel computes it, on a Snapshot ----
+_INT64_MAX = (1 << 63) - 1
+
+
+def headroom_gangs_of(snap, member_rows, cap, on_equal=False):
+    """kt_headroom_gangs_launch for one gang, restated on a Snapshot (no GPU) -> (copies, limiting, blocker position inside
+    ``member_rows``).  copies: the leading admitted gangs of a dry-run gang admission of ``cap`` consecutive copies of the gang
+    against the stored status and reserved amounts.  Copy j meets on throttle t the stored reserved row plus j x A_t (what one
+    admitted copy reserves on t: one pod per member t affects, every name such a member carries by value and by presence; from
+    copy 1 on the count and those names are present), judged by ``_gang_first_stopped``; per throttle the candidates end at the
+    running minimum and where a named amount would leave int64, the first failing one is found by the kernel's 64-ary search,
+    and the answer is the lexicographic minimum of (h_t, first stopped member at j = h_t, t).  limiting / blocker: -1 / -1 when
+    all ``cap`` copies are admitted.  A member whose PreFilter is an Error or whose row is invalid: 0 copies, the walk of copy 0
+    ends in front of it, limiting -1 when it is the blocker itself."""
+    members, eq, cap = [int(p) for p in member_rows], bool(on_equal), int(cap)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap.n_pods and bool(int(snap.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    g = len(members) if bad_at is None else bad_at  # the members that are walked
+    members, affected = members[:g], affected[:g]
+    reqs = [pod_requests(snap, p) for p in members]
+    best = (cap if bad_at is None else 0, g, -1)  # (h, first, t)
+    for t in (sorted(set().union(*affected)) if affected else []):
+        f = int(snap.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        th = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+        used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+        flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+        names = {d: (bool(flg >> d & 1), d in used, used.get(d, 0)) for d in range(snap.D)}
+        ustate = (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names)
+        res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+        hit = [t in a for a in affected]
+        # A_t: only what the threshold names is summed (the rest is never compared)
+        per, per_p, per_c = {}, set(), 0
+        for j in range(g):
+            if hit[j]:
+                per_c += 1
+                for d, v in reqs[j].items():
+                    per_p.add(d)
+                    if d in th[0]:
+                        per[d] = min(per.get(d, 0) + v, _INT64_MAX)
+        if th[1] is None:
+            per_c = 0
+
+        def first_stopped(j):
+            r = {d: res.get(d, 0) + j * per.get(d, 0) for d in (set(res) | per_p if j > 0 else set(res))}
+            rc = (res_count or 0) + j * per_c if (res_count is not None or j > 0) else None
+            s = _gang_first_stopped(members, hit, reqs, th, ustate, r, rc, eq3, eq)
+            return g if s is None else s
+
+        # the range: up to the running minimum, and no further than every named amount stays inside int64
+        top = best[0] if best[0] < cap else cap - 1
+        if bad_at is None:
+            if per_c > 0:
+                top = min(top, (_INT64_MAX - (res_count or 0)) // per_c)
+            for d, a in per.items():
+                if a > 0:
+                    top = min(top, (_INT64_MAX - res.get(d, 0)) // a)
+        lo, known, first = 0, False, g
+        while True:  # the 64-ary search for the first candidate in [lo, top] that fails
+            hi = top - 1 if known else top
+            n = hi - lo + 1
+            if n <= 0:
+                break
+            step = (n + 63) // 64
+            probes = [(j, first_stopped(j)) for j in (hi - (63 - lane) * step for lane in range(64)) if j >= lo]
+            fail = next((k for k, (_, s) in enumerate(probes) if s < g), None)
+            if fail is None:
+                lo = hi + 1
+                if not known:
+                    break
+                continue
+            (top, first), known = probes[fail], True
+            if fail > 0:
+                lo = probes[fail - 1][0] + 1
+        if known and (top, first) < best[:2]:
+            best = (top, first, t)
+    h, first, t = best
+    if bad_at is not None:
+        return 0, (t if first < g else -1), first
+    return (cap, -1, -1) if h >= cap else (h, t, first)
+
+
 # ---- forecast over pages (kt_paged_forecast): the closed form over a list of page snapshots ----
 def paged_forecast_of(snaps, pod_row, instants, on_equal=False, ctx=None):
     """kt_paged_forecast for one pod, in closed form over the page snapshots (no GPU) -> (first, verdicts [len(instants)]):
