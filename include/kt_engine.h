@@ -99,7 +99,10 @@ int32_t kt_upsert_namespaces(kt_engine* e, const kt_snapshot* batch, const int32
  * kt_check issued right behind it included — first waits for the newest such call, so the order "feed the event, then
  * the next PreFilter sees it" holds (kt_delete_pods and kt_upsert_pod likewise).  Larger batches block as before.
  * A batch may name a pod row more than once (coalesced informer events — Add, then Update of one pod): the entries are applied
- * in batch order, the LAST one wins, exactly as if they had arrived in separate calls (incremental engines included). */
+ * in batch order, the LAST one wins, exactly as if they had arrived in separate calls (incremental engines included).
+ * The whole batch is validated before anything of it is kept: a refused batch (a row or namespace id outside the capacity, more
+ * labels than the engine keeps, a request beyond 2^60) leaves the engine as it was — its bounds, its "a negative request was fed"
+ * mark, its views and its compiled program included. */
 int32_t kt_upsert_pods(kt_engine* e, const kt_snapshot* batch, const int64_t* pod_rows);
 /* Throttles: spec (threshold, overrides, selector), stored status and reserved amounts of each row. */
 int32_t kt_upsert_throttles(kt_engine* e, const kt_snapshot* batch, const int32_t* thr_rows);
@@ -142,7 +145,9 @@ int32_t kt_upsert_throttle(kt_engine* e, int32_t thr_row, uint32_t flags, uint32
                            const uint8_t* nreq_op, const uint32_t* nreq_key, const uint32_t* nreq_val_off, const uint32_t* nreq_val);
 
 /* Scheduler-side reserved amounts per throttle — the value reservedResourceAmount(nn) returns
- * (pkg/controllers/reserved_resource_amounts.go:113-126,148-156); the pod map itself stays in Go. */
+ * (pkg/controllers/reserved_resource_amounts.go:113-126,148-156); the pod map itself stays in Go.
+ * The whole batch is validated before the first row is stored (an amount beyond 2^60: KT_ERR_OVERFLOW_RISK, nothing is changed);
+ * kt_set_status below likewise. */
 int32_t kt_set_reserved(kt_engine* e, int32_t n, const int32_t* thr_rows, const kt_amounts* reserved);
 /* Stored CR status as the informer cache holds it (what CheckThrottledFor reads, throttle_types.go:128-153). */
 typedef struct kt_status {
@@ -380,7 +385,8 @@ int32_t kt_headroom_fetch(kt_engine* e, int64_t n, int64_t* out_copies, int32_t*
  *      twice within one gang (KT_ERR_INVALID_ARGUMENT), a pod row outside the table (KT_ERR_OUT_OF_RANGE), cap outside
  *      [1, KT_HEADROOM_MAX_CAP] (KT_ERR_INVALID_ARGUMENT), n x throttle_rows > 2^31 (KT_ERR_OUT_OF_RANGE), a stored `used` wider
  *      than int64 (KT_ERR_UNSUPPORTED), and an engine that has been fed a negative request (KT_ERR_UNSUPPORTED: the search rests
- *      on sums that only grow; kt_headroom_launch keeps serving such an engine pod by pod).  n == 0 is KT_OK and launches
+ *      on sums that only grow; kt_headroom_launch keeps serving such an engine pod by pod; the mark is set by an ACCEPTED pod batch
+ *      and stays when that pod is deleted or overwritten — only kt_load_snapshot clears it).  n == 0 is KT_OK and launches
  *      nothing.
  *      Slots: the engine's ONE check slot, exactly as kt_headroom_launch uses it.  A pending kt_headroom_launch and a pending
  *      kt_headroom_gangs_launch replace each other, and a fetch of the other kind answers KT_ERR_NOT_READY.

@@ -42,7 +42,7 @@ static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int6
   int64_t hi = e->pod_rows_hi, ns_hi = e->pod_ns_hi;
   unsigned __int128 batch_max[KT_MAX_DIMS] = {0}, batch_total[KT_MAX_DIMS] = {0};
   uint64_t batch_or[KT_MAX_DIMS] = {0};
-  const bool neg_before = e->neg_seen;
+  bool batch_neg = false;  // committed with max_abs / or_abs below: a refused batch leaves the engine as it was
   for (int64_t i = 0; i < n; ++i) {
     const int64_t row = rows ? rows[i] : i;
     if (row < 0 || row >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "pod row %lld", (long long)row);
@@ -59,14 +59,14 @@ static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int6
         if ((b->ctr_present[k] >> d) & 1u) {
           sum[d] += uabs(b->ctr_req[(size_t)k * D + d]);
           batch_or[d] |= (uint64_t)uabs(b->ctr_req[(size_t)k * D + d]);
-          if (b->ctr_req[(size_t)k * D + d] < 0) e->neg_seen = true;
+          if (b->ctr_req[(size_t)k * D + d] < 0) batch_neg = true;
         }
     if (b->pod_ovh_present[i] >> 31)
       for (int d = 0; d < D; ++d)
         if ((b->pod_ovh_present[i] >> d) & 1u) {
           sum[d] += uabs(b->pod_ovh[(size_t)i * D + d]);
           batch_or[d] |= (uint64_t)uabs(b->pod_ovh[(size_t)i * D + d]);
-          if (b->pod_ovh[(size_t)i * D + d] < 0) e->neg_seen = true;
+          if (b->pod_ovh[(size_t)i * D + d] < 0) batch_neg = true;
         }
     for (int d = 0; d < D; ++d) batch_max[d] = std::max(batch_max[d], sum[d]), batch_total[d] += sum[d];
   }
@@ -76,7 +76,8 @@ static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int6
     if (batch_max[d] > kSumBound)
       return e->fail(KT_ERR_OVERFLOW_RISK, "dimension %d: a pod's request exceeds 2^60 at this scale; use a coarser scale for it", d);
   // the scan lists / views: patched in place when the batch fits what they were built for, else rebuilt by the next scan
-  const bool patch = views_patchable(e, n, batch_max, batch_or, e->neg_seen && !neg_before);
+  const bool patch = views_patchable(e, n, batch_max, batch_or, batch_neg && !e->neg_seen);
+  e->neg_seen = e->neg_seen || batch_neg;
   for (int d = 0; d < D; ++d) {
     if (batch_max[d] > e->max_abs[d]) e->recs_valid = false;  // kRecTight was judged against the old bound
     e->max_abs[d] = std::max(batch_max[d], e->max_abs[d]);
@@ -599,12 +600,16 @@ int32_t kt_set_reserved(kt_engine* e, int32_t n, const int32_t* rows, const kt_a
   KT_HIP(e, hipSetDevice(e->device));
   for (int32_t i = 0; i < n; ++i)
     if (rows[i] < 0 || rows[i] >= e->thr_rows_hi) return e->fail(KT_ERR_OUT_OF_RANGE, "throttle row %d", rows[i]);
+  for (int32_t i = 0; i < n; ++i) {  // the whole batch is validated before the first row is stored
+    HostAmount a;
+    amount_from_table(*reserved, (size_t)i, e->D, a);
+    if (!amount_in_bound(a, e->D)) return e->fail(KT_ERR_OVERFLOW_RISK, "reserved amount beyond 2^60");
+  }
   int32_t rc = sync_status_to_host(e);
   if (rc != KT_OK) return rc;
   for (int32_t i = 0; i < n; ++i) {
     HostAmount a;
     amount_from_table(*reserved, (size_t)i, e->D, a);
-    if (!amount_in_bound(a, e->D)) return e->fail(KT_ERR_OVERFLOW_RISK, "reserved amount beyond 2^60");
     e->thr[(size_t)rows[i]].reserved = a;
   }
   e->status_host_dirty = true;
@@ -617,6 +622,11 @@ int32_t kt_set_status(kt_engine* e, int32_t n, const int32_t* rows, const kt_sta
   KT_HIP(e, hipSetDevice(e->device));
   for (int32_t i = 0; i < n; ++i)
     if (rows[i] < 0 || rows[i] >= e->thr_rows_hi) return e->fail(KT_ERR_OUT_OF_RANGE, "throttle row %d", rows[i]);
+  for (int32_t i = 0; i < n; ++i) {  // the whole batch is validated before the first row is stored
+    HostAmount u;
+    amount_from_table(st->used, (size_t)i, e->D, u);
+    if (!amount_in_bound(u, e->D)) return e->fail(KT_ERR_OVERFLOW_RISK, "status.used beyond 2^60");
+  }
   int32_t rc = sync_status_to_host(e);
   if (rc != KT_OK) return rc;
   const uint32_t dm = (1u << e->D) - 1u;
@@ -625,7 +635,6 @@ int32_t kt_set_status(kt_engine* e, int32_t n, const int32_t* rows, const kt_sta
     HostAmount u, c;
     amount_from_table(st->used, (size_t)i, e->D, u);
     amount_from_table(st->calc, (size_t)i, e->D, c);
-    if (!amount_in_bound(u, e->D)) return e->fail(KT_ERR_OVERFLOW_RISK, "status.used beyond 2^60");
     h.used = u;
     h.calc = c;
     h.thrl_flag = st->thrl_flag ? st->thrl_flag[i] & dm : 0;

@@ -1,0 +1,864 @@
+"""An engine that has lived through events, and what the query family answers on it (not a test file).
+
+Almost every GPU case of the query family builds its engine with ``Engine.for_snapshot``, asks once and closes it.  The plugin does
+the opposite: one engine lives for days, is fed pod, Throttle and reservation events, and is asked in between.  This module holds
+
+  * ``Pool``: one small hand-made cluster (three resource names; ``wide=True``: twenty, so two pages) as a pool of pod KINDS and
+    throttle KINDS, the pattern of test_match_codes_gpu.Pool — every variant a life needs (another threshold, a moved override
+    window, another selector, another namespace) is a throttle kind of its own, so one label and scale dictionary serves all;
+  * ``Mirror``: per page one Snapshot of what a freshly loaded engine would be loaded from, edited in place by every event
+    (``state[row] -> pod kind`` and ``tstate[row] -> throttle kind``, -1 for a deleted row; the stored status and the reserved
+    amounts live in the snapshot's own arrays); ``n_thr`` and ``n_pods`` stay the highest row ever used + 1;
+  * ``battery``: everything the query family answers for one fixed question set, for both ``on_equal`` values;
+  * ``model_battery``: the same dictionary from the host models (``paging.*_of``) and the oracle, on the mirror alone;
+  * ``Life``: the events, applied to the mirror and — when it has engines — to the live engine(s), and ``hold()``: live against a twin
+    loaded fresh from the mirror (which side moved?), live against the models (who is right?), live against itself (queries are dry);
+  * the lives, each a function of a Life: tests/test_queries_after_events_gpu.py runs them on the GPU, tests/test_lived_engine_cpu.py
+    replays them on the mirror alone and asserts they are not vacuous.
+
+Every comparison is exact: integers and bytes."""
+import copy
+from types import SimpleNamespace
+
+import numpy as np
+
+import forecast_reference as FR
+from kube_throttler_amd import engine as E
+from kube_throttler_amd import paging
+from kube_throttler_amd import snapshot as S
+from kube_throttler_amd.objects import ClusterState
+from test_engine_gpu import _permute_pods, _with_pods, assert_reconcile_equal, _rows_of
+
+NOW = FR.NOW
+INSTANTS = FR.instants_under_test()
+B = FR.BOUNDARY_TEXTS
+CAP = 24
+CAPS = (CAP, E.HEADROOM_MAX_CAP)
+P_CAP, T_CAP = 64, 24  # capacities of the live engine: above what the cluster starts with
+STATUS_BITS = S.THR_CALC_AT_NONZERO | S.THR_THROTTLED_POD
+NS = ("ns0", "ns1", "ns2")
+APPS = {"j": "job", "w": "web", "d": "db"}
+EXTRA = [f"example.com/r{k:02d}" for k in range(17)]  # wide=True: 3 + 17 names, two pages
+
+
+# ---- the pool --------------------------------------------------------------------------------------------------------------
+def _pod(name, ns, labels, requests, running=False):
+    p = {"kind": "Pod", "metadata": {"name": name, "namespace": ns, "labels": dict(labels)},
+         "spec": {"schedulerName": "my-scheduler", "containers": [{"name": "c", "resources": {"requests": dict(requests)}}]},
+         "status": {"phase": "Running" if running else "Pending"}}
+    if running:
+        p["spec"]["nodeName"] = "n1"
+    return p
+
+
+def _thr(name, terms, threshold, ns=None, overrides=None):
+    kind = "Throttle" if ns else "ClusterThrottle"
+    md = {"name": name}
+    if ns:
+        md["namespace"] = ns
+    sel = []
+    for labels in terms:
+        t = {"podSelector": {"matchLabels": dict(labels)}}
+        if not ns:
+            t["namespaceSelector"] = {"matchLabels": {"env": "prod"}}
+        sel.append(t)
+    spec = {"throttlerName": "kube-throttler", "selector": {"selectorTerms": sel}, "threshold": threshold}
+    if overrides:
+        spec["temporaryThresholdOverrides"] = overrides
+    return {"kind": kind, "metadata": md, "spec": spec}
+
+
+def _rr(**kw):
+    names = {"cpu": "cpu", "mem": "memory", "gpu": "amd.com/gpu"}
+    return {"resourceRequests": {names[k]: v for k, v in kw.items()}}
+
+
+def _cnt(n, **kw):
+    out = {"resourceCounts": {"pod": n}}
+    if kw:
+        out.update(_rr(**kw))
+    return out
+
+
+class Pool:
+    """The cluster as kinds: ``pod[name]`` / ``thr[name]`` are rows of the pool's snapshots ``snaps`` (one per page)."""
+
+    def __init__(self, wide=False):
+        cs = ClusterState()
+        cs.add_namespace("ns0", {"env": "prod", "kubernetes.io/metadata.name": "ns0"})
+        cs.add_namespace("ns1", {"env": "prod", "kubernetes.io/metadata.name": "ns1"})
+        cs.add_namespace("ns2", {"env": "dev", "kubernetes.io/metadata.name": "ns2"})  # (no ClusterThrottle admits it)
+        self.pod, self.thr = {}, {}
+
+        def pod(name, *a, **kw):
+            self.pod[name] = len(cs.pods)
+            cs.add(_pod(name, *a, **kw))
+
+        def thr(name, *a, **kw):
+            self.thr[name] = len(cs.throttles)
+            cs.add(_thr(name.split("@")[0], *a, **kw))
+
+        # every (namespace, app, team), pending and running: "0jx-p" is the pending job pod of team x in ns0
+        cpu = {"j": 300, "w": 200, "d": 500}
+        for n, ns in enumerate(NS):
+            for a, app in APPS.items():
+                for k, team in enumerate("xy"):
+                    for running in (False, True):
+                        req = {"cpu": f"{cpu[a] + 100 * k + 100 * running}m", "memory": f"{64 * (n + 1)}Mi"}
+                        if a == "d":
+                            req["amd.com/gpu"] = "1"
+                        if wide and a == "w":  # (the web pods carry the names of the second page too)
+                            req.update({name: "1" for name in EXTRA})
+                        pod(f"{n}{a}{team}-{'r' if running else 'p'}", ns, {"app": app, "team": team}, req, running)
+        pod("none", "ns0", {"app": "none"}, {"cpu": "100m", "memory": "64Mi"})                    # nothing matches it
+        pod("zero", "ns1", {"app": "job", "team": "x"}, {"cpu": "100m", "amd.com/gpu": "0"})     # carries a name with value 0
+        pod("ghost-p", "ghost", {"app": "job", "team": "x"}, {"cpu": "100m"})                     # no Namespace object: Error
+        pod("two", "ns0", {"app": "job", "team": "x", "m": "two"}, {"cpu": "100m", "memory": "64Mi"})  # both terms of t-two
+        pod("big", "ns0", {"app": "job", "team": "y"}, {"cpu": "5", "memory": "64Mi"})           # more than t-job admits at all
+        pod("small", "ns0", {"app": "job", "team": "y"}, {"cpu": "50m", "memory": "32Mi"})       # (an upsert's other requests)
+        pod("neg", "ns0", {"app": "web", "team": "y"}, {"cpu": "300m", "memory": "64Mi"}, True)  # (cpu made negative below)
+        pod("0wz-r", "ns0", {"app": "web", "team": "z"}, {"cpu": "100m", "memory": "64Mi"}, True)
+
+        win = lambda b, e, th: [{"begin": B[b], "end": B[e], "threshold": th}]
+        x = {name: "3" for name in EXTRA[-4:]} if wide else {}  # (c-web's names of both pages)
+        # the twelve throttles the cluster starts with (rows 0..11 of the mirror, in this order)
+        thr("ns0/t-job", [{"app": "job"}], _rr(cpu="1", mem="1Gi"), ns="ns0")
+        thr("ns0/t-web", [{"app": "web"}], _cnt(2), ns="ns0")
+        thr("ns1/t-job", [{"app": "job"}], _rr(cpu="1700m"), ns="ns1")
+        thr("ns1/t-team", [{"team": "x"}], _cnt(10), ns="ns1")
+        thr("ns2/t-db", [{"app": "db"}], _rr(cpu="2", gpu="2"), ns="ns2")
+        thr("c-job", [{"app": "job"}], _cnt(8, cpu="3"))
+        thr("c-web", [{"app": "web"}], {"resourceRequests": dict(_rr(cpu="1500m")["resourceRequests"], **x)},
+            overrides=win(3, 6, _cnt(20, cpu="10")))
+        thr("c-x", [{"team": "x"}], _cnt(7), overrides=win(1, 8, _cnt(40)))
+        thr("ns0/t-two", [{"m": "two"}, {"app": "job", "team": "x"}], _cnt(4), ns="ns0")
+        thr("ns2/t-web", [{"app": "web"}], _rr(mem="256Mi"), ns="ns2")
+        thr("c-db", [{"app": "db"}], _rr(gpu="6"))
+        thr("ns1/t-web", [{"app": "web"}], _rr(cpu="900m", mem="1Gi"), ns="ns1")
+        self.initial = list(self.thr)
+        # variants: the same throttle after an event ("name@what")
+        thr("ns1/t-job@tight", [{"app": "job"}], _rr(cpu="1"), ns="ns1")                           # a threshold edit
+        thr("ns1/t-web@mem", [{"app": "web"}], _rr(cpu="900m", mem="300Mi"), ns="ns1")             # ... of a name of the last page
+        thr("c-web@moved", [{"app": "web"}], {"resourceRequests": dict(_rr(cpu="1500m")["resourceRequests"], **x)},
+            overrides=win(2, 4, _cnt(20, cpu="10")))                                                # the window moved
+        thr("ns0/t-job@ovr", [{"app": "job"}], _rr(cpu="1", mem="1Gi"), ns="ns0", overrides=win(5, 7, _rr(cpu="4", mem="1Gi")))
+        thr("c-x@plain", [{"team": "x"}], _cnt(7))                                                  # its override removed
+        thr("ns1/t-job@web", [{"app": "web"}], _rr(cpu="2"), ns="ns1")                             # another selector
+        thr("ns1/t-team@ns2", [{"team": "x"}], _cnt(10), ns="ns2")                                 # moved to another namespace
+        thr("c-none", [{"app": "none"}], _cnt(0))                                                   # blocks the pod nobody blocked
+        thr("c-y", [{"team": "y"}], _cnt(5))                                                        # a freed row's next tenant
+        thr("ns2/t-web@db", [{"app": "db"}], _rr(mem="256Mi"), ns="ns2")                           # (an unrelated selector change)
+        self.cs = cs
+        pages = cs.build_pages()
+        assert len(pages) == (2 if wide else 1), len(pages)
+        self.snaps = [b.snapshot for b in pages]
+        self.dims = [b.dims for b in pages]
+        self.scales = [b.scales for b in pages]
+        for s, dims in zip(self.snaps, self.dims):
+            if "cpu" in dims:  # the one pod with a negative request
+                k = int(s.pod_ctr_off[self.pod["neg"]])
+                s.ctr_req[k, dims["cpu"]] = -s.ctr_req[k, dims["cpu"]]
+
+    # the pods the cluster starts with: row r holds PLACEMENT[r]
+    @property
+    def placement(self):
+        skip = {"neg", "small"}
+        return [name for name in self.pod if name not in skip]
+
+    def dim(self, name):
+        """(page, dimension) of a resource name"""
+        for k, dims in enumerate(self.dims):
+            if name in dims:
+                return k, dims[name]
+        raise KeyError(name)
+
+
+_POOLS = {}
+
+
+def pool(wide=False):
+    if wide not in _POOLS:
+        _POOLS[wide] = Pool(wide)
+    return _POOLS[wide]
+
+
+# ---- the question set ------------------------------------------------------------------------------------------------------
+class Questions:
+    """Fixed ROWS (events change what they hold): 8 single pods, 4 gangs of 1, 2, 3 and 5 members, 10 candidates."""
+
+    def __init__(self, pl):
+        r = {name: i for i, name in enumerate(pl.placement)}
+        self.row = r
+        self.pods = np.array([r[n] for n in ("0jx-p", "0wx-p", "1jy-p", "1wx-p", "none", "ghost-p", "big", "zero")], np.int64)
+        gangs = [["2jx-p"],                                        # no throttle reaches it
+                 ["1jx-p", "zero"],                                # both meet c-x, which has room for one: rolled back
+                 ["1jy-p", "0dy-p", "2jy-p"],                      # members that meet different throttles: admitted
+                 ["0jy-p", "1wy-p", "2wy-p", "ghost-p", "1dy-p"]]  # a member in the namespace without an object
+        self.gang_rows = np.array([r[n] for g in gangs for n in g], np.int64)
+        self.gang_off = np.cumsum([0] + [len(g) for g in gangs]).astype(np.int64)
+        self.cands = np.array([r[n] for n in ("1jx-r", "0jy-r", "0jx-r", "0wx-r", "0wy-r", "2dx-r", "1wx-r", "1wy-r", "2wx-r", "0dx-r")],
+                              np.int64)
+
+    def members(self, g):
+        return self.gang_rows[self.gang_off[g]:self.gang_off[g + 1]]
+
+
+# ---- the mirror ------------------------------------------------------------------------------------------------------------
+THR_SPEC_FIELDS = ("thr_ns", "thr_spec", "thr_spec_msgs_fp", "thr_ovr_off", "ovr_begin_s", "ovr_begin_ns", "ovr_end_s", "ovr_end_ns",
+                   "ovr_flags", "ovr_thr", "thr_term_off", "term_flags", "term_preq_off", "term_nreq_off", "preq", "nreq")
+POD_FIELDS = ("n_pods", "pod_ns", "pod_flags", "pod_label_off", "pod_label_key", "pod_label_pair", "pod_ctr_off", "ctr_init",
+              "ctr_present", "ctr_req", "pod_ovh_present", "pod_ovh")
+
+
+class Mirror:
+    def __init__(self, pl, pod_capacity=P_CAP, thr_capacity=T_CAP):
+        self.pl = pl
+        self.P, self.T = pod_capacity, thr_capacity
+        self.state = np.full(self.P, -1, np.int64)
+        self.tstate = np.full(self.T, -1, np.int64)
+        self.n_pods = self.n_thr = 0
+        self.snaps = []
+        for base in pl.snaps:
+            m = copy.copy(base)
+            m._keep = None
+            # the status side lives here, in arrays of the engine's capacity, and is edited in place
+            m.thr_flags = np.zeros(self.T, np.uint32)
+            for tab in ("thr_used", "thr_calc", "thr_reserved"):
+                setattr(m, tab, S.Amounts(self.T, base.D))
+            m.thr_thrl_flag, m.thr_thrl_has = np.zeros(self.T, np.uint32), np.zeros(self.T, np.uint32)
+            m.thr_status_msgs_fp = np.zeros(self.T, np.uint64)
+            self.snaps.append(m)
+
+    @property
+    def snap(self):
+        return self.snaps[0]
+
+    # -- pods
+    def put_pods(self, rows, kinds):
+        for r, k in zip(rows, kinds):  # (a row named twice: the last wins)
+            self.state[int(r)] = self.pl.pod[k] if isinstance(k, str) else int(k)
+            self.n_pods = max(self.n_pods, int(r) + 1)
+        self._refresh_pods()
+
+    def drop_pods(self, rows):
+        for r in rows:
+            self.state[int(r)] = -1
+        self._refresh_pods()
+
+    def _refresh_pods(self):
+        for m, base in zip(self.snaps, self.pl.snaps):
+            w = _with_pods(base, self.state[:self.n_pods])
+            for f in POD_FIELDS:
+                setattr(m, f, getattr(w, f))
+
+    # -- throttles
+    def put_throttles(self, rows, kinds):
+        for t, k in zip(rows, kinds):
+            self.tstate[int(t)] = self.pl.thr[k]
+            self.n_thr = max(self.n_thr, int(t) + 1)
+        self._refresh_throttles()
+
+    def drop_throttles(self, rows):
+        for t in rows:
+            self.tstate[int(t)] = -1
+            self._clear_status(int(t))
+        self._refresh_throttles()
+
+    def _clear_status(self, t):
+        for m in self.snaps:
+            for tab in (m.thr_used, m.thr_calc, m.thr_reserved):
+                tab.set_row(t, {}, None)
+            m.thr_thrl_flag[t] = m.thr_thrl_has[t] = 0
+            m.thr_status_msgs_fp[t] = 0
+            m.thr_flags[t] = 0
+
+    def _refresh_throttles(self):
+        n = self.n_thr
+        held = self.tstate[:n] >= 0
+        for m, base in zip(self.snaps, self.pl.snaps):
+            tb = base.throttle_batch(np.where(held, self.tstate[:n], 0))
+            for f in THR_SPEC_FIELDS:
+                setattr(m, f, getattr(tb, f))
+            m.n_thr = n
+            m.thr_flags[:n] = np.where(held, (tb.thr_flags[:n] & ~np.uint32(STATUS_BITS)) | (m.thr_flags[:n] & np.uint32(STATUS_BITS)), 0)
+            m._keep = None
+
+    # -- reserved amounts and stored status
+    def set_reserved(self, t, kinds, only_page=None):
+        """Throttle row t's reserved amount becomes what these pod kinds ask together (``only_page``: on that page alone)."""
+        for k, (m, base) in enumerate(zip(self.snaps, self.pl.snaps)):
+            if only_page is not None and k != only_page:
+                continue
+            vals = {}
+            for name in kinds:
+                for d, v in paging.pod_requests(base, self.pl.pod[name]).items():
+                    vals[d] = vals.get(d, 0) + v
+            m.thr_reserved.set_row(t, vals, len(kinds))
+
+    def take_reserved(self, reserved, k=0):
+        """The totals an admission model returned become page k's reserved table."""
+        m = self.snaps[k]
+        n = self.n_thr
+        for f in ("v", "present", "count", "has_count"):
+            getattr(m.thr_reserved, f)[:n] = getattr(reserved, f)[:n]
+
+    def reserved(self, k=0):
+        m, n = self.snaps[k], self.n_thr
+        return tuple(np.array(getattr(m.thr_reserved, f)[:n]) for f in ("v", "present", "count", "has_count"))
+
+    def reconcile(self, oracle_mod, now=NOW):
+        """The oracle's reconcile of every page becomes the stored status (CodesTwin.step's pattern); a calculated threshold is
+        replaced as a whole: where some page replaces it, every page has calculatedAt set.  -> per page (rows, result)"""
+        out = []
+        for m in self.snaps:
+            rows = responsible(m)
+            want = oracle_mod.Oracle(m).reconcile(now, rows=rows)
+            m.apply_status(want.used, want.calc, want.calc_updated, want.thrl_flag, want.thrl_has, want.thrl_pod, want.error, rows=rows)
+            out.append((rows, want))
+        if len(self.snaps) > 1:
+            any_set = np.zeros(self.n_thr, bool)
+            for m in self.snaps:
+                any_set |= (m.thr_flags[:self.n_thr] & S.THR_CALC_AT_NONZERO) != 0
+            for m in self.snaps:
+                m.thr_flags[:self.n_thr] |= np.where(any_set, np.uint32(S.THR_CALC_AT_NONZERO), np.uint32(0))
+        return out
+
+
+def responsible(snap):
+    need = S.THR_VALID | S.THR_RESPONSIBLE
+    return np.nonzero((snap.thr_flags[:snap.n_thr] & need) == need)[0].astype(np.int32)
+
+
+def load_fields(snap):
+    """The fields a load reads, as comparable values (tables cut to the rows in use)."""
+    out = {"D": snap.D, "n_ns": snap.n_ns, "n_pods": snap.n_pods, "n_thr": snap.n_thr}
+    n, T = snap.n_pods, snap.n_thr
+    nl, nc = int(snap.pod_label_off[n]), int(snap.pod_ctr_off[n])
+    no, nt = int(snap.thr_ovr_off[T]), int(snap.thr_term_off[T])
+    cut = {"pod_ns": n, "pod_flags": n, "pod_label_off": n + 1, "pod_label_key": nl, "pod_label_pair": nl, "pod_ctr_off": n + 1,
+           "ctr_init": nc, "ctr_present": nc, "ctr_req": nc, "pod_ovh_present": n, "pod_ovh": n, "thr_flags": T, "thr_ns": T,
+           "thr_thrl_flag": T, "thr_thrl_has": T, "thr_status_msgs_fp": T, "thr_spec_msgs_fp": T, "thr_ovr_off": T + 1,
+           "ovr_begin_s": no, "ovr_begin_ns": no, "ovr_end_s": no, "ovr_end_ns": no, "ovr_flags": no, "thr_term_off": T + 1,
+           "term_flags": nt, "term_preq_off": nt + 1, "term_nreq_off": nt + 1, "ns_valid": snap.n_ns, "ns_label_off": snap.n_ns + 1}
+    for f, k in cut.items():
+        out[f] = np.asarray(getattr(snap, f))[:k].tobytes()
+    for tab, k in (("thr_spec", T), ("thr_calc", T), ("thr_used", T), ("thr_reserved", T), ("ovr_thr", no)):
+        a = getattr(snap, tab)
+        out[tab] = tuple(np.asarray(getattr(a, f))[:k].tobytes() for f in ("v", "present", "count", "has_count"))
+    for name in ("preq", "nreq"):
+        op, key, val_off, val = getattr(snap, name).arrays()
+        r = len(getattr(snap, name))
+        out[name] = (op[:r].tobytes(), key[:r].tobytes(), val_off[:r + 1].tobytes(), val[:int(val_off[r])].tobytes())
+    # a deleted pod row is gated by its flags: what lies behind it is not read
+    live = (np.asarray(snap.pod_flags)[:n] & S.POD_VALID) != 0
+    out["live_rows"] = live.tobytes()
+    return out
+
+
+# ---- the battery -----------------------------------------------------------------------------------------------------------
+def _answer(f):
+    """An EngineError is recorded as its code, so a refusal compares like a value."""
+    try:
+        out = f()
+    except E.EngineError as err:
+        return ("error", err.code)
+    out = out if isinstance(out, tuple) else (out,)
+    return tuple(x if isinstance(x, (list, int)) else np.array(x) for x in out)
+
+
+def _amounts(a, n):
+    return tuple(np.array(getattr(a, f)[:n]) for f in ("v", "present", "count", "has_count"))
+
+
+def battery(eng, q, now=NOW):
+    """Everything the query family answers for the question set ``q`` on one engine, or on a list of page engines (the paged entry
+    points), for both ``on_equal`` values -> {(query, on_equal): arrays | ("error", code)}."""
+    if isinstance(eng, (list, tuple)):
+        return _paged_battery(list(eng), q, now)
+    out = {}
+    for eq in (False, True):
+        out["check", eq] = _answer(lambda: eng.check(rows=q.pods, on_equal=eq, want_status=True))
+        out["admit", eq] = _answer(lambda: eng.admit(rows=q.gang_rows, on_equal=eq, commit=False))
+        out["admit_gangs", eq] = _answer(lambda: eng.admit_gangs(q.gang_rows, q.gang_off, on_equal=eq, commit=False))
+        for cap in CAPS:
+            out["headroom", cap, eq] = _answer(lambda: eng.headroom(rows=q.pods, cap=cap, on_equal=eq))
+            out["headroom_gangs", cap, eq] = _answer(lambda: eng.headroom_gangs(q.gang_rows, q.gang_off, cap=cap, on_equal=eq))
+        for rep in (False, True):
+            out["preempt", rep, eq] = _answer(lambda: eng.preempt(q.pods, q.cands, now, on_equal=eq, reprieve=rep))
+            out["preempt_gangs", rep, eq] = _answer(lambda: eng.preempt_gangs(q.gang_rows, q.gang_off, q.cands, now, on_equal=eq, reprieve=rep))
+        out["forecast", eq] = _answer(lambda: eng.forecast(q.pods, INSTANTS, on_equal=eq))
+        out["forecast_gangs", eq] = _answer(lambda: eng.forecast_gangs(q.gang_rows, q.gang_off, INSTANTS, on_equal=eq))
+    out["override_instants"] = _answer(lambda: eng.override_instants(NOW, FR.BEYOND))
+    out["reserved"] = _answer(lambda: _amounts(eng.fetch_reserved(), eng.throttle_rows()))
+    return out
+
+
+def _paged_battery(engs, q, now):
+    out = {}
+    for eq in (False, True):
+        out["check", eq] = _answer(lambda: E.paged_check(engs, len(q.pods), rows=q.pods, on_equal=eq))
+        out["check_status", eq] = out["check", eq][:1]
+        out["admit", eq] = _answer(lambda: E.paged_admit(engs, q.gang_rows, on_equal=eq, commit=False))
+        out["admit_gangs", eq] = _answer(lambda: E.paged_admit_gangs(engs, q.gang_rows, q.gang_off, on_equal=eq, commit=False))
+        for cap in CAPS:
+            out["headroom", cap, eq] = _answer(lambda: E.paged_headroom(engs, q.pods, cap, on_equal=eq))
+        for rep in (False, True):
+            out["preempt", rep, eq] = _answer(lambda: E.paged_preempt(engs, q.pods, q.cands, now, on_equal=eq, reprieve=rep))
+            out["preempt_gangs", rep, eq] = _answer(lambda: E.paged_preempt_gangs(engs, q.gang_rows, q.gang_off, q.cands, now, on_equal=eq, reprieve=rep))
+        out["forecast", eq] = _answer(lambda: E.paged_forecast(engs, q.pods, INSTANTS, on_equal=eq))
+        out["forecast_gangs", eq] = _answer(lambda: E.paged_forecast_gangs(engs, q.gang_rows, q.gang_off, INSTANTS, on_equal=eq))
+    for k, e in enumerate(engs):
+        out["override_instants", k] = _answer(lambda: e.override_instants(NOW, FR.BEYOND))
+        out["reserved", k] = _answer(lambda: _amounts(e.fetch_reserved(), e.throttle_rows()))
+    return out
+
+
+def _model_admit_gangs(snap, q, eq, oracle_mod):
+    """test_gang_admit_cpu.model_admit_gangs on a Snapshot: every member takes the oracle's in-order step, also behind one that
+    failed; a gang with a member that is not Success gives its reservations back."""
+    work = copy.copy(snap)
+    work._keep = None
+    work.thr_reserved = snap.thr_reserved.copy()
+    st_all, sm_all, admitted = [], [], []
+    for g in range(len(q.gang_off) - 1):
+        st, sm, res = oracle_mod.Oracle(work).admit(rows=q.members(g), on_equal=eq)
+        valid = (np.asarray(snap.pod_flags)[q.members(g)] & S.POD_VALID) != 0  # (kt_engine.h: an invalid pod row fails its gang)
+        ok = bool(((sm & np.uint64(3)) == 0).all() and valid.all())
+        if ok:
+            for f in ("v", "present", "count", "has_count"):
+                getattr(work.thr_reserved, f)[:snap.n_thr] = getattr(res, f)[:snap.n_thr]
+            work._keep = None
+        st_all.append(st), sm_all.append(sm), admitted.append(ok)
+    return np.concatenate(st_all), np.concatenate(sm_all), np.array(admitted, np.uint8)
+
+
+def _queue_pos(blockers, q):
+    """The models name a blocker by its position inside the gang, the engine by its position in the queue."""
+    out = np.array(blockers, np.int64)
+    off = q.gang_off[:-1].reshape((-1,) + (1,) * (out.ndim - 1))
+    return np.where(out >= 0, out + off, out)
+
+
+def model_battery(mirror, q, oracle_mod, now=NOW):
+    """``battery``'s dictionary from the host models and the oracle on the mirror (a paged mirror: the queries the models cover)."""
+    snaps = mirror.snaps
+    if len(snaps) > 1:
+        return _paged_model_battery(mirror, q, oracle_mod, now)
+    snap = snaps[0]
+    page = [SimpleNamespace(snapshot=snap)]
+    ng, m, T = len(q.gang_off) - 1, len(q.cands), snap.n_thr
+    ctx = paging.preempt_context(snap, now)
+    out = {}
+    for eq in (False, True):
+        out["check", eq] = _answer(lambda: oracle_mod.Oracle(snap).check(rows=q.pods, on_equal=eq, want_status=True))
+        st, sm, _ = oracle_mod.Oracle(snap).admit(rows=q.gang_rows, on_equal=eq)
+        out["admit", eq] = (np.array(st), np.array(sm))
+        out["admit_gangs", eq] = _model_admit_gangs(snap, q, eq, oracle_mod)
+        for cap in CAPS:
+            h = [paging.headroom_of(page, p, cap, eq) for p in q.pods]
+            out["headroom", cap, eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32))
+            h = [paging.headroom_gangs_of(snap, q.members(g), cap, eq) for g in range(ng)]
+            out["headroom_gangs", cap, eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32),
+                                              _queue_pos([x[2] for x in h], q))
+        for rep in (False, True):
+            a = [paging.preempt_of(snap, p, q.cands, now, eq, ctx=ctx, reprieve=rep) for p in q.pods]
+            out["preempt", rep, eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8).reshape(len(a), m))
+            a = [paging.preempt_gangs_of(snap, q.members(g), q.cands, now, eq, ctx=ctx, reprieve=rep) for g in range(ng)]
+            out["preempt_gangs", rep, eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8).reshape(ng, m),
+                                             _queue_pos([x[2] for x in a], q))
+        a = [paging.forecast_of(snap, p, INSTANTS, eq, ctx=ctx) for p in q.pods]
+        out["forecast", eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8))
+        a = [paging.forecast_gangs_of(snap, q.members(g), INSTANTS, eq, ctx=ctx) for g in range(ng)]
+        out["forecast_gangs", eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8),
+                                     _queue_pos([x[2] for x in a], q))
+    inst = paging.override_instants_of(snap, NOW, FR.BEYOND)
+    out["override_instants"] = ([(int(a), int(b)) for a, b in inst], len(inst))
+    out["reserved"] = _amounts(snap.thr_reserved, T)
+    return out
+
+
+def _paged_model_battery(mirror, q, oracle_mod, now):
+    snaps = mirror.snaps
+    pages = [SimpleNamespace(snapshot=s) for s in snaps]
+    ng, m = len(q.gang_off) - 1, len(q.cands)
+    ctx = paging.paged_preempt_context(snaps, now)
+    out = {}
+    for eq in (False, True):
+        out["check_status", eq] = (paging.combine_status([oracle_mod.Oracle(s).check(rows=q.pods, on_equal=eq)[0] for s in snaps]),)
+        for cap in CAPS:
+            h = [paging.headroom_of(pages, p, cap, eq) for p in q.pods]
+            out["headroom", cap, eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32))
+        for rep in (False, True):
+            a = [paging.paged_preempt_of(snaps, p, q.cands, now, eq, reprieve=rep, ctx=ctx) for p in q.pods]
+            out["preempt", rep, eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8).reshape(len(a), m))
+            a = [paging.paged_preempt_gangs_of(snaps, q.members(g), q.cands, now, eq, reprieve=rep, ctx=ctx) for g in range(ng)]
+            out["preempt_gangs", rep, eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8).reshape(ng, m),
+                                             _queue_pos([x[2] for x in a], q))
+        a = [paging.paged_forecast_of(snaps, p, INSTANTS, eq, ctx=ctx) for p in q.pods]
+        out["forecast", eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8))
+        a = [paging.paged_forecast_gangs_of(snaps, q.members(g), INSTANTS, eq, ctx=ctx) for g in range(ng)]
+        out["forecast_gangs", eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8),
+                                     _queue_pos([x[2] for x in a], q))
+    for k, s in enumerate(snaps):
+        inst = paging.override_instants_of(s, NOW, FR.BEYOND)
+        out["override_instants", k] = ([(int(a), int(b)) for a, b in inst], len(inst))
+        out["reserved", k] = _amounts(s.thr_reserved, s.n_thr)
+    return out
+
+
+def same(a, b):
+    """Two answers, bit for bit."""
+    err_a, err_b = isinstance(a[0], str), isinstance(b[0], str)
+    if err_a or err_b:
+        return err_a and err_b and tuple(a) == tuple(b)
+    if len(a) != len(b):
+        return False
+    for x, y in zip(a, b):
+        if isinstance(x, np.ndarray) or isinstance(y, np.ndarray):
+            x, y = np.asarray(x), np.asarray(y)
+            if x.dtype != y.dtype or x.shape != y.shape or x.tobytes() != y.tobytes():
+                return False
+        elif x != y:
+            return False
+    return True
+
+
+def differences(a, b, keys=None):
+    """The keys (of ``keys``, default: those of b) at which two batteries differ."""
+    return [k for k in (b if keys is None else keys) if k not in a or not same(a[k], b[k])]
+
+
+def assert_same(a, b, what, keys=None):
+    bad = differences(a, b, keys)
+    assert not bad, f"{what}: differ at {bad[:6]}\n  {a.get(bad[0])}\n  {b.get(bad[0])}"
+
+
+# ---- a life ----------------------------------------------------------------------------------------------------------------
+class Life:
+    """The mirror, and — with ``gpu=True`` — the live engine (one per page), fed by events from empty with spare capacity.  Every
+    event is applied to both.  ``hold()`` records the models' battery (``self.held``: [(step name, battery)]); with engines it first
+    compares live, twin and models."""
+
+    def __init__(self, oracle_mod, gpu=False, wide=False):
+        self.o = oracle_mod
+        self.pl = pool(wide)
+        self.q = Questions(self.pl)
+        self.mirror = Mirror(self.pl)
+        self.engines = []
+        self.held = []
+        self.live_held = []
+        self.soft = None  # a list: hold() collects what differs there and goes on (a survey of a whole life)
+        names = self.pl.placement
+        self.mirror.put_throttles(range(len(self.pl.initial)), self.pl.initial)
+        self.mirror.put_pods(range(len(names)), names)
+        if gpu:
+            for m, base in zip(self.mirror.snaps, self.pl.snaps):
+                e = E.Engine(base.D, max(base.L, 1), P_CAP, T_CAP, max(base.n_ns, 1) + 1)
+                self.engines.append(e)
+                e.upsert_namespaces(base)
+                e.upsert_throttles(m.throttle_batch(np.arange(m.n_thr)), rows=np.arange(m.n_thr))
+                e.upsert_pods(_permute_pods(base, self.mirror.state[:len(names)]), rows=np.arange(len(names)))
+
+    @property
+    def eng(self):
+        return self.engines[0]
+
+    def close(self):
+        for e in self.engines:
+            e.close()
+        self.engines = []
+
+    def row(self, name):
+        return self.q.row[name]
+
+    # -- events
+    def upsert_pods(self, rows, kinds):
+        rows = np.asarray(rows, np.int64)
+        src = np.array([self.pl.pod[k] for k in kinds], np.int64)
+        for e, base in zip(self.engines, self.pl.snaps):
+            e.upsert_pods(_permute_pods(base, src), rows=rows)
+        self.mirror.put_pods(rows, kinds)
+
+    def delete_pods(self, rows):
+        for e in self.engines:
+            e.delete_pods(np.asarray(rows, np.int64))
+        self.mirror.drop_pods(rows)
+
+    def upsert_throttles(self, rows, kinds):
+        self.mirror.put_throttles(rows, kinds)
+        for e, m in zip(self.engines, self.mirror.snaps):
+            e.upsert_throttles(m.throttle_batch(np.asarray(rows)), rows=np.asarray(rows, np.int32))
+
+    def delete_throttles(self, rows):
+        for e in self.engines:
+            e.delete_throttles(np.asarray(rows, np.int32))
+        self.mirror.drop_throttles(rows)
+
+    def set_reserved(self, t, kinds, only_page=None):
+        self.mirror.set_reserved(t, kinds, only_page)
+        for e, m in zip(self.engines, self.mirror.snaps):
+            a = S.Amounts(1, m.D)
+            for f in ("v", "present", "count", "has_count"):
+                getattr(a, f)[0] = getattr(m.thr_reserved, f)[t]
+            e.set_reserved(np.array([t], np.int32), a)
+
+    def set_used(self, t, name, value):
+        """kt_set_status from the host: one throttle's `used` of one name is raised (the rest of its status as stored)."""
+        k, d = self.pl.dim(name)
+        m = self.mirror.snaps[k]
+        m.thr_used.v[t, d] = value
+        m.thr_used.present[t] |= np.uint32(1 << d)
+        for e, m in zip(self.engines, self.mirror.snaps):
+            used, calc = S.Amounts(1, m.D), S.Amounts(1, m.D)
+            for f in ("v", "present", "count", "has_count"):
+                getattr(used, f)[0] = getattr(m.thr_used, f)[t]
+                getattr(calc, f)[0] = getattr(m.thr_calc, f)[t]
+            fl = int(m.thr_flags[t])
+            e.set_status(np.array([t], np.int32), used, calc, [1 if fl & S.THR_CALC_AT_NONZERO else 0], [m.thr_thrl_flag[t]],
+                         [m.thr_thrl_has[t]], [1 if fl & S.THR_THROTTLED_POD else 0], msgs_fp=[m.thr_status_msgs_fp[t]])
+
+    def reconcile(self, now=NOW):
+        """reconcile(apply) on the live engine, the oracle's status into the mirror; the two are compared on the way."""
+        want = self.mirror.reconcile(self.o, now)
+        if len(self.engines) == 1:
+            got = self.eng.reconcile(now, apply=True)
+            rows, w = want[0]
+            assert_reconcile_equal(_rows_of(got, rows, self.mirror.snap.D), w, len(rows))
+        elif self.engines:
+            E.paged_reconcile(self.engines, now, apply=True)
+
+    def admit_commit(self, rows, on_equal=False):
+        """admit(commit=True) of a short queue: the mirror takes the admission model's reservation."""
+        rows = np.asarray(rows, np.int64)
+        snap = self.mirror.snap
+        st, sm, res = self.o.Oracle(snap).admit(rows=rows, on_equal=on_equal)
+        if self.engines:
+            got = _answer(lambda: self.eng.admit(rows=rows, on_equal=on_equal, commit=True))
+            assert same(got, (np.array(st), np.array(sm))), f"admit(commit): {got} against the oracle's {(st, sm)}"
+        self.mirror.take_reserved(res)
+        return sm
+
+    def admit_gangs_commit(self, q, on_equal=False):
+        snap = self.mirror.snap
+        want = _model_admit_gangs(snap, q, on_equal, self.o)
+        work = copy.copy(snap)
+        work.thr_reserved = snap.thr_reserved.copy()
+        for g in range(len(q.gang_off) - 1):  # the admitted gangs' reservations, gang by gang
+            if want[2][g]:
+                work._keep = None
+                _, _, res = self.o.Oracle(work).admit(rows=q.members(g), on_equal=on_equal)
+                for f in ("v", "present", "count", "has_count"):
+                    getattr(work.thr_reserved, f)[:snap.n_thr] = getattr(res, f)[:snap.n_thr]
+        if self.engines:
+            got = _answer(lambda: self.eng.admit_gangs(q.gang_rows, q.gang_off, on_equal=on_equal, commit=True))
+            assert same(got, want), f"admit_gangs(commit): {got} against the model's {want}"
+        self.mirror.take_reserved(work.thr_reserved)
+        return want[2]
+
+    # -- hold
+    def twin(self):
+        return [E.Engine.for_snapshot(m) for m in self.mirror.snaps]
+
+    def hold(self, step, refused=(), live_refuses=()):
+        """``refused``: query names the engine answers KT_ERR_UNSUPPORTED on live AND twin (the models are not asked);
+        ``live_refuses``: ... on the live engine only — the twin serves them and is held to the models."""
+        model = model_battery(self.mirror, self.q, self.o)
+        self.held.append((step, model))
+        if not self.engines:
+            return model
+        target = self.engines if len(self.engines) > 1 else self.eng
+        live = battery(target, self.q)
+        tw = self.twin()
+        try:
+            twin = battery(tw if len(tw) > 1 else tw[0], self.q)
+        finally:
+            for e in tw:
+                e.close()
+        again = battery(target, self.q)
+        problems = []
+
+        def expect(x, y, what, keys=None):
+            bad = differences(x, y, keys)
+            if bad:
+                problems.append(f"{step}: {what}: differ at {bad[:8]}\n  {x.get(bad[0])}\n  {y.get(bad[0])}")
+
+        expect(live, again, "a second run of the battery on the live engine (queries are dry)")
+        unsupported = ("error", -7)
+        plain = [k for k in live if k[0] not in refused and k[0] not in live_refuses]
+        for k in live:
+            if k[0] in refused and not (live[k] == unsupported and twin[k] == unsupported):
+                problems.append(f"{step}: {k}: live {live[k]}, twin {twin[k]}: both refuse it")
+            elif k[0] in live_refuses and live[k] != unsupported:
+                problems.append(f"{step}: {k}: live {live[k]}: the live engine refuses it")
+        assert set(live) == set(twin)
+        expect(live, twin, "live engine against a twin loaded fresh from the mirror", plain)
+        expect(twin, model, "twin against the host models", [k for k in model if k[0] not in refused])
+        expect(live, model, "live engine against the host models", [k for k in model if k in plain])
+        if self.soft is None:
+            assert not problems, "\n".join(problems)
+        self.soft = None if self.soft is None else self.soft + problems
+        self.live_held.append((step, live))
+        return live
+
+
+# ---- the lives: every step is named --------------------------------------------------------------------------------------------
+def start(life):
+    life.reconcile()
+    life.hold("start")
+
+
+def life_pod_events(life):
+    r = life.row
+    start(life)
+    life.upsert_pods([r("0jy-r")], ["0jx-r"])               # other requests (and another team) in a candidate's row
+    life.hold("an upsert changes the requests of a candidate's row")
+    life.upsert_pods([r("1jy-p")], ["1jy-r"])               # a gang member (and single pod) becomes running ...
+    life.hold("a pending gang member becomes running")
+    life.upsert_pods([r("1jy-p")], ["1jy-p"])               # ... and pending again
+    life.hold("... and pending again")
+    n = life.mirror.n_pods
+    life.upsert_pods([n + 2], ["1jy-r"])                    # beyond pod_rows_hi (row n and n + 1 stay empty)
+    life.hold("a row is appended beyond pod_rows_hi")
+    life.delete_pods([r("0dy-p"), r("0jx-r")])              # a member of gang 2 and a candidate
+    life.hold("a delete hits a gang member and a candidate")
+    life.upsert_pods([r("0dy-p")], ["1dx-r"])               # the freed row: a pod of another namespace
+    life.hold("the freed row is reused by a pod of another namespace")
+    life.upsert_pods([r("0wx-r"), r("none"), r("0wx-r")], ["0wy-p", "0wz-r", "small"])  # one batch names a row twice: the last wins
+    life.hold("one batch names a row twice")
+
+
+def life_threshold_and_override_events(life):
+    t = {name: i for i, name in enumerate(life.pl.initial)}
+    start(life)
+    compiles = life.eng.compiles() if life.engines else None
+
+    def step(name):
+        life.hold(name)  # (no reconcile: the stored status is the old one, on the engine and in the mirror)
+        if life.engines:
+            assert life.eng.compiles() == compiles, f"{name}: {life.eng.compiles()} compiles, {compiles} before"
+
+    life.upsert_throttles([t["ns1/t-job"]], ["ns1/t-job@tight"])
+    step("a threshold edit moves the limiting throttle of a headroom answer")
+    life.upsert_throttles([t["c-web"]], ["c-web@moved"])
+    step("an override window is moved")
+    life.upsert_throttles([t["ns0/t-job"]], ["ns0/t-job@ovr"])
+    step("an override is added to a throttle that had none")
+    life.upsert_throttles([t["c-x"]], ["c-x@plain"])
+    step("an override is removed")
+    life.reconcile()
+    step("one reconcile(apply) behind the four events")
+
+
+def life_selector_and_row_events(life):
+    t = {name: i for i, name in enumerate(life.pl.initial)}
+    start(life)
+    compiles = [life.eng.compiles() if life.engines else 0]
+
+    def step(name):
+        life.hold(name)
+        if life.engines:
+            assert life.eng.compiles() == compiles[0] + 1, f"{name}: {life.eng.compiles()} compiles, {compiles[0]} before"
+            compiles[0] += 1
+
+    life.upsert_throttles([t["ns1/t-job"]], ["ns1/t-job@web"])      # right after reconcile(apply): the device's status is newer
+    step("a throttle's selector changes right after reconcile(apply)")
+    life.reconcile()
+    life.upsert_throttles([t["ns1/t-team"]], ["ns1/t-team@ns2"])
+    step("a throttle moves namespace")
+    life.reconcile()
+    new = life.mirror.n_thr + 1                                     # beyond thr_rows_hi (a row stays empty in between)
+    life.upsert_throttles([new], ["c-none"])
+    step("a new throttle appears in a row beyond thr_rows_hi")
+    life.reconcile()
+    life.delete_throttles([t["c-x"]])                               # the row that limited gang 1
+    step("delete_throttles removes the row that limited a gang")
+    life.reconcile()
+    life.upsert_throttles([t["c-x"]], ["c-y"])
+    step("the freed row is reused by a ClusterThrottle")
+    life.reconcile()
+    life.hold("... and has been reconciled too")
+
+
+def life_reservations_survive(life):
+    t = {name: i for i, name in enumerate(life.pl.initial)}
+    r = life.row
+    start(life)
+    life.set_reserved(t["ns1/t-job"], ["1jx-p"])
+    life.set_reserved(t["c-db"], ["0dx-p"])
+    life.hold("set_reserved on two rows")
+    life.admit_gangs_commit(life.q)
+    life.hold("admit_gangs(commit=True)")
+    life.admit_commit([r("0dx-p"), r("1wx-p"), r("none"), r("1jy-p"), r("two")])
+    life.hold("admit(commit=True) on a short queue")
+    life.upsert_throttles([t["ns2/t-web"]], ["ns2/t-web@db"])       # reserved amounts the device advanced go to the host and back
+    life.hold("a selector-changing throttle event of an unrelated row")
+    life.reconcile()
+    used =int(life.mirror.snap.thr_used.v[t["ns1/t-web"], life.pl.dim("cpu")[1]])
+    life.set_used(t["ns1/t-web"], "cpu", used + 150)
+    life.hold("a set_status from the host raises one throttle's used")
+
+
+def life_negative_came_and_went(life):
+    start(life)
+    n = life.mirror.n_pods
+    life.upsert_pods([n], ["neg"])
+    life.hold("a pod with a negative request is there", refused=("headroom_gangs",))
+    life.reconcile()
+    life.hold("... and has been reconciled", refused=("headroom_gangs",))
+    life.delete_pods([n])
+    life.hold("the pod with the negative request is gone", live_refuses=("headroom_gangs",))
+    life.reconcile()
+    life.hold("... and a reconcile behind it", live_refuses=("headroom_gangs",))
+
+
+def life_two_pages(life):
+    t = {name: i for i, name in enumerate(life.pl.initial)}
+    r = life.row
+    start(life)
+    life.upsert_pods([r("1wy-p")], ["1wx-r"])
+    life.hold("a pod upsert")
+    life.delete_pods([r("0wx-r")])
+    life.hold("a pod delete")
+    life.upsert_pods([r("0wx-r")], ["1wy-r"])
+    life.hold("the row is reused")
+    life.set_reserved(t["ns1/t-web"], ["1wx-p"], only_page=1)
+    life.hold("set_reserved on page 1")
+    life.upsert_throttles([t["ns1/t-web"]], ["ns1/t-web@mem"])
+    life.hold("a threshold edit on page 1")
+    life.reconcile()
+    life.hold("a reconcile behind them")
+
+
+LIVES = {"pod_events": life_pod_events, "threshold_and_override_events": life_threshold_and_override_events,
+         "selector_and_row_events": life_selector_and_row_events, "reservations_survive": life_reservations_survive,
+         "negative_came_and_went": life_negative_came_and_went}
+
+
+# ---- refused batches -------------------------------------------------------------------------------------------------------
+REFUSALS = ("row-outside-capacity", "namespace-id-outside-capacity", "more-labels-than-kept", "request-beyond-2^60")
+
+
+def refused_pod_batch(pl, case, page=0):
+    """(batch, rows, expected code): entry 0 a pod with a NEGATIVE request that is larger than any the engine holds and has new
+    odd low bits, entry 1 the pod the engine refuses the batch for."""
+    base = pl.snaps[page]
+    b = _permute_pods(base, [pl.pod["neg"], pl.pod["0jx-p"]])
+    b.ctr_req[0, pl.dim("cpu")[1]] = -((1 << 40) + 12345)
+    rows = np.array([P_CAP - 2, P_CAP - 1], np.int64)
+    code = -2
+    if case == "row-outside-capacity":
+        rows[1] = P_CAP
+    elif case == "namespace-id-outside-capacity":
+        b.pod_ns[1] = 1000
+    elif case == "more-labels-than-kept":
+        k = base.L + 1
+        lo = int(b.pod_label_off[1])
+        b.pod_label_key = np.concatenate([b.pod_label_key[:lo], np.arange(k, dtype=np.uint32)])
+        b.pod_label_pair = np.concatenate([b.pod_label_pair[:lo], np.arange(k, dtype=np.uint32)])
+        b.pod_label_off[2] = lo + k
+    elif case == "request-beyond-2^60":
+        b.ctr_req[1, pl.dim("cpu")[1]] = 1 << 61
+        code = -4
+    else:
+        raise KeyError(case)
+    return b, rows, code

@@ -1,0 +1,145 @@
+"""The lives of tests/lived_engine.py, replayed on the mirror alone (models and oracle, no GPU): they are not vacuous.
+
+tests/test_queries_after_events_gpu.py holds a live engine to a fresh twin and to the host models after every event of a life.  That
+tests something only if the events move the answers and the answers show every kind of outcome — which is checked here, where it
+can be checked without a GPU:
+  * every event changes at least one model answer of the battery against the step before;
+  * over all lives the battery shows a pod admitted, blocked `active`, blocked `insufficient` and an Error; a gang admitted and a gang
+    rolled back (a member was admitted, the gang is not); a headroom of 0, one strictly between 0 and CAP and one at CAP; a
+    preemption prefix of 0, an inner one and "no prefix helps"; a forecast that flips inside the instants;
+  * the mirror after each life equals a mirror built in one go from the same final placement, in every field a load reads;
+  * the refused batches are refused for the stated reason alone, behind a negative, larger, odd request."""
+import numpy as np
+import pytest
+
+import forecast_reference as FR
+import lived_engine as LE
+from kube_throttler_amd import snapshot as S
+
+ALL_LIVES = dict(LE.LIVES, two_pages=LE.life_two_pages)
+
+
+@pytest.fixture(scope="module")
+def replayed(oracle_mod):
+    out = {}
+    for name, script in ALL_LIVES.items():
+        life = LE.Life(oracle_mod, gpu=False, wide=name == "two_pages")
+        script(life)
+        out[name] = life
+    return out
+
+
+@pytest.mark.parametrize("name", list(ALL_LIVES))
+def test_every_event_moves_an_answer(name, replayed):
+    held = replayed[name].held
+    assert len(held) >= 5
+    for (before, a), (step, b) in zip(held[:-1], held[1:]):
+        moved = LE.differences(a, b)
+        print(f"{name}: {step}: {len(moved)} answers moved, e.g. {moved[:4]}")
+        assert moved, f"{name}: '{step}' changes no model answer against '{before}'"
+
+
+def test_a_headroom_answer_changes_its_limiting_throttle(replayed):
+    """What the threshold edit is for: same pod, another limiting row."""
+    held = replayed["threshold_and_override_events"].held  # (the check reads the STORED calculated threshold: the last step's reconcile)
+    (_, a), (_, b) = held[0], held[-1]
+    la, lb = a["headroom", LE.CAP, False][1], b["headroom", LE.CAP, False][1]
+    assert ((la != lb) & (la >= 0) & (lb >= 0)).any(), (la, lb)
+
+
+def test_the_new_throttle_blocks_a_pod_nobody_blocked(replayed):
+    life = replayed["selector_and_row_events"]
+    steps = dict(life.held)
+    i = list(life.q.pods).index(life.row("none"))
+    assert steps["start"]["check", False][1][i] == 0
+    assert int(steps["a new throttle appears in a row beyond thr_rows_hi"]["check", False][1][i]) & 3 == S.VERDICT_BLOCK
+
+
+def test_deleted_rows_answer_as_the_header_says(replayed):
+    """0 copies, blocked in front of the deleted member, no limiting throttle."""
+    life = replayed["pod_events"]
+    b = dict(life.held)["a delete hits a gang member and a candidate"]
+    copies, limiting, blocker = b["headroom_gangs", LE.CAP, False]
+    assert (copies[2], limiting[2], blocker[2]) == (0, -1, life.q.gang_off[2] + 1)
+
+
+def test_the_battery_shows_every_outcome_kind(replayed):
+    seen = set()
+    for life in replayed.values():
+        if len(life.mirror.snaps) > 1:
+            continue
+        q = life.q
+        for _, b in life.held:
+            for eq in (False, True):
+                verdict, _, active, insufficient = S.summary_fields(b["admit", eq][1])
+                seen |= {"pod admitted"} if (verdict == 0).any() else set()
+                seen |= {"pod active"} if ((verdict == 1) & (active > 0)).any() else set()
+                seen |= {"pod insufficient"} if ((verdict == 1) & (insufficient > 0)).any() else set()
+                seen |= {"pod error"} if (verdict == 2).any() else set()
+                _, sm, admitted = b["admit_gangs", eq]
+                for g in range(len(admitted)):
+                    v = sm[q.gang_off[g]:q.gang_off[g + 1]] & np.uint64(3)
+                    if admitted[g] and len(v) > 1:
+                        seen.add("gang admitted")
+                    if not admitted[g] and (v == 0).any():
+                        seen.add("gang rolled back")
+                for kind in ("headroom", "headroom_gangs"):
+                    c = b[kind, LE.CAP, eq][0]
+                    seen |= {f"{kind} 0"} if (c == 0).any() else set()
+                    seen |= {f"{kind} inner"} if ((c > 0) & (c < LE.CAP)).any() else set()
+                    seen |= {f"{kind} cap"} if (c == LE.CAP).any() else set()
+                for kind in ("preempt", "preempt_gangs"):
+                    for rep in (False, True):
+                        k = b[kind, rep, eq][0]
+                        seen |= {f"{kind} 0"} if (k == 0).any() else set()
+                        seen |= {f"{kind} inner"} if (k > 0).any() else set()
+                        seen |= {f"{kind} none"} if (k == -1).any() else set()
+                    plain, walked = b[kind, False, eq][1], b[kind, True, eq][1]
+                    if plain.sum() > walked.sum():
+                        seen.add(f"{kind} reprieve puts a victim back")
+                for kind in ("forecast", "forecast_gangs"):
+                    if any(FR.flips(row) for row in b[kind, eq][1]):
+                        seen.add(f"{kind} flips")
+    want = {"pod admitted", "pod active", "pod insufficient", "pod error", "gang admitted", "gang rolled back"}
+    want |= {f"{k} {x}" for k in ("headroom", "headroom_gangs") for x in ("0", "inner", "cap")}
+    want |= {f"{k} {x}" for k in ("preempt", "preempt_gangs") for x in ("0", "inner", "none", "reprieve puts a victim back")}
+    want |= {"forecast flips", "forecast_gangs flips"}
+    assert want <= seen, sorted(want - seen)
+
+
+@pytest.mark.parametrize("name", list(ALL_LIVES))
+def test_the_mirror_equals_one_built_from_scratch(name, replayed):
+    life = replayed[name]
+    old = life.mirror
+    pod_name = {v: k for k, v in life.pl.pod.items()}
+    thr_name = {v: k for k, v in life.pl.thr.items()}
+    new = LE.Mirror(life.pl)
+    new.n_thr, new.n_pods = old.n_thr, old.n_pods
+    held = [t for t in range(old.n_thr) if old.tstate[t] >= 0]
+    new.put_throttles(held, [thr_name[int(old.tstate[t])] for t in held])
+    live = [r for r in range(old.n_pods) if old.state[r] >= 0]
+    new.put_pods(live, [pod_name[int(old.state[r])] for r in live])
+    for a, b in zip(old.snaps, new.snaps):  # the stored status and the reservations are the life's own: taken over as they are
+        for f in ("thr_used", "thr_calc", "thr_reserved", "thr_thrl_flag", "thr_thrl_has", "thr_status_msgs_fp"):
+            setattr(b, f, getattr(a, f))
+        b.thr_flags[:] |= a.thr_flags & np.uint32(LE.STATUS_BITS)
+        fa, fb = LE.load_fields(a), LE.load_fields(b)
+        assert fa.keys() == fb.keys()
+        for f in fa:
+            assert fa[f] == fb[f], f"{name}: field {f}"
+
+
+@pytest.mark.parametrize("case", LE.REFUSALS)
+def test_the_refused_batches_break_one_rule_each(case):
+    pl = LE.pool()
+    b, rows, code = LE.refused_pod_batch(pl, case)
+    base = pl.snaps[0]
+    d = pl.dim("cpu")[1]
+    neg = int(b.ctr_req[0, d])
+    assert neg < 0 and -neg > int(np.abs(base.ctr_req).max()) and neg & 1, "entry 0: negative, larger than any request, odd"
+    assert 0 <= rows[0] < LE.P_CAP and b.pod_ns[0] < base.n_ns and b.pod_label_off[1] <= base.L
+    broken = {"row-outside-capacity": rows[1] >= LE.P_CAP, "namespace-id-outside-capacity": b.pod_ns[1] >= base.n_ns + 1,
+              "more-labels-than-kept": int(b.pod_label_off[2]) - int(b.pod_label_off[1]) > max(base.L, 1),
+              "request-beyond-2^60": int(np.abs(b.ctr_req[1]).max()) > 1 << 60}
+    assert [k for k, v in broken.items() if v] == [case]
+    assert code == (-4 if case == "request-beyond-2^60" else -2)

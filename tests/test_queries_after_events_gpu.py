@@ -1,0 +1,220 @@
+"""The admission queries on an engine that has lived through events.
+
+Every other GPU file of the query family loads an engine with Engine.for_snapshot, asks once and closes it.  Here each test is one
+short life of tests/lived_engine.py: an engine created EMPTY with spare capacity, fed by events, reconciled, and after every further
+event held (``Life.hold``) to
+  * a twin loaded fresh from the mirror at that moment — every array of the whole battery bit for bit (which side moved?),
+  * the host models ``paging.*_of`` and the oracle on the mirror (who is right?),
+  * itself: a second run of the battery equals the first (queries are dry).
+The battery is check, dry admit, dry admit_gangs, headroom, headroom_gangs, preempt and preempt_gangs with and without reprieve,
+forecast, forecast_gangs, override_instants and fetch_reserved, for both ``on_equal`` values.  tests/test_lived_engine_cpu.py shows
+on the models alone that every event of every life moves an answer and that the lives show every kind of outcome.  No tolerance."""
+import numpy as np
+import pytest
+
+import lived_engine as LE
+from kube_throttler_amd import engine as E
+from kube_throttler_amd import snapshot as S
+
+pytestmark = pytest.mark.gpu
+NOW = LE.NOW
+
+
+def live(script, oracle_mod, wide=False):
+    life = LE.Life(oracle_mod, gpu=True, wide=wide)
+    try:
+        script(life)
+        return [name for name, _ in life.held]
+    finally:
+        life.close()
+
+
+def test_pod_events(oracle_mod):
+    assert len(live(LE.life_pod_events, oracle_mod)) == 8
+
+
+def test_threshold_and_override_events(oracle_mod):
+    """upload_spec_tables without a recompile: compiles() stays (asserted inside the life after every event), the stored status is
+    the old one until the last step's reconcile."""
+    assert len(live(LE.life_threshold_and_override_events, oracle_mod)) == 6
+
+
+def test_selector_and_row_events(oracle_mod):
+    """A recompile with device-newer status, a throttle row beyond thr_rows_hi, a freed and a reused row: compiles() rises by one
+    per event (asserted inside the life)."""
+    assert len(live(LE.life_selector_and_row_events, oracle_mod)) == 7
+
+
+def test_reservations_survive(oracle_mod):
+    """fetch_reserved is part of the battery: it equals the mirror at every step."""
+    assert len(live(LE.life_reservations_survive, oracle_mod)) == 6
+
+
+def test_two_pages_live(oracle_mod):
+    assert len(live(LE.life_two_pages, oracle_mod, wide=True)) == 7
+
+
+def _fingerprint(eng):
+    return eng.kernel_name(E.KERNEL_AGGREGATE), eng.packed_words()
+
+
+@pytest.mark.parametrize("case", LE.REFUSALS)
+def test_a_refused_batch_leaves_the_engine_as_it_was(case, oracle_mod):
+    """kt_upsert_pods refuses a batch whose SECOND pod breaks a rule; the first carries a negative request, larger than any the
+    engine holds, with new odd low bits.  Nothing of it may stay: not the "a negative request was fed" mark (headroom_gangs would
+    answer KT_ERR_UNSUPPORTED and the aggregate would leave the packed fold for good), not the bounds the pack plan is made from."""
+    life = LE.Life(oracle_mod, gpu=True)
+    try:
+        LE.start(life)
+        eng = life.eng
+        before = life.live_held[-1][1]
+        fold = _fingerprint(eng)
+        counters = eng.compiles(), eng.view_builds()
+        batch, rows, code = LE.refused_pod_batch(life.pl, case)
+        with pytest.raises(E.EngineError) as err:
+            eng.upsert_pods(batch, rows=rows)
+        assert err.value.code == code, err.value
+        assert (eng.compiles(), eng.view_builds()) == counters
+        after = life.hold(f"a refused batch: {case}")
+        LE.assert_same(before, after, "the battery before and after the refused batch")
+        for cap in LE.CAPS:
+            for eq in (False, True):
+                assert not isinstance(after["headroom_gangs", cap, eq][0], str), "headroom_gangs is still served"
+        life.reconcile()
+        assert _fingerprint(eng) == fold, "the aggregate's kernel and its packed fold after the next reconcile"
+        assert (eng.compiles(), eng.view_builds()) == counters
+        LE.assert_same(before, life.hold("... and a reconcile behind it"), "the battery behind the next reconcile")
+    finally:
+        life.close()
+
+
+@pytest.mark.parametrize("call", ["set_reserved", "set_status"])
+def test_a_refused_status_batch_leaves_the_engine_as_it_was(call, oracle_mod):
+    """kt_set_reserved / kt_set_status refuse an amount beyond 2^60 (kt_upsert_throttles validates its whole batch before it stores
+    a row; these two stored row by row): a good row in front of the refused one must not stay changed."""
+    life = LE.Life(oracle_mod, gpu=True)
+    try:
+        LE.start(life)
+        eng = life.eng
+        before = life.live_held[-1][1]
+        D = life.mirror.snap.D
+        rows = np.array([2, 5], np.int32)
+        bad = S.Amounts(2, D)
+        bad.set_row(0, {0: 7}, 1)
+        bad.set_row(1, {0: 1 << 61}, 1)
+        with pytest.raises(E.EngineError) as err:
+            if call == "set_reserved":
+                eng.set_reserved(rows, bad)
+            else:
+                eng.set_status(rows, bad, S.Amounts(2, D), [0, 0], [0, 0], [0, 0], [0, 0])
+        assert err.value.code == -4, err.value
+        LE.assert_same(before, life.hold(f"a refused {call}"), f"the battery before and after the refused {call}")
+        life.set_reserved(3, ["1jx-p"])  # the next accepted call uploads the host's tables: nothing of the refused batch is among them
+        life.hold("... and an accepted set_reserved of another row behind it")
+    finally:
+        life.close()
+
+
+def test_a_negative_request_that_came_and_went(oracle_mod):
+    """While the pod is there headroom_gangs is KT_ERR_UNSUPPORTED on the live engine and on the twin, everything else equals twin
+    and models.  Afterwards the live engine still refuses — kt_engine.h: "has been fed" — while the twin serves it, and every other
+    answer of the live engine equals the twin's although the twin folds packed and the live engine plain."""
+    life = LE.Life(oracle_mod, gpu=True)
+    try:
+        LE.life_negative_came_and_went(life)
+        with pytest.raises(E.EngineError) as err:
+            life.eng.headroom_gangs(life.q.gang_rows, life.q.gang_off, cap=LE.CAP)
+        assert err.value.code == -7 and "has been fed a negative request" in str(err.value), err.value
+        assert life.eng.packed_words() == 0, "the live engine folds plain"
+        tw = life.twin()[0]
+        try:
+            tw.reconcile(NOW, apply=False)
+            assert tw.packed_words() > 0, "the twin folds packed"
+        finally:
+            tw.close()
+    finally:
+        life.close()
+
+
+def _code(f):
+    try:
+        f()
+    except E.EngineError as err:
+        return err.code
+    return 0
+
+
+def test_pending_results_across_queries(oracle_mod):
+    """What kt_engine.h promises about results that are pending while another query is launched, on an engine that has had events:
+    a pending forecast and a pending preempt result are independent; a preempt's dry finalize drops a pending reconcile report; the
+    one headroom slot and the one preempt slot answer KT_ERR_NOT_READY to the other kind's fetch; a pending kt_check_launch is
+    dropped by every query that uses the check slot; result buffers regrow under an unfetched smaller launch."""
+    life = LE.Life(oracle_mod, gpu=True)
+    try:
+        LE.start(life)
+        life.upsert_pods([life.row("0jy-r")], ["0jx-r"])
+        want = life.hold("an upsert before the slots are looked at")
+        eng, q = life.eng, life.q
+        ng, n, m, k = len(q.gang_off) - 1, len(q.pods), len(q.cands), len(LE.INSTANTS)
+        same = lambda got, key: LE.same(LE._answer(lambda: got), want[key])
+        # a forecast launched and not yet fetched is still fetchable, and correct, behind a preempt launch — and the other way round
+        eng.forecast_launch(q.pods, LE.INSTANTS)
+        eng.preempt_launch(q.pods, q.cands, NOW)
+        assert same(eng.forecast_fetch(n, k), ("forecast", False)) and same(eng.preempt_fetch(n, m), ("preempt", False, False))
+        eng.preempt_launch(q.pods, q.cands, NOW)
+        eng.forecast_launch(q.pods, LE.INSTANTS)
+        assert same(eng.preempt_fetch(n, m), ("preempt", False, False)) and same(eng.forecast_fetch(n, k), ("forecast", False))
+        # a pending reconcile report is gone behind a preempt (its dry finalize wrote the result buffers)
+        eng.reconcile_launch(NOW, apply=False)
+        eng.preempt(q.pods, q.cands, NOW)
+        assert _code(lambda: eng.reconcile_fetch()) == -5
+        # one headroom slot, one preempt slot, one forecast slot: the other kind's fetch is not ready
+        eng.headroom_launch(n, q.pods, LE.CAP)
+        assert _code(lambda: eng.headroom_gangs_fetch(ng)) == -5
+        assert same(eng.headroom_fetch(n), ("headroom", LE.CAP, False))
+        eng.headroom_gangs_launch(q.gang_rows, q.gang_off, LE.CAP)
+        assert _code(lambda: eng.headroom_fetch(n)) == -5
+        assert same(eng.headroom_gangs_fetch(ng), ("headroom_gangs", LE.CAP, False))
+        eng.preempt_launch(q.pods, q.cands, NOW)
+        assert _code(lambda: eng.preempt_gangs_fetch(ng, m)) == -5
+        eng.preempt_gangs_launch(q.gang_rows, q.gang_off, q.cands, NOW)
+        assert _code(lambda: eng.preempt_fetch(n, m)) == -5
+        assert same(eng.preempt_gangs_fetch(ng, m), ("preempt_gangs", False, False))
+        eng.forecast_launch(q.pods, LE.INSTANTS)
+        assert _code(lambda: eng.forecast_gangs_fetch(ng, k)) == -5
+        eng.forecast_gangs_launch(q.gang_rows, q.gang_off, LE.INSTANTS)
+        assert _code(lambda: eng.forecast_fetch(n, k)) == -5
+        assert same(eng.forecast_gangs_fetch(ng, k), ("forecast_gangs", False))
+        # a pending kt_check_launch (with the status matrix: not the few-pod path) is gone behind every query that uses the slot
+        for ask in (lambda: eng.headroom(rows=q.pods, cap=LE.CAP), lambda: eng.headroom_gangs(q.gang_rows, q.gang_off, cap=LE.CAP),
+                    lambda: eng.preempt(q.pods, q.cands, NOW), lambda: eng.preempt_gangs(q.gang_rows, q.gang_off, q.cands, NOW),
+                    lambda: eng.forecast(q.pods, LE.INSTANTS), lambda: eng.forecast_gangs(q.gang_rows, q.gang_off, LE.INSTANTS)):
+            eng.check_launch(len(q.gang_rows), q.gang_rows, want_status=True)
+            ask()
+            assert _code(lambda: eng.check_fetch(len(q.gang_rows), want_status=True)) == -5
+        # ... and replaced behind an admission, whose results ARE read with kt_check_fetch
+        eng.check_launch(len(q.gang_rows), q.gang_rows, on_equal=True, want_status=True)
+        eng.admit(rows=q.gang_rows)
+        assert same(eng.check_fetch(len(q.gang_rows), want_status=True), ("admit", False))
+        # result buffers regrow under a smaller launch that was never fetched
+        eng.forecast_launch(q.pods[:1], LE.INSTANTS[:2])
+        eng.forecast_launch(q.pods, LE.INSTANTS)
+        assert same(eng.forecast_fetch(n, k), ("forecast", False))
+        eng.forecast_gangs_launch(q.members(0), [0, 1], LE.INSTANTS[:2])
+        eng.forecast_gangs_launch(q.gang_rows, q.gang_off, LE.INSTANTS)
+        assert same(eng.forecast_gangs_fetch(ng, k), ("forecast_gangs", False))
+        eng.preempt_launch(q.pods[:1], q.cands[:2], NOW)
+        eng.preempt_reprieve_launch(q.pods, q.cands, NOW)
+        assert same(eng.preempt_fetch(n, m), ("preempt", True, False))
+        eng.preempt_gangs_launch(q.members(0), [0, 1], q.cands[:2], NOW)
+        eng.preempt_gangs_reprieve_launch(q.gang_rows, q.gang_off, q.cands, NOW)
+        assert same(eng.preempt_gangs_fetch(ng, m), ("preempt_gangs", True, False))
+        eng.headroom_launch(1, q.pods[:1], LE.CAP)
+        eng.headroom_launch(n, q.pods, LE.CAP)
+        assert same(eng.headroom_fetch(n), ("headroom", LE.CAP, False))
+        eng.headroom_gangs_launch(q.members(0), [0, 1], LE.CAP)
+        eng.headroom_gangs_launch(q.gang_rows, q.gang_off, LE.CAP)
+        assert same(eng.headroom_gangs_fetch(ng), ("headroom_gangs", LE.CAP, False))
+        life.hold("behind all of it the battery is what it was")
+    finally:
+        life.close()
