@@ -90,6 +90,13 @@ const char* kt_last_error(kt_engine* e);
 /* ---- state feed: what the informer event handlers push (throttle_controller.go:400-536,
  *      clusterthrottle_controller.go:428-570).  A batch is a kt_snapshot whose sections may be empty
  *      (n_ns / n_pods / n_thr = 0).  rows == NULL means batch index i -> row i. ------------------------ */
+/* Namespaces: the object of each row (ns_valid[i] == 0: the row has no object, its pods answer Error) and its labels.  A batch may
+ * name a row more than once: the LAST entry wins.  kt_upsert_namespaces, kt_upsert_namespace and kt_delete_namespaces validate the
+ * whole batch before anything of it is kept: a refused batch (a row outside namespace_capacity: KT_ERR_OUT_OF_RANGE) leaves the
+ * engine as it was — every namespace it names, the compiled program and the views included; nothing is recompiled for it.
+ * An accepted namespace event is host work only: the next launch compiles the program again.  A result that is pending when the
+ * event arrives (kt_check_launch, kt_reconcile_launch, kt_forecast_launch and the other *_launch calls) is not touched by it: its
+ * fetch returns either the exact answer of the state at its launch or KT_ERR_NOT_READY, never anything else. */
 int32_t kt_upsert_namespaces(kt_engine* e, const kt_snapshot* batch, const int32_t* ns_rows);
 /* Pods: the effective request of each pod is computed ON DEVICE from the batch's containers —
  * resourcelist.PodRequestResourceList (pkg/resourcelist/resourcelist.go:27-46) + ResourceAmountOfPod
@@ -106,6 +113,8 @@ int32_t kt_upsert_namespaces(kt_engine* e, const kt_snapshot* batch, const int32
 int32_t kt_upsert_pods(kt_engine* e, const kt_snapshot* batch, const int64_t* pod_rows);
 /* Throttles: spec (threshold, overrides, selector), stored status and reserved amounts of each row. */
 int32_t kt_upsert_throttles(kt_engine* e, const kt_snapshot* batch, const int32_t* thr_rows);
+/* The rows lose their objects and labels, as by kt_upsert_namespaces with ns_valid == 0; the pods that name them stay.  The whole
+ * batch is validated first, see above. */
 int32_t kt_delete_namespaces(kt_engine* e, int32_t n, const int32_t* ns_rows);
 /* Pods leave by row.  A batch may name a row more than once, and rows that hold no pod (never fed, or deleted before — a Delete and
  * the DeletedFinalStateUnknown tombstone of one pod, a work queue drained into one call); both are no-ops beyond the first: the

@@ -25,10 +25,9 @@ int32_t kt_upsert_namespaces(kt_engine* e, const kt_snapshot* b, const int32_t* 
 int32_t kt_delete_namespaces(kt_engine* e, int32_t n, const int32_t* rows) {
   if (!e || (n > 0 && !rows)) return KT_ERR_INVALID_ARGUMENT;
   StateLock lk(e);
-  for (int32_t i = 0; i < n; ++i) {
+  for (int32_t i = 0; i < n; ++i)  // the whole batch first: a refused batch leaves the engine as it was
     if (rows[i] < 0 || rows[i] >= e->cfg.namespace_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "namespace row %d", rows[i]);
-    e->ns[(size_t)rows[i]] = HostNamespace();
-  }
+  for (int32_t i = 0; i < n; ++i) e->ns[(size_t)rows[i]] = HostNamespace();
   if (n > 0) e->program_dirty = true, ++e->ns_gen;
   return KT_OK;
 }

@@ -299,6 +299,7 @@ def lib():
         for name in ("kt_upsert_namespaces", "kt_upsert_pods", "kt_upsert_throttles"):
             getattr(L, name).argtypes = [C.c_void_p, C.POINTER(S.KtSnapshot), C.c_void_p]
         L.kt_delete_namespaces.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.kt_upsert_namespace.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.kt_delete_pods.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.kt_delete_throttles.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.kt_load_snapshot.argtypes = [C.c_void_p, C.POINTER(S.KtSnapshot)]
@@ -453,6 +454,12 @@ class Engine:
         st = batch.as_struct()
         a, p = self._rows(rows, np.int32)
         self._ck(lib().kt_upsert_namespaces(self._h, C.byref(st), p))
+
+    def upsert_namespace(self, row, exists, label_keys=(), label_pairs=()):
+        """kt_upsert_namespace: one Namespace event through the flat form (what the plugin mirror calls)."""
+        keys = np.ascontiguousarray(label_keys, dtype=np.uint32)
+        pairs = np.ascontiguousarray(label_pairs, dtype=np.uint32)
+        self._ck(lib().kt_upsert_namespace(self._h, int(row), 1 if exists else 0, len(keys), keys.ctypes.data, pairs.ctypes.data))
 
     def upsert_pods(self, batch: S.Snapshot, rows=None):
         st = batch.as_struct()

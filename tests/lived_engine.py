@@ -8,7 +8,8 @@ the opposite: one engine lives for days, is fed pod, Throttle and reservation ev
     window, another selector, another namespace) is a throttle kind of its own, so one label and scale dictionary serves all;
   * ``Mirror``: per page one Snapshot of what a freshly loaded engine would be loaded from, edited in place by every event
     (``state[row] -> pod kind`` and ``tstate[row] -> throttle kind``, -1 for a deleted row; the stored status and the reserved
-    amounts live in the snapshot's own arrays); ``n_thr`` and ``n_pods`` stay the highest row ever used + 1;
+    amounts live in the snapshot's own arrays); ``n_thr`` and ``n_pods`` stay the highest row ever used + 1; the namespace side is
+    ``nstate[row] -> namespace kind`` ("gone": no object) with ``ns_valid`` / ``ns_label_*`` arrays of the mirror's own;
   * ``battery``: everything the query family answers for one fixed question set, for both ``on_equal`` values;
   * ``model_battery``: the same dictionary from the host models (``paging.*_of``) and the oracle, on the mirror alone;
   * ``Life``: the events, applied to the mirror and — when it has engines — to the live engine(s), and ``hold()``: live against a twin
@@ -37,6 +38,8 @@ CAPS = (CAP, E.HEADROOM_MAX_CAP)
 P_CAP, T_CAP = 64, 24  # capacities of the live engine: above what the cluster starts with
 STATUS_BITS = S.THR_CALC_AT_NONZERO | S.THR_THROTTLED_POD
 NS = ("ns0", "ns1", "ns2")
+GHOST, SPARE = 3, 4  # namespace rows: the one without an object ("ghost"), and the row the live engine keeps spare
+NS_CAP = SPARE + 1   # namespace capacity of the live engine
 APPS = {"j": "job", "w": "web", "d": "db"}
 EXTRA = [f"example.com/r{k:02d}" for k in range(17)]  # wide=True: 3 + 17 names, two pages
 
@@ -158,6 +161,26 @@ class Pool:
             if "cpu" in dims:  # the one pod with a negative request
                 k = int(s.pod_ctr_off[self.pod["neg"]])
                 s.ctr_req[k, dims["cpu"]] = -s.ctr_req[k, dims["cpu"]]
+        # namespace kinds, per page: the label list the pool gives each row, and the ids of env=prod / env=dev
+        self.ns_lists, self.env = [], []
+        for s in self.snaps:
+            assert s.n_ns == GHOST + 1 and list(s.ns_valid[:s.n_ns]) == [1, 1, 1, 0]
+            lists = {name: [(int(s.ns_label_key[i]), int(s.ns_label_pair[i])) for i in range(int(s.ns_label_off[r]), int(s.ns_label_off[r + 1]))]
+                     for r, name in enumerate(NS)}
+            (key, prod), = set(lists["ns0"]) & set(lists["ns1"])            # the one pair the two prod namespaces share
+            (dev,) = [p for k, p in lists["ns2"] if k == key]
+            assert dev != prod
+            self.ns_lists.append(lists)
+            self.env.append((key, {"prod": prod, "dev": dev}))
+
+    def ns_kind(self, kind, page=0):
+        """A namespace KIND -> (valid, [(key id, pair id)]): "gone" (no object), "ns1" (the labels the pool gives that row),
+        "ns2@prod" / "ns0@dev" (... with the env pair swapped: the pool's dictionary has both ids)."""
+        if kind == "gone":
+            return 0, []
+        name, _, env = kind.partition("@")
+        key, pairs = self.env[page]
+        return 1, [(k, pairs[env] if env and k == key else p) for k, p in self.ns_lists[page][name]]
 
     # the pods the cluster starts with: row r holds PLACEMENT[r]
     @property
@@ -206,6 +229,7 @@ class Questions:
 # ---- the mirror ------------------------------------------------------------------------------------------------------------
 THR_SPEC_FIELDS = ("thr_ns", "thr_spec", "thr_spec_msgs_fp", "thr_ovr_off", "ovr_begin_s", "ovr_begin_ns", "ovr_end_s", "ovr_end_ns",
                    "ovr_flags", "ovr_thr", "thr_term_off", "term_flags", "term_preq_off", "term_nreq_off", "preq", "nreq")
+NS_FIELDS = ("ns_valid", "ns_label_off", "ns_label_key", "ns_label_pair")
 POD_FIELDS = ("n_pods", "pod_ns", "pod_flags", "pod_label_off", "pod_label_key", "pod_label_pair", "pod_ctr_off", "ctr_init",
               "ctr_present", "ctr_req", "pod_ovh_present", "pod_ovh")
 
@@ -228,26 +252,81 @@ class Mirror:
             m.thr_thrl_flag, m.thr_thrl_has = np.zeros(self.T, np.uint32), np.zeros(self.T, np.uint32)
             m.thr_status_msgs_fp = np.zeros(self.T, np.uint64)
             self.snaps.append(m)
+        # the namespace side: ``nstate[row] -> namespace kind``; every page gets arrays of its own (the pool's are shared)
+        self.nstate = list(NS) + ["gone"]
+        self.pod_ns = {}  # pod row -> namespace row, where a pod was fed into another namespace than its kind's
+        self._refresh_namespaces()
+        for m, base in zip(self.snaps, pl.snaps):
+            for f in NS_FIELDS:
+                assert np.array_equal(getattr(m, f), getattr(base, f)[:len(getattr(m, f))]), f"the mirror starts as the pool: {f}"
 
     @property
     def snap(self):
         return self.snaps[0]
 
-    # -- pods
-    def put_pods(self, rows, kinds):
+    # -- namespaces
+    def put_namespaces(self, rows, kinds):
         for r, k in zip(rows, kinds):  # (a row named twice: the last wins)
+            self._grow_namespaces(int(r) + 1)
+            self.nstate[int(r)] = k
+        self._refresh_namespaces()
+
+    def drop_namespaces(self, rows):
+        self.put_namespaces(rows, ["gone"] * len(rows))
+
+    def _grow_namespaces(self, n):
+        self.nstate += ["gone"] * (n - len(self.nstate))
+
+    def namespace_batch(self, kinds, page=0):
+        """A namespaces-only batch of these kinds, in this order (for kt_upsert_namespaces)."""
+        base = self.pl.snaps[page]
+        b = S.Snapshot(base.D, base.L)
+        lists = [self.pl.ns_kind(k, page) for k in kinds]
+        b.alloc_namespaces(len(kinds), sum(len(l) for _, l in lists))
+        b.alloc_pods(0, 0, 0)
+        b.alloc_throttles(0, 0, 0)
+        n = 0
+        for i, (valid, labels) in enumerate(lists):
+            b.ns_valid[i] = valid
+            for key, pair in labels:
+                b.ns_label_key[n], b.ns_label_pair[n] = key, pair
+                n += 1
+            b.ns_label_off[i + 1] = n
+        return b
+
+    def _refresh_namespaces(self):
+        for k, m in enumerate(self.snaps):
+            b = self.namespace_batch(self.nstate, k)
+            m.n_ns = b.n_ns
+            for f in NS_FIELDS:
+                setattr(m, f, getattr(b, f))
+            m._keep = None
+
+    # -- pods
+    def put_pods(self, rows, kinds, ns=None):
+        """``ns``: the namespace row each pod is fed with (None: its kind's own)."""
+        for i, (r, k) in enumerate(zip(rows, kinds)):  # (a row named twice: the last wins)
             self.state[int(r)] = self.pl.pod[k] if isinstance(k, str) else int(k)
             self.n_pods = max(self.n_pods, int(r) + 1)
+            self.pod_ns.pop(int(r), None)
+            if ns is not None and ns[i] is not None:
+                self.pod_ns[int(r)] = int(ns[i])
+                if int(ns[i]) >= len(self.nstate):  # a pod in front of its Namespace object: the row exists, without an object
+                    self._grow_namespaces(int(ns[i]) + 1)
+                    self._refresh_namespaces()
         self._refresh_pods()
 
     def drop_pods(self, rows):
         for r in rows:
             self.state[int(r)] = -1
+            self.pod_ns.pop(int(r), None)
         self._refresh_pods()
 
     def _refresh_pods(self):
         for m, base in zip(self.snaps, self.pl.snaps):
             w = _with_pods(base, self.state[:self.n_pods])
+            for r, ns in self.pod_ns.items():
+                w.pod_ns[r] = ns
             for f in POD_FIELDS:
                 setattr(m, f, getattr(w, f))
 
@@ -335,7 +414,8 @@ def load_fields(snap):
     n, T = snap.n_pods, snap.n_thr
     nl, nc = int(snap.pod_label_off[n]), int(snap.pod_ctr_off[n])
     no, nt = int(snap.thr_ovr_off[T]), int(snap.thr_term_off[T])
-    cut = {"pod_ns": n, "pod_flags": n, "pod_label_off": n + 1, "pod_label_key": nl, "pod_label_pair": nl, "pod_ctr_off": n + 1,
+    nn = int(snap.ns_label_off[snap.n_ns])
+    cut = {"ns_label_key": nn, "ns_label_pair": nn,"pod_ns": n, "pod_flags": n, "pod_label_off": n + 1, "pod_label_key": nl, "pod_label_pair": nl, "pod_ctr_off": n + 1,
            "ctr_init": nc, "ctr_present": nc, "ctr_req": nc, "pod_ovh_present": n, "pod_ovh": n, "thr_flags": T, "thr_ns": T,
            "thr_thrl_flag": T, "thr_thrl_has": T, "thr_status_msgs_fp": T, "thr_spec_msgs_fp": T, "thr_ovr_off": T + 1,
            "ovr_begin_s": no, "ovr_begin_ns": no, "ovr_end_s": no, "ovr_end_ns": no, "ovr_flags": no, "thr_term_off": T + 1,
@@ -571,13 +651,39 @@ class Life:
     def row(self, name):
         return self.q.row[name]
 
+    def compiles(self):
+        return [e.compiles() for e in self.engines]
+
     # -- events
-    def upsert_pods(self, rows, kinds):
+    def upsert_namespaces(self, rows, kinds):
+        """kt_upsert_namespaces with ``rows=``: the batch holds the kinds in the order given (a row named twice included)."""
+        for k, e in enumerate(self.engines):
+            e.upsert_namespaces(self.mirror.namespace_batch(kinds, k), rows=np.asarray(rows, np.int32))
+        self.mirror.put_namespaces(rows, kinds)
+
+    def delete_namespaces(self, rows):
+        for e in self.engines:
+            e.delete_namespaces(np.asarray(rows, np.int32))
+        self.mirror.drop_namespaces(rows)
+
+    def upsert_namespace_flat(self, row, kind):
+        """kt_upsert_namespace(row, exists, ...): the call the plugin mirror uses."""
+        for k, e in enumerate(self.engines):
+            valid, labels = self.pl.ns_kind(kind, k)
+            e.upsert_namespace(row, valid, [key for key, _ in labels], [pair for _, pair in labels])
+        self.mirror.put_namespaces([row], [kind])
+
+    def upsert_pods(self, rows, kinds, ns=None):
+        """``ns``: the namespace rows the pods are fed with (None: their kinds' own)."""
         rows = np.asarray(rows, np.int64)
         src = np.array([self.pl.pod[k] for k in kinds], np.int64)
         for e, base in zip(self.engines, self.pl.snaps):
-            e.upsert_pods(_permute_pods(base, src), rows=rows)
-        self.mirror.put_pods(rows, kinds)
+            b = _permute_pods(base, src)
+            for i, x in enumerate(ns or ()):
+                if x is not None:
+                    b.pod_ns[i] = x
+            e.upsert_pods(b, rows=rows)
+        self.mirror.put_pods(rows, kinds, ns)
 
     def delete_pods(self, rows):
         for e in self.engines:
@@ -829,9 +935,124 @@ def life_two_pages(life):
     life.hold("a reconcile behind them")
 
 
+class _Gaps:
+    """compiles() of every page's engine from one hold to the next: a gap that holds namespace events (or a pod of a namespace row
+    the program was not compiled for) costs exactly ONE compile, however many events it holds; a gap without events costs none."""
+
+    def __init__(self, life):
+        self.life = life
+        self.at = life.compiles()
+
+    def hold(self, name, compiled, **kw):
+        out = self.life.hold(name, **kw)
+        now = self.life.compiles()
+        want = [c + (1 if compiled else 0) for c in self.at]
+        assert now == want, f"{name}: compiles() {now}, {self.at} at the step before"
+        self.at = now
+        return out
+
+
+def _assert_battery_is(life, step, then):
+    """The battery held last equals the one held at step number ``then``, byte for byte: models, and the live engine where there is one."""
+    assert_same(life.held[-1][1], life.held[then][1], f"{step}: the models' battery against the one of '{life.held[then][0]}'")
+    if life.engines:
+        assert_same(life.live_held[-1][1], life.live_held[then][1], f"{step}: the live battery against the one of '{life.held[then][0]}'")
+
+
+def life_namespace_labels(life):
+    start(life)
+    g = _Gaps(life)
+    life.upsert_namespaces([2], ["ns2@prod"])               # the ClusterThrottles now reach the pods of ns2
+    g.hold("ns2 becomes prod", True)
+    life.reconcile()
+    g.hold("... and has been reconciled", False)
+    life.upsert_namespaces([0], ["ns0@dev"])
+    g.hold("ns0 becomes dev", True)
+    life.reconcile()
+    g.hold("... and has been reconciled too", False)
+    life.upsert_namespaces([2, 0], ["ns2", "ns0"])          # one batch, two rows
+    life.reconcile()
+    g.hold("both changes are undone in one batch, and a reconcile behind it", True)
+    _assert_battery_is(life, "labels and status are those of the start", 0)
+    life.upsert_namespaces([1, 2, 1], ["ns1@dev", "ns2@prod", "ns1"])  # one batch names a row twice: the last wins, ns1 stays prod
+    g.hold("one batch names a row twice", True)
+    _assert_battery_is(life, "ns1 named twice, as it was: what ns2 -> prod alone gave", 1)
+
+
+def life_namespace_deleted_and_back(life):
+    start(life)
+    g = _Gaps(life)
+    life.delete_namespaces([1])                             # its pods, gang members and candidates: Error among the answers
+    g.hold("delete_namespaces takes the object of ns1", True)
+    life.upsert_namespaces([1], ["ns1"])
+    g.hold("the object returns with its old labels", True)
+    _assert_battery_is(life, "ns1 is back", 0)
+    life.upsert_namespaces([1], ["gone"])                   # the same state, reached by ns_valid = 0 ...
+    g.hold("upsert_namespaces with ns_valid = 0", True)
+    _assert_battery_is(life, "ns_valid = 0", 1)
+    life.upsert_namespace_flat(1, "ns1")
+    g.hold("the object returns through the flat form", True)
+    _assert_battery_is(life, "ns1 is back again", 0)
+    life.upsert_namespace_flat(1, "gone")                   # ... and by the flat form with exists = 0
+    g.hold("the flat form with exists = 0", True)
+    _assert_battery_is(life, "exists = 0", 1)
+    life.reconcile()
+    g.hold("a reconcile while the object is gone", False)
+    life.upsert_namespaces([1], ["ns1@dev"])
+    g.hold("the object returns with other labels", True)  # (a reconcile behind it moves nothing: no ClusterThrottle counts ns1 either way)
+
+
+def life_namespace_arrives_after_its_pods(life):
+    r = life.row
+    start(life)
+    g = _Gaps(life)
+    life.upsert_namespaces([GHOST], ["ns0"])                # ghost-p and the gang that held an Error member are judged now
+    g.hold("the namespace without an object gets one", True)
+    life.upsert_pods([r("0jy-r")], ["0jy-r"], ns=[GHOST])   # (the only pod there was pending: a reconcile alone would move nothing)
+    g.hold("a running candidate moves there", False)
+    life.reconcile()
+    g.hold("... and has been reconciled", False)
+    life.upsert_pods([r("1jy-p")], ["1jy-p"], ns=[SPARE])   # beyond ns_rows_hi and beyond what the program was compiled for
+    g.hold("a pod arrives in a namespace row nobody has named yet", True)
+    life.upsert_namespaces([SPARE], ["ns1"])
+    g.hold("... and its Namespace object afterwards", True)
+
+
+def life_namespace_events_among_the_others(life):
+    t = {name: i for i, name in enumerate(life.pl.initial)}
+    r = life.row
+    start(life)
+    g = _Gaps(life)
+    life.reconcile()
+    life.upsert_namespaces([2], ["ns2@prod"])               # right after reconcile(apply): the device's status is newer
+    g.hold("a namespace event right after reconcile(apply)", True)
+    life.reconcile()
+    life.admit_commit([r("0dx-p"), r("1wx-p"), r("none"), r("1jy-p"), r("two")])
+    life.admit_gangs_commit(life.q)
+    life.upsert_namespaces([2], ["ns2"])                    # the reserved rows the device advanced go to the host and back
+    g.hold("a namespace event behind admit(commit=True) and admit_gangs(commit=True)", True)
+    life.upsert_namespaces([1], ["ns1@dev"])
+    life.upsert_pods([r("1jx-r")], ["1jy-r"])
+    g.hold("a namespace event, then a pod event of that namespace", True)
+    life.upsert_pods([r("1jx-r")], ["1jx-r"])
+    life.upsert_namespaces([1], ["ns1"])
+    g.hold("a pod event, then a namespace event of its namespace", True)
+    life.upsert_namespaces([0], ["ns0@dev"])
+    life.upsert_throttles([t["ns1/t-job"]], ["ns1/t-job@tight"])
+    g.hold("a namespace event, then a threshold-only throttle event", True)
+    life.reconcile()
+    g.hold("... and a reconcile behind them", False)
+
+
 LIVES = {"pod_events": life_pod_events, "threshold_and_override_events": life_threshold_and_override_events,
          "selector_and_row_events": life_selector_and_row_events, "reservations_survive": life_reservations_survive,
-         "negative_came_and_went": life_negative_came_and_went}
+         "negative_came_and_went": life_negative_came_and_went, "namespace_labels": life_namespace_labels,
+         "namespace_deleted_and_back": life_namespace_deleted_and_back,
+         "namespace_arrives_after_its_pods": life_namespace_arrives_after_its_pods,
+         "namespace_events_among_the_others": life_namespace_events_among_the_others}
+# the lives of a cluster with twenty resource names: two pages, every event reaches both
+WIDE_LIVES = {"two_pages": life_two_pages, "namespace_labels_wide": life_namespace_labels,
+              "namespace_deleted_and_back_wide": life_namespace_deleted_and_back}
 
 
 # ---- refused batches -------------------------------------------------------------------------------------------------------

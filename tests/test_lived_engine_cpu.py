@@ -16,14 +16,14 @@ import forecast_reference as FR
 import lived_engine as LE
 from kube_throttler_amd import snapshot as S
 
-ALL_LIVES = dict(LE.LIVES, two_pages=LE.life_two_pages)
+ALL_LIVES = dict(LE.LIVES, **LE.WIDE_LIVES)
 
 
 @pytest.fixture(scope="module")
 def replayed(oracle_mod):
     out = {}
     for name, script in ALL_LIVES.items():
-        life = LE.Life(oracle_mod, gpu=False, wide=name == "two_pages")
+        life = LE.Life(oracle_mod, gpu=False, wide=name in LE.WIDE_LIVES)
         script(life)
         out[name] = life
     return out
@@ -37,6 +37,33 @@ def test_every_event_moves_an_answer(name, replayed):
         moved = LE.differences(a, b)
         print(f"{name}: {step}: {len(moved)} answers moved, e.g. {moved[:4]}")
         assert moved, f"{name}: '{step}' changes no model answer against '{before}'"
+
+
+def test_namespace_events_move_most_of_the_battery(replayed):
+    """A namespace event is no corner of the battery: of its 28 entries the ns2 -> prod swap moves 20, the ns1 delete 26 (all but
+    override_instants and the reserved rows) and the object's return moves them all back; the ghost's object moves 18."""
+    def moved(name, a, b):
+        held = replayed[name].held
+        assert len(held[a][1]) == 28
+        return len(LE.differences(held[a][1], held[b][1]))
+
+    assert replayed["namespace_labels"].held[1][0] == "ns2 becomes prod"
+    assert moved("namespace_labels", 0, 1) == 20
+    assert replayed["namespace_deleted_and_back"].held[1][0] == "delete_namespaces takes the object of ns1"
+    assert moved("namespace_deleted_and_back", 0, 1) == 26
+    assert moved("namespace_deleted_and_back", 0, 2) == 0
+    assert replayed["namespace_arrives_after_its_pods"].held[1][0] == "the namespace without an object gets one"
+    assert moved("namespace_arrives_after_its_pods", 0, 1) == 18
+
+
+def test_a_deleted_namespace_answers_error(replayed):
+    """The pods of ns1 among the single pods and the gang members answer Error while its object is gone, by the models."""
+    life = replayed["namespace_deleted_and_back"]
+    b = dict(life.held)["delete_namespaces takes the object of ns1"]
+    ns1 = [i for i, p in enumerate(life.q.pods) if life.pl.placement[p].startswith("1") or life.pl.placement[p] == "zero"]
+    assert len(ns1) >= 3
+    for eq in (False, True):
+        assert ((b["check", eq][1][ns1] & np.uint64(3)) == S.VERDICT_ERROR).all()
 
 
 def test_a_headroom_answer_changes_its_limiting_throttle(replayed):
@@ -117,8 +144,9 @@ def test_the_mirror_equals_one_built_from_scratch(name, replayed):
     new.n_thr, new.n_pods = old.n_thr, old.n_pods
     held = [t for t in range(old.n_thr) if old.tstate[t] >= 0]
     new.put_throttles(held, [thr_name[int(old.tstate[t])] for t in held])
+    new.put_namespaces(range(len(old.nstate)), old.nstate)
     live = [r for r in range(old.n_pods) if old.state[r] >= 0]
-    new.put_pods(live, [pod_name[int(old.state[r])] for r in live])
+    new.put_pods(live, [pod_name[int(old.state[r])] for r in live], [old.pod_ns.get(r) for r in live])
     for a, b in zip(old.snaps, new.snaps):  # the stored status and the reservations are the life's own: taken over as they are
         for f in ("thr_used", "thr_calc", "thr_reserved", "thr_thrl_flag", "thr_thrl_has", "thr_status_msgs_fp"):
             setattr(b, f, getattr(a, f))

@@ -182,12 +182,16 @@ def run_rule(x, lo, hi):
     return x & ~(((x | hi) - lo) & m) & m
 
 
-def assert_records(e, st_w, live, ns_of, expect_overflow=(), rows=None):
+def assert_records(e, st_w, live, ns_of, expect_overflow=(), rows=None, no_object=()):
     """The records of engine e against its planes and the oracle's status matrix st_w[row, throttle] (live[row]: the row holds a
     pod; ns_of[row]: its namespace row; rows: the rows to look at, default all).  The words a record decodes to are EXACTLY the
     planes' words after the run rule (Engine.match_runs: the word and the run masks of a plane for a namespace).  Rows without a
     pod are gated by the pod's state, as the planes': their records are not looked at.  And the view table is the row table
-    through `rows`: every record of the countable scan view is the record of the pod row it lists."""
+    through `rows`: every record of the countable scan view is the record of the pod row it lists.
+    no_object: namespace rows whose Namespace object is gone while Throttles of their own stay.  Their pods answer Error for
+    every throttle (the matrix row is all 255 and names no throttle), but the table still lists the terms of those Throttles their
+    labels match — the verdict is gated by the namespace, not by the table.  For them the header is held to the planes instead:
+    the number of bits the run rule leaves."""
     runs = {}
     rec, none = e.match_codes()
     assert none is None
@@ -198,6 +202,16 @@ def assert_records(e, st_w, live, ns_of, expect_overflow=(), rows=None):
     hdr, words, asc = decode(rec[:n], look)
     affected = ((st_w != 0) & (st_w != 255)).sum(axis=1)
     for r in look:
+        if int(ns_of[r]) in no_object:
+            assert (st_w[r] == 255).all(), f"row {r}: its namespace has no object, the oracle does not answer Error"
+            bits = 0
+            for k in range(mw.shape[0]):
+                key = (int(ns_of[r]), k)
+                if key not in runs:
+                    runs[key] = e.match_runs(*key)
+                w, lo, hi = runs[key]
+                bits += bin(run_rule(int(mw[k, r]), lo, hi)).count("1") if w >= 0 else 0
+            affected[r] = bits
         if affected[r] > 15:
             assert hdr[r] == 0xFF, f"row {r}: {affected[r]} throttles affect the pod, header {hdr[r]}"
             continue

@@ -1,8 +1,8 @@
 """The admission queries on an engine that has lived through events.
 
 Every other GPU file of the query family loads an engine with Engine.for_snapshot, asks once and closes it.  Here each test is one
-short life of tests/lived_engine.py: an engine created EMPTY with spare capacity, fed by events, reconciled, and after every further
-event held (``Life.hold``) to
+short life of tests/lived_engine.py: an engine created EMPTY with spare capacity, fed by events (pods, throttles, reservations,
+stored status, Namespace objects), reconciled, and after every further event held (``Life.hold``) to
   * a twin loaded fresh from the mirror at that moment — every array of the whole battery bit for bit (which side moved?),
   * the host models ``paging.*_of`` and the oracle on the mirror (who is right?),
   * itself: a second run of the battery equals the first (queries are dry).
@@ -52,6 +52,36 @@ def test_reservations_survive(oracle_mod):
 
 def test_two_pages_live(oracle_mod):
     assert len(live(LE.life_two_pages, oracle_mod, wide=True)) == 7
+
+
+def test_namespace_labels(oracle_mod):
+    """Label swaps of Namespace objects reach the ClusterThrottles' namespaceSelector: one compile per gap with events, none in a
+    gap without (asserted inside the life), a batch of two rows, a batch that names a row twice."""
+    assert len(live(LE.life_namespace_labels, oracle_mod)) == 7
+
+
+def test_namespace_deleted_and_back(oracle_mod):
+    """kt_delete_namespaces, kt_upsert_namespaces with ns_valid = 0 and kt_upsert_namespace with exists = 0 reach the same state;
+    the object's return gives the battery of the start back byte for byte (asserted inside the life)."""
+    assert len(live(LE.life_namespace_deleted_and_back, oracle_mod)) == 8
+
+
+def test_namespace_arrives_after_its_pods(oracle_mod):
+    """An object for the row that had none, and a pod in a namespace row beyond what the program was compiled for."""
+    assert len(live(LE.life_namespace_arrives_after_its_pods, oracle_mod)) == 6
+
+
+def test_namespace_events_among_the_others(oracle_mod):
+    """Behind reconcile(apply) (device-newer status), behind committed admissions (fetch_reserved is in the battery), beside pod
+    events of the same namespace in both orders, in front of a threshold-only throttle event."""
+    assert len(live(LE.life_namespace_events_among_the_others, oracle_mod)) == 7
+
+
+@pytest.mark.parametrize("script,steps", [(LE.life_namespace_labels, 7), (LE.life_namespace_deleted_and_back, 8)],
+                         ids=["labels", "deleted_and_back"])
+def test_namespace_events_on_two_pages(script, steps, oracle_mod):
+    """Every event reaches both pages' engines; paged_reconcile and the paged battery follow."""
+    assert len(live(script, oracle_mod, wide=True)) == steps
 
 
 def _fingerprint(eng):
@@ -115,6 +145,36 @@ def test_a_refused_status_batch_leaves_the_engine_as_it_was(call, oracle_mod):
         life.close()
 
 
+@pytest.mark.parametrize("call", ["delete_namespaces", "upsert_namespaces"])
+def test_a_refused_namespace_batch_leaves_the_engine_as_it_was(call, oracle_mod):
+    """The batch is [ns1, which holds counted pods; a row outside the capacity].  The refused call compiles nothing, so the battery
+    cannot show what it left on the host: the decisive step is the recompile an UNRELATED selector-changing throttle event forces
+    afterwards.  (kt_delete_namespaces stored row by row while it validated: the live engine lost ns1 there.)"""
+    life = LE.Life(oracle_mod, gpu=True)
+    try:
+        LE.start(life)
+        eng = life.eng
+        before = life.live_held[-1][1]
+        counters = eng.compiles(), eng.view_builds()
+        rows = np.array([1, LE.NS_CAP], np.int32)
+        with pytest.raises(E.EngineError) as err:
+            if call == "delete_namespaces":
+                eng.delete_namespaces(rows)
+            else:  # (the good entry carries labels that would change answers: no ClusterThrottle admits env=dev)
+                eng.upsert_namespaces(life.mirror.namespace_batch(["ns1@dev", "ns0"]), rows=rows)
+        assert err.value.code == -2, err.value
+        assert (eng.compiles(), eng.view_builds()) == counters
+        after = life.hold(f"a refused {call}")
+        LE.assert_same(before, after, f"the battery before and after the refused {call}")
+        assert (eng.compiles(), eng.view_builds()) == counters
+        t = life.pl.initial.index("ns2/t-web")
+        life.upsert_throttles([t], ["ns2/t-web@db"])
+        life.hold("... and an unrelated selector-changing throttle event behind it: the program is compiled from the host's state")
+        assert eng.compiles() == counters[0] + 1
+    finally:
+        life.close()
+
+
 def test_a_negative_request_that_came_and_went(oracle_mod):
     """While the pod is there headroom_gangs is KT_ERR_UNSUPPORTED on the live engine and on the twin, everything else equals twin
     and models.  Afterwards the live engine still refuses — kt_engine.h: "has been fed" — while the twin serves it, and every other
@@ -142,6 +202,58 @@ def _code(f):
     except E.EngineError as err:
         return err.code
     return 0
+
+
+def test_pending_results_across_a_namespace_event(oracle_mod):
+    """kt_engine.h: a result that is pending when a namespace event arrives is not touched by it — "its fetch returns either the
+    exact answer of the state at its launch or KT_ERR_NOT_READY, never anything else".  A check, a reconcile report and a forecast
+    are each launched in front of a namespace event that moves their answer, and fetched behind it."""
+    life = LE.Life(oracle_mod, gpu=True)
+    try:
+        LE.start(life)
+        eng, q = life.eng, life.q
+        at_start = life.live_held[-1][1]
+        n, k = len(q.pods), len(LE.INSTANTS)
+        outcome = {}
+
+        def fetched(what, fetch, is_exact):
+            try:
+                got = fetch()
+            except E.EngineError as err:
+                assert err.code == -5, f"{what}: {err}"
+                outcome[what] = "KT_ERR_NOT_READY"
+                return
+            assert is_exact(got), f"{what}: neither the answer of the state at launch nor KT_ERR_NOT_READY: {got}"
+            outcome[what] = "the answer of the state at launch"
+
+        eng.check_launch(n, q.pods, want_status=True)
+        life.upsert_namespaces([1], ["ns1@dev"])
+        fetched("check", lambda: eng.check_fetch(n, want_status=True), lambda got: LE.same(LE._answer(lambda: got), at_start["check", False]))
+        moved = life.hold("ns1 becomes dev behind a pending check")
+        assert LE.differences(moved, at_start, [("check", False)]), "the event moves the check's answer"
+
+        rows = LE.responsible(life.mirror.snap)
+        want = oracle_mod.Oracle(life.mirror.snap).reconcile(NOW, rows=rows)  # the report of the state at launch: ns1 is dev
+        eng.reconcile_launch(NOW, apply=False)
+        life.upsert_namespaces([1], ["ns1"])
+        after = oracle_mod.Oracle(life.mirror.snap).reconcile(NOW, rows=rows)
+        assert not np.array_equal(want.used.count, after.used.count), "the event moves the report"
+
+        def report_is_exact(got):
+            LE.assert_reconcile_equal(LE._rows_of(got, rows, life.mirror.snap.D), want, len(rows))
+            return True
+
+        fetched("reconcile report", eng.reconcile_fetch, report_is_exact)
+        LE.assert_same(at_start, life.hold("ns1 is prod again behind a pending reconcile report"), "the battery of the start")
+
+        eng.forecast_launch(q.pods, LE.INSTANTS)
+        life.delete_namespaces([1])
+        fetched("forecast", lambda: eng.forecast_fetch(n, k), lambda got: LE.same(LE._answer(lambda: got), at_start["forecast", False]))
+        gone = life.hold("ns1 is deleted behind a pending forecast")
+        assert LE.differences(gone, at_start, [("forecast", False)])
+        print("pending across a namespace event:", outcome)
+    finally:
+        life.close()
 
 
 def test_pending_results_across_queries(oracle_mod):
