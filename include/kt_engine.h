@@ -757,6 +757,38 @@ int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n
  * kt_headroom_launch.  Uses page 0's check slot.  out_copies [n] and out_limiting [n] are both nullable. */
 int32_t kt_paged_headroom(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal,
                           int64_t cap, int64_t* out_copies, int32_t* out_limiting);
+/* kt_headroom_gangs_launch over the pages, synchronous (n_pages == 1 returns byte for byte what kt_headroom_gangs_launch +
+ * kt_headroom_gangs_fetch return): out_copies[g] = the number of LEADING admitted gangs of a dry kt_paged_admit_gangs over `cap`
+ * consecutive copies of gang g, against every page's stored status and current reserved amounts.  out_blocker[g] and
+ * out_limiting[g] are kt_headroom_gangs_launch's, read off the COMBINED row the paged admission returns to that member at its
+ * turn: the queue position of the first member of the first copy that is not admitted whose combined verdict is not Success, and
+ * the lowest throttle row whose combined status is not KT_STATUS_NOT_THROTTLED there; the -1 rules, the Error / invalid-member
+ * rule and the rule for a gang no throttle affects are the single-engine ones.  What pages add to the definition:
+ *   - an admitted copy reserves on every page, each page its own names' values and the presence of all the names the member
+ *     carries on that page; the pod count is judged once, on page 0;
+ *   - each page reads the threshold kt_admit reads on that page (that page's stored calculatedAt flag).  Nothing is reconciled:
+ *     the call is held to paged admission, not to the preemption family's "replaced as a whole" rule;
+ *   - copy j passes on throttle t iff the in-order member walk passes on every page, each against its own reserved row plus
+ *     j x (what one admitted copy reserves there): the answer is the lexicographic minimum over all (throttle, page) pairs of
+ *     (copies, first stopped member, throttle row).  Where every page carries the same count part it equals the minimum over
+ *     the pages' own kt_headroom_gangs answers of (copies, blocker or the gang size if -1, limiting or +inf if -1), mapped back
+ *     to (cap, -1, -1) at the cap; a gang of one pod equals kt_paged_headroom in copies and limiting.
+ * One kt_check of page 0 with the status matrix over the members of all gangs and ONE kernel (kt_headroom_gangs_paged: one wave
+ * per gang, lane = a candidate number of copies, the running minimum cuts the search over pages as well as over throttles) on
+ * page 0's stream.  Refused, before anything is launched and before a check slot or pending result of any page is touched:
+ * what kt_headroom_gangs_launch refuses about its arguments (pod_rows missing, every gang_off defect, a pod twice within ONE
+ * gang, cap outside [1, KT_HEADROOM_MAX_CAP]: KT_ERR_INVALID_ARGUMENT; a pod row outside a page's capacity, n x throttle_rows
+ * > 2^31: KT_ERR_OUT_OF_RANGE), what kt_paged_headroom refuses about the page set (different throttle-row counts, an engine named
+ * twice: KT_ERR_INVALID_ARGUMENT; different devices: KT_ERR_UNSUPPORTED), and per page with KT_ERR_UNSUPPORTED a stored `used`
+ * wider than int64 or an engine that has been fed a negative request — on ANY page: the search rests on sums that only grow.
+ * n == 0 with n_gangs == 0 is KT_OK and launches nothing.  Locking (every page exclusively, in address order) and ordering are
+ * kt_paged_admit's.  The call uses page 0's check slot and page 0's headroom result buffers and hands the results out:
+ * afterwards no headroom result of either kind is pending on page 0 (kt_headroom_fetch and kt_headroom_gangs_fetch answer
+ * KT_ERR_NOT_READY), a pending kt_check_launch of page 0 is gone, and stored status and reserved amounts of no page have
+ * changed.  out_copies, out_limiting and out_blocker [n_gangs] are all nullable.  One rank only. */
+int32_t kt_paged_headroom_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                const int64_t* gang_off, int32_t on_equal, int64_t cap, int64_t* out_copies, int32_t* out_limiting,
+                                int64_t* out_blocker);
 /* kt_preempt_launch and, with KT_PREEMPT_REPRIEVE in `flags`, kt_preempt_reprieve_launch over the pages, synchronous: their
  * definitions on the cluster of ALL names — counted pods, S_k, the m_eff cut, the victim mask, exact presence by contributor
  * counts, the operational walk with no monotonicity assumption, KT_PREEMPT_NONE.  n_pages == 1 returns byte for byte what

@@ -385,7 +385,7 @@ func (e *Engine) AdmitGangs(rows []int64, gangOff []int64, onEqual, commit bool)
 // kt_headroom_fetch): the number of leading Success verdicts a dry-run Admit of cap copies of the pod would return against the
 // stored status and the current reserved amounts, in [0, cap], and the lowest throttle row that blocks the next copy (-1: all
 // cap copies fit, or the pod's PreFilter is an error — then copies is 0).  Nothing is reserved.  cap in [1, 2^31-1].  The call
-// takes the engine's one check slot, like Admit.
+// takes the engine's one check slot, like Admit.  Whole gangs: kt_headroom_gangs_launch, over pages kt_paged_headroom_gangs (not wrapped here).
 func (e *Engine) Headroom(rows []int64, onEqual bool, cap int64) (copies []int64, limiting []int32, err error) {
 	e.mu.Lock() // the check slot is one per engine: see mu
 	defer e.mu.Unlock()

@@ -899,6 +899,100 @@ int32_t kt_headroom_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_copi
 }
 
 // ---------------------------------------------------------------------------------------------------
+// headroom, for gangs, over pages: kt_headroom_gangs_launch on the cluster of all names (kt_kernels_headroom_gangs_paged.hip)
+// ---------------------------------------------------------------------------------------------------
+// kt_paged_headroom's scaffolding with kt_headroom_gangs_launch's gang arguments: the gang defects and "a pod twice" asked per
+// gang, then the page set and every page's engine; one check of page 0, ONE kernel over the descriptors kt_admit reads, the
+// results through page 0's headroom buffers and out.
+int32_t kt_paged_headroom_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                const int64_t* gang_off, int32_t on_equal, int64_t cap, int64_t* out_copies, int32_t* out_limiting,
+                                int64_t* out_blocker) {
+  if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  PageLocks locks;
+  int32_t rc = paged_lock("paged headroom gangs", pages, n_pages, n, locks);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = pages[0];
+  // ---- refusals: nothing is launched and no slot or pending result of any page is touched before the last of them
+  if (n > 0 && !pod_rows) return e0->fail(KT_ERR_INVALID_ARGUMENT, "headroom gangs: pod_rows missing");
+  if ((rc = gangs_valid(e0, n, n_gangs, gang_off)) != KT_OK) return rc;
+  {
+    // gangs are judged independently: a pod may be in several of them, but not twice in one (it would reserve twice)
+    std::vector<int64_t> sorted;
+    for (int64_t g = 0; g < n_gangs; ++g) {
+      sorted.assign(pod_rows + gang_off[g], pod_rows + gang_off[g + 1]);
+      std::sort(sorted.begin(), sorted.end());
+      for (size_t j = 1; j < sorted.size(); ++j)
+        if (sorted[j] == sorted[j - 1])
+          return e0->fail(KT_ERR_INVALID_ARGUMENT, "headroom gangs: pod row %lld is in gang %lld twice", (long long)sorted[j], (long long)g);
+    }
+  }
+  if (!headroom_cap_ok(cap))
+    return e0->fail(KT_ERR_INVALID_ARGUMENT, "headroom gangs: cap = %lld, not in [1, %d]", (long long)cap, KT_HEADROOM_MAX_CAP);
+  if ((rc = paged_same_cluster("paged headroom gangs", pages, n_pages, n, pod_rows)) != KT_OK) return rc;  // (the rows are range-checked in place)
+  const int32_t T = e0->thr_rows_hi;
+  if ((double)n * (double)T > 2147483648.0)
+    return e0->fail(KT_ERR_OUT_OF_RANGE, "headroom gangs: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  for (int32_t k = 0; k < n_pages; ++k) {
+    kt_engine* e = pages[k];
+    if (e->wide)
+      return e->fail(KT_ERR_UNSUPPORTED, "headroom gangs: the stored `used` of page %d is wider than int64 (kt_headroom_gangs_paged reads int64 tables)",
+                     k);
+    if (e->neg_seen)
+      return e->fail(KT_ERR_UNSUPPORTED,
+                     "headroom gangs: page %d has been fed a negative request; the search over the copies rests on sums that only grow "
+                     "(kt_paged_headroom serves such pages pod by pod)",
+                     k);
+  }
+  if (n == 0) return KT_OK;  // (no gangs) nothing is launched
+  hipStream_t s = nullptr;
+  if ((rc = paged_order(pages, n_pages, &s)) != KT_OK) return rc;
+  // ---- from here on the call owns page 0's check slot and headroom result
+  e0->headroom_ready = false, e0->headroom_gangs = false;
+  if (e0->d_headroom_copies.cap < (size_t)n_gangs || e0->d_headroom_limiting.cap < (size_t)n_gangs ||
+      e0->d_headroom_blocker.cap < (size_t)n_gangs || e0->d_headroom_gang_off.cap < (size_t)n_gangs + 1) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_headroom_gangs_launch)
+    if (e0->last_stream) KT_HIP(e0, hipStreamSynchronize(e0->last_stream));
+    KT_HIP(e0, e0->d_headroom_copies.reserve((size_t)n_gangs));
+    KT_HIP(e0, e0->d_headroom_limiting.reserve((size_t)n_gangs));
+    KT_HIP(e0, e0->d_headroom_blocker.reserve((size_t)n_gangs));
+    KT_HIP(e0, e0->d_headroom_gang_off.reserve((size_t)n_gangs + 1));
+  }
+  // the offsets travel on the launch's stream, behind an earlier launch's kernel (the call is synchronous: the caller's memory is
+  // not referenced after return)
+  KT_HIP(e0, hipMemcpyAsync(e0->d_headroom_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s));
+  // ONE check of page 0 over the members of all gangs: which throttles affect which pod, and the error rows
+  rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e0->check_ready = false;  // the slot holds this call's rows (as with kt_paged_headroom): a pending kt_check_launch is gone
+  if (rc != KT_OK) {
+    (void)hipStreamSynchronize(s);  // the copy of the offsets reads the caller's memory
+    return rc;
+  }
+  if (!e0->admit_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->admit_pages_ev, hipEventDisableTiming));
+  KT_HIP(e0, hipEventSynchronize(e0->admit_pages_ev));  // the previous launch's copy has read h_admit_pages
+  e0->h_admit_pages.resize((size_t)n_pages);
+  for (int32_t k = 0; k < n_pages; ++k) {
+    const kt_engine* e = pages[k];
+    e0->h_admit_pages[(size_t)k] = kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  }
+  KT_HIP(e0, e0->d_admit_pages.reserve(sizeof(kt::AdmitPage) * (size_t)n_pages));
+  hipError_t herr = hipSuccess;
+  if (!kt::launch_headroom_gangs_paged(e0->h_admit_pages.data(), n_pages, (kt::AdmitPage*)e0->d_admit_pages.p, e0->admit_pages_ev, n_gangs,
+                                       e0->d_rows.p, e0->d_headroom_gang_off.p, T, on_equal != 0, (uint32_t)cap, e0->d_status.p, e0->d_summary.p,
+                                       e0->d_headroom_copies.p, e0->d_headroom_limiting.p, e0->d_headroom_blocker.p, s, &herr)) {
+    (void)hipStreamSynchronize(s);
+    return e0->fail(KT_ERR_DEVICE, "paged headroom gangs: copy of the page descriptors: %s", hipGetErrorString(herr));
+  }
+  KT_HIP(e0, hipGetLastError());
+  e0->last_stream = s;
+  if (out_copies) KT_HIP(e0, hipMemcpyAsync(out_copies, e0->d_headroom_copies.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
+  if (out_limiting) KT_HIP(e0, hipMemcpyAsync(out_limiting, e0->d_headroom_limiting.p, (size_t)n_gangs * 4, hipMemcpyDeviceToHost, s));
+  if (out_blocker) KT_HIP(e0, hipMemcpyAsync(out_blocker, e0->d_headroom_blocker.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
+  KT_HIP(e0, hipStreamSynchronize(s));
+  e0->headroom_ready = false;  // the results have been handed out: no headroom result of either kind is pending on page 0
+  return KT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // preempt: the shortest victim prefix that lets a blocked pod through (kt_kernels_preempt.hip), and the reprieve pass that shrinks
 // its victim mask to a minimal set (kt_kernels_reprieve.hip)
 // ---------------------------------------------------------------------------------------------------

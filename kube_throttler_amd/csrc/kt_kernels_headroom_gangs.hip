@@ -90,8 +90,8 @@ __global__ __launch_bounds__(kWave) void kt_headroom_gangs(const HeadroomGangArg
       }
     }
     const bool err = bad < i1;
-    // the lexicographic minimum of (h_t, first_t, t) over the throttles so far (wave-uniform); the throttles come in ascending
-    // order, so a tie in (h, first) keeps the lower row
+    // the lexicographic minimum of (h_t, first_t, t) over the throttles so far (wave-uniform).  The row takes part in the
+    // comparison: the chunk list is filled round by round over the lanes (admit_append_marked), not in row order
     int64_t best_h = err ? 0 : cap, best_first = bad;
     int32_t best_t = -1;
     for (int c0 = 0; c0 < T; c0 += kPreemptChunk) {
@@ -180,7 +180,8 @@ __global__ __launch_bounds__(kWave) void kt_headroom_gangs(const HeadroomGangArg
           if (!known) continue;
           h = top;
         }
-        if (h < best_h || (h == best_h && first < best_first)) best_h = h, best_first = first, best_t = (int32_t)t;
+        if (h < best_h || (h == best_h && (first < best_first || (first == best_first && (int32_t)t < best_t))))
+          best_h = h, best_first = first, best_t = (int32_t)t;
       }
       __syncthreads();  // the next chunk rewrites the list
     }

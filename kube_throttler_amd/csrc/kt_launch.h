@@ -119,6 +119,13 @@ bool launch_headroom(const AdmitPage* pages, int n_pages, AdmitPage* pages_dev, 
 void launch_headroom_gangs(const AdmitPage& pg, int64_t n_gangs, const int64_t* rows_dev, const int64_t* gang_off_dev, int T, bool on_equal,
                            uint32_t cap, const uint8_t* status, const uint64_t* summary, int64_t* copies, int32_t* limiting, int64_t* blocker,
                            hipStream_t s);
+// ... over n_pages >= 1 pages (kt_kernels_headroom_gangs_paged.hip): the descriptors of launch_headroom, copied to pages_dev and
+// guarded by pages_copied as there; status / summary: ONE check of page 0 over rows_dev [n], the members of all gangs; copies
+// [n_gangs], limiting [n_gangs] and blocker [n_gangs] out, on page 0.  false: the copy failed (*hip_err)
+bool launch_headroom_gangs_paged(const AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n_gangs,
+                                 const int64_t* rows_dev, const int64_t* gang_off_dev, int T, bool on_equal, uint32_t cap, const uint8_t* status,
+                                 const uint64_t* summary, int64_t* copies, int32_t* limiting, int64_t* blocker, hipStream_t s,
+                                 hipError_t* hip_err);
 // the shortest victim prefix per preemptor (kt_kernels_preempt.hip): one wave per preemptor.  rows_dev [n + m]: the preemptors,
 // then the candidates; status / summary: ONE check over those rows; partial: aggregate rows with exact per-name contributor counts;
 // calc / calc_updated / error: a dry finalize at `now`; prefix [n] and victims [n][m] out

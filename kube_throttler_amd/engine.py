@@ -44,7 +44,7 @@ EXPORTS = [
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
-    "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch",
+    "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch", "kt_paged_headroom_gangs",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -144,6 +144,28 @@ def paged_headroom(engines, rows, cap, on_equal=False):
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_headroom: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return copies[:n], limiting[:n]
+
+
+def paged_headroom_gangs(engines, pod_rows, gang_off, cap, on_equal=False, want_limiting=True, want_blocker=True):
+    """kt_paged_headroom_gangs: kt_headroom_gangs_launch + kt_headroom_gangs_fetch over the page engines, on the cluster of all
+    resource names -> (copies int64 [n_gangs] in [0, cap], limiting throttle row int32 [n_gangs] or None, blocker int64 [n_gangs]
+    or None).  Per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` the number of leading admitted gangs of a dry paged gang
+    admission of ``members * cap``; the queue position of the first member of the first copy that is not admitted whose
+    combined verdict is not Success, and the lowest throttle row that stops it there (both -1 when all ``cap`` copies are
+    admitted; limiting -1 when the blocker's verdict is an Error)."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    a = np.ascontiguousarray(pod_rows, dtype=np.int64)
+    g = _gang_offsets(gang_off)
+    n, ng = len(a), len(g) - 1
+    copies = np.zeros(max(ng, 1), np.int64)
+    limiting = np.zeros(max(ng, 1), np.int32) if want_limiting else None
+    blocker = np.zeros(max(ng, 1), np.int64) if want_blocker else None
+    rc = lib().kt_paged_headroom_gangs(hs, len(engines), n, a.ctypes.data if n else None, ng, g.ctypes.data, int(on_equal), int(cap),
+                                       copies.ctypes.data, None if limiting is None else limiting.ctypes.data,
+                                       None if blocker is None else blocker.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_headroom_gangs: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return copies[:ng], (None if limiting is None else limiting[:ng]), (None if blocker is None else blocker[:ng])
 
 
 def paged_preempt(engines, pod_rows, cand_rows, now, on_equal=False, reprieve=False, want_victims=True):
@@ -358,6 +380,8 @@ def lib():
         L.kt_headroom_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_paged_headroom.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                         C.c_void_p]
+        L.kt_paged_headroom_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_paged_preempt.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
                                        C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.kt_paged_preempt_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,

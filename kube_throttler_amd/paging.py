@@ -1267,6 +1267,99 @@ def paged_forecast_gangs_of(snaps, member_rows, instants, on_equal=False, ctx=No
     return first, verdicts_, [s if s < g else -1 for s in stopped]
 
 
+# ---- headroom for gangs over pages (kt_paged_headroom_gangs), as the kernel computes it, over a list of page snapshots ----
+def paged_headroom_gangs_of(snaps, member_rows, cap, on_equal=False):
+    """kt_paged_headroom_gangs for one gang, restated over the page snapshots (no GPU) -> (copies, limiting, blocker position
+    inside ``member_rows``): ``headroom_gangs_of`` on the cluster of all names, held to a dry paged gang admission of ``cap``
+    consecutive copies.  Which throttles affect which member and "a member is an Error or invalid" are page 0's.  Every
+    (throttle, page) pair is a throttle of its own: the page's own threshold (its stored calculatedAt flag; nothing is
+    reconciled), `used`, throttled flags and reserved row, A_t of that page (the values and the presence of the names the
+    affected members carry THERE); the pod count — threshold, flag, what a copy adds, the int64 cut — is page 0's, judged once,
+    and a page k != 0 none of whose names an affected member requests with a non-zero value is skipped.  The candidates of a pair
+    end at the running minimum over the pairs before it and where a named amount of the page would leave int64; the first
+    failing one is found by the kernel's 64-ary search, and the answer is the lexicographic minimum of (h, first stopped member
+    at j = h, t), throttles ascending and the pages inside a throttle.  With one snapshot this is ``headroom_gangs_of``."""
+    snap0 = snaps[0]
+    members, eq, cap = [int(p) for p in member_rows], bool(on_equal), int(cap)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap0.n_pods and bool(int(snap0.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap0, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    g = len(members) if bad_at is None else bad_at  # the members that are walked
+    members, affected = members[:g], affected[:g]
+    page_reqs = [[pod_requests(s, p) for p in members] for s in snaps]
+    best = (cap if bad_at is None else 0, g, -1)  # (h, first, t)
+    for t in (sorted(set().union(*affected)) if affected else []):
+        hit = [t in a for a in affected]
+        for k, s in enumerate(snaps):
+            reqs = page_reqs[k]
+            if k != 0 and not any(hit[j] and v != 0 for j in range(g) for v in reqs[j].values()):
+                continue  # nothing on this page is compared
+            f = int(s.thr_flags[t])
+            eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+            th = _amount_dict(s.thr_calc if f & S.THR_CALC_AT_NONZERO else s.thr_spec, t, s.D)
+            used, used_count = _amount_dict(s.thr_used, t, s.D)
+            flg = int(s.thr_thrl_flag[t]) & int(s.thr_thrl_has[t])
+            names = {d: (bool(flg >> d & 1), d in used, used.get(d, 0)) for d in range(s.D)}
+            res, res_count = _amount_dict(s.thr_reserved, t, s.D)
+            if k == 0:
+                ustate = (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names)
+            else:  # the pod count is page 0's: here the threshold does not name it and its flag is false
+                th, ustate = (th[0], None), (False, used_count is not None, used_count or 0, names)
+            # A_t of this page: only what the threshold names is summed (the rest is never compared)
+            per, per_p, per_c = {}, set(), 0
+            for j in range(g):
+                if hit[j]:
+                    per_c += 1
+                    for d, v in reqs[j].items():
+                        per_p.add(d)
+                        if d in th[0]:
+                            per[d] = min(per.get(d, 0) + v, _INT64_MAX)
+            if th[1] is None:
+                per_c = 0
+
+            def first_stopped(j):
+                r = {d: res.get(d, 0) + j * per.get(d, 0) for d in (set(res) | per_p if j > 0 else set(res))}
+                rc = (res_count or 0) + j * per_c if (res_count is not None or j > 0) else None
+                st = _gang_first_stopped(members, hit, reqs, th, ustate, r, rc, eq3, eq)
+                return g if st is None else st
+
+            # the range: up to the running minimum, and no further than every named amount of this page stays inside int64
+            top = best[0] if best[0] < cap else cap - 1
+            if bad_at is None:
+                if per_c > 0:
+                    top = min(top, (_INT64_MAX - (res_count or 0)) // per_c)
+                for d, a in per.items():
+                    if a > 0:
+                        top = min(top, (_INT64_MAX - res.get(d, 0)) // a)
+            lo, known, first = 0, False, g
+            while True:  # the 64-ary search for the first candidate in [lo, top] that fails
+                hi = top - 1 if known else top
+                n = hi - lo + 1
+                if n <= 0:
+                    break
+                step = (n + 63) // 64
+                probes = [(j, first_stopped(j)) for j in (hi - (63 - lane) * step for lane in range(64)) if j >= lo]
+                fail = next((i for i, (_, st) in enumerate(probes) if st < g), None)
+                if fail is None:
+                    lo = hi + 1
+                    if not known:
+                        break
+                    continue
+                (top, first), known = probes[fail], True
+                if fail > 0:
+                    lo = probes[fail - 1][0] + 1
+            if known and (top, first) < best[:2]:
+                best = (top, first, t)
+    h, first, t = best
+    if bad_at is not None:
+        return 0, (t if first < g else -1), first
+    return (cap, -1, -1) if h >= cap else (h, t, first)
+
+
 class PagedEngine:
     """One HIP engine per page of a ``ClusterState.build_pages()`` result; reconcile and check run on every page (the
     selector scan is repeated per page: the price of more than 16 resource names) and come back combined."""
@@ -1325,6 +1418,15 @@ class PagedEngine:
         verdicts of a dry-run admission of ``[pod] * cap`` with every page's names -> (copies [n], limiting throttle row [n],
         -1 when all ``cap`` are admitted).  Nothing is reserved."""
         return E.paged_headroom(self.engines, rows, cap, on_equal=on_equal)
+
+    def headroom_gangs(self, pod_rows, gang_off, cap, on_equal=False, want_limiting=True, want_blocker=True):
+        """How many copies of each gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` the throttles still admit as a whole, over every
+        page's names, through kt_paged_headroom_gangs (any number of pages; one page goes through the same call): the leading
+        admitted gangs of a dry-run paged gang admission of ``members * cap`` -> (copies [n_gangs], limiting throttle row
+        [n_gangs] or None, blocker queue position [n_gangs] or None; -1 / -1 when all ``cap`` copies are admitted).  Nothing is
+        reserved on any page."""
+        return E.paged_headroom_gangs(self.engines, pod_rows, gang_off, cap, on_equal=on_equal, want_limiting=want_limiting,
+                                      want_blocker=want_blocker)
 
     def preempt(self, pod_rows, cand_rows, now, on_equal=False, reprieve=False, want_victims=True):
         """The shortest victim prefix of the caller-ordered ``cand_rows`` that lets each pod of ``pod_rows`` through, over every
