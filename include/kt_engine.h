@@ -638,6 +638,48 @@ int32_t kt_forecast_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_row
 int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first /* [n_gangs], nullable */,
                                 uint8_t* out_verdicts /* [n_gangs][n_inst], nullable */,
                                 int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
+/* ---- headroom forecast: how many copies of a pod the throttles admit at each instant — kt_headroom_launch ("how many, now") and
+ *      kt_forecast_launch ("whether, when") asked at once: how many replicas fit once the night override begins, and at which
+ *      instant `want` replicas fit.
+ *      Notation as for kt_forecast_launch: the instants t_0 < .. < t_{m-1}, state R_t, "a throttle whose reconcile is an error, or
+ *      that is not valid and responsible, keeps its stored status in every R_t", the two facts about the replace rule, both
+ *      override ends inclusive; reserved amounts are read as they stand.
+ *      out_copies[i][k] (nullable, [n][n_inst]) is headroom(p_i, cap, on_equal) as kt_headroom_launch defines it, evaluated in
+ *      R_{t_k}: the number of leading Success verdicts of a dry kt_admit_launch over [p_i] * cap with R_{t_k} as the stored
+ *      status.  It lies in [0, cap].
+ *      out_limiting[i][k] (nullable, [n][n_inst]) is the lowest throttle row whose status is not KT_STATUS_NOT_THROTTLED in the row
+ *      PreFilter returns for the first copy that is not admitted in R_{t_k}, and -1 where all `cap` copies are admitted.
+ *      out_first[i] (nullable) is the smallest k with out_copies[i][k] >= want, or KT_FORECAST_NONE.
+ *      A pod whose PreFilter is an Error, or whose row is invalid: 0 copies at every instant, limiting -1, KT_FORECAST_NONE.  A pod
+ *      no throttle affects: `cap` at every instant, limiting -1, first 0.  A pod with a negative request is served, as by
+ *      kt_headroom_launch.
+ *      Identities:
+ *        (I1) with cap == want == 1, out_copies[i][k] == 1 exactly where kt_forecast_launch reports KT_VERDICT_SUCCESS, and
+ *             out_first is byte for byte kt_forecast_fetch's; an Error verdict is 0 copies and limiting -1.
+ *        (I2) with inst = [t] on an engine whose last action was kt_reconcile_launch(t, KT_RECONCILE_APPLY) plus fetch,
+ *             out_copies[:][0] and out_limiting[:][0] are byte for byte what kt_headroom_launch plus fetch report with the same cap
+ *             and on_equal.
+ *        (I3) the call is a dry run: stored status, reserved amounts and a pending kt_aggregate_launch's sums are unchanged.
+ *      One kt_check launch with the status matrix over pod_rows, the aggregate and dry finalize (at t_0) of kt_forecast_launch, and
+ *      one launch of kt_headroom_forecast (csrc/kt_kernels_headroom_forecast.hip): one wave per pod, lane = instant position; the
+ *      lane computes its instant's threshold as kt_forecast does and takes kt_headroom's closed form per amount; the answer is
+ *      the lexicographic minimum of (copies, throttle row) over the affecting throttles.
+ *      Refused before anything is launched, in this order: the instants as kt_forecast_launch refuses them and a missing pod_rows
+ *      with n > 0 (KT_ERR_INVALID_ARGUMENT); cap outside [1, KT_HEADROOM_MAX_CAP] or want outside [1, cap]
+ *      (KT_ERR_INVALID_ARGUMENT); a pod row outside the table, n x throttle_rows or n x n_inst > 2^31 (KT_ERR_OUT_OF_RANGE); `used`
+ *      wider than int64, a KT_VARIANT_INCREMENTAL engine, an exchange world above 1 (KT_ERR_UNSUPPORTED; the |request| sums probe
+ *      runs first where the sums are not known).  A refused call leaves the check slot, the reconcile report and every result
+ *      buffer alone.  n == 0 is KT_OK and launches nothing.
+ *      Slots: those of kt_forecast_launch — the ONE check slot, its dry finalize drops a pending reconcile report, a pending
+ *      kt_aggregate_launch keeps its sums, a pending preempt result of any kind stays fetchable.  The result SHARES the one pending
+ *      forecast result as its third kind: a later forecast launch of any kind replaces it; kt_forecast_fetch and
+ *      kt_forecast_gangs_fetch after this launch answer KT_ERR_NOT_READY, and kt_headroom_forecast_fetch answers it after theirs.
+ *      kt_headroom_forecast_fetch synchronises.
+ *      Out of scope: more than KT_MAX_DIMS resource names (pages), gangs, several ranks. ------------------------------------ */
+int32_t kt_headroom_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
+                                    const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want, void* stream);
+int32_t kt_headroom_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first /* [n], nullable */,
+                                   int64_t* out_copies /* [n][n_inst], nullable */, int32_t* out_limiting /* [n][n_inst], nullable */);
 /* The sorted, distinct instants in (from, until] at which the CalculateThreshold of some valid and responsible throttle can change:
  * every parsed non-zero `begin` of an override, and for every parsed non-zero `end` the instant end + 1 ns — the FIRST instant at
  * which the override is no longer active.  That is deliberately not the `end` that NextOverrideHappensIn

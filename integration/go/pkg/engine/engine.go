@@ -404,6 +404,36 @@ func (e *Engine) Headroom(rows []int64, onEqual bool, cap int64) (copies []int64
 	return copies, limiting, nil
 }
 
+// HeadroomForecast answers Headroom's question at each of the strictly ascending instants (instS / instNs, same length): for every
+// pod row of rows and every instant, how many copies of the pod the throttles admit once every valid and responsible throttle
+// has been reconciled at that instant — temporaryThresholdOverrides begin and end — each on the state as it is now
+// (kt_headroom_forecast_launch + kt_headroom_forecast_fetch).  copies[i*len(instS)+k] in [0, cap], limiting alike (-1: all cap
+// copies fit, or the pod's PreFilter is an error — then copies is 0), first[i] the smallest k with at least want copies or -1.
+// A dry run: stored status and reserved amounts stay.  cap in [1, 2^31-1], want in [1, cap].  Launch and fetch run under e.mu,
+// like every other user of the check slot.  One engine, single pods.  Not compiled in this repository (no Go toolchain in its build).
+func (e *Engine) HeadroomForecast(rows, instS []int64, instNs []int32, onEqual bool, cap, want int64) (first, copies []int64, limiting []int32, err error) {
+	e.mu.Lock() // the check slot is one per engine: see mu
+	defer e.mu.Unlock()
+	if len(rows) == 0 {
+		return nil, nil, nil, nil
+	}
+	if len(instS) == 0 || len(instS) != len(instNs) {
+		return nil, nil, nil, fmt.Errorf("HeadroomForecast: %d seconds and %d nanoseconds", len(instS), len(instNs))
+	}
+	if rc := C.kt_headroom_forecast_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(len(instS)), i64(instS), i32(instNs),
+		b2i(onEqual), C.int64_t(cap), C.int64_t(want), nil); rc != C.KT_OK {
+		return nil, nil, nil, e.err(rc)
+	}
+	first = make([]int64, len(rows))
+	copies = make([]int64, len(rows)*len(instS))
+	limiting = make([]int32, len(rows)*len(instS))
+	if rc := C.kt_headroom_forecast_fetch(e.h, C.int64_t(len(rows)), (*C.int64_t)(unsafe.Pointer(&first[0])),
+		(*C.int64_t)(unsafe.Pointer(&copies[0])), (*C.int32_t)(unsafe.Pointer(&limiting[0]))); rc != C.KT_OK {
+		return nil, nil, nil, e.err(rc)
+	}
+	return first, copies, limiting, nil
+}
+
 // Preempt answers, for every blocked pod row of rows, the shortest prefix of the caller-ordered candidate list cands (typically
 // ascending priority) whose deletion, followed by a reconcile of every throttle at now, makes PreFilter Success
 // (kt_preempt_launch + kt_preempt_fetch): prefix[i] in [0, len(cands)], 0 = the pod already passes against a fresh reconcile,

@@ -10,7 +10,8 @@
 // state of `used` (gang_walk); and what the two reprieve kernels (kt_preempt_reprieve, kt_kernels_preempt_gangs_reprieve.hip:
 // kt_preempt_gangs_reprieve) share: arguments, the list's state in LDS or HBM with its sizes, the list (counted, then gathered) and
 // the walk over the masked positions, generic in who is judged; and what the two forecast kernels (kt_kernels_forecast.hip,
-// kt_kernels_forecast_paged.hip) share on top of the four steps: the comparison of two instants.  The page descriptors themselves
+// kt_kernels_forecast_paged.hip) share on top of the four steps: the comparison of two instants.  And what kt_headroom and
+// kt_headroom_forecast (kt_kernels_headroom_forecast.hip) share: the closed form of one amount against a run of identical pods.  The page descriptors themselves
 // (AdmitPage, PreemptPage) are host-visible: kt_launch.h.
 #pragma once
 #include <algorithm>
@@ -128,6 +129,50 @@ __device__ __forceinline__ bool preempt_fails(int64_t vp, bool th_has, int64_t t
   const __int128 s = (__int128)(u_pres ? uv : 0) + (r_has ? rv : 0);
   if ((u_pres || r_has) && admit_cmp(s, tv, eq3)) return true;  // step 3
   return admit_cmp(s + vp, tv, eq);                             // step 4
+}
+
+// ---- what kt_headroom and kt_headroom_forecast share: the closed form of one amount ----------------------------------------------
+// One amount of one throttle as a run of identical pods meets it: a resource name (v = the pod's request) or the pod count
+// (v = 1).  Copy j (0-based) is checked against used + reserved + j * va, where va is what Reserve adds per admitted copy
+// (admit_reserve: the request when the pod's presence bit is set), and from copy 1 on the amount is present in `reserved`
+// because the pod brought it in.
+struct HeadroomTerm {
+  int64_t v, va, tv, uv, rv;
+  bool th_has;    // the threshold names the amount
+  bool present0;  // the amount is present in used or reserved before copy 0
+  bool brings;    // an admitted copy makes it present in reserved
+  bool flagged;   // step 2: status.throttled says so
+  bool eq3, eq;   // isThrottledOnEqual of step 3 and of step 4
+};
+// the four CheckThrottledFor steps (throttle_types.go:128-153) of copy j: does it pass all of them
+__device__ __forceinline__ bool headroom_passes(const HeadroomTerm& m, uint32_t j) {
+  if (m.flagged) return false;  // step 2
+  if (!m.th_has) return true;
+  if (m.v > m.tv) return false;  // step 1
+  const __int128 s = (__int128)m.uv + m.rv + (__int128)j * m.va;
+  if ((m.present0 || (j > 0 && m.brings)) && admit_cmp(s, m.tv, m.eq3)) return false;  // step 3
+  return !admit_cmp(s + m.v, m.tv, m.eq);                                                // step 4
+}
+// the largest h in [0, cap] with h * v <= room (v > 0, room >= 0).  cap * v is compared first, in 128 bits; below that the
+// quotient is < cap <= 2^31 and is found by bisection: 31 multiplications, exact for every 128-bit room, no division
+__device__ __forceinline__ uint32_t headroom_fit(__int128 room, int64_t v, uint32_t cap) {
+  if ((__int128)cap * v <= room) return cap;
+  uint32_t lo = 0, hi = cap;  // lo * v <= room < hi * v
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if ((__int128)mid * v <= room) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+// the leading copies that pass.  Copy 0 is decided as it stands (its presence rule differs).  With va > 0 (then va == v) the
+// sums grow: step 4 of copy j implies step 3 of copy j, so the copies that pass are those with
+// used + reserved + (j + 1) v < tv (on_equal) or <= tv (not): floor((tv - used - reserved - on_equal) / v) of them.  With
+// va <= 0 the sums do not grow: copies 1.. all fare as copy 1 does, or better.
+__device__ __forceinline__ uint32_t headroom_of_term(const HeadroomTerm& m, uint32_t cap) {
+  if (!headroom_passes(m, 0u)) return 0u;
+  if (!m.th_has || m.va <= 0) return headroom_passes(m, 1u) ? cap : 1u;
+  return headroom_fit((__int128)m.tv - m.uv - m.rv - (m.eq ? 1 : 0), m.v, cap);
 }
 
 // instant a <= instant b, (seconds, nanoseconds) each: the forecast kernels' override windows are inclusive at both ends

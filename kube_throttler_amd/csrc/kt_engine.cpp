@@ -402,7 +402,7 @@ int32_t kt_engine_destroy(kt_engine* e) {
   e->d_headroom_copies.release(); e->d_headroom_limiting.release(); e->d_headroom_gang_off.release(); e->d_headroom_blocker.release();
   e->d_preempt_prefix.release(); e->d_preempt_victims.release(); e->d_preempt_partial.release(); e->d_preempt_gang_off.release(); e->d_preempt_blocker.release(); e->d_reprieve_ws.release();
   e->d_forecast_first.release(); e->d_forecast_verdicts.release(); e->d_forecast_inst_s.release(); e->d_forecast_inst_ns.release();
-  e->d_forecast_gang_off.release(); e->d_forecast_blocker.release();
+  e->d_forecast_gang_off.release(); e->d_forecast_blocker.release(); e->d_forecast_copies.release(); e->d_forecast_limiting.release();
   e->d_used_hi.release(); e->d_out_used_hi.release();
   e->d_ovr_begin_s.release(); e->d_ovr_end_s.release(); e->d_ovr_begin_ns.release(); e->d_ovr_end_ns.release();
   e->d_partial.release();

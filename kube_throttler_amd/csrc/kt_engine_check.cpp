@@ -1507,7 +1507,7 @@ static int32_t forecast_locked(kt_engine* e, int64_t n, const int64_t* pod_rows,
   if (e->exchange_world > 1) return e->fail(KT_ERR_UNSUPPORTED, "forecast: the engine exchanges partials with %d ranks (one rank only)", e->exchange_world);
   if (e->wide && e->req_sums_valid) return e->fail(KT_ERR_UNSUPPORTED, "forecast: `used` is wider than int64 (kt_forecast reads int64 sums)");
   if (n == 0) {  // nothing is launched
-    e->forecast_ready = true, e->forecast_gangs = false, e->forecast_n = 0, e->forecast_m = n_inst;
+    e->forecast_ready = true, e->forecast_kind = kForecastPods, e->forecast_n = 0, e->forecast_m = n_inst;
     return KT_OK;
   }
   KT_HIP(e, hipSetDevice(e->device));
@@ -1548,7 +1548,7 @@ static int32_t forecast_locked(kt_engine* e, int64_t n, const int64_t* pod_rows,
                       e->d_preempt_partial.p, e->d_out_error.p, e->d_forecast_first.p, e->d_forecast_verdicts.p, s);
   KT_HIP(e, hipGetLastError());
   e->last_stream = s;
-  e->forecast_ready = true, e->forecast_gangs = false, e->forecast_n = n, e->forecast_m = n_inst;
+  e->forecast_ready = true, e->forecast_kind = kForecastPods, e->forecast_n = n, e->forecast_m = n_inst;
   return KT_OK;
 }
 
@@ -1563,7 +1563,7 @@ int32_t kt_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, uint8_t* 
   if (!e) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
-  if (!e->forecast_ready || e->forecast_gangs) return e->fail(KT_ERR_NOT_READY, "kt_forecast_fetch before kt_forecast_launch");
+  if (!e->forecast_ready || e->forecast_kind != kForecastPods) return e->fail(KT_ERR_NOT_READY, "kt_forecast_fetch before kt_forecast_launch");
   if (n < 0 || n > e->forecast_n) return e->fail(KT_ERR_OUT_OF_RANGE, "n=%lld, the last forecast launch had %lld pods", (long long)n, (long long)e->forecast_n);
   if (n == 0) return KT_OK;
   hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
@@ -1574,11 +1574,109 @@ int32_t kt_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, uint8_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// headroom forecast: how many copies of a pod the throttles admit at each instant (kt_kernels_headroom_forecast.hip)
+// ---------------------------------------------------------------------------------------------------
+// forecast_locked's sequence with kt_headroom_forecast in kt_forecast's place: the refusals in its order (cap and want behind the
+// instants), the |request| sums probe, ONE check, the dry aggregate and finalize at t_0, the kernel.  The result shares the one
+// pending forecast result as its third kind.  The caller holds the launch lock.
+static int32_t headroom_forecast_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
+                                        const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want, void* stream) {
+  if (int32_t bad = forecast_instants_valid(e, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) return bad;
+  if (!headroom_cap_ok(cap))
+    return e->fail(KT_ERR_INVALID_ARGUMENT, "headroom forecast: cap = %lld, not in [1, %d]", (long long)cap, KT_HEADROOM_MAX_CAP);
+  if (want < 1 || want > cap)
+    return e->fail(KT_ERR_INVALID_ARGUMENT, "headroom forecast: want = %lld, not in [1, cap = %lld]", (long long)want, (long long)cap);
+  for (int64_t i = 0; i < n; ++i)
+    if (pod_rows[i] < 0 || pod_rows[i] >= e->cfg.pod_capacity)
+      return e->fail(KT_ERR_OUT_OF_RANGE, "headroom forecast: pod row %lld", (long long)pod_rows[i]);
+  const int32_t T = e->thr_rows_hi;  // (moved by throttle batches only, under this lock: ensure_ready below does not change it)
+  if ((double)n * (double)T > 2147483648.0)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "headroom forecast: n x throttle_rows = %lld x %d exceeds 2^31 matrix bytes", (long long)n, T);
+  if ((double)n * (double)n_inst > 2147483648.0)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "headroom forecast: n x n_inst = %lld x %lld exceeds 2^31 results", (long long)n, (long long)n_inst);
+  if (e->incremental) return e->fail(KT_ERR_UNSUPPORTED, "headroom forecast: not for KT_VARIANT_INCREMENTAL engines");
+  if (e->exchange_world > 1)
+    return e->fail(KT_ERR_UNSUPPORTED, "headroom forecast: the engine exchanges partials with %d ranks (one rank only)", e->exchange_world);
+  if (e->wide && e->req_sums_valid)
+    return e->fail(KT_ERR_UNSUPPORTED, "headroom forecast: `used` is wider than int64 (kt_headroom_forecast reads int64 sums)");
+  if (n == 0) {  // nothing is launched
+    e->forecast_ready = true, e->forecast_kind = kForecastHeadroom, e->forecast_n = 0, e->forecast_m = n_inst;
+    return KT_OK;
+  }
+  KT_HIP(e, hipSetDevice(e->device));
+  hipStream_t s = pick_stream(e, stream);
+  // the |request| sums probe where the sums are unknown, before the check slot or any result buffer is touched (as forecast_locked)
+  int32_t rc = ensure_ready(e, s);
+  if (rc == KT_OK) rc = request_sums_in_range(e, s);
+  if (rc != KT_OK) return rc;
+  if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "headroom forecast: `used` is wider than int64 (kt_headroom_forecast reads int64 sums)");
+  e->forecast_ready = false;
+  const size_t cells = (size_t)n * (size_t)n_inst;
+  if (e->d_forecast_first.cap < (size_t)n || e->d_forecast_copies.cap < cells || e->d_forecast_limiting.cap < cells ||
+      e->d_forecast_inst_s.cap < (size_t)n_inst || e->d_forecast_inst_ns.cap < (size_t)n_inst) {
+    // a launch that was never fetched may still be using the old buffers, on the stream it was given (as kt_forecast_launch)
+    if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
+    KT_HIP(e, e->d_forecast_first.reserve((size_t)n));
+    KT_HIP(e, e->d_forecast_copies.reserve(cells));
+    KT_HIP(e, e->d_forecast_limiting.reserve(cells));
+    KT_HIP(e, e->d_forecast_inst_s.reserve((size_t)n_inst));
+    KT_HIP(e, e->d_forecast_inst_ns.reserve((size_t)n_inst));
+  }
+  // the instants travel on the launch's stream, behind an earlier forecast's kernel; the caller's memory is not referenced after
+  // return
+  KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_s.p, inst_s, (size_t)n_inst * 8, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_ns.p, inst_ns, (size_t)n_inst * 4, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  // ONE check over the pods: which throttles affect which pod, and the error rows.  The preempt result lives in buffers this
+  // call does not write: it stays fetchable
+  const bool preempt_was_ready = e->preempt_ready;
+  rc = check_launch_locked(e, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
+  e->check_ready = false;  // the slot holds this call's rows (as with kt_forecast_launch): a pending kt_check_launch is gone
+  e->preempt_ready = preempt_was_ready;
+  if (rc != KT_OK) return rc;
+  // the aggregate with exact contributor counts and the error bytes; the dry finalize runs at t_0
+  if ((rc = preempt_reconcile_locked(e, inst_s[0], inst_ns[0], s)) != KT_OK) return rc;
+  const kt::AdmitPage pg{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u};
+  kt::launch_headroom_forecast(pg, n, n_inst, e->d_rows.p, e->d_forecast_inst_s.p, e->d_forecast_inst_ns.p, T, on_equal != 0, (uint32_t)cap,
+                               (uint32_t)want, e->d_status.p, e->d_summary.p, e->d_preempt_partial.p, e->d_out_error.p, e->d_forecast_first.p,
+                               e->d_forecast_copies.p, e->d_forecast_limiting.p, s);
+  KT_HIP(e, hipGetLastError());
+  e->last_stream = s;
+  e->forecast_ready = true, e->forecast_kind = kForecastHeadroom, e->forecast_n = n, e->forecast_m = n_inst;
+  return KT_OK;
+}
+
+int32_t kt_headroom_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns,
+                                    int32_t on_equal, int64_t cap, int64_t want, void* stream) {
+  if (!e || n < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  return headroom_forecast_locked(e, n, pod_rows, n_inst, inst_s, inst_ns, on_equal, cap, want, stream);
+}
+
+int32_t kt_headroom_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, int64_t* out_copies, int32_t* out_limiting) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (!e->forecast_ready || e->forecast_kind != kForecastHeadroom)
+    return e->fail(KT_ERR_NOT_READY, "kt_headroom_forecast_fetch before kt_headroom_forecast_launch");
+  if (n < 0 || n > e->forecast_n)
+    return e->fail(KT_ERR_OUT_OF_RANGE, "n=%lld, the last headroom forecast launch had %lld pods", (long long)n, (long long)e->forecast_n);
+  if (n == 0) return KT_OK;
+  hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
+  const size_t cells = (size_t)n * (size_t)e->forecast_m;
+  if (out_first) KT_HIP(e, hipMemcpyAsync(out_first, e->d_forecast_first.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (out_copies) KT_HIP(e, hipMemcpyAsync(out_copies, e->d_forecast_copies.p, cells * 8, hipMemcpyDeviceToHost, s));
+  if (out_limiting) KT_HIP(e, hipMemcpyAsync(out_limiting, e->d_forecast_limiting.p, cells * 4, hipMemcpyDeviceToHost, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  return KT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // forecast, for gangs: the first instant at which a whole gang is admitted (kt_kernels_forecast_gangs.hip)
 // ---------------------------------------------------------------------------------------------------
 // The refusals of forecast_locked in its order (the instants first, then the gang defects and "a pod twice" asked per gang), then
 // the same launches with kt_forecast_gangs in kt_forecast's place.  The result shares the one pending forecast result;
-// forecast_gangs tells the fetches apart.  The caller holds the launch lock.
+// forecast_kind tells the fetches apart.  The caller holds the launch lock.
 static int32_t forecast_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_inst,
                                      const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, void* stream) {
   if (int32_t bad = forecast_instants_valid(e, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) return bad;
@@ -1610,7 +1708,7 @@ static int32_t forecast_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod
   if (e->wide && e->req_sums_valid)
     return e->fail(KT_ERR_UNSUPPORTED, "forecast gangs: `used` is wider than int64 (kt_forecast_gangs reads int64 sums)");
   if (n == 0) {  // (no gangs) nothing is launched
-    e->forecast_ready = true, e->forecast_gangs = true, e->forecast_n = 0, e->forecast_m = n_inst;
+    e->forecast_ready = true, e->forecast_kind = kForecastGangs, e->forecast_n = 0, e->forecast_m = n_inst;
     return KT_OK;
   }
   KT_HIP(e, hipSetDevice(e->device));
@@ -1654,7 +1752,7 @@ static int32_t forecast_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod
                             e->d_forecast_verdicts.p, e->d_forecast_blocker.p, s);
   KT_HIP(e, hipGetLastError());
   e->last_stream = s;
-  e->forecast_ready = true, e->forecast_gangs = true, e->forecast_n = n_gangs, e->forecast_m = n_inst;
+  e->forecast_ready = true, e->forecast_kind = kForecastGangs, e->forecast_n = n_gangs, e->forecast_m = n_inst;
   return KT_OK;
 }
 
@@ -1669,7 +1767,7 @@ int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_firs
   if (!e) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
-  if (!e->forecast_ready || !e->forecast_gangs) return e->fail(KT_ERR_NOT_READY, "kt_forecast_gangs_fetch before kt_forecast_gangs_launch");
+  if (!e->forecast_ready || e->forecast_kind != kForecastGangs) return e->fail(KT_ERR_NOT_READY, "kt_forecast_gangs_fetch before kt_forecast_gangs_launch");
   if (n_gangs < 0 || n_gangs > e->forecast_n)
     return e->fail(KT_ERR_OUT_OF_RANGE, "n_gangs=%lld, the last forecast gangs launch had %lld gangs", (long long)n_gangs, (long long)e->forecast_n);
   if (n_gangs == 0) return KT_OK;
@@ -1725,7 +1823,7 @@ int32_t kt_paged_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, c
     if (e->wide) return e->fail(KT_ERR_UNSUPPORTED, "forecast: `used` of page %d is wider than int64 (kt_forecast_paged reads int64 sums)", k);
   }
   // ---- from here on the call owns page 0's check slot and forecast result and every page's reconcile report
-  e0->forecast_ready = false, e0->forecast_gangs = false;
+  e0->forecast_ready = false, e0->forecast_kind = kForecastPods;
   if (!e0->preempt_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->preempt_pages_ev, hipEventDisableTiming));
   KT_HIP(e0, hipEventSynchronize(e0->preempt_pages_ev));  // the previous call's copy has read h_preempt_pages
   e0->h_preempt_pages.assign((size_t)n_pages, kt::PreemptPage{});
@@ -1835,7 +1933,7 @@ int32_t kt_paged_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_
       return e->fail(KT_ERR_UNSUPPORTED, "forecast gangs: `used` of page %d is wider than int64 (kt_forecast_gangs_paged reads int64 sums)", k);
   }
   // ---- from here on the call owns page 0's check slot and forecast result and every page's reconcile report
-  e0->forecast_ready = false, e0->forecast_gangs = false;
+  e0->forecast_ready = false, e0->forecast_kind = kForecastPods;
   if (!e0->preempt_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->preempt_pages_ev, hipEventDisableTiming));
   KT_HIP(e0, hipEventSynchronize(e0->preempt_pages_ev));  // the previous call's copy has read h_preempt_pages
   e0->h_preempt_pages.assign((size_t)n_pages, kt::PreemptPage{});

@@ -5,7 +5,7 @@
 // reservedResourceAmounts.addPod, reserved_resource_amounts.go:66-77), copy after copy, until the first copy that is not
 // admitted.  Every affecting throttle reserves every admitted copy, so the answer is the minimum over the affecting
 // throttles t of h_t, the copies t alone lets through, and inside a throttle the pod count and every requested resource name
-// are independent: h_t is the minimum over them of a closed form (headroom_of_term below).  Nothing is walked in sequence and
+// are independent: h_t is the minimum over them of a closed form (headroom_of_term, kt_admit_common.h).  Nothing is walked in sequence and
 // nothing is mutable, so — unlike kt_admit, which is ONE wave — the pods are independent: one wave per pod, the grid strides.
 //
 //   input   status matrix [n][T] and summary words [n] of a preceding kt_check launch over the same rows (which throttles
@@ -38,49 +38,6 @@ struct HeadroomArgs {
   int32_t T, on_equal;
   uint32_t cap;  // 1 .. 2^31 - 1
 };
-
-// One amount of one throttle as a run of identical pods meets it: a resource name (v = the pod's request) or the pod count
-// (v = 1).  Copy j (0-based) is checked against used + reserved + j * va, where va is what Reserve adds per admitted copy
-// (admit_reserve: the request when the pod's presence bit is set), and from copy 1 on the amount is present in `reserved`
-// because the pod brought it in.
-struct HeadroomTerm {
-  int64_t v, va, tv, uv, rv;
-  bool th_has;    // the threshold names the amount
-  bool present0;  // the amount is present in used or reserved before copy 0
-  bool brings;    // an admitted copy makes it present in reserved
-  bool flagged;   // step 2: status.throttled says so
-  bool eq3, eq;   // isThrottledOnEqual of step 3 and of step 4
-};
-// the four CheckThrottledFor steps (throttle_types.go:128-153) of copy j: does it pass all of them
-__device__ __forceinline__ bool headroom_passes(const HeadroomTerm& m, uint32_t j) {
-  if (m.flagged) return false;  // step 2
-  if (!m.th_has) return true;
-  if (m.v > m.tv) return false;  // step 1
-  const __int128 s = (__int128)m.uv + m.rv + (__int128)j * m.va;
-  if ((m.present0 || (j > 0 && m.brings)) && admit_cmp(s, m.tv, m.eq3)) return false;  // step 3
-  return !admit_cmp(s + m.v, m.tv, m.eq);                                                // step 4
-}
-// the largest h in [0, cap] with h * v <= room (v > 0, room >= 0).  cap * v is compared first, in 128 bits; below that the
-// quotient is < cap <= 2^31 and is found by bisection: 31 multiplications, exact for every 128-bit room, no division
-__device__ __forceinline__ uint32_t headroom_fit(__int128 room, int64_t v, uint32_t cap) {
-  if ((__int128)cap * v <= room) return cap;
-  uint32_t lo = 0, hi = cap;  // lo * v <= room < hi * v
-  while (hi - lo > 1u) {
-    const uint32_t mid = lo + (hi - lo) / 2u;
-    if ((__int128)mid * v <= room) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-// the leading copies that pass.  Copy 0 is decided as it stands (its presence rule differs).  With va > 0 (then va == v) the
-// sums grow: step 4 of copy j implies step 3 of copy j, so the copies that pass are those with
-// used + reserved + (j + 1) v < tv (on_equal) or <= tv (not): floor((tv - used - reserved - on_equal) / v) of them.  With
-// va <= 0 the sums do not grow: copies 1.. all fare as copy 1 does, or better.
-__device__ __forceinline__ uint32_t headroom_of_term(const HeadroomTerm& m, uint32_t cap) {
-  if (!headroom_passes(m, 0u)) return 0u;
-  if (!m.th_has || m.va <= 0) return headroom_passes(m, 1u) ? cap : 1u;
-  return headroom_fit((__int128)m.tv - m.uv - m.rv - (m.eq ? 1 : 0), m.v, cap);
-}
 
 // A reserved amount whose presence bit (has_count) is clear reads as 0 below, whatever the table holds: that is the state kt_admit
 // starts from (admit_load_state stores 0 for such an entry, and admit_count_bits / admit_name_bits then read the state unmasked).

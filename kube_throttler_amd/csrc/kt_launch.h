@@ -195,6 +195,12 @@ void launch_preempt_gangs_reprieve_paged(const PreemptPage* pages, int n_pages, 
 void launch_forecast(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, const int64_t* inst_s, const int32_t* inst_ns, int T,
                      bool on_equal, const uint8_t* status, const uint64_t* summary, const unsigned long long* partial, const uint8_t* error,
                      int64_t* first, uint8_t* verdicts, hipStream_t s);
+// how many copies of a pod the throttles admit at each instant (kt_kernels_headroom_forecast.hip): launch_forecast's inputs plus cap
+// and want (1 <= want <= cap <= 2^31 - 1); first [n], copies [n][m] and limiting [n][m] out
+void launch_headroom_forecast(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, const int64_t* inst_s, const int32_t* inst_ns,
+                              int T, bool on_equal, uint32_t cap, uint32_t want, const uint8_t* status, const uint64_t* summary,
+                              const unsigned long long* partial, const uint8_t* error, int64_t* first, int64_t* copies, int32_t* limiting,
+                              hipStream_t s);
 // ... over n_pages >= 1 pages (kt_kernels_forecast_paged.hip): the descriptors of launch_preempt_paged (every page's own dense
 // aggregate and the error bytes of its dry finalize; calc / calc_updated are not read), copied to pages_dev and guarded by
 // pages_copied as there; status / summary: ONE check of page 0 over rows_dev [n]; first [n] and verdicts [n][m] out, on page 0.

@@ -45,6 +45,7 @@ EXPORTS = [
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
     "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch", "kt_paged_headroom_gangs",
+    "kt_headroom_forecast_launch", "kt_headroom_forecast_fetch",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -400,6 +401,9 @@ def lib():
                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.kt_forecast_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.kt_headroom_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                                  C.c_int64, C.c_void_p]
+        L.kt_headroom_forecast_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_forecast_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                C.c_int32, C.c_void_p]
         L.kt_forecast_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -943,6 +947,33 @@ class Engine:
         A dry run: stored status and reserved amounts stay as they are."""
         self.forecast_gangs_launch(pod_rows, gang_off, instants, on_equal)
         return self.forecast_gangs_fetch(len(_gang_offsets(gang_off)) - 1, len(instants), want_verdicts, want_blocker)
+
+    # ---- headroom forecast: how many copies of a pod the throttles admit at each instant
+    def headroom_forecast_launch(self, pod_rows, instants, cap, want=1, on_equal=False, stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        inst_s = np.ascontiguousarray([int(t[0]) for t in instants], dtype=np.int64)
+        inst_ns = np.ascontiguousarray([int(t[1]) for t in instants], dtype=np.int32)
+        m = len(inst_s)
+        self._ck(lib().kt_headroom_forecast_launch(self._h, len(a), p if len(a) else None, m, inst_s.ctypes.data if m else None,
+                                                   inst_ns.ctypes.data if m else None, int(on_equal), int(cap), int(want), stream))
+
+    def headroom_forecast_fetch(self, n, n_inst, want_copies=True, want_limiting=True):
+        first = np.zeros(max(n, 1), np.int64)
+        copies = np.zeros(max(n * n_inst, 1), np.int64) if want_copies else None
+        limiting = np.zeros(max(n * n_inst, 1), np.int32) if want_limiting else None
+        self._ck(lib().kt_headroom_forecast_fetch(self._h, n, first.ctypes.data, None if copies is None else copies.ctypes.data,
+                                                  None if limiting is None else limiting.ctypes.data))
+        return (first[:n], (None if copies is None else copies[:n * n_inst].reshape(n, n_inst)),
+                (None if limiting is None else limiting[:n * n_inst].reshape(n, n_inst)))
+
+    def headroom_forecast(self, pod_rows, instants, *, cap, want=1, on_equal=False):
+        """kt_headroom_forecast_launch + kt_headroom_forecast_fetch: per pod and per instant the number of leading Success
+        verdicts a dry-run admission of ``cap`` copies of the pod returns once every valid and responsible throttle has been
+        reconciled at that instant (each on the state as it is now), the lowest throttle row that stops the next copy (-1: all
+        ``cap`` are admitted), and the first position with at least ``want`` copies (FORECAST_NONE: none) -> (first int64 [n],
+        copies int64 [n][n_inst], limiting int32 [n][n_inst]).  A dry run: stored status and reserved amounts stay as they are."""
+        self.headroom_forecast_launch(pod_rows, instants, cap, want, on_equal)
+        return self.headroom_forecast_fetch(len(pod_rows), len(instants))
 
     def override_instants(self, from_, until, cap=None):
         """kt_override_instants: the sorted, distinct instants in (from_, until] at which some valid and responsible throttle's

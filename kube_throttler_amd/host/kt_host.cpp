@@ -1445,6 +1445,46 @@ RetryAfterResult KubeThrottler::RetryAfter(const std::string& pod_key, const std
   return out;
 }
 
+// When do `want` further pods of this pod's shape fit: RetryAfter's instants, one kt_headroom_forecast_launch +
+// kt_headroom_forecast_fetch over them with cap = want on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).
+ScaleAfterResult KubeThrottler::ScaleAfter(const std::string& pod_key, int64_t want, const std::string& now_rfc3339, int64_t horizon_seconds) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  ScaleAfterResult out;
+  std::vector<int64_t> inst_s;
+  std::vector<int32_t> inst_ns;
+  if (!retry_after_instants(p, "ScaleAfter", "headroom forecast", now_rfc3339, horizon_seconds, &inst_s, &inst_ns, &out.error)) return out;
+  const int64_t row = p.pod_rows.find(pod_key);
+  if (row < 0) {
+    out.error = "pod " + pod_key + " is not known to the plugin (OnPodAdd first)";
+    return out;
+  }
+  if (want < 1) {
+    out.error = "ScaleAfter: want " + std::to_string(want);
+    return out;
+  }
+  const int64_t m = (int64_t)inst_s.size();
+  int64_t first = KT_FORECAST_NONE;
+  std::vector<int32_t> limiting((size_t)m, -1);
+  out.copies_at.assign((size_t)m, 0);
+  int32_t rc = kt_headroom_forecast_launch(p.e, 1, &row, m, inst_s.data(), inst_ns.data(), /*isThrottledOnEqual=*/0, /*cap=*/want, want, nullptr);
+  if (rc == KT_OK) rc = kt_headroom_forecast_fetch(p.e, 1, &first, out.copies_at.data(), limiting.data());
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    out.copies_at.clear();
+    return out;
+  }
+  for (int64_t k = 0; k < m; ++k) {
+    out.instants.emplace_back(inst_s[(size_t)k], inst_ns[(size_t)k]);
+    const int32_t t = limiting[(size_t)k];
+    out.limiting_at.push_back(t >= 0 && (size_t)t < p.thr_by_row.size() && p.thr_live[(size_t)t] ? p.thr_by_row[(size_t)t].Key() : std::string());
+  }
+  RetryAfterResult at;  // (the instant's text is RetryAfter's)
+  retry_after_first(at, first, inst_s, inst_ns);
+  out.found = at.has, out.instantSec = at.instantSec, out.instantNsec = at.instantNsec, out.instant = at.instant;
+  return out;
+}
+
 // When is this gang admitted: RetryAfter's instants, one kt_forecast_gangs_launch + kt_forecast_gangs_fetch with the members as ONE
 // gang on the mirror's one engine (isThrottledOnEqual = false, as PreFilter).  Nothing is changed.
 GangRetryAfterResult KubeThrottler::RetryAfterGang(const std::vector<std::string>& member_keys, const std::string& now_rfc3339,

@@ -197,6 +197,21 @@ struct GangRetryAfterResult {
   std::vector<std::string> blockers_at;  // per judged instant the Pod::Key() of the first member that is not admitted; empty: the gang passes
 };
 
+// ScaleAfter: the first instant at which `want` further pods of a pod's shape fit, and how many fit at each judged instant
+struct ScaleAfterResult {
+  bool found = false;            // some instant of the window admits `want` copies: `instant` is the first
+  int64_t instantSec = 0;        // the instant (Unix seconds, nanoseconds); == now: they fit against a fresh reconcile
+  int32_t instantNsec = 0;
+  std::string instant;           // ... as RFC3339 (UTC, with nanoseconds where they are not zero)
+  // the instants that were judged — now, then every override boundary in (now, now + horizon] — and per instant the copies
+  // admitted (in [0, want]) and the Throttle::Key() of the lowest-row throttle that stops the next one (empty: all `want` fit, or
+  // the pod's PreFilter is an Error)
+  std::vector<std::pair<int64_t, int32_t>> instants;
+  std::vector<int64_t> copies_at;
+  std::vector<std::string> limiting_at;
+  std::string error;             // not empty: the call failed (unknown pod, want < 1, a paged mirror, engine error)
+};
+
 // KubeThrottlerPluginArgs (pkg/scheduler_plugin/plugin_args.go:33-40) + engine sizing
 struct PluginArgs {
   std::string name;                 // throttler name (required)
@@ -290,6 +305,14 @@ class KubeThrottler {
   // now ++ boundaries.  The members' own RetryAfter answers do not compose into this one.  A dry run; a member named twice, an
   // unknown key, an empty gang and a mirror on several pages answer an error.
   GangRetryAfterResult RetryAfterGang(const std::vector<std::string>& member_keys, const std::string& now_rfc3339, int64_t horizon_seconds);
+
+  // When do `want` replicas fit: per instant of now ++ the override boundaries in (now, now + horizon] the number of further pods
+  // of pod_key's shape that PreFilter + Reserve would admit one after the other if every throttle were reconciled then (at most
+  // `want`), the throttle that stops the next one, and the first instant at which all `want` fit.  kt_override_instants for the
+  // boundaries, ONE kt_headroom_forecast_launch over now ++ boundaries with cap = want — what an autoscaler asks before it
+  // scales a Job up for the night window.  A dry run; the reserved totals are read as they stand.  An unknown key, want < 1 and a
+  // mirror on several pages answer an error.
+  ScaleAfterResult ScaleAfter(const std::string& pod_key, int64_t want, const std::string& now_rfc3339, int64_t horizon_seconds);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

@@ -969,6 +969,66 @@ def forecast_of(snap, pod_row, instants, on_equal=False, ctx=None):
     return next((k for k in range(m) if not fails[k]), -1), verdicts_
 
 
+# ---- headroom forecast (kt_headroom_forecast_launch), in closed form on a Snapshot ----
+def headroom_forecast_of(snap, pod_row, instants, cap, want=1, on_equal=False, ctx=None):
+    """kt_headroom_forecast_launch for one pod, in closed form on a Snapshot (no GPU) -> (first, copies [len(instants)], limiting
+    [len(instants)]).  copies[k]: the leading Success verdicts of a dry admission of ``[pod] * cap`` once every valid and
+    responsible throttle has been reconciled at ``instants[k]`` on the state as it is now — per throttle and instant
+    ``forecast_of``'s threshold (CalculateThreshold, the replace rule, which threshold the check reads, throttled from the fresh
+    sums), per amount ``headroom_of``'s closed form, the minimum over both; limiting[k]: the lowest throttle row that stops the
+    next copy, -1 where all ``cap`` are admitted; first: the smallest k with copies[k] >= want, or -1.  A throttle whose reconcile
+    is an error is judged from its stored status, at every instant.  ``ctx`` is ``preempt_context``'s aggregate (any ``now``)."""
+    inst = [_instant(t) for t in instants]
+    ctx = preempt_context(snap, inst[0]) if ctx is None else ctx
+    p, eq, m, cap = int(pod_row), bool(on_equal), len(inst), int(cap)
+    if not (0 <= p < snap.n_pods) or not int(snap.pod_flags[p]) & S.POD_VALID:
+        return -1, [0] * m, [-1] * m
+    err, affected = affected_throttles(snap, p)
+    if err:
+        return -1, [0] * m, [-1] * m
+    req = {d: v for d, v in pod_requests(snap, p).items() if v != 0}  # (every name in it is present: the pod brings it)
+    best = [(cap, -1)] * m  # (copies, row): affected is ascending, so a strict < keeps the lowest row of a tie
+    for t in affected:
+        th = ctx["thr"][t]
+        f = int(snap.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+        r_hc = res_count is not None
+        if th["error"]:  # the stored status, at every instant
+            used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+            sth, sth_count = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+            flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+            u_hc = used_count is not None
+            h = _copies_of_amount(1, True, sth_count is not None, sth_count or 0, used_count or 0, res_count or 0, u_hc or r_hc,
+                                  bool(f & S.THR_THROTTLED_POD), eq3, eq, cap)
+            for d, v in req.items():
+                h = min(h, _copies_of_amount(v, True, d in sth, sth.get(d, 0), used.get(d, 0), res.get(d, 0), d in used or d in res,
+                                             bool(flg >> d & 1), eq3, eq, cap))
+            best = [(h, t) if h < b[0] else b for b in best]
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        u_hc = pods > 0
+        stored = _amount_dict(snap.thr_calc, t, snap.D)
+        spec, spec_count = _amount_dict(snap.thr_spec, t, snap.D)
+        for k, at in enumerate(inst):
+            calc, cc, any_err = _calculated_threshold(snap, t, at)
+            fp = int(snap.thr_spec_msgs_fp[t]) if any_err else 0
+            replace = (calc, cc) != stored or int(snap.thr_status_msgs_fp[t]) != fp
+            rd, rd_count = (calc, cc) if (f & S.THR_CALC_AT_NONZERO) or replace else (spec, spec_count)
+            h = _copies_of_amount(1, True, rd_count is not None, rd_count or 0, pods if u_hc else 0, res_count or 0, u_hc or r_hc,
+                                  cc is not None and u_hc and pods >= cc, eq3, eq, cap)
+            for d, v in req.items():
+                u_pr = cnt.get(d, 0) > 0
+                uv = val.get(d, 0) if u_pr else 0
+                cv = calc.get(d)
+                h = min(h, _copies_of_amount(v, True, d in rd, rd.get(d, 0), uv, res.get(d, 0), u_pr or d in res,
+                                             cv is not None and u_pr and uv >= cv, eq3, eq, cap))
+            if h < best[k][0]:
+                best[k] = (h, t)
+    copies = [b[0] for b in best]
+    return next((k for k in range(m) if copies[k] >= int(want)), -1), copies, [b[1] for b in best]
+
+
 # ---- forecast, for gangs (kt_forecast_gangs_launch), in closed form on a Snapshot ----
 def forecast_gangs_of(snap, member_rows, instants, on_equal=False, ctx=None):
     """kt_forecast_gangs_launch for one gang, in closed form on a Snapshot (no GPU) -> (first, verdicts [len(instants)], blockers
