@@ -10,7 +10,8 @@ the opposite: one engine lives for days, is fed pod, Throttle and reservation ev
     (``state[row] -> pod kind`` and ``tstate[row] -> throttle kind``, -1 for a deleted row; the stored status and the reserved
     amounts live in the snapshot's own arrays); ``n_thr`` and ``n_pods`` stay the highest row ever used + 1; the namespace side is
     ``nstate[row] -> namespace kind`` ("gone": no object) with ``ns_valid`` / ``ns_label_*`` arrays of the mirror's own;
-  * ``battery``: everything the query family answers for one fixed question set, for both ``on_equal`` values;
+  * ``battery``: everything the query family answers for one fixed question set, for both ``on_equal`` values — the headroom
+    forecast (first, copies and limiting at every instant of ``INSTANTS``) and, over pages, the paged gang headroom included;
   * ``model_battery``: the same dictionary from the host models (``paging.*_of``) and the oracle, on the mirror alone;
   * ``Life``: the events, applied to the mirror and — when it has engines — to the live engine(s), and ``hold()``: live against a twin
     loaded fresh from the mirror (which side moved?), live against the models (who is right?), live against itself (queries are dry);
@@ -35,6 +36,7 @@ INSTANTS = FR.instants_under_test()
 B = FR.BOUNDARY_TEXTS
 CAP = 24
 CAPS = (CAP, E.HEADROOM_MAX_CAP)
+WANT = 3  # the headroom forecast's `want`: `first` is the first instant with at least so many copies
 P_CAP, T_CAP = 64, 24  # capacities of the live engine: above what the cluster starts with
 STATUS_BITS = S.THR_CALC_AT_NONZERO | S.THR_THROTTLED_POD
 NS = ("ns0", "ns1", "ns2")
@@ -84,7 +86,8 @@ def _cnt(n, **kw):
 
 
 class Pool:
-    """The cluster as kinds: ``pod[name]`` / ``thr[name]`` are rows of the pool's snapshots ``snaps`` (one per page)."""
+    """The cluster as kinds: ``pod[name]`` / ``thr[name]`` are rows of the pool's snapshots ``snaps`` (one per page).  With
+    ``wide=True`` the names sort into cpu, the GPU name and r00..r13 on page 0, r14..r16 and memory on page 1."""
 
     def __init__(self, wide=False):
         cs = ClusterState()
@@ -121,6 +124,7 @@ class Pool:
         pod("small", "ns0", {"app": "job", "team": "y"}, {"cpu": "50m", "memory": "32Mi"})       # (an upsert's other requests)
         pod("neg", "ns0", {"app": "web", "team": "y"}, {"cpu": "300m", "memory": "64Mi"}, True)  # (cpu made negative below)
         pod("0wz-r", "ns0", {"app": "web", "team": "z"}, {"cpu": "100m", "memory": "64Mi"}, True)
+        pod("neg1", "ns1", {"app": "web", "team": "y"}, {"cpu": "300m", "memory": "128Mi"}, True)  # (memory made negative below)
 
         win = lambda b, e, th: [{"begin": B[b], "end": B[e], "threshold": th}]
         x = {name: "3" for name in EXTRA[-4:]} if wide else {}  # (c-web's names of both pages)
@@ -151,6 +155,14 @@ class Pool:
         thr("c-none", [{"app": "none"}], _cnt(0))                                                   # blocks the pod nobody blocked
         thr("c-y", [{"team": "y"}], _cnt(5))                                                        # a freed row's next tenant
         thr("ns2/t-web@db", [{"app": "db"}], _rr(mem="256Mi"), ns="ns2")                           # (an unrelated selector change)
+        # the web throttles with room: what the running web pods use stays well below, on the names of both pages (the first of
+        # c-web's four names lies on page 0 and leaves more room than the three of the last page)
+        room = dict({EXTRA[-4]: "40"}, **{name: "17" for name in EXTRA[-3:]}) if wide else {}
+        thr("ns0/t-web@room", [{"app": "web"}], _cnt(20), ns="ns0")
+        thr("ns1/t-web@room", [{"app": "web"}], _rr(cpu="10", mem="2Gi"), ns="ns1")
+        thr("ns1/t-web@room-mem", [{"app": "web"}], _rr(cpu="10", mem="768Mi"), ns="ns1")          # ... and memory edited
+        thr("c-web@room", [{"app": "web"}], {"resourceRequests": dict(_rr(cpu="20")["resourceRequests"], **room)},
+            overrides=win(3, 6, _cnt(20, cpu="10")))
         self.cs = cs
         pages = cs.build_pages()
         assert len(pages) == (2 if wide else 1), len(pages)
@@ -158,9 +170,10 @@ class Pool:
         self.dims = [b.dims for b in pages]
         self.scales = [b.scales for b in pages]
         for s, dims in zip(self.snaps, self.dims):
-            if "cpu" in dims:  # the one pod with a negative request
-                k = int(s.pod_ctr_off[self.pod["neg"]])
-                s.ctr_req[k, dims["cpu"]] = -s.ctr_req[k, dims["cpu"]]
+            for kind, name in (("neg", "cpu"), ("neg1", "memory")):  # the pods with a negative request, each on one page alone
+                if name in dims:
+                    k = int(s.pod_ctr_off[self.pod[kind]])
+                    s.ctr_req[k, dims[name]] = -s.ctr_req[k, dims[name]]
         # namespace kinds, per page: the label list the pool gives each row, and the ids of env=prod / env=dev
         self.ns_lists, self.env = [], []
         for s in self.snaps:
@@ -185,7 +198,7 @@ class Pool:
     # the pods the cluster starts with: row r holds PLACEMENT[r]
     @property
     def placement(self):
-        skip = {"neg", "small"}
+        skip = {"neg", "neg1", "small"}
         return [name for name in self.pod if name not in skip]
 
     def dim(self, name):
@@ -207,7 +220,10 @@ def pool(wide=False):
 
 # ---- the question set ------------------------------------------------------------------------------------------------------
 class Questions:
-    """Fixed ROWS (events change what they hold): 8 single pods, 4 gangs of 1, 2, 3 and 5 members, 10 candidates."""
+    """Fixed ROWS (events change what they hold): 8 single pods, 4 gangs of 1, 2, 3 and 5 members, 10 candidates; the wide pool has
+    a fifth gang (``WEB_GANG``) of two pending web pods, whose names of the last page decide its headroom once the web throttles
+    leave room."""
+    WEB_GANG = 4
 
     def __init__(self, pl):
         r = {name: i for i, name in enumerate(pl.placement)}
@@ -217,6 +233,8 @@ class Questions:
                  ["1jx-p", "zero"],                                # both meet c-x, which has room for one: rolled back
                  ["1jy-p", "0dy-p", "2jy-p"],                      # members that meet different throttles: admitted
                  ["0jy-p", "1wy-p", "2wy-p", "ghost-p", "1dy-p"]]  # a member in the namespace without an object
+        if len(pl.snaps) > 1:
+            gangs.append(["1wy-p", "0wy-p"])                       # web pods alone: they carry the names of the last page
         self.gang_rows = np.array([r[n] for g in gangs for n in g], np.int64)
         self.gang_off = np.cumsum([0] + [len(g) for g in gangs]).astype(np.int64)
         self.cands = np.array([r[n] for n in ("1jx-r", "0jy-r", "0jx-r", "0wx-r", "0wy-r", "2dx-r", "1wx-r", "1wy-r", "2wx-r", "0dx-r")],
@@ -463,6 +481,7 @@ def battery(eng, q, now=NOW):
         for cap in CAPS:
             out["headroom", cap, eq] = _answer(lambda: eng.headroom(rows=q.pods, cap=cap, on_equal=eq))
             out["headroom_gangs", cap, eq] = _answer(lambda: eng.headroom_gangs(q.gang_rows, q.gang_off, cap=cap, on_equal=eq))
+            out["headroom_forecast", cap, eq] = _answer(lambda: eng.headroom_forecast(q.pods, INSTANTS, cap=cap, want=WANT, on_equal=eq))
         for rep in (False, True):
             out["preempt", rep, eq] = _answer(lambda: eng.preempt(q.pods, q.cands, now, on_equal=eq, reprieve=rep))
             out["preempt_gangs", rep, eq] = _answer(lambda: eng.preempt_gangs(q.gang_rows, q.gang_off, q.cands, now, on_equal=eq, reprieve=rep))
@@ -482,6 +501,7 @@ def _paged_battery(engs, q, now):
         out["admit_gangs", eq] = _answer(lambda: E.paged_admit_gangs(engs, q.gang_rows, q.gang_off, on_equal=eq, commit=False))
         for cap in CAPS:
             out["headroom", cap, eq] = _answer(lambda: E.paged_headroom(engs, q.pods, cap, on_equal=eq))
+            out["headroom_gangs", cap, eq] = _answer(lambda: E.paged_headroom_gangs(engs, q.gang_rows, q.gang_off, cap, on_equal=eq))
         for rep in (False, True):
             out["preempt", rep, eq] = _answer(lambda: E.paged_preempt(engs, q.pods, q.cands, now, on_equal=eq, reprieve=rep))
             out["preempt_gangs", rep, eq] = _answer(lambda: E.paged_preempt_gangs(engs, q.gang_rows, q.gang_off, q.cands, now, on_equal=eq, reprieve=rep))
@@ -540,6 +560,10 @@ def model_battery(mirror, q, oracle_mod, now=NOW):
             h = [paging.headroom_gangs_of(snap, q.members(g), cap, eq) for g in range(ng)]
             out["headroom_gangs", cap, eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32),
                                               _queue_pos([x[2] for x in h], q))
+            a = [paging.headroom_forecast_of(snap, p, INSTANTS, cap, WANT, eq, ctx=ctx) for p in q.pods]
+            out["headroom_forecast", cap, eq] = (np.array([x[0] for x in a], np.int64),
+                                                 np.array([x[1] for x in a], np.int64).reshape(len(a), len(INSTANTS)),
+                                                 np.array([x[2] for x in a], np.int32).reshape(len(a), len(INSTANTS)))
         for rep in (False, True):
             a = [paging.preempt_of(snap, p, q.cands, now, eq, ctx=ctx, reprieve=rep) for p in q.pods]
             out["preempt", rep, eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8).reshape(len(a), m))
@@ -568,6 +592,9 @@ def _paged_model_battery(mirror, q, oracle_mod, now):
         for cap in CAPS:
             h = [paging.headroom_of(pages, p, cap, eq) for p in q.pods]
             out["headroom", cap, eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32))
+            h = [paging.paged_headroom_gangs_of(snaps, q.members(g), cap, eq) for g in range(ng)]
+            out["headroom_gangs", cap, eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32),
+                                              _queue_pos([x[2] for x in h], q))
         for rep in (False, True):
             a = [paging.paged_preempt_of(snaps, p, q.cands, now, eq, reprieve=rep, ctx=ctx) for p in q.pods]
             out["preempt", rep, eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8).reshape(len(a), m))
@@ -583,6 +610,16 @@ def _paged_model_battery(mirror, q, oracle_mod, now):
         inst = paging.override_instants_of(s, NOW, FR.BEYOND)
         out["override_instants", k] = ([(int(a), int(b)) for a, b in inst], len(inst))
         out["reserved", k] = _amounts(s.thr_reserved, s.n_thr)
+    return out
+
+
+def page_zero_alone(mirror, q, cap=CAP):
+    """What page 0 alone would answer for the gangs' headroom (``headroom_gangs_of`` on its snapshot), shaped as the battery's
+    ``("headroom_gangs", cap, eq)`` -> {eq: answer}.  Where the paged answer differs from it, a name of a later page decides."""
+    out = {}
+    for eq in (False, True):
+        h = [paging.headroom_gangs_of(mirror.snaps[0], q.members(g), cap, eq) for g in range(len(q.gang_off) - 1)]
+        out[eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32), _queue_pos([x[2] for x in h], q))
     return out
 
 
@@ -627,6 +664,7 @@ class Life:
         self.engines = []
         self.held = []
         self.live_held = []
+        self.alone = []  # a paged life: [(step name, page_zero_alone)]
         self.soft = None  # a list: hold() collects what differs there and goes on (a survey of a whole life)
         names = self.pl.placement
         self.mirror.put_throttles(range(len(self.pl.initial)), self.pl.initial)
@@ -770,6 +808,8 @@ class Life:
         ``live_refuses``: ... on the live engine only — the twin serves them and is held to the models."""
         model = model_battery(self.mirror, self.q, self.o)
         self.held.append((step, model))
+        if len(self.mirror.snaps) > 1:
+            self.alone.append((step, page_zero_alone(self.mirror, self.q)))
         if not self.engines:
             return model
         target = self.engines if len(self.engines) > 1 else self.eng
@@ -935,6 +975,48 @@ def life_two_pages(life):
     life.hold("a reconcile behind them")
 
 
+PAGE_ONE_STEPS = ("set_reserved on page 1 takes a copy of the web gang", "a threshold edit of a last-page name, reconciled",
+                  "a pod event changes a member's request of a last-page name", "set_reserved on page 0: the decider moves to page 0",
+                  "set_reserved on page 1: the decider moves back to page 1")
+
+
+def life_page_one_decides(life):
+    """The web gang (``Questions.WEB_GANG``) on web throttles that leave room: its headroom is decided by names of the last page,
+    and every step named in PAGE_ONE_STEPS moves it (tests/test_lived_engine_cpu.py asserts that on the models)."""
+    t = {name: i for i, name in enumerate(life.pl.initial)}
+    r = life.row
+    start(life)
+    life.upsert_throttles([t["ns0/t-web"], t["c-web"], t["ns1/t-web"]], ["ns0/t-web@room", "c-web@room", "ns1/t-web@room"])
+    life.reconcile()
+    life.hold("the web throttles leave room, reconciled: page 1 decides the web gang")
+    life.set_reserved(t["c-web"], ["1wx-p", "0wx-p"], only_page=1)      # two pods' worth of c-web's names of the last page
+    life.hold(PAGE_ONE_STEPS[0])
+    life.upsert_throttles([t["ns1/t-web"]], ["ns1/t-web@room-mem"])     # memory is a name of the last page: ns1/t-web limits now
+    life.reconcile()
+    life.hold(PAGE_ONE_STEPS[1])
+    life.upsert_pods([r("1wy-p")], ["0wy-p"], ns=[1])                    # same namespace, labels and cpu; half the memory
+    life.hold(PAGE_ONE_STEPS[2])
+    life.set_reserved(t["ns0/t-web"], ["0wx-p"] * 14, only_page=0)      # the pod count is page 0's
+    life.hold(PAGE_ONE_STEPS[3])
+    life.set_reserved(t["c-web"], ["1wx-p", "0wx-p"] * 5, only_page=1)
+    life.hold(PAGE_ONE_STEPS[4])
+
+
+def life_negative_on_page_one(life):
+    """life_negative_came_and_went on two pages: the negative request is of a name of the last page, so page 1's engine alone is
+    fed one — the paged gang headroom is refused as a whole."""
+    start(life)
+    n = life.mirror.n_pods
+    life.upsert_pods([n], ["neg1"])
+    life.hold("a pod with a negative request of a last-page name is there", refused=("headroom_gangs",))
+    life.reconcile()
+    life.hold("... and has been reconciled", refused=("headroom_gangs",))
+    life.delete_pods([n])
+    life.hold("the pod with the negative request is gone", live_refuses=("headroom_gangs",))
+    life.reconcile()
+    life.hold("... and a reconcile behind it", live_refuses=("headroom_gangs",))
+
+
 class _Gaps:
     """compiles() of every page's engine from one hold to the next: a gap that holds namespace events (or a pod of a namespace row
     the program was not compiled for) costs exactly ONE compile, however many events it holds; a gap without events costs none."""
@@ -1051,7 +1133,8 @@ LIVES = {"pod_events": life_pod_events, "threshold_and_override_events": life_th
          "namespace_arrives_after_its_pods": life_namespace_arrives_after_its_pods,
          "namespace_events_among_the_others": life_namespace_events_among_the_others}
 # the lives of a cluster with twenty resource names: two pages, every event reaches both
-WIDE_LIVES = {"two_pages": life_two_pages, "namespace_labels_wide": life_namespace_labels,
+WIDE_LIVES = {"two_pages": life_two_pages, "page_one_decides": life_page_one_decides,
+              "negative_on_page_one": life_negative_on_page_one, "namespace_labels_wide": life_namespace_labels,
               "namespace_deleted_and_back_wide": life_namespace_deleted_and_back}
 
 

@@ -6,8 +6,9 @@ stored status, Namespace objects), reconciled, and after every further event hel
   * a twin loaded fresh from the mirror at that moment — every array of the whole battery bit for bit (which side moved?),
   * the host models ``paging.*_of`` and the oracle on the mirror (who is right?),
   * itself: a second run of the battery equals the first (queries are dry).
-The battery is check, dry admit, dry admit_gangs, headroom, headroom_gangs, preempt and preempt_gangs with and without reprieve,
-forecast, forecast_gangs, override_instants and fetch_reserved, for both ``on_equal`` values.  tests/test_lived_engine_cpu.py shows
+The battery is check, dry admit, dry admit_gangs, headroom, headroom_gangs, headroom_forecast, preempt and preempt_gangs with and
+without reprieve, forecast, forecast_gangs, override_instants and fetch_reserved, for both ``on_equal`` values; on two pages the
+paged entry points, the paged gang headroom among them.  tests/test_lived_engine_cpu.py shows
 on the models alone that every event of every life moves an answer and that the lives show every kind of outcome.  No tolerance."""
 import numpy as np
 import pytest
@@ -52,6 +53,34 @@ def test_reservations_survive(oracle_mod):
 
 def test_two_pages_live(oracle_mod):
     assert len(live(LE.life_two_pages, oracle_mod, wide=True)) == 7
+
+
+def test_page_one_decides_live(oracle_mod):
+    """The web gang's paged headroom is decided by names of the last page: a reserved row, a threshold and a member's request of
+    page 1 move it, and the deciding (throttle, page) pair goes to page 0 and back (tests/test_lived_engine_cpu.py asserts all of
+    that on the models; here the live page engines are held to twin and models at every step)."""
+    assert len(live(LE.life_page_one_decides, oracle_mod, wide=True)) == 7
+
+
+def test_a_negative_request_on_page_one(oracle_mod):
+    """Only page 1's engine has been fed a negative request.  kt_paged_headroom_gangs answers KT_ERR_UNSUPPORTED when ANY page has:
+    on live and twin while the pod is there, on the live engines alone once it has gone; every other paged answer equals twin and
+    models throughout.  Page 0's engine alone still serves its own gang headroom."""
+    life = LE.Life(oracle_mod, gpu=True, wide=True)
+    try:
+        LE.life_negative_on_page_one(life)
+        assert len(life.held) == 5
+        q = life.q
+        with pytest.raises(E.EngineError) as err:
+            E.paged_headroom_gangs(life.engines, q.gang_rows, q.gang_off, LE.CAP)
+        assert err.value.code == -7, err.value
+        got = LE._answer(lambda: life.engines[0].headroom_gangs(q.gang_rows, q.gang_off, cap=LE.CAP))
+        assert LE.same(got, life.alone[-1][1][False]), f"page 0's engine alone: {got}"
+        with pytest.raises(E.EngineError) as err:
+            life.engines[1].headroom_gangs(q.gang_rows, q.gang_off, cap=LE.CAP)
+        assert err.value.code == -7 and "has been fed a negative request" in str(err.value), err.value
+    finally:
+        life.close()
 
 
 def test_namespace_labels(oracle_mod):
@@ -206,8 +235,8 @@ def _code(f):
 
 def test_pending_results_across_a_namespace_event(oracle_mod):
     """kt_engine.h: a result that is pending when a namespace event arrives is not touched by it — "its fetch returns either the
-    exact answer of the state at its launch or KT_ERR_NOT_READY, never anything else".  A check, a reconcile report and a forecast
-    are each launched in front of a namespace event that moves their answer, and fetched behind it."""
+    exact answer of the state at its launch or KT_ERR_NOT_READY, never anything else".  A check, a reconcile report, a forecast
+    and a headroom forecast are each launched in front of a namespace event that moves their answer, and fetched behind it."""
     life = LE.Life(oracle_mod, gpu=True)
     try:
         LE.start(life)
@@ -251,6 +280,14 @@ def test_pending_results_across_a_namespace_event(oracle_mod):
         fetched("forecast", lambda: eng.forecast_fetch(n, k), lambda got: LE.same(LE._answer(lambda: got), at_start["forecast", False]))
         gone = life.hold("ns1 is deleted behind a pending forecast")
         assert LE.differences(gone, at_start, [("forecast", False)])
+
+        key = ("headroom_forecast", LE.CAP, False)
+        eng.headroom_forecast_launch(q.pods, LE.INSTANTS, LE.CAP, want=LE.WANT)
+        life.upsert_namespaces([1], ["ns1"])
+        fetched("headroom forecast", lambda: eng.headroom_forecast_fetch(n, k), lambda got: LE.same(LE._answer(lambda: got), gone[key]))
+        back = life.hold("ns1 returns behind a pending headroom forecast")
+        assert LE.differences(back, gone, [key]), "the event moves the headroom forecast's answer"
+        LE.assert_same(at_start, back, "the battery of the start")
         print("pending across a namespace event:", outcome)
     finally:
         life.close()
@@ -260,7 +297,8 @@ def test_pending_results_across_queries(oracle_mod):
     """What kt_engine.h promises about results that are pending while another query is launched, on an engine that has had events:
     a pending forecast and a pending preempt result are independent; a preempt's dry finalize drops a pending reconcile report; the
     one headroom slot and the one preempt slot answer KT_ERR_NOT_READY to the other kind's fetch; a pending kt_check_launch is
-    dropped by every query that uses the check slot; result buffers regrow under an unfetched smaller launch."""
+    dropped by every query that uses the check slot; result buffers regrow under an unfetched smaller launch.  The headroom
+    forecast is the forecast result's third kind."""
     life = LE.Life(oracle_mod, gpu=True)
     try:
         LE.start(life)
@@ -297,10 +335,40 @@ def test_pending_results_across_queries(oracle_mod):
         eng.forecast_gangs_launch(q.gang_rows, q.gang_off, LE.INSTANTS)
         assert _code(lambda: eng.forecast_fetch(n, k)) == -5
         assert same(eng.forecast_gangs_fetch(ng, k), ("forecast_gangs", False))
+        # the headroom forecast is the forecast result's third kind
+        hf = ("headroom_forecast", LE.CAP, False)
+        hf_launch = lambda: eng.headroom_forecast_launch(q.pods, LE.INSTANTS, LE.CAP, want=LE.WANT)
+        hf_launch()
+        assert _code(lambda: eng.forecast_fetch(n, k)) == -5 and _code(lambda: eng.forecast_gangs_fetch(ng, k)) == -5
+        assert same(eng.headroom_forecast_fetch(n, k), hf)
+        eng.forecast_launch(q.pods, LE.INSTANTS)
+        assert _code(lambda: eng.headroom_forecast_fetch(n, k)) == -5
+        assert same(eng.forecast_fetch(n, k), ("forecast", False))
+        eng.forecast_gangs_launch(q.gang_rows, q.gang_off, LE.INSTANTS)
+        assert _code(lambda: eng.headroom_forecast_fetch(n, k)) == -5
+        assert same(eng.forecast_gangs_fetch(ng, k), ("forecast_gangs", False))
+        # ... a pending preempt result of either kind stays fetchable behind it, and it behind a preempt launch
+        eng.preempt_launch(q.pods, q.cands, NOW)
+        hf_launch()
+        assert same(eng.preempt_fetch(n, m), ("preempt", False, False)) and same(eng.headroom_forecast_fetch(n, k), hf)
+        eng.preempt_gangs_launch(q.gang_rows, q.gang_off, q.cands, NOW)
+        hf_launch()
+        assert same(eng.preempt_gangs_fetch(ng, m), ("preempt_gangs", False, False)) and same(eng.headroom_forecast_fetch(n, k), hf)
+        hf_launch()
+        eng.preempt_launch(q.pods, q.cands, NOW)
+        assert same(eng.headroom_forecast_fetch(n, k), hf) and same(eng.preempt_fetch(n, m), ("preempt", False, False))
+        hf_launch()
+        eng.preempt_gangs_launch(q.gang_rows, q.gang_off, q.cands, NOW)
+        assert same(eng.headroom_forecast_fetch(n, k), hf) and same(eng.preempt_gangs_fetch(ng, m), ("preempt_gangs", False, False))
+        # ... and its dry finalize drops a pending reconcile report
+        eng.reconcile_launch(NOW, apply=False)
+        eng.headroom_forecast(q.pods, LE.INSTANTS, cap=LE.CAP, want=LE.WANT)
+        assert _code(lambda: eng.reconcile_fetch()) == -5
         # a pending kt_check_launch (with the status matrix: not the few-pod path) is gone behind every query that uses the slot
         for ask in (lambda: eng.headroom(rows=q.pods, cap=LE.CAP), lambda: eng.headroom_gangs(q.gang_rows, q.gang_off, cap=LE.CAP),
                     lambda: eng.preempt(q.pods, q.cands, NOW), lambda: eng.preempt_gangs(q.gang_rows, q.gang_off, q.cands, NOW),
-                    lambda: eng.forecast(q.pods, LE.INSTANTS), lambda: eng.forecast_gangs(q.gang_rows, q.gang_off, LE.INSTANTS)):
+                    lambda: eng.forecast(q.pods, LE.INSTANTS), lambda: eng.forecast_gangs(q.gang_rows, q.gang_off, LE.INSTANTS),
+                    lambda: eng.headroom_forecast(q.pods, LE.INSTANTS, cap=LE.CAP, want=LE.WANT)):
             eng.check_launch(len(q.gang_rows), q.gang_rows, want_status=True)
             ask()
             assert _code(lambda: eng.check_fetch(len(q.gang_rows), want_status=True)) == -5
@@ -327,6 +395,21 @@ def test_pending_results_across_queries(oracle_mod):
         eng.headroom_gangs_launch(q.members(0), [0, 1], LE.CAP)
         eng.headroom_gangs_launch(q.gang_rows, q.gang_off, LE.CAP)
         assert same(eng.headroom_gangs_fetch(ng), ("headroom_gangs", LE.CAP, False))
+        # ... the headroom forecast's too: 1 pod x 2 instants, never fetched, then every pod x 70 instants (from position 64 on a
+        # lane owns a second cell of a pod's row of the copies buffer, which the kernel also uses as scratch)
+        last = LE.INSTANTS[-1]
+        long = list(LE.INSTANTS) + [(int(last[0]) + 3600 * (i + 1), i) for i in range(70 - k)]
+        assert len(long) == 70 and [(int(a), int(b)) for a, b in long] == sorted({(int(a), int(b)) for a, b in long})
+        snap = life.mirror.snap
+        ctx = LE.paging.preempt_context(snap, NOW)
+        a = [LE.paging.headroom_forecast_of(snap, p, long, LE.CAP, LE.WANT, False, ctx=ctx) for p in q.pods]
+        model = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.int64).reshape(n, 70),
+                 np.array([x[2] for x in a], np.int32).reshape(n, 70))
+        eng.headroom_forecast_launch(q.pods[:1], LE.INSTANTS[:2], LE.CAP, want=LE.WANT)
+        eng.headroom_forecast_launch(q.pods, long, LE.CAP, want=LE.WANT)
+        got = LE._answer(lambda: eng.headroom_forecast_fetch(n, 70))
+        assert LE.same(got, model), f"70 instants behind an unfetched 1 x 2 launch:\n  {got}\n  {model}"
+        assert LE.same(tuple(x[:, :k] if x.ndim == 2 else x for x in got[1:]), tuple(want[hf][1:])), "... its first instants are the battery's"
         life.hold("behind all of it the battery is what it was")
     finally:
         life.close()
