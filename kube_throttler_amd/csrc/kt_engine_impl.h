@@ -4,7 +4,8 @@
 //   kt_engine_compile.cpp    throttles + namespaces -> selector program + index (compile_program)
 //   kt_engine_feed.cpp       state feed: namespaces, pods, throttles, status, reserved amounts, snapshots
 //   kt_engine_reconcile.cpp  aggregate / exchange (kt_comm_*) / finalize and their fetches
-//   kt_engine_check.cpp      PreFilter: sweeps, few-pod checks, admission queues, pages
+//   kt_engine_check.cpp      PreFilter: sweeps, few-pod checks, the match cache, admission queues, pages
+//   kt_engine_queries.cpp    admission queries: headroom, preempt, forecast, headroom forecast; their gang and paged forms
 //   kt_engine_views.cpp      the scan views of the aggregate and the sweep: built, patched by pod events, settled
 #pragma once
 #include <hip/hip_runtime.h>
@@ -673,6 +674,18 @@ KT_INTERNAL void reqs_from_pool(const kt_reqs& pool, uint32_t b, uint32_t e_, st
 // (kt_engine_check.cpp) the program's match cache, current for a scan enqueued on s behind this call — mc.mw == nullptr: none;
 // the countable view's planes (ScanView::mx), where they are valid, are written through by the same launch
 KT_INTERNAL int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchCacheArgs& mc);
+// (kt_engine_check.cpp) what the admission queues there and the queries of kt_engine_queries.cpp share: the check behind every
+// one of them (allow_small: false for callers that go on working on the device-side rows / summaries), the gang offsets'
+// defects, and the steps of a call over several page engines
+KT_INTERNAL int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags, hipStream_t s,
+                                        bool allow_small = true);
+KT_INTERNAL int32_t gangs_valid(kt_engine* e, int64_t n, int64_t n_gangs, const int64_t* gang_off);
+typedef std::vector<std::unique_ptr<LaunchLock>> PageLocks;
+KT_INTERNAL int32_t paged_lock(const char* what, kt_engine* const* pages, int32_t n_pages, int64_t n, PageLocks& locks);
+KT_INTERNAL int32_t paged_same_cluster(const char* what, kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows);
+KT_INTERNAL int32_t paged_order(kt_engine* const* pages, int32_t n_pages, hipStream_t* s);
+// page e as kt_admit and the query kernels read it
+inline kt::AdmitPage admit_page_of(const kt_engine* e) { return kt::AdmitPage{e->pods.flags, e->pods.req, e->tt, e->D, e->pods.DS, 0u, 0u, 0u}; }
 // a pod event batch no larger than this is applied to the scan views / queued for the match cache in place
 constexpr int64_t kPatchBatchMax = 65536;
 // (kt_engine_views.cpp)
