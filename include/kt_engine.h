@@ -675,7 +675,7 @@ int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_firs
  *      forecast result as its third kind: a later forecast launch of any kind replaces it; kt_forecast_fetch and
  *      kt_forecast_gangs_fetch after this launch answer KT_ERR_NOT_READY, and kt_headroom_forecast_fetch answers it after theirs.
  *      kt_headroom_forecast_fetch synchronises.
- *      Out of scope: more than KT_MAX_DIMS resource names (pages), gangs, several ranks. ------------------------------------ */
+ *      More than KT_MAX_DIMS resource names: kt_paged_headroom_forecast.  Out of scope: gangs, several ranks. --------------- */
 int32_t kt_headroom_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
                                     const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want, void* stream);
 int32_t kt_headroom_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first /* [n], nullable */,
@@ -1011,6 +1011,56 @@ int32_t kt_paged_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_
                                 const int64_t* gang_off, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal,
                                 int64_t* out_first /* [n_gangs], nullable */, uint8_t* out_verdicts /* [n_gangs][n_inst], nullable */,
                                 int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
+/* kt_headroom_forecast_launch + kt_headroom_forecast_fetch over the pages, synchronous: what they return on the cluster of ALL
+ * names.  out_copies[i][k] is the number of leading Success verdicts of a dry kt_paged_admit over [p_i] * cap with R_{t_k} as the
+ * stored status of every page (every valid and responsible throttle reconciled at t_k on every page, on the state as it is now);
+ * out_limiting[i][k] is the lowest throttle row whose COMBINED status is not KT_STATUS_NOT_THROTTLED in the row the first refused
+ * copy gets, and -1 where all `cap` copies are admitted; out_first[i] is the smallest k with out_copies[i][k] >= want, or
+ * KT_FORECAST_NONE.  A pod whose PreFilter is an Error on page 0, or whose row is invalid: 0 / -1 / KT_FORECAST_NONE.  A pod no
+ * throttle affects: cap / -1 / 0.  Negative requests are served, as kt_headroom_launch and kt_paged_headroom serve them.
+ * The answer is NOT a combination of existing calls.  The minimum of the pages' own kt_headroom_forecast_launch answers is wrong:
+ * status.calculatedThreshold is compared and replaced as a whole, so a page that holds nothing the pod requests can replace the
+ * threshold for the pages that do, at some instants and not at others.  kt_paged_headroom once per instant would need the status
+ * applied at each instant: not a dry run.
+ * The rules about pages are kt_paged_forecast's, word for word: the affecting throttles come from ONE check of page 0; `stored` and
+ * `calc_at_any` are ORs over the pages; `differs` is the OR over EVERY page (pages none of whose names the pod requests included;
+ * page 0 adds the count comparison); the throttle reads status.calculatedThreshold on every page iff calc_at_any || differs, else
+ * spec.threshold on every page; status.throttled is IsThrottled(used, true) against the calculated threshold either way.  The
+ * rules about headroom are kt_paged_headroom's: the pod count is judged on page 0 only; each page judges its own names against its
+ * own reserved row and presence bits; the throttle's number is the minimum over the count and every needed name of every page;
+ * the answer is the lexicographic minimum of (copies, throttle row) over the affecting throttles.
+ * Identities:
+ *   (P1) n_pages == 1 returns byte for byte what kt_headroom_forecast_launch + kt_headroom_forecast_fetch return on that engine.
+ *   (I1) with cap == want == 1, out_copies[i][k] == 1 exactly where kt_paged_forecast reports KT_VERDICT_SUCCESS and out_first is
+ *        byte for byte kt_paged_forecast's; an Error verdict is 0 copies and limiting -1, a Block verdict limiting >= 0.
+ *   (I2) with inst = [t] on pages whose last action was kt_paged_reconcile(t, KT_RECONCILE_APPLY) and whose stored calculatedAt
+ *        flags then agree across the pages for every affecting throttle, out_copies[:][0] and out_limiting[:][0] are byte for byte
+ *        kt_paged_headroom's with the same cap and on_equal.  Where the flags disagree this call follows kt_paged_forecast (the
+ *        throttle has been replaced once some page says so: calc_at_any) and kt_paged_headroom reads each page's own flag.
+ *   (I3) the call is a dry run: stored status, reserved amounts and a pending kt_aggregate_launch's sums are unchanged on every page.
+ * On page 0's stream, in order: that check; for every page its dense aggregate and its dry finalize at t_0; the copy of the page
+ * descriptors; one launch of kt_headroom_forecast_paged (csrc/kt_kernels_headroom_forecast_paged.hip: one wave per pod, lane =
+ * instant position; `differs` and the two running minima against the calculated and the spec threshold kept across the pages, one
+ * walk of the overrides per page and block of 64 instants); the copies out.  All three outputs are nullable.
+ * Refused before anything is launched, and before any page's check slot, reconcile report or result buffer is touched, in this
+ * order: a missing page array, n_pages < 1, a NULL page, n < 0 (KT_ERR_INVALID_ARGUMENT); the instants as kt_forecast_launch
+ * refuses them and a missing pod_rows with n > 0 (KT_ERR_INVALID_ARGUMENT); cap outside [1, KT_HEADROOM_MAX_CAP], then want outside
+ * [1, cap] (KT_ERR_INVALID_ARGUMENT); what kt_paged_admit refuses about the page set and the rows (different throttle-row counts,
+ * an engine named twice: KT_ERR_INVALID_ARGUMENT; different devices: KT_ERR_UNSUPPORTED; a pod row outside a page's capacity:
+ * KT_ERR_OUT_OF_RANGE); n x throttle_rows or n x n_inst above 2^31 (KT_ERR_OUT_OF_RANGE); and what kt_forecast_launch refuses about
+ * an engine, asked of every page: a KT_VARIANT_INCREMENTAL engine, an exchange world above 1, a `used` wider than int64
+ * (KT_ERR_UNSUPPORTED) — as in kt_paged_forecast, the one thing that may run first is a page's kernel that sums the |requests|.
+ * n == 0 is KT_OK and launches nothing.  Locking and ordering are kt_paged_admit's.
+ * Slots: kt_paged_forecast's.  The call uses page 0's check slot and page 0's forecast result buffers, grown only once the stream
+ * of an unfetched launch has drained, and hands the results out: afterwards no forecast result of any kind is pending on page 0
+ * (kt_forecast_fetch, kt_forecast_gangs_fetch and kt_headroom_forecast_fetch answer KT_ERR_NOT_READY) while a pending preempt
+ * result of page 0 stays fetchable; every page's pending reconcile report is dropped.  A device error after the first launch is
+ * returned once the stream has drained; no page keeps a pending result.
+ * Out of scope: gangs, several ranks. */
+int32_t kt_paged_headroom_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_inst,
+                                   const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want,
+                                   int64_t* out_first /* [n], nullable */, int64_t* out_copies /* [n][n_inst], nullable */,
+                                   int32_t* out_limiting /* [n][n_inst], nullable */);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

@@ -410,7 +410,8 @@ func (e *Engine) Headroom(rows []int64, onEqual bool, cap int64) (copies []int64
 // (kt_headroom_forecast_launch + kt_headroom_forecast_fetch).  copies[i*len(instS)+k] in [0, cap], limiting alike (-1: all cap
 // copies fit, or the pod's PreFilter is an error — then copies is 0), first[i] the smallest k with at least want copies or -1.
 // A dry run: stored status and reserved amounts stay.  cap in [1, 2^31-1], want in [1, cap].  Launch and fetch run under e.mu,
-// like every other user of the check slot.  One engine, single pods.  Not compiled in this repository (no Go toolchain in its build).
+// like every other user of the check slot.  Single pods; over pages of resource names: kt_paged_headroom_forecast (not wrapped here).  Not
+// compiled in this repository (no Go toolchain in its build).
 func (e *Engine) HeadroomForecast(rows, instS []int64, instNs []int32, onEqual bool, cap, want int64) (first, copies []int64, limiting []int32, err error) {
 	e.mu.Lock() // the check slot is one per engine: see mu
 	defer e.mu.Unlock()

@@ -118,6 +118,12 @@ static int32_t cap_in_range(kt_engine* e, const char* what, int64_t cap) {
   return e->fail(KT_ERR_INVALID_ARGUMENT, "%s: cap = %lld, not in [1, %d]", what, (long long)cap, KT_HEADROOM_MAX_CAP);
 }
 
+// the copies a headroom forecast's `first` asks for
+static int32_t want_in_range(kt_engine* e, const char* what, int64_t want, int64_t cap) {
+  if (want >= 1 && want <= cap) return KT_OK;
+  return e->fail(KT_ERR_INVALID_ARGUMENT, "%s: want = %lld, not in [1, cap = %lld]", what, (long long)want, (long long)cap);
+}
+
 // what every forecast refuses about its instants (and a missing array), in front of everything else
 static int32_t forecast_instants_valid(kt_engine* e, bool rows_missing, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns) {
   if (n_inst < 1) return e->fail(KT_ERR_INVALID_ARGUMENT, "forecast: n_inst = %lld", (long long)n_inst);
@@ -787,8 +793,7 @@ static int32_t headroom_forecast_locked(kt_engine* e, int64_t n, const int64_t* 
   int32_t rc;
   if ((rc = forecast_instants_valid(e, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) != KT_OK) return rc;
   if ((rc = cap_in_range(e, what, cap)) != KT_OK) return rc;
-  if (want < 1 || want > cap)
-    return e->fail(KT_ERR_INVALID_ARGUMENT, "headroom forecast: want = %lld, not in [1, cap = %lld]", (long long)want, (long long)cap);
+  if ((rc = want_in_range(e, what, want, cap)) != KT_OK) return rc;
   if ((rc = rows_in_range(e, what, n, pod_rows)) != KT_OK) return rc;
   if ((rc = matrix_fits(e, what, T, n)) != KT_OK || (rc = verdicts_fit(e, what, n, n_inst, "n", "results")) != KT_OK) return rc;
   if ((rc = serves_dry_reconcile(e, what, -1, kernel)) != KT_OK) return rc;
@@ -1000,6 +1005,58 @@ int32_t kt_paged_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_
       (rc = c.out(out_blocker, e0->d_forecast_blocker.p, ver * 8)) != KT_OK)
     return rc;
   return c.finish(KT_OK);  // (synchronises s; the results have been handed out: no forecast result of either kind is pending on page 0)
+}
+
+// ---------------------------------------------------------------------------------------------------
+// headroom forecast over pages: kt_headroom_forecast_launch + kt_headroom_forecast_fetch on the cluster of all names
+// (kt_kernels_headroom_forecast_paged.hip)
+// ---------------------------------------------------------------------------------------------------
+// kt_paged_forecast's body with cap and want behind the instants, as headroom_forecast_locked orders them, and the copies and
+// limiting rows in the verdict bytes' place.
+int32_t kt_paged_headroom_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_inst,
+                                   const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want,
+                                   int64_t* out_first, int64_t* out_copies, int32_t* out_limiting) {
+  PagedCall c{"paged headroom forecast", pages, n_pages};
+  int32_t rc = c.lock(n);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = c.e0;
+  const char *what = "headroom forecast", *kernel = "kt_headroom_forecast_paged";
+  // ---- refusals: nothing is launched and no slot of any page is touched before the last of them
+  if ((rc = forecast_instants_valid(e0, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) != KT_OK) return rc;
+  if ((rc = cap_in_range(e0, c.what, cap)) != KT_OK || (rc = want_in_range(e0, c.what, want, cap)) != KT_OK) return rc;
+  if ((rc = c.same_cluster(n, pod_rows)) != KT_OK) return rc;  // (the rows are range-checked in place)
+  const int32_t T = e0->thr_rows_hi;
+  if ((rc = matrix_fits(e0, what, T, n)) != KT_OK || (rc = verdicts_fit(e0, what, n, n_inst, "n", "results")) != KT_OK) return rc;
+  for (int32_t k = 0; k < n_pages; ++k)
+    if ((rc = serves_dry_reconcile(pages[k], what, k, kernel)) != KT_OK) return rc;
+  if (n == 0) return KT_OK;  // nothing is launched
+  if ((rc = c.order()) != KT_OK || (rc = ensure_ready(e0, c.s)) != KT_OK) return rc;
+  hipStream_t s = c.s;
+  for (int32_t k = 0; k < n_pages; ++k)  // (before the check slot, a reconcile report or a result buffer of any page is touched)
+    if ((rc = sums_fit_int64(pages[k], what, k, kernel, s)) != KT_OK) return rc;
+  // ---- from here on the call owns page 0's check slot and forecast result and every page's reconcile report
+  e0->forecast_ready = false, e0->forecast_kind = kForecastPods;
+  if ((rc = c.take_preempt_pages()) != KT_OK) return rc;
+  const size_t cells = (size_t)n * (size_t)n_inst, m = (size_t)n_inst;
+  if ((rc = reserve_behind_last_stream(e0, {{e0->d_forecast_first, (size_t)n}, {e0->d_forecast_copies, cells}, {e0->d_forecast_limiting, cells}, {e0->d_forecast_inst_s, m}, {e0->d_forecast_inst_ns, m}})) != KT_OK)
+    return rc;
+  // the instants travel on the same stream, behind an earlier forecast's kernel (the call returns behind finish: the caller's
+  // memory is not referenced afterwards)
+  if ((rc = c.in(e0->d_forecast_inst_s.p, inst_s, m * 8)) != KT_OK || (rc = c.in(e0->d_forecast_inst_ns.p, inst_ns, m * 4)) != KT_OK) return rc;
+  if ((rc = query_check(e0, n, pod_rows, on_equal, s, &kt_engine::preempt_ready)) != KT_OK) return c.finish(rc);
+  if ((rc = reconcile_pages(c, inst_s[0], inst_ns[0])) != KT_OK) return rc;  // (the dry finalize runs at t_0)
+  hipError_t herr = hipSuccess;
+  if (!kt::launch_headroom_forecast_paged(e0->h_preempt_pages.data(), n_pages, (kt::PreemptPage*)e0->d_preempt_pages.p, e0->preempt_pages_ev, n, n_inst,
+                                          e0->d_rows.p, e0->d_forecast_inst_s.p, e0->d_forecast_inst_ns.p, T, on_equal != 0, (uint32_t)cap,
+                                          (uint32_t)want, e0->d_status.p, e0->d_summary.p, e0->d_forecast_first.p, e0->d_forecast_copies.p,
+                                          e0->d_forecast_limiting.p, s, &herr))
+    return c.device_error(herr, "copy of the page descriptors: ");
+  if ((rc = c.launched()) != KT_OK) return rc;
+  e0->last_stream = s;
+  if ((rc = c.out(out_first, e0->d_forecast_first.p, (size_t)n * 8)) != KT_OK || (rc = c.out(out_copies, e0->d_forecast_copies.p, cells * 8)) != KT_OK ||
+      (rc = c.out(out_limiting, e0->d_forecast_limiting.p, cells * 4)) != KT_OK)
+    return rc;
+  return c.finish(KT_OK);  // (synchronises s; the results have been handed out: no forecast result of any kind is pending on page 0)
 }
 
 // Host-only: the instants in (from, until] at which some valid and responsible throttle's CalculateThreshold can change — every

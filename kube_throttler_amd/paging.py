@@ -1249,6 +1249,74 @@ def paged_forecast_of(snaps, pod_row, instants, on_equal=False, ctx=None):
     return next((k for k in range(m) if not fails[k]), -1), verdicts_
 
 
+# ---- headroom forecast over pages (kt_paged_headroom_forecast): the closed form over a list of page snapshots ----
+def paged_headroom_forecast_of(snaps, pod_row, instants, cap, want=1, on_equal=False, ctx=None):
+    """kt_paged_headroom_forecast for one pod, in closed form over the page snapshots (no GPU) -> (first, copies [len(instants)],
+    limiting [len(instants)]): ``headroom_forecast_of`` on the cluster of all names.  The page rules are ``paged_forecast_of``'s —
+    the affecting throttles, the error rows and the pod count are page 0's; the whole-error rule; the whole-threshold rule, with
+    ``differs`` formed over EVERY page — and per amount ``_copies_of_amount`` takes the place of the four steps: the throttle's
+    number at an instant is the minimum over the pod count (page 0) and every requested name of every page, each page against its
+    own reserved row; the answer is the lexicographic minimum of (copies, throttle row).  ``ctx`` is ``paged_preempt_context``'s
+    (any ``now``).  With one page this is ``headroom_forecast_of``."""
+    snap0 = snaps[0]
+    inst = [_instant(t) for t in instants]
+    ctx = paged_preempt_context(snaps, inst[0]) if ctx is None else ctx
+    p, eq, m, cap = int(pod_row), bool(on_equal), len(inst), int(cap)
+    if not (0 <= p < snap0.n_pods) or not int(snap0.pod_flags[p]) & S.POD_VALID:
+        return -1, [0] * m, [-1] * m
+    err, affected = affected_throttles(snap0, p)
+    if err:
+        return -1, [0] * m, [-1] * m
+    req = {(k, d): v for k, s in enumerate(snaps) for d, v in pod_requests(s, p).items() if v != 0}  # (the pod brings every one)
+    best = [(cap, -1)] * m  # (copies, row): affected is ascending, so a strict < keeps the lowest row of a tie
+    for t in affected:
+        th = ctx["thr"][t]
+        f = int(snap0.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _paged_amounts(snaps, "thr_reserved", t)
+        r_hc = res_count is not None
+        calc_at_any = any(int(s.thr_flags[t]) & S.THR_CALC_AT_NONZERO for s in snaps)
+        if th["error"]:  # the stored status of every page, at every instant
+            used, used_count = _paged_amounts(snaps, "thr_used", t)
+            sth, sth_count = _paged_amounts(snaps, "thr_calc" if calc_at_any else "thr_spec", t)
+            u_hc = used_count is not None
+            h = _copies_of_amount(1, True, sth_count is not None, sth_count or 0, used_count or 0, res_count or 0, u_hc or r_hc,
+                                  bool(f & S.THR_THROTTLED_POD), eq3, eq, cap)
+            for (k, d), v in req.items():
+                flg = int(snaps[k].thr_thrl_flag[t]) & int(snaps[k].thr_thrl_has[t])
+                h = min(h, _copies_of_amount(v, True, (k, d) in sth, sth.get((k, d), 0), used.get((k, d), 0), res.get((k, d), 0),
+                                             (k, d) in used or (k, d) in res, bool(flg >> d & 1), eq3, eq, cap))
+            best = [(h, t) if h < b[0] else b for b in best]
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        u_hc = pods > 0
+        spec, spec_count = _paged_amounts(snaps, "thr_spec", t)
+        for j, at in enumerate(inst):
+            calc, cc, differs = {}, None, False
+            for k, s in enumerate(snaps):
+                names, count, any_err = _calculated_threshold(s, t, at)
+                stored, stored_count = _amount_dict(s.thr_calc, t, s.D)
+                fp = int(s.thr_spec_msgs_fp[t]) if any_err else 0
+                differs = differs or names != stored or int(s.thr_status_msgs_fp[t]) != fp
+                if k == 0:  # the count is the same in every page
+                    cc = count
+                    differs = differs or count != stored_count
+                calc.update({(k, d): v for d, v in names.items()})
+            rd, rd_count = (calc, cc) if calc_at_any or differs else (spec, spec_count)
+            h = _copies_of_amount(1, True, rd_count is not None, rd_count or 0, pods if u_hc else 0, res_count or 0, u_hc or r_hc,
+                                  cc is not None and u_hc and pods >= cc, eq3, eq, cap)
+            for kd, v in req.items():
+                u_pr = cnt.get(kd, 0) > 0
+                uv = val.get(kd, 0) if u_pr else 0
+                cv = calc.get(kd)
+                h = min(h, _copies_of_amount(v, True, kd in rd, rd.get(kd, 0), uv, res.get(kd, 0), u_pr or kd in res,
+                                             cv is not None and u_pr and uv >= cv, eq3, eq, cap))
+            if h < best[j][0]:
+                best[j] = (h, t)
+    copies = [b[0] for b in best]
+    return next((k for k in range(m) if copies[k] >= int(want)), -1), copies, [b[1] for b in best]
+
+
 # ---- forecast for gangs over pages (kt_paged_forecast_gangs): the closed form over a list of page snapshots ----
 def paged_forecast_gangs_of(snaps, member_rows, instants, on_equal=False, ctx=None):
     """kt_paged_forecast_gangs for one gang, in closed form over the page snapshots (no GPU) -> (first, verdicts [len(instants)],
@@ -1515,6 +1583,13 @@ class PagedEngine:
         stored changes on any page."""
         return E.paged_forecast_gangs(self.engines, pod_rows, gang_off, instants, on_equal=on_equal, want_verdicts=want_verdicts,
                                       want_blocker=want_blocker)
+
+    def headroom_forecast(self, pod_rows, instants, *, cap, want=1, on_equal=False):
+        """How many copies of each pod of ``pod_rows`` the throttles admit at each of the strictly ascending ``instants``, over every
+        page's names, through kt_paged_headroom_forecast -> (first [n], copies [n][n_inst], limiting [n][n_inst]): the first
+        position with at least ``want`` copies, and per instant the lowest throttle row that stops the next copy.  A dry run:
+        nothing stored changes on any page."""
+        return E.paged_headroom_forecast(self.engines, pod_rows, instants, cap=cap, want=want, on_equal=on_equal)
 
     def override_instants(self, from_, until, cap=None):
         """kt_override_instants of page 0 -> ([(seconds, nanoseconds)], total): every page holds every override's times and parse
