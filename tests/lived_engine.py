@@ -11,12 +11,41 @@ the opposite: one engine lives for days, is fed pod, Throttle and reservation ev
     amounts live in the snapshot's own arrays); ``n_thr`` and ``n_pods`` stay the highest row ever used + 1; the namespace side is
     ``nstate[row] -> namespace kind`` ("gone": no object) with ``ns_valid`` / ``ns_label_*`` arrays of the mirror's own;
   * ``battery``: everything the query family answers for one fixed question set, for both ``on_equal`` values — the headroom
-    forecast (first, copies and limiting at every instant of ``INSTANTS``) and, over pages, the paged gang headroom included;
+    forecast (first, copies and limiting at every instant of ``INSTANTS``) and, over pages, the paged gang headroom and the paged
+    headroom forecast included;
   * ``model_battery``: the same dictionary from the host models (``paging.*_of``) and the oracle, on the mirror alone;
   * ``Life``: the events, applied to the mirror and — when it has engines — to the live engine(s), and ``hold()``: live against a twin
     loaded fresh from the mirror (which side moved?), live against the models (who is right?), live against itself (queries are dry);
   * the lives, each a function of a Life: tests/test_queries_after_events_gpu.py runs them on the GPU, tests/test_lived_engine_cpu.py
     replays them on the mirror alone and asserts they are not vacuous.
+
+Row layouts.  The compact cluster (T_CAP = 24 throttle rows, P_CAP = 64 pod rows, live rows packed from row 0) stays below every
+structure that has bitten these kernels: the affected-throttle list is consumed in chunks of 1024 matrix bytes, 16 per lane, and
+is filled round by round over the lanes (so it is not in row order once a lane owns two live rows and a higher lane one); every
+per-T buffer of a live engine has to grow when its row count passes 1024; pods lie in tiles of 64 rows.  So every life also
+runs, unchanged, on a STRETCHED engine of T_PHYS = 1100 x P_PHYS = 4160 rows: ``Life(..., layout=Layout(name, variant))``.
+
+  * ``Layout``: logical throttle row k lives at physical row tmap[k], logical pod row r at pmap[r], both strictly increasing (the
+    lowest row is the lowest row in both numberings; a permuted layout would change the answers).  ``STRADDLE`` puts the twelve
+    initial throttles on both sides of row 1023/1024 (0 and 1 in one lane with 16 in the next, 15 and 16 neighbours, 1022..1025,
+    c-web and c-x in one lane at 1024 and 1025 below ns1/t-web at 1088, the rest a lane apart in chunk 1, appended rows above);
+    ``GROW`` ends them exactly at row 1023, so the first row a life appends (1024, 1025, 1040 ...) carries the live engine's row
+    count across 1024 between two answered batteries.  ``PMAP`` puts the pods on the edges of tiles 0, 1, 2, 32, 64 and 65.
+  * variants: ``holes`` — the rows outside the maps are never fed; ``fillers`` — every second unmapped throttle row below the last
+    of the twelve initial ones holds ``c-filler`` (valid, responsible, selector app=filler: no pod carries it) and every second
+    unmapped pod row below the highest mapped one holds a pending pod ``filler`` of ns0 (app=idle: no throttle selects it), so the
+    program has several term words and views and tiles hold real records between the life's own.  (The throttle fillers stop at
+    the twelfth throttle so that on ``grow`` the rows from 1024 on are unborn in both variants.)
+  * ``Stretched`` wraps an E.Engine and ``StretchedPages`` the module-level E.paged_* calls: row arguments are mapped on the way in
+    (events, pod_rows, cand_rows, gang members), everything that names a throttle row on the way out (limiting rows, the columns of
+    status matrices, the rows of fetch_reserved and of reconcile results); queue, candidate and instant positions stay.  Mirror,
+    models and lives stay in logical numbering.  ``stretch_snapshot`` builds what a stretched twin is loaded from.
+  * two assertions the translation would otherwise hide: in every status matrix of live engine and twin the physical columns
+    outside tmap are all zero (``Layout.status``; the row of a pod whose PreFilter is an Error is KT_STATUS_ERROR in EVERY column,
+    by the engine's contract and the oracle's, and is exempt as a whole), and the physical matrices of live engine and twin are
+    equal byte for byte over all physical columns (``Life.hold``).
+  * ``stretched_model_battery``: the models on the stretched mirror, mapped back by the same Layout methods —
+    tests/test_lived_engine_cpu.py holds it to the compact mirror's battery (the harness is faithful) and asserts what the layouts cover.
 
 Every comparison is exact: integers and bytes."""
 import copy
@@ -29,7 +58,7 @@ from kube_throttler_amd import engine as E
 from kube_throttler_amd import paging
 from kube_throttler_amd import snapshot as S
 from kube_throttler_amd.objects import ClusterState
-from test_engine_gpu import _permute_pods, _with_pods, assert_reconcile_equal, _rows_of
+from test_engine_gpu import _gather_pods, _permute_pods, _with_pods, assert_reconcile_equal, _rows_of
 
 NOW = FR.NOW
 INSTANTS = FR.instants_under_test()
@@ -125,6 +154,7 @@ class Pool:
         pod("neg", "ns0", {"app": "web", "team": "y"}, {"cpu": "300m", "memory": "64Mi"}, True)  # (cpu made negative below)
         pod("0wz-r", "ns0", {"app": "web", "team": "z"}, {"cpu": "100m", "memory": "64Mi"}, True)
         pod("neg1", "ns1", {"app": "web", "team": "y"}, {"cpu": "300m", "memory": "128Mi"}, True)  # (memory made negative below)
+        pod("filler", "ns0", {"app": "idle"}, {"cpu": "100m"})                                    # (a stretched layout's filler rows)
 
         win = lambda b, e, th: [{"begin": B[b], "end": B[e], "threshold": th}]
         x = {name: "3" for name in EXTRA[-4:]} if wide else {}  # (c-web's names of both pages)
@@ -163,6 +193,9 @@ class Pool:
         thr("ns1/t-web@room-mem", [{"app": "web"}], _rr(cpu="10", mem="768Mi"), ns="ns1")          # ... and memory edited
         thr("c-web@room", [{"app": "web"}], {"resourceRequests": dict(_rr(cpu="20")["resourceRequests"], **room)},
             overrides=win(3, 6, _cnt(20, cpu="10")))
+        thr("ns1/t-job2", [{"app": "job"}], _rr(cpu="1700m"), ns="ns1")                            # ns1/t-job once more: ties with it
+        thr("c-x2", [{"team": "x"}], _cnt(7), overrides=win(1, 8, _cnt(40)))                        # c-x once more
+        thr("c-filler", [{"app": "filler"}], _cnt(3))                                               # (a stretched layout's filler rows)
         self.cs = cs
         pages = cs.build_pages()
         assert len(pages) == (2 if wide else 1), len(pages)
@@ -198,7 +231,7 @@ class Pool:
     # the pods the cluster starts with: row r holds PLACEMENT[r]
     @property
     def placement(self):
-        skip = {"neg", "neg1", "small"}
+        skip = {"neg", "neg1", "small", "filler"}
         return [name for name in self.pod if name not in skip]
 
     def dim(self, name):
@@ -453,6 +486,341 @@ def load_fields(snap):
     return out
 
 
+# ---- row layouts: the same lives on stretched engines -------------------------------------------------------------------------
+T_PHYS, P_PHYS = 1100, 65 * 64  # capacities of a stretched live engine: two chunks of the matrix row, 65 tiles of pod rows
+CHUNK, LANE, TILE = 1024, 16, 64  # matrix bytes per chunk of the affected-throttle list, bytes per lane, pod rows per tile
+# straddle: the twelve initial throttles lie on both sides of the chunk boundary 1023/1024 — rows 0 and 1 share a lane and 16 is
+# the next one (the list reads 0, 16, 1), 15 and 16 are neighbouring lanes, 1022..1025 end chunk 0 and begin chunk 1 (c-job at 1023,
+# c-web and c-x in ONE lane at 1024 and 1025), the rest lie in chunk 1 a lane apart; the rows a life adds follow above.
+STRADDLE = (0, 1, 15, 16, 1022, 1023, 1024, 1025, 1040, 1056, 1072, 1088, 1089, 1090, 1091, 1092, 1094, 1095, 1097, 1099)
+# grow: the twelve initial throttles end exactly at row 1023 (c-web and c-x in one lane at 512 and 513), so the first row a life
+# adds carries the live engine's row count across 1024 and every per-T buffer has to grow behind answered queries.
+GROW = (0, 1, 15, 16, 40, 511, 512, 513, 600, 1021, 1022, 1023, 1024, 1025, 1040, 1041, 1056, 1057, 1072, 1099)
+TMAPS = {"straddle": STRADDLE, "grow": GROW}
+# the pod map: both ends of tiles 0 and 1, the tile boundaries at 128, 2048 and 4096, and the last row of the last tile (logical
+# row 44: the row life_pod_events appends)
+PMAP = (0, 1, 62, 63, 64, 65, 127, 128, 129, 200, 300, 511, 512, 1000, 1023, 1024, 1500, 2047, 2048, 2049, 2500, 3000, 3071, 3072,
+        3500, 4000, 4031, 4032, 4094, 4095, 4096, 4097, 4100, 4110, 4120, 4127, 4128, 4130, 4140, 4150, 4151, 4152, 4157, 4158, 4159)
+VARIANTS = ("holes", "fillers")
+
+
+def _gather_throttles(entries, D, L):
+    """A throttles-only batch whose row i is throttle row t of snapshot s for entries[i] = (s, t); None: an empty row (flags 0).
+    (Snapshot.throttle_batch, over several snapshots.)"""
+    b = S.Snapshot(D, L)
+    b.alloc_namespaces(0, 0)
+    b.alloc_pods(0, 0, 0)
+    live = [e for e in entries if e is not None]
+    b.alloc_throttles(len(entries), int(sum(int(s.thr_ovr_off[t + 1]) - int(s.thr_ovr_off[t]) for s, t in live)),
+                      int(sum(int(s.thr_term_off[t + 1]) - int(s.thr_term_off[t]) for s, t in live)))
+    pools = {}
+    oo = gg = 0
+    for i, e in enumerate(entries):
+        if e is not None:
+            s, t = e
+            if id(s) not in pools:
+                pools[id(s)] = [tuple(np.asarray(x) for x in paging._pool_arrays(p)) for p in (s.preq, s.nreq)]
+            b.thr_flags[i], b.thr_ns[i] = s.thr_flags[t], s.thr_ns[t]
+            for tab in ("thr_spec", "thr_calc", "thr_used", "thr_reserved"):
+                for f in ("v", "present", "count", "has_count"):
+                    getattr(getattr(b, tab), f)[i] = getattr(getattr(s, tab), f)[t]
+            b.thr_thrl_flag[i], b.thr_thrl_has[i] = s.thr_thrl_flag[t], s.thr_thrl_has[t]
+            b.thr_status_msgs_fp[i], b.thr_spec_msgs_fp[i] = s.thr_status_msgs_fp[t], s.thr_spec_msgs_fp[t]
+            for o in range(int(s.thr_ovr_off[t]), int(s.thr_ovr_off[t + 1])):
+                for f in ("ovr_begin_s", "ovr_begin_ns", "ovr_end_s", "ovr_end_ns", "ovr_flags"):
+                    getattr(b, f)[oo] = getattr(s, f)[o]
+                for f in ("v", "present", "count", "has_count"):
+                    getattr(b.ovr_thr, f)[oo] = getattr(s.ovr_thr, f)[o]
+                oo += 1
+            for g in range(int(s.thr_term_off[t]), int(s.thr_term_off[t + 1])):
+                b.term_flags[gg] = s.term_flags[g]
+                for dst, offs, (op, key, val_off, val) in zip((b.preq, b.nreq), (s.term_preq_off, s.term_nreq_off), pools[id(s)]):
+                    for r in range(int(offs[g]), int(offs[g + 1])):
+                        dst.add(int(op[r]), int(key[r]), [int(v) for v in val[int(val_off[r]):int(val_off[r + 1])]])
+                gg += 1
+                b.term_preq_off[gg], b.term_nreq_off[gg] = len(b.preq), len(b.nreq)
+        b.thr_ovr_off[i + 1], b.thr_term_off[i + 1] = oo, gg
+    return b
+
+
+def stretch_snapshot(snap, tmap, pmap, T_phys, P_phys, fillers=None):
+    """The snapshot a stretched twin is loaded from: ``snap``'s throttle row k at row tmap[k] and its pod row r at row pmap[r],
+    namespaces as they are.  ``fillers``: None (the rows outside the maps are empty), or (snapshot, throttle row, pod row, throttle
+    rows to fill, pod rows to fill) — every listed row holds a copy of that throttle / that pod."""
+    tmap, pmap = np.asarray(tmap, np.int64), np.asarray(pmap, np.int64)
+    thr = [None] * (int(tmap[snap.n_thr - 1]) + 1 if snap.n_thr else 0)
+    pods = [None] * (int(pmap[snap.n_pods - 1]) + 1 if snap.n_pods else 0)
+    if fillers is not None:
+        src, ft, fp, thr_rows, pod_rows = fillers
+        thr += [None] * max(0, int(max(thr_rows, default=-1)) + 1 - len(thr))
+        pods += [None] * max(0, int(max(pod_rows, default=-1)) + 1 - len(pods))
+        for t in thr_rows:
+            thr[int(t)] = (src, ft)
+        for r in pod_rows:
+            pods[int(r)] = (src, fp)
+    for k in range(snap.n_thr):
+        thr[int(tmap[k])] = (snap, k)
+    for r in range(snap.n_pods):
+        pods[int(pmap[r])] = (snap, r)
+    assert len(thr) <= T_phys and len(pods) <= P_phys
+    out = copy.copy(snap)
+    out._keep = None
+    tb = _gather_throttles(thr, snap.D, snap.L)
+    for f in THR_SPEC_FIELDS + ("n_thr", "thr_flags", "thr_calc", "thr_used", "thr_reserved", "thr_thrl_flag", "thr_thrl_has",
+                                "thr_status_msgs_fp"):
+        setattr(out, f, getattr(tb, f))
+    empty = np.array([e is None for e in pods], bool)
+    pb = _gather_pods([e or (snap, 0) for e in pods])
+    pb.pod_flags[:len(pods)][empty] = 0  # (a row that holds nothing is gated by its flags, as a deleted one is)
+    for f in POD_FIELDS:
+        setattr(out, f, getattr(pb, f))
+    return out
+
+
+class Layout:
+    """Logical throttle row k lives at physical row tmap[k], logical pod row r at pmap[r]; both maps are strictly increasing, so
+    "the lowest row" is the same row in both numberings.  Translates rows on the way in and everything that names a throttle row
+    on the way out; queue positions, candidate positions and instant positions are left as they are."""
+
+    def __init__(self, name, variant):
+        assert variant in VARIANTS
+        self.name, self.variant = name, variant
+        self.tmap, self.pmap = np.array(TMAPS[name], np.int64), np.array(PMAP, np.int64)
+        for m, cap in ((self.tmap, T_PHYS), (self.pmap, P_PHYS)):
+            assert (np.diff(m) > 0).all() and m[0] >= 0 and m[-1] < cap
+        self.tinv = np.full(T_PHYS, -1, np.int64)
+        self.tinv[self.tmap] = np.arange(len(self.tmap))
+        self.outside = self.tinv < 0
+        self.thr_fillers = self.pod_fillers = np.zeros(0, np.int64)
+        if variant == "fillers":
+            # every second unmapped row: throttles below the last of the twelve initial ones (on `grow` the rows from 1024 on stay
+            # unborn until a life adds one), pods below the highest mapped row
+            self.thr_fillers = np.setdiff1d(np.arange(self.tmap[11]), self.tmap)[::2]
+            self.pod_fillers = np.setdiff1d(np.arange(self.pmap[-1]), self.pmap)[::2]
+
+    def __repr__(self):
+        return f"{self.name}-{self.variant}"
+
+    # -- on the way in
+    def thr(self, rows):
+        return self.tmap[np.asarray(rows, np.int64)].astype(np.int32)
+
+    def pods(self, rows):
+        return self.pmap[np.asarray(rows, np.int64)]
+
+    def questions(self, q):
+        out = copy.copy(q)
+        out.pods, out.gang_rows, out.cands = self.pods(q.pods), self.pods(q.gang_rows), self.pods(q.cands)
+        return out
+
+    def stretch(self, snap, base, pl):
+        """``snap`` (a page of the mirror) in physical numbering; ``base``: the pool's snapshot of that page (the fillers' kinds)."""
+        fillers = (base, pl.thr["c-filler"], pl.pod["filler"], self.thr_fillers, self.pod_fillers) if self.variant == "fillers" else None
+        return stretch_snapshot(snap, self.tmap, self.pmap, T_PHYS, P_PHYS, fillers)
+
+    # -- on the way out
+    def logical_rows(self, n_phys):
+        """The logical row count of an engine with n_phys rows: the map's entries below it."""
+        return int(np.searchsorted(self.tmap, n_phys))
+
+    def limiting(self, l):
+        l = np.asarray(l)
+        back = np.where(l >= 0, self.tinv[np.maximum(l, 0)], l)
+        assert (back[l >= 0] >= 0).all(), f"{self}: a limiting row outside the layout: {l}"
+        return back.astype(l.dtype)
+
+    def status(self, st, n):
+        """A physical status matrix [pods][physical rows] -> its logical columns [pods][n].  The columns outside the map are all
+        zero: asserted here, on the physical matrix, because nobody sees them afterwards."""
+        assert st.shape[1] == (int(self.tmap[n - 1]) + 1 if n else 0), f"{self}: {st.shape[1]} physical columns for {n} logical rows"
+        whole = (st == S.ERROR).all(axis=1)  # (a pod whose PreFilter is an Error: KT_STATUS_ERROR in EVERY column of its row)
+        stray = st[~whole][:, self.outside[:st.shape[1]]]
+        assert not stray.any(), f"{self}: status outside the layout's rows at physical columns " \
+                                f"{np.nonzero(self.outside[:st.shape[1]])[0][np.nonzero(stray.any(axis=0))[0]]}"
+        return np.ascontiguousarray(st[:, self.tmap[:n]])
+
+    def amounts(self, a, n):
+        return tuple(np.array(getattr(a, f) if hasattr(a, "v") else a[i])[self.tmap[:n]]
+                     for i, f in enumerate(("v", "present", "count", "has_count")))
+
+    def battery(self, b, n):
+        """A battery in physical numbering -> in logical numbering (n logical throttle rows)."""
+        out = {}
+        for k, a in b.items():
+            name = k if isinstance(k, str) else k[0]
+            if isinstance(a[0], str):
+                out[k] = a
+            elif name in ("check", "check_status", "admit", "admit_gangs"):
+                out[k] = (self.status(a[0], n),) + tuple(a[1:])
+            elif name == "headroom":
+                out[k] = (a[0], self.limiting(a[1]))
+            elif name == "headroom_gangs":
+                out[k] = (a[0], self.limiting(a[1]), a[2])
+            elif name == "headroom_forecast":
+                out[k] = (a[0], a[1], self.limiting(a[2]))
+            elif name == "reserved":
+                out[k] = self.amounts(a, n)
+            else:
+                out[k] = a
+        return out
+
+
+class Stretched:
+    """An E.Engine of capacity T_PHYS x P_PHYS behind a Layout: the lives feed it and ask it in logical numbering.  Every physical
+    status matrix it has returned is kept in ``matrices`` (``take_matrices``): Life.hold compares the live engine's with the
+    twin's byte for byte over all physical columns."""
+    PLAIN = ("close", "compiles", "view_builds", "upsert_namespaces", "upsert_namespace", "delete_namespaces", "override_instants", "D")
+
+    def __init__(self, raw, lay):
+        self.raw, self.lay, self.matrices = raw, lay, []
+
+    def __getattr__(self, name):
+        if name in Stretched.PLAIN:  # what names no throttle row and no pod row
+            return getattr(self.raw, name)
+        raise AttributeError(f"Stretched: {name} is not translated")
+
+    def take_matrices(self):
+        out, self.matrices = self.matrices, []
+        return out
+
+    def throttle_rows(self):
+        return self.lay.logical_rows(self.raw.throttle_rows())
+
+    def _status(self, st):
+        self.matrices.append(np.array(st))
+        return self.lay.status(st, self.throttle_rows())
+
+    # -- events
+    def upsert_pods(self, batch, rows):
+        self.raw.upsert_pods(batch, rows=self.lay.pods(rows))
+
+    def delete_pods(self, rows):
+        self.raw.delete_pods(self.lay.pods(rows))
+
+    def upsert_throttles(self, batch, rows):
+        self.raw.upsert_throttles(batch, rows=self.lay.thr(rows))
+
+    def delete_throttles(self, rows):
+        self.raw.delete_throttles(self.lay.thr(rows))
+
+    def set_reserved(self, rows, amounts):
+        self.raw.set_reserved(self.lay.thr(rows), amounts)
+
+    def set_status(self, rows, *a, **kw):
+        self.raw.set_status(self.lay.thr(rows), *a, **kw)
+
+    def _reconciled(self, got):
+        return _rows_of(got, self.lay.tmap[:self.throttle_rows()], self.raw.D)
+
+    def reconcile(self, now, apply=True):
+        return self._reconciled(self.raw.reconcile(now, apply=apply))
+
+    def reconcile_rows(self, now, rows, apply=True):
+        return self._reconciled(self.raw.reconcile_rows(now, self.lay.thr(rows), apply=apply))
+
+    def fetch_reserved(self):
+        n = self.throttle_rows()
+        out = S.Amounts(n, self.raw.D)
+        for f, x in zip(("v", "present", "count", "has_count"), self.lay.amounts(self.raw.fetch_reserved(), n)):
+            getattr(out, f)[:n] = x
+        return out
+
+    # -- queries
+    def check(self, rows, on_equal=False, want_status=True):
+        st, sm = self.raw.check(rows=self.lay.pods(rows), on_equal=on_equal, want_status=want_status)
+        return (self._status(st) if want_status else None), sm
+
+    def admit(self, rows, on_equal=False, commit=False):
+        st, sm = self.raw.admit(rows=self.lay.pods(rows), on_equal=on_equal, commit=commit)
+        return self._status(st), sm
+
+    def admit_gangs(self, rows, gang_off, on_equal=False, commit=False):
+        st, sm, admitted = self.raw.admit_gangs(self.lay.pods(rows), gang_off, on_equal=on_equal, commit=commit)
+        return self._status(st), sm, admitted
+
+    def headroom(self, rows, cap, on_equal=False):
+        copies, limiting = self.raw.headroom(rows=self.lay.pods(rows), cap=cap, on_equal=on_equal)
+        return copies, self.lay.limiting(limiting)
+
+    def headroom_gangs(self, pod_rows, gang_off, cap, on_equal=False):
+        copies, limiting, blocker = self.raw.headroom_gangs(self.lay.pods(pod_rows), gang_off, cap=cap, on_equal=on_equal)
+        return copies, self.lay.limiting(limiting), blocker
+
+    def headroom_forecast(self, pod_rows, instants, cap, want=1, on_equal=False):
+        first, copies, limiting = self.raw.headroom_forecast(self.lay.pods(pod_rows), instants, cap=cap, want=want, on_equal=on_equal)
+        return first, copies, self.lay.limiting(limiting)
+
+    def preempt(self, pod_rows, cand_rows, now, on_equal=False, reprieve=False):
+        return self.raw.preempt(self.lay.pods(pod_rows), self.lay.pods(cand_rows), now, on_equal=on_equal, reprieve=reprieve)
+
+    def preempt_gangs(self, pod_rows, gang_off, cand_rows, now, on_equal=False, reprieve=False):
+        return self.raw.preempt_gangs(self.lay.pods(pod_rows), gang_off, self.lay.pods(cand_rows), now, on_equal=on_equal, reprieve=reprieve)
+
+    def forecast(self, pod_rows, instants, on_equal=False):
+        return self.raw.forecast(self.lay.pods(pod_rows), instants, on_equal=on_equal)
+
+    def forecast_gangs(self, pod_rows, gang_off, instants, on_equal=False):
+        return self.raw.forecast_gangs(self.lay.pods(pod_rows), gang_off, instants, on_equal=on_equal)
+
+
+class StretchedPages:
+    """The module-level E.paged_* calls over Stretched page engines, translated the same way (the physical status matrices are
+    kept by the first page's engine)."""
+
+    def __init__(self, engs):
+        self.first, self.lay = engs[0], engs[0].lay
+
+    @staticmethod
+    def _raw(engs):
+        return [e.raw for e in engs]
+
+    def paged_reconcile(self, engs, now, apply=True):
+        return E.paged_reconcile(self._raw(engs), now, apply=apply)
+
+    def paged_check(self, engs, n, rows, on_equal=False):
+        st, sm = E.paged_check(self._raw(engs), n, rows=self.lay.pods(rows), on_equal=on_equal)
+        return self.first._status(st), sm
+
+    def paged_admit(self, engs, rows, on_equal=False, commit=False):
+        st, sm = E.paged_admit(self._raw(engs), self.lay.pods(rows), on_equal=on_equal, commit=commit)
+        return self.first._status(st), sm
+
+    def paged_admit_gangs(self, engs, rows, gang_off, on_equal=False, commit=False):
+        st, sm, admitted = E.paged_admit_gangs(self._raw(engs), self.lay.pods(rows), gang_off, on_equal=on_equal, commit=commit)
+        return self.first._status(st), sm, admitted
+
+    def paged_headroom(self, engs, rows, cap, on_equal=False):
+        copies, limiting = E.paged_headroom(self._raw(engs), self.lay.pods(rows), cap, on_equal=on_equal)
+        return copies, self.lay.limiting(limiting)
+
+    def paged_headroom_gangs(self, engs, pod_rows, gang_off, cap, on_equal=False):
+        copies, limiting, blocker = E.paged_headroom_gangs(self._raw(engs), self.lay.pods(pod_rows), gang_off, cap, on_equal=on_equal)
+        return copies, self.lay.limiting(limiting), blocker
+
+    def paged_headroom_forecast(self, engs, pod_rows, instants, cap, want=1, on_equal=False):
+        first, copies, limiting = E.paged_headroom_forecast(self._raw(engs), self.lay.pods(pod_rows), instants, cap=cap, want=want,
+                                                            on_equal=on_equal)
+        return first, copies, self.lay.limiting(limiting)
+
+    def paged_preempt(self, engs, pod_rows, cand_rows, now, on_equal=False, reprieve=False):
+        return E.paged_preempt(self._raw(engs), self.lay.pods(pod_rows), self.lay.pods(cand_rows), now, on_equal=on_equal, reprieve=reprieve)
+
+    def paged_preempt_gangs(self, engs, pod_rows, gang_off, cand_rows, now, on_equal=False, reprieve=False):
+        return E.paged_preempt_gangs(self._raw(engs), self.lay.pods(pod_rows), gang_off, self.lay.pods(cand_rows), now,
+                                     on_equal=on_equal, reprieve=reprieve)
+
+    def paged_forecast(self, engs, pod_rows, instants, on_equal=False):
+        return E.paged_forecast(self._raw(engs), self.lay.pods(pod_rows), instants, on_equal=on_equal)
+
+    def paged_forecast_gangs(self, engs, pod_rows, gang_off, instants, on_equal=False):
+        return E.paged_forecast_gangs(self._raw(engs), self.lay.pods(pod_rows), gang_off, instants, on_equal=on_equal)
+
+
+def paged_api(engs):
+    """The E.paged_* entry points for these page engines: the module itself, or its translation for Stretched ones."""
+    return StretchedPages(engs) if isinstance(engs[0], Stretched) else E
+
+
 # ---- the battery -----------------------------------------------------------------------------------------------------------
 def _answer(f):
     """An EngineError is recorded as its code, so a refusal compares like a value."""
@@ -493,20 +861,22 @@ def battery(eng, q, now=NOW):
 
 
 def _paged_battery(engs, q, now):
+    P = paged_api(engs)
     out = {}
     for eq in (False, True):
-        out["check", eq] = _answer(lambda: E.paged_check(engs, len(q.pods), rows=q.pods, on_equal=eq))
+        out["check", eq] = _answer(lambda: P.paged_check(engs, len(q.pods), rows=q.pods, on_equal=eq))
         out["check_status", eq] = out["check", eq][:1]
-        out["admit", eq] = _answer(lambda: E.paged_admit(engs, q.gang_rows, on_equal=eq, commit=False))
-        out["admit_gangs", eq] = _answer(lambda: E.paged_admit_gangs(engs, q.gang_rows, q.gang_off, on_equal=eq, commit=False))
+        out["admit", eq] = _answer(lambda: P.paged_admit(engs, q.gang_rows, on_equal=eq, commit=False))
+        out["admit_gangs", eq] = _answer(lambda: P.paged_admit_gangs(engs, q.gang_rows, q.gang_off, on_equal=eq, commit=False))
         for cap in CAPS:
-            out["headroom", cap, eq] = _answer(lambda: E.paged_headroom(engs, q.pods, cap, on_equal=eq))
-            out["headroom_gangs", cap, eq] = _answer(lambda: E.paged_headroom_gangs(engs, q.gang_rows, q.gang_off, cap, on_equal=eq))
+            out["headroom", cap, eq] = _answer(lambda: P.paged_headroom(engs, q.pods, cap, on_equal=eq))
+            out["headroom_gangs", cap, eq] = _answer(lambda: P.paged_headroom_gangs(engs, q.gang_rows, q.gang_off, cap, on_equal=eq))
+            out["headroom_forecast", cap, eq] = _answer(lambda: P.paged_headroom_forecast(engs, q.pods, INSTANTS, cap=cap, want=WANT, on_equal=eq))
         for rep in (False, True):
-            out["preempt", rep, eq] = _answer(lambda: E.paged_preempt(engs, q.pods, q.cands, now, on_equal=eq, reprieve=rep))
-            out["preempt_gangs", rep, eq] = _answer(lambda: E.paged_preempt_gangs(engs, q.gang_rows, q.gang_off, q.cands, now, on_equal=eq, reprieve=rep))
-        out["forecast", eq] = _answer(lambda: E.paged_forecast(engs, q.pods, INSTANTS, on_equal=eq))
-        out["forecast_gangs", eq] = _answer(lambda: E.paged_forecast_gangs(engs, q.gang_rows, q.gang_off, INSTANTS, on_equal=eq))
+            out["preempt", rep, eq] = _answer(lambda: P.paged_preempt(engs, q.pods, q.cands, now, on_equal=eq, reprieve=rep))
+            out["preempt_gangs", rep, eq] = _answer(lambda: P.paged_preempt_gangs(engs, q.gang_rows, q.gang_off, q.cands, now, on_equal=eq, reprieve=rep))
+        out["forecast", eq] = _answer(lambda: P.paged_forecast(engs, q.pods, INSTANTS, on_equal=eq))
+        out["forecast_gangs", eq] = _answer(lambda: P.paged_forecast_gangs(engs, q.gang_rows, q.gang_off, INSTANTS, on_equal=eq))
     for k, e in enumerate(engs):
         out["override_instants", k] = _answer(lambda: e.override_instants(NOW, FR.BEYOND))
         out["reserved", k] = _answer(lambda: _amounts(e.fetch_reserved(), e.throttle_rows()))
@@ -595,6 +965,10 @@ def _paged_model_battery(mirror, q, oracle_mod, now):
             h = [paging.paged_headroom_gangs_of(snaps, q.members(g), cap, eq) for g in range(ng)]
             out["headroom_gangs", cap, eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32),
                                               _queue_pos([x[2] for x in h], q))
+            a = [paging.paged_headroom_forecast_of(snaps, p, INSTANTS, cap, WANT, eq, ctx=ctx) for p in q.pods]
+            out["headroom_forecast", cap, eq] = (np.array([x[0] for x in a], np.int64),
+                                                 np.array([x[1] for x in a], np.int64).reshape(len(a), len(INSTANTS)),
+                                                 np.array([x[2] for x in a], np.int32).reshape(len(a), len(INSTANTS)))
         for rep in (False, True):
             a = [paging.paged_preempt_of(snaps, p, q.cands, now, eq, reprieve=rep, ctx=ctx) for p in q.pods]
             out["preempt", rep, eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.uint8).reshape(len(a), m))
@@ -613,6 +987,22 @@ def _paged_model_battery(mirror, q, oracle_mod, now):
     return out
 
 
+def stretched_model_battery(mirror, q, lay, oracle_mod):
+    """``model_battery`` on the STRETCHED mirror — every page's snapshot in physical numbering, the questions' rows mapped in —
+    with the answers mapped back by the Layout methods the Stretched engines use -> (battery in logical numbering, the stretched
+    snapshots)."""
+    snaps = [lay.stretch(m, base, mirror.pl) for m, base in zip(mirror.snaps, mirror.pl.snaps)]
+    return lay.battery(model_battery(SimpleNamespace(snaps=snaps), lay.questions(q), oracle_mod), mirror.n_thr), snaps
+
+
+def reconcile_answer(oracle_mod, snap, rows, now=NOW):
+    """The oracle's dry reconcile of these throttle rows, as comparable arrays."""
+    w = oracle_mod.Oracle(snap).reconcile(now, rows=np.asarray(rows, np.int32))
+    n = len(rows)
+    return tuple(np.array(getattr(w, f)[:n]) for f in ("calc_updated", "thrl_flag", "thrl_has", "thrl_pod", "error")) + \
+        _amounts(w.used, n) + _amounts(w.calc, n)
+
+
 def page_zero_alone(mirror, q, cap=CAP):
     """What page 0 alone would answer for the gangs' headroom (``headroom_gangs_of`` on its snapshot), shaped as the battery's
     ``("headroom_gangs", cap, eq)`` -> {eq: answer}.  Where the paged answer differs from it, a name of a later page decides."""
@@ -620,6 +1010,19 @@ def page_zero_alone(mirror, q, cap=CAP):
     for eq in (False, True):
         h = [paging.headroom_gangs_of(mirror.snaps[0], q.members(g), cap, eq) for g in range(len(q.gang_off) - 1)]
         out[eq] = (np.array([x[0] for x in h], np.int64), np.array([x[1] for x in h], np.int32), _queue_pos([x[2] for x in h], q))
+    return out
+
+
+def page_zero_alone_forecast(mirror, q, cap=CAP):
+    """... and for the pods' headroom forecast (``headroom_forecast_of`` on page 0's snapshot), shaped as the battery's
+    ``("headroom_forecast", cap, eq)`` -> {eq: answer}."""
+    snap = mirror.snaps[0]
+    ctx = paging.preempt_context(snap, NOW)
+    out = {}
+    for eq in (False, True):
+        a = [paging.headroom_forecast_of(snap, p, INSTANTS, cap, WANT, eq, ctx=ctx) for p in q.pods]
+        out[eq] = (np.array([x[0] for x in a], np.int64), np.array([x[1] for x in a], np.int64).reshape(len(a), len(INSTANTS)),
+                   np.array([x[2] for x in a], np.int32).reshape(len(a), len(INSTANTS)))
     return out
 
 
@@ -656,8 +1059,12 @@ class Life:
     event is applied to both.  ``hold()`` records the models' battery (``self.held``: [(step name, battery)]); with engines it first
     compares live, twin and models."""
 
-    def __init__(self, oracle_mod, gpu=False, wide=False):
+    def __init__(self, oracle_mod, gpu=False, wide=False, layout=None):
+        """``layout``: a Layout — the live engine and every twin are Stretched ones (capacities T_PHYS x P_PHYS, on the variant
+        "fillers" with the filler rows fed first); the mirror, the models and the lives stay in logical numbering."""
         self.o = oracle_mod
+        self.layout = layout
+        self.watch = None  # a function (life, step): called by every hold() (tests/test_lived_engine_cpu.py)
         self.pl = pool(wide)
         self.q = Questions(self.pl)
         self.mirror = Mirror(self.pl)
@@ -665,15 +1072,23 @@ class Life:
         self.held = []
         self.live_held = []
         self.alone = []  # a paged life: [(step name, page_zero_alone)]
+        self.alone_forecast = []  # ... [(step name, page_zero_alone_forecast)]
         self.soft = None  # a list: hold() collects what differs there and goes on (a survey of a whole life)
         names = self.pl.placement
         self.mirror.put_throttles(range(len(self.pl.initial)), self.pl.initial)
         self.mirror.put_pods(range(len(names)), names)
         if gpu:
             for m, base in zip(self.mirror.snaps, self.pl.snaps):
-                e = E.Engine(base.D, max(base.L, 1), P_CAP, T_CAP, max(base.n_ns, 1) + 1)
+                if layout is None:
+                    e = E.Engine(base.D, max(base.L, 1), P_CAP, T_CAP, max(base.n_ns, 1) + 1)
+                else:
+                    e = Stretched(E.Engine(base.D, max(base.L, 1), P_PHYS, T_PHYS, max(base.n_ns, 1) + 1), layout)
                 self.engines.append(e)
                 e.upsert_namespaces(base)
+                if layout is not None and len(layout.thr_fillers):
+                    e.raw.upsert_throttles(_gather_throttles([(base, self.pl.thr["c-filler"])] * len(layout.thr_fillers), base.D, base.L),
+                                           rows=layout.thr_fillers.astype(np.int32))
+                    e.raw.upsert_pods(_permute_pods(base, [self.pl.pod["filler"]] * len(layout.pod_fillers)), rows=layout.pod_fillers)
                 e.upsert_throttles(m.throttle_batch(np.arange(m.n_thr)), rows=np.arange(m.n_thr))
                 e.upsert_pods(_permute_pods(base, self.mirror.state[:len(names)]), rows=np.arange(len(names)))
 
@@ -769,7 +1184,7 @@ class Life:
             rows, w = want[0]
             assert_reconcile_equal(_rows_of(got, rows, self.mirror.snap.D), w, len(rows))
         elif self.engines:
-            E.paged_reconcile(self.engines, now, apply=True)
+            paged_api(self.engines).paged_reconcile(self.engines, now, apply=True)
 
     def admit_commit(self, rows, on_equal=False):
         """admit(commit=True) of a short queue: the mirror takes the admission model's reservation."""
@@ -801,7 +1216,10 @@ class Life:
 
     # -- hold
     def twin(self):
-        return [E.Engine.for_snapshot(m) for m in self.mirror.snaps]
+        if self.layout is None:
+            return [E.Engine.for_snapshot(m) for m in self.mirror.snaps]
+        return [Stretched(E.Engine.for_snapshot(self.layout.stretch(m, base, self.pl)), self.layout)
+                for m, base in zip(self.mirror.snaps, self.pl.snaps)]
 
     def hold(self, step, refused=(), live_refuses=()):
         """``refused``: query names the engine answers KT_ERR_UNSUPPORTED on live AND twin (the models are not asked);
@@ -810,9 +1228,14 @@ class Life:
         self.held.append((step, model))
         if len(self.mirror.snaps) > 1:
             self.alone.append((step, page_zero_alone(self.mirror, self.q)))
+            self.alone_forecast.append((step, page_zero_alone_forecast(self.mirror, self.q)))
+        if self.watch is not None:
+            self.watch(self, step)
         if not self.engines:
             return model
         target = self.engines if len(self.engines) > 1 else self.eng
+        if self.layout is not None:
+            self.engines[0].take_matrices()  # (what committed admissions since the last hold left there)
         live = battery(target, self.q)
         tw = self.twin()
         try:
@@ -820,8 +1243,17 @@ class Life:
         finally:
             for e in tw:
                 e.close()
-        again = battery(target, self.q)
         problems = []
+        if self.layout is not None:  # the physical status matrices, over all physical columns (the first page's engine keeps them)
+            a, b = self.engines[0].take_matrices(), tw[0].take_matrices()
+            assert len(a) == len(b) and len(a) >= 6, (len(a), len(b))
+            for i, (x, y) in enumerate(zip(a, b)):
+                if x.shape != y.shape or x.tobytes() != y.tobytes():
+                    problems.append(f"{step}: physical status matrix number {i} of the battery: live {x.shape} and twin {y.shape} differ"
+                                    + (f" at physical columns {np.nonzero((x != y).any(axis=0))[0]}" if x.shape == y.shape else ""))
+        again = battery(target, self.q)
+        if self.layout is not None:
+            self.engines[0].take_matrices()
 
         def expect(x, y, what, keys=None):
             bad = differences(x, y, keys)
@@ -1017,6 +1449,28 @@ def life_negative_on_page_one(life):
     life.hold("... and a reconcile behind it", live_refuses=("headroom_gangs",))
 
 
+def life_rows_appended(life):
+    """Throttle rows appended behind the twelve (on the layout `grow`: the first of them carries the row count across 1024), each a
+    second copy of a throttle that limits an answer: same selector, same threshold, so the same number of copies from a row far
+    above — a tie, and the lower row is the one to report.  Then the lower row goes (the far row limits alone) and returns."""
+    t = {name: i for i, name in enumerate(life.pl.initial)}
+    start(life)
+    n = life.mirror.n_thr
+    life.upsert_throttles([n], ["ns1/t-job2"])
+    life.reconcile()
+    life.hold("a second ns1/t-job is appended and reconciled")
+    life.upsert_throttles([n + 1, n + 3], ["c-x2", "c-y"])   # one batch, two rows, one row stays empty in between
+    life.reconcile()
+    life.hold("one batch appends a second c-x and c-y")
+    life.delete_throttles([t["ns1/t-job"], t["c-x"]])
+    life.hold("the lower rows of both ties are deleted")
+    life.upsert_throttles([t["ns1/t-job"], t["c-x"]], ["ns1/t-job", "c-x"])
+    life.reconcile()
+    life.hold("... and return")
+    life.delete_throttles([n, n + 1])
+    life.hold("the appended copies are deleted")
+
+
 class _Gaps:
     """compiles() of every page's engine from one hold to the next: a gap that holds namespace events (or a pod of a namespace row
     the program was not compiled for) costs exactly ONE compile, however many events it holds; a gap without events costs none."""
@@ -1128,7 +1582,8 @@ def life_namespace_events_among_the_others(life):
 
 LIVES = {"pod_events": life_pod_events, "threshold_and_override_events": life_threshold_and_override_events,
          "selector_and_row_events": life_selector_and_row_events, "reservations_survive": life_reservations_survive,
-         "negative_came_and_went": life_negative_came_and_went, "namespace_labels": life_namespace_labels,
+         "negative_came_and_went": life_negative_came_and_went, "rows_appended": life_rows_appended,
+         "namespace_labels": life_namespace_labels,
          "namespace_deleted_and_back": life_namespace_deleted_and_back,
          "namespace_arrives_after_its_pods": life_namespace_arrives_after_its_pods,
          "namespace_events_among_the_others": life_namespace_events_among_the_others}

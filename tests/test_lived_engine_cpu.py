@@ -9,15 +9,23 @@ can be checked without a GPU:
     preemption prefix of 0, an inner one and "no prefix helps"; a forecast that flips inside the instants; a headroom forecast
     with copies of 0, inner and CAP, copies and limiting rows that differ between two instants, `first` 0, inner and none; over
     the wide lives a paged gang headroom of 0, inner and CAP, an inner answer that a name of the last page decides, and a
-    deciding (throttle, page) pair that moves to the other page;
+    deciding (throttle, page) pair that moves to the other page; a paged headroom forecast that differs from page 0's alone and
+    one whose `first` lies inside the instants;
   * the named steps of the life ``page_one_decides`` each move the web gang's paged headroom entry;
   * the mirror after each life equals a mirror built in one go from the same final placement, in every field a load reads;
-  * the refused batches are refused for the stated reason alone, behind a negative, larger, odd request."""
+  * the refused batches are refused for the stated reason alone, behind a negative, larger, odd request;
+  * the stretched row layouts (lived_engine.Layout) are faithful — models and oracle on the STRETCHED mirror, answers mapped back by
+    the methods the Stretched engines use, equal the compact mirror's byte for byte at every hold — and cover what they are for:
+    both chunks of the matrix row, a list order that differs from the row order, ties between far rows, a row count that crosses 1024."""
+import copy
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
 import forecast_reference as FR
 import lived_engine as LE
+from kube_throttler_amd import paging
 from kube_throttler_amd import snapshot as S
 
 ALL_LIVES = dict(LE.LIVES, **LE.WIDE_LIVES)
@@ -126,6 +134,23 @@ def _paged_gang_headroom_kinds(life):
     return seen
 
 
+def _paged_headroom_forecast_kinds(life):
+    """The outcome kinds of the paged headroom forecast over one wide life: an answer that differs from what page 0 alone would
+    give (a name of a later page decides copies or limiting row at some instant), and a `first` inside the instants."""
+    seen = set()
+    assert [step for step, _ in life.alone_forecast] == [step for step, _ in life.held]
+    for (_, b), (_, alone) in zip(life.held, life.alone_forecast):
+        for eq in (False, True):
+            ans = b["headroom_forecast", LE.CAP, eq]
+            if isinstance(ans[0], str):
+                continue
+            if not LE.same(ans, alone[eq]):
+                seen.add("paged headroom_forecast differs from page 0's alone")
+            if (ans[0] > 0).any():
+                seen.add("paged headroom_forecast first inner")
+    return seen
+
+
 def test_the_steps_of_page_one_decides_move_the_web_gang(replayed):
     """The web gang's ("headroom_gangs", CAP, False) entry: decided by page 1 once the web throttles leave room, moved by every step
     of PAGE_ONE_STEPS against the step before, and the deciding (throttle, page) pair goes to page 0 and back with copies inner."""
@@ -163,7 +188,7 @@ def test_the_battery_shows_every_outcome_kind(replayed):
     seen = set()
     for life in replayed.values():
         if len(life.mirror.snaps) > 1:
-            seen |= _paged_gang_headroom_kinds(life)
+            seen |= _paged_gang_headroom_kinds(life) | _paged_headroom_forecast_kinds(life)
             continue
         q = life.q
         for _, b in life.held:
@@ -216,6 +241,7 @@ def test_the_battery_shows_every_outcome_kind(replayed):
     want |= {f"headroom_forecast {x}" for x in ("0", "inner", "cap", "first 0", "first inner", "first none",
                                                 "copies differ between two instants", "limiting row differs between two instants")}
     want |= {f"paged headroom_gangs {x}" for x in ("0", "inner", "cap", "page 1 decides an inner answer", "the decider changes page")}
+    want |= {"paged headroom_forecast differs from page 0's alone", "paged headroom_forecast first inner"}
     assert want <= seen, sorted(want - seen)
 
 
@@ -256,3 +282,148 @@ def test_the_refused_batches_break_one_rule_each(case):
               "request-beyond-2^60": int(np.abs(b.ctr_req[1]).max()) > 1 << 60}
     assert [k for k, v in broken.items() if v] == [case]
     assert code == (-4 if case == "request-beyond-2^60" else -2)
+
+
+# ---- the stretched layouts ---------------------------------------------------------------------------------------------------
+FILLER_LIVES = ("selector_and_row_events",)  # the lives whose `fillers` variant is replayed here (the others: too slow, see below)
+STRETCHED = [(name, layout, variant) for name in ALL_LIVES for layout in LE.TMAPS for variant in LE.VARIANTS
+             if variant == "holes" or name in FILLER_LIVES]
+_RUNS = {}
+
+
+def _stretched_run(name, layout, variant, oracle_mod):
+    """One life replayed with a Layout: per hold the models' battery and the oracle's dry reconcile on the stretched mirror (mapped
+    back) next to the compact mirror's, and the stretched snapshots themselves."""
+    key = (name, layout, variant)
+    if key not in _RUNS:
+        lay = LE.Layout(layout, variant)
+        life = LE.Life(oracle_mod, gpu=False, wide=name in LE.WIDE_LIVES, layout=lay)
+        holds = []
+
+        def watch(life, step):
+            got, snaps = LE.stretched_model_battery(life.mirror, life.q, lay, oracle_mod)
+            reconciles = []
+            for m, s in zip(life.mirror.snaps, snaps):
+                rows = LE.responsible(m)
+                reconciles.append((LE.reconcile_answer(oracle_mod, s, lay.thr(rows)), LE.reconcile_answer(oracle_mod, m, rows)))
+            holds.append(SimpleNamespace(step=step, got=got, want=life.held[-1][1], reconciles=reconciles, snaps=snaps,
+                                         q=lay.questions(life.q), lay=lay))
+
+        life.watch = watch
+        ALL_LIVES[name](life)
+        assert len(holds) == len(life.held) >= 5
+        _RUNS[key] = holds
+    return _RUNS[key]
+
+
+@pytest.mark.parametrize("name,layout,variant", STRETCHED, ids=["-".join(x) for x in STRETCHED])
+def test_the_stretched_mirror_answers_as_the_compact_one(name, layout, variant, oracle_mod):
+    """Faithfulness of the harness, before it is trusted on a GPU: at every hold of every life the oracle's reconcile, check and
+    admit and the ``paging.*_of`` models on the stretched mirror (T up to 1100 rows, P up to 4160), mapped back, equal the same on
+    the compact mirror — integers and bytes.  The status matrices' columns outside the map are all zero (Layout.status asserts it).
+    With `fillers` a hold costs about 12 s here (``preempt_context`` walks 2000 filler pods x 500 filler throttles in Python), so
+    that variant replays ``selector_and_row_events`` alone — the life that appends, deletes and re-tenants throttle rows; every
+    other life is dropped from `fillers` HERE (all of LIVES and WIDE_LIVES but that one), and every life runs on `holes`."""
+    holds = _stretched_run(name, layout, variant, oracle_mod)
+    for h in holds:
+        LE.assert_same(h.got, h.want, f"{name} on {h.lay}: '{h.step}': the stretched mirror's battery against the compact one's")
+        assert set(h.got) == set(h.want)
+        for k, (got, want) in enumerate(h.reconciles):
+            assert LE.same(got, want), f"{name} on {h.lay}: '{h.step}': the oracle's reconcile of page {k}"
+
+
+def _without_row(snaps, t):
+    out = []
+    for s in snaps:
+        c = copy.copy(s)
+        c._keep = None
+        c.thr_flags = s.thr_flags.copy()
+        c.thr_flags[t] = 0
+        out.append(c)
+    return out
+
+
+def _ties(h, kind, eq=False):
+    """The ties among one hold's answers of ``kind``: (copies, limiting row L, the other row) where the models answer the same
+    number of copies with throttle row L taken away, and name a row at least a lane above L instead — physical rows."""
+    ans = h.got[kind, LE.CAP, eq]
+    if isinstance(ans[0], str):
+        return []
+    lim = np.asarray(ans[2] if kind == "headroom_forecast" else ans[1])
+    cop = np.asarray(ans[1] if kind == "headroom_forecast" else ans[0])
+    out, ctxs = [], {}
+    n = len(h.q.gang_off) - 1 if kind == "headroom_gangs" else len(h.q.pods)
+    for i in range(n):
+        for l in sorted(set(int(x) for x in np.atleast_1d(lim[i]) if x >= 0)):
+            L = int(h.lay.tmap[l])
+            snaps = _without_row(h.snaps, L)
+            if kind == "headroom":
+                c2, l2 = paging.headroom_of([SimpleNamespace(snapshot=s) for s in snaps], int(h.q.pods[i]), LE.CAP, eq)
+                pairs = [(int(cop[i]), c2, l2)]
+            elif kind == "headroom_gangs":
+                c2, l2, _ = paging.paged_headroom_gangs_of(snaps, h.q.members(i), LE.CAP, eq) if len(snaps) > 1 else \
+                    paging.headroom_gangs_of(snaps[0], h.q.members(i), LE.CAP, eq)
+                pairs = [(int(cop[i]), c2, l2)]
+            else:
+                if L not in ctxs:
+                    ctxs[L] = paging.paged_preempt_context(snaps, LE.NOW) if len(snaps) > 1 else paging.preempt_context(snaps[0], LE.NOW)
+                _, c2, l2 = paging.paged_headroom_forecast_of(snaps, int(h.q.pods[i]), LE.INSTANTS, LE.CAP, LE.WANT, eq, ctx=ctxs[L]) \
+                    if len(snaps) > 1 else paging.headroom_forecast_of(snaps[0], int(h.q.pods[i]), LE.INSTANTS, LE.CAP, LE.WANT, eq, ctx=ctxs[L])
+                pairs = [(int(c), int(a), int(b)) for c, x, a, b in zip(cop[i], lim[i], c2, l2) if x == l]
+            out += [(c, L, int(b)) for c, a, b in pairs if a == c and b >= L + LE.LANE]
+    return out
+
+
+def _list_order_differs(rows):
+    """Within one chunk of the matrix row: two of these rows in one 16-byte lane and one in a higher lane — the affected-throttle
+    list, filled round by round over the lanes, then reads low, HIGH, low."""
+    rows = np.asarray(rows, np.int64)
+    for c in set(rows // LE.CHUNK):
+        lanes = sorted(rows[rows // LE.CHUNK == c] // LE.LANE)
+        for a, b in zip(lanes[:-1], lanes[1:]):
+            if a == b and lanes[-1] > a:
+                return True
+    return False
+
+
+@pytest.mark.parametrize("layout", list(LE.TMAPS))
+def test_what_the_layouts_cover(layout, oracle_mod):
+    """Know what the stretched lives reach (on the stretched mirror, `holes`; the fillers affect no question pod): a question pod
+    with live affecting throttles in both chunks of the matrix row; one whose affecting rows make the list order differ from the
+    row order; for headroom, gang headroom and headroom forecast an answer where two affecting rows at least 16 rows apart allow
+    the same number of copies and the lower one is reported — an inner number of copies among them; a gang over two tiles of pod
+    rows; and on `grow` a life whose row count is at or below 1024 at one hold and above it at a later one."""
+    both = order = 0
+    crossed, ties, inner = [], {}, {}
+    kinds = ("headroom", "headroom_gangs", "headroom_forecast")
+    for name in sorted(ALL_LIVES, key=lambda n: n != "rows_appended"):  # (the life made for ties first: the search stops early)
+        holds = _stretched_run(name, layout, "holes", oracle_mod)
+        counts = [h.snaps[0].n_thr for h in holds]
+        if any(a <= LE.CHUNK < b for i, a in enumerate(counts) for b in counts[i + 1:]):
+            crossed.append(name)
+        for h in holds:
+            for p in sorted(set(int(x) for x in h.q.pods) | set(int(x) for x in h.q.gang_rows)):
+                if not int(h.snaps[0].pod_flags[p]) & S.POD_VALID:
+                    continue
+                err, rows = paging.affected_throttles(h.snaps[0], p)
+                rows = np.asarray(rows, np.int64)
+                both += bool(len(rows) and rows.min() < LE.CHUNK <= rows.max())
+                order += _list_order_differs(rows)
+            for kind in kinds:
+                if not inner.get(kind):
+                    found = _ties(h, kind)
+                    ties[kind] = ties.get(kind, 0) + len(found)
+                    inner[kind] = inner.get(kind, 0) + sum(0 < c < LE.CAP for c, _, _ in found)
+                    if found:
+                        print(f"{layout}: {name}: '{h.step}': {kind} ties (copies, limiting row, the other row): {found[:4]}")
+        q = holds[0].q
+        for g in range(len(q.gang_off) - 1):
+            if len(q.members(g)) > 1:
+                assert len(set(int(r) // LE.TILE for r in q.members(g))) >= 2, f"gang {g} lies in one tile of pod rows"
+    print(f"{layout}: {both} (hold, pod) pairs with affecting rows in both chunks, {order} whose list order differs from the row order, "
+          f"ties {ties} (inner {inner}), row count crosses 1024 in {crossed}")
+    assert both >= 20 and order >= 20
+    for kind in kinds:
+        assert ties[kind] >= 1 and inner[kind] >= 1, f"{kind}: {ties[kind]} ties, {inner[kind]} at an inner number of copies"
+    if layout == "grow":
+        assert "rows_appended" in crossed and "selector_and_row_events" in crossed, crossed

@@ -8,8 +8,13 @@ stored status, Namespace objects), reconciled, and after every further event hel
   * itself: a second run of the battery equals the first (queries are dry).
 The battery is check, dry admit, dry admit_gangs, headroom, headroom_gangs, headroom_forecast, preempt and preempt_gangs with and
 without reprieve, forecast, forecast_gangs, override_instants and fetch_reserved, for both ``on_equal`` values; on two pages the
-paged entry points, the paged gang headroom among them.  tests/test_lived_engine_cpu.py shows
-on the models alone that every event of every life moves an answer and that the lives show every kind of outcome.  No tolerance."""
+paged entry points, the paged gang headroom and the paged headroom forecast among them.  tests/test_lived_engine_cpu.py shows
+on the models alone that every event of every life moves an answer and that the lives show every kind of outcome.  No tolerance.
+
+``test_a_life_on_a_stretched_layout`` runs every life once more on engines of 1100 throttle rows and 4160 pod rows, its rows spread
+by a lived_engine.Layout over both chunks of the matrix row and over 65 tiles of pod rows (`straddle`, `grow`), the rows in between
+empty (`holes`) or holding records that affect nothing (`fillers`); there Life.hold also compares the physical status matrices of
+live engine and twin over all 1100 columns and asserts that the columns outside the layout are zero."""
 import numpy as np
 import pytest
 
@@ -49,6 +54,11 @@ def test_selector_and_row_events(oracle_mod):
 def test_reservations_survive(oracle_mod):
     """fetch_reserved is part of the battery: it equals the mirror at every step."""
     assert len(live(LE.life_reservations_survive, oracle_mod)) == 6
+
+
+def test_rows_appended(oracle_mod):
+    """Second copies of limiting throttles in appended rows: ties, the lower row of a tie deleted and back."""
+    assert len(live(LE.life_rows_appended, oracle_mod)) == 6
 
 
 def test_two_pages_live(oracle_mod):
@@ -111,6 +121,30 @@ def test_namespace_events_among_the_others(oracle_mod):
 def test_namespace_events_on_two_pages(script, steps, oracle_mod):
     """Every event reaches both pages' engines; paged_reconcile and the paged battery follow."""
     assert len(live(script, oracle_mod, wide=True)) == steps
+
+
+STEPS = {"pod_events": 8, "threshold_and_override_events": 6, "selector_and_row_events": 7, "reservations_survive": 6,
+         "negative_came_and_went": 5, "rows_appended": 6, "namespace_labels": 7, "namespace_deleted_and_back": 8,
+         "namespace_arrives_after_its_pods": 6, "namespace_events_among_the_others": 7, "two_pages": 7, "page_one_decides": 7,
+         "negative_on_page_one": 5, "namespace_labels_wide": 7, "namespace_deleted_and_back_wide": 8}
+STRETCHED = [(name, layout, variant) for name in list(LE.LIVES) + list(LE.WIDE_LIVES) for layout in LE.TMAPS for variant in LE.VARIANTS]
+
+
+@pytest.mark.parametrize("name,layout,variant", STRETCHED, ids=["-".join(x) for x in STRETCHED])
+def test_a_life_on_a_stretched_layout(name, layout, variant, oracle_mod):
+    """The same life, event for event and hold for hold, on Stretched engines: `straddle` puts the twelve throttles on both sides
+    of row 1023/1024 and two of one pod's into one lane below a third, `grow` lets the first appended row carry the live engine's
+    row count across 1024 behind answered queries; the pods lie on the edges of tiles 0, 1, 2, 32, 64 and 65.  What the life
+    asserts about compiles() holds here too; kernel names and packed_words() belong to the compact cluster and are not asked."""
+    wide = name in LE.WIDE_LIVES
+    life = LE.Life(oracle_mod, gpu=True, wide=wide, layout=LE.Layout(layout, variant))
+    try:
+        (LE.WIDE_LIVES if wide else LE.LIVES)[name](life)
+        assert len(life.held) == len(life.live_held) == STEPS[name]
+        counts = [e.raw.throttle_rows() for e in life.engines]
+        assert all(LE.CHUNK <= c <= LE.T_PHYS for c in counts), counts
+    finally:
+        life.close()
 
 
 def _fingerprint(eng):
