@@ -675,11 +675,56 @@ int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_firs
  *      forecast result as its third kind: a later forecast launch of any kind replaces it; kt_forecast_fetch and
  *      kt_forecast_gangs_fetch after this launch answer KT_ERR_NOT_READY, and kt_headroom_forecast_fetch answers it after theirs.
  *      kt_headroom_forecast_fetch synchronises.
- *      More than KT_MAX_DIMS resource names: kt_paged_headroom_forecast.  Out of scope: gangs, several ranks. --------------- */
+ *      More than KT_MAX_DIMS resource names: kt_paged_headroom_forecast.  Whole gangs: kt_headroom_forecast_gangs_launch.  Out of
+ *      scope: several ranks. ----------------------------------------------------------------------------------------------- */
 int32_t kt_headroom_forecast_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_inst, const int64_t* inst_s,
                                     const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want, void* stream);
 int32_t kt_headroom_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first /* [n], nullable */,
                                    int64_t* out_copies /* [n][n_inst], nullable */, int32_t* out_limiting /* [n][n_inst], nullable */);
+/* ---- headroom forecast, for gangs: how many copies of a whole gang the throttles admit at each instant — kt_headroom_gangs_launch
+ *      ("how many, now") and kt_forecast_gangs_launch ("whether, when") asked at once: how many more replicas of a training job
+ *      fit once the night override begins, and at which instant `want` of them fit.
+ *      The notation (instants t_0 < .. < t_{m-1}, state R_t) and the rule about throttles that keep their stored status are those of
+ *      kt_forecast_launch; gang g is the queue positions [gang_off[g], gang_off[g + 1]) as in kt_admit_gangs_launch.
+ *      out_copies[g][k], out_blocker[g][k] and out_limiting[g][k] (each nullable, [n_gangs][n_inst]) are exactly what
+ *      kt_headroom_gangs_launch defines, evaluated with R_{t_k} as the stored status: the number of leading admitted gangs of a dry
+ *      kt_admit_gangs_launch over `cap` consecutive copies of the gang; the queue position (index into pod_rows) of the first member
+ *      of the first refused copy that is not Success; the lowest throttle row that stops that member at its turn.  Blocker and
+ *      limiting are -1 where all `cap` copies are admitted, limiting also where the blocker's verdict is an Error.
+ *      A gang with an Error or invalid member reports 0 copies at every instant; its walk ends in front of that member, and an earlier
+ *      member that some throttle stops at t_k is the blocker there.  A gang no throttle affects: `cap`, -1, -1 and first 0.
+ *      out_first[g] (nullable) is the smallest k with out_copies[g][k] >= want, or KT_FORECAST_NONE.
+ *      Identities:
+ *        (G1) a gang of one pod reports byte for byte the first, copies and limiting that kt_headroom_forecast_launch reports for
+ *             that pod; its blocker is its own position where copies < cap, else -1.
+ *        (G2) with cap == want == 1, out_copies[g][k] == 1 exactly where kt_forecast_gangs_launch reports KT_VERDICT_SUCCESS, and
+ *             out_first and out_blocker are byte for byte those of kt_forecast_gangs_fetch.
+ *        (G3) with inst = [t] on an engine whose last action was kt_reconcile_launch(t, KT_RECONCILE_APPLY) plus fetch, column 0 is
+ *             byte for byte what kt_headroom_gangs_launch plus fetch report with the same cap and on_equal.
+ *        (G4) the call is a dry run: stored status, reserved amounts and a pending kt_aggregate_launch's sums are unchanged.
+ *      One kt_check launch with the status matrix over pod_rows, the aggregate and dry finalize (at t_0) of kt_forecast_launch, and
+ *      one launch of kt_headroom_forecast_gangs (csrc/kt_kernels_headroom_forecast_gangs.hip): one wave per gang, lane = instant
+ *      position; the lane computes its instant's threshold as kt_forecast_gangs does and bisects the copies of its OWN instant, every
+ *      probe judged by the gang walk of admission itself with the candidate's reserved row (1 + 31 rounds at the most); the answer
+ *      is the lexicographic minimum of (copies, blocker, throttle row) over the affecting throttles.
+ *      Refused before anything is launched, in this order: the instants as kt_forecast_launch refuses them and a missing array; cap
+ *      outside [1, KT_HEADROOM_MAX_CAP], then want outside [1, cap]; every gang_off defect kt_admit_gangs_launch refuses, a pod named
+ *      twice within ONE gang (KT_ERR_INVALID_ARGUMENT); a pod row outside the table; n x throttle_rows or n_gangs x n_inst > 2^31
+ *      (KT_ERR_OUT_OF_RANGE); what kt_forecast_gangs_launch refuses as unsupported (the |request| sums probe runs first where the sums
+ *      are not known); an engine that has been fed a negative request — the search over the copies rests on sums that only grow,
+ *      kt_headroom_forecast_launch serves such an engine pod by pod (KT_ERR_UNSUPPORTED).  A refused call leaves the check slot, the
+ *      reconcile report and every result buffer alone.  n == 0 is allowed only with n_gangs == 0: KT_OK, nothing is launched.
+ *      Slots: those of kt_forecast_gangs_launch; a pending preempt result of any kind stays fetchable.  The result SHARES the one
+ *      pending forecast result as its fourth kind: a later forecast launch of any kind replaces it, and each of the four fetches
+ *      answers KT_ERR_NOT_READY after a launch of another kind.  kt_headroom_forecast_gangs_fetch synchronises.
+ *      Out of scope: more than KT_MAX_DIMS resource names (pages), several ranks. ----------------------------------------------- */
+int32_t kt_headroom_forecast_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                          int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, int64_t cap,
+                                          int64_t want, void* stream);
+int32_t kt_headroom_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first /* [n_gangs], nullable */,
+                                         int64_t* out_copies /* [n_gangs][n_inst], nullable */,
+                                         int32_t* out_limiting /* [n_gangs][n_inst], nullable */,
+                                         int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
 /* The sorted, distinct instants in (from, until] at which the CalculateThreshold of some valid and responsible throttle can change:
  * every parsed non-zero `begin` of an override, and for every parsed non-zero `end` the instant end + 1 ns — the FIRST instant at
  * which the override is no longer active.  That is deliberately not the `end` that NextOverrideHappensIn

@@ -435,6 +435,44 @@ func (e *Engine) HeadroomForecast(rows, instS []int64, instNs []int32, onEqual b
 	return first, copies, limiting, nil
 }
 
+// HeadroomForecastGangs answers HeadroomForecast's question for whole gangs: gang g is rows[gangOff[g]:gangOff[g+1]] (gangOff
+// starts at 0 and ends at len(rows)); for every gang and every instant, how many consecutive copies of the gang an in-order, all
+// or nothing admission admits once every valid and responsible throttle has been reconciled at that instant
+// (kt_headroom_forecast_gangs_launch + kt_headroom_forecast_gangs_fetch).  With m = len(instS): copies[g*m+k] in [0, cap],
+// blocker[g*m+k] the index into rows of the first member of the first refused copy that is not admitted, limiting[g*m+k] the
+// lowest throttle row that stops it (both -1: all cap copies fit; limiting also -1 where the blocker's PreFilter is an error),
+// first[g] the smallest k with at least want copies or -1.  A dry run: stored status and reserved amounts stay.  An engine that
+// was fed a negative request is refused (HeadroomForecast serves it pod by pod).  Launch and fetch run under e.mu, like every
+// other user of the check slot.  One engine only: there is no paged form.  Not compiled in this repository (no Go toolchain in
+// its build).
+func (e *Engine) HeadroomForecastGangs(rows, gangOff, instS []int64, instNs []int32, onEqual bool, cap, want int64) (first, copies []int64, limiting []int32, blocker []int64, err error) {
+	e.mu.Lock() // the check slot is one per engine: see mu
+	defer e.mu.Unlock()
+	if len(rows) == 0 {
+		return nil, nil, nil, nil, nil
+	}
+	if len(gangOff) < 2 {
+		return nil, nil, nil, nil, fmt.Errorf("HeadroomForecastGangs: %d offsets for %d rows", len(gangOff), len(rows))
+	}
+	if len(instS) == 0 || len(instS) != len(instNs) {
+		return nil, nil, nil, nil, fmt.Errorf("HeadroomForecastGangs: %d seconds and %d nanoseconds", len(instS), len(instNs))
+	}
+	nGangs := len(gangOff) - 1
+	if rc := C.kt_headroom_forecast_gangs_launch(e.h, C.int64_t(len(rows)), i64(rows), C.int64_t(nGangs), i64(gangOff), C.int64_t(len(instS)),
+		i64(instS), i32(instNs), b2i(onEqual), C.int64_t(cap), C.int64_t(want), nil); rc != C.KT_OK {
+		return nil, nil, nil, nil, e.err(rc)
+	}
+	first = make([]int64, nGangs)
+	copies = make([]int64, nGangs*len(instS))
+	limiting = make([]int32, nGangs*len(instS))
+	blocker = make([]int64, nGangs*len(instS))
+	if rc := C.kt_headroom_forecast_gangs_fetch(e.h, C.int64_t(nGangs), (*C.int64_t)(unsafe.Pointer(&first[0])),
+		(*C.int64_t)(unsafe.Pointer(&copies[0])), (*C.int32_t)(unsafe.Pointer(&limiting[0])), (*C.int64_t)(unsafe.Pointer(&blocker[0]))); rc != C.KT_OK {
+		return nil, nil, nil, nil, e.err(rc)
+	}
+	return first, copies, limiting, blocker, nil
+}
+
 // Preempt answers, for every blocked pod row of rows, the shortest prefix of the caller-ordered candidate list cands (typically
 // ascending priority) whose deletion, followed by a reconcile of every throttle at now, makes PreFilter Success
 // (kt_preempt_launch + kt_preempt_fetch): prefix[i] in [0, len(cands)], 0 = the pod already passes against a fresh reconcile,

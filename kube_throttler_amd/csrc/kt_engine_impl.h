@@ -222,7 +222,7 @@ extern thread_local std::string g_create_error;  // text of the last kt_engine_c
 enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSw_NO_MATCH_CACHE_AGG, kSw_NO_MATCH_CODES, kSw_NO_MATCH_CODES_AGG, kSw_NO_TILE_PAIRS_CHECK, kSwCount };
 static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE", "KT_NO_MATCH_CACHE_AGG", "KT_NO_MATCH_CODES", "KT_NO_MATCH_CODES_AGG", "KT_NO_TILE_PAIRS_CHECK"};
 // which launch the one pending forecast result belongs to: only that launch's fetch may read it
-enum ForecastKind { kForecastPods, kForecastGangs, kForecastHeadroom };
+enum ForecastKind { kForecastPods, kForecastGangs, kForecastHeadroom, kForecastHeadroomGangs };
 struct kt_engine {
   bool sw[kSwCount] = {};  // EnvSwitch values (load_env_switches)
   uint32_t reprieve_lds_cap_limit = 0;  // KT_REPRIEVE_LDS_CAP (test hook, read with the switches): at most so many list entries of
@@ -409,7 +409,9 @@ struct kt_engine {
   ForecastKind forecast_kind = kForecastPods;
   DevBuf<int64_t> d_forecast_gang_off, d_forecast_blocker;
   // kt_headroom_forecast_launch shares it as the third kind (first per pod in d_forecast_first, forecast_n = the pods); its copies
-  // and limiting rows [n][n_inst] live in buffers of their own
+  // and limiting rows [n][n_inst] live in buffers of their own.  kt_headroom_forecast_gangs_launch is the fourth kind (first per
+  // GANG, forecast_n = the gangs): copies and limiting [n_gangs][n_inst] in these, the blocking member in d_forecast_blocker, the
+  // offsets in d_forecast_gang_off
   DevBuf<int64_t> d_forecast_copies;
   DevBuf<int32_t> d_forecast_limiting;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap

@@ -101,16 +101,17 @@ static int32_t stored_used_fits(kt_engine* e, const char* what, int page, const 
   return e->fail(KT_ERR_UNSUPPORTED, "%s: the stored `used` of page %d is wider than int64 (%s reads int64 tables)", what, page, kernel);
 }
 // ... and the gang forms search over the copies, which takes sums that only grow
-static int32_t sums_only_grow(kt_engine* e, int page) {
+static int32_t sums_only_grow(kt_engine* e, const char* what, int page, const char* pod_by_pod = "kt_headroom_launch") {
   if (!e->neg_seen) return KT_OK;
   if (page < 0)
     return e->fail(KT_ERR_UNSUPPORTED,
-                   "headroom gangs: the engine has been fed a negative request; the search over the copies rests on sums that only grow "
-                   "(kt_headroom_launch serves such an engine pod by pod)");
+                   "%s: the engine has been fed a negative request; the search over the copies rests on sums that only grow "
+                   "(%s serves such an engine pod by pod)",
+                   what, pod_by_pod);
   return e->fail(KT_ERR_UNSUPPORTED,
-                 "headroom gangs: page %d has been fed a negative request; the search over the copies rests on sums that only grow "
+                 "%s: page %d has been fed a negative request; the search over the copies rests on sums that only grow "
                  "(kt_paged_headroom serves such pages pod by pod)",
-                 page);
+                 what, page);
 }
 
 static int32_t cap_in_range(kt_engine* e, const char* what, int64_t cap) {
@@ -371,7 +372,7 @@ int32_t kt_headroom_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_row
   if ((rc = cap_in_range(e, what, cap)) != KT_OK) return rc;
   if ((rc = matrix_fits(e, what, T, n)) != KT_OK) return rc;
   if ((rc = stored_used_fits(e, what, -1, "kt_headroom_gangs")) != KT_OK) return rc;
-  if ((rc = sums_only_grow(e, -1)) != KT_OK) return rc;
+  if ((rc = sums_only_grow(e, what, -1)) != KT_OK) return rc;
   e->headroom_ready = false, e->headroom_gangs = false;
   if (n == 0) {  // (no gangs) nothing is launched
     e->headroom_ready = true, e->headroom_gangs = true, e->headroom_n = 0;
@@ -430,7 +431,7 @@ int32_t kt_paged_headroom_gangs(kt_engine* const* pages, int32_t n_pages, int64_
   if ((rc = matrix_fits(e0, what, T, n)) != KT_OK) return rc;
   for (int32_t k = 0; k < n_pages; ++k) {
     if ((rc = stored_used_fits(pages[k], what, k, "kt_headroom_gangs_paged")) != KT_OK) return rc;
-    if ((rc = sums_only_grow(pages[k], k)) != KT_OK) return rc;
+    if ((rc = sums_only_grow(pages[k], what, k)) != KT_OK) return rc;
   }
   if (n == 0) return KT_OK;  // (no gangs) nothing is launched
   if ((rc = c.order()) != KT_OK) return rc;
@@ -905,6 +906,79 @@ int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_firs
   if (n_gangs == 0) return KT_OK;
   const size_t ng = (size_t)n_gangs, ver = ng * (size_t)e->forecast_m;
   return fetch_out(e, {{out_first, e->d_forecast_first.p, ng * 8}, {out_verdicts, e->d_forecast_verdicts.p, ver}, {out_blocker, e->d_forecast_blocker.p, ver * 8}});
+}
+
+// ---------------------------------------------------------------------------------------------------
+// headroom forecast, for gangs: how many copies of a whole gang the throttles admit at each instant
+// (kt_kernels_headroom_forecast_gangs.hip)
+// ---------------------------------------------------------------------------------------------------
+// forecast_gangs_locked's sequence with kt_headroom_forecast_gangs in kt_forecast_gangs' place: the refusals in its order (cap and
+// want behind the instants, as the headroom forecast), the |request| sums probe, and behind it the last refusal — the search over
+// the copies takes sums that only grow; then ONE check, the dry aggregate and finalize at t_0, the kernel.  The result shares the
+// one pending forecast result as its fourth kind.  The caller holds the launch lock.
+static int32_t headroom_forecast_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                              int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, int64_t cap,
+                                              int64_t want, void* stream) {
+  const char *what = "headroom forecast gangs", *kernel = "kt_headroom_forecast_gangs";
+  const int32_t T = e->thr_rows_hi;  // (moved by throttle batches only, under this lock: ensure_ready below does not change it)
+  int32_t rc;
+  if ((rc = forecast_instants_valid(e, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) != KT_OK) return rc;
+  if ((rc = cap_in_range(e, what, cap)) != KT_OK) return rc;
+  if ((rc = want_in_range(e, what, want, cap)) != KT_OK) return rc;
+  if ((rc = gangs_valid(e, n, n_gangs, gang_off)) != KT_OK) return rc;
+  if ((rc = no_row_twice_in_a_gang(e, what, pod_rows, n_gangs, gang_off)) != KT_OK) return rc;
+  if ((rc = rows_in_range(e, what, n, pod_rows)) != KT_OK) return rc;
+  if ((rc = matrix_fits(e, what, T, n)) != KT_OK || (rc = verdicts_fit(e, what, n_gangs, n_inst, "n_gangs", "results")) != KT_OK) return rc;
+  if ((rc = serves_dry_reconcile(e, what, -1, kernel)) != KT_OK) return rc;
+  if (n == 0) {  // (no gangs) nothing is launched
+    e->forecast_ready = true, e->forecast_kind = kForecastHeadroomGangs, e->forecast_n = 0, e->forecast_m = n_inst;
+    return KT_OK;
+  }
+  KT_HIP(e, hipSetDevice(e->device));
+  hipStream_t s = pick_stream(e, stream);
+  if ((rc = ensure_ready(e, s)) != KT_OK || (rc = sums_fit_int64(e, what, -1, kernel, s)) != KT_OK) return rc;
+  if ((rc = sums_only_grow(e, what, -1, "kt_headroom_forecast_launch")) != KT_OK) return rc;
+  e->forecast_ready = false;
+  const size_t ng = (size_t)n_gangs, m = (size_t)n_inst, cells = ng * m;
+  if ((rc = reserve_behind_last_stream(e, {{e->d_forecast_first, ng}, {e->d_forecast_copies, cells}, {e->d_forecast_limiting, cells}, {e->d_forecast_blocker, cells}, {e->d_forecast_inst_s, m}, {e->d_forecast_inst_ns, m}, {e->d_forecast_gang_off, ng + 1}})) != KT_OK)
+    return rc;
+  // the instants and the offsets travel on the launch's stream, behind an earlier forecast's kernel; the caller's memory is not
+  // referenced after return
+  KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_s.p, inst_s, m * 8, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_ns.p, inst_ns, m * 4, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipMemcpyAsync(e->d_forecast_gang_off.p, gang_off, (ng + 1) * 8, hipMemcpyHostToDevice, s));
+  KT_HIP(e, hipStreamSynchronize(s));
+  if ((rc = query_check(e, n, pod_rows, on_equal, s, &kt_engine::preempt_ready)) != KT_OK) return rc;  // over the members of all gangs
+  // the aggregate with exact contributor counts and the error bytes; the dry finalize runs at t_0
+  if ((rc = preempt_reconcile_locked(e, inst_s[0], inst_ns[0], s)) != KT_OK) return rc;
+  kt::launch_headroom_forecast_gangs(admit_page_of(e), n_gangs, n_inst, e->d_rows.p, e->d_forecast_gang_off.p, e->d_forecast_inst_s.p,
+                                     e->d_forecast_inst_ns.p, T, on_equal != 0, (uint32_t)cap, (uint32_t)want, e->d_status.p, e->d_summary.p,
+                                     e->d_preempt_partial.p, e->d_out_error.p, e->d_forecast_first.p, e->d_forecast_copies.p,
+                                     e->d_forecast_limiting.p, e->d_forecast_blocker.p, s);
+  KT_HIP(e, hipGetLastError());
+  e->last_stream = s;
+  e->forecast_ready = true, e->forecast_kind = kForecastHeadroomGangs, e->forecast_n = n_gangs, e->forecast_m = n_inst;
+  return KT_OK;
+}
+
+int32_t kt_headroom_forecast_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_inst,
+                                          const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  return headroom_forecast_gangs_locked(e, n, pod_rows, n_gangs, gang_off, n_inst, inst_s, inst_ns, on_equal, cap, want, stream);
+}
+
+int32_t kt_headroom_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first, int64_t* out_copies, int32_t* out_limiting,
+                                         int64_t* out_blocker) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (int32_t bad = fetch_ready(e, e->forecast_ready && e->forecast_kind == kForecastHeadroomGangs, "headroom_forecast_gangs", "headroom forecast gangs",
+                                true, n_gangs, e->forecast_n))
+    return bad;
+  if (n_gangs == 0) return KT_OK;
+  const size_t ng = (size_t)n_gangs, cells = ng * (size_t)e->forecast_m;
+  return fetch_out(e, {{out_first, e->d_forecast_first.p, ng * 8}, {out_copies, e->d_forecast_copies.p, cells * 8}, {out_limiting, e->d_forecast_limiting.p, cells * 4}, {out_blocker, e->d_forecast_blocker.p, cells * 8}});
 }
 
 // ---------------------------------------------------------------------------------------------------

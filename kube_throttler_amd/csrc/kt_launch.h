@@ -216,6 +216,13 @@ void launch_forecast_gangs(const AdmitPage& pg, int64_t n_gangs, int64_t m, cons
                            const int64_t* inst_s, const int32_t* inst_ns, int T, bool on_equal, const uint8_t* status, const uint64_t* summary,
                            const unsigned long long* partial, const uint8_t* error, int64_t* first, uint8_t* verdicts, int64_t* blocker,
                            hipStream_t s);
+// how many copies of a whole gang the throttles admit at each instant (kt_kernels_headroom_forecast_gangs.hip): one wave per gang,
+// lane = instant position, every lane searches the copies of its own instant.  launch_forecast_gangs' inputs plus cap and want
+// (1 <= want <= cap <= 2^31 - 1); first [n_gangs], copies [n_gangs][m], limiting [n_gangs][m] and blocker [n_gangs][m] out
+void launch_headroom_forecast_gangs(const AdmitPage& pg, int64_t n_gangs, int64_t m, const int64_t* rows_dev, const int64_t* gang_off_dev,
+                                    const int64_t* inst_s, const int32_t* inst_ns, int T, bool on_equal, uint32_t cap, uint32_t want,
+                                    const uint8_t* status, const uint64_t* summary, const unsigned long long* partial, const uint8_t* error,
+                                    int64_t* first, int64_t* copies, int32_t* limiting, int64_t* blocker, hipStream_t s);
 // ... over n_pages >= 1 pages (kt_kernels_forecast_gangs_paged.hip): the descriptors of launch_forecast_paged, copied to pages_dev and
 // guarded by pages_copied as there; status / summary: ONE check of page 0 over rows_dev [n], the members of all gangs; first
 // [n_gangs], verdicts [n_gangs][m] and blocker [n_gangs][m] out, on page 0.  false: the copy failed (*hip_err)

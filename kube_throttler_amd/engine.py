@@ -46,6 +46,7 @@ EXPORTS = [
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
     "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch", "kt_paged_headroom_gangs",
     "kt_headroom_forecast_launch", "kt_headroom_forecast_fetch", "kt_paged_headroom_forecast",
+    "kt_headroom_forecast_gangs_launch", "kt_headroom_forecast_gangs_fetch",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -435,6 +436,9 @@ def lib():
         L.kt_forecast_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                C.c_int32, C.c_void_p]
         L.kt_forecast_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kt_headroom_forecast_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                        C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]
+        L.kt_headroom_forecast_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_override_instants.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_int64)]
         _LIB = L
@@ -1002,6 +1006,40 @@ class Engine:
         copies int64 [n][n_inst], limiting int32 [n][n_inst]).  A dry run: stored status and reserved amounts stay as they are."""
         self.headroom_forecast_launch(pod_rows, instants, cap, want, on_equal)
         return self.headroom_forecast_fetch(len(pod_rows), len(instants))
+
+    # ---- headroom forecast, for gangs: how many copies of a whole gang the throttles admit at each instant
+    def headroom_forecast_gangs_launch(self, pod_rows, gang_off, instants, cap, want=1, on_equal=False, stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        g = _gang_offsets(gang_off)
+        inst_s = np.ascontiguousarray([int(t[0]) for t in instants], dtype=np.int64)
+        inst_ns = np.ascontiguousarray([int(t[1]) for t in instants], dtype=np.int32)
+        m = len(inst_s)
+        self._ck(lib().kt_headroom_forecast_gangs_launch(self._h, len(a), p if len(a) else None, len(g) - 1, g.ctypes.data, m,
+                                                         inst_s.ctypes.data if m else None, inst_ns.ctypes.data if m else None,
+                                                         int(on_equal), int(cap), int(want), stream))
+
+    def headroom_forecast_gangs_fetch(self, n_gangs, n_inst, want_copies=True, want_limiting=True, want_blocker=True):
+        cells = max(n_gangs * n_inst, 1)
+        first = np.zeros(max(n_gangs, 1), np.int64)
+        copies = np.zeros(cells, np.int64) if want_copies else None
+        limiting = np.zeros(cells, np.int32) if want_limiting else None
+        blk = np.zeros(cells, np.int64) if want_blocker else None
+        self._ck(lib().kt_headroom_forecast_gangs_fetch(self._h, n_gangs, first.ctypes.data, None if copies is None else copies.ctypes.data,
+                                                        None if limiting is None else limiting.ctypes.data,
+                                                        None if blk is None else blk.ctypes.data))
+        shaped = lambda x: None if x is None else x[:n_gangs * n_inst].reshape(n_gangs, n_inst)
+        return first[:n_gangs], shaped(copies), shaped(limiting), shaped(blk)
+
+    def headroom_forecast_gangs(self, pod_rows, gang_off, instants, *, cap, want=1, on_equal=False):
+        """kt_headroom_forecast_gangs_launch + kt_headroom_forecast_gangs_fetch: per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]``
+        and per instant the number of leading admitted gangs a dry-run gang admission of ``cap`` consecutive copies of the gang
+        returns once every valid and responsible throttle has been reconciled at that instant (each on the state as it is now), the
+        lowest throttle row that stops the first member of the first refused copy that is not admitted, that member's queue
+        position (both -1: all ``cap`` are admitted), and the first position with at least ``want`` copies (FORECAST_NONE: none)
+        -> (first int64 [n_gangs], copies int64 [n_gangs][n_inst], limiting int32 [n_gangs][n_inst], blocker int64
+        [n_gangs][n_inst]).  A dry run: stored status and reserved amounts stay as they are."""
+        self.headroom_forecast_gangs_launch(pod_rows, gang_off, instants, cap, want, on_equal)
+        return self.headroom_forecast_gangs_fetch(len(_gang_offsets(gang_off)) - 1, len(instants))
 
     def override_instants(self, from_, until, cap=None):
         """kt_override_instants: the sorted, distinct instants in (from_, until] at which some valid and responsible throttle's

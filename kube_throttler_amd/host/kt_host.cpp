@@ -1534,6 +1534,65 @@ GangRetryAfterResult KubeThrottler::RetryAfterGang(const std::vector<std::string
   return res;
 }
 
+// When do `want` further replicas of this gang fit: RetryAfter's instants, one kt_headroom_forecast_gangs_launch +
+// kt_headroom_forecast_gangs_fetch with the members as ONE gang and cap = want on the mirror's one engine (isThrottledOnEqual =
+// false, as PreFilter).  Nothing is changed.
+GangScaleAfterResult KubeThrottler::ScaleAfterGang(const std::vector<std::string>& member_keys, int64_t want, const std::string& now_rfc3339,
+                                                   int64_t horizon_seconds) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  GangScaleAfterResult res;
+  ScaleAfterResult& out = res.scale;
+  std::vector<int64_t> inst_s;
+  std::vector<int32_t> inst_ns;
+  if (!retry_after_instants(p, "ScaleAfterGang", "gang headroom forecast", now_rfc3339, horizon_seconds, &inst_s, &inst_ns, &out.error)) return res;
+  if (member_keys.empty()) {
+    out.error = "ScaleAfterGang: a gang without members";
+    return res;
+  }
+  std::vector<int64_t> rows(member_keys.size());
+  std::set<std::string> seen;
+  for (size_t i = 0; i < rows.size(); ++i) {
+    if ((rows[i] = p.pod_rows.find(member_keys[i])) < 0) {
+      out.error = "pod " + member_keys[i] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+    if (!seen.insert(member_keys[i]).second) {  // (it would reserve twice: the engine refuses it too)
+      out.error = "ScaleAfterGang: pod " + member_keys[i] + " is a member twice";
+      return res;
+    }
+  }
+  if (want < 1) {
+    out.error = "ScaleAfterGang: want " + std::to_string(want);
+    return res;
+  }
+  const int64_t m = (int64_t)inst_s.size();
+  const int64_t gang_off[2] = {0, (int64_t)rows.size()};
+  int64_t first = KT_FORECAST_NONE;
+  std::vector<int32_t> limiting((size_t)m, -1);
+  std::vector<int64_t> blockers((size_t)m, -1);
+  out.copies_at.assign((size_t)m, 0);
+  int32_t rc = kt_headroom_forecast_gangs_launch(p.e, (int64_t)rows.size(), rows.data(), 1, gang_off, m, inst_s.data(), inst_ns.data(),
+                                                 /*isThrottledOnEqual=*/0, /*cap=*/want, want, nullptr);
+  if (rc == KT_OK) rc = kt_headroom_forecast_gangs_fetch(p.e, 1, &first, out.copies_at.data(), limiting.data(), blockers.data());
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    out.copies_at.clear();
+    return res;
+  }
+  for (int64_t k = 0; k < m; ++k) {
+    out.instants.emplace_back(inst_s[(size_t)k], inst_ns[(size_t)k]);
+    const int32_t t = limiting[(size_t)k];
+    out.limiting_at.push_back(t >= 0 && (size_t)t < p.thr_by_row.size() && p.thr_live[(size_t)t] ? p.thr_by_row[(size_t)t].Key() : std::string());
+    const int64_t b = blockers[(size_t)k];
+    res.blockers_at.push_back(b >= 0 && (size_t)b < member_keys.size() ? member_keys[(size_t)b] : std::string());
+  }
+  RetryAfterResult at;  // (the instant's text is RetryAfter's)
+  retry_after_first(at, first, inst_s, inst_ns);
+  out.found = at.has, out.instantSec = at.instantSec, out.instantNsec = at.instantNsec, out.instant = at.instant;
+  return res;
+}
+
 // A scheduling pass over a queue of GANGS (jobs whose pods only run together), in order: every member gets PreFilter and, on
 // Success, Reserve; a gang with a member that did not succeed gets Unreserve for all its members (plugin.go:240-257) before the next
 // gang is looked at — ONE engine launch per segment (kt_paged_admit_gangs) instead of up to 3 x n calls.  Segments end on gang

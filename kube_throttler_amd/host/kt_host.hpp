@@ -212,6 +212,15 @@ struct ScaleAfterResult {
   std::string error;             // not empty: the call failed (unknown pod, want < 1, a paged mirror, engine error)
 };
 
+// ScaleAfterGang: the first instant at which `want` further replicas of a whole gang fit, how many fit at each judged instant and
+// which member stops the next one
+struct GangScaleAfterResult {
+  ScaleAfterResult scale;                // found / instant / instants / copies_at / limiting_at / error as for ScaleAfter, for the gang as
+                                         // a whole (limiting is empty too where the blocker's PreFilter is an Error)
+  std::vector<std::string> blockers_at;  // per judged instant the Pod::Key() of the first member of replica number copies_at that is
+                                         // not admitted; empty: all `want` fit
+};
+
 // KubeThrottlerPluginArgs (pkg/scheduler_plugin/plugin_args.go:33-40) + engine sizing
 struct PluginArgs {
   std::string name;                 // throttler name (required)
@@ -313,6 +322,15 @@ class KubeThrottler {
   // scales a Job up for the night window.  A dry run; the reserved totals are read as they stand.  An unknown key, want < 1 and a
   // mirror on several pages answer an error.
   ScaleAfterResult ScaleAfter(const std::string& pod_key, int64_t want, const std::string& now_rfc3339, int64_t horizon_seconds);
+
+  // The same for a gang: per instant of now ++ the override boundaries the number of further whole replicas of the members' shapes
+  // that AdmitGangs would admit one after the other if every throttle were reconciled then (at most `want`), the throttle and the
+  // member that stop the next one, and the first instant at which all `want` fit.  Each admitted member reserves against the
+  // throttles the later members and the later replicas meet: the members' own ScaleAfter answers do not compose into this one.
+  // ONE kt_headroom_forecast_gangs_launch over now ++ boundaries with cap = want.  A dry run; a member named twice, an unknown key,
+  // an empty gang, want < 1 and a mirror on several pages answer an error.
+  GangScaleAfterResult ScaleAfterGang(const std::vector<std::string>& member_keys, int64_t want, const std::string& now_rfc3339,
+                                      int64_t horizon_seconds);
 
   // ---- reconcile of every responsible throttle at `now` (RFC3339); fills per-throttle status by Key()
   bool ReconcileAll(const std::string& now_rfc3339, std::map<std::string, ThrottleStatus>* out, std::string* err);

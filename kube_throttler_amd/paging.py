@@ -1179,6 +1179,116 @@ def headroom_gangs_of(snap, member_rows, cap, on_equal=False):
     return (cap, -1, -1) if h >= cap else (h, t, first)
 
 
+# ---- headroom forecast, for gangs (kt_headroom_forecast_gangs_launch), as the kernel computes it, on a Snapshot ----
+def headroom_forecast_gangs_of(snap, member_rows, instants, cap, want=1, on_equal=False, ctx=None):
+    """kt_headroom_forecast_gangs_launch for one gang, restated on a Snapshot (no GPU) -> (first, copies [len(instants)], limiting
+    [len(instants)], blocker positions inside ``member_rows`` [len(instants)]).  copies[k]: ``headroom_gangs_of`` once every valid
+    and responsible throttle has been reconciled at ``instants[k]`` on the state as it is now: ``forecast_gangs_of``'s threshold
+    and throttled flags per throttle and instant, ``headroom_gangs_of``'s A_t, range and judge per candidate copy, the first
+    failing candidate found by bisection per instant, and per instant the lexicographic minimum of (h_t, first stopped member at
+    j = h_t, t).  A throttle whose reconcile is an error is judged once from the stored tables.  limiting / blocker: -1 / -1 where
+    all ``cap`` copies are admitted; a member whose PreFilter is an Error or whose row is invalid: 0 copies at every instant, the
+    walk of copy 0 ends in front of it, limiting -1 where it is the blocker itself.  first: the smallest k with copies[k] >=
+    ``want``, or -1.  ``ctx`` is ``preempt_context``'s aggregate (any ``now``)."""
+    inst = [_instant(t) for t in instants]
+    ctx = preempt_context(snap, inst[0]) if ctx is None else ctx
+    members, eq, cap, m = [int(p) for p in member_rows], bool(on_equal), int(cap), len(inst)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap.n_pods and bool(int(snap.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    g = len(members) if bad_at is None else bad_at  # the members that are walked
+    members, affected = members[:g], affected[:g]
+    reqs = [pod_requests(snap, p) for p in members]
+    start = (cap if bad_at is None else 0, g, -1)  # (h, first, t)
+    best, kept = [start] * m, start  # per instant; and over the throttles that keep their stored status
+
+    def judge(hit, th, ustate, res, res_count, eq3, top):
+        """(h_t, first stopped member at j = h_t) of one throttle against one threshold and state of `used`, candidates up to
+        ``top``; None: it passes there"""
+        per, per_p, per_c = {}, set(), 0  # A_t: only what the threshold names is summed (the rest is never compared)
+        for j in range(g):
+            if hit[j]:
+                per_c += 1
+                for d, v in reqs[j].items():
+                    per_p.add(d)
+                    if d in th[0]:
+                        per[d] = min(per.get(d, 0) + v, _INT64_MAX)
+        if th[1] is None:
+            per_c = 0
+
+        def first_stopped(j):
+            r = {d: res.get(d, 0) + j * per.get(d, 0) for d in (set(res) | per_p if j > 0 else set(res))}
+            rc = (res_count or 0) + j * per_c if (res_count is not None or j > 0) else None
+            s = _gang_first_stopped(members, hit, reqs, th, ustate, r, rc, eq3, eq)
+            return g if s is None else s
+
+        if bad_at is None:  # no further than every named amount stays inside int64
+            if per_c > 0:
+                top = min(top, (_INT64_MAX - (res_count or 0)) // per_c)
+            for d, a in per.items():
+                if a > 0:
+                    top = min(top, (_INT64_MAX - res.get(d, 0)) // a)
+        first = first_stopped(top)
+        if first >= g:
+            return None
+        lo, hi = 0, top  # hi has been seen to fail, everything below lo passes
+        while lo < hi:
+            mid = lo + (hi - lo) // 2
+            s = first_stopped(mid)
+            if s < g:
+                hi, first = mid, s
+            else:
+                lo = mid + 1
+        return hi, first
+
+    for t in (sorted(set().union(*affected)) if affected else []):
+        th = ctx["thr"][t]
+        f = int(snap.thr_flags[t])
+        eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+        res, res_count = _amount_dict(snap.thr_reserved, t, snap.D)
+        hit = [t in a for a in affected]
+        if th["error"]:  # the stored status, at every instant
+            used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+            sth = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+            flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+            names = {d: (bool(flg >> d & 1), d in used, used.get(d, 0)) for d in range(snap.D)}
+            ustate = (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names)
+            got = judge(hit, sth, ustate, res, res_count, eq3, kept[0] if kept[0] < cap else cap - 1)
+            if got is not None:
+                kept = min(kept, got + (t,))
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        stored = _amount_dict(snap.thr_calc, t, snap.D)
+        spec = _amount_dict(snap.thr_spec, t, snap.D)
+        for k, at in enumerate(inst):
+            calc, cc, any_err = _calculated_threshold(snap, t, at)
+            fp = int(snap.thr_spec_msgs_fp[t]) if any_err else 0
+            replace = (calc, cc) != stored or int(snap.thr_status_msgs_fp[t]) != fp
+            rd = (calc, cc) if (f & S.THR_CALC_AT_NONZERO) or replace else spec
+            names = {}
+            for d in range(snap.D):
+                u_pr, cv = cnt.get(d, 0) > 0, calc.get(d)
+                names[d] = (cv is not None and u_pr and val.get(d, 0) >= cv, u_pr, val.get(d, 0))
+            ustate = (cc is not None and pods > 0 and pods >= cc, pods > 0, pods, names)
+            got = judge(hit, rd, ustate, res, res_count, eq3, best[k][0] if best[k][0] < cap else cap - 1)
+            if got is not None:
+                best[k] = min(best[k], got + (t,))
+    copies, limiting, blocker = [], [], []
+    for k in range(m):
+        h, first, t = min(best[k], kept)
+        if bad_at is not None:
+            copies.append(0), limiting.append(t if first < g else -1), blocker.append(first)
+        elif h >= cap:
+            copies.append(cap), limiting.append(-1), blocker.append(-1)
+        else:
+            copies.append(h), limiting.append(t), blocker.append(first)
+    return next((k for k in range(m) if copies[k] >= int(want)), -1), copies, limiting, blocker
+
+
 # ---- forecast over pages (kt_paged_forecast): the closed form over a list of page snapshots ----
 def paged_forecast_of(snaps, pod_row, instants, on_equal=False, ctx=None):
     """kt_paged_forecast for one pod, in closed form over the page snapshots (no GPU) -> (first, verdicts [len(instants)]):
