@@ -717,7 +717,7 @@ int32_t kt_headroom_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first /
  *      Slots: those of kt_forecast_gangs_launch; a pending preempt result of any kind stays fetchable.  The result SHARES the one
  *      pending forecast result as its fourth kind: a later forecast launch of any kind replaces it, and each of the four fetches
  *      answers KT_ERR_NOT_READY after a launch of another kind.  kt_headroom_forecast_gangs_fetch synchronises.
- *      Out of scope: more than KT_MAX_DIMS resource names (pages), several ranks. ----------------------------------------------- */
+ *      More than KT_MAX_DIMS resource names: kt_paged_headroom_forecast_gangs.  Out of scope: several ranks. -------------------- */
 int32_t kt_headroom_forecast_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
                                           int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, int64_t cap,
                                           int64_t want, void* stream);
@@ -1101,11 +1101,81 @@ int32_t kt_paged_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_
  * (kt_forecast_fetch, kt_forecast_gangs_fetch and kt_headroom_forecast_fetch answer KT_ERR_NOT_READY) while a pending preempt
  * result of page 0 stays fetchable; every page's pending reconcile report is dropped.  A device error after the first launch is
  * returned once the stream has drained; no page keeps a pending result.
- * Out of scope: gangs, several ranks. */
+ * Whole gangs: kt_paged_headroom_forecast_gangs.  Out of scope: several ranks. */
 int32_t kt_paged_headroom_forecast(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_inst,
                                    const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, int64_t cap, int64_t want,
                                    int64_t* out_first /* [n], nullable */, int64_t* out_copies /* [n][n_inst], nullable */,
                                    int32_t* out_limiting /* [n][n_inst], nullable */);
+/* kt_headroom_forecast_gangs_launch + kt_headroom_forecast_gangs_fetch over the pages, synchronous: what they return on the cluster
+ * of ALL names.  out_copies[g][k] is the number of leading admitted gangs of a dry kt_paged_admit_gangs over `cap` consecutive
+ * copies of gang g with R_{t_k} as the stored status of every page (every valid and responsible throttle reconciled at t_k on every
+ * page, on the state as it is now); out_blocker[g][k] is the queue position of the first member of the first refused copy whose
+ * COMBINED verdict is not Success; out_limiting[g][k] is the lowest throttle row whose combined status is not
+ * KT_STATUS_NOT_THROTTLED in that member's row at its turn.  Both are -1 where all `cap` copies pass; limiting is also -1 where the
+ * blocker's verdict is an Error.  out_first[g] is the smallest k with out_copies[g][k] >= want, or KT_FORECAST_NONE.  A gang with an
+ * Error or invalid member reports 0 copies at every instant: its walk ends in front of that member, and an earlier member that some
+ * throttle stops at t_k on some page is the blocker there.  A gang no throttle affects: cap / -1 / -1 and first 0.
+ * The answer is NOT a combination of existing calls.  The minimum of the pages' own kt_headroom_forecast_gangs_launch answers is
+ * wrong: status.calculatedThreshold is compared and replaced as a whole, so a page that holds nothing the gang requests can replace
+ * the threshold for the pages that do, at some instants and not at others.  kt_paged_headroom_gangs once per instant would need the
+ * status applied at each instant — not a dry run — and reads each page's own calculatedAt flag, not the forecast's whole-throttle
+ * rule.
+ * The rules about pages and thresholds are kt_paged_forecast_gangs', word for word: the affecting throttles and the Error members
+ * come from ONE check of page 0; `stored` and `calc_at_any` are ORs over the pages; `differs` is the OR over EVERY page (pages none
+ * of whose names any member requests included; page 0 adds the count comparison); the throttle reads status.calculatedThreshold on
+ * every page iff calc_at_any || differs, else spec.threshold on every page; the throttled bits are IsThrottled(used, true) against
+ * the calculated threshold either way.  A throttle that keeps its stored status — its reconcile is an error, or it is not valid and
+ * responsible, on some page — is read on every page against its stored calculated threshold where calc_at_any holds and against
+ * spec.threshold otherwise: NOT the page's own calculatedAt flag, which kt_paged_headroom_gangs reads.
+ * The rules about pages and copies are kt_paged_headroom_gangs': an admitted copy reserves on every page, each page its own names'
+ * values and the presence of the names a member carries there; the pod count is judged and reserved once, on page 0; copy j passes
+ * on throttle t iff the in-order member walk passes on every page, each page against its own reserved row plus j x what one copy
+ * reserves there; per instant every (throttle, page) pair is a throttle of its own and the answer is the lexicographic minimum over
+ * the pairs of (copies, first stopped position, throttle row); a page k != 0 none of whose names an affected member requests with
+ * a non-zero value is skipped in the walk — never in `differs`.
+ * Identities:
+ *   (P1) n_pages == 1 returns byte for byte what kt_headroom_forecast_gangs_launch + kt_headroom_forecast_gangs_fetch return on
+ *        that engine.
+ *   (G1) a gang of one pod reports byte for byte the first, copies and limiting of kt_paged_headroom_forecast for that pod; its
+ *        blocker is its own position where copies < cap, else -1.
+ *   (G2) with cap == want == 1, out_copies[g][k] == 1 exactly where kt_paged_forecast_gangs reports KT_VERDICT_SUCCESS; out_first
+ *        and out_blocker are byte for byte its own.
+ *   (G3) with inst = [t] on pages whose last action was kt_paged_reconcile(t, KT_RECONCILE_APPLY) and whose stored calculatedAt
+ *        flags then agree across the pages for every affecting throttle, column 0 is byte for byte kt_paged_headroom_gangs' answer
+ *        with the same cap and on_equal.  Where the flags disagree this call follows kt_paged_forecast_gangs (the throttle has been
+ *        replaced once some page says so: calc_at_any) and kt_paged_headroom_gangs reads each page's own flag.
+ *   (G4) the call is a dry run: stored status, reserved amounts and a pending kt_aggregate_launch's sums are unchanged on every
+ *        page.
+ * On page 0's stream, in order: that check; for every page its dense aggregate and its dry finalize at t_0; the copies in (the
+ * instants, the gang offsets, the page descriptors); one launch of kt_headroom_forecast_gangs_paged
+ * (csrc/kt_kernels_headroom_forecast_gangs_paged.hip: one wave per gang, lane = instant position; per block of 64 instants a first
+ * pass over the pages for `differs`, a second in which every lane searches the copies of its own instant page by page, its range
+ * cut at its running minimum over the pairs before); the copies out.  All four outputs are nullable.
+ * Refused before anything is launched, and before any page's check slot, reconcile report or result buffer is touched, in this
+ * order: a missing page array, n_pages < 1, a NULL page, n < 0 (KT_ERR_INVALID_ARGUMENT); the instants as kt_forecast_launch
+ * refuses them and a missing array (KT_ERR_INVALID_ARGUMENT); cap outside [1, KT_HEADROOM_MAX_CAP], then want outside [1, cap]
+ * (KT_ERR_INVALID_ARGUMENT); every gang_off defect kt_admit_gangs_launch refuses and a pod named twice within ONE gang
+ * (KT_ERR_INVALID_ARGUMENT); what kt_paged_admit refuses about the page set and the rows (different throttle-row counts, an engine
+ * named twice: KT_ERR_INVALID_ARGUMENT; different devices: KT_ERR_UNSUPPORTED; a pod row outside a page's capacity:
+ * KT_ERR_OUT_OF_RANGE); n x throttle_rows or n_gangs x n_inst above 2^31 (KT_ERR_OUT_OF_RANGE); what kt_forecast_gangs_launch
+ * refuses about an engine, asked of every page: a KT_VARIANT_INCREMENTAL engine, an exchange world above 1, a `used` wider than
+ * int64 (KT_ERR_UNSUPPORTED) — as in the siblings, the one thing that may run first is a page's kernel that sums the |requests|;
+ * and last an engine that has been fed a negative request, on ANY page (KT_ERR_UNSUPPORTED: the search over the copies rests on
+ * sums that only grow; kt_paged_headroom_forecast serves such pages pod by pod).
+ * n == 0 is allowed only with n_gangs == 0: KT_OK, nothing is launched.  Locking and ordering are kt_paged_admit's.
+ * Slots: kt_paged_forecast's.  The call uses page 0's check slot and page 0's forecast result buffers, grown only once the stream
+ * of an unfetched launch has drained, and hands the results out: afterwards no forecast result of any kind is pending on page 0
+ * (kt_forecast_fetch, kt_forecast_gangs_fetch, kt_headroom_forecast_fetch and kt_headroom_forecast_gangs_fetch answer
+ * KT_ERR_NOT_READY) while a pending preempt result of page 0 stays fetchable; every page's pending reconcile report is dropped; a
+ * pending kt_aggregate_launch of any page keeps its sums.  A device error after the first launch is returned once the stream has
+ * drained; no page keeps a pending result.
+ * Out of scope: several ranks. */
+int32_t kt_paged_headroom_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                         const int64_t* gang_off, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns,
+                                         int32_t on_equal, int64_t cap, int64_t want, int64_t* out_first /* [n_gangs], nullable */,
+                                         int64_t* out_copies /* [n_gangs][n_inst], nullable */,
+                                         int32_t* out_limiting /* [n_gangs][n_inst], nullable */,
+                                         int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
 
 /* Development aid: the engine reads its A/B switches (KT_NO_* / KT_SYNC_INGEST ... environment variables, all off by default)
  * once, at kt_engine_create; a tool that flips one on a live engine calls this afterwards. */

@@ -443,8 +443,8 @@ func (e *Engine) HeadroomForecast(rows, instS []int64, instNs []int32, onEqual b
 // lowest throttle row that stops it (both -1: all cap copies fit; limiting also -1 where the blocker's PreFilter is an error),
 // first[g] the smallest k with at least want copies or -1.  A dry run: stored status and reserved amounts stay.  An engine that
 // was fed a negative request is refused (HeadroomForecast serves it pod by pod).  Launch and fetch run under e.mu, like every
-// other user of the check slot.  One engine only: there is no paged form.  Not compiled in this repository (no Go toolchain in
-// its build).
+// other user of the check slot.  Over pages of resource names: kt_paged_headroom_forecast_gangs (not wrapped here).  Not compiled
+// in this repository (no Go toolchain in its build).
 func (e *Engine) HeadroomForecastGangs(rows, gangOff, instS []int64, instNs []int32, onEqual bool, cap, want int64) (first, copies []int64, limiting []int32, blocker []int64, err error) {
 	e.mu.Lock() // the check slot is one per engine: see mu
 	defer e.mu.Unlock()

@@ -101,17 +101,17 @@ static int32_t stored_used_fits(kt_engine* e, const char* what, int page, const 
   return e->fail(KT_ERR_UNSUPPORTED, "%s: the stored `used` of page %d is wider than int64 (%s reads int64 tables)", what, page, kernel);
 }
 // ... and the gang forms search over the copies, which takes sums that only grow
-static int32_t sums_only_grow(kt_engine* e, const char* what, int page, const char* pod_by_pod = "kt_headroom_launch") {
+static int32_t sums_only_grow(kt_engine* e, const char* what, int page, const char* pod_by_pod = nullptr) {
   if (!e->neg_seen) return KT_OK;
   if (page < 0)
     return e->fail(KT_ERR_UNSUPPORTED,
                    "%s: the engine has been fed a negative request; the search over the copies rests on sums that only grow "
                    "(%s serves such an engine pod by pod)",
-                   what, pod_by_pod);
+                   what, pod_by_pod ? pod_by_pod : "kt_headroom_launch");
   return e->fail(KT_ERR_UNSUPPORTED,
                  "%s: page %d has been fed a negative request; the search over the copies rests on sums that only grow "
-                 "(kt_paged_headroom serves such pages pod by pod)",
-                 what, page);
+                 "(%s serves such pages pod by pod)",
+                 what, page, pod_by_pod ? pod_by_pod : "kt_paged_headroom");
 }
 
 static int32_t cap_in_range(kt_engine* e, const char* what, int64_t cap) {
@@ -1129,6 +1129,67 @@ int32_t kt_paged_headroom_forecast(kt_engine* const* pages, int32_t n_pages, int
   e0->last_stream = s;
   if ((rc = c.out(out_first, e0->d_forecast_first.p, (size_t)n * 8)) != KT_OK || (rc = c.out(out_copies, e0->d_forecast_copies.p, cells * 8)) != KT_OK ||
       (rc = c.out(out_limiting, e0->d_forecast_limiting.p, cells * 4)) != KT_OK)
+    return rc;
+  return c.finish(KT_OK);  // (synchronises s; the results have been handed out: no forecast result of any kind is pending on page 0)
+}
+
+// ---------------------------------------------------------------------------------------------------
+// headroom forecast for gangs over pages: kt_headroom_forecast_gangs_launch + kt_headroom_forecast_gangs_fetch on the cluster of
+// all names (kt_kernels_headroom_forecast_gangs_paged.hip)
+// ---------------------------------------------------------------------------------------------------
+// kt_paged_forecast_gangs' body with cap and want behind the instants, as headroom_forecast_gangs_locked orders them, the last
+// refusal of that call asked of every page, and the copies, limiting rows and blockers in the verdict bytes' place.
+int32_t kt_paged_headroom_forecast_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                         const int64_t* gang_off, int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal,
+                                         int64_t cap, int64_t want, int64_t* out_first, int64_t* out_copies, int32_t* out_limiting,
+                                         int64_t* out_blocker) {
+  if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  PagedCall c{"paged headroom forecast gangs", pages, n_pages};
+  int32_t rc = c.lock(n);
+  if (rc != KT_OK) return rc;
+  kt_engine* e0 = c.e0;
+  const char *what = "headroom forecast gangs", *kernel = "kt_headroom_forecast_gangs_paged";
+  // ---- refusals: nothing is launched and no slot of any page is touched before the last of them
+  if ((rc = forecast_instants_valid(e0, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) != KT_OK) return rc;
+  if ((rc = cap_in_range(e0, c.what, cap)) != KT_OK || (rc = want_in_range(e0, c.what, want, cap)) != KT_OK) return rc;
+  if ((rc = gangs_valid(e0, n, n_gangs, gang_off)) != KT_OK) return rc;
+  if ((rc = no_row_twice_in_a_gang(e0, what, pod_rows, n_gangs, gang_off)) != KT_OK) return rc;
+  if ((rc = c.same_cluster(n, pod_rows)) != KT_OK) return rc;  // (the rows are range-checked in place)
+  const int32_t T = e0->thr_rows_hi;
+  if ((rc = matrix_fits(e0, what, T, n)) != KT_OK || (rc = verdicts_fit(e0, what, n_gangs, n_inst, "n_gangs", "results")) != KT_OK) return rc;
+  for (int32_t k = 0; k < n_pages; ++k)
+    if ((rc = serves_dry_reconcile(pages[k], what, k, kernel)) != KT_OK) return rc;
+  if (n == 0) return KT_OK;  // (no gangs) nothing is launched
+  if ((rc = c.order()) != KT_OK || (rc = ensure_ready(e0, c.s)) != KT_OK) return rc;
+  hipStream_t s = c.s;
+  for (int32_t k = 0; k < n_pages; ++k)  // (before the check slot, a reconcile report or a result buffer of any page is touched)
+    if ((rc = sums_fit_int64(pages[k], what, k, kernel, s)) != KT_OK) return rc;
+  for (int32_t k = 0; k < n_pages; ++k)  // the search over the copies takes sums that only grow, on every page
+    if ((rc = sums_only_grow(pages[k], what, k, "kt_paged_headroom_forecast")) != KT_OK) return rc;
+  // ---- from here on the call owns page 0's check slot and forecast result and every page's reconcile report
+  e0->forecast_ready = false, e0->forecast_kind = kForecastPods;
+  if ((rc = c.take_preempt_pages()) != KT_OK) return rc;
+  const size_t ng = (size_t)n_gangs, m = (size_t)n_inst, cells = ng * m;
+  if ((rc = reserve_behind_last_stream(e0, {{e0->d_forecast_first, ng}, {e0->d_forecast_copies, cells}, {e0->d_forecast_limiting, cells}, {e0->d_forecast_blocker, cells}, {e0->d_forecast_inst_s, m}, {e0->d_forecast_inst_ns, m}, {e0->d_forecast_gang_off, ng + 1}})) != KT_OK)
+    return rc;
+  // the instants and the offsets travel on the same stream, behind an earlier forecast's kernel (the call returns behind finish:
+  // the caller's memory is not referenced afterwards)
+  if ((rc = c.in(e0->d_forecast_inst_s.p, inst_s, m * 8)) != KT_OK || (rc = c.in(e0->d_forecast_inst_ns.p, inst_ns, m * 4)) != KT_OK ||
+      (rc = c.in(e0->d_forecast_gang_off.p, gang_off, (ng + 1) * 8)) != KT_OK)
+    return rc;
+  if ((rc = query_check(e0, n, pod_rows, on_equal, s, &kt_engine::preempt_ready)) != KT_OK) return c.finish(rc);  // over the members of all gangs
+  if ((rc = reconcile_pages(c, inst_s[0], inst_ns[0])) != KT_OK) return rc;  // (the dry finalize runs at t_0)
+  hipError_t herr = hipSuccess;
+  if (!kt::launch_headroom_forecast_gangs_paged(e0->h_preempt_pages.data(), n_pages, (kt::PreemptPage*)e0->d_preempt_pages.p, e0->preempt_pages_ev,
+                                                n_gangs, n_inst, e0->d_rows.p, e0->d_forecast_gang_off.p, e0->d_forecast_inst_s.p,
+                                                e0->d_forecast_inst_ns.p, T, on_equal != 0, (uint32_t)cap, (uint32_t)want, e0->d_status.p,
+                                                e0->d_summary.p, e0->d_forecast_first.p, e0->d_forecast_copies.p, e0->d_forecast_limiting.p,
+                                                e0->d_forecast_blocker.p, s, &herr))
+    return c.device_error(herr, "copy of the page descriptors: ");
+  if ((rc = c.launched()) != KT_OK) return rc;
+  e0->last_stream = s;
+  if ((rc = c.out(out_first, e0->d_forecast_first.p, ng * 8)) != KT_OK || (rc = c.out(out_copies, e0->d_forecast_copies.p, cells * 8)) != KT_OK ||
+      (rc = c.out(out_limiting, e0->d_forecast_limiting.p, cells * 4)) != KT_OK || (rc = c.out(out_blocker, e0->d_forecast_blocker.p, cells * 8)) != KT_OK)
     return rc;
   return c.finish(KT_OK);  // (synchronises s; the results have been handed out: no forecast result of any kind is pending on page 0)
 }

@@ -56,84 +56,6 @@ struct ForecastGangsPagedArgs {
   int32_t T, on_equal;
 };
 
-// what does not depend on the instant of throttle t on one page: one batch of wave-uniform loads
-template <int DT>
-struct ForecastPageThr {
-  uint32_t ovr0, ovr1, s_p, k_p, names;  // names: those some threshold of the throttle can name on this page
-  bool fp_differs, spec_diff;            // the messages fingerprint differs; spec against the stored calculated threshold, by value
-  int64_t sv[DT], kv[DT];
-};
-
-template <int DT>
-__device__ __forceinline__ ForecastPageThr<DT> forecast_page_thr(const ThrTables& tt, int D, uint32_t t) {
-  ForecastPageThr<DT> r;
-  r.ovr0 = tt.ovr_off[t], r.ovr1 = tt.ovr_off[t + 1];
-  const uint64_t status_fp = tt.status_msgs_fp[t], spec_fp = tt.spec_msgs_fp[t];
-  r.s_p = tt.spec.present[t], r.k_p = tt.calc.present[t];
-  // whether an override has a parse error (the messages of CalculateThreshold: they do not depend on the instant)
-  r.names = r.s_p | r.k_p;
-  bool any_err = false;
-  for (uint32_t o = r.ovr0; o < r.ovr1; ++o) {
-    if (tt.ovr_flags[o] & kOvrParseError) any_err = true;
-    else r.names |= tt.ovr_thr.present[o];
-  }
-  r.fp_differs = status_fp != (any_err ? spec_fp : 0ull);
-  r.spec_diff = false;
-#pragma unroll
-  for (int d = 0; d < DT; ++d) {
-    r.sv[d] = r.kv[d] = 0;
-    if (d >= D) continue;
-    r.sv[d] = tt.spec.v[(size_t)t * D + d], r.kv[d] = tt.calc.v[(size_t)t * D + d];
-    r.spec_diff |= ((r.s_p >> d) & 1u) && r.sv[d] != r.kv[d];
-  }
-  return r;
-}
-
-// CalculateThreshold of the throttle on one page at the lane's instant: first active override wins, per name and for the count;
-// no active override: spec.threshold, otherwise the merged override REPLACES it.  *diff: it differs by value from the stored
-// calculated threshold over the names it has.  The whole wave arrives (one ballot per override).
-template <int DT>
-__device__ __forceinline__ void forecast_page_calc(const ThrTables& tt, int D, uint32_t t, const ForecastPageThr<DT>& pt, int64_t ts, int32_t tn,
-                                                   bool* c_hc_out, int64_t* c_c_out, uint32_t* c_p_out, int64_t (&c_v)[DT], bool* diff_out) {
-  bool active_found = false, c_hc = false, diff = false;
-  int64_t c_c = 0;
-  uint32_t c_p = 0;
-#pragma unroll
-  for (int d = 0; d < DT; ++d) c_v[d] = 0;
-  for (uint32_t o = pt.ovr0; o < pt.ovr1; ++o) {
-    // one batch of loads per override (wave-uniform)
-    const uint8_t of = tt.ovr_flags[o];
-    const int64_t ob_s = tt.ovr_begin_s[o], oe_s = tt.ovr_end_s[o];
-    const int32_t ob_ns = tt.ovr_begin_ns[o], oe_ns = tt.ovr_end_ns[o];
-    const bool o_hc = tt.ovr_thr.has_count[o] != 0;
-    const int64_t o_c = tt.ovr_thr.count[o];
-    const uint32_t op = tt.ovr_thr.present[o];
-    if (of & kOvrParseError) continue;
-    const bool end_zero = oe_s == kZeroTimeS && oe_ns == 0;
-    const bool active = forecast_le(ob_s, ob_ns, ts, tn) && (end_zero || forecast_le(ts, tn, oe_s, oe_ns));
-    if (__ballot(active) == 0ull) continue;
-    active_found |= active;
-    if (active && !c_hc && o_hc) c_hc = true, c_c = o_c;
-    const uint32_t take = active ? op & ~c_p : 0u;  // the names this override decides at this lane's instant
-    c_p |= take;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-      if (d >= D || !((op >> d) & 1u)) continue;  // (wave-uniform)
-      const int64_t o_v = tt.ovr_thr.v[(size_t)o * D + d];
-      if ((take >> d) & 1u) {
-        diff |= o_v != pt.kv[d];
-        c_v[d] = o_v;
-      }
-    }
-  }
-  if (!active_found) {
-    c_p = pt.s_p, c_hc = tt.spec.has_count[t] != 0, c_c = tt.spec.count[t], diff = pt.spec_diff;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) c_v[d] = pt.sv[d];
-  }
-  *c_hc_out = c_hc, *c_c_out = c_c, *c_p_out = c_p, *diff_out = diff;
-}
-
 template <int DT>
 __global__ __launch_bounds__(kWave) void kt_forecast_gangs_paged(const ForecastGangsPagedArgs a) {
   __shared__ uint32_t chunk_list[kPreemptChunk];

@@ -237,6 +237,15 @@ bool launch_headroom_forecast_paged(const PreemptPage* pages, int n_pages, Preem
                                     const int64_t* rows_dev, const int64_t* inst_s, const int32_t* inst_ns, int T, bool on_equal, uint32_t cap,
                                     uint32_t want, const uint8_t* status, const uint64_t* summary, int64_t* first, int64_t* copies,
                                     int32_t* limiting, hipStream_t s, hipError_t* hip_err);
+// how many copies of a whole gang the throttles admit at each instant over n_pages >= 1 pages
+// (kt_kernels_headroom_forecast_gangs_paged.hip): launch_forecast_gangs_paged's inputs plus cap and want (1 <= want <= cap <=
+// 2^31 - 1); first [n_gangs], copies [n_gangs][m], limiting [n_gangs][m] and blocker [n_gangs][m] out, on page 0.  false: the copy
+// failed (*hip_err)
+bool launch_headroom_forecast_gangs_paged(const PreemptPage* pages, int n_pages, PreemptPage* pages_dev, hipEvent_t pages_copied, int64_t n_gangs,
+                                          int64_t m, const int64_t* rows_dev, const int64_t* gang_off_dev, const int64_t* inst_s,
+                                          const int32_t* inst_ns, int T, bool on_equal, uint32_t cap, uint32_t want, const uint8_t* status,
+                                          const uint64_t* summary, int64_t* first, int64_t* copies, int32_t* limiting, int64_t* blocker,
+                                          hipStream_t s, hipError_t* hip_err);
 
 inline int dt_bucket(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : 16; }
 inline int dt_bucket_ix(int D) { return D <= 8 ? 8 : 16; }  // indexed kernels: two instantiations

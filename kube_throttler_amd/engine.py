@@ -46,7 +46,7 @@ EXPORTS = [
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
     "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch", "kt_paged_headroom_gangs",
     "kt_headroom_forecast_launch", "kt_headroom_forecast_fetch", "kt_paged_headroom_forecast",
-    "kt_headroom_forecast_gangs_launch", "kt_headroom_forecast_gangs_fetch",
+    "kt_headroom_forecast_gangs_launch", "kt_headroom_forecast_gangs_fetch", "kt_paged_headroom_forecast_gangs",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -290,6 +290,38 @@ def paged_headroom_forecast(engines, pod_rows, instants, *, cap, want=1, on_equa
             (None if limiting is None else limiting[:n * m].reshape(n, m)))
 
 
+def paged_headroom_forecast_gangs(engines, pod_rows, gang_off, instants, *, cap, want=1, on_equal=False, want_copies=True,
+                                  want_limiting=True, want_blocker=True):
+    """kt_paged_headroom_forecast_gangs: kt_headroom_forecast_gangs_launch + kt_headroom_forecast_gangs_fetch over the page engines,
+    on the cluster of all resource names -> (first int64 [n_gangs], copies int64 [n_gangs][n_inst] or None, limiting int32
+    [n_gangs][n_inst] or None, blocker int64 [n_gangs][n_inst] or None).  Per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` and per
+    instant the number of leading admitted gangs a dry-run paged gang admission of ``cap`` consecutive copies returns once every
+    valid and responsible throttle has been reconciled at that instant on every page, the queue position of the first member of
+    the first refused copy that is not admitted and the lowest throttle row that stops it (-1 / -1: all ``cap`` copies are
+    admitted), and the first position with at least ``want`` copies (FORECAST_NONE: none).  At each instant a throttle reads its
+    calculated threshold on every page when any page's reconcile replaces it (or any page has it stored), and keeps its stored
+    status on every page when its reconcile is an error on any page."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    a = np.ascontiguousarray(pod_rows, dtype=np.int64)
+    g = _gang_offsets(gang_off)
+    inst_s = np.ascontiguousarray([int(t[0]) for t in instants], dtype=np.int64)
+    inst_ns = np.ascontiguousarray([int(t[1]) for t in instants], dtype=np.int32)
+    n, m, ng = len(a), len(inst_s), len(g) - 1
+    first = np.zeros(max(ng, 1), np.int64)
+    copies = np.zeros(max(ng * m, 1), np.int64) if want_copies else None
+    limiting = np.zeros(max(ng * m, 1), np.int32) if want_limiting else None
+    blk = np.zeros(max(ng * m, 1), np.int64) if want_blocker else None
+    rc = lib().kt_paged_headroom_forecast_gangs(hs, len(engines), n, a.ctypes.data if n else None, ng, g.ctypes.data, m,
+                                                inst_s.ctypes.data if m else None, inst_ns.ctypes.data if m else None, int(on_equal),
+                                                int(cap), int(want), first.ctypes.data, None if copies is None else copies.ctypes.data,
+                                                None if limiting is None else limiting.ctypes.data,
+                                                None if blk is None else blk.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_headroom_forecast_gangs: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return (first[:ng], (None if copies is None else copies[:ng * m].reshape(ng, m)),
+            (None if limiting is None else limiting[:ng * m].reshape(ng, m)), (None if blk is None else blk[:ng * m].reshape(ng, m)))
+
+
 def paged_reconcile(engines, now, apply=True):
     """kt_paged_reconcile: a reconcile on every page engine -> (per-page ReconcileResult list, replaced_any [T], error_any [T])."""
     hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
@@ -428,6 +460,9 @@ def lib():
                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_paged_headroom_forecast.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                  C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kt_paged_headroom_forecast_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.kt_forecast_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.kt_headroom_forecast_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,

@@ -1598,6 +1598,145 @@ def paged_headroom_gangs_of(snaps, member_rows, cap, on_equal=False):
     return (cap, -1, -1) if h >= cap else (h, t, first)
 
 
+# ---- headroom forecast for gangs over pages (kt_paged_headroom_forecast_gangs), as the kernel computes it, over page snapshots ----
+def paged_headroom_forecast_gangs_of(snaps, member_rows, instants, cap, want=1, on_equal=False, ctx=None):
+    """kt_paged_headroom_forecast_gangs for one gang, restated over the page snapshots (no GPU) -> (first, copies [len(instants)],
+    limiting [len(instants)], blocker positions inside ``member_rows`` [len(instants)]): ``headroom_forecast_gangs_of`` on the
+    cluster of all names.  ``paged_forecast_gangs_of``'s threshold per throttle and instant — the whole-error rule and the
+    whole-threshold rule, `differs` over EVERY page, a throttle that keeps its stored status read against the stored calculated
+    threshold where calculatedAt is set on some page and against spec otherwise — with ``paged_headroom_gangs_of``'s copies per
+    (throttle, page) pair: the page's own reserved row, A_t of that page, the pod count (threshold, flag, what a copy adds, the
+    int64 cut) page 0's and judged once, a page k != 0 none of whose names an affected member requests with a non-zero value
+    skipped.  Per pair and instant the candidates end at the running minimum and where a named amount of the page would leave
+    int64, the first failing one is found by bisection, and per instant the answer is the lexicographic minimum over the pairs of
+    (h, first stopped member at j = h, t).  Which throttles affect which member and "a member is an Error or invalid" are page
+    0's.  ``ctx`` is ``paged_preempt_context``'s (any ``now``: only its sums and error marks are read).  With one snapshot this is
+    ``headroom_forecast_gangs_of``; with one member its first, copies and limiting are ``paged_headroom_forecast_of``'s."""
+    snap0 = snaps[0]
+    inst = [_instant(t) for t in instants]
+    ctx = paged_preempt_context(snaps, inst[0]) if ctx is None else ctx
+    members, eq, cap, m = [int(p) for p in member_rows], bool(on_equal), int(cap), len(inst)
+    affected, bad_at = [], None  # per member its affecting throttles; the first member that is invalid or an Error
+    for j, p in enumerate(members):
+        valid = 0 <= p < snap0.n_pods and bool(int(snap0.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap0, p) if valid else (True, [])
+        if (err or not valid) and bad_at is None:
+            bad_at = j
+        affected.append(set(rows))
+    g = len(members) if bad_at is None else bad_at  # the members that are walked
+    members, affected = members[:g], affected[:g]
+    page_reqs = [[pod_requests(s, p) for p in members] for s in snaps]
+    start = (cap if bad_at is None else 0, g, -1)  # (h, first, t)
+    best, kept = [start] * m, start  # per instant; and over the pairs that keep their stored status
+
+    def judge(reqs, hit, th, ustate, res, res_count, eq3, top):
+        """(h, first stopped member at j = h) of one (throttle, page) pair against one threshold and state of `used`, candidates
+        up to ``top``; None: it passes there"""
+        per, per_p, per_c = {}, set(), 0  # A_t of the page: only what the threshold names is summed (the rest is never compared)
+        for j in range(g):
+            if hit[j]:
+                per_c += 1
+                for d, v in reqs[j].items():
+                    per_p.add(d)
+                    if d in th[0]:
+                        per[d] = min(per.get(d, 0) + v, _INT64_MAX)
+        if th[1] is None:
+            per_c = 0
+
+        def first_stopped(j):
+            r = {d: res.get(d, 0) + j * per.get(d, 0) for d in (set(res) | per_p if j > 0 else set(res))}
+            rc = (res_count or 0) + j * per_c if (res_count is not None or j > 0) else None
+            s = _gang_first_stopped(members, hit, reqs, th, ustate, r, rc, eq3, eq)
+            return g if s is None else s
+
+        if bad_at is None:  # no further than every named amount of this page stays inside int64
+            if per_c > 0:
+                top = min(top, (_INT64_MAX - (res_count or 0)) // per_c)
+            for d, a in per.items():
+                if a > 0:
+                    top = min(top, (_INT64_MAX - res.get(d, 0)) // a)
+        first = first_stopped(top)
+        if first >= g:
+            return None
+        lo, hi = 0, top  # hi has been seen to fail, everything below lo passes
+        while lo < hi:
+            mid = lo + (hi - lo) // 2
+            s = first_stopped(mid)
+            if s < g:
+                hi, first = mid, s
+            else:
+                lo = mid + 1
+        return hi, first
+
+    for t in (sorted(set().union(*affected)) if affected else []):
+        th = ctx["thr"][t]
+        hit = [t in a for a in affected]
+        calc_at_any = any(int(s.thr_flags[t]) & S.THR_CALC_AT_NONZERO for s in snaps)
+        # page 0 carries the pod count; elsewhere a page none of whose names an affected member requests stops nobody
+        walked = [k == 0 or any(hit[j] and v != 0 for j in range(g) for v in page_reqs[k][j].values()) for k in range(len(snaps))]
+        need = S.THR_VALID | S.THR_RESPONSIBLE
+        if th["error"] or any((int(s.thr_flags[t]) & need) != need for s in snaps):  # the stored status of every page, at every instant
+            for k, s in enumerate(snaps):
+                if not walked[k]:
+                    continue
+                f = int(s.thr_flags[t])
+                eq3 = eq if f & S.THR_CLUSTER else True  # throttle_types.go:143 vs clusterthrottle_types.go:45
+                sth = _amount_dict(s.thr_calc if calc_at_any else s.thr_spec, t, s.D)
+                used, used_count = _amount_dict(s.thr_used, t, s.D)
+                flg = int(s.thr_thrl_flag[t]) & int(s.thr_thrl_has[t])
+                names = {d: (bool(flg >> d & 1), d in used, used.get(d, 0)) for d in range(s.D)}
+                res, res_count = _amount_dict(s.thr_reserved, t, s.D)
+                if k == 0:
+                    ustate = (bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, names)
+                else:  # the pod count is page 0's: here the threshold does not name it and its flag is false
+                    sth, ustate = (sth[0], None), (False, used_count is not None, used_count or 0, names)
+                got = judge(page_reqs[k], hit, sth, ustate, res, res_count, eq3, kept[0] if kept[0] < cap else cap - 1)
+                if got is not None:
+                    kept = min(kept, got + (t,))
+            continue
+        val, cnt, pods = th["val"], th["cnt"], th["pods"]
+        for i, at in enumerate(inst):
+            calcs, differs = [], False
+            for k, s in enumerate(snaps):
+                page_names, count, any_err = _calculated_threshold(s, t, at)
+                stored, stored_count = _amount_dict(s.thr_calc, t, s.D)
+                fp = int(s.thr_spec_msgs_fp[t]) if any_err else 0
+                differs = differs or page_names != stored or int(s.thr_status_msgs_fp[t]) != fp
+                if k == 0:  # the count is the same in every page
+                    differs = differs or count != stored_count
+                calcs.append((page_names, count))
+            reads_calc = calc_at_any or differs
+            for k, s in enumerate(snaps):
+                if not walked[k]:
+                    continue
+                f = int(s.thr_flags[t])
+                eq3 = eq if f & S.THR_CLUSTER else True
+                calc, cc = calcs[k]
+                rd = (calc, cc) if reads_calc else _amount_dict(s.thr_spec, t, s.D)
+                names = {}
+                for d in range(s.D):
+                    u_pr, cv, uv = cnt.get((k, d), 0) > 0, calc.get(d), val.get((k, d), 0)
+                    names[d] = (cv is not None and u_pr and uv >= cv, u_pr, uv)
+                if k == 0:
+                    ustate = (cc is not None and pods > 0 and pods >= cc, pods > 0, pods, names)
+                else:  # the pod count is page 0's
+                    rd, ustate = (rd[0], None), (False, pods > 0, pods, names)
+                res, res_count = _amount_dict(s.thr_reserved, t, s.D)
+                got = judge(page_reqs[k], hit, rd, ustate, res, res_count, eq3, best[i][0] if best[i][0] < cap else cap - 1)
+                if got is not None:
+                    best[i] = min(best[i], got + (t,))
+    copies, limiting, blocker = [], [], []
+    for i in range(m):
+        h, first, t = min(best[i], kept)
+        if bad_at is not None:
+            copies.append(0), limiting.append(t if first < g else -1), blocker.append(first)
+        elif h >= cap:
+            copies.append(cap), limiting.append(-1), blocker.append(-1)
+        else:
+            copies.append(h), limiting.append(t), blocker.append(first)
+    return next((i for i in range(m) if copies[i] >= int(want)), -1), copies, limiting, blocker
+
+
 class PagedEngine:
     """One HIP engine per page of a ``ClusterState.build_pages()`` result; reconcile and check run on every page (the
     selector scan is repeated per page: the price of more than 16 resource names) and come back combined."""
@@ -1700,6 +1839,17 @@ class PagedEngine:
         position with at least ``want`` copies, and per instant the lowest throttle row that stops the next copy.  A dry run:
         nothing stored changes on any page."""
         return E.paged_headroom_forecast(self.engines, pod_rows, instants, cap=cap, want=want, on_equal=on_equal)
+
+    def headroom_forecast_gangs(self, pod_rows, gang_off, instants, *, cap, want=1, on_equal=False, want_copies=True, want_limiting=True,
+                                want_blocker=True):
+        """How many copies of each gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` the throttles admit as a whole at each of the
+        strictly ascending ``instants``, over every page's names, through kt_paged_headroom_forecast_gangs (any number of pages;
+        one page goes through the same call) -> (first [n_gangs], copies [n_gangs][n_inst] or None, limiting [n_gangs][n_inst] or
+        None, blocker [n_gangs][n_inst] or None): the first position with at least ``want`` copies, and per instant the lowest
+        throttle row that stops the next copy and the queue position of the member it stops.  A dry run: nothing stored changes
+        on any page."""
+        return E.paged_headroom_forecast_gangs(self.engines, pod_rows, gang_off, instants, cap=cap, want=want, on_equal=on_equal,
+                                               want_copies=want_copies, want_limiting=want_limiting, want_blocker=want_blocker)
 
     def override_instants(self, from_, until, cap=None):
         """kt_override_instants of page 0 -> ([(seconds, nanoseconds)], total): every page holds every override's times and parse
