@@ -111,8 +111,39 @@ int32_t kt_upsert_namespaces(kt_engine* e, const kt_snapshot* batch, const int32
  * labels than the engine keeps, a request beyond 2^60) leaves the engine as it was — its bounds, its "a negative request was fed"
  * mark, its views and its compiled program included. */
 int32_t kt_upsert_pods(kt_engine* e, const kt_snapshot* batch, const int64_t* pod_rows);
-/* Throttles: spec (threshold, overrides, selector), stored status and reserved amounts of each row. */
+/* Throttles: spec (threshold, overrides, selector), stored status and reserved amounts of each row.
+ * The whole batch is validated before anything of it is kept — by kt_upsert_throttles, kt_upsert_throttle and kt_load_snapshot
+ * alike, with the one pass kt_validate_throttles exports (below).  Refused are
+ *   - a row outside throttle_capacity, at any position of the batch, and a namespaced Throttle whose namespace id lies at or beyond
+ *     namespace_capacity (KT_ERR_OUT_OF_RANGE);
+ *   - a batch whose D differs from the engine's;
+ *   - thr_ovr_off / thr_term_off / term_preq_off / term_nreq_off / preq.val_off / nreq.val_off that do not start at 0 or that
+ *     decrease; term_preq_off / term_nreq_off that end beyond preq.n / nreq.n (KT_ERR_OUT_OF_RANGE); a non-empty value range
+ *     with val == NULL;
+ *   - an operator above KT_OP_DOES_NOT_EXIST, a term flag outside KT_TERM_POD_SEL_INVALID | KT_TERM_NS_SEL_INVALID;
+ *   - a presence mask of thr_spec / thr_calc / thr_used / thr_reserved / ovr_thr, or thr_thrl_flag | thr_thrl_has, with a bit at or
+ *     above n_dims;
+ *   - status.used or a reserved amount beyond 2^60 (KT_ERR_OVERFLOW_RISK);
+ * KT_ERR_INVALID_ARGUMENT where no other code is named, and kt_last_error names the array and the position.  The pass reads
+ * nothing beyond what the counts and the offsets it has already checked cover.  A refused call leaves the engine as it was: every
+ * throttle row, the row count, the compiled program, the views, the match cache and the pending results included; nothing is
+ * recompiled for it.
+ * A batch may name a row more than once (coalesced informer events): the entries are applied in batch order, the LAST one wins.
+ * An accepted event whose rows keep what the selector program is compiled from — the VALID / RESPONSIBLE / CLUSTER flags, the
+ * namespace id, the terms with their flags and requirements — only uploads the throttle tables again: a threshold, an override,
+ * a status or a reservation costs no compile.  Anything else (a fresh row beyond the row count included) costs ONE compile per
+ * gap between launches, however many events the gap holds.
+ * Pending results: kt_check_fetch and kt_reconcile_fetch answer KT_ERR_NOT_READY behind an accepted throttle event (the results
+ * describe the old throttle set and its row count); a pending query result (kt_headroom_launch, kt_forecast_launch,
+ * kt_preempt_launch, kt_admit_gangs_launch and their kin) answers the exact state at its launch or KT_ERR_NOT_READY, never
+ * anything else — also when the event grows the row count and with it every per-throttle buffer. */
 int32_t kt_upsert_throttles(kt_engine* e, const kt_snapshot* batch, const int32_t* thr_rows);
+/* The validation pass of kt_upsert_throttles on its own: needs no engine and no device.  n_dims, throttle_capacity and
+ * namespace_capacity are those of the kt_config the batch is meant for; thr_rows may be NULL (batch index i -> row i).  Returns
+ * what kt_upsert_throttles would answer before it stores anything, with the text of kt_last_error in err[0, err_len) (err may be
+ * NULL). */
+int32_t kt_validate_throttles(const kt_snapshot* batch, const int32_t* thr_rows, int32_t n_dims, int32_t throttle_capacity,
+                              int32_t namespace_capacity, char* err, int32_t err_len);
 /* The rows lose their objects and labels, as by kt_upsert_namespaces with ns_valid == 0; the pods that name them stay.  The whole
  * batch is validated first, see above. */
 int32_t kt_delete_namespaces(kt_engine* e, int32_t n, const int32_t* ns_rows);
@@ -121,8 +152,15 @@ int32_t kt_delete_namespaces(kt_engine* e, int32_t n, const int32_t* ns_rows);
  * rows end up empty and their pods are taken out of `used` once (incremental engines included).  Every row must lie inside
  * pod_capacity. */
 int32_t kt_delete_pods(kt_engine* e, int64_t n, const int64_t* pod_rows);
+/* Throttles leave by row: the rows end up empty (their stored status, reservations and matrix columns zero), the row count stays.
+ * A batch may name a row more than once, and rows that hold nothing (never fed, or deleted before).  Every row must lie inside
+ * throttle_capacity: the whole batch is checked first, a refused batch (KT_ERR_OUT_OF_RANGE) leaves the engine as it was.  An
+ * accepted batch costs one compile per gap; pending results as for kt_upsert_throttles. */
 int32_t kt_delete_throttles(kt_engine* e, int32_t n, const int32_t* thr_rows);
-/* Clears everything and ingests a whole snapshot (rows = indices). */
+/* Clears everything and ingests a whole snapshot (rows = indices).  The snapshot is validated BEFORE anything is cleared: its
+ * size against the capacity, its throttles by the pass of kt_upsert_throttles, its pods by that of kt_upsert_pods.  A refused load
+ * leaves the engine as it was — pods, namespaces, throttles, bounds, the "a negative request was fed" mark, views, match cache,
+ * compiled program and pending results. */
 int32_t kt_load_snapshot(kt_engine* e, const kt_snapshot* s);
 
 /* ---- single-object forms of the state feed: what ONE informer event handler call pushes (OnAdd / OnUpdate of a
@@ -142,7 +180,8 @@ int32_t kt_upsert_pod(kt_engine* e, int64_t pod_row, uint32_t ns, uint32_t flags
  * (n, op [n], key [n], val_off [n+1], val []) like kt_reqs.  The shapes are held against each other before anything is
  * stored (offset arrays start at 0 and never decrease, operators are KT_OP_*, masks name dimensions below n_dims, term flags
  * are KT_TERM_*): a slice passed in the wrong position answers KT_ERR_INVALID_ARGUMENT naming the argument (kt_last_error)
- * instead of feeding a wrong selector silently. */
+ * instead of feeding a wrong selector silently.  It is the validation pass of kt_upsert_throttles over the one-row batch the
+ * arguments make: the text names the array by its kt_snapshot field (thr_spec.present for amt_present[0], preq.op for preq_op). */
 int32_t kt_upsert_throttle(kt_engine* e, int32_t thr_row, uint32_t flags, uint32_t ns, const int64_t* amt_v,
                            const uint32_t* amt_present, const int64_t* amt_count, const uint8_t* amt_has_count,
                            uint32_t thrl_flag, uint32_t thrl_has, uint64_t status_msgs_fp, uint64_t spec_msgs_fp, int32_t n_ovr,

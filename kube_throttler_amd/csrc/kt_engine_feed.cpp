@@ -2,6 +2,7 @@
 // status, reserved amounts, whole snapshots).  throttle_controller.go:400-536, clusterthrottle_controller.go:428-570.
 #include "kt_engine_impl.h"
 #include "kt_rows.h"
+#include "kt_throttle_batch.h"
 
 int32_t kt_upsert_namespaces(kt_engine* e, const kt_snapshot* b, const int32_t* rows) {
   if (!e || !b) return KT_ERR_INVALID_ARGUMENT;
@@ -32,55 +33,67 @@ int32_t kt_delete_namespaces(kt_engine* e, int32_t n, const int32_t* rows) {
   return KT_OK;
 }
 
-static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int64_t* rows) {
+// What the validation pass over a pod batch finds.  commit_pods stores it with the batch once the WHOLE batch has passed — and, in
+// kt_load_snapshot, once the throttles of the snapshot have passed too: a refused call leaves the engine as it was.
+struct PodBatchFacts {
+  int64_t rows_hi = 0, ns_hi = 0;  // one past the highest pod row / namespace id the batch names
+  unsigned __int128 max[KT_MAX_DIMS] = {0}, total[KT_MAX_DIMS] = {0};
+  uint64_t bits[KT_MAX_DIMS] = {0};  // OR of the |requests|
+  bool neg = false;                  // a negative request is among them
+};
+
+// ---- validation + overflow bound (host pass over the batch; nothing of the engine is written)
+static int32_t validate_pods(kt_engine* e, const kt_snapshot* b, const int64_t* rows, PodBatchFacts& f) {
   const int D = e->D;
   if (b->D != D) return e->fail(KT_ERR_INVALID_ARGUMENT, "batch D=%d, engine D=%d", b->D, D);
-  const int64_t n = b->n_pods;
-  if (n <= 0) return KT_OK;
-  // ---- validation + overflow bound (host pass over the batch; the data is copied once, below)
-  int64_t hi = e->pod_rows_hi, ns_hi = e->pod_ns_hi;
-  unsigned __int128 batch_max[KT_MAX_DIMS] = {0}, batch_total[KT_MAX_DIMS] = {0};
-  uint64_t batch_or[KT_MAX_DIMS] = {0};
-  bool batch_neg = false;  // committed with max_abs / or_abs below: a refused batch leaves the engine as it was
-  for (int64_t i = 0; i < n; ++i) {
+  for (int64_t i = 0; i < b->n_pods; ++i) {
     const int64_t row = rows ? rows[i] : i;
     if (row < 0 || row >= e->cfg.pod_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "pod row %lld", (long long)row);
     if (b->pod_ns[i] >= (uint32_t)e->cfg.namespace_capacity)
       return e->fail(KT_ERR_OUT_OF_RANGE, "pod %lld: namespace id %u", (long long)i, b->pod_ns[i]);
-    ns_hi = std::max(ns_hi, (int64_t)b->pod_ns[i] + 1);
+    f.ns_hi = std::max(f.ns_hi, (int64_t)b->pod_ns[i] + 1);
     if (b->pod_label_off[i + 1] - b->pod_label_off[i] > (uint32_t)e->L)
       return e->fail(KT_ERR_OUT_OF_RANGE, "pod %lld has %u labels, engine keeps %d", (long long)i,
                      b->pod_label_off[i + 1] - b->pod_label_off[i], e->L);
-    hi = std::max(hi, row + 1);
+    f.rows_hi = std::max(f.rows_hi, row + 1);
     unsigned __int128 sum[KT_MAX_DIMS] = {0};
     for (uint32_t k = b->pod_ctr_off[i]; k < b->pod_ctr_off[i + 1]; ++k)
       for (int d = 0; d < D; ++d)
         if ((b->ctr_present[k] >> d) & 1u) {
           sum[d] += uabs(b->ctr_req[(size_t)k * D + d]);
-          batch_or[d] |= (uint64_t)uabs(b->ctr_req[(size_t)k * D + d]);
-          if (b->ctr_req[(size_t)k * D + d] < 0) batch_neg = true;
+          f.bits[d] |= (uint64_t)uabs(b->ctr_req[(size_t)k * D + d]);
+          if (b->ctr_req[(size_t)k * D + d] < 0) f.neg = true;
         }
     if (b->pod_ovh_present[i] >> 31)
       for (int d = 0; d < D; ++d)
         if ((b->pod_ovh_present[i] >> d) & 1u) {
           sum[d] += uabs(b->pod_ovh[(size_t)i * D + d]);
-          batch_or[d] |= (uint64_t)uabs(b->pod_ovh[(size_t)i * D + d]);
-          if (b->pod_ovh[(size_t)i * D + d] < 0) batch_neg = true;
+          f.bits[d] |= (uint64_t)uabs(b->pod_ovh[(size_t)i * D + d]);
+          if (b->pod_ovh[(size_t)i * D + d] < 0) f.neg = true;
         }
-    for (int d = 0; d < D; ++d) batch_max[d] = std::max(batch_max[d], sum[d]), batch_total[d] += sum[d];
+    for (int d = 0; d < D; ++d) f.max[d] = std::max(f.max[d], sum[d]), f.total[d] += sum[d];
   }
   // a single request beyond 2^60 is refused here; whether the requests of all pods still ADD UP inside the exact range
   // is checked against their actual sum when a reconcile scans them (request_sums_in_range)
   for (int d = 0; d < D; ++d)
-    if (batch_max[d] > kSumBound)
+    if (f.max[d] > kSumBound)
       return e->fail(KT_ERR_OVERFLOW_RISK, "dimension %d: a pod's request exceeds 2^60 at this scale; use a coarser scale for it", d);
+  return KT_OK;
+}
+
+// ---- the batch validate_pods has passed goes in: bounds and marks first, then the data (copied once)
+static int32_t commit_pods(kt_engine* e, const kt_snapshot* b, const int64_t* rows, const PodBatchFacts& f) {
+  const int D = e->D;
+  const int64_t n = b->n_pods;
+  if (n <= 0) return KT_OK;
+  const int64_t hi = std::max(e->pod_rows_hi, f.rows_hi), ns_hi = std::max(e->pod_ns_hi, f.ns_hi);
   // the scan lists / views: patched in place when the batch fits what they were built for, else rebuilt by the next scan
-  const bool patch = views_patchable(e, n, batch_max, batch_or, batch_neg && !e->neg_seen);
-  e->neg_seen = e->neg_seen || batch_neg;
+  const bool patch = views_patchable(e, n, f.max, f.bits, f.neg && !e->neg_seen);
+  e->neg_seen = e->neg_seen || f.neg;
   for (int d = 0; d < D; ++d) {
-    if (batch_max[d] > e->max_abs[d]) e->recs_valid = false;  // kRecTight was judged against the old bound
-    e->max_abs[d] = std::max(batch_max[d], e->max_abs[d]);
-    e->or_abs[d] |= batch_or[d];
+    if (f.max[d] > e->max_abs[d]) e->recs_valid = false;  // kRecTight was judged against the old bound
+    e->max_abs[d] = std::max(f.max[d], e->max_abs[d]);
+    e->or_abs[d] |= f.bits[d];
   }
   if (!patch) e->views.invalidate();
   // the match cache: these rows get new atom rows below — the next cached sweep refreshes their words first (a list that outgrows
@@ -96,7 +109,7 @@ static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int6
   // the overflow guard's bound grows by what this batch brings; only when it passes 2^60 does the next reconcile count
   // exactly on the device (request_sums_in_range), which also forgets the overwritten and deleted pods again
   for (int d = 0; d < D; ++d) {
-    e->req_sum_bound[d] += batch_total[d];
+    e->req_sum_bound[d] += f.total[d];
     if (e->req_sum_bound[d] > rank_sum_bound(e->exchange_world)) e->req_sums_valid = false;
   }
   e->pod_ns_hi = ns_hi;
@@ -263,6 +276,12 @@ static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int6
   return KT_OK;
 }
 
+static int32_t upsert_pods_locked(kt_engine* e, const kt_snapshot* b, const int64_t* rows) {
+  PodBatchFacts facts;
+  int32_t rc = validate_pods(e, b, rows, facts);
+  return rc != KT_OK ? rc : commit_pods(e, b, rows, facts);
+}
+
 int32_t kt_upsert_pods(kt_engine* e, const kt_snapshot* b, const int64_t* rows) {
   if (!e || !b) return KT_ERR_INVALID_ARGUMENT;
   StateLock lk(e, /*settle=*/false);  // pod feed calls pipeline on the engine's stream
@@ -352,23 +371,18 @@ int32_t kt_delete_pods(kt_engine* e, int64_t n, const int64_t* rows) {
   return KT_OK;
 }
 
-static int32_t upsert_throttles_locked(kt_engine* e, const kt_snapshot* b, const int32_t* rows) {
+// The whole batch against the engine's shape, before anything of it is kept (kt_throttle_batch.cpp: rows, namespace ids, offsets,
+// operators, term flags, masks, the 2^60 bound).  Writes nothing but the error text.
+static int32_t validate_throttles(kt_engine* e, const kt_snapshot* b, const int32_t* rows) {
+  char msg[256];
+  int32_t rc = kt::validate_throttle_batch(b, rows, e->D, e->cfg.throttle_capacity, e->cfg.namespace_capacity, msg, sizeof msg);
+  return rc == KT_OK ? KT_OK : e->fail(rc, "%s", msg);
+}
+
+// ---- the batch validate_throttles has passed is stored, entry by entry in batch order: the last entry of a row wins
+static int32_t commit_throttles(kt_engine* e, const kt_snapshot* b, const int32_t* rows) {
   const int D = e->D;
-  if (b->n_thr > 0 && b->D != D) return e->fail(KT_ERR_INVALID_ARGUMENT, "batch D=%d, engine D=%d", b->D, D);
-  for (int32_t i = 0; i < b->n_thr; ++i) {
-    const int32_t row = rows ? rows[i] : i;
-    if (row < 0 || row >= e->cfg.throttle_capacity) return e->fail(KT_ERR_OUT_OF_RANGE, "throttle row %d", row);
-    if (!(b->thr_flags[i] & KT_THR_CLUSTER) && b->thr_ns[i] >= (uint32_t)e->cfg.namespace_capacity)
-      return e->fail(KT_ERR_OUT_OF_RANGE, "throttle %d: namespace id %u", i, b->thr_ns[i]);
-  }
   if (b->n_thr <= 0) return KT_OK;
-  for (int32_t i = 0; i < b->n_thr; ++i) {  // the whole batch is validated before the first row is stored
-    HostAmount u, r;
-    amount_from_table(b->thr_used, (size_t)i, D, u);
-    amount_from_table(b->thr_reserved, (size_t)i, D, r);
-    if (!amount_in_bound(u, D) || !amount_in_bound(r, D))
-      return e->fail(KT_ERR_OVERFLOW_RISK, "throttle %d: status.used / reserved beyond 2^60", i);
-  }
   int32_t rc = sync_status_to_host(e);
   if (rc != KT_OK) return rc;
   for (int32_t i = 0; i < b->n_thr; ++i) {
@@ -379,8 +393,8 @@ static int32_t upsert_throttles_locked(kt_engine* e, const kt_snapshot* b, const
     amount_from_table(b->thr_calc, (size_t)i, D, h.calc);
     amount_from_table(b->thr_used, (size_t)i, D, h.used);
     amount_from_table(b->thr_reserved, (size_t)i, D, h.reserved);
-    h.thrl_flag = b->thr_thrl_flag[i] & ((1u << D) - 1u);
-    h.thrl_has = b->thr_thrl_has[i] & ((1u << D) - 1u);
+    h.thrl_flag = b->thr_thrl_flag[i];  // (bits at or above D were refused)
+    h.thrl_has = b->thr_thrl_has[i];
     h.status_fp = b->thr_status_msgs_fp[i];
     h.spec_fp = b->thr_spec_msgs_fp[i];
     for (uint32_t o = b->thr_ovr_off[i]; o < b->thr_ovr_off[i + 1]; ++o) {
@@ -416,6 +430,11 @@ static int32_t upsert_throttles_locked(kt_engine* e, const kt_snapshot* b, const
   // results of earlier launches describe the old throttle set (and its row count): not fetchable any more
   e->reconcile_ready = e->check_ready = false;
   return KT_OK;
+}
+
+static int32_t upsert_throttles_locked(kt_engine* e, const kt_snapshot* b, const int32_t* rows) {
+  int32_t rc = validate_throttles(e, b, rows);
+  return rc != KT_OK ? rc : commit_throttles(e, b, rows);
 }
 
 int32_t kt_upsert_throttles(kt_engine* e, const kt_snapshot* b, const int32_t* rows) {
@@ -516,36 +535,9 @@ int32_t kt_upsert_throttle(kt_engine* e, int32_t thr_row, uint32_t flags, uint32
                    n_preq ? const_cast<uint32_t*>(preq_val_off) : zero1, const_cast<uint32_t*>(preq_val)};
   b.nreq = kt_reqs{n_nreq, const_cast<uint8_t*>(nreq_op), const_cast<uint32_t*>(nreq_key),
                    n_nreq ? const_cast<uint32_t*>(nreq_val_off) : zero1, const_cast<uint32_t*>(nreq_val)};
-  if (n_terms > 0 && (term_preq_off[n_terms] > n_preq || term_nreq_off[n_terms] > n_nreq))
-    return e->fail(KT_ERR_OUT_OF_RANGE, "selector terms reference %u / %u requirements, pools hold %u / %u", term_preq_off[n_terms],
-                   term_nreq_off[n_terms], n_preq, n_nreq);
   // 37 positional arguments: one slice in the wrong position is a silent mis-feed unless the shapes are held against each
-  // other here — offsets start at 0 and never decrease, every operator is one of the four, masks name existing dimensions
-  auto bad = [&](const char* what, long long i, long long v) {
-    return e->fail(KT_ERR_INVALID_ARGUMENT, "kt_upsert_throttle(row %d): %s[%lld] = %lld does not fit the other arguments", thr_row, what, i, v);
-  };
-  const uint32_t dmask = D >= 32 ? ~0u : (1u << D) - 1u;
-  for (int k = 0; k < 4; ++k)
-    if (amt_present[k] & ~dmask) return bad("amt_present", k, amt_present[k]);
-  if ((thrl_has | thrl_flag) & ~dmask) return bad("thrl_has | thrl_flag", 0, thrl_has | thrl_flag);
-  for (int32_t o = 0; o < n_ovr; ++o)
-    if (ovr_present[o] & ~dmask) return bad("ovr_present", o, ovr_present[o]);
-  if (n_terms > 0 && (term_preq_off[0] != 0u || term_nreq_off[0] != 0u)) return bad("term_preq_off / term_nreq_off", 0, term_preq_off[0] | term_nreq_off[0]);
-  for (int32_t t = 0; t < n_terms; ++t) {
-    if (term_preq_off[t + 1] < term_preq_off[t]) return bad("term_preq_off", t + 1, term_preq_off[t + 1]);
-    if (term_nreq_off[t + 1] < term_nreq_off[t]) return bad("term_nreq_off", t + 1, term_nreq_off[t + 1]);
-    if (term_flags[t] & ~(KT_TERM_POD_SEL_INVALID | KT_TERM_NS_SEL_INVALID)) return bad("term_flags", t, term_flags[t]);
-  }
-  struct Pool { const char* name; uint32_t n; const uint8_t* op; const uint32_t* val_off; const uint32_t* val; };
-  const Pool pools[2] = {{"preq", n_preq, preq_op, preq_val_off, preq_val}, {"nreq", n_nreq, nreq_op, nreq_val_off, nreq_val}};
-  for (const Pool& pl : pools) {
-    if (pl.n && pl.val_off[0] != 0u) return bad(pl.name, 0, pl.val_off[0]);
-    for (uint32_t r = 0; r < pl.n; ++r) {
-      if (pl.op[r] > KT_OP_DOES_NOT_EXIST) return bad(pl.name, r, pl.op[r]);
-      if (pl.val_off[r + 1] < pl.val_off[r]) return bad(pl.name, r + 1, pl.val_off[r + 1]);
-    }
-    if (pl.n && pl.val_off[pl.n] > 0u && !pl.val) return bad(pl.name, pl.n, pl.val_off[pl.n]);
-  }
+  // other — offsets start at 0 and never decrease, every operator is one of the four, masks name existing dimensions.  The batch
+  // form holds them (kt_throttle_batch.cpp) and names the array by its kt_snapshot field: thr_spec.present for amt_present[0], ...
   return kt_upsert_throttles(e, &b, &thr_row);
 }
 
@@ -554,8 +546,13 @@ int32_t kt_load_snapshot(kt_engine* e, const kt_snapshot* s) {
   if (!e || !s) return KT_ERR_INVALID_ARGUMENT;
   StateLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
+  // everything that can refuse the snapshot comes first: a refused load leaves the engine as it was, like every other feed call
   if (s->n_ns > e->cfg.namespace_capacity || s->n_pods > e->cfg.pod_capacity || s->n_thr > e->cfg.throttle_capacity)
     return e->fail(KT_ERR_OUT_OF_RANGE, "snapshot larger than the configured capacity");
+  int32_t rc = validate_throttles(e, s, nullptr);
+  if (rc != KT_OK) return rc;
+  PodBatchFacts facts;
+  if ((rc = validate_pods(e, s, nullptr, facts)) != KT_OK) return rc;
   if (e->last_stream) KT_HIP(e, hipStreamSynchronize(e->last_stream));
   // clear
   KT_HIP(e, hipMemsetAsync(e->pods.flags, 0, (size_t)e->cfg.pod_capacity * 4, e->own_stream));
@@ -588,9 +585,8 @@ int32_t kt_load_snapshot(kt_engine* e, const kt_snapshot* s) {
       n.labels.emplace_back(s->ns_label_key[k], s->ns_label_pair[k]);
   }
   e->ns_rows_hi = s->n_ns;
-  int32_t rc = upsert_throttles_locked(e, s, nullptr);
-  if (rc != KT_OK) return rc;
-  return upsert_pods_locked(e, s, nullptr);
+  if ((rc = commit_throttles(e, s, nullptr)) != KT_OK) return rc;
+  return commit_pods(e, s, nullptr, facts);
 }
 
 int32_t kt_set_reserved(kt_engine* e, int32_t n, const int32_t* rows, const kt_amounts* reserved) {

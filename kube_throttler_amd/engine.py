@@ -47,6 +47,7 @@ EXPORTS = [
     "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch", "kt_paged_headroom_gangs",
     "kt_headroom_forecast_launch", "kt_headroom_forecast_fetch", "kt_paged_headroom_forecast",
     "kt_headroom_forecast_gangs_launch", "kt_headroom_forecast_gangs_fetch", "kt_paged_headroom_forecast_gangs",
+    "kt_validate_throttles",
 ]
 HEADROOM_MAX_CAP = 0x7FFFFFFF
 PREEMPT_NONE = -1
@@ -68,6 +69,17 @@ def partial_layout(n_dims: int) -> dict:
     if rc != KT_OK:
         raise EngineError(rc, f"kt_partial_layout({n_dims})")
     return dict(zip(("stride", "values", "presence", "pods", "errors"), (int(x.value) for x in v)))
+
+
+def validate_throttles(batch: S.Snapshot, n_dims: int, throttle_capacity: int, namespace_capacity: int, rows=None):
+    """kt_validate_throttles(): the validation pass of kt_upsert_throttles over ``batch`` for an engine of this shape (no engine,
+    no GPU needed) -> (code, text): KT_OK and '' or what the feed call would answer and kt_last_error would say."""
+    st = batch.as_struct()
+    a = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+    err = C.create_string_buffer(256)
+    rc = lib().kt_validate_throttles(C.byref(st), None if a is None else a.ctypes.data, int(n_dims), int(throttle_capacity),
+                                     int(namespace_capacity), err, len(err))
+    return rc, err.value.decode()
 
 
 def version() -> str:
@@ -385,6 +397,8 @@ def lib():
         L.kt_delete_pods.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.kt_delete_throttles.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.kt_load_snapshot.argtypes = [C.c_void_p, C.POINTER(S.KtSnapshot)]
+        if hasattr(L, "kt_validate_throttles"):  # (KT_ENGINE_LIB may name an older build)
+            L.kt_validate_throttles.argtypes = [C.POINTER(S.KtSnapshot), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]
         L.kt_set_reserved.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(S.KtAmounts)]
         L.kt_set_status.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(KtStatus)]
         L.kt_reconcile_launch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]
@@ -837,12 +851,17 @@ class Engine:
         """kt_admit_gangs_launch: the queue ``rows`` in consecutive gangs ``[gang_off[g], gang_off[g + 1])``, each admitted all or
         nothing (a gang with a member that is not admitted is rolled back before the next one starts) ->
         (status matrix, summary words — both as PreFilter answered at each pod's turn —, admitted byte per gang)."""
+        n, ng = self.admit_gangs_launch(rows, gang_off, on_equal, commit)
+        status, summary = self.check_fetch(n, want_status)
+        return status, summary, self.admit_gangs_fetch(ng)
+
+    def admit_gangs_launch(self, rows, gang_off, on_equal=False, commit=False, stream=None):
+        """kt_admit_gangs_launch alone -> (queue length, gangs): read the results with check_fetch and admit_gangs_fetch."""
         a, p = self._rows(rows, np.int64)
         g = _gang_offsets(gang_off)
         n, ng = len(a), len(g) - 1
-        self._ck(lib().kt_admit_gangs_launch(self._h, n, p, ng, g.ctypes.data, int(on_equal), ADMIT_COMMIT if commit else 0, None))
-        status, summary = self.check_fetch(n, want_status)
-        return status, summary, self.admit_gangs_fetch(ng)
+        self._ck(lib().kt_admit_gangs_launch(self._h, n, p, ng, g.ctypes.data, int(on_equal), ADMIT_COMMIT if commit else 0, stream))
+        return n, ng
 
     def admit_gangs_fetch(self, n_gangs):
         admitted = np.zeros(max(n_gangs, 1), np.uint8)
