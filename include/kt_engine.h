@@ -376,6 +376,49 @@ int32_t kt_admit_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_
 int32_t kt_admit_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
                               int32_t on_equal, uint32_t flags, void* stream);
 int32_t kt_admit_gangs_fetch(kt_engine* e, int64_t n_gangs, uint8_t* out_admitted);
+/* ---- elastic gangs: a gang is admitted once its QUORUM of members fits (Coscheduling's PodGroup.minMember, Volcano's
+ *      minAvailable, Kueue's partial admission), and a member can be made mandatory (a per-task minAvailable: the launcher of an
+ *      MPI job, the head of a Ray cluster).  No prefix or subset of a gang can be judged without the walk — each admitted member
+ *      reserves against the throttles the later ones meet — so the quorum is decided where the walk runs.  Gangs as in
+ *      kt_admit_gangs_launch; min_members [n_gangs]; member_flags [n], nullable (no member is required), bit 0 =
+ *      KT_GANG_MEMBER_REQUIRED.  For g = 0..n_gangs-1 IN ORDER:
+ *      (1)  the walk is kt_admit_gangs_launch's, rules (1), (2) and (4) unchanged: every member, in order, against the stored
+ *           status plus the CURRENT reserved amounts, Reserve on Success; every member is evaluated, also behind one that failed;
+ *           out_summary[i] / out_status[i][*] (kt_check_fetch) are what PreFilter returned at the pod's turn;
+ *      (2)  a member SUCCEEDS iff its verdict at its turn is Success — an Error verdict, an invalid pod row or a pod affected by
+ *           more throttles than the kernel's list holds does not;
+ *      (3)  gang g is admitted iff at least min_members[g] members succeeded AND every member whose flag byte has
+ *           KT_GANG_MEMBER_REQUIRED succeeded;
+ *      (4)  in an admitted gang the members that succeeded stay reserved, the others never reserved; out_members[g]
+ *           (kt_admit_gangs_elastic_fetch) is the number that stay, at least 1;
+ *      (5)  a gang that is not admitted is rolled back exactly as rule (3) of kt_admit_gangs_launch describes — values, pod count,
+ *           which names are present and whether a count is present — and out_members[g] = 0;
+ *      (6)  no per-pod output beyond the existing ones is needed: member i of gang g is in iff out_members[g] > 0 and its
+ *           summary word says Success;
+ *      (7)  KT_ADMIT_COMMIT keeps the final reserved amounts, without it the call is a dry run;
+ *      (8)  with min_members[g] == size of g for every gang and member_flags == NULL, and with every member flagged required at
+ *           any min_members, the call is kt_admit_gangs_launch byte for byte: status, summary, reserved amounts, and
+ *           out_members[g] > 0 where out_admitted[g];
+ *      (9)  a gang of one pod with min_members = 1 is kt_admit_launch's admission of that pod;
+ *      (10) refused before anything is launched, in this order: every gang_off defect kt_admit_gangs_launch refuses;
+ *           min_members == NULL with n_gangs > 0; a min_members[g] outside [1, size of g] (KT_ERR_INVALID_ARGUMENT, the message
+ *           names the gang and both numbers); a flag byte with a bit other than bit 0 (KT_ERR_INVALID_ARGUMENT, the message names
+ *           the queue position); then everything kt_admit_launch refuses.  A refused call leaves the reserved amounts alone, with
+ *           KT_ADMIT_COMMIT too;
+ *      (11) the call uses the gang slot of kt_admit_gangs_launch: behind it kt_admit_gangs_elastic_fetch answers the counts and
+ *           kt_admit_gangs_fetch the bytes (1 where the count is above 0); behind a plain kt_admit_gangs_launch the elastic fetch
+ *           answers KT_ERR_NOT_READY (no counts were kept);
+ *      (12) an engine without throttle rows decides on the host from the summaries, with the same rule; n == 0 is KT_OK and
+ *           launches nothing;
+ *      (13) the duplicate-pod rule of kt_admit_launch holds (the C++ plugin mirror's AdmitElasticGangs takes such a gang through
+ *           PreFilter / Reserve / Unreserve per member).
+ *      One launch: kt_admit_gangs_elastic, the third form of kt_admit's walk; it keeps the state of the gang form and no more, and
+ *      the caller's arrays are not referenced after return. ----------------------------------------------------------------- */
+#define KT_GANG_MEMBER_REQUIRED 0x1u
+int32_t kt_admit_gangs_elastic_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                      const int64_t* min_members /* [n_gangs] */, const uint8_t* member_flags /* [n], nullable */,
+                                      int32_t on_equal, uint32_t flags, void* stream);
+int32_t kt_admit_gangs_elastic_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_members);
 /* ---- headroom: how many copies of a pod the throttles still admit — what a Deployment, Job or autoscaler asks before it
  *      creates pods.  headroom(pod, cap, on_equal) is the number of LEADING Success verdicts kt_admit_launch returns, as a dry
  *      run (no KT_ADMIT_COMMIT), for the queue [pod] * cap against the stored status and the current reserved amounts:
@@ -876,6 +919,14 @@ int32_t kt_paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, cons
 int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
                              const int64_t* gang_off, int32_t on_equal, uint32_t flags, uint64_t* out_summary, uint8_t* out_status,
                              uint8_t* out_gang_admitted);
+/* kt_admit_gangs_elastic_launch over the pages, synchronous, as kt_paged_admit_gangs is kt_admit_gangs_launch over the pages (the
+ * same refusals, in clause (10)'s order, locking and ordering; n_pages == 1 is kt_admit_gangs_elastic_launch + kt_check_fetch +
+ * kt_admit_gangs_elastic_fetch): a kept gang's succeeded members stay reserved on every page, a gang that misses its quorum or a
+ * required member is rolled back on every page.  out_summary [n], out_status [n][throttle rows] and out_members [n_gangs] are all
+ * nullable. */
+int32_t kt_paged_admit_gangs_elastic(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                     const int64_t* gang_off, const int64_t* min_members, const uint8_t* member_flags, int32_t on_equal,
+                                     uint32_t flags, uint64_t* out_summary, uint8_t* out_status, int64_t* out_members);
 /* kt_headroom_launch over the pages, synchronous (n_pages == 1 is kt_headroom_launch + kt_headroom_fetch): the copies of
  * pod_rows[i] that every page's names and the pod count (page 0) still admit — the name part is the minimum over the pages —
  * and the limiting throttle row.  One kt_check of page 0 and ONE kt_headroom launch over every page's tables on page 0's stream.

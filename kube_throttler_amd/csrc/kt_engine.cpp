@@ -396,9 +396,9 @@ int32_t kt_engine_destroy(kt_engine* e) {
                               &e->d_ovr_off, &e->d_out_thrl_flag, &e->d_out_thrl_has};
   for (auto* b : u32s) b->release();
   DevBuf<uint8_t>* u8s[] = {&e->d_term_flags, &e->d_req_op, &e->d_ns_valid, &e->d_ovr_flags, &e->d_out_calc_updated,
-                            &e->d_out_thrl_pod, &e->d_out_error, &e->d_recs2[0], &e->d_recs2[1], &e->d_wvimg[0], &e->d_wvimg[1], &e->d_status, &e->d_stage, &e->d_ev_stage, &e->d_slab, &e->d_admit, &e->d_admit_pages, &e->d_preempt_pages, &e->d_gang_out};
+                            &e->d_out_thrl_pod, &e->d_out_error, &e->d_recs2[0], &e->d_recs2[1], &e->d_wvimg[0], &e->d_wvimg[1], &e->d_status, &e->d_stage, &e->d_ev_stage, &e->d_slab, &e->d_admit, &e->d_admit_pages, &e->d_preempt_pages, &e->d_gang_out, &e->d_gang_flags};
   for (auto* b : u8s) b->release();
-  e->d_status_fp.release(); e->d_spec_fp.release(); e->d_summary.release(); e->d_rows.release(); e->d_gang_off.release();
+  e->d_status_fp.release(); e->d_spec_fp.release(); e->d_summary.release(); e->d_rows.release(); e->d_gang_off.release(); e->d_gang_min.release(); e->d_gang_members.release();
   e->d_headroom_copies.release(); e->d_headroom_limiting.release(); e->d_headroom_gang_off.release(); e->d_headroom_blocker.release();
   e->d_preempt_prefix.release(); e->d_preempt_victims.release(); e->d_preempt_partial.release(); e->d_preempt_gang_off.release(); e->d_preempt_blocker.release(); e->d_reprieve_ws.release();
   e->d_forecast_first.release(); e->d_forecast_verdicts.release(); e->d_forecast_inst_s.release(); e->d_forecast_inst_ns.release();

@@ -298,12 +298,17 @@ int32_t kt_sweep_launch(kt_engine* e, int64_t now_s, int32_t now_ns, uint32_t fl
 // device behind page 0's check slot (kt_check_fetch).
 // Gangs (n_gangs >= 0 with gang_off, else -1: the plain queue): validated by the caller (gangs_valid); page 0 keeps the offsets and the
 // gang bytes on the device (kt_admit_gangs_fetch).
+// Elastic gangs (min_members set, member_flags nullable; validated by the caller: elastic_valid): page 0 keeps the quorums, the flag
+// bytes and the kept members per gang beside them (kt_admit_gangs_elastic_fetch).
 static int32_t admit_locked(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
-                            hipStream_t s, int64_t n_gangs = -1, const int64_t* gang_off = nullptr) {
+                            hipStream_t s, int64_t n_gangs = -1, const int64_t* gang_off = nullptr, const int64_t* min_members = nullptr,
+                            const uint8_t* member_flags = nullptr) {
   kt_engine* e0 = pages[0];
   const int32_t T = e0->thr_rows_hi;
   const bool gangs = n_gangs >= 0;
+  const bool elastic = gangs && min_members != nullptr;
   e0->gang_ready = false;
+  e0->gang_elastic = false;
   for (int32_t k = 0; k < n_pages; ++k)
     if (pages[k]->wide)
       return pages[k]->fail(KT_ERR_UNSUPPORTED, "admit queue: the stored `used` of page %d is wider than int64 (kt_admit reads int64 tables)", k);
@@ -313,17 +318,33 @@ static int32_t admit_locked(kt_engine* const* pages, int32_t n_pages, int64_t n,
   //     in every page; statuses against the current reserved amounts)
   if (gangs && n_gangs > 0) {
     // the offsets go up in front of the check launch: the caller's memory is not referenced after return
-    if (e0->d_gang_off.cap < (size_t)n_gangs + 1 || e0->d_gang_out.cap < (size_t)n_gangs) {
+    const bool grow_elastic = elastic && (e0->d_gang_min.cap < (size_t)n_gangs || e0->d_gang_members.cap < (size_t)n_gangs ||
+                                          (member_flags && e0->d_gang_flags.cap < (size_t)n));
+    if (e0->d_gang_off.cap < (size_t)n_gangs + 1 || e0->d_gang_out.cap < (size_t)n_gangs || grow_elastic) {
       if (e0->last_stream) KT_HIP(e0, hipStreamSynchronize(e0->last_stream));  // the buffers may still be in use
       KT_HIP(e0, e0->d_gang_off.reserve((size_t)n_gangs + 1));
       KT_HIP(e0, e0->d_gang_out.reserve((size_t)n_gangs));
+      if (elastic) {
+        KT_HIP(e0, e0->d_gang_min.reserve((size_t)n_gangs));
+        KT_HIP(e0, e0->d_gang_members.reserve((size_t)n_gangs));
+        if (member_flags) KT_HIP(e0, e0->d_gang_flags.reserve((size_t)n));
+      }
     }
     KT_HIP(e0, hipMemcpyAsync(e0->d_gang_off.p, gang_off, ((size_t)n_gangs + 1) * 8, hipMemcpyHostToDevice, s));
+    if (elastic) {
+      KT_HIP(e0, hipMemcpyAsync(e0->d_gang_min.p, min_members, (size_t)n_gangs * 8, hipMemcpyHostToDevice, s));
+      if (member_flags) KT_HIP(e0, hipMemcpyAsync(e0->d_gang_flags.p, member_flags, (size_t)n, hipMemcpyHostToDevice, s));
+    }
     KT_HIP(e0, hipStreamSynchronize(s));
     e0->h_gang_off.assign(gang_off, gang_off + n_gangs + 1);
+    if (elastic) {
+      e0->h_gang_min.assign(min_members, min_members + n_gangs);
+      if (member_flags) e0->h_gang_flags.assign(member_flags, member_flags + n);
+      else e0->h_gang_flags.clear();
+    }
   }
   int32_t rc = check_launch_locked(e0, n, pod_rows, on_equal, KT_CHECK_STATUS_MATRIX, s, /*allow_small=*/false);
-  if (rc == KT_OK && gangs) e0->gang_ready = true, e0->gang_n = n_gangs, e0->gang_on_device = n > 0 && T > 0;
+  if (rc == KT_OK && gangs) e0->gang_ready = true, e0->gang_n = n_gangs, e0->gang_on_device = n > 0 && T > 0, e0->gang_elastic = elastic;
   if (rc != KT_OK || n == 0 || T == 0) return rc;  // (no throttle rows: a gang is admitted iff no member's PreFilter is an error)
   // (b) the queue in order, one wave, every page's reserved amounts side by side in LDS
   if (!e0->admit_pages_ev) KT_HIP(e0, hipEventCreateWithFlags(&e0->admit_pages_ev, hipEventDisableTiming));
@@ -335,11 +356,12 @@ static int32_t admit_locked(kt_engine* const* pages, int32_t n_pages, int64_t n,
   KT_HIP(e0, e0->d_admit_pages.reserve(sizeof(kt::AdmitPage) * (size_t)n_pages));
   static const bool force_global = getenv("KT_ADMIT_FORCE_GLOBAL") != nullptr;  // test hook: HBM-resident state
   hipError_t herr = hipSuccess;
-  const kt::AdmitGangs ga{e0->d_gang_off.p, n_gangs, e0->d_gang_out.p};
+  kt::AdmitGangs ga{e0->d_gang_off.p, n_gangs, e0->d_gang_out.p};
+  if (elastic) ga.min_dev = e0->d_gang_min.p, ga.flags_dev = member_flags ? e0->d_gang_flags.p : nullptr, ga.members_dev = e0->d_gang_members.p;
   const bool launched = kt::launch_admit(e0->h_admit_pages.data(), n_pages, (kt::AdmitPage*)e0->d_admit_pages.p, e0->admit_pages_ev, n,
                                          pod_rows ? e0->d_rows.p : nullptr, T, on_equal != 0, commit, e0->d_status.p, e0->d_summary.p,
                                          e0->d_admit.p, force_global, s, &herr, gangs ? &ga : nullptr);
-  if (herr != hipSuccess || !launched) e0->gang_ready = false;
+  if (herr != hipSuccess || !launched) e0->gang_ready = false, e0->gang_elastic = false;
   if (herr != hipSuccess) return e0->fail(KT_ERR_DEVICE, "admit queue: copy of the page descriptors: %s", hipGetErrorString(herr));
   if (!launched) return e0->fail(KT_ERR_UNSUPPORTED, "admit queue: %d throttle rows exceed the kernel's LDS list", T);
   KT_HIP(e0, hipGetLastError());
@@ -392,27 +414,75 @@ int32_t kt_admit_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, 
   return admit_locked(&e, 1, n, pod_rows, on_equal, flags, pick_stream(e, stream), n_gangs, gang_off);
 }
 
-// the gang bytes of the last gang launch, under the launch lock; out nullable
-static int32_t gangs_fetch_locked(kt_engine* e, int64_t n_gangs, uint8_t* out) {
+// the gang bytes of the last gang launch, under the launch lock; out nullable.  out_members (nullable): the kept members per gang of
+// an elastic launch, beside the bytes
+static int32_t gangs_fetch_locked(kt_engine* e, int64_t n_gangs, uint8_t* out, int64_t* out_members = nullptr) {
   if (!e->gang_ready) return e->fail(KT_ERR_NOT_READY, "kt_admit_gangs_fetch before kt_admit_gangs_launch");
   if (n_gangs < 0 || n_gangs > e->gang_n)
     return e->fail(KT_ERR_OUT_OF_RANGE, "n_gangs=%lld, the last gang launch had %lld gangs", (long long)n_gangs, (long long)e->gang_n);
   hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
   if (e->gang_on_device) {
     if (n_gangs && out) KT_HIP(e, hipMemcpyAsync(out, e->d_gang_out.p, (size_t)n_gangs, hipMemcpyDeviceToHost, s));
+    if (n_gangs && out_members) KT_HIP(e, hipMemcpyAsync(out_members, e->d_gang_members.p, (size_t)n_gangs * 8, hipMemcpyDeviceToHost, s));
     KT_HIP(e, hipStreamSynchronize(s));
     return KT_OK;
   }
-  // no throttle rows: nothing was reserved; a gang is admitted iff every member's PreFilter answered Success
+  // no throttle rows: nothing was reserved; a gang is admitted iff every member's PreFilter answered Success — an elastic one iff
+  // its quorum of members and every required one did
   std::vector<uint64_t> sm((size_t)e->check_n + 1);
   if (e->check_n) KT_HIP(e, hipMemcpyAsync(sm.data(), e->d_summary.p, (size_t)e->check_n * 8, hipMemcpyDeviceToHost, s));
   KT_HIP(e, hipStreamSynchronize(s));
-  for (int64_t g = 0; g < n_gangs && out; ++g) {
-    out[g] = 1;
-    for (int64_t i = e->h_gang_off[(size_t)g]; i < e->h_gang_off[(size_t)g + 1]; ++i)
-      if (sm[(size_t)i] != 0) out[g] = 0;
+  for (int64_t g = 0; g < n_gangs && (out || out_members); ++g) {
+    bool all = true, required_out = false;
+    int64_t n_in = 0;
+    for (int64_t i = e->h_gang_off[(size_t)g]; i < e->h_gang_off[(size_t)g + 1]; ++i) {
+      const bool ok = sm[(size_t)i] == 0;
+      all &= ok, n_in += ok ? 1 : 0;
+      if (!ok && e->gang_elastic && !e->h_gang_flags.empty() && (e->h_gang_flags[(size_t)i] & KT_GANG_MEMBER_REQUIRED)) required_out = true;
+    }
+    const bool kept = e->gang_elastic ? n_in >= e->h_gang_min[(size_t)g] && !required_out : all;
+    if (out) out[g] = kept ? 1 : 0;
+    if (out_members) out_members[g] = kept ? n_in : 0;
   }
   return KT_OK;
+}
+
+// what kt_admit_gangs_elastic_launch refuses behind gangs_valid: a missing quorum array, a quorum outside [1, size of the gang], a
+// flag byte with a bit other than KT_GANG_MEMBER_REQUIRED
+static int32_t elastic_valid(kt_engine* e, int64_t n, int64_t n_gangs, const int64_t* gang_off, const int64_t* min_members, const uint8_t* member_flags) {
+  if (n_gangs > 0 && !min_members) return e->fail(KT_ERR_INVALID_ARGUMENT, "admit elastic gangs: min_members is NULL");
+  for (int64_t g = 0; g < n_gangs; ++g) {
+    const int64_t size = gang_off[g + 1] - gang_off[g];
+    if (min_members[g] < 1 || min_members[g] > size)
+      return e->fail(KT_ERR_INVALID_ARGUMENT, "admit elastic gangs: min_members[%lld] = %lld of gang %lld is outside [1, %lld], the gang's size",
+                     (long long)g, (long long)min_members[g], (long long)g, (long long)size);
+  }
+  for (int64_t i = 0; member_flags && i < n; ++i)
+    if (member_flags[i] & ~(uint8_t)KT_GANG_MEMBER_REQUIRED)
+      return e->fail(KT_ERR_INVALID_ARGUMENT, "admit elastic gangs: member_flags[%lld] = 0x%02x at queue position %lld has a bit other than KT_GANG_MEMBER_REQUIRED",
+                     (long long)i, (unsigned)member_flags[i], (long long)i);
+  return KT_OK;
+}
+
+int32_t kt_admit_gangs_elastic_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                      const int64_t* min_members, const uint8_t* member_flags, int32_t on_equal, uint32_t flags, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  int32_t rc = gangs_valid(e, n, n_gangs, gang_off);
+  if (rc == KT_OK) rc = elastic_valid(e, n, n_gangs, gang_off, min_members, member_flags);
+  if (rc != KT_OK) return rc;
+  KT_HIP(e, hipSetDevice(e->device));
+  static const int64_t no_quorum = 0;  // (n_gangs == 0: the elastic form with nothing to read)
+  return admit_locked(&e, 1, n, pod_rows, on_equal, flags, pick_stream(e, stream), n_gangs, gang_off, min_members ? min_members : &no_quorum, member_flags);
+}
+
+int32_t kt_admit_gangs_elastic_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_members) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (e->gang_ready && !e->gang_elastic)
+    return e->fail(KT_ERR_NOT_READY, "kt_admit_gangs_elastic_fetch: the pending gang launch is kt_admit_gangs_launch, which keeps no counts");
+  return gangs_fetch_locked(e, n_gangs, nullptr, out_members);
 }
 
 int32_t kt_admit_gangs_fetch(kt_engine* e, int64_t n_gangs, uint8_t* out_admitted) {
@@ -676,28 +746,31 @@ int32_t paged_order(kt_engine* const* pages, int32_t n_pages, hipStream_t* s) {
 // kt_admit_launch / kt_admit_gangs_launch (n_gangs >= 0) over several engines, synchronous: what is specific to more than one engine,
 // then admit_locked
 static int32_t paged_admit(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags,
-                           uint64_t* out_summary, uint8_t* out_status, int64_t n_gangs, const int64_t* gang_off, uint8_t* out_gang_admitted) {
+                           uint64_t* out_summary, uint8_t* out_status, int64_t n_gangs, const int64_t* gang_off, uint8_t* out_gang_admitted,
+                           bool elastic = false, const int64_t* min_members = nullptr, const uint8_t* member_flags = nullptr,
+                           int64_t* out_members = nullptr) {
   PageLocks locks;
   int32_t rc = paged_lock("paged admit", pages, n_pages, n, locks);
   if (rc != KT_OK) return rc;
   kt_engine* e0 = pages[0];
   const int32_t T = e0->thr_rows_hi;
   if (n_gangs >= 0) {
-    const int32_t rcg = gangs_valid(e0, n, n_gangs, gang_off);
+    int32_t rcg = gangs_valid(e0, n, n_gangs, gang_off);
+    if (rcg == KT_OK && elastic) rcg = elastic_valid(e0, n, n_gangs, gang_off, min_members, member_flags);
     if (rcg != KT_OK) return rcg;
   }
   if ((rc = paged_same_cluster("paged admit", pages, n_pages, n, pod_rows)) != KT_OK) return rc;
   if (n == 0) return KT_OK;
   hipStream_t s = nullptr;
   if ((rc = paged_order(pages, n_pages, &s)) != KT_OK) return rc;
-  rc = admit_locked(pages, n_pages, n, pod_rows, on_equal, flags, s, n_gangs, gang_off);
+  rc = admit_locked(pages, n_pages, n, pod_rows, on_equal, flags, s, n_gangs, gang_off, elastic ? min_members : nullptr, member_flags);
   e0->check_ready = false;  // the call used page 0's check slot (as kt_affected_pods): a pending kt_check_launch is gone
   if (rc != KT_OK) return rc;
   if (out_summary) KT_HIP(e0, hipMemcpyAsync(out_summary, e0->d_summary.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   if (out_status && T > 0) KT_HIP(e0, hipMemcpyAsync(out_status, e0->d_status.p, (size_t)n * (size_t)T, hipMemcpyDeviceToHost, s));
   if (n_gangs >= 0) {
-    rc = gangs_fetch_locked(e0, n_gangs, out_gang_admitted);  // (synchronises s)
-    e0->gang_ready = false;  // the results have been handed out
+    rc = gangs_fetch_locked(e0, n_gangs, out_gang_admitted, elastic ? out_members : nullptr);  // (synchronises s)
+    e0->gang_ready = false, e0->gang_elastic = false;  // the results have been handed out
     return rc;
   }
   KT_HIP(e0, hipStreamSynchronize(s));
@@ -713,6 +786,14 @@ int32_t kt_paged_admit_gangs(kt_engine* const* pages, int32_t n_pages, int64_t n
                              int32_t on_equal, uint32_t flags, uint64_t* out_summary, uint8_t* out_status, uint8_t* out_gang_admitted) {
   if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
   return paged_admit(pages, n_pages, n, pod_rows, on_equal, flags, out_summary, out_status, n_gangs, gang_off, out_gang_admitted);
+}
+
+int32_t kt_paged_admit_gangs_elastic(kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows, int64_t n_gangs,
+                                     const int64_t* gang_off, const int64_t* min_members, const uint8_t* member_flags, int32_t on_equal, uint32_t flags,
+                                     uint64_t* out_summary, uint8_t* out_status, int64_t* out_members) {
+  if (n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  return paged_admit(pages, n_pages, n, pod_rows, on_equal, flags, out_summary, out_status, n_gangs, gang_off, nullptr, /*elastic=*/true, min_members,
+                     member_flags, out_members);
 }
 
 int32_t kt_paged_reconcile(kt_engine* const* pages, int32_t n_pages, int64_t now_s, int32_t now_ns, uint32_t flags, int32_t n,

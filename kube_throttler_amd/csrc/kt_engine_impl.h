@@ -366,6 +366,13 @@ struct kt_engine {
   std::vector<int64_t> h_gang_off;
   bool gang_ready = false, gang_on_device = false;  // on_device false: no throttle rows, the bytes follow from the summaries
   int64_t gang_n = 0;
+  // kt_admit_gangs_elastic_launch uses that slot: the quorum per gang, the flag byte per member (when the caller gave some) and the
+  // kept members per gang beside them, the inputs on the host too (no throttle rows: the counts follow from the summaries)
+  DevBuf<int64_t> d_gang_min, d_gang_members;
+  DevBuf<uint8_t> d_gang_flags;
+  std::vector<int64_t> h_gang_min;
+  std::vector<uint8_t> h_gang_flags;  // empty: no member is required
+  bool gang_elastic = false;          // the pending gang result holds counts (kt_admit_gangs_elastic_fetch)
   // the last kt_headroom_launch (on page 0): copies and limiting throttle row per pod, on the device until kt_headroom_fetch
   DevBuf<int64_t> d_headroom_copies;
   DevBuf<int32_t> d_headroom_limiting;

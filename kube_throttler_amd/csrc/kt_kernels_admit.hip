@@ -31,6 +31,11 @@
 // gang's: the reference recomputes the total over the remaining pods, reserved_resource_amounts.go:148-156, so a name only a
 // rolled-back pod brought in disappears again).  An admitted gang costs that copy and nothing else.  For the rollback the touched
 // throttles are re-derived from the members' matrix rows: step (3) rewrites nonzero bytes with nonzero bytes, the list is the same.
+//
+// Elastic gangs (kt_admit_gangs_elastic<DT, IN_LDS>, kt_admit_gangs_elastic_launch): the same walk with another rule at the gang's
+// end — the gang stays when at least min_members[g] members succeeded and no member flagged KT_GANG_MEMBER_REQUIRED failed
+// (PodGroup.minMember / Volcano's minAvailable, a mandatory role).  A kept gang keeps what its succeeded members reserved (the ones
+// that failed never stored: nothing to restore); a gang that misses the rule goes through the rollback above, unchanged.
 #include "kt_admit_common.h"
 
 namespace kt {
@@ -53,7 +58,14 @@ struct AdmitGangArgs {
   uint8_t* gang_out;        // [n_gangs] 1 admitted, 0 rolled back
   uint32_t off_rq, rq_stride;  // page k's saved presence words at off_rq + k * rq_stride (LDS or scratch, as the state)
   uint32_t off_tag;            // [T] 1 + the gang that saved the throttle's presence words last (0: none)
+  // the elastic form (kt_admit_gangs_elastic) alone
+  const int64_t* min_members;   // [n_gangs] the quorum: members that must succeed, in [1, size of the gang]
+  const uint8_t* member_flags;  // [n] nullable: bit 0 = the member is required
+  int64_t* members_out;         // [n_gangs] members that stay reserved; 0: rolled back
 };
+// how a span of the queue ends: never undone (the plain queue), undone unless every member succeeded (gangs), undone unless the
+// quorum and every required member succeeded (elastic gangs)
+enum AdmitMode { kAdmitQueue = 0, kAdmitGangs = 1, kAdmitElastic = 2 };
 
 // The mutable state (reserved amounts of all throttles) lives in LDS when it fits; otherwise in a scratch buffer in
 // HBM that only this wave touches, read and written through L2 (agent-scope atomics: never served from a stale L1 line).
@@ -242,8 +254,11 @@ __device__ __forceinline__ void admit_unreserve(const AdmitPage& pg, const Admit
 // GANGS: the queue positions [gang_off[g], gang_off[g + 1]) are admitted all or nothing, gang after gang; a gang with a member
 // that was not admitted is rolled back (every member that reserved: Unreserve on every page) before the next one starts.  The
 // per-pod outputs stay what PreFilter returned at the pod's turn.  Without GANGS the whole queue is one span that is never undone.
-template <int DT, bool IN_LDS, bool GANGS>
+// ELASTIC: the gang is kept iff at least min_members[g] members succeeded and no required one failed; the members that failed never
+// stored, so a kept partial gang needs no restore, and one that misses the rule takes the same rollback.
+template <int DT, bool IN_LDS, int MODE>
 __device__ __forceinline__ void admit_walk(const AdmitPagedArgs& a, const AdmitGangArgs& ga) {
+  constexpr bool GANGS = MODE != kAdmitQueue, ELASTIC = MODE == kAdmitElastic;
   KT_LDS unsigned char* lds = (KT_LDS unsigned char*)kt_smem;
   lds_u32wp list = (lds_u32wp)(lds + a.off_list);  // affected throttles of the current pod
   const int T = a.T, n_pages = a.n_pages;
@@ -263,15 +278,34 @@ __device__ __forceinline__ void admit_walk(const AdmitPagedArgs& a, const AdmitG
   const bool eq = a.on_equal != 0;
   const int64_t n_spans = GANGS ? ga.n_gangs : 1;
   int64_t span_begin = 0, span_end = GANGS ? ga.gang_off[n_spans > 0 ? 1 : 0] : a.n;  // (gang_off[0] == 0)
+  int64_t quorum_next = 0;  // ELASTIC: min_members of the next gang
+  if constexpr (ELASTIC)
+    if (n_spans > 0) quorum_next = ga.min_members[0];
   for (int64_t g = 0; g < n_spans; ++g) {
     const int64_t i0 = span_begin, i1 = span_end;
+    const int64_t quorum = quorum_next;
     if constexpr (GANGS) {  // the next gang's end is asked for a gang ahead: its trip to HBM runs beside this gang's walk
       span_begin = i1;
-      if (g + 1 < n_spans) span_end = ga.gang_off[g + 2];
+      if (g + 1 < n_spans) {
+        span_end = ga.gang_off[g + 2];
+        if constexpr (ELASTIC) quorum_next = ga.min_members[g + 1];  // ... and its quorum beside it
+      }
     }
     bool all_in = true;  // wave-uniform: every member so far was admitted
+    int64_t n_in = 0;           // ELASTIC, wave-uniform: members that succeeded so far
+    bool required_out = false;  // ELASTIC, wave-uniform: a required member failed
     for (int64_t i = i0; i < i1; ++i) {
-      const int64_t p = a.rows ? a.rows[i] : i;
+      // ELASTIC: the flag byte is asked for in front of the pod row, without a branch (no flags: a byte that is there anyway, masked
+      // off below), and first looked at behind the verdict: one trip to memory with the row's
+      uint32_t flag_byte = 0;
+      int64_t p;
+      if constexpr (ELASTIC) {  // (the row without a branch too, so that the two loads leave together)
+        flag_byte = *(ga.member_flags ? ga.member_flags + i : (const uint8_t*)ga.gang_off);
+        const int64_t r = *(a.rows ? a.rows + i : ga.gang_off);
+        p = a.rows ? r : i;
+      } else {
+        p = a.rows ? a.rows[i] : i;
+      }
       uint8_t* row = a.status + i * T;
       // ---- (1) affected throttles: nonzero bytes of the matrix row, 16 per lane and chunk
       bool err;
@@ -280,6 +314,7 @@ __device__ __forceinline__ void admit_walk(const AdmitPagedArgs& a, const AdmitG
         // error row (selector / namespace error, plugin.go:154-168), empty row, or a pod affected by more
         // throttles than the list holds: the pre-computed summary stands and nothing is reserved
         if constexpr (GANGS) all_in = false;
+        if constexpr (ELASTIC) required_out |= ga.member_flags && (flag_byte & 1u) != 0;
         continue;
       }
       // ---- (2) lane = (affected throttle, dimension), over every page
@@ -314,8 +349,10 @@ __device__ __forceinline__ void admit_walk(const AdmitPagedArgs& a, const AdmitG
       }
       if ((n_exc | n_act | n_ins) != 0) {
         if constexpr (GANGS) all_in = false;
+        if constexpr (ELASTIC) required_out |= ga.member_flags && (flag_byte & 1u) != 0;
         continue;
       }
+      if constexpr (ELASTIC) n_in += 1;
       // ---- (4) Success: Reserve on every page
       if constexpr (GANGS) {  // the first touch of a throttle in this gang saves every page's presence word of it
         const uint32_t gt = (uint32_t)g + 1u;
@@ -332,8 +369,13 @@ __device__ __forceinline__ void admit_walk(const AdmitPagedArgs& a, const AdmitG
       }
     }
     if constexpr (GANGS) {
-      if (lane == 0) ga.gang_out[g] = all_in ? 1 : 0;
-      if (!all_in) {
+      bool kept = all_in;  // wave-uniform: the gang stays
+      if constexpr (ELASTIC) {
+        kept = n_in >= quorum && !required_out;
+        if (lane == 0) ga.members_out[g] = kept ? n_in : 0;
+      }
+      if (lane == 0) ga.gang_out[g] = kept ? 1 : 0;
+      if (!kept) {
         // ---- rolled back: Unreserve of every member that reserved.  A member reserved iff it was not skipped in (1) — decided
         //      again from the same inputs (an error byte is never rewritten, nonzero bytes stay nonzero) — and its summary word,
         //      read back through L2, says Success
@@ -359,14 +401,18 @@ __device__ __forceinline__ void admit_walk(const AdmitPagedArgs& a, const AdmitG
     }
 }
 
-// the two kernels: the plain queue, and the queue in gangs
+// the three kernels: the plain queue, the queue in gangs, and the queue in elastic gangs
 template <int DT, bool IN_LDS>
 __global__ __launch_bounds__(kWave) void kt_admit(const AdmitPagedArgs a) {
-  admit_walk<DT, IN_LDS, false>(a, AdmitGangArgs{});
+  admit_walk<DT, IN_LDS, kAdmitQueue>(a, AdmitGangArgs{});
 }
 template <int DT, bool IN_LDS>
 __global__ __launch_bounds__(kWave) void kt_admit_gangs(const AdmitPagedArgs a, const AdmitGangArgs ga) {
-  admit_walk<DT, IN_LDS, true>(a, ga);
+  admit_walk<DT, IN_LDS, kAdmitGangs>(a, ga);
+}
+template <int DT, bool IN_LDS>
+__global__ __launch_bounds__(kWave) void kt_admit_gangs_elastic(const AdmitPagedArgs a, const AdmitGangArgs ga) {
+  admit_walk<DT, IN_LDS, kAdmitElastic>(a, ga);
 }
 
 // LDS: state + list when the state fits, else the list alone
@@ -380,11 +426,12 @@ size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages) {
   return b;
 }
 
-// gangs: one saved copy of the presence words per page and the gang tags, beside the state (LDS or scratch)
+// gangs (both forms): one saved copy of the presence words per page and the gang tags, beside the state (LDS or scratch)
 size_t admit_gang_extra_bytes(int T, int n_pages) { return ((size_t)n_pages + 1) * (((size_t)T * 4 + 15) / 16 * 16); }
 
 // scratch: admit_paged_state_bytes (+ admit_gang_extra_bytes with gangs) bytes of device memory, used when the state does not
-// fit in LDS (or when forced).  gangs (nullable): the gang form, its extra state counted for it alone
+// fit in LDS (or when forced).  gangs (nullable): the gang form, its extra state counted for it alone; with gangs->min_dev the
+// elastic form (the same extra state)
 bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,
                   bool on_equal, bool commit, uint8_t* status, uint64_t* summary, void* scratch, bool force_global, hipStream_t s,
                   hipError_t* hip_err, const AdmitGangs* gangs) {
@@ -409,6 +456,7 @@ bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_
     ga.off_rq = take(extra);
     ga.off_tag = ga.off_rq + (uint32_t)n_pages * ga.rq_stride;
     ga.gang_off = gangs->off_dev, ga.n_gangs = gangs->n_gangs, ga.gang_out = gangs->out_dev;
+    ga.min_members = gangs->min_dev, ga.member_flags = gangs->flags_dev, ga.members_out = gangs->members_dev;
   }
   if (!in_lds) o = 0;
   a.pages = pages_dev, a.n_pages = n_pages, a.rows = rows_dev, a.n = n, a.scratch = (unsigned char*)scratch;
@@ -420,7 +468,11 @@ bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_
   if ((*hip_err = hipEventRecord(pages_copied, s)) != hipSuccess) return false;
   const int DT = dt_bucket(maxD);
 #define KT_ADMIT_CASE(DT_)                                                                                        \
-  if (gangs) {                                                                                                   \
+  if (gangs && gangs->min_dev) {                                                                                 \
+    auto kfn = in_lds ? kt_admit_gangs_elastic<DT_, true> : kt_admit_gangs_elastic<DT_, false>;                  \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
+    hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a, ga);                                          \
+  } else if (gangs) {                                                                                            \
     auto kfn = in_lds ? kt_admit_gangs<DT_, true> : kt_admit_gangs<DT_, false>;                                  \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
     hipLaunchKernelGGL(kfn, dim3(1), dim3(kWave), lds_bytes, s, a, ga);                                          \

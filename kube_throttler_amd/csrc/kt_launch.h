@@ -98,10 +98,15 @@ size_t admit_state_bytes(int T, int D);  // one page
 size_t admit_paged_state_bytes(int T, const AdmitPage* pages, int n_pages);
 // gangs (kt_admit_gangs_launch): the queue positions [off_dev[g], off_dev[g + 1]) are admitted all or nothing, out_dev[g] = 1
 // admitted / 0 rolled back; the gang form keeps admit_gang_extra_bytes more state (LDS, or scratch behind the pages' state)
+// elastic gangs (kt_admit_gangs_elastic_launch, min_dev set): gang g is kept iff at least min_dev[g] members succeeded and none whose
+// flags_dev byte has bit 0 failed; members_dev[g] = the members that stay reserved, 0 rolled back.  The same extra state
 struct AdmitGangs {
   const int64_t* off_dev;  // [n_gangs + 1] in device memory
   int64_t n_gangs;
   uint8_t* out_dev;        // [n_gangs]
+  const int64_t* min_dev = nullptr;    // [n_gangs] nullable: all or nothing
+  const uint8_t* flags_dev = nullptr;  // [n] nullable: no member is required
+  int64_t* members_dev = nullptr;      // [n_gangs] with min_dev
 };
 size_t admit_gang_extra_bytes(int T, int n_pages);
 bool launch_admit(AdmitPage* pages, int n_pages, AdmitPage* pages_dev, hipEvent_t pages_copied, int64_t n, const int64_t* rows_dev, int T,

@@ -25,6 +25,7 @@ ERR_NAMES = {-1: "KT_ERR_INVALID_ARGUMENT", -2: "KT_ERR_OUT_OF_RANGE", -3: "KT_E
              -5: "KT_ERR_NOT_READY", -6: "KT_ERR_NO_DEVICE", -7: "KT_ERR_UNSUPPORTED"}
 RECONCILE_APPLY = 0x1
 ADMIT_COMMIT = 0x1
+GANG_MEMBER_REQUIRED = 0x1
 VARIANT_INCREMENTAL = 0x100  # | VARIANT_INDEXED: pod events keep the `used` partials current (N2)
 CHECK_STATUS_MATRIX = 0x1
 KERNEL_CHECK, KERNEL_AGGREGATE, KERNEL_FINALIZE, KERNEL_PREPARE, KERNEL_REDUCE = 0, 1, 2, 3, 4
@@ -41,6 +42,7 @@ EXPORTS = [
     "kt_comm_allreduce_partial", "kt_comm_destroy", "kt_reconcile_rows_launch", "kt_set_exchange_world", "kt_counter", "kt_reconcile_fetch_used_hi",
     "kt_set_wide_sums", "kt_partial_words", "kt_partial_layout", "kt_debug_reload_env", "kt_affected_pods", "kt_paged_check", "kt_paged_reconcile",
     "kt_paged_admit", "kt_admit_gangs_launch", "kt_admit_gangs_fetch", "kt_paged_admit_gangs",
+    "kt_admit_gangs_elastic_launch", "kt_admit_gangs_elastic_fetch", "kt_paged_admit_gangs_elastic",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
@@ -142,6 +144,42 @@ def paged_admit_gangs(engines, rows, gang_off, on_equal=False, commit=False):
     if rc != KT_OK:
         raise EngineError(rc, "kt_paged_admit_gangs: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
     return status[:n, :T], summary[:n], admitted[:ng]
+
+
+def _elastic_rule(min_members, required, n, ng):
+    """min_members [n_gangs] int64 and the flag bytes [n] (None: no member is required) of an elastic gang call."""
+    mm = np.ascontiguousarray(min_members, dtype=np.int64)
+    if mm.shape != (ng,):
+        raise ValueError(f"min_members: one quorum per gang ({ng}), got shape {mm.shape}")
+    if required is None:
+        return mm, None
+    rq = np.ascontiguousarray(required)
+    if rq.shape != (n,):
+        raise ValueError(f"required: one entry per queue position ({n}), got shape {rq.shape}")
+    if rq.dtype == np.bool_:
+        rq = rq.astype(np.uint8) * GANG_MEMBER_REQUIRED
+    return mm, np.ascontiguousarray(rq, dtype=np.uint8)
+
+
+def paged_admit_gangs_elastic(engines, rows, gang_off, min_members, required=None, on_equal=False, commit=False):
+    """kt_paged_admit_gangs_elastic: the queue ``rows`` in consecutive gangs, gang g kept once ``min_members[g]`` members and every
+    ``required`` one (bool, or flag bytes with GANG_MEMBER_REQUIRED, per queue position) succeeded, over the page engines ->
+    (status matrix [n][T] and summary words [n] at each pod's turn, members that stay reserved per gang: 0 rolled back)."""
+    hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    T = engines[0].throttle_rows()
+    rows_a = np.ascontiguousarray(rows, dtype=np.int64)
+    g = _gang_offsets(gang_off)
+    n, ng = len(rows_a), len(g) - 1
+    mm, rq = _elastic_rule(min_members, required, n, ng)
+    status = np.zeros((max(n, 1), max(T, 1)), np.uint8)
+    summary = np.zeros(max(n, 1), np.uint64)
+    members = np.zeros(max(ng, 1), np.int64)
+    rc = lib().kt_paged_admit_gangs_elastic(hs, len(engines), n, rows_a.ctypes.data if n else None, ng, g.ctypes.data,
+                                            mm.ctypes.data if ng else None, None if rq is None or not n else rq.ctypes.data, int(on_equal),
+                                            ADMIT_COMMIT if commit else 0, summary.ctypes.data, status.ctypes.data, members.ctypes.data)
+    if rc != KT_OK:
+        raise EngineError(rc, "kt_paged_admit_gangs_elastic: " + "; ".join(lib().kt_last_error(e._h).decode() for e in engines))
+    return status[:n, :T], summary[:n], members[:ng]
 
 
 def paged_headroom(engines, rows, cap, on_equal=False):
@@ -446,6 +484,11 @@ def lib():
         L.kt_fetch_reserved.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(S.KtAmounts)]
         L.kt_admit_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         L.kt_admit_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.kt_admit_gangs_elastic_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                    C.c_uint32, C.c_void_p]
+        L.kt_admit_gangs_elastic_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.kt_paged_admit_gangs_elastic.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_paged_admit_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_headroom_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
@@ -867,6 +910,33 @@ class Engine:
         admitted = np.zeros(max(n_gangs, 1), np.uint8)
         self._ck(lib().kt_admit_gangs_fetch(self._h, n_gangs, admitted.ctypes.data))
         return admitted[:n_gangs]
+
+    def admit_gangs_elastic(self, rows, gang_off, min_members, required=None, on_equal=False, commit=False, want_status=True):
+        """kt_admit_gangs_elastic_launch: the queue ``rows`` in consecutive gangs ``[gang_off[g], gang_off[g + 1])``; gang g is kept
+        once at least ``min_members[g]`` members succeeded and every ``required`` one did (bool, or flag bytes with
+        GANG_MEMBER_REQUIRED, per queue position; None: none), else rolled back -> (status matrix, summary words — both as PreFilter
+        answered at each pod's turn —, members that stay reserved per gang: 0 rolled back).  Member i of gang g is in iff
+        ``members[g] > 0`` and its summary word says Success."""
+        n, ng = self.admit_gangs_elastic_launch(rows, gang_off, min_members, required, on_equal, commit)
+        status, summary = self.check_fetch(n, want_status)
+        return status, summary, self.admit_gangs_elastic_fetch(ng)
+
+    def admit_gangs_elastic_launch(self, rows, gang_off, min_members, required=None, on_equal=False, commit=False, stream=None):
+        """kt_admit_gangs_elastic_launch alone -> (queue length, gangs): read the results with check_fetch and
+        admit_gangs_elastic_fetch (the counts) or admit_gangs_fetch (the bytes)."""
+        a, p = self._rows(rows, np.int64)
+        g = _gang_offsets(gang_off)
+        n, ng = len(a), len(g) - 1
+        mm, rq = _elastic_rule(min_members, required, n, ng)
+        self._ck(lib().kt_admit_gangs_elastic_launch(self._h, n, p, ng, g.ctypes.data, mm.ctypes.data if ng else None,
+                                                     None if rq is None or not n else rq.ctypes.data, int(on_equal),
+                                                     ADMIT_COMMIT if commit else 0, stream))
+        return n, ng
+
+    def admit_gangs_elastic_fetch(self, n_gangs):
+        members = np.zeros(max(n_gangs, 1), np.int64)
+        self._ck(lib().kt_admit_gangs_elastic_fetch(self._h, n_gangs, members.ctypes.data))
+        return members[:n_gangs]
 
     # ---- headroom: how many copies of a pod the throttles still admit
     def headroom_launch(self, n, rows=None, cap=1, on_equal=False, stream=None):

@@ -1115,9 +1115,16 @@ bool KubeThrottler::OnPodUpdate(const Pod& old_pod, const Pod& new_pod, std::str
 // the reservations on every page), committed; the pod-keyed reservation map receives what the engine reserved.  gang_off
 // (nullable; [g0, g1] into the queue, gang_off[g0] == i0, gang_off[g1] == i1): the segment in gangs (kt_paged_admit_gangs) — only
 // members of ADMITTED gangs enter the map, the engine has already taken the others' amounts out again; admitted[g] receives the flag.
+// elastic (nullable, with gang_off): the segment in elastic gangs (kt_paged_admit_gangs_elastic) under min_members [per gang of the
+// queue] and required [per queue position, empty: none]; members[g] receives the count, admitted is not used.
+struct ElasticRule {
+  const std::vector<int64_t>* min_members;
+  const std::vector<uint8_t>* required;
+  std::vector<int64_t>* members;
+};
 static void admit_engine_segment(KubeThrottler::Impl& p, const std::vector<std::string>& pod_keys, const std::vector<int64_t>& rows, size_t i0, size_t i1,
                                  std::vector<Status>* out_p, const std::vector<int64_t>* gang_off, std::vector<uint8_t>* admitted, size_t g0 = 0,
-                                 size_t g1 = 0) {
+                                 size_t g1 = 0, const ElasticRule* elastic = nullptr) {
   std::vector<Status>& out = *out_p;
   const size_t m = i1 - i0;
   if (m == 0) return;
@@ -1129,7 +1136,17 @@ static void admit_engine_segment(KubeThrottler::Impl& p, const std::vector<std::
   std::vector<int64_t> off;      // the segment's gangs, relative to i0
   std::vector<uint8_t> flags;
   int32_t rc;
-  if (gang_off) {
+  std::vector<int64_t> kept;     // elastic: the members that stay, per gang of the segment
+  if (gang_off && elastic) {
+    for (size_t g = g0; g <= g1; ++g) off.push_back((*gang_off)[g] - (int64_t)i0);
+    kept.assign(g1 - g0, 0);
+    const bool any_required = !elastic->required->empty();
+    rc = kt_paged_admit_gangs_elastic(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, (int64_t)(g1 - g0), off.data(),
+                                      elastic->min_members->data() + g0, any_required ? elastic->required->data() + i0 : nullptr,
+                                      /*isThrottledOnEqual=*/0, KT_ADMIT_COMMIT, summary.data(), T > 0 ? status.data() : nullptr, kept.data());
+    flags.resize(kept.size());
+    for (size_t g = 0; g < kept.size(); ++g) flags[g] = kept[g] > 0 ? 1 : 0;
+  } else if (gang_off) {
     for (size_t g = g0; g <= g1; ++g) off.push_back((*gang_off)[g] - (int64_t)i0);
     flags.assign(g1 - g0, 0);
     rc = kt_paged_admit_gangs(p.pages.data(), (int32_t)p.pages.size(), (int64_t)m, rows.data() + i0, (int64_t)(g1 - g0), off.data(),
@@ -1145,7 +1162,8 @@ static void admit_engine_segment(KubeThrottler::Impl& p, const std::vector<std::
   }
   std::vector<uint8_t> keeps(m, 1);  // the pod's reservation stands (always, without gangs)
   for (size_t g = 0; g + 1 < off.size(); ++g) {
-    (*admitted)[g0 + g] = flags[g];
+    if (elastic) (*elastic->members)[g0 + g] = kept[g];
+    else (*admitted)[g0 + g] = flags[g];
     for (int64_t j = off[g]; j < off[g + 1]; ++j) keeps[(size_t)j] = flags[g];
   }
   for (size_t j = 0; j < m; ++j) {
@@ -1657,6 +1675,93 @@ GangAdmission KubeThrottler::AdmitGangs(const std::vector<std::vector<std::strin
     if (!all)
       for (int64_t i = gang_off[g]; i < gang_off[g + 1]; ++i) Unreserve(p.pods.at(pod_keys[(size_t)i]));
     res.admitted[g] = all ? 1 : 0;
+    seg0 = g + 1;
+  }
+  flush(G);
+  return res;
+}
+
+// The same pass over ELASTIC gangs (a job that starts once its quorum of pods fits, PodGroup.minMember / minAvailable, with
+// members that can be made mandatory): ONE engine launch per segment (kt_paged_admit_gangs_elastic), the segments of AdmitGangs.  A gang
+// that goes the plain way: PreFilter per member and Reserve on Success, then Unreserve of all members if the rule fails.
+ElasticGangAdmission KubeThrottler::AdmitElasticGangs(const std::vector<ElasticGang>& gangs) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  ElasticGangAdmission res;
+  std::vector<std::string> pod_keys;
+  std::vector<int64_t> gang_off{0}, min_members;
+  std::vector<uint8_t> required;
+  bool any_required = false;
+  for (auto& g : gangs) {
+    pod_keys.insert(pod_keys.end(), g.members.begin(), g.members.end());
+    gang_off.push_back((int64_t)pod_keys.size());
+    min_members.push_back(g.min_members);
+    any_required |= !g.required.empty();
+  }
+  const size_t n = pod_keys.size(), G = gangs.size();
+  res.status.assign(n, Status{});
+  res.members.assign(G, 0);
+  auto refuse = [&](const std::string& why) {
+    for (auto& st : res.status) st.code = Error, st.reasons = {why};
+    return res;
+  };
+  for (size_t g = 0; g < G; ++g) {
+    const size_t size = gangs[g].members.size();
+    if (size && (gangs[g].min_members < 1 || gangs[g].min_members > (int64_t)size))
+      return refuse("AdmitElasticGangs: gang " + std::to_string(g) + " asks for " + std::to_string(gangs[g].min_members) + " of its " +
+                    std::to_string(size) + " members");
+    if (!gangs[g].required.empty() && gangs[g].required.size() != size)
+      return refuse("AdmitElasticGangs: gang " + std::to_string(g) + " has " + std::to_string(size) + " members and " +
+                    std::to_string(gangs[g].required.size()) + " required flags");
+    if (any_required)
+      for (size_t j = 0; j < size; ++j) required.push_back(!gangs[g].required.empty() && gangs[g].required[j] ? KT_GANG_MEMBER_REQUIRED : 0);
+  }
+  std::vector<int64_t> rows(n);
+  for (size_t i = 0; i < n; ++i) {
+    rows[i] = p.pod_rows.find(pod_keys[i]);
+    if (rows[i] < 0) return refuse("pod " + pod_keys[i] + " is not known to the plugin (OnPodAdd first)");
+  }
+  auto already_reserved = [&](const std::string& key) {
+    for (auto& kv : p.reserved)
+      if (kv.second.count(key)) return true;
+    return false;
+  };
+  const ElasticRule rule{&min_members, &required, &res.members};
+  size_t seg0 = 0;  // first gang of the current engine segment
+  std::set<std::string> in_segment;
+  auto flush = [&](size_t g_end) {
+    if (g_end > seg0)
+      admit_engine_segment(p, pod_keys, rows, (size_t)gang_off[seg0], (size_t)gang_off[g_end], &res.status, &gang_off, nullptr, seg0, g_end, &rule);
+    in_segment.clear();
+  };
+  for (size_t g = 0; g < G; ++g) {
+    if (gangs[g].members.empty()) {  // nothing to place: admitted with no members, and no engine gang (the C-ABI refuses empty ones)
+      flush(g);
+      seg0 = g + 1;
+      continue;
+    }
+    bool plain = false;
+    std::set<std::string> own;
+    for (auto& key : gangs[g].members) plain |= !own.insert(key).second || in_segment.count(key) || already_reserved(key);
+    if (!plain) {
+      in_segment.insert(own.begin(), own.end());
+      continue;
+    }
+    flush(g);
+    int64_t n_in = 0;
+    bool required_out = false;
+    for (int64_t i = gang_off[g]; i < gang_off[g + 1]; ++i) {
+      const Pod pod = p.pods.at(pod_keys[(size_t)i]);
+      Status& st = res.status[(size_t)i];
+      st = PreFilter(pod);
+      if (st.IsSuccess()) st = Reserve(pod);
+      if (st.IsSuccess()) ++n_in;
+      else if (any_required && required[(size_t)i]) required_out = true;
+    }
+    const bool kept = n_in >= gangs[g].min_members && !required_out;
+    if (!kept)
+      for (int64_t i = gang_off[g]; i < gang_off[g + 1]; ++i) Unreserve(p.pods.at(pod_keys[(size_t)i]));
+    res.members[g] = kept ? n_in : 0;
     seg0 = g + 1;
   }
   flush(G);

@@ -150,6 +150,20 @@ struct GangAdmission {
   std::vector<uint8_t> admitted;
 };
 
+// AdmitElasticGangs: a gang that starts once its quorum of members fits (PodGroup.minMember / minAvailable) — the members by
+// Key(), how many of them must succeed (1 .. size), and per member whether it is required (a launcher, a head node)
+struct ElasticGang {
+  std::vector<std::string> members;
+  int64_t min_members = 0;
+  std::vector<uint8_t> required;  // per member, 1: the gang is rolled back when this one fails; empty: none
+};
+// ... what PreFilter / Reserve answered per pod (in the order of the flattened gangs), and per gang the members that stay reserved
+// (0: rolled back, every member un-reserved).  A member is in iff its gang's count is above 0 and its own status is Success
+struct ElasticGangAdmission {
+  std::vector<Status> status;
+  std::vector<int64_t> members;
+};
+
 // Headroom: how many further pods of a pod's shape the throttles still admit, and the throttle that stops the next one
 struct HeadroomResult {
   int64_t copies = 0;     // in [0, cap]
@@ -268,6 +282,12 @@ class KubeThrottler {
   // that did not succeed gets Unreserve for every member before the next gang — one engine launch per segment
   // (kt_paged_admit_gangs).  Only members of admitted gangs are in the reservation map afterwards (Unreserve works pod by pod)
   GangAdmission AdmitGangs(const std::vector<std::vector<std::string>>& gangs);
+  // the same pass over ELASTIC gangs: a gang stays once at least min_members members succeeded and every required one did — the
+  // members that succeeded keep their reservation, the others never reserved; otherwise every member gets Unreserve.  One engine
+  // launch per segment (kt_paged_admit_gangs_elastic), the segments of AdmitGangs.  Only members that stay are in the reservation
+  // map afterwards.  An empty gang is admitted with 0 members; min_members outside [1, size] or a `required` of the wrong length
+  // is an Error on every status
+  ElasticGangAdmission AdmitElasticGangs(const std::vector<ElasticGang>& gangs);
 
   // ---- how many replicas fit: the number of pods of pod_key's shape (same namespace, labels and requests) that PreFilter +
   // Reserve would admit one after the other right now, at most cap (1 .. KT_HEADROOM_MAX_CAP), and the throttle that stops the

@@ -1790,6 +1790,18 @@ class PagedEngine:
         assert (verdicts(status)[ok] == v[ok]).all(), "kt_paged_admit_gangs: summary words disagree with the combined status rows"
         return status, v, admitted
 
+    def admit_gangs_elastic(self, rows, gang_off, min_members, required=None, on_equal=False, commit=False):
+        """The queue ``rows`` in consecutive gangs through kt_paged_admit_gangs_elastic: gang g is kept once at least
+        ``min_members[g]`` members succeeded and every ``required`` one did, else rolled back on every page before the next one
+        starts -> (status matrix [n][throttles] at each pod's turn, verdict per pod, members that stay reserved per gang: 0 rolled
+        back), combined over the pages."""
+        status, summary, members = E.paged_admit_gangs_elastic(self.engines, rows, gang_off, min_members, required, on_equal=on_equal,
+                                                               commit=commit)
+        v = np.where(summary == 2, S.VERDICT_ERROR, np.where((summary & 1) != 0, S.VERDICT_BLOCK, S.VERDICT_ALLOW)).astype(np.uint8)
+        ok = v != S.VERDICT_ERROR  # (an error row keeps page 0's precomputed status row; its summary word says error)
+        assert (verdicts(status)[ok] == v[ok]).all(), "kt_paged_admit_gangs_elastic: summary words disagree with the combined status rows"
+        return status, v, members
+
     def headroom(self, rows, cap, on_equal=False):
         """How many copies of each pod of ``rows`` the throttles still admit, through kt_paged_headroom: the leading Success
         verdicts of a dry-run admission of ``[pod] * cap`` with every page's names -> (copies [n], limiting throttle row [n],
