@@ -720,6 +720,66 @@ int32_t kt_forecast_gangs_launch(kt_engine* e, int64_t n, const int64_t* pod_row
 int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first /* [n_gangs], nullable */,
                                 uint8_t* out_verdicts /* [n_gangs][n_inst], nullable */,
                                 int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
+/* ---- forecast, for elastic gangs: the first instant at which a gang's QUORUM fits — what kt_admit_gangs_elastic_launch is to
+ *      kt_admit_gangs_launch, asked over instants: the backoff of a job admitted with minMember that does not start today.
+ *      kt_forecast_gangs_launch can only say when the WHOLE gang fits; for an elastic job that is too late, or never.
+ *      Notation as for kt_forecast_gangs_launch: the instants t_0 < .. < t_{m-1}, state R_t, "a throttle whose reconcile is an error,
+ *      or that is not valid and responsible, keeps its stored status in every R_t", both override ends inclusive, gang g = the queue
+ *      positions [gang_off[g], gang_off[g + 1]) of pod_rows.  min_members [n_gangs] and member_flags [n] (nullable: no member is
+ *      required; bit 0 = KT_GANG_MEMBER_REQUIRED) as in kt_admit_gangs_elastic_launch.  Gangs are judged independently of each
+ *      other, each against the stored reserved amounts; a pod may be a member of several gangs.  The call is a dry run.
+ *      The walk, per gang g and instant t_k:
+ *      (1)  the members are walked in order in R_{t_k}, exactly as rule (1) of kt_admit_gangs_elastic_launch walks them: each is
+ *           judged against the stored status of R_{t_k} plus what the earlier members of g that SUCCEEDED reserved;
+ *      (2)  Reserve is kt_admit's: the value of every name carried, the presence of all names carried (zero-valued ones included),
+ *           count + 1, and the count becomes present;
+ *      (3)  a member that does not succeed reserves on NO throttle — not on the one that stopped it, and not on the others that
+ *           affect it either; every member is evaluated, also behind one that failed;
+ *      (4)  a member whose PreFilter is an Error (summary word 2), or whose row is invalid, does not succeed at any instant; a
+ *           member no throttle affects succeeds and reserves nowhere;
+ *      (5)  the forecast has no list capacity: the clause "affected by more throttles than the kernel's list holds" of the
+ *           admission's rule (2) does not apply, a member affected by any number of throttles is judged on all of them.
+ *      The outputs (all nullable, [n_gangs][n_inst] but out_first):
+ *      (6)  out_members[g][k] is the number of members that succeed at t_k — reported whether or not the gang is admitted, so a
+ *           caller sees how far from its quorum the gang is;
+ *      (7)  out_verdicts[g][k] is KT_VERDICT_ERROR at every k iff the rule can be met at no instant because of members that never
+ *           succeed: a required member is an Error or invalid member, or (size of g - such members) < min_members[g].  Otherwise
+ *           it is KT_VERDICT_SUCCESS iff out_members[g][k] >= min_members[g] and every required member succeeded at t_k, and
+ *           KT_VERDICT_UNSCHEDULABLE otherwise;
+ *      (8)  out_first[g] ([n_gangs]) is the smallest k whose verdict is KT_VERDICT_SUCCESS, or KT_FORECAST_NONE;
+ *      (9)  out_blocker[g][k] is -1 where the verdict is Success; otherwise the queue position of the first REQUIRED member that did
+ *           not succeed at t_k, or, if there is none, of the first member that did not succeed.
+ *      Identities:
+ *      (E1) with min_members[g] == size of g for every gang and member_flags == NULL, out_first, out_verdicts and out_blocker are
+ *           kt_forecast_gangs_launch's byte for byte, and out_members[g][k] equals the size of g exactly where the verdict is
+ *           Success; the same holds with every member flagged required at any min_members;
+ *      (E2) a gang of one pod with min_members = 1 reports kt_forecast_launch's first and verdict bytes for that pod;
+ *      (E3) with inst = [t]: on an engine whose stored status IS R_t, a dry kt_admit_gangs_elastic_launch of the one gang g returns
+ *           out_members > 0 exactly where this call's verdict is Success, and then the same number (for members within that
+ *           kernel's list capacity).
+ *      Refused before anything is launched, in this order: what kt_forecast_gangs_launch refuses about the instants (n_inst < 1,
+ *      an inst_ns outside [0, 10^9), instants that are not strictly ascending, a missing array); every gang_off defect; the
+ *      min_members / member_flags refusals of clause (10) of kt_admit_gangs_elastic_launch, with the same codes and messages; then
+ *      the rest of kt_forecast_gangs_launch's list in its order — a pod named twice within ONE gang, a pod row outside the capacity,
+ *      n x throttle_rows or n_gangs x n_inst > 2^31, `used` wider than int64, a KT_VARIANT_INCREMENTAL engine, an exchange world
+ *      above 1.  A refused call leaves the check slot, the reconcile report and every result buffer alone.  n == 0 is allowed only
+ *      with n_gangs == 0: KT_OK, nothing is launched.
+ *      Slots: those of kt_forecast_gangs_launch.  The result SHARES the one pending forecast result as a kind of its own: every
+ *      other forecast fetch answers KT_ERR_NOT_READY behind this launch, and kt_forecast_gangs_elastic_fetch answers the same
+ *      behind theirs.  min_members and member_flags travel on the launch's stream; the caller's arrays are not referenced after
+ *      return.  kt_forecast_gangs_elastic_fetch synchronises.
+ *      One kt_check launch with the status matrix over pod_rows, the aggregate and dry finalize (at t_0) of kt_forecast_launch, one
+ *      launch of kt_forecast_gangs_elastic (csrc/kt_kernels_forecast_gangs_elastic.hip) — one wave per (gang, instant) pair, the
+ *      judge member-major: the union of the members' throttles as a compact state in LDS (or, beyond its capacity, in a workspace
+ *      in device memory), the members in order against it — and one small launch behind it for out_first.
+ *      Out of scope: more than KT_MAX_DIMS resource names, several ranks. ------------------------------------------------------ */
+int32_t kt_forecast_gangs_elastic_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                         const int64_t* min_members /* [n_gangs] */, const uint8_t* member_flags /* [n], nullable */,
+                                         int64_t n_inst, const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, void* stream);
+int32_t kt_forecast_gangs_elastic_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first /* [n_gangs], nullable */,
+                                        uint8_t* out_verdicts /* [n_gangs][n_inst], nullable */,
+                                        int64_t* out_members /* [n_gangs][n_inst], nullable */,
+                                        int64_t* out_blocker /* [n_gangs][n_inst], nullable */);
 /* ---- headroom forecast: how many copies of a pod the throttles admit at each instant — kt_headroom_launch ("how many, now") and
  *      kt_forecast_launch ("whether, when") asked at once: how many replicas fit once the night override begins, and at which
  *      instant `want` replicas fit.

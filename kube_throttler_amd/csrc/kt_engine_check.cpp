@@ -447,9 +447,9 @@ static int32_t gangs_fetch_locked(kt_engine* e, int64_t n_gangs, uint8_t* out, i
   return KT_OK;
 }
 
-// what kt_admit_gangs_elastic_launch refuses behind gangs_valid: a missing quorum array, a quorum outside [1, size of the gang], a
-// flag byte with a bit other than KT_GANG_MEMBER_REQUIRED
-static int32_t elastic_valid(kt_engine* e, int64_t n, int64_t n_gangs, const int64_t* gang_off, const int64_t* min_members, const uint8_t* member_flags) {
+// what the elastic gang calls refuse behind gangs_valid: a missing quorum array, a quorum outside [1, size of the gang], a flag byte
+// with a bit other than KT_GANG_MEMBER_REQUIRED (the wording names the admission, as gangs_valid's does, for every caller)
+int32_t elastic_valid(kt_engine* e, int64_t n, int64_t n_gangs, const int64_t* gang_off, const int64_t* min_members, const uint8_t* member_flags) {
   if (n_gangs > 0 && !min_members) return e->fail(KT_ERR_INVALID_ARGUMENT, "admit elastic gangs: min_members is NULL");
   for (int64_t g = 0; g < n_gangs; ++g) {
     const int64_t size = gang_off[g + 1] - gang_off[g];

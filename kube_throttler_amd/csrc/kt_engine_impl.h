@@ -218,15 +218,18 @@ extern thread_local std::string g_create_error;  // text of the last kt_engine_c
 // getenv on every pod event and launch (getenv is not safe beside a setenv of another thread, and the pod event
 // path is tuned to a few microseconds).  Read at the same two moments, with a VALUE instead of a flag and therefore not in the
 // table: KT_REPRIEVE_LDS_CAP (kt_engine::reprieve_lds_cap_limit, a test hook of kt_preempt_reprieve_launch and
-// kt_preempt_gangs_reprieve_launch).
+// kt_preempt_gangs_reprieve_launch) and KT_FORECAST_ELASTIC_LDS_CAP (kt_engine::forecast_elastic_lds_cap_limit, the same hook for
+// kt_forecast_gangs_elastic_launch).
 enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSw_NO_MATCH_CACHE_AGG, kSw_NO_MATCH_CODES, kSw_NO_MATCH_CODES_AGG, kSw_NO_TILE_PAIRS_CHECK, kSwCount };
 static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE", "KT_NO_MATCH_CACHE_AGG", "KT_NO_MATCH_CODES", "KT_NO_MATCH_CODES_AGG", "KT_NO_TILE_PAIRS_CHECK"};
 // which launch the one pending forecast result belongs to: only that launch's fetch may read it
-enum ForecastKind { kForecastPods, kForecastGangs, kForecastHeadroom, kForecastHeadroomGangs };
+enum ForecastKind { kForecastPods, kForecastGangs, kForecastHeadroom, kForecastHeadroomGangs, kForecastGangsElastic };
 struct kt_engine {
   bool sw[kSwCount] = {};  // EnvSwitch values (load_env_switches)
   uint32_t reprieve_lds_cap_limit = 0;  // KT_REPRIEVE_LDS_CAP (test hook, read with the switches): at most so many list entries of
                                         // kt_preempt_reprieve stay in LDS, a longer list takes the HBM workspace; 0 = no limit
+  uint32_t forecast_elastic_lds_cap_limit = 0;  // KT_FORECAST_ELASTIC_LDS_CAP (test hook, read with the switches): at most so many union
+                                                // entries of kt_forecast_gangs_elastic stay in LDS; 0 = no limit
   kt_config cfg{};
   // writers (state feed, launches, fetches) hold it exclusively for the duration of the call; the single-pod PreFilter
   // path (kt_check with n <= 8, summaries only) holds it SHARED: it reads device tables nobody may rewrite meanwhile,
@@ -421,6 +424,12 @@ struct kt_engine {
   // offsets in d_forecast_gang_off
   DevBuf<int64_t> d_forecast_copies;
   DevBuf<int32_t> d_forecast_limiting;
+  // kt_forecast_gangs_elastic_launch is the fifth kind (first per GANG, verdict bytes, blocker and offsets in the gang forecast's
+  // buffers): the members that succeed [n_gangs][n_inst], the quorum per gang and the flag byte per member as the kernel reads them,
+  // and the state of a union that outgrows LDS (kt::forecast_gangs_elastic_ws_bytes)
+  DevBuf<int64_t> d_forecast_members, d_forecast_min;
+  DevBuf<uint8_t> d_forecast_flags;
+  DevBuf<unsigned char> d_forecast_elastic_ws;
   DevBuf<uint8_t> d_slab;  // per-workgroup LDS table spill area of kt_aggregate_bitmap
   unsigned long long* ext_partial = nullptr;  // caller-owned partial buffer (kt_use_partial_buffer)
   int64_t ext_partial_words = 0;
@@ -689,6 +698,11 @@ KT_INTERNAL int32_t match_cache_for_scan(kt_engine* e, hipStream_t s, kt::MatchC
 KT_INTERNAL int32_t check_launch_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int32_t on_equal, uint32_t flags, hipStream_t s,
                                         bool allow_small = true);
 KT_INTERNAL int32_t gangs_valid(kt_engine* e, int64_t n, int64_t n_gangs, const int64_t* gang_off);
+// the rule of an elastic gang call, behind gangs_valid (kt_admit_gangs_elastic_launch, kt_paged_admit_gangs_elastic,
+// kt_forecast_gangs_elastic_launch): a missing quorum array, a quorum outside [1, size of the gang], a flag byte with a bit other than
+// KT_GANG_MEMBER_REQUIRED
+KT_INTERNAL int32_t elastic_valid(kt_engine* e, int64_t n, int64_t n_gangs, const int64_t* gang_off, const int64_t* min_members,
+                                  const uint8_t* member_flags);
 typedef std::vector<std::unique_ptr<LaunchLock>> PageLocks;
 KT_INTERNAL int32_t paged_lock(const char* what, kt_engine* const* pages, int32_t n_pages, int64_t n, PageLocks& locks);
 KT_INTERNAL int32_t paged_same_cluster(const char* what, kt_engine* const* pages, int32_t n_pages, int64_t n, const int64_t* pod_rows);

@@ -850,19 +850,30 @@ int32_t kt_headroom_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, 
 // The refusals of forecast_locked in its order (the instants first, then the gang defects and "a pod twice" asked per gang), then
 // the same launches with kt_forecast_gangs in kt_forecast's place.  The result shares the one pending forecast result;
 // forecast_kind tells the fetches apart.  The caller holds the launch lock.
+// `rule` (kt_forecast_gangs_elastic_launch): the quorum per gang and the flag byte per member.  Its refusals come behind the gang
+// defects (they read the sizes) and before the rest; the arrays travel on the launch's stream beside the offsets; the kernel is
+// kt_forecast_gangs_elastic with the small launch for `first` behind it, and the result is the kind of its own.
+struct ElasticRule {
+  const int64_t* min_members;   // [n_gangs]
+  const uint8_t* member_flags;  // [n], nullable
+};
 static int32_t forecast_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_inst,
-                                     const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, void* stream) {
-  const char *what = "forecast gangs", *kernel = "kt_forecast_gangs";
+                                     const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, void* stream,
+                                     const ElasticRule* rule = nullptr) {
+  const char* what = rule ? "forecast elastic gangs" : "forecast gangs";
+  const char* kernel = rule ? "kt_forecast_gangs_elastic" : "kt_forecast_gangs";
+  const ForecastKind kind = rule ? kForecastGangsElastic : kForecastGangs;
   const int32_t T = e->thr_rows_hi;  // (moved by throttle batches only, under this lock: ensure_ready below does not change it)
   int32_t rc;
   if ((rc = forecast_instants_valid(e, n > 0 && !pod_rows, n_inst, inst_s, inst_ns)) != KT_OK) return rc;
   if ((rc = gangs_valid(e, n, n_gangs, gang_off)) != KT_OK) return rc;
+  if (rule && (rc = elastic_valid(e, n, n_gangs, gang_off, rule->min_members, rule->member_flags)) != KT_OK) return rc;
   if ((rc = no_row_twice_in_a_gang(e, what, pod_rows, n_gangs, gang_off)) != KT_OK) return rc;
   if ((rc = rows_in_range(e, what, n, pod_rows)) != KT_OK) return rc;
   if ((rc = matrix_fits(e, what, T, n)) != KT_OK || (rc = verdicts_fit(e, what, n_gangs, n_inst, "n_gangs")) != KT_OK) return rc;
   if ((rc = serves_dry_reconcile(e, what, -1, kernel)) != KT_OK) return rc;
   if (n == 0) {  // (no gangs) nothing is launched
-    e->forecast_ready = true, e->forecast_kind = kForecastGangs, e->forecast_n = 0, e->forecast_m = n_inst;
+    e->forecast_ready = true, e->forecast_kind = kind, e->forecast_n = 0, e->forecast_m = n_inst;
     return KT_OK;
   }
   KT_HIP(e, hipSetDevice(e->device));
@@ -870,23 +881,35 @@ static int32_t forecast_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod
   if ((rc = ensure_ready(e, s)) != KT_OK || (rc = sums_fit_int64(e, what, -1, kernel, s)) != KT_OK) return rc;
   e->forecast_ready = false;
   const size_t ng = (size_t)n_gangs, m = (size_t)n_inst, ver = ng * m;
-  if ((rc = reserve_behind_last_stream(e, {{e->d_forecast_first, ng}, {e->d_forecast_verdicts, ver + 1}, {e->d_forecast_blocker, ver}, {e->d_forecast_inst_s, m}, {e->d_forecast_inst_ns, m}, {e->d_forecast_gang_off, ng + 1}})) != KT_OK)
+  const bool flagged = rule && rule->member_flags;
+  const size_t ws = rule ? kt::forecast_gangs_elastic_ws_bytes(T, e->D, n_gangs, n_inst, e->forecast_elastic_lds_cap_limit) : 0;
+  if ((rc = reserve_behind_last_stream(e, {{e->d_forecast_first, ng}, {e->d_forecast_verdicts, ver + 1}, {e->d_forecast_blocker, ver}, {e->d_forecast_inst_s, m}, {e->d_forecast_inst_ns, m}, {e->d_forecast_gang_off, ng + 1},
+                                           {e->d_forecast_members, rule ? ver : 0}, {e->d_forecast_min, rule ? ng : 0}, {e->d_forecast_flags, flagged ? (size_t)n : 0}, {e->d_forecast_elastic_ws, ws}})) != KT_OK)
     return rc;
   // the instants and the offsets travel on the launch's stream, behind an earlier forecast's kernel; the caller's memory is not
   // referenced after return
   KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_s.p, inst_s, m * 8, hipMemcpyHostToDevice, s));
   KT_HIP(e, hipMemcpyAsync(e->d_forecast_inst_ns.p, inst_ns, m * 4, hipMemcpyHostToDevice, s));
   KT_HIP(e, hipMemcpyAsync(e->d_forecast_gang_off.p, gang_off, (ng + 1) * 8, hipMemcpyHostToDevice, s));
+  if (rule) KT_HIP(e, hipMemcpyAsync(e->d_forecast_min.p, rule->min_members, ng * 8, hipMemcpyHostToDevice, s));
+  if (flagged) KT_HIP(e, hipMemcpyAsync(e->d_forecast_flags.p, rule->member_flags, (size_t)n, hipMemcpyHostToDevice, s));
   KT_HIP(e, hipStreamSynchronize(s));
   if ((rc = query_check(e, n, pod_rows, on_equal, s, &kt_engine::preempt_ready)) != KT_OK) return rc;  // over the members of all gangs
   // the aggregate with exact contributor counts and the error bytes; the dry finalize runs at t_0
   if ((rc = preempt_reconcile_locked(e, inst_s[0], inst_ns[0], s)) != KT_OK) return rc;
-  kt::launch_forecast_gangs(admit_page_of(e), n_gangs, n_inst, e->d_rows.p, e->d_forecast_gang_off.p, e->d_forecast_inst_s.p, e->d_forecast_inst_ns.p, T,
-                            on_equal != 0, e->d_status.p, e->d_summary.p, e->d_preempt_partial.p, e->d_out_error.p, e->d_forecast_first.p,
-                            e->d_forecast_verdicts.p, e->d_forecast_blocker.p, s);
+  if (rule)
+    kt::launch_forecast_gangs_elastic(admit_page_of(e), n_gangs, n_inst, e->d_rows.p, e->d_forecast_gang_off.p, e->d_forecast_min.p,
+                                      flagged ? e->d_forecast_flags.p : nullptr, e->d_forecast_inst_s.p, e->d_forecast_inst_ns.p, T, on_equal != 0,
+                                      e->d_status.p, e->d_summary.p, e->d_preempt_partial.p, e->d_out_error.p, e->d_forecast_first.p,
+                                      e->d_forecast_verdicts.p, e->d_forecast_members.p, e->d_forecast_blocker.p,
+                                      ws != 0 ? e->d_forecast_elastic_ws.p : nullptr, e->forecast_elastic_lds_cap_limit, s);
+  else
+    kt::launch_forecast_gangs(admit_page_of(e), n_gangs, n_inst, e->d_rows.p, e->d_forecast_gang_off.p, e->d_forecast_inst_s.p, e->d_forecast_inst_ns.p, T,
+                              on_equal != 0, e->d_status.p, e->d_summary.p, e->d_preempt_partial.p, e->d_out_error.p, e->d_forecast_first.p,
+                              e->d_forecast_verdicts.p, e->d_forecast_blocker.p, s);
   KT_HIP(e, hipGetLastError());
   e->last_stream = s;
-  e->forecast_ready = true, e->forecast_kind = kForecastGangs, e->forecast_n = n_gangs, e->forecast_m = n_inst;
+  e->forecast_ready = true, e->forecast_kind = kind, e->forecast_n = n_gangs, e->forecast_m = n_inst;
   return KT_OK;
 }
 
@@ -906,6 +929,31 @@ int32_t kt_forecast_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_firs
   if (n_gangs == 0) return KT_OK;
   const size_t ng = (size_t)n_gangs, ver = ng * (size_t)e->forecast_m;
   return fetch_out(e, {{out_first, e->d_forecast_first.p, ng * 8}, {out_verdicts, e->d_forecast_verdicts.p, ver}, {out_blocker, e->d_forecast_blocker.p, ver * 8}});
+}
+
+// ---------------------------------------------------------------------------------------------------
+// forecast, for elastic gangs: the first instant at which a gang's quorum fits (kt_kernels_forecast_gangs_elastic.hip)
+// ---------------------------------------------------------------------------------------------------
+int32_t kt_forecast_gangs_elastic_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                         const int64_t* min_members, const uint8_t* member_flags, int64_t n_inst, const int64_t* inst_s,
+                                         const int32_t* inst_ns, int32_t on_equal, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  const ElasticRule rule{min_members, member_flags};
+  return forecast_gangs_locked(e, n, pod_rows, n_gangs, gang_off, n_inst, inst_s, inst_ns, on_equal, stream, &rule);
+}
+
+int32_t kt_forecast_gangs_elastic_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_first, uint8_t* out_verdicts, int64_t* out_members,
+                                        int64_t* out_blocker) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (int32_t bad = fetch_ready(e, e->forecast_ready && e->forecast_kind == kForecastGangsElastic, "forecast_gangs_elastic", "forecast elastic gangs", true,
+                                n_gangs, e->forecast_n))
+    return bad;
+  if (n_gangs == 0) return KT_OK;
+  const size_t ng = (size_t)n_gangs, ver = ng * (size_t)e->forecast_m;
+  return fetch_out(e, {{out_first, e->d_forecast_first.p, ng * 8}, {out_verdicts, e->d_forecast_verdicts.p, ver}, {out_members, e->d_forecast_members.p, ver * 8}, {out_blocker, e->d_forecast_blocker.p, ver * 8}});
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -221,6 +221,19 @@ void launch_forecast_gangs(const AdmitPage& pg, int64_t n_gangs, int64_t m, cons
                            const int64_t* inst_s, const int32_t* inst_ns, int T, bool on_equal, const uint8_t* status, const uint64_t* summary,
                            const unsigned long long* partial, const uint8_t* error, int64_t* first, uint8_t* verdicts, int64_t* blocker,
                            hipStream_t s);
+// the first instant at which a gang's QUORUM fits (kt_kernels_forecast_gangs_elastic.hip): one wave per (gang, instant) pair, the
+// members walked in order, a failed member reserving nowhere.  launch_forecast_gangs' inputs plus min_dev [n_gangs] and flags_dev [n]
+// (nullable: no member is required; bit 0 = required); first [n_gangs] (by a small launch behind the kernel, on the same stream),
+// verdicts, members and blocker [n_gangs][m] out.  A pair's union of affecting throttles lives in LDS up to
+// forecast_gangs_elastic_lds_cap(D, limit) entries (limit: a test hook that lowers the capacity, 0 = none), beyond that in `ws`:
+// forecast_gangs_elastic_ws_bytes bytes of device memory (0: no union can outgrow LDS, ws may be null)
+uint32_t forecast_gangs_elastic_lds_cap(int D, uint32_t limit);
+size_t forecast_gangs_elastic_ws_bytes(int T, int D, int64_t n_gangs, int64_t m, uint32_t lds_cap_limit);
+void launch_forecast_gangs_elastic(const AdmitPage& pg, int64_t n_gangs, int64_t m, const int64_t* rows_dev, const int64_t* gang_off_dev,
+                                   const int64_t* min_dev, const uint8_t* flags_dev, const int64_t* inst_s, const int32_t* inst_ns, int T,
+                                   bool on_equal, const uint8_t* status, const uint64_t* summary, const unsigned long long* partial,
+                                   const uint8_t* error, int64_t* first, uint8_t* verdicts, int64_t* members, int64_t* blocker, void* ws,
+                                   uint32_t lds_cap_limit, hipStream_t s);
 // how many copies of a whole gang the throttles admit at each instant (kt_kernels_headroom_forecast_gangs.hip): one wave per gang,
 // lane = instant position, every lane searches the copies of its own instant.  launch_forecast_gangs' inputs plus cap and want
 // (1 <= want <= cap <= 2^31 - 1); first [n_gangs], copies [n_gangs][m], limiting [n_gangs][m] and blocker [n_gangs][m] out

@@ -45,6 +45,7 @@ EXPORTS = [
     "kt_admit_gangs_elastic_launch", "kt_admit_gangs_elastic_fetch", "kt_paged_admit_gangs_elastic",
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
+    "kt_forecast_gangs_elastic_launch", "kt_forecast_gangs_elastic_fetch",
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
     "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch", "kt_paged_headroom_gangs",
     "kt_headroom_forecast_launch", "kt_headroom_forecast_fetch", "kt_paged_headroom_forecast",
@@ -528,6 +529,9 @@ def lib():
         L.kt_forecast_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                C.c_int32, C.c_void_p]
         L.kt_forecast_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kt_forecast_gangs_elastic_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.kt_forecast_gangs_elastic_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_headroom_forecast_gangs_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                         C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]
         L.kt_headroom_forecast_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1103,6 +1107,45 @@ class Engine:
         A dry run: stored status and reserved amounts stay as they are."""
         self.forecast_gangs_launch(pod_rows, gang_off, instants, on_equal)
         return self.forecast_gangs_fetch(len(_gang_offsets(gang_off)) - 1, len(instants), want_verdicts, want_blocker)
+
+    # ---- forecast, for elastic gangs: the first instant at which a gang's quorum fits
+    def forecast_gangs_elastic_launch(self, pod_rows, gang_off, min_members, instants, required=None, on_equal=False, stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        g = _gang_offsets(gang_off)
+        n, ng = len(a), len(g) - 1
+        mm, rq = _elastic_rule(min_members, required, n, ng)
+        inst_s = np.ascontiguousarray([int(t[0]) for t in instants], dtype=np.int64)
+        inst_ns = np.ascontiguousarray([int(t[1]) for t in instants], dtype=np.int32)
+        m = len(inst_s)
+        self._ck(lib().kt_forecast_gangs_elastic_launch(self._h, n, p if n else None, ng, g.ctypes.data, mm.ctypes.data if ng else None,
+                                                        None if rq is None or not n else rq.ctypes.data, m,
+                                                        inst_s.ctypes.data if m else None, inst_ns.ctypes.data if m else None,
+                                                        int(on_equal), stream))
+
+    def forecast_gangs_elastic_fetch(self, n_gangs, n_inst, want_verdicts=True, want_members=True, want_blocker=True):
+        cells = max(n_gangs * n_inst, 1)
+        first = np.zeros(max(n_gangs, 1), np.int64)
+        flat = np.zeros(cells, np.uint8) if want_verdicts else None
+        mem = np.zeros(cells, np.int64) if want_members else None
+        blk = np.zeros(cells, np.int64) if want_blocker else None
+        self._ck(lib().kt_forecast_gangs_elastic_fetch(self._h, n_gangs, first.ctypes.data, None if flat is None else flat.ctypes.data,
+                                                       None if mem is None else mem.ctypes.data, None if blk is None else blk.ctypes.data))
+        shaped = lambda x: None if x is None else x[:n_gangs * n_inst].reshape(n_gangs, n_inst)
+        return first[:n_gangs], shaped(flat), shaped(mem), shaped(blk)
+
+    def forecast_gangs_elastic(self, pod_rows, gang_off, min_members, instants, required=None, on_equal=False, want_verdicts=True,
+                               want_members=True, want_blocker=True):
+        """kt_forecast_gangs_elastic_launch + kt_forecast_gangs_elastic_fetch: per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]``
+        and per instant an in-order walk of its members once every valid and responsible throttle has been reconciled at that
+        instant — a member that succeeds reserves against the throttles the later ones meet, one that fails reserves nowhere —
+        and the elastic rule on it: Success iff at least ``min_members[g]`` members succeed and every ``required`` one does (bool,
+        or flag bytes with GANG_MEMBER_REQUIRED, per queue position; None: none); Error at every instant where members that never
+        succeed put the rule out of reach -> (first int64 [n_gangs]: the first position whose verdict is Success, FORECAST_NONE:
+        none; verdicts uint8 [n_gangs][n_inst]; members int64 [n_gangs][n_inst]: how many succeed, admitted or not; blocker int64
+        [n_gangs][n_inst]: the first required member that does not succeed, else the first member that does not, -1 where the
+        verdict is Success) — each of the last three None where not wanted.  A dry run."""
+        self.forecast_gangs_elastic_launch(pod_rows, gang_off, min_members, instants, required, on_equal)
+        return self.forecast_gangs_elastic_fetch(len(_gang_offsets(gang_off)) - 1, len(instants), want_verdicts, want_members, want_blocker)
 
     # ---- headroom forecast: how many copies of a pod the throttles admit at each instant
     def headroom_forecast_launch(self, pod_rows, instants, cap, want=1, on_equal=False, stream=None):

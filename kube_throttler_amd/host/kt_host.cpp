@@ -1405,7 +1405,7 @@ static void retry_after_first(RetryAfterResult& out, int64_t first, const std::v
   out.instant = buf;
 }
 
-// What RetryAfter and RetryAfterGang (`who`) share in front of their launch: a mirror on pages refuses, `now` and the horizon are
+// What RetryAfter, RetryAfterGang and their siblings (`who`) share in front of their launch: a mirror on pages refuses, `now` and the horizon are
 // checked, then inst = now ++ the override boundaries in (now, now + horizon] (kt_override_instants, twice: count, then fill).
 // false: *error says why (an engine error included)
 template <class IMPL>
@@ -1547,6 +1547,71 @@ GangRetryAfterResult KubeThrottler::RetryAfterGang(const std::vector<std::string
     out.instants.emplace_back(inst_s[(size_t)k], inst_ns[(size_t)k]);
     const int64_t b = blockers[(size_t)k];
     res.blockers_at.push_back(b >= 0 && (size_t)b < member_keys.size() ? member_keys[(size_t)b] : std::string());
+  }
+  retry_after_first(out, first, inst_s, inst_ns);
+  return res;
+}
+
+// When does this gang's quorum fit: RetryAfterGang with ElasticGang's rule — RetryAfter's instants, one
+// kt_forecast_gangs_elastic_launch + kt_forecast_gangs_elastic_fetch with the members as ONE gang on the mirror's one engine
+// (isThrottledOnEqual = false, as PreFilter).  Nothing is changed.
+ElasticGangRetryAfterResult KubeThrottler::RetryAfterElasticGang(const std::vector<std::string>& member_keys, int64_t min_members,
+                                                                 const std::vector<uint8_t>& required, const std::string& now_rfc3339,
+                                                                 int64_t horizon_seconds) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  ElasticGangRetryAfterResult res;
+  RetryAfterResult& out = res.retry;
+  std::vector<int64_t> inst_s;
+  std::vector<int32_t> inst_ns;
+  if (!retry_after_instants(p, "RetryAfterElasticGang", "elastic gang forecast", now_rfc3339, horizon_seconds, &inst_s, &inst_ns, &out.error))
+    return res;
+  const size_t size = member_keys.size();
+  if (size == 0) {
+    out.error = "RetryAfterElasticGang: a gang without members";
+    return res;
+  }
+  if (min_members < 1 || min_members > (int64_t)size) {  // (worded as AdmitElasticGangs words it)
+    out.error = "RetryAfterElasticGang: gang 0 asks for " + std::to_string(min_members) + " of its " + std::to_string(size) + " members";
+    return res;
+  }
+  if (!required.empty() && required.size() != size) {
+    out.error = "RetryAfterElasticGang: gang 0 has " + std::to_string(size) + " members and " + std::to_string(required.size()) + " required flags";
+    return res;
+  }
+  std::vector<int64_t> rows(size);
+  std::set<std::string> seen;
+  for (size_t i = 0; i < size; ++i) {
+    if ((rows[i] = p.pod_rows.find(member_keys[i])) < 0) {
+      out.error = "pod " + member_keys[i] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+    if (!seen.insert(member_keys[i]).second) {  // (it would reserve twice: the engine refuses it too)
+      out.error = "RetryAfterElasticGang: pod " + member_keys[i] + " is a member twice";
+      return res;
+    }
+  }
+  std::vector<uint8_t> flags;
+  for (size_t i = 0; i < required.size(); ++i) flags.push_back(required[i] ? KT_GANG_MEMBER_REQUIRED : 0);
+  const int64_t m = (int64_t)inst_s.size();
+  const int64_t gang_off[2] = {0, (int64_t)size};
+  int64_t first = KT_FORECAST_NONE;
+  std::vector<int64_t> blockers((size_t)m, -1);
+  out.verdicts_at.assign((size_t)m, 0);
+  res.members_at.assign((size_t)m, 0);
+  int32_t rc = kt_forecast_gangs_elastic_launch(p.e, (int64_t)size, rows.data(), 1, gang_off, &min_members, flags.empty() ? nullptr : flags.data(), m,
+                                                inst_s.data(), inst_ns.data(), /*isThrottledOnEqual=*/0, nullptr);
+  if (rc == KT_OK) rc = kt_forecast_gangs_elastic_fetch(p.e, 1, &first, out.verdicts_at.data(), res.members_at.data(), blockers.data());
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    out.verdicts_at.clear();
+    res.members_at.clear();
+    return res;
+  }
+  for (int64_t k = 0; k < m; ++k) {
+    out.instants.emplace_back(inst_s[(size_t)k], inst_ns[(size_t)k]);
+    const int64_t b = blockers[(size_t)k];
+    res.blockers_at.push_back(b >= 0 && (size_t)b < size ? member_keys[(size_t)b] : std::string());
   }
   retry_after_first(out, first, inst_s, inst_ns);
   return res;

@@ -211,6 +211,16 @@ struct GangRetryAfterResult {
   std::vector<std::string> blockers_at;  // per judged instant the Pod::Key() of the first member that is not admitted; empty: the gang passes
 };
 
+// RetryAfterElasticGang: the first instant at which a gang's QUORUM fits (ElasticGang's rule), who stops it and how many members
+// succeed at each judged instant
+struct ElasticGangRetryAfterResult {
+  RetryAfterResult retry;                // has / instant / instants / verdicts_at / error as for RetryAfter, for the gang under its rule;
+                                         // KT_VERDICT_ERROR at every instant: members that never succeed put the rule out of reach
+  std::vector<std::string> blockers_at;  // per judged instant the Pod::Key() of the first required member that does not succeed, else
+                                         // of the first member that does not; empty: the rule is met
+  std::vector<int64_t> members_at;       // per judged instant the members that succeed, whether or not the rule is met
+};
+
 // ScaleAfter: the first instant at which `want` further pods of a pod's shape fit, and how many fit at each judged instant
 struct ScaleAfterResult {
   bool found = false;            // some instant of the window admits `want` copies: `instant` is the first
@@ -334,6 +344,13 @@ class KubeThrottler {
   // now ++ boundaries.  The members' own RetryAfter answers do not compose into this one.  A dry run; a member named twice, an
   // unknown key, an empty gang and a mirror on several pages answer an error.
   GangRetryAfterResult RetryAfterGang(const std::vector<std::string>& member_keys, const std::string& now_rfc3339, int64_t horizon_seconds);
+  // RetryAfterGang under ElasticGang's rule — the backoff of a job admitted with minMember: at least `min_members` of the members,
+  // walked in order (one that fails reserves nowhere), and every member whose `required` byte is set (empty: none) succeed.  The
+  // boundaries come from kt_override_instants, then ONE kt_forecast_gangs_elastic_launch over now ++ boundaries.  A rule defect
+  // answers an error worded as AdmitElasticGangs words it; a mirror on several pages answers the "pages" error.  Nothing is changed
+  ElasticGangRetryAfterResult RetryAfterElasticGang(const std::vector<std::string>& member_keys, int64_t min_members,
+                                                    const std::vector<uint8_t>& required, const std::string& now_rfc3339,
+                                                    int64_t horizon_seconds);
 
   // When do `want` replicas fit: per instant of now ++ the override boundaries in (now, now + horizon] the number of further pods
   // of pod_key's shape that PreFilter + Reserve would admit one after the other if every throttle were reconciled then (at most
