@@ -629,6 +629,59 @@ int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefi
  *      More than KT_MAX_DIMS resource names: kt_paged_preempt_gangs with KT_PREEMPT_REPRIEVE.  Out of scope: several ranks. -- */
 int32_t kt_preempt_gangs_reprieve_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
                                          const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream);
+/* ---- preempt, for elastic gangs: the shortest victim prefix that lets a gang's QUORUM in — what kt_admit_gangs_elastic_launch is
+ *      to kt_admit_gangs_launch, asked of kt_preempt_gangs_launch.  That call can only say which victims let the WHOLE gang in; for
+ *      an elastic job that evicts too many pods, or is KT_PREEMPT_NONE although one eviction would start the job.
+ *      Notation as for kt_preempt_gangs_launch: counted pods, the candidates c_0 .. c_{m-1}, state S_k, the m_eff cut, exact
+ *      presence from contributor counts; a throttle whose reconcile is an error, or that is not valid and responsible, keeps its
+ *      stored status in every S_k.  Gangs are judged INDEPENDENTLY, each against the stored reserved amounts.  The rule arrays are
+ *      those of kt_admit_gangs_elastic_launch: min_members[g] in [1, size of gang g], member_flags[i] per queue position (NULL: no
+ *      member is required; bit 0 = KT_GANG_MEMBER_REQUIRED).  flags: 0 or KT_PREEMPT_REPRIEVE.  A dry run.
+ *      THE WALK of gang g in a state: the members go in order; each is judged against the state plus what the earlier members that
+ *      SUCCEEDED reserved (Reserve is kt_admit's: the value of every name carried, the presence of all names carried, zero-valued
+ *      ones included, count + 1); a member that fails reserves nowhere; every member is evaluated, also behind one that failed; a
+ *      member whose PreFilter is an Error or whose row is invalid never succeeds; a member is judged on every throttle that affects
+ *      it (there is no list capacity).  The state PASSES iff at least min_members[g] members succeed and every required one does.
+ *      out_prefix[g]: the smallest k in [0, m_eff] whose S_k passes; KT_PREEMPT_NONE if none does, and if the rule is out of reach:
+ *      a required member never succeeds, or size - (members that never succeed) < min_members[g].  The verdict is NOT monotone in k
+ *      (a longer prefix can let an optional member in whose reservation shuts a required one out): every k up to the first pass is
+ *      evaluated, nothing is bisected.
+ *      out_victims[g][j] (nullable, [n_gangs][n_cand]) without the flag: 1 iff j < out_prefix[g], c_j is counted and a throttle that
+ *      affects at least one member of g — succeeding or not; the row of an Error member names no throttle — matches c_j.  Deleting
+ *      exactly the masked pods gives the success list of S_prefix.  All zero for a prefix <= 0.  With KT_PREEMPT_REPRIEVE: V = M,
+ *      and for j = prefix-1 .. 0 over the masked positions c_j is put back (V' = V \ {c_j}) and stays back iff S(V') passes the
+ *      rule — S(V') as kt_preempt_gangs_reprieve_launch defines it, the walk above as the judge, nothing assumed about signs.
+ *      out_members[g] (nullable): the members that succeed in the final state — S_prefix, or S(V) behind the reprieve; S_0 where
+ *      the prefix is KT_PREEMPT_NONE.
+ *      out_blocker[g] (nullable): -1 iff out_prefix[g] == 0; otherwise the queue position of the first required member that does
+ *      not succeed in S_0, and if there is none, of the first member that does not.
+ *      (P1) min_members[g] = size with NULL flags, or every member required: prefix and victims are kt_preempt_gangs_launch's byte
+ *           for byte (with the flag: kt_preempt_gangs_reprieve_launch's), out_members = size wherever the prefix is >= 0, and the
+ *           blocker is equal for gangs whose members are all valid and not Error.
+ *      (P2) a gang of one with min 1: kt_preempt_launch's / kt_preempt_reprieve_launch's prefix and victim row.
+ *      (P3) prefix >= 0, members within kt_admit's list capacity: on a second engine that holds the cluster without the final
+ *           victims, reconciled at `now` with KT_RECONCILE_APPLY, a dry kt_admit_gangs_elastic_launch of the gang returns
+ *           out_members[g].
+ *      Refused before anything is launched, in this order: every gang_off defect; the min_members / member_flags refusals of
+ *      kt_admit_gangs_elastic_launch with the same codes and messages; a flags bit other than KT_PREEMPT_REPRIEVE
+ *      (KT_ERR_INVALID_ARGUMENT); everything kt_preempt_gangs_launch refuses, in its order.  A refused call leaves the check slot,
+ *      the reconcile report and every result buffer alone.  n == 0 is allowed only with n_gangs == 0.
+ *      Slots are those of kt_preempt_gangs_launch; the result is the third kind of the one pending preempt result: the other
+ *      preempt fetches answer KT_ERR_NOT_READY behind this launch and kt_preempt_gangs_elastic_fetch answers the same behind
+ *      theirs; a pending forecast stays fetchable.  The rule arrays travel on the launch's stream and are not referenced after
+ *      return.  kt_preempt_gangs_elastic_fetch synchronises.
+ *      One kt_check launch over pod_rows ++ cand_rows, the aggregate and dry finalize of kt_preempt_launch, and ONE launch of
+ *      kt_preempt_gangs_elastic (csrc/kt_kernels_preempt_gangs_elastic.hip): one wave per gang, the union of the members' throttles
+ *      as a compact state (in LDS, or in a device workspace where it outgrows it) that candidate c_{k-1} moves from S_{k-1} to S_k,
+ *      the members walked in order on it; the reprieve runs in the same kernel.  A candidate that touches no throttle of the union
+ *      costs one ballot.  Out of scope: more than KT_MAX_DIMS resource names, several ranks, elastic headroom. ------------------- */
+int32_t kt_preempt_gangs_elastic_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                        const int64_t* min_members /* [n_gangs] */, const uint8_t* member_flags /* [n], nullable */,
+                                        int64_t n_cand, const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal,
+                                        uint32_t flags, void* stream);
+int32_t kt_preempt_gangs_elastic_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefix /* [n_gangs], nullable */,
+                                       uint8_t* out_victims /* [n_gangs][n_cand], nullable */, int64_t* out_members /* [n_gangs], nullable */,
+                                       int64_t* out_blocker /* [n_gangs], nullable */);
 /* ---- forecast: the first instant at which a blocked pod passes — the one axis no other query looks along.
  *      temporaryThresholdOverrides make every threshold a step function of the clock (throttle_types.go:65-106,
  *      temporary_threshold_override.go:57-70): a pod that PreFilter rejects now may pass when a night-time override begins or a

@@ -15,13 +15,16 @@ static bool getenv_flag(const char* name) {
 }
 static void load_env_switches(kt_engine* e) {
   for (int k = 0; k < kSwCount; ++k) e->sw[k] = getenv_flag(kEnvSwitchName[k]);
-  // the two switches with a value (kt_engine_impl.h, beside the table): a positive entry count, anything else = no limit
+  // the three switches with a value (kt_engine_impl.h, beside the table): a positive entry count, anything else = no limit
   const char* cap = getenv("KT_REPRIEVE_LDS_CAP");
   const long cap_n = cap ? strtol(cap, nullptr, 10) : 0;
   e->reprieve_lds_cap_limit = cap_n > 0 && cap_n <= 0x7FFFFFFFl ? (uint32_t)cap_n : 0u;
   const char* ecap = getenv("KT_FORECAST_ELASTIC_LDS_CAP");
   const long ecap_n = ecap ? strtol(ecap, nullptr, 10) : 0;
   e->forecast_elastic_lds_cap_limit = ecap_n > 0 && ecap_n <= 0x7FFFFFFFl ? (uint32_t)ecap_n : 0u;
+  const char* pcap = getenv("KT_PREEMPT_ELASTIC_LDS_CAP");
+  const long pcap_n = pcap ? strtol(pcap, nullptr, 10) : 0;
+  e->preempt_elastic_lds_cap_limit = pcap_n > 0 && pcap_n <= 0x7FFFFFFFl ? (uint32_t)pcap_n : 0u;
 }
 
 // CheckRecs about to be rewritten IN PLACE: no few-pod check may start on them (recs_valid = false under recs_mu) and
@@ -404,6 +407,7 @@ int32_t kt_engine_destroy(kt_engine* e) {
   e->d_status_fp.release(); e->d_spec_fp.release(); e->d_summary.release(); e->d_rows.release(); e->d_gang_off.release(); e->d_gang_min.release(); e->d_gang_members.release();
   e->d_headroom_copies.release(); e->d_headroom_limiting.release(); e->d_headroom_gang_off.release(); e->d_headroom_blocker.release();
   e->d_preempt_prefix.release(); e->d_preempt_victims.release(); e->d_preempt_partial.release(); e->d_preempt_gang_off.release(); e->d_preempt_blocker.release(); e->d_reprieve_ws.release();
+  e->d_preempt_members.release(); e->d_preempt_min.release(); e->d_preempt_flags.release(); e->d_preempt_elastic_ws.release();
   e->d_forecast_first.release(); e->d_forecast_verdicts.release(); e->d_forecast_inst_s.release(); e->d_forecast_inst_ns.release();
   e->d_forecast_gang_off.release(); e->d_forecast_blocker.release(); e->d_forecast_copies.release(); e->d_forecast_limiting.release();
   e->d_forecast_members.release(); e->d_forecast_min.release(); e->d_forecast_flags.release(); e->d_forecast_elastic_ws.release();

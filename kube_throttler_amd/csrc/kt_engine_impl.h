@@ -219,10 +219,13 @@ extern thread_local std::string g_create_error;  // text of the last kt_engine_c
 // path is tuned to a few microseconds).  Read at the same two moments, with a VALUE instead of a flag and therefore not in the
 // table: KT_REPRIEVE_LDS_CAP (kt_engine::reprieve_lds_cap_limit, a test hook of kt_preempt_reprieve_launch and
 // kt_preempt_gangs_reprieve_launch) and KT_FORECAST_ELASTIC_LDS_CAP (kt_engine::forecast_elastic_lds_cap_limit, the same hook for
-// kt_forecast_gangs_elastic_launch).
+// kt_forecast_gangs_elastic_launch) and KT_PREEMPT_ELASTIC_LDS_CAP (kt_engine::preempt_elastic_lds_cap_limit, the same hook for
+// kt_preempt_gangs_elastic_launch).
 enum EnvSwitch { kSw_FEED_NO_STAGE, kSw_FORCE_NS_ORDER, kSw_INGEST_EVENT_WAIT, kSw_NO_FEED_FEW, kSw_NO_FEED_FUSION, kSw_NO_FUSED, kSw_NO_NS_ORDER, kSw_NO_PACK, kSw_NO_SCAN_VIEW, kSw_NO_SWEEP, kSw_NO_VERDICT_IMAGES, kSw_NO_WG_RANGES, kSw_SYNC_INGEST, kSw_INGEST_TRUST_FENCE, kSw_NO_VIEW_PATCH, kSw_CHECK_ONE_PER_CU, kSw_AGG_SMALL_WINDOW, kSw_AGG_ONE_PER_CU, kSw_NO_MATCH_CACHE, kSw_NO_MATCH_CACHE_AGG, kSw_NO_MATCH_CODES, kSw_NO_MATCH_CODES_AGG, kSw_NO_TILE_PAIRS_CHECK, kSwCount };
 static const char* const kEnvSwitchName[kSwCount] = {"KT_FEED_NO_STAGE", "KT_FORCE_NS_ORDER", "KT_INGEST_EVENT_WAIT", "KT_NO_FEED_FEW", "KT_NO_FEED_FUSION", "KT_NO_FUSED", "KT_NO_NS_ORDER", "KT_NO_PACK", "KT_NO_SCAN_VIEW", "KT_NO_SWEEP", "KT_NO_VERDICT_IMAGES", "KT_NO_WG_RANGES", "KT_SYNC_INGEST", "KT_INGEST_TRUST_FENCE", "KT_NO_VIEW_PATCH", "KT_CHECK_ONE_PER_CU", "KT_AGG_SMALL_WINDOW", "KT_AGG_ONE_PER_CU", "KT_NO_MATCH_CACHE", "KT_NO_MATCH_CACHE_AGG", "KT_NO_MATCH_CODES", "KT_NO_MATCH_CODES_AGG", "KT_NO_TILE_PAIRS_CHECK"};
 // which launch the one pending forecast result belongs to: only that launch's fetch may read it
+// ... and which launch the one pending preempt result belongs to
+enum PreemptKind { kPreemptPods, kPreemptGangs, kPreemptGangsElastic };
 enum ForecastKind { kForecastPods, kForecastGangs, kForecastHeadroom, kForecastHeadroomGangs, kForecastGangsElastic };
 struct kt_engine {
   bool sw[kSwCount] = {};  // EnvSwitch values (load_env_switches)
@@ -230,6 +233,8 @@ struct kt_engine {
                                         // kt_preempt_reprieve stay in LDS, a longer list takes the HBM workspace; 0 = no limit
   uint32_t forecast_elastic_lds_cap_limit = 0;  // KT_FORECAST_ELASTIC_LDS_CAP (test hook, read with the switches): at most so many union
                                                 // entries of kt_forecast_gangs_elastic stay in LDS; 0 = no limit
+  uint32_t preempt_elastic_lds_cap_limit = 0;  // KT_PREEMPT_ELASTIC_LDS_CAP (test hook, read with the switches): at most so many union
+                                               // entries of kt_preempt_gangs_elastic stay in LDS; 0 = no limit
   kt_config cfg{};
   // writers (state feed, launches, fetches) hold it exclusively for the duration of the call; the single-pod PreFilter
   // path (kt_check with n <= 8, summaries only) holds it SHARED: it reads device tables nobody may rewrite meanwhile,
@@ -402,8 +407,14 @@ struct kt_engine {
   hipEvent_t preempt_pages_ev = nullptr;
   // kt_preempt_gangs_launch shares that one pending result (prefix and victim bytes per GANG, preempt_n = the gangs); the kind tag
   // says which fetch may read it.  Its offsets and the blocking member per gang live in buffers of their own
-  bool preempt_gangs = false;
+  PreemptKind preempt_kind = kPreemptPods;
   DevBuf<int64_t> d_preempt_gang_off, d_preempt_blocker;
+  // kt_preempt_gangs_elastic_launch is the third kind (prefix, victim bytes, blocker and offsets in the gang form's buffers): the
+  // members that succeed per gang, the quorum per gang and the flag byte per member as the kernel reads them, and the state of a
+  // union that outgrows LDS (kt::preempt_gangs_elastic_ws_bytes)
+  DevBuf<int64_t> d_preempt_members, d_preempt_min;
+  DevBuf<uint8_t> d_preempt_flags;
+  DevBuf<unsigned char> d_preempt_elastic_ws;
   // the last kt_forecast_launch: first passing position per pod and the verdict bytes [n][n_inst], on the device until
   // kt_forecast_fetch — buffers of their own: a pending forecast and a pending preempt result do not disturb each other;
   // d_forecast_inst_*: the instants as the kernel reads them.  kt_paged_forecast writes the same buffers of page 0 and hands

@@ -482,7 +482,7 @@ static int32_t preempt_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, 
   if ((rc = serves_dry_reconcile(e, what, -1, "kt_preempt")) != KT_OK) return rc;
   e->preempt_ready = false;
   if (n == 0) {  // nothing is launched
-    e->preempt_ready = true, e->preempt_gangs = false, e->preempt_n = 0, e->preempt_m = n_cand;
+    e->preempt_ready = true, e->preempt_kind = kPreemptPods, e->preempt_n = 0, e->preempt_m = n_cand;
     return KT_OK;
   }
   KT_HIP(e, hipSetDevice(e->device));
@@ -506,7 +506,7 @@ static int32_t preempt_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, 
     KT_HIP(e, hipGetLastError());
   }
   e->last_stream = s;
-  e->preempt_ready = true, e->preempt_gangs = false, e->preempt_n = n, e->preempt_m = n_cand;
+  e->preempt_ready = true, e->preempt_kind = kPreemptPods, e->preempt_n = n, e->preempt_m = n_cand;
   return KT_OK;
 }
 
@@ -528,7 +528,7 @@ int32_t kt_preempt_fetch(kt_engine* e, int64_t n, int64_t* out_prefix, uint8_t* 
   if (!e) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
-  if (int32_t bad = fetch_ready(e, e->preempt_ready && !e->preempt_gangs, "preempt", "preempt", false, n, e->preempt_n)) return bad;
+  if (int32_t bad = fetch_ready(e, e->preempt_ready && e->preempt_kind == kPreemptPods, "preempt", "preempt", false, n, e->preempt_n)) return bad;
   if (n == 0) return KT_OK;
   return fetch_out(e, {{out_prefix, e->d_preempt_prefix.p, (size_t)n * 8}, {out_victims, e->d_preempt_victims.p, (size_t)n * (size_t)e->preempt_m}});
 }
@@ -590,11 +590,21 @@ int32_t kt_paged_preempt(kt_engine* const* pages, int32_t n_pages, int64_t n, co
 // ---------------------------------------------------------------------------------------------------
 // kt_preempt_gangs_launch: the refusals of preempt_locked in its order (with the gang defects in front, and "a pod twice" asked
 // per gang), then the same launches with kt_preempt_gangs in kt_preempt's place.  The result shares the one pending preempt result;
-// preempt_gangs tells the fetches apart.  With `reprieve` (kt_preempt_gangs_reprieve_launch): behind them on the same stream the one
+// preempt_kind tells the fetches apart.  With `reprieve` (kt_preempt_gangs_reprieve_launch): behind them on the same stream the one
 // launch of kt_preempt_gangs_reprieve that rewrites the victim bytes in place.  The caller holds the launch lock.
+// `rule` (kt_preempt_gangs_elastic_launch, which has refused the rule's own defects): the quorum per gang and the flag byte per
+// member.  The arrays travel on the launch's stream beside the offsets; the kernel is kt_preempt_gangs_elastic, which walks the
+// victims back itself when `reprieve` is set, and the result is the kind of its own.
+struct ElasticRule {
+  const int64_t* min_members;   // [n_gangs]
+  const uint8_t* member_flags;  // [n], nullable
+};
 static int32_t preempt_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_cand,
-                                    const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream, bool reprieve) {
-  const char *what = "preempt gangs", *kernel = "kt_preempt_gangs";
+                                    const int64_t* cand_rows, int64_t now_s, int32_t now_ns, int32_t on_equal, void* stream, bool reprieve,
+                                    const ElasticRule* rule = nullptr) {
+  const char* what = rule ? "preempt elastic gangs" : "preempt gangs";
+  const char* kernel = rule ? "kt_preempt_gangs_elastic" : "kt_preempt_gangs";
+  const PreemptKind kind = rule ? kPreemptGangsElastic : kPreemptGangs;
   const int32_t T = e->thr_rows_hi;  // (moved by throttle batches only, under this lock: ensure_ready below does not change it)
   int32_t rc;
   if ((rc = gangs_valid(e, n, n_gangs, gang_off)) != KT_OK) return rc;
@@ -605,7 +615,7 @@ static int32_t preempt_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_
   if ((rc = matrix_fits(e, what, T, n, n_cand)) != KT_OK) return rc;
   if ((rc = serves_dry_reconcile(e, what, -1, kernel)) != KT_OK) return rc;
   if (n == 0) {  // (no gangs) nothing is launched
-    e->preempt_ready = true, e->preempt_gangs = true, e->preempt_n = 0, e->preempt_m = n_cand;
+    e->preempt_ready = true, e->preempt_kind = kind, e->preempt_n = 0, e->preempt_m = n_cand;
     return KT_OK;
   }
   KT_HIP(e, hipSetDevice(e->device));
@@ -613,28 +623,41 @@ static int32_t preempt_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_
   if ((rc = ensure_ready(e, s)) != KT_OK || (rc = sums_fit_int64(e, what, -1, kernel, s)) != KT_OK) return rc;
   const size_t ng = (size_t)n_gangs, vic = ng * (size_t)n_cand;
   // the reprieve kernel's list state where it can outgrow LDS (0 bytes: it cannot, or nothing is walked)
-  const size_t ws = reprieve && n_cand > 0 ? kt::reprieve_ws_bytes(T, e->D, n_gangs, e->reprieve_lds_cap_limit) : 0;
-  if ((rc = reserve_behind_last_stream(e, {{e->d_preempt_prefix, ng}, {e->d_preempt_victims, vic + 1}, {e->d_preempt_blocker, ng}, {e->d_preempt_gang_off, ng + 1}, {e->d_reprieve_ws, ws}})) != KT_OK)
+  const size_t ws = rule ? 0 : reprieve && n_cand > 0 ? kt::reprieve_ws_bytes(T, e->D, n_gangs, e->reprieve_lds_cap_limit) : 0;
+  // ... and the elastic kernel's state of a union (it builds it for every gang, whatever the list holds)
+  const size_t ews = rule ? kt::preempt_gangs_elastic_ws_bytes(T, e->D, n_gangs, e->preempt_elastic_lds_cap_limit) : 0;
+  const bool flagged = rule && rule->member_flags;
+  if ((rc = reserve_behind_last_stream(e, {{e->d_preempt_prefix, ng}, {e->d_preempt_victims, vic + 1}, {e->d_preempt_blocker, ng}, {e->d_preempt_gang_off, ng + 1}, {e->d_reprieve_ws, ws},
+                                           {e->d_preempt_members, rule ? ng : 0}, {e->d_preempt_min, rule ? ng : 0}, {e->d_preempt_flags, flagged ? (size_t)n : 0}, {e->d_preempt_elastic_ws, ews}})) != KT_OK)
     return rc;
   // the offsets travel on the launch's stream, behind an earlier launch's kernel; the caller's memory is not referenced after return
   KT_HIP(e, hipMemcpyAsync(e->d_preempt_gang_off.p, gang_off, (ng + 1) * 8, hipMemcpyHostToDevice, s));
+  if (rule) KT_HIP(e, hipMemcpyAsync(e->d_preempt_min.p, rule->min_members, ng * 8, hipMemcpyHostToDevice, s));
+  if (flagged) KT_HIP(e, hipMemcpyAsync(e->d_preempt_flags.p, rule->member_flags, (size_t)n, hipMemcpyHostToDevice, s));
   KT_HIP(e, hipStreamSynchronize(s));
   const std::vector<int64_t> rows = joined_rows(n, pod_rows, n_cand, cand_rows);
   if ((rc = query_check(e, n + n_cand, rows.data(), on_equal, s, &kt_engine::forecast_ready)) != KT_OK) return rc;
   if ((rc = preempt_reconcile_locked(e, now_s, now_ns, s)) != KT_OK) return rc;
   const kt::AdmitPage pg = admit_page_of(e);
-  kt::launch_preempt_gangs(pg, n, n_cand, e->d_rows.p, n_gangs, e->d_preempt_gang_off.p, e->thr_rows_hi, on_equal != 0, e->d_status.p, e->d_summary.p,
-                           e->d_preempt_partial.p, e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p,
-                           e->d_preempt_victims.p, e->d_preempt_blocker.p, s);
+  if (rule)
+    kt::launch_preempt_gangs_elastic(pg, n, n_cand, e->d_rows.p, n_gangs, e->d_preempt_gang_off.p, e->d_preempt_min.p,
+                                     flagged ? e->d_preempt_flags.p : nullptr, e->thr_rows_hi, on_equal != 0, reprieve, e->d_status.p, e->d_summary.p,
+                                     e->d_preempt_partial.p, e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p,
+                                     e->d_preempt_victims.p, e->d_preempt_members.p, e->d_preempt_blocker.p,
+                                     ews != 0 ? e->d_preempt_elastic_ws.p : nullptr, e->preempt_elastic_lds_cap_limit, s);
+  else
+    kt::launch_preempt_gangs(pg, n, n_cand, e->d_rows.p, n_gangs, e->d_preempt_gang_off.p, e->thr_rows_hi, on_equal != 0, e->d_status.p, e->d_summary.p,
+                             e->d_preempt_partial.p, e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p,
+                             e->d_preempt_victims.p, e->d_preempt_blocker.p, s);
   KT_HIP(e, hipGetLastError());
-  if (reprieve) {
+  if (reprieve && !rule) {
     kt::launch_preempt_gangs_reprieve(pg, n, n_cand, e->d_rows.p, n_gangs, e->d_preempt_gang_off.p, e->thr_rows_hi, on_equal != 0, e->d_status.p,
                                       e->d_preempt_partial.p, e->d_out_calc.tab(), e->d_out_calc_updated.p, e->d_out_error.p, e->d_preempt_prefix.p,
                                       e->d_preempt_victims.p, ws != 0 ? e->d_reprieve_ws.p : nullptr, e->reprieve_lds_cap_limit, s);
     KT_HIP(e, hipGetLastError());
   }
   e->last_stream = s;
-  e->preempt_ready = true, e->preempt_gangs = true, e->preempt_n = n_gangs, e->preempt_m = n_cand;
+  e->preempt_ready = true, e->preempt_kind = kind, e->preempt_n = n_gangs, e->preempt_m = n_cand;
   return KT_OK;
 }
 
@@ -656,10 +679,42 @@ int32_t kt_preempt_gangs_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefi
   if (!e) return KT_ERR_INVALID_ARGUMENT;
   LaunchLock lk(e);
   KT_HIP(e, hipSetDevice(e->device));
-  if (int32_t bad = fetch_ready(e, e->preempt_ready && e->preempt_gangs, "preempt_gangs", "preempt gangs", true, n_gangs, e->preempt_n)) return bad;
+  if (int32_t bad = fetch_ready(e, e->preempt_ready && e->preempt_kind == kPreemptGangs, "preempt_gangs", "preempt gangs", true, n_gangs, e->preempt_n)) return bad;
   if (n_gangs == 0) return KT_OK;
   const size_t ng = (size_t)n_gangs;
   return fetch_out(e, {{out_prefix, e->d_preempt_prefix.p, ng * 8}, {out_victims, e->d_preempt_victims.p, ng * (size_t)e->preempt_m}, {out_blocker, e->d_preempt_blocker.p, ng * 8}});
+}
+
+// ---------------------------------------------------------------------------------------------------
+// preempt, for elastic gangs: the shortest victim prefix that lets a gang's quorum in (kt_kernels_preempt_gangs_elastic.hip)
+// ---------------------------------------------------------------------------------------------------
+// The refusals: every gang_off defect, the rule's (elastic_valid, worded as kt_admit_gangs_elastic_launch words them), a flag bit
+// other than KT_PREEMPT_REPRIEVE, then everything preempt_gangs_locked refuses in its order.
+int32_t kt_preempt_gangs_elastic_launch(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off,
+                                        const int64_t* min_members, const uint8_t* member_flags, int64_t n_cand, const int64_t* cand_rows,
+                                        int64_t now_s, int32_t now_ns, int32_t on_equal, uint32_t flags, void* stream) {
+  if (!e || n < 0 || n_gangs < 0) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  int32_t rc = gangs_valid(e, n, n_gangs, gang_off);
+  if (rc == KT_OK) rc = elastic_valid(e, n, n_gangs, gang_off, min_members, member_flags);
+  if (rc != KT_OK) return rc;
+  if (flags & ~KT_PREEMPT_REPRIEVE) return e->fail(KT_ERR_INVALID_ARGUMENT, "preempt elastic gangs: flags = 0x%x", flags);
+  const ElasticRule rule{min_members, member_flags};
+  return preempt_gangs_locked(e, n, pod_rows, n_gangs, gang_off, n_cand, cand_rows, now_s, now_ns, on_equal, stream,
+                              (flags & KT_PREEMPT_REPRIEVE) != 0, &rule);
+}
+
+int32_t kt_preempt_gangs_elastic_fetch(kt_engine* e, int64_t n_gangs, int64_t* out_prefix, uint8_t* out_victims, int64_t* out_members,
+                                       int64_t* out_blocker) {
+  if (!e) return KT_ERR_INVALID_ARGUMENT;
+  LaunchLock lk(e);
+  KT_HIP(e, hipSetDevice(e->device));
+  if (int32_t bad = fetch_ready(e, e->preempt_ready && e->preempt_kind == kPreemptGangsElastic, "preempt_gangs_elastic", "preempt elastic gangs", true,
+                                n_gangs, e->preempt_n))
+    return bad;
+  if (n_gangs == 0) return KT_OK;
+  const size_t ng = (size_t)n_gangs;
+  return fetch_out(e, {{out_prefix, e->d_preempt_prefix.p, ng * 8}, {out_victims, e->d_preempt_victims.p, ng * (size_t)e->preempt_m}, {out_members, e->d_preempt_members.p, ng * 8}, {out_blocker, e->d_preempt_blocker.p, ng * 8}});
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -853,10 +908,6 @@ int32_t kt_headroom_forecast_fetch(kt_engine* e, int64_t n, int64_t* out_first, 
 // `rule` (kt_forecast_gangs_elastic_launch): the quorum per gang and the flag byte per member.  Its refusals come behind the gang
 // defects (they read the sizes) and before the rest; the arrays travel on the launch's stream beside the offsets; the kernel is
 // kt_forecast_gangs_elastic with the small launch for `first` behind it, and the result is the kind of its own.
-struct ElasticRule {
-  const int64_t* min_members;   // [n_gangs]
-  const uint8_t* member_flags;  // [n], nullable
-};
 static int32_t forecast_gangs_locked(kt_engine* e, int64_t n, const int64_t* pod_rows, int64_t n_gangs, const int64_t* gang_off, int64_t n_inst,
                                      const int64_t* inst_s, const int32_t* inst_ns, int32_t on_equal, void* stream,
                                      const ElasticRule* rule = nullptr) {

@@ -159,6 +159,20 @@ void launch_preempt_gangs_reprieve(const AdmitPage& pg, int64_t n, int64_t m, co
                                    int T, bool on_equal, const uint8_t* status, const unsigned long long* partial, const AmountTab& calc,
                                    const uint8_t* calc_updated, const uint8_t* error, const int64_t* prefix, uint8_t* victims, void* ws,
                                    uint32_t lds_cap_limit, hipStream_t s);
+// the shortest victim prefix that lets a gang's QUORUM in (kt_kernels_preempt_gangs_elastic.hip): one wave per gang, the members
+// walked in order in every S_k, a failed member reserving nowhere.  launch_preempt_gangs' inputs plus min_dev [n_gangs] and flags_dev
+// [n] (nullable: no member is required; bit 0 = required); `reprieve`: the masked victims are walked back in the same kernel.
+// prefix, members (the successes in the final state) and blocker [n_gangs] and victims [n_gangs][m] out.  A gang's union of
+// affecting throttles lives in LDS up to preempt_gangs_elastic_lds_cap(D, limit) entries (limit: a test hook that lowers the
+// capacity, 0 = none), beyond that in `ws`: preempt_gangs_elastic_ws_bytes bytes of device memory (0: no union can outgrow LDS, ws
+// may be null)
+uint32_t preempt_gangs_elastic_lds_cap(int D, uint32_t limit);
+size_t preempt_gangs_elastic_ws_bytes(int T, int D, int64_t n_gangs, uint32_t lds_cap_limit);
+void launch_preempt_gangs_elastic(const AdmitPage& pg, int64_t n, int64_t m, const int64_t* rows_dev, int64_t n_gangs, const int64_t* gang_off_dev,
+                                  const int64_t* min_dev, const uint8_t* flags_dev, int T, bool on_equal, bool reprieve, const uint8_t* status,
+                                  const uint64_t* summary, const unsigned long long* partial, const AmountTab& calc, const uint8_t* calc_updated,
+                                  const uint8_t* error, int64_t* prefix, uint8_t* victims, int64_t* members, int64_t* blocker, void* ws,
+                                  uint32_t lds_cap_limit, hipStream_t s);
 // the victim prefix and its reprieve pass over n_pages >= 1 pages (kt_kernels_preempt_paged.hip).  One descriptor per page: the
 // page as kt_admit reads it (the state offsets are unused), and of that page's own dense aggregate and dry finalize at `now` the
 // partial rows with exact contributor counts, the calculated threshold and the calc_updated / error bytes.  launch_preempt_paged

@@ -46,6 +46,7 @@ EXPORTS = [
     "kt_headroom_launch", "kt_headroom_fetch", "kt_paged_headroom", "kt_preempt_launch", "kt_preempt_fetch",
     "kt_preempt_reprieve_launch", "kt_preempt_gangs_launch", "kt_preempt_gangs_reprieve_launch", "kt_preempt_gangs_fetch", "kt_forecast_launch", "kt_forecast_fetch", "kt_forecast_gangs_launch", "kt_forecast_gangs_fetch", "kt_override_instants",
     "kt_forecast_gangs_elastic_launch", "kt_forecast_gangs_elastic_fetch",
+    "kt_preempt_gangs_elastic_launch", "kt_preempt_gangs_elastic_fetch",
     "kt_paged_preempt", "kt_paged_forecast", "kt_debug_match_planes", "kt_debug_match_codes", "kt_debug_match_runs", "kt_paged_preempt_gangs",
     "kt_paged_forecast_gangs", "kt_headroom_gangs_launch", "kt_headroom_gangs_fetch", "kt_paged_headroom_gangs",
     "kt_headroom_forecast_launch", "kt_headroom_forecast_fetch", "kt_paged_headroom_forecast",
@@ -512,6 +513,9 @@ def lib():
                                               C.c_int32, C.c_int32, C.c_void_p]
         L.kt_preempt_gangs_reprieve_launch.argtypes = L.kt_preempt_gangs_launch.argtypes
         L.kt_preempt_gangs_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kt_preempt_gangs_elastic_launch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]
+        L.kt_preempt_gangs_elastic_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kt_paged_forecast.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p]
         L.kt_paged_forecast_gangs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -1054,6 +1058,40 @@ class Engine:
         same, the victim bytes are a minimal set."""
         (self.preempt_gangs_reprieve_launch if reprieve else self.preempt_gangs_launch)(pod_rows, gang_off, cand_rows, now, on_equal)
         return self.preempt_gangs_fetch(len(_gang_offsets(gang_off)) - 1, len(cand_rows), want_victims)
+
+    # ---- preempt, for elastic gangs: the shortest victim prefix that lets a gang's quorum in
+    def preempt_gangs_elastic_launch(self, pod_rows, gang_off, min_members, cand_rows, now, required=None, on_equal=False, reprieve=False,
+                                     stream=None):
+        a, p = self._rows(pod_rows, np.int64)
+        c, q = self._rows(cand_rows, np.int64)
+        g = _gang_offsets(gang_off)
+        n, ng = len(a), len(g) - 1
+        mm, rq = _elastic_rule(min_members, required, n, ng)
+        self._ck(lib().kt_preempt_gangs_elastic_launch(self._h, n, p if n else None, ng, g.ctypes.data, mm.ctypes.data if ng else None,
+                                                       None if rq is None or not n else rq.ctypes.data, len(c), q if len(c) else None,
+                                                       int(now[0]), int(now[1]), int(on_equal), PREEMPT_REPRIEVE if reprieve else 0, stream))
+
+    def preempt_gangs_elastic_fetch(self, n_gangs, n_cand, want_victims=True):
+        prefix, members, blocker = (np.zeros(max(n_gangs, 1), np.int64) for _ in range(3))
+        flat = np.zeros(max(n_gangs * n_cand, 1), np.uint8) if want_victims else None
+        self._ck(lib().kt_preempt_gangs_elastic_fetch(self._h, n_gangs, prefix.ctypes.data, None if flat is None else flat.ctypes.data,
+                                                      members.ctypes.data, blocker.ctypes.data))
+        return (prefix[:n_gangs], (None if flat is None else flat[:n_gangs * n_cand].reshape(n_gangs, n_cand)), members[:n_gangs],
+                blocker[:n_gangs])
+
+    def preempt_gangs_elastic(self, pod_rows, gang_off, min_members, cand_rows, now, required=None, on_equal=False, reprieve=False,
+                              want_victims=True):
+        """kt_preempt_gangs_elastic_launch + kt_preempt_gangs_elastic_fetch: per gang ``pod_rows[gang_off[g]:gang_off[g + 1]]`` the
+        smallest k for which an in-order walk of its members — a member that succeeds reserves against the throttles the later
+        ones meet, one that fails reserves nowhere — has at least ``min_members[g]`` successes and every ``required`` member (bool,
+        or flag bytes with GANG_MEMBER_REQUIRED, per queue position; None: none) among them, once the candidates ``cand_rows[:k]``
+        are gone and every throttle has been reconciled at ``now`` (PREEMPT_NONE: no prefix does, or members that never succeed put
+        the rule out of reach) -> (prefix int64 [n_gangs]; victims uint8 [n_gangs][n_cand] or None; members int64 [n_gangs]: how
+        many succeed in the final state, in S_0 where there is no prefix; blocker int64 [n_gangs]: the first required member that
+        does not succeed with nothing deleted, else the first member that does not, -1 where the prefix is 0).  ``reprieve``: the
+        victims are walked back, last first, and each stays back as long as the rule still holds.  A dry run."""
+        self.preempt_gangs_elastic_launch(pod_rows, gang_off, min_members, cand_rows, now, required, on_equal, reprieve)
+        return self.preempt_gangs_elastic_fetch(len(_gang_offsets(gang_off)) - 1, len(cand_rows), want_victims)
 
     # ---- forecast: the first instant at which a blocked pod passes
     def forecast_launch(self, pod_rows, instants, on_equal=False, stream=None):

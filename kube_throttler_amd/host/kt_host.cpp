@@ -1390,6 +1390,69 @@ GangPreemptResult KubeThrottler::PreemptGang(const std::vector<std::string>& mem
   return res;
 }
 
+// Which of the candidates have to go before the gang's quorum is in: PreemptGang with ElasticGang's rule — one
+// kt_preempt_gangs_elastic_launch + kt_preempt_gangs_elastic_fetch with the members as ONE gang on the mirror's one engine
+// (isThrottledOnEqual = false, as PreFilter).  Nothing is changed.
+ElasticGangPreemptResult KubeThrottler::PreemptElasticGang(const std::vector<std::string>& member_keys, int64_t min_members,
+                                                           const std::vector<uint8_t>& required, const std::vector<std::string>& candidate_keys,
+                                                           const std::string& now_rfc3339, bool reprieve) {
+  std::lock_guard<std::recursive_mutex> lk(p_->mu);
+  auto& p = *p_;
+  ElasticGangPreemptResult res;
+  PreemptResult& out = res.preempt;
+  if (p.pages.size() > 1) {
+    out.error = "PreemptElasticGang: the mirror runs on " + std::to_string(p.pages.size()) + " pages (more than " + std::to_string(p.D) +
+                " resource names); the preemption query has no paged form";
+    return res;
+  }
+  int64_t now_s;
+  int32_t now_ns;
+  if (!ParseRFC3339(now_rfc3339, &now_s, &now_ns, &out.error)) return res;
+  const size_t size = member_keys.size();
+  if (size == 0) {
+    out.error = "PreemptElasticGang: a gang without members";
+    return res;
+  }
+  if (min_members < 1 || min_members > (int64_t)size) {  // (worded as AdmitElasticGangs words it)
+    out.error = "PreemptElasticGang: gang 0 asks for " + std::to_string(min_members) + " of its " + std::to_string(size) + " members";
+    return res;
+  }
+  if (!required.empty() && required.size() != size) {
+    out.error = "PreemptElasticGang: gang 0 has " + std::to_string(size) + " members and " + std::to_string(required.size()) + " required flags";
+    return res;
+  }
+  std::vector<int64_t> rows(size), cand(candidate_keys.size());
+  for (size_t i = 0; i < size; ++i)
+    if ((rows[i] = p.pod_rows.find(member_keys[i])) < 0) {
+      out.error = "pod " + member_keys[i] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+  for (size_t j = 0; j < cand.size(); ++j)
+    if ((cand[j] = p.pod_rows.find(candidate_keys[j])) < 0) {
+      out.error = "candidate " + candidate_keys[j] + " is not known to the plugin (OnPodAdd first)";
+      return res;
+    }
+  std::vector<uint8_t> flags;
+  for (size_t i = 0; i < required.size(); ++i) flags.push_back(required[i] ? KT_GANG_MEMBER_REQUIRED : 0);
+  const int64_t gang_off[2] = {0, (int64_t)size};
+  int64_t prefix = KT_PREEMPT_NONE, blocker = -1;
+  std::vector<uint8_t> mask(cand.size() + 1);
+  int32_t rc = kt_preempt_gangs_elastic_launch(p.e, (int64_t)size, rows.data(), 1, gang_off, &min_members, flags.empty() ? nullptr : flags.data(),
+                                               (int64_t)cand.size(), cand.data(), now_s, now_ns, /*isThrottledOnEqual=*/0,
+                                               reprieve ? KT_PREEMPT_REPRIEVE : 0u, nullptr);
+  if (rc == KT_OK) rc = kt_preempt_gangs_elastic_fetch(p.e, 1, &prefix, mask.data(), &res.members, &blocker);
+  if (rc != KT_OK) {
+    out.error = p.engine_error(rc);
+    res.members = 0;
+    return res;
+  }
+  out.none = prefix < 0;
+  for (size_t j = 0; j < cand.size(); ++j)
+    if (mask[j]) out.victims.push_back(candidate_keys[j]);
+  if (blocker >= 0 && (size_t)blocker < size) res.blocker = member_keys[(size_t)blocker];
+  return res;
+}
+
 // has / instantSec / instantNsec / instant of a RetryAfterResult from the first passing position (KT_FORECAST_NONE: none)
 static void retry_after_first(RetryAfterResult& out, int64_t first, const std::vector<int64_t>& inst_s, const std::vector<int32_t>& inst_ns) {
   out.has = first >= 0;

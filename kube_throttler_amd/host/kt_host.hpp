@@ -193,6 +193,16 @@ struct GangPreemptResult {
   std::string blocker;    // Pod::Key() of the first member that is not admitted with nothing deleted; empty: the gang already passes
 };
 
+// PreemptElasticGang: the pods that would have to go before a gang's QUORUM is in (ElasticGang's rule), who stops it as things
+// stand and how many members are in once the victims are gone
+struct ElasticGangPreemptResult {
+  PreemptResult preempt;  // none / victims / error as for Preempt, for the gang under its rule (none also where members that never
+                          // succeed put the rule out of reach)
+  std::string blocker;    // Pod::Key() of the first required member that does not succeed with nothing deleted, else of the first
+                          // member that does not; empty: the rule is met as things stand
+  int64_t members = 0;    // the members that succeed once the victims are gone; with nothing deleted where `none` is set
+};
+
 // RetryAfter: the first instant at which a blocked pod passes PreFilter, among `now` and the override boundaries up to the horizon
 struct RetryAfterResult {
   bool has = false;              // some instant of the window lets the pod through: `instant` is the first
@@ -344,6 +354,13 @@ class KubeThrottler {
   // now ++ boundaries.  The members' own RetryAfter answers do not compose into this one.  A dry run; a member named twice, an
   // unknown key, an empty gang and a mirror on several pages answer an error.
   GangRetryAfterResult RetryAfterGang(const std::vector<std::string>& member_keys, const std::string& now_rfc3339, int64_t horizon_seconds);
+  // PreemptGang under ElasticGang's rule — the eviction set of a job admitted with minMember: at least `min_members` of the
+  // members, and every member whose `required` byte is set (empty: none), have to succeed; the shortest prefix of the candidates
+  // that achieves it, with `reprieve` shrunk to a minimal set.  A quorum outside 1 .. size or a `required` of another length answers
+  // an error worded as AdmitElasticGangs words it; a mirror on several pages answers the "pages" error.  Nothing is changed
+  ElasticGangPreemptResult PreemptElasticGang(const std::vector<std::string>& member_keys, int64_t min_members,
+                                              const std::vector<uint8_t>& required, const std::vector<std::string>& candidate_keys,
+                                              const std::string& now_rfc3339, bool reprieve = false);
   // RetryAfterGang under ElasticGang's rule — the backoff of a job admitted with minMember: at least `min_members` of the members,
   // walked in order (one that fails reserves nowhere), and every member whose `required` byte is set (empty: none) succeed.  The
   // boundaries come from kt_override_instants, then ONE kt_forecast_gangs_elastic_launch over now ++ boundaries.  A rule defect

@@ -762,6 +762,115 @@ def preempt_gangs_of(snap, member_rows, cand_rows, now, on_equal=False, ctx=None
     return prefix, victims, (-1 if prefix == 0 or block0 >= g else block0)
 
 
+# ---- preempt, for elastic gangs (kt_preempt_gangs_elastic_launch): member-major, on the sums of ``preempt_context`` ----
+def preempt_gangs_elastic_of(snap, member_rows, min_members, required, cand_rows, now, on_equal=False, ctx=None, reprieve=False):
+    """kt_preempt_gangs_elastic_launch for one gang on a Snapshot (no GPU) -> (prefix, victims [len(cand_rows)], members, blocker).
+    In every state the members are walked in order: a member that succeeds reserves on every throttle that affects it, one that
+    fails reserves nowhere, every member is evaluated, one whose PreFilter is an Error or whose row is invalid never succeeds; the
+    state passes iff at least ``min_members`` members succeed and every ``required`` one (bools per member, None: none) does.
+    prefix: the smallest k whose S_k passes (-1: none, or members that never succeed put the rule out of reach) — every k up to it
+    is walked, the verdict is not monotone in k.  victims[j] = 1 iff j < prefix, the candidate is counted and a throttle that
+    affects some member matches it.  members: the successes in the final state (S_0 where there is no prefix).  blocker: -1 iff
+    prefix == 0, else the position in ``member_rows`` of the first required member that does not succeed in S_0, else of the first
+    member that does not.  The state per throttle of the union is what ``preempt_gangs_of`` forms — `used` lowered candidate by
+    candidate, exact presence — but the reservations are formed member by member, across throttles.
+    ``reprieve`` (KT_PREEMPT_REPRIEVE): the masked victims are put back one by one, the last first, and each stays back iff the
+    state still passes; victims and members are what remains."""
+    ctx = preempt_context(snap, now) if ctx is None else ctx
+    members, cands, eq = [int(p) for p in member_rows], [int(c) for c in cand_rows], bool(on_equal)
+    m, g, quorum = len(cands), len(members), int(min_members)
+    required = [bool(x) for x in required] if required is not None else [False] * g
+    affected, never = [], []
+    for p in members:
+        valid = 0 <= p < snap.n_pods and bool(int(snap.pod_flags[p]) & S.POD_VALID)
+        err, rows = affected_throttles(snap, p) if valid else (True, [])
+        never.append(err or not valid)
+        affected.append(rows)
+    m_eff = m
+    for j, c in enumerate(cands):
+        if not (0 <= c < snap.n_pods) or not int(snap.pod_flags[c]) & S.POD_VALID or affected_throttles(snap, c)[0]:
+            m_eff = j
+            break
+    counted = lambda c: (int(snap.pod_flags[c]) & (_COUNTABLE | S.POD_FINISHED)) == _COUNTABLE
+    reqs = [pod_requests(snap, p) if 0 <= p < snap.n_pods else {} for p in members]
+    creq = [pod_requests(snap, c) if counted(c) else {} for c in cands[:m_eff]]
+    union = sorted(set().union(*affected)) if affected else []
+    hits = [[t for t in union if counted(c) and t in ctx["match"].get(c, ())] for c in cands[:m_eff]]
+    # the state: per reconciled throttle of the union [values, contributor counts, counted pods]; an error throttle keeps its stored status
+    state = {t: [dict(ctx["thr"][t]["val"]), dict(ctx["thr"][t]["cnt"]), ctx["thr"][t]["pods"]] for t in union if not ctx["thr"][t]["error"]}
+
+    def move(j, sign):
+        for t in hits[j]:
+            if t in state:
+                val, cnt, _ = state[t]
+                state[t][2] += sign
+                for d, v in creq[j].items():
+                    val[d] = val.get(d, 0) + sign * v
+                    cnt[d] = cnt.get(d, 0) + sign
+
+    def walk():
+        res = {t: list(_amount_dict(snap.thr_reserved, t, snap.D)) for t in union}  # the stored rows: [{name: value}, count or None]
+        ok = []
+        for j in range(g):
+            bad = never[j]
+            for t in ([] if bad else affected[j]):
+                th, f = ctx["thr"][t], int(snap.thr_flags[t])
+                eq3 = eq if f & S.THR_CLUSTER else True
+                rv, rc = res[t]
+                if t in state:
+                    val, cnt, pods = state[t]
+                    cc = th["calc_count"]
+                    bad = bad or _amount_fails(1, th["th_count"], cc is not None and pods > 0 and pods >= cc, pods > 0, pods, rc is not None, rc or 0, eq3, eq)
+                    for d, v in reqs[j].items():
+                        u_pr, cv = cnt.get(d, 0) > 0, th["calc"].get(d)
+                        bad = bad or (v != 0 and _amount_fails(v, th["th"].get(d), cv is not None and u_pr and val.get(d, 0) >= cv, u_pr, val.get(d, 0),
+                                                               d in rv, rv.get(d, 0), eq3, eq))
+                else:
+                    used, used_count = _amount_dict(snap.thr_used, t, snap.D)
+                    sth, sth_count = _amount_dict(snap.thr_calc if f & S.THR_CALC_AT_NONZERO else snap.thr_spec, t, snap.D)
+                    flg = int(snap.thr_thrl_flag[t]) & int(snap.thr_thrl_has[t])
+                    bad = bad or _amount_fails(1, sth_count, bool(f & S.THR_THROTTLED_POD), used_count is not None, used_count or 0, rc is not None,
+                                               rc or 0, eq3, eq)
+                    for d, v in reqs[j].items():
+                        bad = bad or (v != 0 and _amount_fails(v, sth.get(d), bool(flg >> d & 1), d in used, used.get(d, 0), d in rv, rv.get(d, 0), eq3, eq))
+            ok.append(not bad)
+            if not bad:  # Reserve: every name the pod carries becomes present, zero-valued ones included; count + 1
+                for t in affected[j]:
+                    for d, v in reqs[j].items():
+                        res[t][0][d] = res[t][0].get(d, 0) + v
+                    res[t][1] = (res[t][1] or 0) + 1
+        return ok
+
+    out_of_reach = any(n and r for n, r in zip(never, required)) or g - sum(never) < quorum
+    passes = lambda ok: not out_of_reach and sum(ok) >= quorum and not any(r and not o for r, o in zip(required, ok))
+    ok0 = ok = walk()
+    prefix = 0 if passes(ok) else -1
+    k = 0
+    while prefix < 0 and not out_of_reach and k < m_eff:
+        k += 1
+        if hits[k - 1]:  # (a candidate that touches no throttle of the union: the verdict of k - 1 stands)
+            move(k - 1, -1)
+            ok = walk()
+            if passes(ok):
+                prefix = k
+    failed = [j for j in range(g) if not ok0[j]]
+    blocker = -1 if prefix == 0 else next((j for j in failed if required[j]), failed[0])
+    victims = [int(j < prefix and bool(hits[j])) for j in range(m)]
+    if prefix < 0:
+        return prefix, victims, sum(ok0), blocker
+    if reprieve:
+        for j in range(prefix - 1, -1, -1):
+            if not victims[j]:
+                continue
+            move(j, 1)
+            back = walk()
+            if passes(back):
+                victims[j], ok = 0, back
+            else:
+                move(j, -1)
+    return prefix, victims, sum(ok), blocker
+
+
 # ---- preempt, for gangs, over pages (kt_paged_preempt_gangs): the closed form over a list of page snapshots ----
 def paged_preempt_gangs_of(snaps, member_rows, cand_rows, now, on_equal=False, reprieve=False, ctx=None):
     """kt_paged_preempt_gangs for one gang, in closed form over the page snapshots (no GPU) -> (prefix, victims [len(cand_rows)],
